@@ -6,11 +6,19 @@
 
 One "step" = one full pipeline call on one batch: VAE encode of the masked image, 30 denoising steps of the 12 B-param
 DiT (hand-written HIP: MFMA GEMMs, flash attention, fused norms / scheduler), VAE decode.  Inputs are resident in HBM
-before the timed region.  Rank 0 prints ONE JSON line (contract in the task description), carrying
-  roofline     : MFMA roofline of the dominant kernel (gemm8p), measured live with HIP events on its launch stream
-  cpu_baseline : the CPU oracle (plain PyTorch restatement, `oracle/`) timed LIVE on this box's host cores: BASELINE config 1 in full
-                 (576x512, 4 steps, fp32, 57 blocks: ~2 min in a subprocess that overlaps model init / warm-up and ends before the timed
-                 region) + a bounded block sample at the GPU workload's own token count
+before the timed region.  Rank 0 prints ONE JSON line (contract in the task description).  A plain run does only what the
+headline needs: set-up, W warm-up calls, K timed calls, the result line.
+
+    --dump-outputs DIR : after the timed calls, the images the last timed call returned, as float32 / float64 .npy files under DIR
+                         (a fixed, seeded sample of them when the whole batch would not fit in 48 MiB); inputs are seeded, so two
+                         builds can be compared output for output
+    --full             : also the untimed extras, each its own measurement, added to the same line:
+      roofline     : MFMA roofline of the dominant kernel (gemm8p), measured live with HIP events on its launch stream, the attention
+                     kernel forms of one eager call, one call with the attention score bound ignored, the pil-vs-pt output delta and
+                     the live MFMA-only peak probe
+      cpu_baseline : the CPU oracle (plain PyTorch restatement, `oracle/`) timed LIVE on this box's host cores: BASELINE config 1 in full
+                     (576x512, 4 steps, fp32, 57 blocks: ~2 min in a subprocess that overlaps model init / warm-up and ends before the
+                     timed region) + a bounded block sample at the GPU workload's own token count
 """
 import argparse
 import json
@@ -33,6 +41,17 @@ def dit_flops(S: int) -> float:
     return 57 * (24 * D * D * N + 4 * N * N * D) + 2 * (384 * D * S + 4096 * D * T_TXT + 64 * D * S)
 
 
+def _cpu_budget() -> int:
+    """Host CPUs this process may use: its affinity mask, capped by OMP_NUM_THREADS when that is set (on a shared host both can be
+    far below os.cpu_count(), and a thread pool sized by the machine's count only slows itself down)."""
+    n = len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else (os.cpu_count() or 1)
+    try:
+        n = min(n, int(os.environ.get("OMP_NUM_THREADS", n)))
+    except ValueError:
+        pass
+    return max(1, n)
+
+
 def cpu_baseline(height, width, steps, budget_s=25.0):
     """Oracle double + single block (full width, fp32) at this workload's token count, timed on the host cores and
     extrapolated: s/img = steps * (19 t_double + 38 t_single).  A reported baseline, not a target."""
@@ -41,7 +60,7 @@ def cpu_baseline(height, width, steps, budget_s=25.0):
     S = (height // 16) * (width // 16)
     # pick the thread count that is actually fastest on this box for the dominant op shape (oversubscribing every
     # logical CPU is several times slower than ~1 thread per physical core on large hosts); ~2 s of calibration
-    ncpu = os.cpu_count() or 1
+    ncpu = _cpu_budget()
     xa, wa = torch.randn(S + T_TXT, D), torch.randn(4 * D, D)
     best_t, best_n = float("inf"), ncpu
     for nthr in sorted({ncpu, max(1, ncpu // 2), max(1, ncpu // 4), min(ncpu, 64), min(ncpu, 32)}, reverse=True):
@@ -87,7 +106,7 @@ def cpu_baseline(height, width, steps, budget_s=25.0):
     s_img = steps * (19 * t_d + 38 * t_s)
     return {"value": 1.0 / s_img, "unit": "images/sec", "cores": best_n, "kind": "port",
             "sample": f"oracle/flux_oracle.py fp32: {len(td)} double-block ({t_d:.2f} s mean) + {len(ts)} single-block ({t_s:.2f} s mean) executions at full "
-                      f"width (D=3072, N={S + T_TXT}, B=1) after warm-up on {best_n} threads (fastest of a 5-point sweep; {ncpu} logical CPUs); "
+                      f"width (D=3072, N={S + T_TXT}, B=1) after warm-up on {best_n} threads (fastest of a 5-point sweep; {ncpu} CPUs available); "
                       f"extrapolated s/img = {steps} x (19 t_d + 38 t_s) = {s_img:.0f} s (VAE/text encoders excluded); "
                       f"sample wall {time.time() - t0:.0f} s"}
 
@@ -96,13 +115,13 @@ def cpu_baseline_c1(steps=4):
     """BASELINE.md section 3 / BASELINE.json config 1, as specified: SL512 (576 x 512, S = 1152, N = 1664), batch 1, 4 Euler
     steps, fp32, guidance 30, the FULL 19 + 38 block model on the host cores (oracle/pipeline_oracle.denoise), embeddings /
     latents injected.  ~50 GB of host RAM and minutes of CPU time: run once per round with `bench.py --cpu-baseline-c1`
-    and committed under profiles/; the default bench line carries the bounded sample above plus this record."""
+    and committed under profiles/; a `bench.py --full` line carries the bounded sample above plus this record."""
     from oracle import flux_oracle as fo
     from oracle import pipeline_oracle as po
     # BASELINE.md asks for set_num_threads(os.cpu_count()); on this box's 256 logical CPUs (SMT) that oversubscription is
     # pathologically slow (a first attempt did not finish one forward in 20 minutes), so the thread count is the fastest of
-    # a short sweep on the dominant op shape, as in cpu_baseline() above
-    ncpu = os.cpu_count() or 1
+    # a short sweep on the dominant op shape, as in cpu_baseline() above, within the CPUs this process may use
+    ncpu = _cpu_budget()
     xa, wa = torch.randn(1664, D), torch.randn(4 * D, D)
     best_t, best_n = float("inf"), ncpu
     for nthr in sorted({max(1, ncpu // 2), max(1, ncpu // 4), min(ncpu, 64), min(ncpu, 32)}, reverse=True):
@@ -155,6 +174,29 @@ def _transport():
     return "RCCL" if dist.get_backend() == "nccl" else dist.get_backend()
 
 
+DUMP_WHOLE_BYTES = 48 << 20    # --dump-outputs writes the whole batch up to this size, a sample of it above
+DUMP_SAMPLE = 1 << 22          # elements of that sample (16 MiB of float32)
+
+
+def dump_outputs(dirname, images, rank, world):
+    """--dump-outputs: the images the last timed call returned (B x 3 x H x W, what a caller of pipe(output_type="pt") receives).
+      images.npy               float32, the whole batch when it fits in DUMP_WHOLE_BYTES; otherwise
+      images_sample.npy        float32, DUMP_SAMPLE elements of the flattened batch at sorted positions drawn with seed 0
+      images_channel_mean.npy  float64 B x 3, every image's per-channel mean over ALL its pixels
+    In a multi-GPU run, ranks other than 0 add _rank<r> to the names."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    sfx = "" if rank == 0 else f"_rank{rank}"
+    x = images.detach()
+    if x.numel() * 4 <= DUMP_WHOLE_BYTES:
+        np.save(os.path.join(dirname, f"images{sfx}.npy"), x.float().cpu().numpy())
+    else:
+        idx = torch.randint(0, x.numel(), (DUMP_SAMPLE,), generator=torch.Generator().manual_seed(0)).sort().values
+        np.save(os.path.join(dirname, f"images_sample{sfx}.npy"), x.reshape(-1)[idx.to(x.device)].float().cpu().numpy())
+    np.save(os.path.join(dirname, f"images_channel_mean{sfx}.npy"),
+            x.mean(dim=tuple(range(2, x.dim())), dtype=torch.float64).cpu().numpy())
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -175,6 +217,9 @@ def main():
     ap.add_argument("--option", action="append", default=[], metavar="NAME=VALUE", help=argparse.SUPPRESS)  # tuning knobs (tfx_set_option)
     ap.add_argument("--no-text-encoders", action="store_true", help="inject fixed prompt embeddings instead of running T5-XXL / CLIP-L per call")
     ap.add_argument("--fp8", action="store_true", help="BASELINE config 5: e4m3 block linears on the fp8 MFMA (NOT the bf16 headline)")
+    ap.add_argument("--full", action="store_true", help="also the untimed extras (live CPU baseline, roofline sample call, attention A/B, "
+                    "pil delta, MFMA peak probe; the --no-* options above switch single ones off); a plain run times the steps only")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the images of the last timed call to DIR/<name>.npy (float32 / float64)")
     a = ap.parse_args()
     if a.cpu_baseline_c1:
         # (first the bounded sample of the GPU workload's own geometry -- one double + one single block at P1024's token count,
@@ -189,7 +234,7 @@ def main():
     # here so that its ~2 minutes (47.6 GB of fp32 weights, a warm-up forward, 4 steps) overlap the model initialisation and the UNTIMED
     # warm-up calls of this process; it is waited for BEFORE the timed region starts, so the timed calls have the host to themselves.
     c1_proc = None
-    if int(os.environ.get("RANK", "0")) == 0 and a.gpus == 1 and not a.no_cpu_baseline:
+    if int(os.environ.get("RANK", "0")) == 0 and a.gpus == 1 and a.full and not a.no_cpu_baseline:
         import subprocess
         c1_proc = subprocess.Popen([sys.executable, os.path.abspath(__file__), "--cpu-baseline-c1"], stdout=subprocess.PIPE,
                                    stderr=subprocess.DEVNULL, text=True, env=dict(os.environ, HIP_VISIBLE_DEVICES="", ROCR_VISIBLE_DEVICES=""))
@@ -298,9 +343,9 @@ def main():
     torch.cuda.synchronize()
     c1_rec = None
     if c1_proc is not None:      # the host-side baseline finishes before anything is timed
-        try:
-            c1_out, _ = c1_proc.communicate(timeout=900)
-        except Exception:            # a host that cannot finish C1 in 15 minutes must not hold the GPU measurement
+        try:     # at most 6 minutes from its start, so that a --full run ends within 10 minutes
+            c1_out, _ = c1_proc.communicate(timeout=max(1.0, 360.0 - (time.time() - t_c1_start)))
+        except Exception:            # a host that cannot finish C1 in 6 minutes must not hold the GPU measurement
             c1_proc.kill()
             c1_out = ""
         try:
@@ -321,59 +366,61 @@ def main():
     torch.cuda.synchronize()
     elapsed = tdist.max_over_ranks(time.perf_counter() - t0, dev)
     own_all = tdist.all_ranks(own, dev)
-    # roofline sample: ONE MORE call, untimed and eager (the library's per-launch HIP events only see eager launches; a
-    # replayed graph's kernels are not individually timed), so that the sample is every GEMM / attention launch of a whole
-    # call -- 30 steps, VAE, text encoders -- not just the eager first step of a graph-replayed call
-    pipe.enable_hip_graph(False)
-    if rank == 0:
-        ops.prof_enable(True)
-    ops.attention_mode_counts(reset=True)
-    one_call()
-    torch.cuda.synchronize()
-    ops.prof_enable(False)
-    attn_modes = {k: v for k, v in ops.attention_mode_counts(reset=True).items() if v}     # which attention stream every launch of a call took
-    pipe.enable_hip_graph(not a.no_graph)
-    # the reference-free attention stream is selected per launch from the block's q / k RMSNorm weights (tfx_*_block.attn_score_bound);
-    # what a checkpoint whose norm scales do NOT admit it would see: one untimed call (after one warm-up call that re-captures the step
-    # graph) with the bound ignored -- every launch on the guarded kernel
-    unbounded_s = None
-    if rank == 0 and world == 1 and not a.no_attention_ab:
-        ops.set_option("attention_use_bound", 0)
-        tr._session = None                       # the captured step graphs hold the kernels chosen at capture
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, out, rank, world)
+    # ---- --full only: untimed extras after the timed region, each a measurement of its own
+    attn_modes, unbounded_s, pil_delta_ms, probe = {}, None, None, {}
+    if a.full:
+        # roofline sample: ONE MORE call, untimed and eager (the library's per-launch HIP events only see eager launches; a
+        # replayed graph's kernels are not individually timed), so that the sample is every GEMM / attention launch of a whole
+        # call -- 30 steps, VAE, text encoders -- not just the eager first step of a graph-replayed call
+        pipe.enable_hip_graph(False)
+        if rank == 0:
+            ops.prof_enable(True)
+        ops.attention_mode_counts(reset=True)
         one_call()
         torch.cuda.synchronize()
-        t1 = time.perf_counter()
-        one_call()
-        torch.cuda.synchronize()
-        unbounded_s = time.perf_counter() - t1
-        ops.set_option("attention_use_bound", 1)
-        tr._session = None
-    # what the timed calls leave out of a17: output_type="pt" keeps the decoded images on the device; one untimed call with
-    # output_type="pil" (device -> host copy + uint8 / PIL conversion of the batch) gives the difference
-    pil_delta_ms = None
-    if rank == 0 and not a.no_pil_delta:
-        def timed(kind):
+        ops.prof_enable(False)
+        attn_modes = {k: v for k, v in ops.attention_mode_counts(reset=True).items() if v}     # which attention stream every launch of a call took
+        pipe.enable_hip_graph(not a.no_graph)
+        # the reference-free attention stream is selected per launch from the block's q / k RMSNorm weights (tfx_*_block.attn_score_bound);
+        # what a checkpoint whose norm scales do NOT admit it would see: one untimed call (after one warm-up call that re-captures the step
+        # graph) with the bound ignored -- every launch on the guarded kernel
+        if rank == 0 and world == 1 and not a.no_attention_ab:
+            ops.set_option("attention_use_bound", 0)
+            tr._session = None                       # the captured step graphs hold the kernels chosen at capture
+            one_call()
             torch.cuda.synchronize()
             t1 = time.perf_counter()
-            with torch.no_grad():
-                pipe(prompt_embeds=pe, pooled_prompt_embeds=pooled, image=image, mask_image=mask, height=H, width=W,
-                     num_inference_steps=1, guidance_scale=30.0, generator=gen, output_type=kind)
+            one_call()
             torch.cuda.synchronize()
-            return time.perf_counter() - t1
-        timed("pt")
-        t_pt, t_pil = min(timed("pt"), timed("pt")), min(timed("pil"), timed("pil"))
-        pil_delta_ms = (t_pil - t_pt) * 1e3
-    # the matrix-pipe rate this board sustains at its power cap on random operands (tfx_mfma_peak_probe, LIVE: the product library's own
-    # MFMA-only kernel, ~2.5 s each): the denominator of roofline.frac_of_capped; bf16 and e4m3
-    probe = {}
-    if rank == 0 and not a.no_peak_probe:
-        gp = torch.Generator().manual_seed(5)
-        rb = torch.randn(1 << 20, generator=gp)
-        probe["bf16"] = ops.mfma_peak_probe(rb.to(torch.bfloat16).to(dev), fp8=False, seconds=2.5)
-        try:
-            probe["e4m3"] = ops.mfma_peak_probe(rb.to(torch.float8_e4m3fn).view(torch.uint8).to(dev), fp8=True, seconds=2.5)
-        except Exception as e:
-            probe["e4m3"] = {"error": f"{type(e).__name__}: {e}"}
+            unbounded_s = time.perf_counter() - t1
+            ops.set_option("attention_use_bound", 1)
+            tr._session = None
+        # what the timed calls leave out of a17: output_type="pt" keeps the decoded images on the device; one untimed call with
+        # output_type="pil" (device -> host copy + uint8 / PIL conversion of the batch) gives the difference
+        if rank == 0 and not a.no_pil_delta:
+            def timed(kind):
+                torch.cuda.synchronize()
+                t1 = time.perf_counter()
+                with torch.no_grad():
+                    pipe(prompt_embeds=pe, pooled_prompt_embeds=pooled, image=image, mask_image=mask, height=H, width=W,
+                         num_inference_steps=1, guidance_scale=30.0, generator=gen, output_type=kind)
+                torch.cuda.synchronize()
+                return time.perf_counter() - t1
+            timed("pt")
+            t_pt, t_pil = min(timed("pt"), timed("pt")), min(timed("pil"), timed("pil"))
+            pil_delta_ms = (t_pil - t_pt) * 1e3
+        # the matrix-pipe rate this board sustains at its power cap on random operands (tfx_mfma_peak_probe, LIVE: the product library's own
+        # MFMA-only kernel, ~2.5 s each): the denominator of roofline.frac_of_capped; bf16 and e4m3
+        if rank == 0 and not a.no_peak_probe:
+            gp = torch.Generator().manual_seed(5)
+            rb = torch.randn(1 << 20, generator=gp)
+            probe["bf16"] = ops.mfma_peak_probe(rb.to(torch.bfloat16).to(dev), fp8=False, seconds=2.5)
+            try:
+                probe["e4m3"] = ops.mfma_peak_probe(rb.to(torch.float8_e4m3fn).view(torch.uint8).to(dev), fp8=True, seconds=2.5)
+            except Exception as e:
+                probe["e4m3"] = {"error": f"{type(e).__name__}: {e}"}
     seen = tdist.ranks_seen(dev)   # ranks that answered an RCCL all-reduce
     # results travel to rank 0 the way the batch driver collects them (untimed here: `value` is generation throughput): a per-image
     # checksum of every rank's last call, gathered over RCCL -- rank 0 checks that every rank produced finite images
@@ -480,6 +527,9 @@ def main():
                 "workload_block_sample": c1_rec.get("workload_block_sample")}
         elif c1_rec is not None:
             rec["cpu_baseline"] = {"value": None, "unit": "images/sec", "cores": None, "kind": "port", "live": True, "sample": c1_rec["error"]}
+        if not a.full:      # a plain run measured none of these: its line carries the headline and the run's own bookkeeping
+            for k in ("pil_output_delta_ms_per_call", "roofline", "cpu_baseline"):
+                del rec[k]
         print(json.dumps(rec), flush=True)
     tdist.shutdown()
 

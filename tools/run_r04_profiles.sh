@@ -4,13 +4,13 @@
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 out=gpurun_out/r04; mkdir -p $out
 # 0. the default bench line (hipGraph replay) as the driver runs it
-timeout 900 python bench.py > $out/bench.log 2>&1; grep '^{"metric"' $out/bench.log > $out/r04_bench.json
+timeout 900 python bench.py --full > $out/bench.log 2>&1; grep '^{"metric"' $out/bench.log > $out/r04_bench.json
 # 1. kernel-trace summary of the default bench run (eager, so that every launch is in the trace) + its bench line
-rocprofv3 --kernel-trace --stats -d $out/trace -o r04 --output-format csv -- python bench.py --no-cpu-baseline --no-pil-delta --no-graph --steps 1 --warmup 1 > $out/bench_under_rocprof.log 2>&1
+rocprofv3 --kernel-trace --stats -d $out/trace -o r04 --output-format csv -- python bench.py --full --no-cpu-baseline --no-pil-delta --no-graph --steps 1 --warmup 1 > $out/bench_under_rocprof.log 2>&1
 grep "^{\"metric\"" $out/bench_under_rocprof.log > $out/r04_bench_under_rocprof.json
 cp $out/trace/*kernel_stats.csv $out/r04_bench_kernel_stats.csv 2>/dev/null; rm -rf $out/trace
 # 2. matrix-pipe busy over a 2-step bench
-rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE --kernel-trace -d $out/mfma -o r04 --output-format csv -- python bench.py --no-cpu-baseline --no-pil-delta --no-graph --steps 1 --warmup 0 --denoise-steps 2 > $out/mfma.log 2>&1
+rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE --kernel-trace -d $out/mfma -o r04 --output-format csv -- python bench.py --full --no-cpu-baseline --no-pil-delta --no-graph --steps 1 --warmup 0 --denoise-steps 2 > $out/mfma.log 2>&1
 python tools/pmc_bench_util.py $out/mfma/r04_counter_collection.csv $out/r04_mfma_util.json > $out/mfma_util.log 2>&1
 # 3. GEMM traffic at the three dominant shapes (separate passes)
 for c in FETCH_SIZE WRITE_SIZE "SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE"; do

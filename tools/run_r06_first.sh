@@ -6,7 +6,7 @@ out=gpurun_out/r06a; mkdir -p $out
 ( time timeout 1500 python -m pytest tests -x -q -m gpu --durations=60 ) > $out/gputests.log 2>&1
 tail -75 $out/gputests.log | head -70
 ( time timeout 900 python -m pytest tools/variant_tests -x -q -m gpu ) > $out/variants.log 2>&1; tail -5 $out/variants.log
-( time timeout 900 python bench.py --steps 3 --warmup 2 ) > $out/bench.log 2>&1; grep '^{"metric"' $out/bench.log > $out/r06_bench_first.json; tail -3 $out/bench.log | cut -c1-600
+( time timeout 900 python bench.py --full --steps 3 --warmup 2 ) > $out/bench.log 2>&1; grep '^{"metric"' $out/bench.log > $out/r06_bench_first.json; tail -3 $out/bench.log | cut -c1-600
 timeout 600 python tools/gemm_shapes_power.py --tag r06 --hipblaslt --out $out/r06_gemm_shapes.jsonl > $out/shapes.log 2>&1; tail -2 $out/shapes.log
 timeout 300 python tools/qkn_ab6.py $out/r06_qkn_ab.json > $out/qkn_ab.log 2>&1; tail -12 $out/qkn_ab.log
 ls $out

@@ -4,7 +4,7 @@
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 out=gpurun_out/r06i; mkdir -p $out
 timeout 1500 python -m pytest tests/test_kernels_gpu.py tests/test_fullsize_gpu.py tests/test_model_gpu.py tests/test_pipeline_gpu.py tests/test_configs_gpu.py tests/test_text_encoders_gpu.py -q -m gpu 2>&1 | tail -8 | cut -c1-250
-b1() { timeout 400 python bench.py --no-cpu-baseline --no-attention-ab --no-pil-delta --no-peak-probe --batch 1 --steps 4 --warmup 2 "$@" 2>&1 | grep '^{"metric"' | python -c "import sys,json; d=json.loads(sys.stdin.read()); print(round(d['sec_per_img_per_gpu'],4), round(d['dit_algorithmic_tflops_per_gpu']), round(d['roofline']['achieved']), round(d['roofline']['attention']['achieved']))"; }
+b1() { timeout 400 python bench.py --full --no-cpu-baseline --no-attention-ab --no-pil-delta --no-peak-probe --batch 1 --steps 4 --warmup 2 "$@" 2>&1 | grep '^{"metric"' | python -c "import sys,json; d=json.loads(sys.stdin.read()); print(round(d['sec_per_img_per_gpu'],4), round(d['dit_algorithmic_tflops_per_gpu']), round(d['roofline']['achieved']), round(d['roofline']['attention']['achieved']))"; }
 for r in 1 2; do
   echo "== SL512 b1 round-5 behaviour (ln_joint 0, ln_prefetch 0)"; b1 --height 576 --width 512 --option ln_joint=0 --option ln_prefetch=0
   echo "== SL512 b1 ln_joint 1, ln_prefetch 0"; b1 --height 576 --width 512 --option ln_prefetch=0
