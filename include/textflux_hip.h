@@ -33,7 +33,7 @@ const char* tfx_last_error(void);
  * two since ABI 6) and returns how many values there are.  A binding
  * compares them with its own view of this header BEFORE the first call that passes a struct: a library built from an older
  * header would otherwise ignore the tail fields of a grown struct silently (no reference counterpart: the reference has no FFI). */
-#define TFX_ABI_VERSION 8
+#define TFX_ABI_VERSION 9
 int tfx_abi_info(int32_t* out, int n);
 /* Writes the gcnArchName of the current device (e.g. "gfx950:sramecc+:xnack-") into buf.  Needs a GPU. */
 int tfx_query_arch(char* buf, int buflen);
@@ -44,7 +44,10 @@ int tfx_query_arch(char* buf, int buflen);
  *      A [batch][M,K] (lda, a_bstride), W [N,K] nn.Linear layout (ldw), bias [N] or NULL, C [batch][M,N].
  *      epilogue: 0 bias | 1 bias, then tanh-GELU on columns >= gelu_from_col (activations.py:83; the split form is the
  *      fused [k|v|q|mlp] projection of FluxSingleTransformerBlock) | 3 C = res + (A@W^T + bias) | 2 C = res + gate[b,:] * (A@W^T + bias)
- *      (gated residual, transformer_flux.py:733-735, 817-818, 824-826, 830-831, 837; res may alias C).
+ *      (gated residual, transformer_flux.py:733-735, 817-818, 824-826, 830-831, 837; res may alias C) | 4 (ABI 9) C = bf16(cscale[n] *
+ *      (A@W^T)): a per-output-column fp32 factor read from DEVICE memory at run time, bias must be NULL -- the down projection
+ *      t = bf16(c * (x @ Acat^T)) of runtime LoRA adapters (tfx_gemm_bf16_lora below; PEFT's lora_A + scaling, D/utils/peft_utils.py:103-120):
+ *      a captured graph sees a new adapter scale without re-capture.  tfx_gemm_bf16 only.
  *      variant: -1 auto, 0 generic FMA kernel (any shape), 1 MFMA path (K % 64 == 0, N % 8 == 0, 16-byte aligned;
  *      the persistent kernel when K % 128 == 0, else the one-tile kernel), 2 / 3 force the one-tile / persistent MFMA
  *      kernel (tests: the two agree bit for bit). */
@@ -66,6 +69,8 @@ typedef struct tfx_gemm_args {
    * for every batch sample, every nn.Linear).  bf16 entry points only; what the VAE mid-block attention's q k^T and P v products are
    * (k and v^T differ per image): one launch per query-row chunk for the whole batch instead of one per image. */
   int64_t w_bstride;
+  /* ABI 9: epilogue 4's factors, fp32 [N], 16-byte aligned (ignored by every other epilogue) */
+  const float* cscale;
 } tfx_gemm_args;
 int tfx_gemm_bf16(const tfx_gemm_args* args, int variant, tfx_stream stream);
 
@@ -84,6 +89,37 @@ typedef struct tfx_qkn_args {
   float eps;
 } tfx_qkn_args;
 int tfx_gemm_bf16_qkn(const tfx_gemm_args* args, const tfx_qkn_args* qkn, tfx_stream stream);
+
+/* ABI 9.  A Linear with RUNTIME (unmerged) LoRA adapters (PEFT's lora.Linear.forward, scaled per call as
+ * transformer_flux.py:1073-1079 / D/utils/peft_utils.py:103-120 do): the low-rank update is a K-extension of the GEMM,
+ *     C = epi(A @ W^T + T @ Bm^T + bias)          ONE fp32 accumulation, then the epilogue of tfx_gemm_bf16 / tfx_gemm_bf16_qkn,
+ * where T = bf16(c * (A @ Acat^T)) [batch][M, nseg * R] is the scaled down-projection the caller computed before (c = scale * adapter
+ * weight * alpha / r), so the fused q / k norm + RoPE epilogue (qkn != NULL) sees the adapted projection.  The engine's rounding points:
+ * T once to bf16, the sum once in the epilogue; PEFT rounds the down projection, the up projection, the scaled update and the base
+ * Linear separately.
+ *   R          padded rank: 128 or 256 (zero-pad smaller ranks; several adapters on one Linear concatenate along the rank axis);
+ *   segments   a fused weight holds several reference Linears as row ranges of seg_cols rows (a multiple of 256), each with its own
+ *              A: output column n belongs to segment min(n / seg_cols, nseg - 1), nseg <= 4, and reads T's columns
+ *              [seg * R, seg * R + R) -- or, t_seg_stride != 0 (where nseg * R exceeds A's row pitch), the R columns of a T matrix of its
+ *              own, t_seg_stride elements above the previous segment's (a multiple of 8, no overlap).  seg_mask bit s = segment s carries an adapter; tiles of other segments skip the tail (their
+ *              T block and Bm rows are never read).  Row-split launches: bit 8 + s for the rows below split_row;
+ *   placement  the kernel addresses the tail through the descriptors of A and W, so: T is addressed with args->lda / a_bstride
+ *              (nseg * R <= lda) and lies ABOVE A with both inside one caller-owned byte range below 4 GiB - 64 KiB that is readable
+ *              throughout (e.g. one allocation [x | T]); Bm == W + K, i.e. row n of Bm is stored behind row n of W (ldw >= K + R).
+ *   row split  split_row > 0 (a multiple of 256, < M): rows below it (the TEXT rows of the joint [text | image] stream) use W2 / bias2 /
+ *              gate2 / norm_q2 / norm_k2; W2 (with its own Bm behind its rows, same ldw) lies above W within 4 GiB.  0 = off.
+ * Always the persistent MFMA kernel on whole tiles (K % 128 == 0, N % 8 == 0, 16-byte aligned rows; args->workspace is ignored: an
+ * adapted GEMM is never K-sliced); operands it cannot take are refused, there is no fallback.  bf16 only. */
+typedef struct tfx_lora_args {
+  const void* T; const void* Bm;
+  int32_t R, seg_cols, nseg;
+  uint32_t seg_mask;
+  int32_t split_row;
+  const void* W2; const void* bias2; const void* gate2; const void* norm_q2; const void* norm_k2;
+  int64_t t_seg_stride;
+} tfx_lora_args;
+int tfx_gemm_bf16_lora(const tfx_gemm_args* args, const tfx_qkn_args* qkn /* NULL = no q/k norm */, const tfx_lora_args* lora,
+                       tfx_stream stream);
 
 /* Same operands, C = fp32 raw accumulators [batch][M, N] (ldc / c_bstride in floats, C 16-byte aligned); bias must be
  * NULL and epilogue 0.  Used where a product must reach its consumer unrounded: the q k^T scores of the VAE mid-block
@@ -204,7 +240,20 @@ int tfx_advance_step(int32_t* step_ptr, tfx_stream stream);
  * Workspace (caller-owned, bf16): hid [B][N,D], xn [B][N,D], y [B][N,7D], with N = T + S (text rows first). */
 /* w8 / w8_scale (optional, may be NULL): the same weight as e4m3 bytes [out,in] with one fp32 scale per output channel
  * (tfx_quantize_rows_fp8 of w); used when tfx_dit_desc.flags bit 2 is set and in % 256 == 0, see below. */
-typedef struct tfx_linear { const void* w; const void* b; const void* w8; const float* w8_scale; } tfx_linear;
+/* ABI 9, runtime (unmerged) LoRA adapters on a block Linear (all 0 / NULL = none: the forward then issues exactly the launches it always
+ * did).  ldw: row pitch of w in elements (0 = in_features); an adapted Linear keeps its up-projection rows Bcat [out, lora_r] BEHIND its
+ * weight rows, columns [in, in + lora_r) of w (ldw >= in + lora_r); the two Linears of a double block's [img; txt] pair share ldw and
+ * lora_r when either is adapted.  lora_a: Acat [lora_nseg * lora_r, in] bf16, the segments' zero-padded A stacked (segment = one
+ * reference Linear of the fused weight: D output columns each; 1 segment = the whole Linear); lora_r 128 or 256; lora_mask bit s =
+ * segment s is adapted; lora_scale_off: index of this Linear's lora_nseg * lora_r factors c in tfx_dit_desc.lora_scale (a multiple of 4).
+ * The Linear then runs as  t = bf16(c * (x @ Acat^T))  (tfx_gemm_bf16, epilogue 4)  +  tfx_gemm_bf16_lora.  Block Linears only: the
+ * fields are ignored for x_embedder / proj_out of tfx_dit_desc.  Not with flags bit 2 (fp8 linears): refused. */
+typedef struct tfx_linear {
+  const void* w; const void* b; const void* w8; const float* w8_scale;
+  int64_t ldw;
+  const void* lora_a;
+  int32_t lora_r, lora_nseg, lora_mask, lora_scale_off;
+} tfx_linear;
 /* attn_score_bound (ABI 6, optional): tfx_attn_args.score_bound of THIS block's attention launch, from this block's own q / k
  * RMSNorm weights -- 128 * max(max|norm_q|, max|norm_added_q|) * max(max|norm_k|, max|norm_added_k|) * 128^-0.5 (+ rounding margin).
  * 0 = unknown: the launch falls back to tfx_dit_desc.attn_score_bound (0 there too = no promise).  Per block, so that one block
@@ -257,12 +306,21 @@ typedef struct tfx_dit_desc {
    * caller derives it from the q / k RMSNorm weights: 128 * max|w_q| * max|w_k| * 128^-0.5 (text-stream norms included), see
    * tfx_attn_args; since ABI 6 the per-block fields are the ones the engine fills. */
   float attn_score_bound;
+  /* ABI 9: scratch and factors of the runtime LoRA adapters (required when any block Linear carries lora_a).  lora_t_xn / lora_t_y hold
+   * the down projections T of Linears whose input lives in xn / in y: T of input A sits at A + (lora_t_xn - xn) resp. A + (lora_t_y - y),
+   * so each region mirrors its buffer's shape -- lora_t_xn: 1 (D >= 1024) or 4 (smaller D: one per segment) matrices [B][N, D],
+   * lora_t_y: [B][N, 7D] -- and must lie ABOVE it within 4 GiB - 64 KiB, end included (tfx_workspace_layout flags bit 3 places them).
+   * lora_scale: fp32 device vector of every adapted Linear's factors c = call scale * adapter weight * alpha / r, read by the
+   * kernels when they run: rewriting it changes the strength of the next forward / graph replay, nothing is re-captured. */
+  void* lora_t_xn; void* lora_t_y; const float* lora_scale;
 } tfx_dit_desc;
 int tfx_dit_forward(const tfx_dit_desc* desc, tfx_stream stream);
 
 /* Caller-owned workspace of tfx_dit_forward for one problem size, as ONE allocation: total bytes, and the byte offsets
  * (256-byte aligned) of its parts in off[0..5] = hid, xn, y, q8, q8_scale, gemm_workspace (q8 / q8_scale only when
- * flags bit 2 (fp8 linears) is set, else -1); *gemm_workspace_bytes = size of the split-K / stream-K scratch (128 MiB).  Host-side
+ * flags bit 2 (fp8 linears) is set, else -1); *gemm_workspace_bytes = size of the split-K / stream-K scratch (128 MiB).  flags bit 3
+ * (ABI 9, runtime LoRA adapters): `off` has 8 entries, off[6] / off[7] = lora_t_xn / lora_t_y, appended BEHIND the parts above (whose
+ * offsets do not change); without the bit only off[0..5] are written and the total is what it always was.  Host-side
  * arithmetic only, no GPU needed.  ("never allocate persistent memory except through an explicit
  * workspace the Python side owns".) */
 int64_t tfx_workspace_bytes(int32_t B, int32_t S, int32_t T, int32_t D, int32_t flags);

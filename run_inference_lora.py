@@ -1,7 +1,9 @@
 #!/usr/bin/env python3
 """LoRA variant of run_inference.py: base FLUX.1-Fill-dev transformer + TextFlux LoRA merged at load (reference:
 run_inference_lora.py:44-73: lora_state_dict(..., return_alphas=True) + load_lora_into_transformer).  Like the
-reference, --scheduler is parsed but the sampler is chosen by the module-level `scheduler_name`."""
+reference, --scheduler is parsed but the sampler is chosen by the module-level `scheduler_name`.
+Not in the reference: --lora_runtime keeps the adapter unmerged (FluxTransformer2DModel.attach_lora: its strength can change per call,
+it can be unloaded) and --lora_scale sets its strength; the defaults are the merged path at strength 1."""
 import argparse
 import os
 import sys
@@ -15,18 +17,26 @@ from textflux_amd.transformer import FluxTransformer2DModel
 
 LORA = os.environ.get("TEXTFLUX_LORA", "./models/textflux-lora-beta")
 scheduler_name = "default"
+LORA_ADAPTER = "textflux"
 
 
-def load_flux_pipeline():
+def load_flux_pipeline(lora_runtime: bool = False, lora_scale: float = 1.0):
     if base.PIPE is None:
         transformer = FluxTransformer2DModel.from_pretrained(base.BASE, subfolder="transformer", torch_dtype=torch.bfloat16)
         state_dict, network_alphas = FluxFillPipeline.lora_state_dict(LORA, return_alphas=True)
-        FluxFillPipeline.load_lora_into_transformer(state_dict, network_alphas, transformer)
+        if lora_runtime:
+            FluxFillPipeline.load_lora_into_transformer(state_dict, network_alphas, transformer, adapter_name=LORA_ADAPTER, runtime=True)
+            transformer.set_adapters([LORA_ADAPTER], [lora_scale])
+        elif lora_scale != 1.0:
+            from textflux_amd import lora
+            lora.merge_lora_into_transformer(state_dict, network_alphas, transformer, scale=lora_scale)
+        else:
+            FluxFillPipeline.load_lora_into_transformer(state_dict, network_alphas, transformer)
         base.PIPE = FluxFillPipeline.from_pretrained(base.BASE, transformer=transformer, torch_dtype=torch.bfloat16).to("cuda")
     return base.PIPE
 
 
-def main():
+def build_parser():
     ap = argparse.ArgumentParser(description="Flux Text Generation CLI (LoRA)")
     ap.add_argument("--image", type=str, required=True)
     ap.add_argument("--mask", type=str, required=True)
@@ -35,9 +45,16 @@ def main():
     ap.add_argument("--guidance-scale", type=float, default=30)
     ap.add_argument("--seed", type=int, default=42)
     ap.add_argument("--scheduler", type=str, default="default", help="parsed but unused, as in the reference (:538)")
-    a = ap.parse_args()
+    ap.add_argument("--lora_runtime", action="store_true", help="keep the LoRA as an unmerged runtime adapter instead of merging it at load")
+    ap.add_argument("--lora_scale", type=float, default=1.0, help="strength of the LoRA (1.0 = as trained)")
+    return ap
+
+
+def main(argv=None):
+    a = build_parser().parse_args(argv)
     base.scheduler_name = scheduler_name
-    base.process_normal_mode(a.image, a.mask, a.words, a.steps, a.guidance_scale, a.seed, pipe=load_flux_pipeline())
+    base.process_normal_mode(a.image, a.mask, a.words, a.steps, a.guidance_scale, a.seed,
+                             pipe=load_flux_pipeline(a.lora_runtime, a.lora_scale))
     print("\nProcessing completed successfully!")
 
 

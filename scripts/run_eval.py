@@ -53,6 +53,9 @@ def build_parser(lora: bool = False):
     ap.add_argument("--output_dir", type=str, default="visualization_results", help="Main output folder for results")
     if lora:
         ap.add_argument("--lora_weights_path", type=str, help="Path to lora weights")
+        # not in the reference: the LoRA as an unmerged runtime adapter, and its strength (defaults = merged at load, strength 1)
+        ap.add_argument("--lora_runtime", action="store_true", help="keep the LoRA unmerged (runtime adapter) instead of merging it at load")
+        ap.add_argument("--lora_scale", type=float, default=1.0, help="strength of the LoRA (1.0 = as trained)")
     else:
         ap.add_argument("--weights_path", type=str, help="Path to transformer weights")
     ap.add_argument("--font_path", type=str, default="./resource/font/Arial-Unicode-Regular.ttf", help="Path to the font file (.ttf or .ttc)")
@@ -84,7 +87,7 @@ def select_tasks(data_list):
     return tasks, skipped
 
 
-def load_lora_transformer(lora_weights_path, base_transformer=None):
+def load_lora_transformer(lora_weights_path, base_transformer=None, lora_runtime: bool = False, lora_scale: float = 1.0):
     """The reference worker's load sequence (scripts/run_eval_lora.py:148-167): the BASE FLUX.1-Fill-dev transformer, the LoRA file
     through FluxFillPipeline.lora_state_dict(return_alphas=True), the format check (every key names a LoRA / DoRA tensor, else
     ValueError("Invalid LoRA checkpoint.")), then load_lora_into_transformer -- which here MERGES the update into the fused weights
@@ -99,7 +102,15 @@ def load_lora_transformer(lora_weights_path, base_transformer=None):
     state_dict, network_alphas = FluxFillPipeline.lora_state_dict(lora_weights_path, return_alphas=True)
     if not all("lora" in key or "dora_scale" in key for key in state_dict.keys()):
         raise ValueError("Invalid LoRA checkpoint.")
-    FluxFillPipeline.load_lora_into_transformer(state_dict=state_dict, network_alphas=network_alphas, transformer=transformer)
+    if lora_runtime:      # --lora_runtime: attached, not merged (FluxTransformer2DModel.attach_lora)
+        FluxFillPipeline.load_lora_into_transformer(state_dict=state_dict, network_alphas=network_alphas, transformer=transformer,
+                                                    adapter_name="textflux", runtime=True)
+        transformer.set_adapters(["textflux"], [lora_scale])
+    elif lora_scale != 1.0:
+        from textflux_amd import lora
+        lora.merge_lora_into_transformer(state_dict, network_alphas, transformer, scale=lora_scale)
+    else:
+        FluxFillPipeline.load_lora_into_transformer(state_dict=state_dict, network_alphas=network_alphas, transformer=transformer)
     return transformer
 
 
@@ -156,7 +167,7 @@ def main(argv=None, lora: bool = False, script: str = __file__):
     if lora and weights:      # every rank (the reference: every worker) loads the base transformer and merges the LoRA into it
         import torch
         from textflux_amd.pipeline import FluxFillPipeline
-        pipe = FluxFillPipeline.from_pretrained(ri.BASE, transformer=load_lora_transformer(weights), torch_dtype=torch.bfloat16).to("cuda")
+        pipe = FluxFillPipeline.from_pretrained(ri.BASE, transformer=load_lora_transformer(weights, lora_runtime=a.lora_runtime, lora_scale=a.lora_scale), torch_dtype=torch.bfloat16).to("cuda")
     else:
         pipe = ri.load_flux_pipeline(text_encoders=True)     # every rank encodes its own prompts: no rank-0 straggler
     if a.scheduler == "overshoot":

@@ -21,7 +21,7 @@ c_void_p, c_int, c_int32, c_int64, c_float, c_char_p = C.c_void_p, C.c_int, C.c_
 # TFX_ABI_VERSION of the include/textflux_hip.h the ctypes mirrors below were written against (tests/test_capi_symbols.py asserts
 # that it equals the header's): the library's stamp is compared with THIS constant, so a binding copied without include/ still
 # loads, and a ctypes mirror edited without the header (or the other way round) fails a test instead of passing the check.
-ABI_VERSION = 8
+ABI_VERSION = 9
 
 
 class GemmArgs(C.Structure):
@@ -36,12 +36,19 @@ class GemmArgs(C.Structure):
         ("res", c_void_p), ("ldr", c_int64), ("r_bstride", c_int64),
         ("workspace", c_void_p), ("workspace_bytes", c_int64),
         ("w_bstride", c_int64),
+        ("cscale", c_void_p),
     ]
 
 
 class QknArgs(C.Structure):
     _fields_ = [("norm_q", c_void_p), ("norm_k", c_void_p), ("rope_cs", c_void_p), ("pos0", c_int32), ("q0", c_int32), ("q1", c_int32),
                 ("k0", c_int32), ("k1", c_int32), ("eps", c_float)]
+
+
+class LoraArgs(C.Structure):
+    _fields_ = [("T", c_void_p), ("Bm", c_void_p), ("R", c_int32), ("seg_cols", c_int32), ("nseg", c_int32), ("seg_mask", C.c_uint32),
+                ("split_row", c_int32), ("W2", c_void_p), ("bias2", c_void_p), ("gate2", c_void_p), ("norm_q2", c_void_p),
+                ("norm_k2", c_void_p), ("t_seg_stride", c_int64)]
 
 
 class AttnArgs(C.Structure):
@@ -55,7 +62,9 @@ class AttnArgs(C.Structure):
 
 
 class Linear(C.Structure):
-    _fields_ = [("w", c_void_p), ("b", c_void_p), ("w8", c_void_p), ("w8_scale", c_void_p)]
+    _fields_ = [("w", c_void_p), ("b", c_void_p), ("w8", c_void_p), ("w8_scale", c_void_p),
+                ("ldw", c_int64), ("lora_a", c_void_p), ("lora_r", c_int32), ("lora_nseg", c_int32), ("lora_mask", c_int32),
+                ("lora_scale_off", c_int32)]
 
 
 class DoubleBlock(C.Structure):
@@ -86,6 +95,7 @@ class DitDesc(C.Structure):
         ("rope_cs", c_void_p),
         ("euler_gate", c_void_p), ("euler_gate_bstride", c_int64),
         ("attn_score_bound", c_float),
+        ("lora_t_xn", c_void_p), ("lora_t_y", c_void_p), ("lora_scale", c_void_p),
     ]
 
 
@@ -102,6 +112,7 @@ SIGNATURES = {
     "tfx_query_arch": (c_int, [c_char_p, c_int]),
     "tfx_gemm_bf16": (c_int, [C.POINTER(GemmArgs), c_int, c_void_p]),
     "tfx_gemm_bf16_qkn": (c_int, [C.POINTER(GemmArgs), C.POINTER(QknArgs), c_void_p]),
+    "tfx_gemm_bf16_lora": (c_int, [C.POINTER(GemmArgs), C.POINTER(QknArgs), C.POINTER(LoraArgs), c_void_p]),
     "tfx_gemm_bf16_f32": (c_int, [C.POINTER(GemmArgs), c_void_p]),
     "tfx_gemm_fp8": (c_int, [C.POINTER(GemmArgs), c_void_p, c_int64, c_void_p, c_void_p]),
     "tfx_ln_modulate_fp8": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_void_p, c_void_p,

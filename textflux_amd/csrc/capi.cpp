@@ -15,14 +15,25 @@ inline hipStream_t S(tfx_stream s) { return (hipStream_t)s; }
 inline const uint16_t* bf(const void* p) { return (const uint16_t*)p; }
 inline uint16_t* bf(void* p) { return (uint16_t*)p; }
 
+#define TRY(x)            \
+  do {                    \
+    if (int _e = (x)) return _e; \
+  } while (0)
+
+// runtime LoRA adapters: what an adapted Linear of the forward in progress needs beyond its own operands (tfx_dit_desc: the T scratch
+// regions and the factor vector); set for the duration of dit_forward
+struct LoraCtx { const tfx_dit_desc* d; };
+thread_local const LoraCtx* g_lora = nullptr;
+
 struct Gemm {
   GemmArgs a;
   const tfx_linear* lin;
+  const tfx_linear* lin2 = nullptr;     // row-split launches: the Linear of the rows below split_row
   Gemm(const void* A, int64_t lda, int64_t abs_, const tfx_linear& l, int64_t ldw, void* C, int64_t ldc, int64_t cbs,
        int M, int N, int K, int batch) : lin(&l) {
     a = GemmArgs();
     a.A = A; a.lda = lda; a.a_bstride = abs_;
-    a.W = l.w; a.ldw = ldw; a.bias = l.b;
+    a.W = l.w; a.ldw = l.ldw > 0 ? l.ldw : ldw; a.bias = l.b;
     a.C = C; a.ldc = ldc; a.c_bstride = cbs;
     a.M = M; a.N = N; a.K = K; a.batch = batch;
     a.epilogue = EPI_BIAS;
@@ -35,7 +46,7 @@ struct Gemm {
   Gemm& scratch(void* ws, int64_t bytes) { a.workspace = ws; a.workspace_bytes = bytes; return *this; }
   // row-split weights: rows [0, split_row) of every sample (the text rows of the joint stream) take l2 / gate2 (/ norm weights wq2, wk2)
   Gemm& rowsplit(int split_row, const tfx_linear& l2, const void* gate2 = nullptr) {
-    a.split_row = split_row; a.W2 = l2.w; a.bias2 = l2.b; a.gate2 = gate2;
+    a.split_row = split_row; a.W2 = l2.w; a.bias2 = l2.b; a.gate2 = gate2; lin2 = &l2;
     return *this;
   }
   Gemm& qknorm2(const void* wq2, const void* wk2) { a.qkn_wq2 = wq2; a.qkn_wk2 = wk2; return *this; }
@@ -53,10 +64,61 @@ struct Gemm {
     if (t.a.split_row > 0 && !(t.a.qkn_wq2 && t.a.qkn_wk2)) return false;
     return fp8 ? gemm_fp8_qkn_ok(t.a) : gemm_qkn_ok(t.a);
   }
-  int run(hipStream_t st) const { return gemm_bf16(a, st); }
+  bool adapted() const { return lin->lora_a || (a.split_row > 0 && lin2 && lin2->lora_a); }
+  // t = bf16(c * (x @ Acat^T)) into the T scratch that mirrors x's buffer, then the GEMM with the low-rank tail (gemm_bf16_lora)
+  int run_lora(hipStream_t st) const {
+    if (!g_lora) return fail("dit_forward: adapted Linear outside a forward");
+    const tfx_dit_desc& d = *g_lora->d;
+    if (!d.lora_t_xn || !d.lora_t_y || !d.lora_scale)
+      return fail("dit_forward: a block Linear carries a runtime LoRA adapter but lora_t_xn / lora_t_y / lora_scale are null");
+    const tfx_linear* l2 = a.split_row > 0 ? lin2 : nullptr;
+    const tfx_linear& ref = lin->lora_a ? *lin : *l2;
+    const int R = ref.lora_r, nseg = ref.lora_nseg;
+    if (R <= 0 || nseg <= 0 || nseg > 4) return fail("dit_forward: bad lora_r / lora_nseg on an adapted Linear");
+    if (l2 && (l2->ldw != lin->ldw || (l2->lora_a && lin->lora_a && (l2->lora_r != R || l2->lora_nseg != nseg))))
+      return fail("dit_forward: the [img; txt] Linears of a joint launch must share ldw, lora_r and lora_nseg");
+    const int64_t hid_elems = (int64_t)d.B * (d.S + d.T) * d.D;
+    const char* A = (const char*)a.A;
+    const bool in_xn = A >= (const char*)d.xn && A < (const char*)d.xn + hid_elems * 2;
+    const bool in_y = A >= (const char*)d.y && A < (const char*)d.y + hid_elems * 14;
+    if (!in_xn && !in_y) return fail("dit_forward: adapted Linear whose input is neither xn nor y");
+    char* T = const_cast<char*>(A) + (in_xn ? (const char*)d.lora_t_xn - (const char*)d.xn : (const char*)d.lora_t_y - (const char*)d.y);
+    const bool planes = (int64_t)nseg * R > a.lda;        // the segments' T blocks do not fit one row: a matrix per segment
+    if (planes && (!in_xn || d.D >= 1024)) return fail("dit_forward: lora_nseg * lora_r exceeds the input's row pitch");
+    auto down = [&](const tfx_linear& l, int row0, int rows) -> int {
+      if (!l.lora_a || rows <= 0) return 0;
+      GemmArgs g = GemmArgs();
+      g.A = A + (int64_t)row0 * a.lda * 2; g.lda = a.lda; g.a_bstride = a.a_bstride;
+      g.ldw = a.K; g.bias = nullptr;
+      g.ldc = a.lda; g.c_bstride = a.a_bstride;
+      g.M = rows; g.K = a.K; g.batch = a.batch;
+      g.epilogue = EPI_COLSCALE;
+      g.workspace = a.workspace; g.workspace_bytes = a.workspace_bytes;
+      for (int s = 0; s < (planes ? nseg : 1); ++s) {
+        if (planes && !((l.lora_mask >> s) & 1)) continue;
+        g.W = (const char*)l.lora_a + (int64_t)s * R * a.K * 2;
+        g.C = T + (int64_t)row0 * a.lda * 2 + (int64_t)s * hid_elems * 2;
+        g.N = planes ? R : nseg * R;
+        g.cscale = d.lora_scale + l.lora_scale_off + s * R;
+        if (int e = gemm_bf16(g, st)) return e;
+      }
+      return 0;
+    };
+    if (l2) {
+      TRY(down(*l2, 0, a.split_row));
+      TRY(down(*lin, a.split_row, a.M - a.split_row));
+    } else {
+      TRY(down(*lin, 0, a.M));
+    }
+    LoraArgs la{T, (const char*)a.W + (int64_t)a.K * 2, R, nseg > 1 ? d.D : a.N, nseg,
+                (uint32_t)lin->lora_mask | (l2 ? (uint32_t)l2->lora_mask << 8 : 0u), planes ? hid_elems : 0};
+    return gemm_bf16_lora(a, la, st);
+  }
+  int run(hipStream_t st) const { return adapted() ? run_lora(st) : gemm_bf16(a, st); }
   bool fp8_ready() const { return lin->w8 && lin->w8_scale && a.K % 256 == 0; }
   // fp8 linear whose activation rows were already quantised by the producer (ln_modulate_fp8)
   int run_pre(hipStream_t st, const void* q, int64_t qld, int64_t qbs, const float* qs, int64_t qs_bs) const {
+    if (adapted()) return fail("dit_forward: runtime LoRA adapters and fp8 linears (flags bit 2) cannot be combined");
     GemmArgs f = a;
     f.A = q; f.lda = qld; f.a_bstride = qbs;
     f.W = lin->w8;
@@ -65,6 +127,7 @@ struct Gemm {
   }
   // fp8 linears (desc.flags bit 2): quantise the activation rows into the q8 workspace, then the e4m3 GEMM
   int run(hipStream_t st, void* q8, float* q8_scale) const {
+    if (adapted()) return q8 ? fail("dit_forward: runtime LoRA adapters and fp8 linears (flags bit 2) cannot be combined") : run_lora(st);
     if (!q8 || !lin->w8 || !lin->w8_scale || a.K % 256) return gemm_bf16(a, st);
     if (int e = quantize_rows_fp8(a.A, a.lda, a.a_bstride, q8, a.K, (int64_t)a.M * a.K, q8_scale, a.M, a.M, a.batch, a.K, st))
       return e;
@@ -75,11 +138,6 @@ struct Gemm {
     return gemm_fp8(f, st);
   }
 };
-
-#define TRY(x)            \
-  do {                    \
-    if (int _e = (x)) return _e; \
-  } while (0)
 
 static int g_fp8_fuse_qkn = 1;    // tfx_set_option fp8_fuse_qkn: 0 = fp8 projections followed by the separate q / k norm + RoPE pass (round 4; A/B knob)
 static int g_ln_joint = 1;        // tfx_set_option ln_joint: 0 = the LayerNorm + modulation of a double block's text and image rows as two launches (A/B knob)
@@ -107,6 +165,8 @@ int dit_forward(const tfx_dit_desc& d, hipStream_t st) {
   void* q8 = (d.flags & 4) ? d.q8 : nullptr;
   float* q8s = (d.flags & 4) ? d.q8_scale : nullptr;
   if ((d.flags & 4) && (!d.q8 || !d.q8_scale)) return fail("dit_forward: fp8 flag set but the q8 workspace is null");
+  const LoraCtx lora_ctx{&d};
+  struct LoraScope { LoraScope(const LoraCtx* c) { g_lora = c; } ~LoraScope() { g_lora = nullptr; } } lora_scope(&lora_ctx);
 
   if (!(d.flags & 1)) {
     // x_embedder (transformer_flux.py:1086) straight into the image rows of the joint stream; text rows <- ctx0
@@ -139,6 +199,7 @@ int dit_forward(const tfx_dit_desc& d, hipStream_t st) {
   // (persistent kernel, enough tiles to fill the chip unsplit; since round 5 in fp8 mode too), else the GEMM followed by the separate pass
   const bool may_fuse = d.rope_cs != nullptr;
   auto fused_here = [&](const Gemm& gm, int row0, const void* nq, const void* nk) -> bool {
+    if (gm.adapted()) return may_fuse;   // the tail launch is never K-sliced: the fused epilogue rides on every adapted projection
     Gemm t = gm;      // with the scratch the launch will have: a GEMM the auto path K-slices cannot carry the fused epilogue
     t.scratch(d.gemm_workspace, d.gemm_workspace_bytes);
     const bool f8 = q8 && gm.fp8_ready();
@@ -182,7 +243,7 @@ int dit_forward(const tfx_dit_desc& d, hipStream_t st) {
           TRY(ln_modulate(hid_img, xn_img, mi, mi + D, mbs, Sn, B, D, D, hid_bs, D, hid_bs, eps, st));
           TRY(ln_modulate(hid, xn, mt, mt + D, mbs, T, B, D, D, hid_bs, D, hid_bs, eps, st));
         }
-        const bool fj = may_fuse && jq.qknorm_ok(w.norm_q, w.norm_k, d.rope_cs, 0, D, eps);
+        const bool fj = may_fuse && (jq.adapted() || jq.qknorm_ok(w.norm_q, w.norm_k, d.rope_cs, 0, D, eps));
         if (fj) jq.qknorm(w.norm_q, w.norm_k, d.rope_cs, 0, D, eps);
         TRY(jq.run(st));
         if (!fj)
@@ -310,6 +371,7 @@ int tfx_gemm_bf16(const tfx_gemm_args* g, int variant, tfx_stream stream) {
   a.gate = g->gate; a.gate_bstride = g->gate_bstride;
   a.res = g->res; a.ldr = g->ldr; a.r_bstride = g->r_bstride;
   a.workspace = g->workspace; a.workspace_bytes = g->workspace_bytes;
+  a.cscale = g->cscale;
   if (!a.A || !a.W || !a.C) return fail("tfx_gemm_bf16: null matrix pointer");
 #ifdef TFX_BENCH
   if (g_bench_qkn.cs) {
@@ -345,6 +407,43 @@ int tfx_gemm_bf16_qkn(const tfx_gemm_args* g, const tfx_qkn_args* q, tfx_stream 
   a.qkn_wq = q->norm_q; a.qkn_wk = q->norm_k; a.qkn_rope_cs = q->rope_cs; a.qkn_pos0 = q->pos0;
   a.qkn_q0 = q->q0; a.qkn_q1 = q->q1; a.qkn_k0 = q->k0; a.qkn_k1 = q->k1; a.qkn_eps = q->eps;
   return gemm_bf16(a, S(stream));     // refuses shapes the fused epilogue cannot take (gemm_qkn_ok)
+}
+
+int tfx_gemm_bf16_lora(const tfx_gemm_args* g, const tfx_qkn_args* q, const tfx_lora_args* l, tfx_stream stream) {
+  if (!g || !l) return fail("tfx_gemm_bf16_lora: null args");
+  if (!g->A || !g->W || !g->C) return fail("tfx_gemm_bf16_lora: null matrix pointer");
+  if (!l->T || !l->Bm) return fail("tfx_gemm_bf16_lora: null adapter operand (T / Bm)");
+  GemmArgs a;
+  a.A = g->A; a.lda = g->lda; a.a_bstride = g->a_bstride;
+  a.W = g->W; a.ldw = g->ldw; a.bias = g->bias; a.w_bstride = g->w_bstride;
+  a.C = g->C; a.ldc = g->ldc; a.c_bstride = g->c_bstride;
+  a.M = g->M; a.N = g->N; a.K = g->K; a.batch = g->batch;
+  a.epilogue = g->epilogue; a.gelu_from_col = g->gelu_from_col;
+  a.gate = g->gate; a.gate_bstride = g->gate_bstride;
+  a.res = g->res; a.ldr = g->ldr; a.r_bstride = g->r_bstride;
+  if (q) {
+    if (!q->norm_q || !q->norm_k || !q->rope_cs) return fail("tfx_gemm_bf16_lora: norm weights and the rotary table are required");
+    if ((uintptr_t)q->norm_q % 16 || (uintptr_t)q->norm_k % 16 || (uintptr_t)q->rope_cs % 16)
+      return fail("tfx_gemm_bf16_lora: norm weights and the rotary table must be 16-byte aligned");
+    if (q->q0 < 0 || q->q1 < q->q0 || q->q1 > g->N || q->k0 < 0 || q->k1 < q->k0 || q->k1 > g->N || q->pos0 < 0)
+      return fail("tfx_gemm_bf16_lora: column ranges outside [0, N)");
+    if (g->epilogue != EPI_BIAS && g->epilogue != EPI_BIAS_GELU) return fail("tfx_gemm_bf16_lora: with q/k norm the epilogue must be 0 (bias) or 1 (bias + GELU from a column)");
+    a.epilogue = EPI_BIAS_GELU;      // as tfx_gemm_bf16_qkn: plain bias = GELU from a column beyond N
+    a.gelu_from_col = g->epilogue == EPI_BIAS_GELU ? g->gelu_from_col : (g->N + 255) / 256 * 256;
+    a.gate = nullptr; a.gate_bstride = 0; a.res = nullptr; a.ldr = 0; a.r_bstride = 0;
+    a.qkn_wq = q->norm_q; a.qkn_wk = q->norm_k; a.qkn_rope_cs = q->rope_cs; a.qkn_pos0 = q->pos0;
+    a.qkn_q0 = q->q0; a.qkn_q1 = q->q1; a.qkn_k0 = q->k0; a.qkn_k1 = q->k1; a.qkn_eps = q->eps;
+  }
+  if (l->split_row > 0) {
+    if (!l->W2) return fail("tfx_gemm_bf16_lora: row-split weights need W2");
+    if (q && ((uintptr_t)l->norm_q2 % 16 || (uintptr_t)l->norm_k2 % 16)) return fail("tfx_gemm_bf16_lora: norm_q2 / norm_k2 must be 16-byte aligned");
+    a.split_row = l->split_row; a.W2 = l->W2; a.bias2 = l->bias2; a.gate2 = l->gate2; a.qkn_wq2 = l->norm_q2; a.qkn_wk2 = l->norm_k2;
+  } else if (l->split_row < 0) {
+    return fail("tfx_gemm_bf16_lora: split_row must not be negative");
+  }
+  if (l->t_seg_stride < 0) return fail("tfx_gemm_bf16_lora: t_seg_stride must not be negative");
+  LoraArgs la{l->T, l->Bm, l->R, l->seg_cols, l->nseg, l->seg_mask, l->t_seg_stride};
+  return gemm_bf16_lora(a, la, S(stream));
 }
 
 int tfx_gemm_bf16_f32(const tfx_gemm_args* g, tfx_stream stream) {
@@ -686,12 +785,18 @@ int tfx_workspace_layout(int32_t B, int32_t Sn, int32_t T, int32_t D, int32_t fl
   off[3] = fp8 ? o : -1; o += q8;
   off[4] = fp8 ? o : -1; o += q8s;
   off[5] = o;
+  if (flags & 8) {   // runtime LoRA adapters: the T scratch behind everything else (tfx_dit_desc.lora_t_xn / lora_t_y)
+    o += gws;
+    off[6] = o; o += (D >= 1024 ? 1 : 4) * hid;
+    off[7] = o;
+  }
   if (gemm_ws_bytes) *gemm_ws_bytes = gws;
   return 0;
 }
 int64_t tfx_workspace_bytes(int32_t B, int32_t Sn, int32_t T, int32_t D, int32_t flags) {
-  int64_t off[6], gws = 0;
+  int64_t off[8], gws = 0;
   if (tfx_workspace_layout(B, Sn, T, D, flags, off, &gws)) return -1;
+  if (flags & 8) return off[7] + ((off[3] >= 0 ? off[3] : off[5]) - off[2]);   // ... + lora_t_y, the size of y
   return off[5] + gws;
 }
 

@@ -76,6 +76,10 @@ struct GemmParams {
   const bf16_t* bias2; const bf16_t* gate2; const bf16_t* nq_w2; const bf16_t* nk_w2;
   // fused per-head RMSNorm + RoPE of the q / k column ranges (QKN kernel instantiation; see GemmArgs)
   const bf16_t* nq_w; const bf16_t* nk_w; const float* rope_cs; int rope_pos0, nq0, nq1, nk0, nk1; float n_eps;
+  // runtime LoRA tail (LORA kernel instantiation; see gemm8pp_kernel and LoraArgs): T lies t_off bytes above A with A's row pitch and
+  // batch stride, the up-projection rows sit in W's rows at columns [K, K + 64 lora_rt)
+  uint32_t t_off, t_seg; int lora_rt, seg_cols, nseg; uint32_t seg_mask;   // t_seg: bytes between the T blocks of two segments
+  const float* cscale;                              // EPI_COLSCALE: per-output-column factor
 };
 
 // ------------------------------------------------------------------------------------------------
@@ -133,6 +137,7 @@ __global__ __launch_bounds__(256) void gemm_generic_kernel(GemmParams p) {
       if (n >= p.N) continue;
       if (p.ws) { p.ws[b * p.ws_bs + (int64_t)m * p.ws_ld + n] = acc[i][j]; continue; }   // fp32-output mode (raw accumulators)
       float v = acc[i][j] + (p.bias ? bf2f(p.bias[n]) : 0.f);
+      if (EPI == EPI_COLSCALE) v = acc[i][j] * p.cscale[n];
       if (EPI == EPI_BIAS_GELU) { if (n >= p.gelu_from) v = gelu_tanh(round_bf(v)); }   // the Linear's bf16 output is what nn.GELU sees (attention.py:1209-1212)
       if (EPI == EPI_BIAS_GATE_RES) {
         const float g = bf2f(p.gate[b * p.gate_bs + n]);
@@ -317,6 +322,12 @@ __device__ __forceinline__ void tile_epilogue(f32x4 (&acc)[8][4], const GemmPara
 #pragma unroll
     for (int d = 0; d < RES_DEPTH; ++d) load_res(d, rr[d]);
   }
+  f32x4 csc[4];           // EPI_COLSCALE: the fp32 factors of this lane's 4 x 4 columns (columns beyond N: zeros, never stored)
+  if constexpr (EPI == EPI_COLSCALE) {
+    const auto rsrcS = uniform_rsrc(p.cscale, p.N * 4);
+#pragma unroll
+    for (int nj = 0; nj < 4; ++nj) csc[nj] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsrcS, (ncol + nj * 16) * 4, 0, 0));
+  }
   const bool in_q = QKN && n0 >= p.nq0 && n0 < p.nq1;
   const bool norm_tile = QKN && (in_q || (n0 >= p.nk0 && n0 < p.nk1));      // block-uniform
   // every operand request of this tile's K loop (incl. the next tile's first K-tiles) is older than the stores below;
@@ -420,7 +431,7 @@ __device__ __forceinline__ void tile_epilogue(f32x4 (&acc)[8][4], const GemmPara
             v[3] = __uint_as_float(p1 & 0xffff0000u) * rinv[mi];
           } else {
 #pragma unroll
-            for (int e = 0; e < 4; ++e) v[e] = acc[mi][nj][e] + bs[e];
+            for (int e = 0; e < 4; ++e) v[e] = EPI == EPI_COLSCALE ? acc[mi][nj][e] * csc[nj][e] : acc[mi][nj][e] + bs[e];
           }
           if (GELU) {   // nn.GELU acts on the Linear's bf16 OUTPUT (activations.py:85-88 after the bf16 nn.Linear): round first
             round_bf2(v[0], v[1]);
@@ -820,7 +831,18 @@ constexpr int PP_LDS_TOTAL = PP_STG + 8 * PP_STG_WAVE;  // 163840 = all of the C
 // output, * weight) and the interleaved-pair RoPE applied in the epilogue, rounding for rounding as rmsnorm_rope_kernel
 // (elementwise.hip) does it after the fact (reference: D/models/attention_processor.py:2001-2037).  A head's 128 columns
 // belong to two waves (column stripes wc, wc ^ 1): their partial sums meet in LDS between two extra barriers per such tile.
-template <int EPI, int PLACE = 2, bool FP8 = false, bool SPLIT = false, bool QKN = false>
+// LORA (runtime, unmerged low-rank adapters: y = epi(x W^T + t B^T + bias), t = bf16(c * x A^T) computed by an earlier launch): the
+// update is a K-EXTENSION of the tile -- after the K / 64 K-tiles of (x, W) the accumulators take lora_rt = R / 64 K-tiles of (t, B)
+// and only then the epilogue runs, so the q / k norm + RoPE epilogue sees the adapted projection.  No second set of request offsets:
+// T has x's row pitch and batch stride and lies t_off bytes above it inside x's descriptor range, one block per segment t_seg bytes
+// apart (R-wide column blocks of one matrix: t_seg = 2 R; or one matrix of x's shape per segment where the row pitch is too short)
+// (segment = a reference Linear's row range of the fused weight, seg_cols output columns each); B's row n is stored behind W's row n
+// (columns [K, K + R) of a weight with row pitch >= K + R).  A tail request therefore differs from a main request only in its SCALAR
+// origin: x side  cur.xoff + t_off + seg * t_seg,  W side  cur.woff + K * 2  (text rows of a row-split launch: w2_off is already in
+// woff, and T's text rows were produced from the text Linear's A).  The tail is a peeled pair per 128 of rank in front of the closing
+// pair (which then consumes the tail's last two K-tiles); tiles whose segment has no adapter (seg_mask bit seg, bit 8 + seg for the
+// text rows) take the plain sequence -- a wave-uniform branch between tiles, never between the K-tiles of the steady-state loop.
+template <int EPI, int PLACE = 2, bool FP8 = false, bool SPLIT = false, bool QKN = false, bool LORA = false>
 __global__ __launch_bounds__(512) void gemm8pp_kernel(GemmParams p) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int tid = threadIdx.x;
@@ -922,10 +944,12 @@ __global__ __launch_bounds__(512) void gemm8pp_kernel(GemmParams p) {
       else srow[q][j] = (uint32_t)(g * 128 + (pc >> 2) * 64 + (q == 2 ? 32 : 0) + (pc & 3) * 8) * (uint32_t)(p.ldw * ESZ);
     }
   // num_records: the operand's extent in bytes (< 2^32, persist_ok)
+  // (LORA: x's range runs on to the end of T's last row, W's rows are lora_rt K-tiles longer)
+  const int kx_end = LORA ? (int)((p.t_off + (uint32_t)(p.nseg - 1) * p.t_seg) >> 1) + p.lora_rt * 64 : p.K, kw_end = LORA ? p.K + p.lora_rt * 64 : p.K;
   const auto rsrcX = __builtin_amdgcn_make_buffer_rsrc(
-      (void*)p.A, 0, (int)(uint32_t)((((int64_t)(p.batch - 1) * p.a_bs + (int64_t)(p.M - 1) * p.lda + p.K) * ESZ)), 0x00020000);
+      (void*)p.A, 0, (int)(uint32_t)((((int64_t)(p.batch - 1) * p.a_bs + (int64_t)(p.M - 1) * p.lda + kx_end) * ESZ)), 0x00020000);
   const auto rsrcW = __builtin_amdgcn_make_buffer_rsrc(
-      (void*)p.W, 0, (int)((uint32_t)((((int64_t)(p.batch - 1) * p.w_bs + (int64_t)(p.N - 1) * p.ldw + p.K) * ESZ)) + (p.split_row > 0 ? p.w2_off : 0u)), 0x00020000);
+      (void*)p.W, 0, (int)((uint32_t)((((int64_t)(p.batch - 1) * p.w_bs + (int64_t)(p.N - 1) * p.ldw + kw_end) * ESZ)) + (p.split_row > 0 ? p.w2_off : 0u)), 0x00020000);
 
   // request item q of K-tile kt of the tile with origins (xo, wo) into buffer set `set`
   auto stage = [&](int q, uint32_t xo, uint32_t wo, int kt, int set) {
@@ -1049,6 +1073,17 @@ __global__ __launch_bounds__(512) void gemm8pp_kernel(GemmParams p) {
     for (int u = u0; u < nt - 2; u += 2) {
       PP_TILE(0, cx, cw, u + 2);
       PP_TILE(1, cx, cw, u + 3);
+    }
+    if constexpr (LORA) {
+      // the low-rank tail: each pair consumes the two K-tiles in LDS (first the main loop's last two) and requests tail K-tiles v, v + 1
+      const int seg = min((int)(cur.n0 >= p.seg_cols) + (int)(cur.n0 >= 2 * p.seg_cols) + (int)(cur.n0 >= 3 * p.seg_cols), p.nseg - 1);
+      if ((p.seg_mask >> (seg + (cur.second ? 8 : 0))) & 1u) {
+        const uint32_t tx = cx + p.t_off + (uint32_t)seg * p.t_seg, tw = cw + (uint32_t)nt * 128u;
+        for (int v = 0; v < p.lora_rt; v += 2) {
+          PP_TILE(0, tx, tw, v);
+          PP_TILE(1, tx, tw, v + 1);
+        }
+      }
     }
     PP_TILE(0, nx, nw, 0);  // K-tiles nt-2, nt-1: their requests are the next tile's K-tiles 0 and 1
     PP_TILE(1, nx, nw, 1);
@@ -1517,6 +1552,11 @@ __global__ __launch_bounds__(256) void tail_reduce_kernel(GemmParams p) {
 #pragma unroll
     for (int e = 0; e < 8; ++e) v[e] = gelu_tanh(round_bf(v[e]));
   }
+  if (EPI == EPI_COLSCALE) {
+    const f32x4 c0 = *reinterpret_cast<const f32x4*>(p.cscale + n), c1 = *reinterpret_cast<const f32x4*>(p.cscale + n + 4);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) { v[e] *= c0[e]; v[4 + e] *= c1[e]; }
+  }
   if (EPI == EPI_BIAS_GATE_RES) {
     float gt[8];
     unpack8(graw, gt);
@@ -1652,6 +1692,8 @@ static GemmParams make_params(const GemmArgs& a) {
   if (a.split_row > 0) p.w2_off = (uint32_t)((const char*)a.W2 - (const char*)a.W);
   p.nq_w = (const bf16_t*)a.qkn_wq; p.nk_w = (const bf16_t*)a.qkn_wk; p.rope_cs = a.qkn_rope_cs; p.rope_pos0 = a.qkn_pos0;
   p.nq0 = a.qkn_q0; p.nq1 = a.qkn_q1; p.nk0 = a.qkn_k0; p.nk1 = a.qkn_k1; p.n_eps = a.qkn_eps;
+  p.t_off = 0; p.t_seg = 0; p.lora_rt = 0; p.seg_cols = 0; p.nseg = 0; p.seg_mask = 0;
+  p.cscale = a.cscale;
   return p;
 }
 
@@ -1866,6 +1908,8 @@ int gemm_bf16_variant(const GemmArgs& a, int variant, hipStream_t st) {
   if (variant >= 1 && !fast_ok(a)) return fail("gemm: shape/alignment not supported by the MFMA kernel");
   if (a.epilogue == EPI_BIAS_GATE_RES && (!a.gate || !a.res)) return fail("gemm: gate/res pointers required");
   if (a.epilogue == EPI_BIAS_RES && !a.res) return fail("gemm: res pointer required");
+  if (a.epilogue == EPI_COLSCALE && (!a.cscale || (uintptr_t)a.cscale % 16 || a.bias || a.split_row > 0))
+    return fail("gemm: the column-scale epilogue needs a 16-byte aligned fp32 cscale vector and takes no bias / row-split weights");
   const GemmParams p = make_params(a);
   if (a.split_row > 0 && !((variant == 1 || variant == 3) && gemm_rowsplit_ok(a))) return fail("gemm: row-split weights need the persistent MFMA kernel");
   switch (a.epilogue) {
@@ -1873,6 +1917,7 @@ int gemm_bf16_variant(const GemmArgs& a, int variant, hipStream_t st) {
     case EPI_BIAS_GELU: return launch_variant<EPI_BIAS_GELU>(p, variant, a.workspace, a.workspace_bytes, st);
     case EPI_BIAS_GATE_RES: return launch_variant<EPI_BIAS_GATE_RES>(p, variant, a.workspace, a.workspace_bytes, st);
     case EPI_BIAS_RES: return launch_variant<EPI_BIAS_RES>(p, variant, a.workspace, a.workspace_bytes, st);
+    case EPI_COLSCALE: return launch_variant<EPI_COLSCALE>(p, variant, a.workspace, a.workspace_bytes, st);
   }
   return fail("gemm: unknown epilogue %d", a.epilogue);
 }
@@ -1912,6 +1957,70 @@ bool gemm_qkn_ok(const GemmArgs& a) {
   if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 8) cus = 256;
   // ... and no K-sliced units in the launch the auto path would make with this workspace (tail_reduce_kernel has no such epilogue)
   return plan_slices(p, cus & ~7, p.K >> 6, a.workspace, a.workspace_bytes).sk == 1;
+}
+
+// ---- runtime LoRA tail (gemm8pp_kernel<.., LORA = true>): C = epi(A W^T + T B^T + bias), one fp32 accumulation.  Always the persistent
+// kernel on WHOLE tiles -- an adapted GEMM is never K-sliced (the tail would have to ride on one slice and tail_reduce_kernel has no
+// q / k-norm epilogue), whatever its tile count; shapes the persistent kernel does not take are refused, there is no fallback.
+template <int EPI, bool QKN>
+static int launch_lora(const GemmParams& p, hipStream_t st) {
+  static int grid = 0;
+  if (!grid) {
+    int dev = 0, cus = 0;
+    (void)hipGetDevice(&dev);
+    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 8) cus = 256;
+    const void* fn = (const void*)gemm8pp_kernel<EPI, 2, false, false, QKN, true>;
+    hipFuncAttributes fa;  // forces the (lazily loaded) code object in before the attribute is set
+    (void)hipFuncGetAttributes(&fa, fn);
+    (void)hipGetLastError();
+    const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, PP_LDS_TOTAL);
+    if (e != hipSuccess) return fail("gemm_lora: cannot raise dynamic LDS limit to %d bytes: %s", PP_LDS_TOTAL, hipGetErrorString(e));
+    grid = cus & ~7;
+  }
+  const bool prof = prof_on(st);
+  if (prof) prof_begin(0, 2.0 * p.M * (double)p.N * (p.K + p.lora_rt * 64) * p.batch, st);
+  gemm8pp_kernel<EPI, 2, false, false, QKN, true><<<grid, 512, PP_LDS_TOTAL, st>>>(p);
+  if (prof) prof_end(0, st);
+  return check_launch("gemm_bf16_lora");
+}
+
+int gemm_bf16_lora(const GemmArgs& a, const LoraArgs& l, hipStream_t st) {
+  if (a.M <= 0 || a.N <= 0 || a.batch <= 0) return 0;
+  if (a.K <= 0) return fail("gemm_lora: K must be positive");
+  if (!fast_ok(a) || a.conv_cin > 0 || a.w_bstride) return fail("gemm_lora: shape/alignment not supported by the persistent MFMA kernel");
+  if (a.epilogue == EPI_BIAS_GATE_RES && (!a.gate || !a.res)) return fail("gemm_lora: gate/res pointers required");
+  if (a.epilogue == EPI_BIAS_RES && !a.res) return fail("gemm_lora: res pointer required");
+  if (a.epilogue == EPI_COLSCALE) return fail("gemm_lora: the column-scale epilogue is the down projection's (tfx_gemm_bf16)");
+  if (l.R < 128 || l.R % 128 || l.R > LORA_MAX_RANK) return fail("gemm_lora: R (the padded rank) must be 128 or 256");
+  if (l.nseg < 1 || l.nseg > 4 || l.seg_cols <= 0 || l.seg_cols % 256) return fail("gemm_lora: 1..4 segments of seg_cols %% 256 == 0 output columns");
+  if ((int64_t)(l.nseg - 1) * l.seg_cols >= a.N) return fail("gemm_lora: segment %d starts beyond N", l.nseg - 1);
+  const uint32_t ok_bits = (1u << l.nseg) - 1u;
+  if (l.seg_mask & ~(ok_bits | (a.split_row > 0 ? ok_bits << 8 : 0u))) return fail("gemm_lora: seg_mask has bits outside its %d segments", l.nseg);
+  // placement (include/textflux_hip.h): T above A inside one 32-bit byte range, addressed with A's pitches; B behind W's rows
+  const int64_t d = (const char*)l.T - (const char*)a.A;
+  if ((uintptr_t)l.T % 16 || d <= 0) return fail("gemm_lora: T must be 16-byte aligned and lie above A");
+  const int64_t t_seg = l.t_seg > 0 ? l.t_seg : l.R;      // elements between the T blocks of two segments
+  if (t_seg == l.R ? (int64_t)l.nseg * l.R > a.lda : (l.R > a.lda || t_seg % 8 || t_seg < (int64_t)(a.batch - 1) * a.a_bstride + (int64_t)(a.M - 1) * a.lda + l.R))
+    return fail("gemm_lora: T's %d blocks of R columns do not fit A's row pitch (or overlap as separate matrices)", l.nseg);
+  if ((const char*)l.Bm != (const char*)a.W + (int64_t)a.K * 2 || a.ldw < (int64_t)a.K + l.R) return fail("gemm_lora: Bm must be W + K with ldw >= K + R");
+  if (a.split_row > 0 && !gemm_rowsplit_ok(a)) return fail("gemm_lora: shape / layout not eligible for row-split weights (gemm_rowsplit_ok)");
+  GemmParams p = make_params(a);
+  if (!persist_ok(p) || d + (l.nseg - 1) * t_seg * 2 + ((int64_t)(p.batch - 1) * p.a_bs + (int64_t)p.tm * 256 * p.lda) * 2 >= (1ll << 32) - 65536)
+    return fail("gemm_lora: K %% 128 == 0 and A, T within one 32-bit byte range are required");
+  p.t_off = (uint32_t)d; p.t_seg = (uint32_t)(t_seg * 2); p.lora_rt = l.R / 64; p.seg_cols = l.seg_cols; p.nseg = l.nseg; p.seg_mask = l.seg_mask;
+  if (a.qkn_rope_cs) {
+    if (a.epilogue != EPI_BIAS_GELU) return fail("gemm_lora: the q/k norm + RoPE epilogue rides on the bias(+GELU) epilogue");
+    if ((a.qkn_q0 | a.qkn_q1 | a.qkn_k0 | a.qkn_k1) % 256 || a.gelu_from_col < (a.qkn_q1 > a.qkn_k1 ? a.qkn_q1 : a.qkn_k1))
+      return fail("gemm_lora: q / k column ranges must be multiples of 256 in front of gelu_from_col");
+    return launch_lora<EPI_BIAS_GELU, true>(p, st);
+  }
+  switch (a.epilogue) {
+    case EPI_BIAS: return launch_lora<EPI_BIAS, false>(p, st);
+    case EPI_BIAS_GELU: return launch_lora<EPI_BIAS_GELU, false>(p, st);
+    case EPI_BIAS_GATE_RES: return launch_lora<EPI_BIAS_GATE_RES, false>(p, st);
+    case EPI_BIAS_RES: return launch_lora<EPI_BIAS_RES, false>(p, st);
+  }
+  return fail("gemm_lora: unknown epilogue %d", a.epilogue);
 }
 
 // The same question for the e4m3 path (gemm_fp8): it slices K only when the whole GEMM has fewer tiles than CUs, so the fused epilogue

@@ -27,6 +27,7 @@ enum Epilogue : int {
   EPI_BIAS_GELU = 1,      // C = gelu_tanh(acc + bias) for columns >= gelu_from_col, plain bias below it
   EPI_BIAS_GATE_RES = 2,  // C = res + gate[b, col] * (acc + bias)
   EPI_BIAS_RES = 3,       // C = res + (acc + bias)   (VAE residual blocks)
+  EPI_COLSCALE = 4,       // C = cscale[col] * acc, cscale fp32 read at run time, no bias (the down projection of a runtime LoRA adapter)
 };
 
 struct GemmArgs {
@@ -65,6 +66,7 @@ struct GemmArgs {
   // sample is below split_row use W2 / bias2 / gate2 / qkn_wq2 / qkn_wk2 instead of W / bias / gate / qkn_wq / qkn_wk -- the text and
   // image projections of a double block in ONE launch over the joint [text | image] rows.  W2 must lie behind W within 4 GiB
   // (one buffer descriptor): the engine allocates the pair as one tensor.
+  const float* cscale = nullptr;                      // EPI_COLSCALE: [N] fp32 device vector, 16-byte aligned
   int split_row = 0;
   const void* W2 = nullptr; const void* bias2 = nullptr; const void* gate2 = nullptr; const void* qkn_wq2 = nullptr; const void* qkn_wk2 = nullptr;
 };
@@ -76,6 +78,15 @@ void set_gemm_splitk(int v);
 int gemm_bf16(const GemmArgs& a, hipStream_t st);            // dispatches fast MFMA kernel or generic fallback
 bool gemm_qkn_ok(const GemmArgs& a);                          // can this GEMM carry the fused q/k norm + RoPE epilogue?
 bool gemm_fp8_qkn_ok(const GemmArgs& a);   // ... for the e4m3 path (gemm_fp8): an unsliced launch, same column conditions
+// Runtime (unmerged) LoRA adapters as a K-extension of the Linear: C = epi(A W^T + T B^T + bias) in ONE fp32 accumulation, T = bf16(c * A Acat^T)
+// from an earlier launch.  T [batch][M, nseg * R] (or nseg matrices [batch][M, R], t_seg) is addressed with A's lda / a_bstride and lies above A inside one 32-bit byte range (the
+// caller owns everything between them); Bm [N, R] = W + K, i.e. columns [K, K + R) of W's rows (ldw >= K + R).  R: padded rank, 128 or 256.
+// Output column n belongs to segment min(n / seg_cols, nseg - 1) and reads T's column block of that index; bit s of seg_mask = segment s
+// carries an adapter (bit 8 + s: for the text rows of a row-split launch).  Persistent kernel, whole tiles only.
+constexpr int LORA_MAX_RANK = 256;
+// t_seg: elements between the T blocks of two segments (0 = R: column blocks of one matrix; else one matrix of A's shape per segment).
+struct LoraArgs { const void* T; const void* Bm; int R, seg_cols, nseg; uint32_t seg_mask; int64_t t_seg = 0; };
+int gemm_bf16_lora(const GemmArgs& a, const LoraArgs& l, hipStream_t st);
 int gemm_bf16_variant(const GemmArgs& a, int variant, hipStream_t st);  // 0 = generic, 1 = MFMA 8-phase
 int gemm_bf16_f32out(const GemmArgs& a, hipStream_t st);     // C = fp32 raw accumulators [batch][M, N] (ldc, c_bstride in floats)
 int mfma_peak_probe(const void* operands, int64_t operand_bytes, int fp8, int ktiles, double* flops, hipStream_t st);   // tfx_mfma_peak_probe

@@ -12,7 +12,7 @@ import torch
 
 from . import _lib as L
 
-EPI_BIAS, EPI_BIAS_GELU, EPI_BIAS_GATE_RES, EPI_BIAS_RES = 0, 1, 2, 3
+EPI_BIAS, EPI_BIAS_GELU, EPI_BIAS_GATE_RES, EPI_BIAS_RES, EPI_COLSCALE = 0, 1, 2, 3, 4
 DEFAULT_ATTENTION = 0      # tfx_set_option("attention_waves", 0): back to the library's default kernel (30 = attn_w4_kernel)
 BF16 = torch.bfloat16
 
@@ -42,10 +42,12 @@ def _rows_view(t: torch.Tensor):
 
 def gemm(a: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None,
          epilogue: int = EPI_BIAS, gelu_from_col: int = 0, gate: Optional[torch.Tensor] = None,
-         res: Optional[torch.Tensor] = None, variant: int = -1, workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
+         res: Optional[torch.Tensor] = None, variant: int = -1, workspace: Optional[torch.Tensor] = None,
+         cscale: Optional[torch.Tensor] = None) -> torch.Tensor:
     """out[b] = epi(a[b] @ w.T + bias).  a: [M,K] or [B,M,K] (row/batch strided views allowed), w: [N,K].
-    workspace: optional device scratch tensor; lets the auto path split K when the GEMM has fewer tiles than CUs."""
-    _chk_dev(a, w, bias, out, gate, res, workspace)
+    workspace: optional device scratch tensor; lets the auto path split K when the GEMM has fewer tiles than CUs.
+    cscale (EPI_COLSCALE): fp32 [N] on the device, out = bf16(cscale * (a @ w.T)), read when the kernel runs."""
+    _chk_dev(a, w, bias, out, gate, res, workspace, cscale)
     assert a.dtype == BF16 and w.dtype == BF16 and w.dim() in (2, 3) and w.stride(-1) == 1
     ap, lda, abs_, M, batch = _rows_view(a)
     N, K = w.shape[-2:]
@@ -71,6 +73,9 @@ def gemm(a: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = None, 
         g.res, g.ldr, g.r_bstride = rp, ldr, rbs
     if workspace is not None:
         g.workspace, g.workspace_bytes = workspace.data_ptr(), workspace.numel() * workspace.element_size()
+    if epilogue == EPI_COLSCALE:
+        assert cscale is not None and cscale.dtype == torch.float32 and cscale.is_contiguous() and cscale.numel() == N
+        g.cscale = cscale.data_ptr()
     L.check(L.lib().tfx_gemm_bf16(C.byref(g), variant, _stream()), "gemm")
     return out
 
@@ -102,6 +107,74 @@ def gemm_qkn(a: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor], nor
     q.norm_q, q.norm_k, q.rope_cs = norm_q.data_ptr(), norm_k.data_ptr(), rope_cs.data_ptr()
     q.pos0, q.q0, q.q1, q.k0, q.k1, q.eps = pos0, q_range[0], q_range[1], k_range[0], k_range[1], eps
     L.check(L.lib().tfx_gemm_bf16_qkn(C.byref(g), C.byref(q), _stream()), "gemm_qkn")
+    return out
+
+
+LORA_MAX_RANK = 256      # padded rank the tail of tfx_gemm_bf16_lora takes (128 or 256)
+
+
+def lora_operands(x: torch.Tensor, t_cols: int):
+    """One allocation [x | T] as tfx_gemm_bf16_lora wants its activations placed: returns (buf, x_view, t_view) with x copied into
+    x_view [.., rows, K]; t_view [.., rows, t_cols] (zeros) shares x_view's row pitch max(K, t_cols) and batch stride and lies above it."""
+    _chk_dev(x)
+    assert x.dtype == BF16 and x.dim() in (2, 3) and t_cols % 8 == 0
+    K = x.shape[-1]
+    buf = torch.zeros(2, *x.shape[:-1], max(K, t_cols), dtype=BF16, device=x.device)
+    buf[0][..., :K].copy_(x)
+    return buf, buf[0][..., :K], buf[1][..., :t_cols]
+
+
+def gemm_lora(a: torch.Tensor, t: torch.Tensor, wb: torch.Tensor, K: int, R: int, seg_cols: int, nseg: int, seg_mask: int,
+              bias: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None, epilogue: int = EPI_BIAS, gelu_from_col: int = 0,
+              gate: Optional[torch.Tensor] = None, res: Optional[torch.Tensor] = None, qkn: Optional[dict] = None,
+              split_row: int = 0, second: Optional[dict] = None, t_seg_stride: int = 0) -> torch.Tensor:
+    """tfx_gemm_bf16_lora: out[b] = epi(a[b] @ W.T + t[b][:, seg block] @ B.T + bias) in one fp32 accumulation.  wb [N, >= K + R] holds
+    W in columns [0, K) and the (zero-padded) up-projection rows B in [K, K + R); t [.., M, nseg * R] shares a's row pitch and batch
+    stride and lies above it (lora_operands); t_seg_stride != 0: t [.., M, R] is segment 0's matrix, segment s's lies s * t_seg_stride
+    elements above it.  qkn: dict(norm_q, norm_k, rope_cs, q_range, k_range, pos0=0, eps=1e-6) for the fused
+    q / k RMSNorm + RoPE epilogue.  split_row / second = dict(wb, bias, gate, norm_q, norm_k): the rows below split_row take the second
+    set, which must live above wb within 4 GiB (one allocation)."""
+    _chk_dev(a, t, wb, bias, out, gate, res)
+    assert a.dtype == BF16 and t.dtype == BF16 and wb.dtype == BF16 and wb.dim() == 2 and wb.stride(1) == 1 and wb.shape[1] >= K + R
+    ap, lda, abs_, M, batch = _rows_view(a)
+    tp, ldt, tbs, Mt, bt = _rows_view(t)
+    assert (ldt, Mt, bt) == (lda, M, batch) and (tbs == abs_ or batch == 1) and a.shape[-1] == K and t.shape[-1] >= (R if t_seg_stride else nseg * R)
+    N = wb.shape[0]
+    if out is None:
+        out = torch.empty(*a.shape[:-1], N, dtype=BF16, device=a.device)
+    cp, ldc, cbs, M2, b2 = _rows_view(out)
+    assert (M2, b2) == (M, batch) and out.shape[-1] == N
+    g = L.GemmArgs()
+    g.A, g.lda, g.a_bstride = ap, lda, abs_
+    g.W, g.ldw, g.bias = wb.data_ptr(), wb.stride(0), _p(bias)
+    g.C, g.ldc, g.c_bstride = cp, ldc, cbs
+    g.M, g.N, g.K, g.batch = M, N, K, batch
+    g.epilogue, g.gelu_from_col = epilogue, gelu_from_col
+    if epilogue in (EPI_BIAS_GATE_RES, EPI_BIAS_RES):
+        assert res is not None
+        if epilogue == EPI_BIAS_GATE_RES:
+            assert gate is not None and gate.stride(-1) == 1
+            g.gate = gate.data_ptr()
+            g.gate_bstride = gate.stride(0) if gate.dim() == 2 else 0
+        rp, ldr, rbs, _, _ = _rows_view(res)
+        g.res, g.ldr, g.r_bstride = rp, ldr, rbs
+    q = None
+    if qkn is not None:
+        q = L.QknArgs()
+        _chk_dev(qkn["norm_q"], qkn["norm_k"], qkn["rope_cs"])
+        assert qkn["rope_cs"].dtype == torch.float32 and qkn["rope_cs"].is_contiguous() and qkn["rope_cs"].shape[0] >= qkn.get("pos0", 0) + M
+        q.norm_q, q.norm_k, q.rope_cs = qkn["norm_q"].data_ptr(), qkn["norm_k"].data_ptr(), qkn["rope_cs"].data_ptr()
+        q.pos0, q.eps = qkn.get("pos0", 0), qkn.get("eps", 1e-6)
+        (q.q0, q.q1), (q.k0, q.k1) = qkn["q_range"], qkn["k_range"]
+    l = L.LoraArgs()
+    l.T, l.Bm, l.R, l.seg_cols, l.nseg, l.seg_mask, l.t_seg_stride = tp, wb.data_ptr() + 2 * K, R, seg_cols, nseg, seg_mask, t_seg_stride
+    if split_row:
+        w2 = second["wb"]
+        _chk_dev(w2, second.get("bias"), second.get("gate"), second.get("norm_q"), second.get("norm_k"))
+        assert w2.dtype == BF16 and w2.shape == wb.shape and w2.stride() == wb.stride()
+        l.split_row, l.W2 = split_row, w2.data_ptr()
+        l.bias2, l.gate2, l.norm_q2, l.norm_k2 = (_p(second.get(k)) for k in ("bias", "gate", "norm_q", "norm_k"))
+    L.check(L.lib().tfx_gemm_bf16_lora(C.byref(g), C.byref(q) if q is not None else None, C.byref(l), _stream()), "gemm_lora")
     return out
 
 

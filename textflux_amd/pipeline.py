@@ -225,13 +225,35 @@ class FluxFillPipeline:
 
     @classmethod
     def load_lora_into_transformer(cls, state_dict, network_alphas, transformer, adapter_name=None, _pipeline=None,
-                                   low_cpu_mem_usage=False):
+                                   low_cpu_mem_usage=False, runtime: bool = False):
+        """runtime=False (default): merge into the fused weights.  runtime=True: attach as an unmerged adapter
+        (FluxTransformer2DModel.attach_lora) whose strength `joint_attention_kwargs={"scale": s}` / set_adapters() change per call."""
         from . import lora
+        if runtime:
+            name = adapter_name or f"default_{len(transformer._adapters)}"        # D/loaders/peft.py: get_adapter_name
+            transformer.attach_lora(name, state_dict, network_alphas)
+            return len({k for k in state_dict if k.endswith(".lora_A.weight")})
         return lora.merge_lora_into_transformer(state_dict, network_alphas, transformer)
 
-    def load_lora_weights(self, path_or_dict, **kwargs):
+    def load_lora_weights(self, path_or_dict, adapter_name=None, runtime: bool = False, **kwargs):
         sd, alphas = self.lora_state_dict(path_or_dict, return_alphas=True, **kwargs)
-        self.load_lora_into_transformer(sd, alphas, self.transformer)
+        self.load_lora_into_transformer(sd, alphas, self.transformer, adapter_name=adapter_name, runtime=runtime)
+
+    # runtime adapters (load_lora_weights(..., runtime=True)): D/loaders/lora_base.py:364-640 forwarded to the transformer
+    def set_adapters(self, adapter_names, adapter_weights=None):
+        self.transformer.set_adapters(adapter_names, adapter_weights)
+
+    def delete_adapters(self, adapter_names):
+        self.transformer.delete_adapters(adapter_names)
+
+    def get_active_adapters(self):
+        return self.transformer.get_active_adapters()
+
+    def unload_lora_weights(self):
+        self.transformer.unload_lora()
+
+    def fuse_lora(self, lora_scale: float = 1.0, **_):
+        self.transformer.fuse_lora(lora_scale)
 
     # ------------------------------------------------------------------ prompt encoding (HIP text encoders, text_encoders.py;
     # any object with the transformers call signature works -- tokenizers are `transformers` objects)
@@ -656,8 +678,27 @@ class FluxFillPipeline:
                           max_sequence_length=max_sequence_length, image=image, mask_image=mask_image,
                           masked_image_latents=masked_image_latents)
         self._guidance_scale, self._joint_attention_kwargs, self._interrupt = guidance_scale, joint_attention_kwargs, False
-        if joint_attention_kwargs is not None and joint_attention_kwargs.get("scale", 1.0) != 1.0:
+        runtime_lora = bool(getattr(self.transformer, "_adapters", None))
+        if joint_attention_kwargs is not None and joint_attention_kwargs.get("scale", 1.0) != 1.0 and not runtime_lora:
             raise NotImplementedError("LoRA is merged at load time in this engine; a runtime `scale` is not supported")
+        # runtime adapters: the call's scale goes into the adapters' factor vector now and the previous one comes back afterwards
+        # (scale_lora_layers / unscale_lora_layers, transformer_flux.py:1073-1079, 1205-1207)
+        lora_scale = joint_attention_kwargs.get("scale") if (runtime_lora and joint_attention_kwargs) else None
+        prev_lora_scale = self.transformer._lora_call_scale if runtime_lora else None
+        if lora_scale is not None:
+            self.transformer._write_scales(lora_scale)
+        try:
+            return self._call_body(prompt, prompt_2, image, mask_image, masked_image_latents, height, width, num_inference_steps,
+                                   sigmas, guidance_scale, num_images_per_prompt, generator, latents, prompt_embeds,
+                                   pooled_prompt_embeds, output_type, return_dict, callback_on_step_end,
+                                   callback_on_step_end_tensor_inputs, max_sequence_length, amo_noise, output_crop)
+        finally:
+            if lora_scale is not None:
+                self.transformer._write_scales(prev_lora_scale)
+
+    def _call_body(self, prompt, prompt_2, image, mask_image, masked_image_latents, height, width, num_inference_steps, sigmas,
+                   guidance_scale, num_images_per_prompt, generator, latents, prompt_embeds, pooled_prompt_embeds, output_type,
+                   return_dict, callback_on_step_end, callback_on_step_end_tensor_inputs, max_sequence_length, amo_noise, output_crop):
         if prompt is not None and isinstance(prompt, str):
             batch_size = 1
         elif prompt is not None and isinstance(prompt, list):

@@ -76,6 +76,12 @@ class FluxTransformer2DModel:
         self.w8: Dict[str, Tuple[torch.Tensor, torch.Tensor]] = {}   # enable_fp8(): name -> (e4m3 bytes [out,in], scale f32 [out])
         self._session: Optional["DitSession"] = None
         self.fuse_qk_norm_rope = True   # q/k RMSNorm + RoPE in the projection GEMM's epilogue where eligible (tfx_dit_desc.rope_cs)
+        # runtime (unmerged) LoRA adapters, see attach_lora(): name -> (state dict, alphas) as loaded; the ACTIVE adapters' weights; the
+        # call scale; and the device state built from them (wide weight copies, stacked A matrices, the fp32 factor vector)
+        self._adapters: Dict[str, Tuple[Dict[str, torch.Tensor], Optional[Dict[str, torch.Tensor]]]] = {}
+        self._adapter_weights: Dict[str, float] = {}
+        self._lora_call_scale = 1.0
+        self._lora: Optional[Dict[str, Any]] = None
         D = self.inner_dim
         self.mod_len = 12 * D * num_layers + 3 * D * num_single_layers + 2 * D
 
@@ -184,6 +190,8 @@ class FluxTransformer2DModel:
             if key in sd:
                 self.w[name].copy_(sd[key].to(BF16))
         self._session = None
+        if self._adapters:
+            self._build_lora(self._adapters)     # the wide [W | Bcat] copies of the adapted Linears follow the new base weights
         return self
 
     def init_random_(self, seed: int = 0, device="cuda", w_std: float = 0.02):
@@ -201,6 +209,8 @@ class FluxTransformer2DModel:
                     e = min(flat.numel(), s + (1 << 26))
                     flat[s:e].copy_((torch.randn(e - s, generator=g, device=t.device) * w_std).to(BF16))
         self._session = None
+        if self._adapters:
+            self._build_lora(self._adapters)
         return self
 
     @classmethod
@@ -276,6 +286,7 @@ class FluxTransformer2DModel:
             self.w8 = {k: (q.to(device), sc.to(device)) for k, (q, sc) in self.w8.items()}
             self.device = torch.device(device)
             self._session = None
+            self._build_lora(self._adapters)
         return self
 
     def eval(self):
@@ -297,6 +308,9 @@ class FluxTransformer2DModel:
         Call after the weights (and any LoRA merge) are final; the bf16 weights stay resident."""
         if not self.w:
             raise RuntimeError("weights not loaded")
+        if on and self._adapters:
+            raise RuntimeError("fp8 linears cannot be enabled while a runtime LoRA adapter is attached (fuse_lora() or "
+                               "unload it first: the e4m3 GEMM has no low-rank tail)")
         self.w8 = {}
         if on:
             for n in self.fp8_linear_names():
@@ -304,6 +318,121 @@ class FluxTransformer2DModel:
                 self.w8[n] = (q, sc)
         self._session = None
         return self
+
+    # ------------------------------------------------------------------ runtime (unmerged) LoRA adapters
+    # Opt-in counterpart of the merge at load (lora.merge_lora_into_transformer stays the default): the adapter is kept next to the
+    # base weights and added inside the block Linears' GEMMs (lora.py "runtime adapters", tfx_gemm_bf16_lora), so its strength can
+    # change per call, and it can be unloaded, swapped or combined with others without re-reading the base weights.  Reference
+    # counterparts: PeftAdapterMixin.load_lora_adapter / set_adapters / delete_adapters / fuse_lora (D/loaders/peft.py:111-700) and
+    # scale_lora_layers (transformer_flux.py:1073-1079).
+    def _build_lora(self, adapters) -> None:
+        """(Re)build the device state of `adapters` (validates before anything changes) and make it current."""
+        from . import lora
+        if not adapters:
+            self._adapters, self._adapter_weights, self._lora, self._session = {}, {}, None, None
+            return
+        if self.w8:
+            raise RuntimeError("runtime LoRA adapters cannot be attached while fp8 linears are enabled (enable_fp8(False) first, or "
+                               "merge the adapter: runtime=False)")
+        if not self.w:
+            raise RuntimeError("weights not loaded")
+        dev = self.device
+        shapes = {k[:-2]: tuple(t.shape) for k, t in self.w.items() if k.endswith(".w")}
+        packs = lora.pack_runtime_adapter(adapters, self._fusion_map(), shapes)
+        partner = lambda n: n[:-3] + ("txt" if n.endswith("img") else "img") if n.endswith(("_img", "_txt")) else None
+        lin, off = {}, 0
+        for name in sorted(set(packs) | {partner(n) for n in packs if partner(n)}):
+            if name in lin:
+                continue
+            group = [name] if partner(name) is None else sorted((name, partner(name)))       # [img, txt]: one allocation, one pitch
+            R = max(packs[n].R for n in group if n in packs)
+            N, K = shapes[group[0]]
+            wide = torch.zeros(len(group), N, K + R, dtype=BF16, device=dev)
+            for gi, n in enumerate(group):
+                wide[gi, :, :K].copy_(self.w[n + ".w"])
+                info = dict(w=wide[gi], ldw=K + R, acat=None, R=R, nseg=0, mask=0, off=0, pack=None)
+                p = packs.get(n)
+                if p is not None:
+                    wide[gi, :, K:K + p.R].copy_(p.Bcat)
+                    acat = torch.zeros(p.nseg, R, K, dtype=BF16, device=dev)
+                    acat[:, :p.R].copy_(p.Acat.view(p.nseg, p.R, K))
+                    info.update(acat=acat.view(p.nseg * R, K), nseg=p.nseg, mask=p.seg_mask, off=off, pack=p)
+                    off += p.nseg * R
+                lin[n] = info
+        self._lora = dict(lin=lin, scale=torch.zeros(max(off, 4), dtype=torch.float32, device=dev))
+        self._adapters = dict(adapters)
+        self._adapter_weights = {n: w for n, w in self._adapter_weights.items() if n in adapters}
+        self._session = None            # descriptors and captured graphs bake the weight / adapter pointers
+        self._write_scales()
+
+    def _write_scales(self, scale: Optional[float] = None) -> None:
+        """Rewrite the fp32 factor vector c = call scale * adapter weight * alpha / r on the current stream: the kernels read it when
+        they run, so neither the session nor a captured step graph changes."""
+        if scale is not None:
+            self._lora_call_scale = float(scale)
+        if self._lora is None:
+            return
+        host = torch.zeros(self._lora["scale"].numel(), dtype=torch.float32)
+        for info in self._lora["lin"].values():
+            p = info["pack"]
+            if p is None:
+                continue
+            c = p.scale_vector(self._adapter_weights, self._lora_call_scale).view(p.nseg, p.R)
+            host[info["off"]:info["off"] + p.nseg * info["R"]].view(p.nseg, info["R"])[:, :p.R] = c
+        self._lora["scale"].copy_(host)
+
+    def attach_lora(self, name: str, state_dict: Dict[str, torch.Tensor], alphas: Optional[Dict[str, torch.Tensor]] = None):
+        """Attach a diffusers / PEFT-format LoRA (lora.lora_state_dict) as runtime adapter `name`, active with weight 1.0."""
+        if name in self._adapters:
+            raise ValueError(f"adapter {name!r} is already attached; delete_adapters({name!r}) first")
+        trial = dict(self._adapters)
+        trial[name] = (dict(state_dict), dict(alphas) if alphas else None)
+        weights = dict(self._adapter_weights)
+        self._adapter_weights[name] = 1.0
+        try:
+            self._build_lora(trial)
+        except Exception:
+            self._adapter_weights = weights
+            raise
+        return self
+
+    def set_adapters(self, adapter_names, weights=None):
+        """The active adapters and their weights (D/loaders/peft.py:352-403): adapters not named contribute nothing."""
+        names = [adapter_names] if isinstance(adapter_names, str) else list(adapter_names)
+        if weights is None or isinstance(weights, (int, float)):
+            weights = [1.0 if weights is None else float(weights)] * len(names)
+        if len(weights) != len(names):
+            raise ValueError(f"{len(names)} adapter names but {len(weights)} weights")
+        unknown = [n for n in names if n not in self._adapters]
+        if unknown:
+            raise ValueError(f"adapters {unknown} are not attached (attached: {sorted(self._adapters)})")
+        self._adapter_weights = {n: 1.0 if w is None else float(w) for n, w in zip(names, weights)}
+        self._write_scales()
+
+    def get_active_adapters(self) -> List[str]:
+        return [n for n in self._adapters if n in self._adapter_weights]
+
+    def delete_adapters(self, adapter_names) -> None:
+        names = [adapter_names] if isinstance(adapter_names, str) else list(adapter_names)
+        unknown = [n for n in names if n not in self._adapters]
+        if unknown:
+            raise ValueError(f"adapters {unknown} are not attached (attached: {sorted(self._adapters)})")
+        self._build_lora({n: v for n, v in self._adapters.items() if n not in names})
+
+    def unload_lora(self) -> None:
+        """Detach every runtime adapter: the compact base weights were never touched, so the model is what it was before."""
+        self._build_lora({})
+        self._lora_call_scale = 1.0
+
+    def fuse_lora(self, lora_scale: float = 1.0) -> None:
+        """Merge the ACTIVE adapters into the base weights at lora_scale * their weight (the merged path's arithmetic:
+        lora.merge_lora_into_transformer), then detach every adapter."""
+        from . import lora
+        active = [(self._adapters[n], self._adapter_weights[n]) for n in self.get_active_adapters()]
+        self._build_lora({})
+        self._lora_call_scale = 1.0
+        for (sd, alphas), w in active:
+            lora.merge_lora_into_transformer(sd, alphas, self, scale=float(lora_scale) * w)
 
     # ------------------------------------------------------------------ conditioning (step-invariant work)
     def _lin(self, x, name, **kw):
@@ -401,7 +530,17 @@ class FluxTransformer2DModel:
         g = (guidance.to(dev, BF16) * 1000).float().expand(B) if guidance is not None else None
         mod = self.modulation(self.temb(t, g, pooled_projections.to(dev, BF16)))
         ses.xin.copy_(hs)
-        out = ses.run(mod).clone()
+        # joint_attention_kwargs["scale"]: the per-call strength of the runtime LoRA adapters (scale_lora_layers / unscale_lora_layers,
+        # transformer_flux.py:1073-1079, 1205-1207); without a runtime adapter there is nothing it could scale
+        scale = (joint_attention_kwargs or {}).get("scale") if self._adapters else None
+        prev = self._lora_call_scale
+        if scale is not None:
+            self._write_scales(scale)
+        try:
+            out = ses.run(mod).clone()
+        finally:
+            if scale is not None:
+                self._write_scales(prev)
         if not return_dict:
             return (out,)
         return SimpleNamespace(sample=out)
@@ -423,8 +562,9 @@ class DitSession:
         self.out = e(B, S, model.out_channels)
         # the engine's workspace is ONE allocation laid out by the library (tfx_workspace_layout): hid | xn | y | q8 | ...
         self.fp8 = bool(model.w8)
-        flags = 4 if self.fp8 else 0
-        off, gws = (C.c_int64 * 6)(), C.c_int64()
+        lora = model._lora              # runtime LoRA adapters: the T scratch rides behind the workspace's usual parts (flags bit 3)
+        flags = (4 if self.fp8 else 0) | (8 if lora else 0)
+        off, gws = (C.c_int64 * 8)(), C.c_int64()
         L.check(L.lib().tfx_workspace_layout(B, S, T, D, flags, off, C.byref(gws)), "workspace_layout")
         total = L.lib().tfx_workspace_bytes(B, S, T, D, flags)
         self.workspace = torch.empty(total, dtype=torch.uint8, device=dev)
@@ -449,6 +589,11 @@ class DitSession:
 
         def lin(name):
             q = w8.get(name)
+            a = lora["lin"].get(name) if lora else None
+            if a is not None:           # adapted (or the partner of an adapted Linear): the wide copy [W | Bcat], see _build_lora
+                return L.Linear(a["w"].data_ptr(), w[name + ".b"].data_ptr(), None, None, a["ldw"],
+                                a["acat"].data_ptr() if a["acat"] is not None else None, a["R"] if a["acat"] is not None else 0,
+                                a["nseg"], a["mask"], a["off"])
             return L.Linear(w[name + ".w"].data_ptr(), w[name + ".b"].data_ptr(), q[0].data_ptr() if q else None,
                             q[1].data_ptr() if q else None)
 
@@ -485,6 +630,11 @@ class DitSession:
         # slices x tiles <= 256 tiles of 256 x 256, i.e. 64 MiB whatever the problem size (the library sizes the scratch at 128 MiB: the attention
         # launches of the blocks put their stream-K partials, 69.2 MB, in the same memory between GEMMs)
         d.gemm_workspace, d.gemm_workspace_bytes = self.gemm_ws.data_ptr(), self.gemm_ws.numel() * 4
+        if lora:
+            self._lora_keepalive = lora         # the descriptor points into its tensors
+            d.lora_t_xn, d.lora_t_y = self.workspace.data_ptr() + off[6], self.workspace.data_ptr() + off[7]
+            d.lora_scale = lora["scale"].data_ptr()
+            self.workspace[off[6]:].zero_()     # rows the down projections never write are read (and multiplied by zero rows of Bcat)
         self.graphs = {}        # (sampler, ...) -> C-level step graph handle (tfx_dit_step_capture)
         self._gb = None
         self._gstream = None    # side stream the step graphs are captured / replayed on
