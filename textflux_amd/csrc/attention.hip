@@ -825,10 +825,8 @@ int joint_attention(const AttnArgs& a, hipStream_t st) {
     return fail("attention: q/k/v must be 16-byte aligned, o 8-byte aligned");
 #ifdef TFX_BENCH
   if (g_attn_waves == 20 && !g_attn_abl) {   // half-tile software-pipelined kernel
-    const bool prof = prof_on(st);
-    if (prof) prof_begin(1, 4.0 * a.B * a.H * (double)a.N * a.N * HD, st);
+    ProfScope prof(1, 4.0 * a.B * a.H * (double)a.N * a.N * HD, st);
     const int rc = joint_attention_hp(a, st);
-    if (prof) prof_end(1, st);
     ++g_attn_mode_count[5];
     return rc ? rc : check_launch("joint_attention");
   }
@@ -845,10 +843,8 @@ int joint_attention(const AttnArgs& a, hipStream_t st) {
   // (tools/dit_ab.py attention_waves=30,40: 481.5 vs 471.1 ms).  Kept selectable, not the default.
 #ifdef TFX_BENCH
   if (g_attn_waves == 40 && w4_ok) {     // same output-store and descriptor constraints as 30
-    const bool prof = prof_on(st);
-    if (prof) prof_begin(1, 4.0 * a.B * a.H * (double)a.N * a.N * HD, st);
+    ProfScope prof(1, 4.0 * a.B * a.H * (double)a.N * a.N * HD, st);
     const int rc = joint_attention_w16(a, st);
-    if (prof) prof_end(1, st);
     ++g_attn_mode_count[6];
     return rc ? rc : check_launch("joint_attention");
   }
@@ -858,8 +854,7 @@ int joint_attention(const AttnArgs& a, hipStream_t st) {
 #else
   if ((g_attn_waves == 30 || g_attn_waves == 34) && w4_ok) {
 #endif
-    const bool prof = prof_on(st);
-    if (prof) prof_begin(1, 4.0 * a.B * a.H * (double)a.N * a.N * HD, st);
+    ProfScope prof(1, 4.0 * a.B * a.H * (double)a.N * a.N * HD, st);
     // 30 (the default) takes the reference-free stream (34) when the caller's score bound allows it (attn_bound_admissible above);
     // an explicit 31 .. 33 runs as named
     const bool bounded = attn_bound_admissible(a.score_bound, a.N);
@@ -870,7 +865,6 @@ int joint_attention(const AttnArgs& a, hipStream_t st) {
     const int mode = bounded && (g_attn_bound || g_attn_waves == 34) ? 4 : 0;    // 30 / 34; the other bookkeeping modes are bench-only
 #endif
     const int rc = joint_attention_w4(a, st, mode);
-    if (prof) prof_end(1, st);
     ++g_attn_mode_count[mode];
     return rc ? rc : check_launch("joint_attention");
   }
@@ -883,35 +877,14 @@ int joint_attention(const AttnArgs& a, hipStream_t st) {
 #else
   const int NW = (g_attn_waves == 16 || g_attn_waves == 9 || g_attn_waves == 10 || g_attn_waves >= 30) ? 8 : g_attn_waves == 12 ? 4 : g_attn_waves;
   const int qblk = NW * 32;
-  static bool attr_set = false;
-  if (!attr_set) {
-    const void* fns[] = {(const void*)attn_kernel<8>, (const void*)attn_mx_kernel<8>,
-#ifdef TFX_BENCH
-                         (const void*)attn_kernel<4>, (const void*)attn_mx_kernel<4>,
-#endif
-    };
-    for (const void* fn : fns) {
-      hipFuncAttributes fa;
-      (void)hipFuncGetAttributes(&fa, fn);
-      (void)hipGetLastError();
-      if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, ATT_LDS) != hipSuccess)
-        return fail("attention: cannot raise dynamic LDS limit");
-    }
-#ifdef TFX_BENCH
-    hipFuncAttributes fa;
-    (void)hipFuncGetAttributes(&fa, (const void*)attn_kernel<8, 0, 2>);
-    (void)hipFuncGetAttributes(&fa, (const void*)attn_pp_kernel<false>);
-    (void)hipGetLastError();
-    if (hipFuncSetAttribute((const void*)attn_kernel<8, 0, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, ATT_LDS2) != hipSuccess ||
-        hipFuncSetAttribute((const void*)attn_pp_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, ATT_LDS_PP) != hipSuccess)
-      return fail("attention: cannot raise dynamic LDS limit (bench variants)");
-#endif
-    attr_set = true;
-  }
+  const int dev = device_facts().dev;
+  if (prepare_kernel<attn_kernel<8>>(dev, ATT_LDS, "attention") || prepare_kernel<attn_mx_kernel<8>>(dev, ATT_LDS, "attention") ||
+      prepare_kernel<attn_kernel<4>>(dev, ATT_LDS, "attention") || prepare_kernel<attn_mx_kernel<4>>(dev, ATT_LDS, "attention") ||
+      prepare_kernel<attn_kernel<8, 0, 2>>(dev, ATT_LDS2, "attention") || prepare_kernel<attn_pp_kernel<false>>(dev, ATT_LDS_PP, "attention"))
+    return 1;     // the message is prepare_kernel's
   const int nqb = (a.N + qblk - 1) / qblk;
   const unsigned grid = (unsigned)(a.B * a.H * nqb);
-  const bool prof = prof_on(st);
-  if (prof) prof_begin(1, 4.0 * a.B * a.H * (double)a.N * a.N * HD, st);
+  ProfScope prof(1, 4.0 * a.B * a.H * (double)a.N * a.N * HD, st);
   const float sl2 = a.scale * 1.4426950408889634f;
 #define ATT_ARGS (const bf16_t*)a.q, (const bf16_t*)a.k, (const bf16_t*)a.v, (bf16_t*)a.o, a.ldq, a.ldk, a.ldv, a.ldo, a.q_bstride, \
                  a.k_bstride, a.v_bstride, a.o_bstride, a.H, a.N, nqb, sl2
@@ -951,7 +924,6 @@ int joint_attention(const AttnArgs& a, hipStream_t st) {
   else                               // exact online maximum
     attn_kernel<8><<<grid, 512, ATT_LDS, st>>>(ATT_ARGS);
 #undef ATT_ARGS
-  if (prof) prof_end(1, st);
   ++g_attn_mode_count[7];
   return check_launch("joint_attention");
 #endif  // TFX_BENCH

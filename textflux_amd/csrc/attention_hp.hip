@@ -337,15 +337,7 @@ __global__ __launch_bounds__(512, 2) void attn_hp_kernel(const bf16_t* Q, const 
 }
 
 int joint_attention_hp(const AttnArgs& a, hipStream_t st) {
-  static bool attr_set = false;
-  if (!attr_set) {
-    hipFuncAttributes fa;
-    (void)hipFuncGetAttributes(&fa, (const void*)attn_hp_kernel);
-    (void)hipGetLastError();
-    if (hipFuncSetAttribute((const void*)attn_hp_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, ATT_LDS_HP) != hipSuccess)
-      return fail("attention: cannot raise dynamic LDS limit to %d bytes", ATT_LDS_HP);
-    attr_set = true;
-  }
+  if (const int rc = prepare_kernel<attn_hp_kernel>(device_facts().dev, ATT_LDS_HP, "attention (attn_hp_kernel)")) return rc;
   const int nqb = (a.N + 255) / 256;
   const unsigned grid = (unsigned)(a.B * a.H * nqb);
   attn_hp_kernel<<<grid, 512, ATT_LDS_HP, st>>>((const bf16_t*)a.q, (const bf16_t*)a.k, (const bf16_t*)a.v, (bf16_t*)a.o, a.ldq,

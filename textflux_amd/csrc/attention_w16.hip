@@ -445,18 +445,11 @@ __global__ __launch_bounds__(256, 1) void attn_w16_kernel(const bf16_t* Q, const
 }
 
 int joint_attention_w16(const AttnArgs& a, hipStream_t st) {
-  static bool attr_set = false;
-  if (!attr_set) {
-    hipFuncAttributes fa;
-    if (hipFuncGetAttributes(&fa, (const void*)attn_w16_kernel) != hipSuccess) return fail("attention: no attn_w16_kernel in this build");
-    (void)hipGetLastError();
-    if (fa.localSizeBytes != 0)
-      return fail("attention: attn_w16_kernel spills %zu bytes per lane -- attention_w16.hip must be compiled with "
-                  "-mllvm -amdgpu-mfma-vgpr-form", (size_t)fa.localSizeBytes);
-    if (hipFuncSetAttribute((const void*)attn_w16_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, ATT_LDS_W16) != hipSuccess)
-      return fail("attention: cannot raise dynamic LDS limit to %d bytes", ATT_LDS_W16);
-    attr_set = true;
-  }
+  const KernelVet no_spills = [](const hipFuncAttributes& fa) {
+    return fa.localSizeBytes == 0 ? 0 : fail("attention: attn_w16_kernel spills %zu bytes per lane -- attention_w16.hip must be compiled with "
+                                             "-mllvm -amdgpu-mfma-vgpr-form", (size_t)fa.localSizeBytes);
+  };
+  if (const int rc = prepare_kernel<attn_w16_kernel>(device_facts().dev, ATT_LDS_W16, "attention (attn_w16_kernel)", no_spills)) return rc;
   const int nqb = (a.N + 255) / 256;
   const unsigned grid = (unsigned)(a.B * a.H * nqb);
   attn_w16_kernel<<<grid, 256, ATT_LDS_W16, st>>>((const bf16_t*)a.q, (const bf16_t*)a.k, (const bf16_t*)a.v, (bf16_t*)a.o, a.ldq,

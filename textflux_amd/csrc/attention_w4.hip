@@ -1196,14 +1196,12 @@ void set_attention_tail_split(int v) { g_w4_split = v; }
 
 // the scratch of (current device, st); allocates it when `may_alloc` (never inside a stream capture)
 static const W4Scratch* w4_scratch(hipStream_t st, bool may_alloc) {
-  int dev = 0;
-  (void)hipGetDevice(&dev);
+  const DeviceFacts dv = device_facts();
   std::lock_guard<std::mutex> lk(g_w4_mu);
   for (int i = 0; i < g_w4_nscr; ++i)
-    if (g_w4_scr[i].dev == dev && g_w4_scr[i].st == st) return &g_w4_scr[i];
+    if (g_w4_scr[i].dev == dv.dev && g_w4_scr[i].st == st) return &g_w4_scr[i];
   if (!may_alloc || g_w4_nscr == W4_PART_SLOTS) return nullptr;
-  W4Scratch s{dev, st, nullptr, 256};
-  if (hipDeviceGetAttribute(&s.cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || s.cus < 8) s.cus = 256;
+  W4Scratch s{dv.dev, st, nullptr, dv.cus};
   if (hipMalloc((void**)&s.part, (size_t)W4_PART_TILES * 256 * W4_PROW * sizeof(float)) != hipSuccess) {
     (void)hipGetLastError();
     return nullptr;
@@ -1241,16 +1239,6 @@ static int g_w4_streamk = 1;
 void set_attention_streamk(int v) { g_w4_streamk = v; }
 static int g_w4_persist = 1;     // tfx_set_option attention_persistent: 0 = one workgroup per (b, h, q-tile) item (round 3)
 void set_attention_persistent(int v) { g_w4_persist = v; }
-static int g_w4_grid() {         // workgroups of the persistent form: one per CU, a whole number per XCD
-  static int grid = 0;
-  if (!grid) {
-    int dev = 0, cus = 0;
-    (void)hipGetDevice(&dev);
-    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 8) cus = 256;
-    grid = cus & ~7;
-  }
-  return grid;
-}
 
 #ifdef TFX_BENCH
 extern "C" void tfx_bench_attn_timers(unsigned long long* dev) {
@@ -1259,33 +1247,27 @@ extern "C" void tfx_bench_attn_timers(unsigned long long* dev) {
 #endif
 
 template <int MODE>
-static int w4_launch(const AttnArgs& a, hipStream_t st, unsigned grid, int nqb, int nfull, int nparts, int nsplit, int xsplit, float* part,
-                     int sk_group, int sk_share) {
-  static bool attr_set = false;
-  const void* fn = (const void*)attn_w4_kernel<MODE>;
-  if (!attr_set) {
-    hipFuncAttributes fa;
-    if (hipFuncGetAttributes(&fa, fn) != hipSuccess) return fail("attention: no attn_w4_kernel<%d> in this build", MODE);
-    (void)hipGetLastError();
-    // built without -mllvm -amdgpu-mfma-vgpr-form (see Makefile) the accumulators land in the AccVGPRs and ~500 registers spill
-    if (fa.localSizeBytes != 0)
-      return fail("attention: attn_w4_kernel<%d> spills %zu bytes per lane -- attention_w4.hip must be compiled with "
-                  "-mllvm -amdgpu-mfma-vgpr-form", MODE, (size_t)fa.localSizeBytes);
-    if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, ATT_LDS_W4 + ((W4_ABL & 256) ? 4096 : 0)) != hipSuccess)
-      return fail("attention: cannot raise dynamic LDS limit to %d bytes", ATT_LDS_W4);
-    attr_set = true;
-  }
+static int w4_launch(const AttnArgs& a, hipStream_t st, unsigned grid, const DeviceFacts& dv, int nqb, int nfull, int nparts, int nsplit, int xsplit,
+                     float* part, int sk_group, int sk_share) {
+  constexpr int lds = ATT_LDS_W4 + ((W4_ABL & 256) ? 4096 : 0);
+  // built without -mllvm -amdgpu-mfma-vgpr-form (see Makefile) the accumulators land in the AccVGPRs and ~500 registers spill
+  const KernelVet no_spills = [](const hipFuncAttributes& fa) {
+    return fa.localSizeBytes == 0 ? 0 : fail("attention: attn_w4_kernel<%d> spills %zu bytes per lane -- attention_w4.hip must be compiled with "
+                                             "-mllvm -amdgpu-mfma-vgpr-form", MODE, (size_t)fa.localSizeBytes);
+  };
+  if (const int rc = prepare_kernel<attn_w4_kernel<MODE>>(dv.dev, lds, "attention (attn_w4_kernel)", no_spills)) return rc;
+  const int pgrid = dv.grid;     // workgroups of the persistent form: one per CU, a whole number per XCD
   // persistent form: one workgroup per CU over all (b, h, q-tile) items, when there are more items than CUs and no tail split
   int T_items = 0;
   if (sk_share > 0) {            // stream-K: one workgroup per CU, T_items = items of one sample, nfull = samples
     T_items = a.H * nqb;
     nfull = a.B;
-    grid = (unsigned)g_w4_grid();
-  } else if (g_w4_persist && nsplit == 1 && (int)grid > g_w4_grid()) {
+    grid = (unsigned)pgrid;
+  } else if (g_w4_persist && nsplit == 1 && (int)grid > pgrid) {
     T_items = (int)grid;
-    grid = (unsigned)g_w4_grid();
+    grid = (unsigned)pgrid;
   }
-  attn_w4_kernel<MODE><<<grid, 256, ATT_LDS_W4 + ((W4_ABL & 256) ? 4096 : 0), st>>>((const bf16_t*)a.q, (const bf16_t*)a.k, (const bf16_t*)a.v, (bf16_t*)a.o, a.ldq,
+  attn_w4_kernel<MODE><<<grid, 256, lds, st>>>((const bf16_t*)a.q, (const bf16_t*)a.k, (const bf16_t*)a.v, (bf16_t*)a.o, a.ldq,
                                                        a.ldk, a.ldv, a.ldo, a.q_bstride, a.k_bstride, a.v_bstride, a.o_bstride, a.H,
                                                        a.N, nqb, a.scale * 1.4426950408889634f, nfull, nparts, nsplit, xsplit, part, T_items, sk_group, sk_share);
   return 0;
@@ -1322,8 +1304,10 @@ int joint_attention_w4(const AttnArgs& a, hipStream_t st, int mode) {
   // floor(Tp / group) (nkv + F) + share + (share / nkv + 1) F + M -- F = an item's prologue + output (tools/attn_item_timers.py: 6 - 9 tile
   // times), M = the partial stores, the merge pass (10 - 12 us) and the gap in front of it.  A piece count per item <= 8 (attn_w4_merge_sk_kernel) needs share >= nkv / 6.
   int sk_group = 0, sk_share = 0;
-  if (g_w4_streamk && g_w4_persist && nsplit == 1 && a.workspace && a.B <= g_w4_grid()) {
-    const int C = g_w4_grid(), nkv = (a.N + W4_KV - 1) / W4_KV, Tp = a.H * nqb, group = C / a.B;
+  const DeviceFacts dv = device_facts();
+  const int pgrid = dv.grid;
+  if (g_w4_streamk && g_w4_persist && nsplit == 1 && a.workspace && a.B <= pgrid) {
+    const int C = pgrid, nkv = (a.N + W4_KV - 1) / W4_KV, Tp = a.H * nqb, group = C / a.B;
     const int full = (Tp / group) * group, R = Tp - full;
     const int share = R ? (R * nkv + group - 1) / group : 0;
     const int64_t need = (int64_t)2 * a.B * group * 256 * W4_PROW * (int64_t)sizeof(float);
@@ -1337,15 +1321,15 @@ int joint_attention_w4(const AttnArgs& a, hipStream_t st, int mode) {
   }
   const unsigned grid = nsplit > 1 ? (unsigned)(((nfull + 7) & ~7) + nparts) : (unsigned)T;
 #ifdef TFX_BENCH
-  const int rc = mode == 4 ? w4_launch<4>(a, st, grid, nqb, nfull, nparts, nsplit, xsplit, part, sk_group, sk_share)
-               : mode == 3 ? w4_launch<3>(a, st, grid, nqb, nfull, nparts, nsplit, xsplit, part, sk_group, sk_share)
-               : mode == 2 ? w4_launch<2>(a, st, grid, nqb, nfull, nparts, nsplit, xsplit, part, sk_group, sk_share)
-               : mode == 1 ? w4_launch<1>(a, st, grid, nqb, nfull, nparts, nsplit, xsplit, part, sk_group, sk_share)
-                           : w4_launch<0>(a, st, grid, nqb, nfull, nparts, nsplit, xsplit, part, sk_group, sk_share);
+  const int rc = mode == 4 ? w4_launch<4>(a, st, grid, dv, nqb, nfull, nparts, nsplit, xsplit, part, sk_group, sk_share)
+               : mode == 3 ? w4_launch<3>(a, st, grid, dv, nqb, nfull, nparts, nsplit, xsplit, part, sk_group, sk_share)
+               : mode == 2 ? w4_launch<2>(a, st, grid, dv, nqb, nfull, nparts, nsplit, xsplit, part, sk_group, sk_share)
+               : mode == 1 ? w4_launch<1>(a, st, grid, dv, nqb, nfull, nparts, nsplit, xsplit, part, sk_group, sk_share)
+                           : w4_launch<0>(a, st, grid, dv, nqb, nfull, nparts, nsplit, xsplit, part, sk_group, sk_share);
 #else   // product library: the reference-free stream and the guarded form; modes 1 .. 3 are A/B builds (round 4), bench library only
   if (mode != 4 && mode != 0) return fail("attention: attn_w4_kernel<%d> is bench-only (libtextflux_hip_bench.so)", mode);
-  const int rc = mode == 4 ? w4_launch<4>(a, st, grid, nqb, nfull, nparts, nsplit, xsplit, part, sk_group, sk_share)
-                           : w4_launch<0>(a, st, grid, nqb, nfull, nparts, nsplit, xsplit, part, sk_group, sk_share);
+  const int rc = mode == 4 ? w4_launch<4>(a, st, grid, dv, nqb, nfull, nparts, nsplit, xsplit, part, sk_group, sk_share)
+                           : w4_launch<0>(a, st, grid, dv, nqb, nfull, nparts, nsplit, xsplit, part, sk_group, sk_share);
 #endif
   if (rc) return rc;
   if (sk_share > 0) attention_note_streamk();

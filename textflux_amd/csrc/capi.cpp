@@ -360,8 +360,9 @@ static struct { const void* wq; const void* wk; const float* cs; int D; } g_benc
 extern "C" void tfx_bench_gemm_qkn(const void* wq, const void* wk, const float* cs, int D) { g_bench_qkn = {wq, wk, cs, D}; }
 #endif
 
-int tfx_gemm_bf16(const tfx_gemm_args* g, int variant, tfx_stream stream) {
-  if (!g) return fail("tfx_gemm_bf16: null args");
+// The one tfx_gemm_args -> GemmArgs conversion: every field of the public struct.  Entry points whose launcher must not see a field
+// reset it afterwards (and say why); everything GemmArgs has beyond the public struct keeps its default.
+static GemmArgs gemm_args(const tfx_gemm_args* g) {
   GemmArgs a;
   a.A = g->A; a.lda = g->lda; a.a_bstride = g->a_bstride;
   a.W = g->W; a.ldw = g->ldw; a.bias = g->bias; a.w_bstride = g->w_bstride;
@@ -372,6 +373,31 @@ int tfx_gemm_bf16(const tfx_gemm_args* g, int variant, tfx_stream stream) {
   a.res = g->res; a.ldr = g->ldr; a.r_bstride = g->r_bstride;
   a.workspace = g->workspace; a.workspace_bytes = g->workspace_bytes;
   a.cscale = g->cscale;
+  return a;
+}
+
+// Validates a tfx_qkn_args against the GEMM it rides on and attaches it.  The fused epilogue is an instantiation of the bias + GELU
+// kernel (norm tiles and GELU tiles are separate straight-line paths): plain bias = GELU from a column beyond N, as tfx_dit_forward
+// passes it; it takes neither gate nor residual.
+static int attach_qkn(const char* who, GemmArgs& a, const tfx_qkn_args* q) {
+  if (!q->norm_q || !q->norm_k || !q->rope_cs) return fail("%s: norm weights and the rotary table are required", who);
+  if ((uintptr_t)q->norm_q % 16 || (uintptr_t)q->norm_k % 16 || (uintptr_t)q->rope_cs % 16)
+    return fail("%s: norm weights and the rotary table must be 16-byte aligned", who);
+  if (q->q0 < 0 || q->q1 < q->q0 || q->q1 > a.N || q->k0 < 0 || q->k1 < q->k0 || q->k1 > a.N || q->pos0 < 0)
+    return fail("%s: column ranges outside [0, N)", who);
+  if (a.epilogue != EPI_BIAS && a.epilogue != EPI_BIAS_GELU)
+    return fail("%s: with q/k norm the epilogue must be 0 (bias) or 1 (bias + GELU from a column)", who);
+  if (a.epilogue == EPI_BIAS) a.gelu_from_col = (a.N + 255) / 256 * 256;
+  a.epilogue = EPI_BIAS_GELU;
+  a.gate = nullptr; a.gate_bstride = 0; a.res = nullptr; a.ldr = 0; a.r_bstride = 0;
+  a.qkn_wq = q->norm_q; a.qkn_wk = q->norm_k; a.qkn_rope_cs = q->rope_cs; a.qkn_pos0 = q->pos0;
+  a.qkn_q0 = q->q0; a.qkn_q1 = q->q1; a.qkn_k0 = q->k0; a.qkn_k1 = q->k1; a.qkn_eps = q->eps;
+  return 0;
+}
+
+int tfx_gemm_bf16(const tfx_gemm_args* g, int variant, tfx_stream stream) {
+  if (!g) return fail("tfx_gemm_bf16: null args");
+  GemmArgs a = gemm_args(g);
   if (!a.A || !a.W || !a.C) return fail("tfx_gemm_bf16: null matrix pointer");
 #ifdef TFX_BENCH
   if (g_bench_qkn.cs) {
@@ -387,25 +413,9 @@ int tfx_gemm_bf16(const tfx_gemm_args* g, int variant, tfx_stream stream) {
 int tfx_gemm_bf16_qkn(const tfx_gemm_args* g, const tfx_qkn_args* q, tfx_stream stream) {
   if (!g || !q) return fail("tfx_gemm_bf16_qkn: null args");
   if (!g->A || !g->W || !g->C) return fail("tfx_gemm_bf16_qkn: null matrix pointer");
-  if (!q->norm_q || !q->norm_k || !q->rope_cs) return fail("tfx_gemm_bf16_qkn: norm weights and the rotary table are required");
-  if ((uintptr_t)q->norm_q % 16 || (uintptr_t)q->norm_k % 16 || (uintptr_t)q->rope_cs % 16)
-    return fail("tfx_gemm_bf16_qkn: norm weights and the rotary table must be 16-byte aligned");
-  if (q->q0 < 0 || q->q1 < q->q0 || q->q1 > g->N || q->k0 < 0 || q->k1 < q->k0 || q->k1 > g->N || q->pos0 < 0)
-    return fail("tfx_gemm_bf16_qkn: column ranges outside [0, N)");
-  GemmArgs a;
-  a.A = g->A; a.lda = g->lda; a.a_bstride = g->a_bstride;
-  a.W = g->W; a.ldw = g->ldw; a.bias = g->bias; a.w_bstride = g->w_bstride;
-  a.C = g->C; a.ldc = g->ldc; a.c_bstride = g->c_bstride;
-  a.M = g->M; a.N = g->N; a.K = g->K; a.batch = g->batch;
-  if (g->epilogue != EPI_BIAS && g->epilogue != EPI_BIAS_GELU) return fail("tfx_gemm_bf16_qkn: epilogue must be 0 (bias) or 1 (bias + GELU from a column)");
-  // the fused epilogue is an instantiation of the bias + GELU kernel (norm tiles and GELU tiles are separate straight-line paths): plain
-  // bias = GELU from a column beyond N, as tfx_dit_forward passes it
-  a.epilogue = EPI_BIAS_GELU;
-  a.gelu_from_col = g->epilogue == EPI_BIAS_GELU ? g->gelu_from_col : (g->N + 255) / 256 * 256;
-  a.gate = nullptr; a.gate_bstride = 0; a.res = nullptr; a.ldr = 0; a.r_bstride = 0;
-  a.workspace = g->workspace; a.workspace_bytes = g->workspace_bytes;
-  a.qkn_wq = q->norm_q; a.qkn_wk = q->norm_k; a.qkn_rope_cs = q->rope_cs; a.qkn_pos0 = q->pos0;
-  a.qkn_q0 = q->q0; a.qkn_q1 = q->q1; a.qkn_k0 = q->k0; a.qkn_k1 = q->k1; a.qkn_eps = q->eps;
+  GemmArgs a = gemm_args(g);
+  a.cscale = nullptr;                 // the column-scale epilogue is not one this entry point admits
+  if (const int rc = attach_qkn("tfx_gemm_bf16_qkn", a, q)) return rc;
   return gemm_bf16(a, S(stream));     // refuses shapes the fused epilogue cannot take (gemm_qkn_ok)
 }
 
@@ -413,27 +423,11 @@ int tfx_gemm_bf16_lora(const tfx_gemm_args* g, const tfx_qkn_args* q, const tfx_
   if (!g || !l) return fail("tfx_gemm_bf16_lora: null args");
   if (!g->A || !g->W || !g->C) return fail("tfx_gemm_bf16_lora: null matrix pointer");
   if (!l->T || !l->Bm) return fail("tfx_gemm_bf16_lora: null adapter operand (T / Bm)");
-  GemmArgs a;
-  a.A = g->A; a.lda = g->lda; a.a_bstride = g->a_bstride;
-  a.W = g->W; a.ldw = g->ldw; a.bias = g->bias; a.w_bstride = g->w_bstride;
-  a.C = g->C; a.ldc = g->ldc; a.c_bstride = g->c_bstride;
-  a.M = g->M; a.N = g->N; a.K = g->K; a.batch = g->batch;
-  a.epilogue = g->epilogue; a.gelu_from_col = g->gelu_from_col;
-  a.gate = g->gate; a.gate_bstride = g->gate_bstride;
-  a.res = g->res; a.ldr = g->ldr; a.r_bstride = g->r_bstride;
-  if (q) {
-    if (!q->norm_q || !q->norm_k || !q->rope_cs) return fail("tfx_gemm_bf16_lora: norm weights and the rotary table are required");
-    if ((uintptr_t)q->norm_q % 16 || (uintptr_t)q->norm_k % 16 || (uintptr_t)q->rope_cs % 16)
-      return fail("tfx_gemm_bf16_lora: norm weights and the rotary table must be 16-byte aligned");
-    if (q->q0 < 0 || q->q1 < q->q0 || q->q1 > g->N || q->k0 < 0 || q->k1 < q->k0 || q->k1 > g->N || q->pos0 < 0)
-      return fail("tfx_gemm_bf16_lora: column ranges outside [0, N)");
-    if (g->epilogue != EPI_BIAS && g->epilogue != EPI_BIAS_GELU) return fail("tfx_gemm_bf16_lora: with q/k norm the epilogue must be 0 (bias) or 1 (bias + GELU from a column)");
-    a.epilogue = EPI_BIAS_GELU;      // as tfx_gemm_bf16_qkn: plain bias = GELU from a column beyond N
-    a.gelu_from_col = g->epilogue == EPI_BIAS_GELU ? g->gelu_from_col : (g->N + 255) / 256 * 256;
-    a.gate = nullptr; a.gate_bstride = 0; a.res = nullptr; a.ldr = 0; a.r_bstride = 0;
-    a.qkn_wq = q->norm_q; a.qkn_wk = q->norm_k; a.qkn_rope_cs = q->rope_cs; a.qkn_pos0 = q->pos0;
-    a.qkn_q0 = q->q0; a.qkn_q1 = q->q1; a.qkn_k0 = q->k0; a.qkn_k1 = q->k1; a.qkn_eps = q->eps;
-  }
+  GemmArgs a = gemm_args(g);
+  a.workspace = nullptr; a.workspace_bytes = 0;   // an adapted GEMM is never K-sliced
+  a.cscale = nullptr;                             // gemm_bf16_lora refuses the column-scale epilogue
+  if (q)
+    if (const int rc = attach_qkn("tfx_gemm_bf16_lora", a, q)) return rc;
   if (l->split_row > 0) {
     if (!l->W2) return fail("tfx_gemm_bf16_lora: row-split weights need W2");
     if (q && ((uintptr_t)l->norm_q2 % 16 || (uintptr_t)l->norm_k2 % 16)) return fail("tfx_gemm_bf16_lora: norm_q2 / norm_k2 must be 16-byte aligned");
@@ -449,29 +443,21 @@ int tfx_gemm_bf16_lora(const tfx_gemm_args* g, const tfx_qkn_args* q, const tfx_
 int tfx_gemm_bf16_f32(const tfx_gemm_args* g, tfx_stream stream) {
   if (!g) return fail("tfx_gemm_bf16_f32: null args");
   if (!g->A || !g->W || !g->C) return fail("tfx_gemm_bf16_f32: null matrix pointer");
-  GemmArgs a;
-  a.A = g->A; a.lda = g->lda; a.a_bstride = g->a_bstride;
-  a.W = g->W; a.ldw = g->ldw; a.bias = g->bias; a.w_bstride = g->w_bstride;
-  a.C = g->C; a.ldc = g->ldc; a.c_bstride = g->c_bstride;
-  a.M = g->M; a.N = g->N; a.K = g->K; a.batch = g->batch;
-  a.epilogue = g->epilogue; a.gelu_from_col = 0;
+  GemmArgs a = gemm_args(g);
+  // raw accumulators: gemm_bf16_f32out admits the plain epilogue only, and its fast_ok() looks at gelu_from_col / gate / res solely
+  // under the other epilogues -- reset all the same, with the workspace it never K-slices into and the scale vector of an epilogue it refuses
+  a.gelu_from_col = 0;
   a.gate = nullptr; a.gate_bstride = 0; a.res = nullptr; a.ldr = 0; a.r_bstride = 0;
+  a.workspace = nullptr; a.workspace_bytes = 0; a.cscale = nullptr;
   return gemm_bf16_f32out(a, S(stream));
 }
 
 int tfx_gemm_fp8(const tfx_gemm_args* g, const float* a_scale, int64_t a_scale_bstride, const float* w_scale,
                  tfx_stream stream) {
   if (!g) return fail("tfx_gemm_fp8: null args");
-  GemmArgs a;
-  a.A = g->A; a.lda = g->lda; a.a_bstride = g->a_bstride;
-  a.W = g->W; a.ldw = g->ldw; a.bias = g->bias; a.w_bstride = g->w_bstride;
-  a.C = g->C; a.ldc = g->ldc; a.c_bstride = g->c_bstride;
-  a.M = g->M; a.N = g->N; a.K = g->K; a.batch = g->batch;
-  a.epilogue = g->epilogue; a.gelu_from_col = g->gelu_from_col;
-  a.gate = g->gate; a.gate_bstride = g->gate_bstride;
-  a.res = g->res; a.ldr = g->ldr; a.r_bstride = g->r_bstride;
+  GemmArgs a = gemm_args(g);
+  a.cscale = nullptr;                 // gemm_fp8 has no column-scale epilogue (it reports 4 as unknown)
   a.a_scale = a_scale; a.a_scale_bstride = a_scale_bstride; a.w_scale = w_scale;
-  a.workspace = g->workspace; a.workspace_bytes = g->workspace_bytes;
   if (!a.A || !a.W || !a.C) return fail("tfx_gemm_fp8: null matrix pointer");
   return gemm_fp8(a, S(stream));
 }

@@ -38,6 +38,7 @@
 // is waited for by its issuer (vmcnt(8): the 4 newest sections may still be in flight), then one barrier -> readable.
 // See DESIGN.md "GEMM".
 #include <algorithm>
+#include <atomic>
 #include <type_traits>
 
 #include "common.h"
@@ -1635,14 +1636,20 @@ __global__ __launch_bounds__(512) void mfma_probe_kernel(const u32x4* __restrict
   if (r == 123456.789f) sink[0] = r;     // keeps the accumulators live; (practically) never taken
 }
 
+static std::atomic<float*> g_probe_sink[MAX_DEVICES];   // per device: 4 bytes, never written in practice (the kernel needs a live side effect)
 int mfma_peak_probe(const void* operands, int64_t operand_bytes, int fp8, int ktiles, double* flops, hipStream_t st) {
   if (!operands || (uintptr_t)operands % 16 || operand_bytes < 16 * 64 * 16) return fail("mfma_peak_probe: operands must be a 16-byte aligned buffer of at least 16 KiB");
   if (ktiles < 48 || ktiles % 48) return fail("mfma_peak_probe: ktiles must be a positive multiple of 48");
-  int dev = 0, cus = 0;
-  (void)hipGetDevice(&dev);
-  if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 8) cus = 256;
-  static float* sink = nullptr;      // 4 bytes, never written in practice (the kernel needs a live side effect)
-  if (!sink && hipMalloc((void**)&sink, 256) != hipSuccess) return fail("mfma_peak_probe: hipMalloc failed");
+  const DeviceFacts dv = device_facts();
+  const int cus = dv.cus;
+  if (dv.dev < 0 || dv.dev >= MAX_DEVICES) return fail("mfma_peak_probe: device ordinal %d is beyond the %d the probe keeps a sink for", dv.dev, MAX_DEVICES);
+  float* sink = g_probe_sink[dv.dev].load(std::memory_order_acquire);
+  if (!sink) {
+    float* fresh = nullptr;
+    if (hipMalloc((void**)&fresh, 256) != hipSuccess) return fail("mfma_peak_probe: hipMalloc failed");
+    if (g_probe_sink[dv.dev].compare_exchange_strong(sink, fresh, std::memory_order_acq_rel)) sink = fresh;
+    else (void)hipFree(fresh);       // another thread was first: `sink` now holds its buffer
+  }
   const int nfrag = (int)std::min<int64_t>(operand_bytes / 16, 1 << 30);
   if (fp8) mfma_probe_kernel<true><<<cus, 512, 0, st>>>((const u32x4*)operands, nfrag, ktiles, sink);
   else mfma_probe_kernel<false><<<cus, 512, 0, st>>>((const u32x4*)operands, nfrag, ktiles, sink);
@@ -1752,11 +1759,58 @@ static SlicePlan plan_slices(const GemmParams& p, int grid, int nt, void* ws, in
   return pl;
 }
 
+// ---- the launchers of the MFMA kernels: prepare_kernel (dynamic LDS limit, per device), then the launch.  The caller checks the launch
+// (check_launch) after the last kernel of its sequence.
+template <auto K>
+static int launch_lds(const char* family, int dev, unsigned grid, unsigned threads, int lds, const GemmParams& p, hipStream_t st) {
+  if (const int rc = prepare_kernel<K>(dev, lds, family)) return rc;
+  K<<<grid, threads, lds, st>>>(p);
+  return 0;
+}
+// a gemm8pp_kernel instantiation: one 512-thread workgroup with 160 KiB of LDS per CU of the current device, a whole number per XCD
+template <auto K>
+static int launch_persistent(const char* family, const DeviceFacts& dv, const GemmParams& p, hipStream_t st) {
+  return launch_lds<K>(family, dv.dev, (unsigned)dv.grid, 512, PP_LDS_TOTAL, p, st);
+}
+// a gemm8p_kernel instantiation: one workgroup per 256 x 256 output tile
+template <auto K>
+static int launch_one_tile(const char* family, const GemmParams& p, hipStream_t st) {
+  return launch_lds<K>(family, device_facts().dev, (unsigned)(p.batch * p.tm * p.tn), 512, LDS_TOTAL, p, st);
+}
+static double gemm_flops(const GemmParams& p) { return 2.0 * p.M * (double)p.N * (p.K + p.lora_rt * 64) * p.batch; }
+
+// ---- argument checks shared by the bf16, LoRA and fp8 entry points (`who` prefixes the message)
+static int check_gate_res(const char* who, const GemmArgs& a) {
+  if (a.epilogue == EPI_BIAS_GATE_RES && (!a.gate || !a.res)) return fail("%s: gate/res pointers required", who);
+  if (a.epilogue == EPI_BIAS_RES && !a.res) return fail("%s: res pointer required", who);
+  return 0;
+}
+// the fused q/k norm + RoPE epilogue: whole heads per tile pair (column ranges on 256-column tile boundaries), and the normalised
+// columns carry no activation (the epilogue instantiates norm and GELU tiles separately)
+static bool qk_ranges_ok(const GemmArgs& a) {
+  if ((a.qkn_q0 | a.qkn_q1 | a.qkn_k0 | a.qkn_k1) % 256) return false;
+  return a.epilogue != EPI_BIAS_GELU || a.gelu_from_col >= (a.qkn_q1 > a.qkn_k1 ? a.qkn_q1 : a.qkn_k1);
+}
+// runtime epilogue -> template argument: f(std::integral_constant<int, EPI>).  COLSCALE = false for the callers without kernels for
+// the column-scale epilogue (they refuse it, or report it as unknown).
+template <bool COLSCALE, class F>
+static int dispatch_epilogue(const char* who, int epilogue, F&& f) {
+  switch (epilogue) {
+    case EPI_BIAS: return f(std::integral_constant<int, EPI_BIAS>{});
+    case EPI_BIAS_GELU: return f(std::integral_constant<int, EPI_BIAS_GELU>{});
+    case EPI_BIAS_GATE_RES: return f(std::integral_constant<int, EPI_BIAS_GATE_RES>{});
+    case EPI_BIAS_RES: return f(std::integral_constant<int, EPI_BIAS_RES>{});
+    case EPI_COLSCALE:
+      if constexpr (COLSCALE) return f(std::integral_constant<int, EPI_COLSCALE>{});
+      break;
+  }
+  return fail("%s: unknown epilogue %d", who, epilogue);
+}
+
 #ifdef TFX_BENCH
 template <int ABL>
 static int launch_ablation(const GemmParams& p, hipStream_t st) {
-  (void)hipFuncSetAttribute((const void*)gemm8p_kernel<EPI_BIAS, ABL>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_TOTAL);
-  gemm8p_kernel<EPI_BIAS, ABL><<<(unsigned)(p.batch * p.tm * p.tn), 512, LDS_TOTAL, st>>>(p);
+  if (const int rc = launch_one_tile<gemm8p_kernel<EPI_BIAS, ABL>>("gemm_ablation", p, st)) return rc;
   return check_launch("gemm_ablation");
 }
 #endif  // TFX_BENCH
@@ -1785,44 +1839,19 @@ static int launch_variant(const GemmParams& p, int variant, void* ws, int64_t ws
 #endif
   }
   if ((variant == 1 || variant == 3) && persist_ok(p)) {
-    static int grid = 0;
-    if (!grid) {
-      int dev = 0, cus = 0;
-      (void)hipGetDevice(&dev);
-      if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 8) cus = 256;
-      const void* fns[2] = {(const void*)gemm8pp_kernel<EPI, 1>, (const void*)gemm8pp_kernel<EPI, 2>};
-      for (const void* fn : fns) {
-        hipFuncAttributes fa;  // forces the (lazily loaded) code object in before the attribute is set
-        (void)hipFuncGetAttributes(&fa, fn);
-        (void)hipGetLastError();
-        const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, PP_LDS_TOTAL);
-        if (e != hipSuccess)
-          return fail("gemm: cannot raise dynamic LDS limit to %d bytes: %s", PP_LDS_TOTAL, hipGetErrorString(e));
-      }
-      grid = cus & ~7;  // one block per CU (160 KiB of LDS each), a whole number per XCD
-    }
-    const bool prof = prof_on(st);
-    if (prof) prof_begin(0, 2.0 * p.M * (double)p.N * p.K * p.batch, st);
+    const DeviceFacts dv = device_facts();
+    const int grid = dv.grid;
+    ProfScope prof(0, gemm_flops(p), st);
     // K-sliced units (variant 1 = auto only; the caller must have passed a workspace for the fp32 partials): plan_slices
     const int nt = p.K >> 6;
     const SlicePlan pl = variant == 1 ? plan_slices(p, grid, nt, ws, ws_bytes) : SlicePlan{1, 0, 0};
     const int sk = pl.sk;
+    int rc;
 #ifdef TFX_BENCH
     if (g_gemm_waves == 4 && sk == 1 && p.K >= 256) {   // one wave per SIMD (tfx_set_option gemm_waves 4): every unsliced bf16 launch
       if (p.rope_cs && EPI != EPI_BIAS_GELU) return fail("gemm: the q/k norm + RoPE epilogue rides on the bias(+GELU) epilogue");
-      static bool attr4[2] = {false, false};
-      const int qi = p.rope_cs ? 1 : 0;
-      const void* fn = qi ? (const void*)gemm4w_kernel<EPI_BIAS_GELU, true> : (const void*)gemm4w_kernel<EPI, false>;
-      if (!attr4[qi]) {
-        hipFuncAttributes fa;
-        (void)hipFuncGetAttributes(&fa, fn);
-        (void)hipGetLastError();
-        if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, W4G_LDS_TOTAL) != hipSuccess)
-          return fail("gemm: cannot raise dynamic LDS limit for the 4-wave kernel");
-        attr4[qi] = true;
-      }
-      if (qi) gemm4w_kernel<EPI_BIAS_GELU, true><<<grid, 256, W4G_LDS_TOTAL, st>>>(p);
-      else gemm4w_kernel<EPI, false><<<grid, 256, W4G_LDS_TOTAL, st>>>(p);
+      rc = p.rope_cs ? launch_lds<gemm4w_kernel<EPI_BIAS_GELU, true>>("gemm (4-wave kernel)", dv.dev, grid, 256, W4G_LDS_TOTAL, p, st)
+                     : launch_lds<gemm4w_kernel<EPI, false>>("gemm (4-wave kernel)", dv.dev, grid, 256, W4G_LDS_TOTAL, p, st);
     } else
 #endif
     if (p.rope_cs) {   // fused q / k RMSNorm + RoPE epilogue: EPI_BIAS_GELU instantiation only (plain bias = gelu_from >= N)
@@ -1831,70 +1860,30 @@ static int launch_variant(const GemmParams& p, int variant, void* ws, int64_t ws
       // unfused launch + the separate 12 us pass it replaces, profiles/r06_batch1_experiments.md; not kept)
       if (sk > 1) return fail("gemm: the q/k norm + RoPE epilogue cannot ride on a K-sliced launch (gemm_qkn_ok)");
       if (EPI != EPI_BIAS_GELU) return fail("gemm: the q/k norm + RoPE epilogue rides on the bias(+GELU) epilogue");
-      static bool attrq = false;
-      const void* fn = (const void*)gemm8pp_kernel<EPI_BIAS_GELU, 2, false, false, true>;
-      if (!attrq) {
-        hipFuncAttributes fa;
-        (void)hipFuncGetAttributes(&fa, fn);
-        (void)hipGetLastError();
-        if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, PP_LDS_TOTAL) != hipSuccess)
-          return fail("gemm: cannot raise dynamic LDS limit for the q/k-norm kernel");
-        attrq = true;
-      }
-      gemm8pp_kernel<EPI_BIAS_GELU, 2, false, false, true><<<grid, 512, PP_LDS_TOTAL, st>>>(p);
+      rc = launch_persistent<gemm8pp_kernel<EPI_BIAS_GELU, 2, false, false, true>>("gemm (q/k-norm kernel)", dv, p, st);
     } else if (sk > 1) {
-      static bool attr = false;
-      if (!attr) {
-        const void* fns[2] = {(const void*)gemm8pp_kernel<EPI_BIAS, 2, false, true>, (const void*)gemm8pp_kernel<EPI, 2, false, true>};
-        for (const void* fn : fns) {
-          hipFuncAttributes fa;
-          (void)hipFuncGetAttributes(&fa, fn);
-          (void)hipGetLastError();
-          if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, PP_LDS_TOTAL) != hipSuccess)
-            return fail("gemm: cannot raise dynamic LDS limit for the K-sliced kernel");
-        }
-        attr = true;
-      }
       GemmParams ps = p;
       ps.ws = (float*)ws; ps.sk = sk; ps.u_full = pl.u_full; ps.tail_r = pl.tail_r;
       if (pl.u_full == 0)     // every tile sliced: no whole-tile epilogue in the stream, the bias-only instantiation serves every EPI
-        gemm8pp_kernel<EPI_BIAS, 2, false, true><<<grid, 512, PP_LDS_TOTAL, st>>>(ps);
+        rc = launch_persistent<gemm8pp_kernel<EPI_BIAS, 2, false, true>>("gemm (K-sliced kernel)", dv, ps, st);
       else
-        gemm8pp_kernel<EPI, 2, false, true><<<grid, 512, PP_LDS_TOTAL, st>>>(ps);
-      tail_reduce_kernel<EPI><<<(unsigned)(p.batch * pl.tail_r * 32), 256, 0, st>>>(ps);
+        rc = launch_persistent<gemm8pp_kernel<EPI, 2, false, true>>("gemm (K-sliced kernel)", dv, ps, st);
+      if (!rc) tail_reduce_kernel<EPI><<<(unsigned)(p.batch * pl.tail_r * 32), 256, 0, st>>>(ps);
     } else if (g_gemm_place == 1) {
-      gemm8pp_kernel<EPI, 1><<<grid, 512, PP_LDS_TOTAL, st>>>(p);
+      rc = launch_persistent<gemm8pp_kernel<EPI, 1>>("gemm", dv, p, st);
     } else {
-      gemm8pp_kernel<EPI, 2><<<grid, 512, PP_LDS_TOTAL, st>>>(p);
+      rc = launch_persistent<gemm8pp_kernel<EPI, 2>>("gemm", dv, p, st);
     }
-    if (prof) prof_end(0, st);
-    return check_launch("gemm_bf16");
+    return rc ? rc : check_launch("gemm_bf16");
   }
   if (variant == 3) return fail("gemm: shape not eligible for the persistent kernel");
   if (variant == 1 || variant == 2) {
     const int conv = p.cin > 0 ? (p.csh ? 2 : 1) : 0;
-    static bool attr_set[3] = {false, false, false};
-    if (!attr_set[conv]) {
-      const void* fn = conv == 2 ? (const void*)gemm8p_kernel<EPI, 0, 2> : conv == 1 ? (const void*)gemm8p_kernel<EPI, 0, 1>
-                                                                                  : (const void*)gemm8p_kernel<EPI, 0, 0>;
-      hipFuncAttributes fa;  // forces the (lazily loaded) code object in before the attribute is set
-      (void)hipFuncGetAttributes(&fa, fn);
-      (void)hipGetLastError();
-      const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_TOTAL);
-      if (e != hipSuccess)
-        return fail("gemm: cannot raise dynamic LDS limit to %d bytes: %s", LDS_TOTAL, hipGetErrorString(e));
-      attr_set[conv] = true;
-    }
-    const unsigned grid = (unsigned)(p.batch * p.tm * p.tn);
-    const bool prof = prof_on(st) && !conv;
-    if (prof) prof_begin(0, 2.0 * p.M * (double)p.N * p.K * p.batch, st);
-    if (conv == 2)
-      gemm8p_kernel<EPI, 0, 2><<<grid, 512, LDS_TOTAL, st>>>(p);
-    else if (conv == 1)
-      gemm8p_kernel<EPI, 0, 1><<<grid, 512, LDS_TOTAL, st>>>(p);
-    else
-      gemm8p_kernel<EPI, 0, 0><<<grid, 512, LDS_TOTAL, st>>>(p);
-    if (prof) prof_end(0, st);
+    ProfScope prof(0, gemm_flops(p), st, !conv);
+    const int rc = conv == 2 ? launch_one_tile<gemm8p_kernel<EPI, 0, 2>>("gemm", p, st)
+                 : conv == 1 ? launch_one_tile<gemm8p_kernel<EPI, 0, 1>>("gemm", p, st)
+                             : launch_one_tile<gemm8p_kernel<EPI, 0, 0>>("gemm", p, st);
+    if (rc) return rc;
   } else {
     dim3 grid((p.N + 63) / 64, (p.M + 63) / 64, p.batch);
     gemm_generic_kernel<EPI><<<grid, 256, 0, st>>>(p);
@@ -1906,20 +1895,14 @@ int gemm_bf16_variant(const GemmArgs& a, int variant, hipStream_t st) {
   if (a.M <= 0 || a.N <= 0 || a.batch <= 0) return 0;
   if (a.K <= 0) return fail("gemm: K must be positive");
   if (variant >= 1 && !fast_ok(a)) return fail("gemm: shape/alignment not supported by the MFMA kernel");
-  if (a.epilogue == EPI_BIAS_GATE_RES && (!a.gate || !a.res)) return fail("gemm: gate/res pointers required");
-  if (a.epilogue == EPI_BIAS_RES && !a.res) return fail("gemm: res pointer required");
+  if (const int rc = check_gate_res("gemm", a)) return rc;
   if (a.epilogue == EPI_COLSCALE && (!a.cscale || (uintptr_t)a.cscale % 16 || a.bias || a.split_row > 0))
     return fail("gemm: the column-scale epilogue needs a 16-byte aligned fp32 cscale vector and takes no bias / row-split weights");
   const GemmParams p = make_params(a);
   if (a.split_row > 0 && !((variant == 1 || variant == 3) && gemm_rowsplit_ok(a))) return fail("gemm: row-split weights need the persistent MFMA kernel");
-  switch (a.epilogue) {
-    case EPI_BIAS: return launch_variant<EPI_BIAS>(p, variant, a.workspace, a.workspace_bytes, st);
-    case EPI_BIAS_GELU: return launch_variant<EPI_BIAS_GELU>(p, variant, a.workspace, a.workspace_bytes, st);
-    case EPI_BIAS_GATE_RES: return launch_variant<EPI_BIAS_GATE_RES>(p, variant, a.workspace, a.workspace_bytes, st);
-    case EPI_BIAS_RES: return launch_variant<EPI_BIAS_RES>(p, variant, a.workspace, a.workspace_bytes, st);
-    case EPI_COLSCALE: return launch_variant<EPI_COLSCALE>(p, variant, a.workspace, a.workspace_bytes, st);
-  }
-  return fail("gemm: unknown epilogue %d", a.epilogue);
+  return dispatch_epilogue<true>("gemm", a.epilogue, [&](auto epi) {
+    return launch_variant<decltype(epi)::value>(p, variant, a.workspace, a.workspace_bytes, st);
+  });
 }
 
 // Row-split weights need the persistent kernel (the tile origin decides the weight set), split_row on a tile boundary, the second
@@ -1949,14 +1932,9 @@ bool gemm_qkn_ok(const GemmArgs& a) {
   if (!fast_ok(a) || a.conv_cin > 0 || (a.epilogue != EPI_BIAS_GELU && a.epilogue != EPI_BIAS)) return false;
   const GemmParams p = make_params(a);
   if (!persist_ok(p)) return false;
-  if ((a.qkn_q0 | a.qkn_q1 | a.qkn_k0 | a.qkn_k1) % 256) return false;
-  // the normalised columns carry no activation (the epilogue instantiates norm and GELU tiles separately)
-  if (a.epilogue == EPI_BIAS_GELU && a.gelu_from_col < (a.qkn_q1 > a.qkn_k1 ? a.qkn_q1 : a.qkn_k1)) return false;
-  int dev = 0, cus = 256;
-  (void)hipGetDevice(&dev);
-  if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 8) cus = 256;
+  if (!qk_ranges_ok(a)) return false;
   // ... and no K-sliced units in the launch the auto path would make with this workspace (tail_reduce_kernel has no such epilogue)
-  return plan_slices(p, cus & ~7, p.K >> 6, a.workspace, a.workspace_bytes).sk == 1;
+  return plan_slices(p, device_facts().grid, p.K >> 6, a.workspace, a.workspace_bytes).sk == 1;
 }
 
 // ---- runtime LoRA tail (gemm8pp_kernel<.., LORA = true>): C = epi(A W^T + T B^T + bias), one fp32 accumulation.  Always the persistent
@@ -1964,32 +1942,16 @@ bool gemm_qkn_ok(const GemmArgs& a) {
 // q / k-norm epilogue), whatever its tile count; shapes the persistent kernel does not take are refused, there is no fallback.
 template <int EPI, bool QKN>
 static int launch_lora(const GemmParams& p, hipStream_t st) {
-  static int grid = 0;
-  if (!grid) {
-    int dev = 0, cus = 0;
-    (void)hipGetDevice(&dev);
-    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 8) cus = 256;
-    const void* fn = (const void*)gemm8pp_kernel<EPI, 2, false, false, QKN, true>;
-    hipFuncAttributes fa;  // forces the (lazily loaded) code object in before the attribute is set
-    (void)hipFuncGetAttributes(&fa, fn);
-    (void)hipGetLastError();
-    const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, PP_LDS_TOTAL);
-    if (e != hipSuccess) return fail("gemm_lora: cannot raise dynamic LDS limit to %d bytes: %s", PP_LDS_TOTAL, hipGetErrorString(e));
-    grid = cus & ~7;
-  }
-  const bool prof = prof_on(st);
-  if (prof) prof_begin(0, 2.0 * p.M * (double)p.N * (p.K + p.lora_rt * 64) * p.batch, st);
-  gemm8pp_kernel<EPI, 2, false, false, QKN, true><<<grid, 512, PP_LDS_TOTAL, st>>>(p);
-  if (prof) prof_end(0, st);
-  return check_launch("gemm_bf16_lora");
+  ProfScope prof(0, gemm_flops(p), st);
+  const int rc = launch_persistent<gemm8pp_kernel<EPI, 2, false, false, QKN, true>>("gemm_lora", device_facts(), p, st);
+  return rc ? rc : check_launch("gemm_bf16_lora");
 }
 
 int gemm_bf16_lora(const GemmArgs& a, const LoraArgs& l, hipStream_t st) {
   if (a.M <= 0 || a.N <= 0 || a.batch <= 0) return 0;
   if (a.K <= 0) return fail("gemm_lora: K must be positive");
   if (!fast_ok(a) || a.conv_cin > 0 || a.w_bstride) return fail("gemm_lora: shape/alignment not supported by the persistent MFMA kernel");
-  if (a.epilogue == EPI_BIAS_GATE_RES && (!a.gate || !a.res)) return fail("gemm_lora: gate/res pointers required");
-  if (a.epilogue == EPI_BIAS_RES && !a.res) return fail("gemm_lora: res pointer required");
+  if (const int rc = check_gate_res("gemm_lora", a)) return rc;
   if (a.epilogue == EPI_COLSCALE) return fail("gemm_lora: the column-scale epilogue is the down projection's (tfx_gemm_bf16)");
   if (l.R < 128 || l.R % 128 || l.R > LORA_MAX_RANK) return fail("gemm_lora: R (the padded rank) must be 128 or 256");
   if (l.nseg < 1 || l.nseg > 4 || l.seg_cols <= 0 || l.seg_cols % 256) return fail("gemm_lora: 1..4 segments of seg_cols %% 256 == 0 output columns");
@@ -2010,30 +1972,20 @@ int gemm_bf16_lora(const GemmArgs& a, const LoraArgs& l, hipStream_t st) {
   p.t_off = (uint32_t)d; p.t_seg = (uint32_t)(t_seg * 2); p.lora_rt = l.R / 64; p.seg_cols = l.seg_cols; p.nseg = l.nseg; p.seg_mask = l.seg_mask;
   if (a.qkn_rope_cs) {
     if (a.epilogue != EPI_BIAS_GELU) return fail("gemm_lora: the q/k norm + RoPE epilogue rides on the bias(+GELU) epilogue");
-    if ((a.qkn_q0 | a.qkn_q1 | a.qkn_k0 | a.qkn_k1) % 256 || a.gelu_from_col < (a.qkn_q1 > a.qkn_k1 ? a.qkn_q1 : a.qkn_k1))
-      return fail("gemm_lora: q / k column ranges must be multiples of 256 in front of gelu_from_col");
+    if (!qk_ranges_ok(a)) return fail("gemm_lora: q / k column ranges must be multiples of 256 in front of gelu_from_col");
     return launch_lora<EPI_BIAS_GELU, true>(p, st);
   }
-  switch (a.epilogue) {
-    case EPI_BIAS: return launch_lora<EPI_BIAS, false>(p, st);
-    case EPI_BIAS_GELU: return launch_lora<EPI_BIAS_GELU, false>(p, st);
-    case EPI_BIAS_GATE_RES: return launch_lora<EPI_BIAS_GATE_RES, false>(p, st);
-    case EPI_BIAS_RES: return launch_lora<EPI_BIAS_RES, false>(p, st);
-  }
-  return fail("gemm_lora: unknown epilogue %d", a.epilogue);
+  return dispatch_epilogue<false>("gemm_lora", a.epilogue, [&](auto epi) { return launch_lora<decltype(epi)::value, false>(p, st); });
 }
 
 // The same question for the e4m3 path (gemm_fp8): it slices K only when the whole GEMM has fewer tiles than CUs, so the fused epilogue
 // is available exactly when it does not (a: the bf16-side description of the Linear, as tfx_dit_forward builds it).
 bool gemm_fp8_qkn_ok(const GemmArgs& a) {
   if (a.conv_cin > 0 || (a.epilogue != EPI_BIAS_GELU && a.epilogue != EPI_BIAS) || a.split_row > 0) return false;
-  if (a.K <= 0 || a.K % 256 || a.N % 8 || (a.qkn_q0 | a.qkn_q1 | a.qkn_k0 | a.qkn_k1) % 256) return false;
-  if (a.epilogue == EPI_BIAS_GELU && (a.gelu_from_col % 256 || a.gelu_from_col < (a.qkn_q1 > a.qkn_k1 ? a.qkn_q1 : a.qkn_k1))) return false;
-  int dev = 0, cus = 256;
-  (void)hipGetDevice(&dev);
-  if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 8) cus = 256;
+  if (a.K <= 0 || a.K % 256 || a.N % 8 || !qk_ranges_ok(a)) return false;
+  if (a.epilogue == EPI_BIAS_GELU && a.gelu_from_col % 256) return false;
   const int64_t T = (int64_t)a.batch * ((a.M + 255) / 256) * ((a.N + 255) / 256);
-  return T >= (cus & ~7);
+  return T >= device_facts().grid;
 }
 
 // ---- fp32 output (raw accumulators, no epilogue): C [batch][M, N] floats with row stride ldc.  The score GEMM of the
@@ -2051,23 +2003,8 @@ int gemm_bf16_f32out(const GemmArgs& a, hipStream_t st) {
   chk.C = const_cast<void*>(a.A);   // alignment of the fp32 C was checked above; the remaining fast-path conditions are operand-side
   chk.ldc = 8; chk.c_bstride = 8;
   if (fast_ok(chk) && persist_ok(p)) {
-    static int grid = 0;
-    if (!grid) {
-      int dev = 0, cus = 0;
-      (void)hipGetDevice(&dev);
-      if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 8) cus = 256;
-      const void* fn = (const void*)gemm8pp_kernel<EPI_BIAS, 2, false, true>;
-      hipFuncAttributes fa;
-      (void)hipFuncGetAttributes(&fa, fn);
-      (void)hipGetLastError();
-      if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, PP_LDS_TOTAL) != hipSuccess)
-        return fail("gemm_f32out: cannot raise dynamic LDS limit");
-      grid = cus & ~7;
-    }
-    const bool prof = prof_on(st);
-    if (prof) prof_begin(0, 2.0 * p.M * (double)p.N * p.K * p.batch, st);
-    gemm8pp_kernel<EPI_BIAS, 2, false, true><<<grid, 512, PP_LDS_TOTAL, st>>>(p);
-    if (prof) prof_end(0, st);
+    ProfScope prof(0, gemm_flops(p), st);
+    if (const int rc = launch_persistent<gemm8pp_kernel<EPI_BIAS, 2, false, true>>("gemm_f32out", device_facts(), p, st)) return rc;
   } else {
     dim3 grid((p.N + 63) / 64, (p.M + 63) / 64, p.batch);
     gemm_generic_kernel<EPI_BIAS><<<grid, 256, 0, st>>>(p);
@@ -2078,53 +2015,25 @@ int gemm_bf16_f32out(const GemmArgs& a, hipStream_t st) {
 // ---- fp8 (e4m3 x e4m3 -> fp32) path: the persistent kernel only
 template <int EPI>
 static int launch_fp8(const GemmParams& p, void* ws, int64_t ws_bytes, hipStream_t st) {
-  static int grid = 0;
-  if (!grid) {
-    int dev = 0, cus = 0;
-    (void)hipGetDevice(&dev);
-    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 8) cus = 256;
-    const void* fns[2] = {(const void*)gemm8pp_kernel<EPI, 2, true>, (const void*)gemm8pp_kernel<EPI_BIAS, 2, true, true>};
-    for (const void* fn : fns) {
-      hipFuncAttributes fa;
-      (void)hipFuncGetAttributes(&fa, fn);
-      (void)hipGetLastError();
-      const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, PP_LDS_TOTAL);
-      if (e != hipSuccess) return fail("gemm_fp8: cannot raise dynamic LDS limit to %d bytes: %s", PP_LDS_TOTAL, hipGetErrorString(e));
-    }
-    grid = cus & ~7;
-  }
-  const bool prof = prof_on(st);
-  if (prof) prof_begin(2, 2.0 * p.M * (double)p.N * p.K * p.batch, st);
+  const DeviceFacts dv = device_facts();
+  const int grid = dv.grid;
+  ProfScope prof(2, gemm_flops(p), st);
   const int T = p.batch * p.tm * p.tn, nt = p.K >> 7;   // 128-byte K-tiles of e4m3
   SlicePlan pl = T < grid ? plan_slices(p, grid, nt, ws, ws_bytes) : SlicePlan{1, 0, 0};   // fp8: whole-GEMM slicing only
+  int rc;
   if (p.rope_cs) {   // fused q / k RMSNorm + RoPE epilogue (round 5: also in fp8 mode; gemm_fp8_qkn_ok)
-    if (pl.sk > 1 || EPI != EPI_BIAS_GELU) {
-      if (prof) prof_end(2, st);
+    if (pl.sk > 1 || EPI != EPI_BIAS_GELU)
       return fail("gemm_fp8: the q/k norm + RoPE epilogue needs an unsliced launch with the bias(+GELU) epilogue (gemm_fp8_qkn_ok)");
-    }
-    static bool attrq = false;
-    const void* fn = (const void*)gemm8pp_kernel<EPI_BIAS_GELU, 2, true, false, true>;
-    if (!attrq) {
-      hipFuncAttributes fa;
-      (void)hipFuncGetAttributes(&fa, fn);
-      (void)hipGetLastError();
-      if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, PP_LDS_TOTAL) != hipSuccess) {
-        if (prof) prof_end(2, st);
-        return fail("gemm_fp8: cannot raise dynamic LDS limit for the q/k-norm kernel");
-      }
-      attrq = true;
-    }
-    gemm8pp_kernel<EPI_BIAS_GELU, 2, true, false, true><<<grid, 512, PP_LDS_TOTAL, st>>>(p);
+    rc = launch_persistent<gemm8pp_kernel<EPI_BIAS_GELU, 2, true, false, true>>("gemm_fp8 (q/k-norm kernel)", dv, p, st);
   } else if (pl.sk > 1) {
     GemmParams ps = p;
     ps.ws = (float*)ws; ps.sk = pl.sk; ps.u_full = 0; ps.tail_r = pl.tail_r;
-    gemm8pp_kernel<EPI_BIAS, 2, true, true><<<grid, 512, PP_LDS_TOTAL, st>>>(ps);
-    tail_reduce_kernel<EPI, true><<<(unsigned)(p.batch * pl.tail_r * 32), 256, 0, st>>>(ps);
+    rc = launch_persistent<gemm8pp_kernel<EPI_BIAS, 2, true, true>>("gemm_fp8", dv, ps, st);
+    if (!rc) tail_reduce_kernel<EPI, true><<<(unsigned)(p.batch * pl.tail_r * 32), 256, 0, st>>>(ps);
   } else {
-    gemm8pp_kernel<EPI, 2, true><<<grid, 512, PP_LDS_TOTAL, st>>>(p);
+    rc = launch_persistent<gemm8pp_kernel<EPI, 2, true>>("gemm_fp8", dv, p, st);
   }
-  if (prof) prof_end(2, st);
-  return check_launch("gemm_fp8");
+  return rc ? rc : check_launch("gemm_fp8");
 }
 
 int gemm_fp8(const GemmArgs& a, hipStream_t st) {
@@ -2139,11 +2048,10 @@ int gemm_fp8(const GemmArgs& a, hipStream_t st) {
         a.ldc % 8 == 0 && a.c_bstride % 8 == 0 && al && (int64_t)(a.batch - 1) * a.a_bstride + (int64_t)tm * 256 * a.lda < (1ll << 32) &&
         (int64_t)tn * 256 * a.ldw < (1ll << 32) && (int64_t)255 * a.lda < (1ll << 31) && (int64_t)255 * a.ldw < (1ll << 31)))
     return fail("gemm_fp8: shape/alignment not supported (K %% 256 == 0, N %% 8 == 0, 16-byte aligned rows)");
-  if ((a.epilogue == EPI_BIAS_GATE_RES || a.epilogue == EPI_BIAS_RES) &&
-      !(a.res && a.ldr % 8 == 0 && a.r_bstride % 8 == 0 && (uintptr_t)a.res % 16 == 0))
-    return fail("gemm_fp8: residual pointer / alignment");
-  if (a.epilogue == EPI_BIAS_GATE_RES && !(a.gate && a.gate_bstride % 4 == 0 && (uintptr_t)a.gate % 8 == 0))
-    return fail("gemm_fp8: gate pointer / alignment");
+  if (const int rc = check_gate_res("gemm_fp8", a)) return rc;
+  if ((a.epilogue == EPI_BIAS_GATE_RES || a.epilogue == EPI_BIAS_RES) && !(a.ldr % 8 == 0 && a.r_bstride % 8 == 0 && (uintptr_t)a.res % 16 == 0))
+    return fail("gemm_fp8: residual alignment");
+  if (a.epilogue == EPI_BIAS_GATE_RES && !(a.gate_bstride % 4 == 0 && (uintptr_t)a.gate % 8 == 0)) return fail("gemm_fp8: gate alignment");
   if (a.epilogue == EPI_BIAS_GELU && a.gelu_from_col % 256) return fail("gemm_fp8: gelu_from_col must be a multiple of 256");
   // the fused q / k norm + RoPE epilogue: every condition of gemm_fp8_qkn_ok is re-checked HERE -- a public caller
   // that sets rope_cs with unaligned column ranges, a GELU range overlapping q / k, row-split weights or null norm weights would
@@ -2153,13 +2061,9 @@ int gemm_fp8(const GemmArgs& a, hipStream_t st) {
     if (!gemm_fp8_qkn_ok(a)) return fail("gemm_fp8: shape / column ranges not eligible for the fused q/k norm + RoPE epilogue (gemm_fp8_qkn_ok)");
   }
   const GemmParams p = make_params(a);
-  switch (a.epilogue) {
-    case EPI_BIAS: return launch_fp8<EPI_BIAS>(p, a.workspace, a.workspace_bytes, st);
-    case EPI_BIAS_GELU: return launch_fp8<EPI_BIAS_GELU>(p, a.workspace, a.workspace_bytes, st);
-    case EPI_BIAS_GATE_RES: return launch_fp8<EPI_BIAS_GATE_RES>(p, a.workspace, a.workspace_bytes, st);
-    case EPI_BIAS_RES: return launch_fp8<EPI_BIAS_RES>(p, a.workspace, a.workspace_bytes, st);
-  }
-  return fail("gemm_fp8: unknown epilogue %d", a.epilogue);
+  return dispatch_epilogue<false>("gemm_fp8", a.epilogue, [&](auto epi) {
+    return launch_fp8<decltype(epi)::value>(p, a.workspace, a.workspace_bytes, st);
+  });
 }
 
 }  // namespace tfx

@@ -1,4 +1,4 @@
-// Error plumbing shared by all launchers (see launch.h).
+// Error plumbing, per-device launch state and the launch-level profiler shared by all launchers (see launch.h).
 #include "launch.h"
 
 #include <cstdarg>
@@ -24,6 +24,37 @@ int check_launch(const char* what) {
 }
 
 const char* last_error() { return g_err; }
+
+// ---- per-device launch state ----------------------------------------------------------------------------
+static std::atomic<int> g_cus[MAX_DEVICES];   // 0 = not asked yet
+
+DeviceFacts device_facts() {
+  int dev = 0;
+  (void)hipGetDevice(&dev);
+  const bool cached = dev >= 0 && dev < MAX_DEVICES;
+  int cus = cached ? g_cus[dev].load(std::memory_order_relaxed) : 0;
+  if (!cus) {
+    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 8) cus = 256;
+    if (cached) g_cus[dev].store(cus, std::memory_order_relaxed);
+  }
+  return DeviceFacts{dev, cus, cus & ~7};
+}
+
+int prepare_kernel(KernelPrep& kp, const void* fn, int dev, int lds_bytes, const char* family, KernelVet vet) {
+  const bool cached = dev >= 0 && dev < MAX_DEVICES;
+  if (cached && kp.lds[dev].load(std::memory_order_acquire) >= lds_bytes) return 0;
+  hipFuncAttributes fa;   // forces the (lazily loaded) code object in before the attribute is set
+  const hipError_t loaded = hipFuncGetAttributes(&fa, fn);
+  (void)hipGetLastError();
+  if (vet) {
+    if (loaded != hipSuccess) return fail("%s: kernel is not in this build: %s", family, hipGetErrorString(loaded));
+    if (const int rc = vet(fa)) return rc;
+  }
+  const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);
+  if (e != hipSuccess) return fail("%s: cannot raise dynamic LDS limit to %d bytes: %s", family, lds_bytes, hipGetErrorString(e));
+  if (cached) kp.lds[dev].store(lds_bytes, std::memory_order_release);
+  return 0;
+}
 
 // ---- launch-level profiler ------------------------------------------------------------------------------
 namespace {

@@ -3,6 +3,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <atomic>
+
 namespace tfx {
 
 // Error plumbing: every launcher returns 0 on success; on failure the message is kept per thread and is
@@ -20,6 +22,40 @@ bool prof_on(hipStream_t st);  // false while `st` is being captured into a grap
 void prof_begin(int kind, double flops, hipStream_t st);
 void prof_end(int kind, hipStream_t st);
 int prof_collect(int kind, double* total_ms, double* total_flops, int* launches);
+// The bracket as a scope: prof_begin now (when profiling is on and `st` is not being captured), prof_end on EVERY way out of the
+// scope -- a record without its end event would make the next prof_collect fail.
+class ProfScope {
+ public:
+  ProfScope(int kind, double flops, hipStream_t st, bool wanted = true) : kind_(kind), st_(st), on_(wanted && prof_on(st)) {
+    if (on_) prof_begin(kind, flops, st);
+  }
+  ~ProfScope() { if (on_) prof_end(kind_, st_); }
+  ProfScope(const ProfScope&) = delete;
+  ProfScope& operator=(const ProfScope&) = delete;
+ private:
+  int kind_; hipStream_t st_; bool on_;
+};
+
+// ---- launch state: all of it is per DEVICE (HIP keeps function attributes on the per-device function object, and two devices of
+// one process need not have the same CU count).  Lock-free: the tables below are indexed by the device ordinal and a race between two
+// threads at most repeats a query / an attribute call, it never skips one.  Ordinals >= MAX_DEVICES are served uncached.
+constexpr int MAX_DEVICES = 64;
+// The CURRENT device: its CU count (256 when the runtime cannot say or says < 8) and the grid of the persistent kernels, one workgroup
+// per CU in a whole number per XCD.  One hipGetDevice per call, no other HIP call after the first on a device.
+struct DeviceFacts { int dev, cus, grid; };
+DeviceFacts device_facts();
+// What prepare_kernel remembers about one kernel: the dynamic LDS limit it set on each device (0 = not prepared there).
+struct KernelPrep { std::atomic<int> lds[MAX_DEVICES]; };
+template <auto K> inline KernelPrep kernel_prep{};     // one per __global__ function (instantiation)
+// Makes `fn` launchable with `lds_bytes` of dynamic LDS on the current device (`dev`, as device_facts() gave it): loads the (lazily loaded) code object, raises the limit
+// and remembers it, so that a later call asking for no more is one atomic load.  `vet`, when given, sees the kernel's attributes before
+// the limit is raised; a non-zero result (its own fail(...)) is returned and nothing is remembered.  Errors name `family` and the bytes.
+using KernelVet = int (*)(const hipFuncAttributes&);
+int prepare_kernel(KernelPrep& kp, const void* fn, int dev, int lds_bytes, const char* family, KernelVet vet = nullptr);
+template <auto K>
+int prepare_kernel(int dev, int lds_bytes, const char* family, KernelVet vet = nullptr) {
+  return prepare_kernel(kernel_prep<K>, (const void*)K, dev, lds_bytes, family, vet);
+}
 
 // GEMM epilogues (C = epi(A @ W^T + bias)).
 enum Epilogue : int {

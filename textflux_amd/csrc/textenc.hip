@@ -201,15 +201,8 @@ int attention64(const AttnArgs& a, const float* rel_bias, int causal, hipStream_
   if (((uintptr_t)a.q | (uintptr_t)a.k | (uintptr_t)a.v) % 16 || (uintptr_t)a.o % 8) return fail("attention64: alignment");
   const int NP = (a.N + 63) / 64 * 64;
   const int lds = NP * A64_KROW + 64 * 2 * (NP + 8);
-  static int lds_set = 0;
-  if (lds > lds_set) {
-    hipFuncAttributes fa;
-    (void)hipFuncGetAttributes(&fa, (const void*)attn64_kernel);
-    (void)hipGetLastError();
-    if (hipFuncSetAttribute((const void*)attn64_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 1024) != hipSuccess)
-      return fail("attention64: cannot raise the dynamic LDS limit");
-    lds_set = 160 * 1024;
-  }
+  // raised once per device to (nearly) all a workgroup can have: N = 512, the most taken, needs 137 KiB
+  if (const int rc = prepare_kernel<attn64_kernel>(device_facts().dev, 160 * 1024 - 1024, "attention64")) return rc;
   attn64_kernel<<<dim3(a.B * a.H, (a.N + 127) / 128), 256, lds, st>>>(
       (const bf16_t*)a.q, (const bf16_t*)a.k, (const bf16_t*)a.v, (bf16_t*)a.o, a.ldq, a.ldk, a.ldv, a.ldo, a.q_bstride,
       a.k_bstride, a.v_bstride, a.o_bstride, a.H, a.N, NP, a.scale, rel_bias, causal);
