@@ -1,6 +1,5 @@
-// extern "C" surface of libtextflux_hip.so (declared in include/textflux_hip.h) and the host-side DiT forward
-// that strings the kernels together (one FluxTransformer2DModel.forward, reference:
-// diffusers/src/diffusers/models/transformers/transformer_flux.py:1028-1212).
+// extern "C" surface of libtextflux_hip.so (declared in include/textflux_hip.h): argument checks and conversions in front of the
+// launch API (launch.h), tfx_set_option, the workspace layout and the step graph.  The DiT forward itself is dit_forward.cpp.
 #include "../../include/textflux_hip.h"
 
 #include <cstring>
@@ -12,321 +11,11 @@ using namespace tfx;
 namespace {
 
 inline hipStream_t S(tfx_stream s) { return (hipStream_t)s; }
-inline const uint16_t* bf(const void* p) { return (const uint16_t*)p; }
-inline uint16_t* bf(void* p) { return (uint16_t*)p; }
 
 #define TRY(x)            \
   do {                    \
     if (int _e = (x)) return _e; \
   } while (0)
-
-// runtime LoRA adapters: what an adapted Linear of the forward in progress needs beyond its own operands (tfx_dit_desc: the T scratch
-// regions and the factor vector); set for the duration of dit_forward
-struct LoraCtx { const tfx_dit_desc* d; };
-thread_local const LoraCtx* g_lora = nullptr;
-
-struct Gemm {
-  GemmArgs a;
-  const tfx_linear* lin;
-  const tfx_linear* lin2 = nullptr;     // row-split launches: the Linear of the rows below split_row
-  Gemm(const void* A, int64_t lda, int64_t abs_, const tfx_linear& l, int64_t ldw, void* C, int64_t ldc, int64_t cbs,
-       int M, int N, int K, int batch) : lin(&l) {
-    a = GemmArgs();
-    a.A = A; a.lda = lda; a.a_bstride = abs_;
-    a.W = l.w; a.ldw = l.ldw > 0 ? l.ldw : ldw; a.bias = l.b;
-    a.C = C; a.ldc = ldc; a.c_bstride = cbs;
-    a.M = M; a.N = N; a.K = K; a.batch = batch;
-    a.epilogue = EPI_BIAS;
-  }
-  Gemm& gelu(int from_col) { a.epilogue = EPI_BIAS_GELU; a.gelu_from_col = from_col; return *this; }
-  Gemm& gate_res(const void* gate, int64_t gbs, const void* res, int64_t ldr, int64_t rbs) {
-    a.epilogue = EPI_BIAS_GATE_RES; a.gate = gate; a.gate_bstride = gbs; a.res = res; a.ldr = ldr; a.r_bstride = rbs;
-    return *this;
-  }
-  Gemm& scratch(void* ws, int64_t bytes) { a.workspace = ws; a.workspace_bytes = bytes; return *this; }
-  // row-split weights: rows [0, split_row) of every sample (the text rows of the joint stream) take l2 / gate2 (/ norm weights wq2, wk2)
-  Gemm& rowsplit(int split_row, const tfx_linear& l2, const void* gate2 = nullptr) {
-    a.split_row = split_row; a.W2 = l2.w; a.bias2 = l2.b; a.gate2 = gate2; lin2 = &l2;
-    return *this;
-  }
-  Gemm& qknorm2(const void* wq2, const void* wk2) { a.qkn_wq2 = wq2; a.qkn_wk2 = wk2; return *this; }
-  bool rowsplit_ok() const { return gemm_rowsplit_ok(a); }
-  // fused per-head RMSNorm + RoPE on the k / q column ranges [0, D) / [2D, 3D) of a [k | v | q | ...] projection
-  Gemm& qknorm(const void* wq, const void* wk, const float* cs, int pos0, int D, float eps) {
-    a.qkn_wq = wq; a.qkn_wk = wk; a.qkn_rope_cs = cs; a.qkn_pos0 = pos0;
-    a.qkn_k0 = 0; a.qkn_k1 = D; a.qkn_q0 = 2 * D; a.qkn_q1 = 3 * D; a.qkn_eps = eps;
-    if (a.epilogue == EPI_BIAS) { a.epilogue = EPI_BIAS_GELU; a.gelu_from_col = 1 << 30; }   // bias only: GELU never starts
-    return *this;
-  }
-  bool qknorm_ok(const void* wq, const void* wk, const float* cs, int pos0, int D, float eps, bool fp8 = false) const {
-    Gemm t = *this;
-    t.qknorm(wq, wk, cs, pos0, D, eps);
-    if (t.a.split_row > 0 && !(t.a.qkn_wq2 && t.a.qkn_wk2)) return false;
-    return fp8 ? gemm_fp8_qkn_ok(t.a) : gemm_qkn_ok(t.a);
-  }
-  bool adapted() const { return lin->lora_a || (a.split_row > 0 && lin2 && lin2->lora_a); }
-  // t = bf16(c * (x @ Acat^T)) into the T scratch that mirrors x's buffer, then the GEMM with the low-rank tail (gemm_bf16_lora)
-  int run_lora(hipStream_t st) const {
-    if (!g_lora) return fail("dit_forward: adapted Linear outside a forward");
-    const tfx_dit_desc& d = *g_lora->d;
-    if (!d.lora_t_xn || !d.lora_t_y || !d.lora_scale)
-      return fail("dit_forward: a block Linear carries a runtime LoRA adapter but lora_t_xn / lora_t_y / lora_scale are null");
-    const tfx_linear* l2 = a.split_row > 0 ? lin2 : nullptr;
-    const tfx_linear& ref = lin->lora_a ? *lin : *l2;
-    const int R = ref.lora_r, nseg = ref.lora_nseg;
-    if (R <= 0 || nseg <= 0 || nseg > 4) return fail("dit_forward: bad lora_r / lora_nseg on an adapted Linear");
-    if (l2 && (l2->ldw != lin->ldw || (l2->lora_a && lin->lora_a && (l2->lora_r != R || l2->lora_nseg != nseg))))
-      return fail("dit_forward: the [img; txt] Linears of a joint launch must share ldw, lora_r and lora_nseg");
-    const int64_t hid_elems = (int64_t)d.B * (d.S + d.T) * d.D;
-    const char* A = (const char*)a.A;
-    const bool in_xn = A >= (const char*)d.xn && A < (const char*)d.xn + hid_elems * 2;
-    const bool in_y = A >= (const char*)d.y && A < (const char*)d.y + hid_elems * 14;
-    if (!in_xn && !in_y) return fail("dit_forward: adapted Linear whose input is neither xn nor y");
-    char* T = const_cast<char*>(A) + (in_xn ? (const char*)d.lora_t_xn - (const char*)d.xn : (const char*)d.lora_t_y - (const char*)d.y);
-    const bool planes = (int64_t)nseg * R > a.lda;        // the segments' T blocks do not fit one row: a matrix per segment
-    if (planes && (!in_xn || d.D >= 1024)) return fail("dit_forward: lora_nseg * lora_r exceeds the input's row pitch");
-    auto down = [&](const tfx_linear& l, int row0, int rows) -> int {
-      if (!l.lora_a || rows <= 0) return 0;
-      GemmArgs g = GemmArgs();
-      g.A = A + (int64_t)row0 * a.lda * 2; g.lda = a.lda; g.a_bstride = a.a_bstride;
-      g.ldw = a.K; g.bias = nullptr;
-      g.ldc = a.lda; g.c_bstride = a.a_bstride;
-      g.M = rows; g.K = a.K; g.batch = a.batch;
-      g.epilogue = EPI_COLSCALE;
-      g.workspace = a.workspace; g.workspace_bytes = a.workspace_bytes;
-      for (int s = 0; s < (planes ? nseg : 1); ++s) {
-        if (planes && !((l.lora_mask >> s) & 1)) continue;
-        g.W = (const char*)l.lora_a + (int64_t)s * R * a.K * 2;
-        g.C = T + (int64_t)row0 * a.lda * 2 + (int64_t)s * hid_elems * 2;
-        g.N = planes ? R : nseg * R;
-        g.cscale = d.lora_scale + l.lora_scale_off + s * R;
-        if (int e = gemm_bf16(g, st)) return e;
-      }
-      return 0;
-    };
-    if (l2) {
-      TRY(down(*l2, 0, a.split_row));
-      TRY(down(*lin, a.split_row, a.M - a.split_row));
-    } else {
-      TRY(down(*lin, 0, a.M));
-    }
-    LoraArgs la{T, (const char*)a.W + (int64_t)a.K * 2, R, nseg > 1 ? d.D : a.N, nseg,
-                (uint32_t)lin->lora_mask | (l2 ? (uint32_t)l2->lora_mask << 8 : 0u), planes ? hid_elems : 0};
-    return gemm_bf16_lora(a, la, st);
-  }
-  int run(hipStream_t st) const { return adapted() ? run_lora(st) : gemm_bf16(a, st); }
-  bool fp8_ready() const { return lin->w8 && lin->w8_scale && a.K % 256 == 0; }
-  // fp8 linear whose activation rows were already quantised by the producer (ln_modulate_fp8)
-  int run_pre(hipStream_t st, const void* q, int64_t qld, int64_t qbs, const float* qs, int64_t qs_bs) const {
-    if (adapted()) return fail("dit_forward: runtime LoRA adapters and fp8 linears (flags bit 2) cannot be combined");
-    GemmArgs f = a;
-    f.A = q; f.lda = qld; f.a_bstride = qbs;
-    f.W = lin->w8;
-    f.a_scale = qs; f.a_scale_bstride = qs_bs; f.w_scale = lin->w8_scale;
-    return gemm_fp8(f, st);
-  }
-  // fp8 linears (desc.flags bit 2): quantise the activation rows into the q8 workspace, then the e4m3 GEMM
-  int run(hipStream_t st, void* q8, float* q8_scale) const {
-    if (adapted()) return q8 ? fail("dit_forward: runtime LoRA adapters and fp8 linears (flags bit 2) cannot be combined") : run_lora(st);
-    if (!q8 || !lin->w8 || !lin->w8_scale || a.K % 256) return gemm_bf16(a, st);
-    if (int e = quantize_rows_fp8(a.A, a.lda, a.a_bstride, q8, a.K, (int64_t)a.M * a.K, q8_scale, a.M, a.M, a.batch, a.K, st))
-      return e;
-    GemmArgs f = a;
-    f.A = q8; f.lda = a.K; f.a_bstride = (int64_t)a.M * a.K;
-    f.W = lin->w8; f.ldw = a.ldw;
-    f.a_scale = q8_scale; f.a_scale_bstride = a.M; f.w_scale = lin->w8_scale;
-    return gemm_fp8(f, st);
-  }
-};
-
-static int g_fp8_fuse_qkn = 1;    // tfx_set_option fp8_fuse_qkn: 0 = fp8 projections followed by the separate q / k norm + RoPE pass (round 4; A/B knob)
-static int g_ln_joint = 1;        // tfx_set_option ln_joint: 0 = the LayerNorm + modulation of a double block's text and image rows as two launches (A/B knob)
-static int g_group_streams = 1;   // tfx_set_option gemm_group_streams: 0 = the text and image GEMMs of a double block as separate launches (A/B knob)
-
-int dit_forward(const tfx_dit_desc& d, hipStream_t st) {
-  const int D = d.D, H = d.H, B = d.B, Sn = d.S, T = d.T, N = Sn + T;
-  if (D != H * 128) return fail("dit_forward: inner dim %d != heads %d * 128", D, H);
-  if (B <= 0 || Sn <= 0 || T < 0) return fail("dit_forward: bad B/S/T");
-  const int64_t D7 = 7ll * D;
-  const int64_t hid_bs = (int64_t)N * D, y_bs = (int64_t)N * D7;
-  uint16_t* hid = bf(d.hid);
-  uint16_t* xn = bf(d.xn);
-  uint16_t* y = bf(d.y);
-  uint16_t* hid_img = hid + (int64_t)T * D;
-  uint16_t* xn_img = xn + (int64_t)T * D;
-  uint16_t* y_img = y + (int64_t)T * D7;
-  const uint16_t* mod = bf(d.mod);
-  const int64_t mbs = d.mod_bstride;
-  const float eps = 1e-6f;
-  const float att_scale = 0.08838834764831845f;  // 128^-0.5
-  const int nblk = d.n_double + d.n_single;
-  const int first = d.first_block < 0 ? 0 : d.first_block;
-  const int last = (d.last_block < 0 || d.last_block > nblk) ? nblk : d.last_block;
-  void* q8 = (d.flags & 4) ? d.q8 : nullptr;
-  float* q8s = (d.flags & 4) ? d.q8_scale : nullptr;
-  if ((d.flags & 4) && (!d.q8 || !d.q8_scale)) return fail("dit_forward: fp8 flag set but the q8 workspace is null");
-  const LoraCtx lora_ctx{&d};
-  struct LoraScope { LoraScope(const LoraCtx* c) { g_lora = c; } ~LoraScope() { g_lora = nullptr; } } lora_scope(&lora_ctx);
-
-  if (!(d.flags & 1)) {
-    // x_embedder (transformer_flux.py:1086) straight into the image rows of the joint stream; text rows <- ctx0
-    TRY(Gemm(d.xin, d.in_channels, (int64_t)Sn * d.in_channels, d.x_embedder, d.in_channels, hid_img, D, hid_bs, Sn, D,
-             d.in_channels, B).run(st));
-    if (T > 0) TRY(copy_rows(d.ctx0, D, (int64_t)T * D, hid, D, hid_bs, T, D, B, st));
-  }
-
-  // y = [k | v | q | ...]; RMSNorm + RoPE of q, k on the row range [row0, row0 + rows) as a separate pass (projections that
-  // did not carry it in their epilogue); attention output overwrites q
-  auto norm_rope_rows = [&](int row0, int rows, const void* nq, const void* nk) -> int {
-    if (rows <= 0) return 0;
-    return rmsnorm_rope(y + (int64_t)row0 * D7, D7, y_bs, 2 * D, 0, H, rows, 0, B, nq, nk, nq, nk, d.cos_tab + (int64_t)row0 * 128,
-                        d.sin_tab + (int64_t)row0 * 128, eps, st);
-  };
-  auto attention = [&](float block_bound) -> int {   // the block's own score bound (ABI 6), else the forward-wide one
-    AttnArgs a;
-    a.q = y + 2 * D; a.k = y; a.v = y + D; a.o = y + 2 * D;
-    a.ldq = a.ldk = a.ldv = a.ldo = D7;
-    a.q_bstride = a.k_bstride = a.v_bstride = a.o_bstride = y_bs;
-    a.B = B; a.H = H; a.N = N; a.scale = att_scale; a.score_bound = block_bound > 0.f ? block_bound : d.attn_score_bound;
-    a.workspace = d.gemm_workspace; a.workspace_bytes = d.gemm_workspace_bytes;   // the split-K scratch is idle between GEMMs: stream-K partials
-    return joint_attention(a, st);
-  };
-
-  // LayerNorm + modulation of rows [row0, row0 + rows) of every batch's joint stream, feeding ONE Linear.  bf16 mode:
-  // xn (bf16) then the GEMM.  fp8 mode: the norm writes the e4m3 rows + scales straight into the q8 workspace
-  // (layout [B][N][D] bytes / [B][N]) and the GEMM consumes them -- no bf16 round trip, no separate quantisation pass.
-  // projection of rows [row0, row0 + rows) into y with q/k norm + RoPE: fused into the GEMM epilogue when the shape allows
-  // (persistent kernel, enough tiles to fill the chip unsplit; since round 5 in fp8 mode too), else the GEMM followed by the separate pass
-  const bool may_fuse = d.rope_cs != nullptr;
-  auto fused_here = [&](const Gemm& gm, int row0, const void* nq, const void* nk) -> bool {
-    if (gm.adapted()) return may_fuse;   // the tail launch is never K-sliced: the fused epilogue rides on every adapted projection
-    Gemm t = gm;      // with the scratch the launch will have: a GEMM the auto path K-slices cannot carry the fused epilogue
-    t.scratch(d.gemm_workspace, d.gemm_workspace_bytes);
-    const bool f8 = q8 && gm.fp8_ready();
-    if (f8 && !g_fp8_fuse_qkn) return false;
-    return may_fuse && t.qknorm_ok(nq, nk, d.rope_cs, row0, D, eps, f8);
-  };
-  auto norm_gemm = [&](const uint16_t* src, int row0, int rows, const uint16_t* shift, const uint16_t* scale, Gemm gm) -> int {
-    gm.scratch(d.gemm_workspace, d.gemm_workspace_bytes);
-    if (q8 && gm.fp8_ready()) {
-      uint8_t* q = (uint8_t*)q8 + (int64_t)row0 * D;
-      float* qs = q8s + row0;
-      TRY(ln_modulate_fp8(src, q, qs, shift, scale, mbs, rows, B, D, D, hid_bs, D, hid_bs, N, eps, st));
-      return gm.run_pre(st, q, D, hid_bs, qs, N);
-    }
-    TRY(ln_modulate(src, xn + (int64_t)row0 * D, shift, scale, mbs, rows, B, D, D, hid_bs, D, hid_bs, eps, st));
-    return gm.run(st, q8, q8s);
-  };
-
-  for (int blk = first; blk < last; ++blk) {
-    if (blk < d.n_double) {
-      // ---- FluxTransformerBlock.forward (transformer_flux.py:794-841)
-      const tfx_double_block& w = d.dbl[blk];
-      const uint16_t* mi = mod + (int64_t)blk * 12 * D;  // img: shift_msa scale_msa gate_msa shift_mlp scale_mlp gate_mlp
-      const uint16_t* mt = mi + 6 * D;                   // txt: same six
-      // The text and image projections of the block as ONE launch each over the joint [text | image] rows (row-split weights) when
-      // the text length is a whole number of tiles and the two weight matrices sit in one allocation (the engine's loader puts
-      // them there); else two launches.  bf16 mode only.
-      Gemm jq(xn, D, hid_bs, w.qkv_img, D, y, D7, y_bs, N, 3 * D, D, B);
-      jq.rowsplit(T, w.qkv_txt).qknorm2(w.norm_added_q, w.norm_added_k).scratch(d.gemm_workspace, d.gemm_workspace_bytes);
-      Gemm jo(y + 2 * D, D7, y_bs, w.out_img, D, hid, D, hid_bs, N, D, D, B);
-      jo.gate_res(mi + 2 * D, mbs, hid, D, hid_bs).rowsplit(T, w.out_txt, mt + 2 * D).scratch(d.gemm_workspace, d.gemm_workspace_bytes);
-      Gemm j1(xn, D, hid_bs, w.ff1_img, D, y + 3 * D, D7, y_bs, N, 4 * D, D, B);
-      j1.gelu(0).rowsplit(T, w.ff1_txt).scratch(d.gemm_workspace, d.gemm_workspace_bytes);
-      Gemm j2(y + 3 * D, D7, y_bs, w.ff2_img, 4 * D, hid, D, hid_bs, N, D, 4 * D, B);
-      j2.gate_res(mi + 5 * D, mbs, hid, D, hid_bs).rowsplit(T, w.ff2_txt, mt + 5 * D).scratch(d.gemm_workspace, d.gemm_workspace_bytes);
-      const bool joint = g_group_streams && T > 0 && !q8 && jq.rowsplit_ok() && jo.rowsplit_ok() && j1.rowsplit_ok() && j2.rowsplit_ok();
-      if (joint) {
-        if (g_ln_joint) {   // round 6: both streams' LayerNorm + modulation as ONE launch over the joint rows (text rows: the second modulation)
-          TRY(ln_modulate_split(hid, xn, mi, mi + D, mt, mt + D, T, mbs, N, B, D, D, hid_bs, D, hid_bs, eps, st));
-        } else {
-          TRY(ln_modulate(hid_img, xn_img, mi, mi + D, mbs, Sn, B, D, D, hid_bs, D, hid_bs, eps, st));
-          TRY(ln_modulate(hid, xn, mt, mt + D, mbs, T, B, D, D, hid_bs, D, hid_bs, eps, st));
-        }
-        const bool fj = may_fuse && (jq.adapted() || jq.qknorm_ok(w.norm_q, w.norm_k, d.rope_cs, 0, D, eps));
-        if (fj) jq.qknorm(w.norm_q, w.norm_k, d.rope_cs, 0, D, eps);
-        TRY(jq.run(st));
-        if (!fj)
-          TRY(rmsnorm_rope(y, D7, y_bs, 2 * D, 0, H, N, T, B, w.norm_q, w.norm_k, w.norm_added_q, w.norm_added_k, d.cos_tab, d.sin_tab, eps, st));
-        TRY(attention(w.attn_score_bound));
-        TRY(jo.run(st));                                                      // hidden += gate_msa * to_out(attn), both streams
-        if (g_ln_joint) {
-          TRY(ln_modulate_split(hid, xn, mi + 3 * D, mi + 4 * D, mt + 3 * D, mt + 4 * D, T, mbs, N, B, D, D, hid_bs, D, hid_bs, eps, st));
-        } else {
-          TRY(ln_modulate(hid_img, xn_img, mi + 3 * D, mi + 4 * D, mbs, Sn, B, D, D, hid_bs, D, hid_bs, eps, st));
-          TRY(ln_modulate(hid, xn, mt + 3 * D, mt + 4 * D, mbs, T, B, D, D, hid_bs, D, hid_bs, eps, st));
-        }
-        TRY(j1.run(st));
-        TRY(j2.run(st));
-        continue;
-      }
-      {
-        Gemm gi(xn_img, D, hid_bs, w.qkv_img, D, y_img, D7, y_bs, Sn, 3 * D, D, B);
-        const bool fi = fused_here(gi, T, w.norm_q, w.norm_k);
-        if (fi) gi.qknorm(w.norm_q, w.norm_k, d.rope_cs, T, D, eps);
-        TRY(norm_gemm(hid_img, T, Sn, mi, mi + D, gi));
-        if (!fi) TRY(norm_rope_rows(T, Sn, w.norm_q, w.norm_k));
-        if (T > 0) {
-          Gemm gt(xn, D, hid_bs, w.qkv_txt, D, y, D7, y_bs, T, 3 * D, D, B);
-          const bool ft = fused_here(gt, 0, w.norm_added_q, w.norm_added_k);
-          if (ft) gt.qknorm(w.norm_added_q, w.norm_added_k, d.rope_cs, 0, D, eps);
-          TRY(norm_gemm(hid, 0, T, mt, mt + D, gt));
-          if (!ft) TRY(norm_rope_rows(0, T, w.norm_added_q, w.norm_added_k));
-        }
-      }
-      TRY(attention(w.attn_score_bound));
-      // hidden += gate_msa * to_out(attn)   (:817-818, 830-831)
-      TRY(Gemm(y_img + 2 * D, D7, y_bs, w.out_img, D, hid_img, D, hid_bs, Sn, D, D, B)
-              .gate_res(mi + 2 * D, mbs, hid_img, D, hid_bs).scratch(d.gemm_workspace, d.gemm_workspace_bytes).run(st, q8, q8s));
-      if (T > 0)
-        TRY(Gemm(y + 2 * D, D7, y_bs, w.out_txt, D, hid, D, hid_bs, T, D, D, B)
-                .gate_res(mt + 2 * D, mbs, hid, D, hid_bs).scratch(d.gemm_workspace, d.gemm_workspace_bytes).run(st, q8, q8s));
-      // MLP: norm2 * (1 + scale_mlp) + shift_mlp -> ff -> gated residual (:820-826, 833-837)
-      TRY(norm_gemm(hid_img, T, Sn, mi + 3 * D, mi + 4 * D,
-                    Gemm(xn_img, D, hid_bs, w.ff1_img, D, y_img + 3 * D, D7, y_bs, Sn, 4 * D, D, B).gelu(0)));
-      if (T > 0)
-        TRY(norm_gemm(hid, 0, T, mt + 3 * D, mt + 4 * D, Gemm(xn, D, hid_bs, w.ff1_txt, D, y + 3 * D, D7, y_bs, T, 4 * D, D, B).gelu(0)));
-      TRY(Gemm(y_img + 3 * D, D7, y_bs, w.ff2_img, 4 * D, hid_img, D, hid_bs, Sn, D, 4 * D, B)
-              .gate_res(mi + 5 * D, mbs, hid_img, D, hid_bs).scratch(d.gemm_workspace, d.gemm_workspace_bytes).run(st, q8, q8s));
-      if (T > 0)
-        TRY(Gemm(y + 3 * D, D7, y_bs, w.ff2_txt, 4 * D, hid, D, hid_bs, T, D, 4 * D, B)
-                .gate_res(mt + 5 * D, mbs, hid, D, hid_bs).scratch(d.gemm_workspace, d.gemm_workspace_bytes).run(st, q8, q8s));
-    } else {
-      // ---- FluxSingleTransformerBlock.forward (transformer_flux.py:715-739) on the joint [text | image] sequence
-      const int j = blk - d.n_double;
-      const tfx_single_block& w = d.sgl[j];
-      const uint16_t* ms = mod + (int64_t)d.n_double * 12 * D + (int64_t)j * 3 * D;  // shift scale gate
-      {
-        Gemm gs = Gemm(xn, D, hid_bs, w.qkv_mlp, D, y, D7, y_bs, N, 7 * D, D, B).gelu(3 * D);
-        const bool fs = fused_here(gs, 0, w.norm_q, w.norm_k);
-        if (fs) gs.qknorm(w.norm_q, w.norm_k, d.rope_cs, 0, D, eps);
-        TRY(norm_gemm(hid, 0, N, ms, ms + D, gs));
-        if (!fs) TRY(norm_rope_rows(0, N, w.norm_q, w.norm_k));
-      }
-      TRY(attention(w.attn_score_bound));
-      TRY(Gemm(y + 2 * D, D7, y_bs, w.proj_out, 5 * D, hid, D, hid_bs, N, D, 5 * D, B)
-              .gate_res(ms + 2 * D, mbs, hid, D, hid_bs).scratch(d.gemm_workspace, d.gemm_workspace_bytes).run(st, q8, q8s));
-    }
-  }
-
-  if (!(d.flags & 2)) {
-    // norm_out (AdaLayerNormContinuous: chunk order scale, shift) + proj_out on the image rows (:1200-1203)
-    const uint16_t* mo = mod + (int64_t)d.n_double * 12 * D + (int64_t)d.n_single * 3 * D;
-    TRY(ln_modulate(hid_img, xn_img, mo + D, mo, mbs, Sn, B, D, D, hid_bs, D, hid_bs, eps, st));
-    if (d.euler_gate) {
-      // flow-matching Euler step in the epilogue: x' = x + bf16(dsigma * bf16(v)), in place on the latent columns of xin
-      // (gate = the step's dsigma in every column, residual = output = xin[:, :, :out_channels])
-      void* lat = const_cast<void*>(d.xin);
-      const int64_t xbs = (int64_t)Sn * d.in_channels;
-      TRY(Gemm(xn_img, D, hid_bs, d.proj_out, D, lat, d.in_channels, xbs, Sn, d.out_channels, D, B)
-              .gate_res(d.euler_gate, d.euler_gate_bstride, lat, d.in_channels, xbs).run(st));
-    } else {
-      TRY(Gemm(xn_img, D, hid_bs, d.proj_out, D, d.out, d.out_channels, (int64_t)Sn * d.out_channels, Sn, d.out_channels,
-               D, B).run(st));
-    }
-  }
-  return 0;
-}
 
 }  // namespace
 
@@ -737,10 +426,10 @@ int tfx_set_option(const char* name, int value) {
     set_gemm_waves(value);
     return 0;
   }
-  if (!std::strcmp(name, "gemm_group_streams")) { g_group_streams = value; return 0; }
-  if (!std::strcmp(name, "ln_joint")) { g_ln_joint = value; return 0; }
+  if (!std::strcmp(name, "gemm_group_streams")) { set_gemm_group_streams(value); return 0; }
+  if (!std::strcmp(name, "ln_joint")) { set_ln_joint(value); return 0; }
   if (!std::strcmp(name, "ln_prefetch")) { set_ln_prefetch(value); return 0; }
-  if (!std::strcmp(name, "fp8_fuse_qkn")) { g_fp8_fuse_qkn = value; return 0; }
+  if (!std::strcmp(name, "fp8_fuse_qkn")) { set_fp8_fuse_qkn(value); return 0; }
   if (!std::strcmp(name, "gemm_splitk")) { set_gemm_splitk(value); return 0; }
   if (!std::strcmp(name, "attention_ablation")) { set_attention_ablation(value); return 0; }  // bench-only
   return fail("tfx_set_option: unknown option '%s'", name);

@@ -5,6 +5,8 @@
 
 #include <atomic>
 
+struct tfx_dit_desc;   // include/textflux_hip.h
+
 namespace tfx {
 
 // Error plumbing: every launcher returns 0 on success; on failure the message is kept per thread and is
@@ -154,17 +156,17 @@ int attention_w4_prepare(hipStream_t st);                      // allocates the 
 void set_attention_tail_split(int v);                          // 0 = never split the last round's q-tiles by keys (bench knob)
 int joint_attention_w4(const AttnArgs& a, hipStream_t st, int mode);   // one wave per SIMD, 64 query rows per wave (attention_w4.hip); mode (attn_w4_kernel<MODE>): 0 bookkeeping on the matrix pipe, 1 row sums on the VALU, 2 = 1 + lazy reference offset, 3 = 0 + lazy reference offset, 4 no reference at all (only when AttnArgs::score_bound is admissible, attention.hip)
 void set_attention_ablation(int a);
-void set_attention_use_bound(int v);
+void set_attention_use_bound(int v);      // 0: ignore AttnArgs::score_bound
 int attention_mode_counts(int64_t* counts, int n, int reset);   // tfx_attention_mode_counts
 void attention_note_streamk();                                   // counts[8]: a w4 launch whose last round ran as the stream-K tail
 int blend_edge(const void* a, int64_t a_bs, int64_t a_ts, int64_t a_us, void* b, int64_t b_bs, int64_t b_ts, int64_t b_us, int batch,
                int extent, int len, int C, hipStream_t st);
 int gate_residual(const void* x, int64_t ldx, int64_t x_bs, const void* gate, int64_t gate_bs, const void* res, int64_t ldr, int64_t r_bs,
-                  void* out, int64_t ldo, int64_t o_bs, int rows, int batch, int D, hipStream_t st);   // 0: ignore AttnArgs::score_bound
+                  void* out, int64_t ldo, int64_t o_bs, int rows, int batch, int D, hipStream_t st);   // out = res + bf16(gate[b, :] * x) (tfx_gate_residual)
 void set_attention_streamk(int v);     // 0: whole (b, h, q-tile) items only; 1 (default): stream-K dealing when it pays and a workspace was passed; 2: whenever admissible
 void set_attention_persistent(int v);  // 0: one workgroup per (b, h, q-tile) item instead of one per CU
 void set_attention_debug(void* p);
-void set_attention_waves(int nw);  // 8 (one 512-thread workgroup per CU) or 4 (two independent 256-thread workgroups)
+void set_attention_waves(int nw);  // which attention kernel joint_attention launches: the values of tfx_set_option "attention_waves" (textflux_hip.h), 0 = the default (30)
 
 int groupnorm_silu_nhwc(const void* x, void* out, const void* gamma, const void* beta, float* stats_ws, int B,
                         int64_t HW, int C, int groups, float eps, bool silu, hipStream_t st);
@@ -218,5 +220,12 @@ int mul_act(const void* a, int64_t lda, const void* b, int64_t ldb, void* out, i
             hipStream_t st);
 int select_step(const void* table, void* cur, int64_t per_step_elems, int* step_ptr, hipStream_t st);
 int advance_step(int* step_ptr, hipStream_t st);
+
+// One DiT forward on the launchers above (dit_forward.cpp; tfx_dit_forward checks the descriptor's pointers in front of it) and its
+// process-wide A/B knobs (tfx_set_option fp8_fuse_qkn / ln_joint / gemm_group_streams, all default 1).
+int dit_forward(const tfx_dit_desc& d, hipStream_t st);
+void set_fp8_fuse_qkn(int v);
+void set_ln_joint(int v);
+void set_gemm_group_streams(int v);
 
 }  // namespace tfx

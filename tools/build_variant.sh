@@ -8,7 +8,7 @@ name=$1; extra=$2; shift 2
 root=$(cd "$(dirname "$0")/.." && pwd); src=$root/textflux_amd/csrc; bd=/tmp/tfx_var_$name; mkdir -p $bd
 declare -A ov; for kv in "$@"; do ov[${kv%%=*}]=${kv#*=}; done
 objs=""
-for f in elementwise.hip imageops.hip gemm.hip attention.hip attention_w4.hip textenc.hip capi.cpp launch.cpp; do
+for f in elementwise.hip imageops.hip gemm.hip attention.hip attention_w4.hip textenc.hip capi.cpp dit_forward.cpp launch.cpp; do
   s=${ov[$f]:-$src/$f}; o=$bd/${f%.*}.o; fl=""
   [ $f = attention_w4.hip ] && fl="-mllvm -amdgpu-mfma-vgpr-form"
   /opt/rocm/bin/hipcc -O3 -std=c++17 -fPIC --offload-arch=gfx950 -Wno-unused-result -I$src -I$root/include $fl $extra -c $s -o $o &
