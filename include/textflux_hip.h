@@ -33,7 +33,7 @@ const char* tfx_last_error(void);
  * two since ABI 6) and returns how many values there are.  A binding
  * compares them with its own view of this header BEFORE the first call that passes a struct: a library built from an older
  * header would otherwise ignore the tail fields of a grown struct silently (no reference counterpart: the reference has no FFI). */
-#define TFX_ABI_VERSION 9
+#define TFX_ABI_VERSION 10
 int tfx_abi_info(int32_t* out, int n);
 /* Writes the gcnArchName of the current device (e.g. "gfx950:sramecc+:xnack-") into buf.  Needs a GPU. */
 int tfx_query_arch(char* buf, int buflen);
@@ -87,6 +87,10 @@ typedef struct tfx_qkn_args {
   const float* rope_cs;
   int32_t pos0, q0, q1, k0, k1;
   float eps;
+  /* ABI 10, mixed-geometry batches: one rotary table per batch sample, rope_bstride table ROWS apart -- output row m of sample b uses
+   * table row b * rope_bstride + pos0 + m; 0 = one table for every sample (what the reference computes: one img_ids per call,
+   * transformer_flux.py:1117-1126).  The fp8 form of the epilogue inside tfx_dit_forward takes the same stride. */
+  int64_t rope_bstride;
 } tfx_qkn_args;
 int tfx_gemm_bf16_qkn(const tfx_gemm_args* args, const tfx_qkn_args* qkn, tfx_stream stream);
 
@@ -157,6 +161,14 @@ int tfx_rmsnorm_rope(void* buf, int64_t ld, int64_t bstride, int32_t q_off, int3
                      int32_t T, int32_t B, const void* wq_img, const void* wk_img, const void* wq_txt,
                      const void* wk_txt, const float* cos_tab, const float* sin_tab, float eps, tfx_stream stream);
 
+/* ABI 10, mixed-geometry batches: the same pass with one cos / sin table per batch sample -- sample b reads cos_tab / sin_tab +
+ * b * tab_bstride (fp32 elements, a multiple of 4; 0 = tfx_rmsnorm_rope).  No reference counterpart: the reference runs one geometry
+ * per call. */
+int tfx_rmsnorm_rope_batched(void* buf, int64_t ld, int64_t bstride, int32_t q_off, int32_t k_off, int32_t H, int32_t Ntok,
+                             int32_t T, int32_t B, const void* wq_img, const void* wk_img, const void* wq_txt,
+                             const void* wk_txt, const float* cos_tab, const float* sin_tab, int64_t tab_bstride, float eps,
+                             tfx_stream stream);
+
 /* the name SURVEY.md §8(b) lists for the same entry point (q AND k of one fused buffer): identical arguments and behaviour */
 int tfx_rmsnorm_rope_qk(void* buf, int64_t ld, int64_t bstride, int32_t q_off, int32_t k_off, int32_t H, int32_t Ntok,
                         int32_t T, int32_t B, const void* wq_img, const void* wk_img, const void* wq_txt,
@@ -200,6 +212,16 @@ typedef struct tfx_attn_args {
    * (item, 64-key tile) units to the CUs instead of whole (b, h, 256-query) items ("attention_streamk", tfx_set_option) when that fills
    * the chip better; contents are scratch, the launch's own stream orders its uses.  tfx_dit_forward passes the split-K scratch. */
   void* workspace; int64_t workspace_bytes;
+  /* optional (ABI 10; NULL = every sample has N rows), mixed-geometry batches: DEVICE int32 [B], sample b's valid length L = seq_len[b].
+   * Queries [0, L) attend to keys [0, L); K / V rows >= L are never read (the sample's buffer descriptors end at row L, so a ragged
+   * last key tile masks as a ragged N does), rows >= L of o are not written, and (b, h, 256-query) items that start at or beyond L are
+   * skipped.  Sample b computes, bit for bit, what a launch with B = 1, N = L on its rows computes in whole-item form.  The lengths
+   * are read by the kernel when it runs: a captured graph sees new lengths without re-capture; each value is clamped to [1, N]
+   * before use, so a bad value cannot address outside the operands.  Launch form: whole items only -- neither the stream-K dealing
+   * nor the tail split is taken (tfx_attention_mode_counts entry 8 stays 0 for such launches); score_bound is judged with the
+   * launch N; "attention_waves" 30 (the default kernel) only, any other value with seq_len is refused.  No reference counterpart:
+   * the reference pads nothing, it runs one geometry per call. */
+  const int32_t* seq_len;
 } tfx_attn_args;
 int tfx_joint_attention(const tfx_attn_args* args, tfx_stream stream);
 
@@ -306,6 +328,20 @@ typedef struct tfx_dit_desc {
    * caller derives it from the q / k RMSNorm weights: 128 * max|w_q| * max|w_k| * 128^-0.5 (text-stream norms included), see
    * tfx_attn_args; since ABI 6 the per-block fields are the ones the engine fills. */
   float attn_score_bound;
+  /* ABI 10, mixed-geometry batches (NULL / 0 = every sample has S image rows: the forward then issues exactly the launches it
+   * always did).  Placement: in front of the runtime-LoRA fields, not behind them -- those three are addressed as the struct's LAST
+   * fields by bindings written against ABI 9 (this repository's own ctypes mirror is checked for it), so the struct grows in front of
+   * them; either way offsets or size change, and a library and a binding of different ABI versions refuse each other (tfx_abi_info).
+   * Sample b's rows are [T text rows | S_b image rows | padding]: S is the PADDED image row count (T + S a multiple of 256 keeps
+   * the GEMMs on whole tiles), seq_len a DEVICE int32 [B] holding T + S_b, read by the attention kernel at run time (tfx_attn_args.seq_len;
+   * a captured step graph serves every mix of lengths up to its size).  rope_bstride: table rows between two samples' rotary tables in
+   * cos_tab / sin_tab / rope_cs (each [B][>= T + S rows]), passed to every fused q | k | v projection (tfx_qkn_args.rope_bstride) and to
+   * the separate norm + RoPE pass (tfx_rmsnorm_rope_batched); required (> 0) with seq_len.  Everything else of the forward is row-wise:
+   * padded rows of xin / hid hold unspecified values, influence no valid row, and their rows of out / xin mean nothing.  fp8 linears
+   * and runtime LoRA adapters work unchanged.  In a tfx_dit_step_* call seq_len needs sampler 2: only the fused Euler form carries
+   * per-sample coefficients (the dsigma rows of euler_gate), and a sample's sigma schedule depends on its own S_b
+   * (calculate_shift, D/pipelines/flux/pipeline_flux_fill.py:1980-1990). */
+  const int32_t* seq_len; int64_t rope_bstride;
   /* ABI 9: scratch and factors of the runtime LoRA adapters (required when any block Linear carries lora_a).  lora_t_xn / lora_t_y hold
    * the down projections T of Linears whose input lives in xn / in y: T of input A sits at A + (lora_t_xn - xn) resp. A + (lora_t_y - y),
    * so each region mirrors its buffer's shape -- lora_t_xn: 1 (D >= 1024) or 4 (smaller D: one per segment) matrices [B][N, D],

@@ -67,6 +67,8 @@ def build_parser(lora: bool = False):
     ap.add_argument("--scheduler", type=str, default="overshoot" if lora else "", help='Sampler, None or "overshoot"')
     # not in the reference: batching, and the {image, mask, text} list interface of the earlier rounds
     ap.add_argument("--batch_size", type=int, default=8, help="same-geometry images per pipeline call")
+    ap.add_argument("--mixed_pad", type=float, default=0.0, help="let images of different sizes share a batch while at most this share of "
+                    "its transformer rows is padding (Euler sampler only; 0 = same-geometry batches only)")
     ap.add_argument("--items", type=str, default=None, help="JSON list of {image, mask, text} instead of --json_path")
     ap.add_argument("--out", type=str, default=None, help="output folder of --items mode")
     ap.add_argument("--num_inference_steps", type=int, default=None, help=argparse.SUPPRESS)
@@ -116,6 +118,8 @@ def load_lora_transformer(lora_weights_path, base_transformer=None, lora_runtime
 
 def main(argv=None, lora: bool = False, script: str = __file__):
     a = build_parser(lora).parse_args(argv)
+    if a.mixed_pad > 0 and a.scheduler == "overshoot":
+        raise SystemExit("--mixed_pad needs the Euler sampler: mixed-geometry batches carry per-sample coefficients only in the fused Euler step")
     legacy = a.items is not None
     weights = a.lora_weights_path if lora else a.weights_path
     if not legacy and not (a.json_path and a.original_images_dir and weights):
@@ -174,7 +178,8 @@ def main(argv=None, lora: bool = False, script: str = __file__):
         ri.use_overshoot_sampler(pipe)
     pipe.enable_hip_graph(True)
     res = batch_driver.run_items(items, pipe, out_dir, batch_size=a.batch_size, num_inference_steps=steps,
-                                 guidance_scale=a.guidance_scale, seed=a.seed, device=f"cuda:{local}", eval_cfg=eval_cfg)
+                                 guidance_scale=a.guidance_scale, seed=a.seed, device=f"cuda:{local}", eval_cfg=eval_cfg,
+                                 mixed_pad=a.mixed_pad)
     print(f"[rank {rank}] {len(res['done'])} images written" + (f"; {len(res['all_done'])}/{len(items)} in total, "
           f"{res['batches']} batches in {res['rounds']} rounds, prompts encoded {res['encode']}" if rank == 0 else ""))
     if rank == 0:

@@ -21,7 +21,7 @@ c_void_p, c_int, c_int32, c_int64, c_float, c_char_p = C.c_void_p, C.c_int, C.c_
 # TFX_ABI_VERSION of the include/textflux_hip.h the ctypes mirrors below were written against (tests/test_capi_symbols.py asserts
 # that it equals the header's): the library's stamp is compared with THIS constant, so a binding copied without include/ still
 # loads, and a ctypes mirror edited without the header (or the other way round) fails a test instead of passing the check.
-ABI_VERSION = 9
+ABI_VERSION = 10
 
 
 class GemmArgs(C.Structure):
@@ -42,7 +42,7 @@ class GemmArgs(C.Structure):
 
 class QknArgs(C.Structure):
     _fields_ = [("norm_q", c_void_p), ("norm_k", c_void_p), ("rope_cs", c_void_p), ("pos0", c_int32), ("q0", c_int32), ("q1", c_int32),
-                ("k0", c_int32), ("k1", c_int32), ("eps", c_float)]
+                ("k0", c_int32), ("k1", c_int32), ("eps", c_float), ("rope_bstride", c_int64)]
 
 
 class LoraArgs(C.Structure):
@@ -58,6 +58,7 @@ class AttnArgs(C.Structure):
         ("q_bstride", c_int64), ("k_bstride", c_int64), ("v_bstride", c_int64), ("o_bstride", c_int64),
         ("B", c_int32), ("H", c_int32), ("N", c_int32), ("scale", c_float), ("score_bound", c_float),
         ("workspace", c_void_p), ("workspace_bytes", c_int64),
+        ("seq_len", c_void_p),
     ]
 
 
@@ -95,6 +96,7 @@ class DitDesc(C.Structure):
         ("rope_cs", c_void_p),
         ("euler_gate", c_void_p), ("euler_gate_bstride", c_int64),
         ("attn_score_bound", c_float),
+        ("seq_len", c_void_p), ("rope_bstride", c_int64),
         ("lora_t_xn", c_void_p), ("lora_t_y", c_void_p), ("lora_scale", c_void_p),
     ]
 
@@ -126,6 +128,8 @@ SIGNATURES = {
                                  c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_void_p]),
     "tfx_rmsnorm_rope_qk": (c_int, [c_void_p, c_int64, c_int64, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32,
                                     c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_void_p]),
+    "tfx_rmsnorm_rope_batched": (c_int, [c_void_p, c_int64, c_int64, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32,
+                                         c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_float, c_void_p]),
     "tfx_gate_residual": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int64,
                                   c_int32, c_int32, c_int32, c_void_p]),
     "tfx_blend_edge_nhwc": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_int64, c_int64, c_int64, c_int32, c_int32, c_int32,

@@ -52,8 +52,9 @@ class Work:
 
 @dataclass
 class Batch:
-    size: Tuple[int, int]
+    size: Tuple[int, int]            # (width, height) of the items; of the item with the most tokens when `mixed`
     items: List[Work] = field(default_factory=list)
+    mixed: bool = False              # items of different sizes: one padded forward per step (FluxFillPipeline.call_mixed)
 
 
 def eval_item_complete(item: Dict[str, Any]) -> bool:
@@ -141,9 +142,43 @@ def _batch_inputs(items: Sequence[Work], device):
     return imgs, masks
 
 
-def plan_batches(works: Sequence[Work], batch_size: int) -> List[Batch]:
+def image_tokens(size: Tuple[int, int]) -> int:
+    """Image tokens of a (width, height) pipeline size: one per 16 x 16 pixels (8x VAE, 2 x 2 patches)."""
+    return (size[0] // 16) * (size[1] // 16)
+
+
+def pad_fraction(sizes: Sequence[Tuple[int, int]], text_tokens: int = 512) -> float:
+    """Share of a batch's transformer rows that are padding: 1 - sum(L_b) / (B * N), L_b = text_tokens + image tokens of item b,
+    N = the longest L_b rounded up to a multiple of 256 (call_mixed's launch length).  0 for a batch of one size: it runs unpadded on
+    the uniform path."""
+    if len(set(tuple(s) for s in sizes)) <= 1:
+        return 0.0
+    lens = [text_tokens + image_tokens(s) for s in sizes]
+    n = (max(lens) + 255) // 256 * 256
+    return 1.0 - sum(lens) / (len(lens) * n)
+
+
+def plan_batches(works: Sequence[Work], batch_size: int, max_pad_fraction: float = 0.0, text_tokens: int = 512) -> List[Batch]:
     """Same-geometry batches of up to batch_size items, deterministic (every rank computes the same plan): geometries in
-    order of first appearance, items in list order."""
+    order of first appearance, items in list order.
+    max_pad_fraction > 0: items of different sizes may share a batch (Batch.mixed; FluxFillPipeline.call_mixed pads their rows to
+    the longest).  Greedy over the items sorted by image token count (stable: ties keep list order): the next item joins the open
+    batch unless the batch is full or pad_fraction of the batch with it would exceed the cap, in which case the batch is closed.
+    text_tokens: the T5 sequence length every item carries (max_sequence_length)."""
+    if max_pad_fraction < 0 or max_pad_fraction >= 1:
+        raise ValueError("max_pad_fraction must be in [0, 1)")
+    if max_pad_fraction > 0:
+        out: List[Batch] = []
+        cur: List[Work] = []
+        close = lambda: out.append(Batch(cur[-1].size, list(cur), mixed=len({w.size for w in cur}) > 1))
+        for w in sorted(works, key=lambda w: image_tokens(w.size)):
+            if cur and (len(cur) >= batch_size or pad_fraction([x.size for x in cur] + [w.size], text_tokens) > max_pad_fraction):
+                close()
+                cur = []
+            cur.append(w)
+        if cur:
+            close()
+        return out
     by_size: Dict[Tuple[int, int], List[Work]] = {}
     for w in works:
         by_size.setdefault(w.size, []).append(w)
@@ -177,13 +212,22 @@ def _flag_min(v: int, device) -> int:
 def run_items(items: Sequence[Dict[str, Any]], pipe, out_dir: Optional[str], batch_size: int = 8, num_inference_steps: int = 30,
               guidance_scale: float = 30.0, seed: int = 42, device="cuda", loader: Optional[Callable] = None,
               save: Optional[Callable] = None, max_sequence_length: int = 512, eval_cfg: Optional[Dict[str, Any]] = None,
-              encode: str = "auto", save_full: Optional[Callable] = None) -> Dict[str, Any]:
+              encode: str = "auto", save_full: Optional[Callable] = None, mixed_pad: float = 0.0) -> Dict[str, Any]:
     """Runs the whole list; returns {"done": [indices this rank wrote], "failed": [...], "all_done": [...] on rank 0,
     "encode": "local" | "rank0"}.  `pipe` needs `encode_prompt(prompt, prompt_2, ...)` and the FluxFillPipeline `__call__`.
     encode: "local" = every rank encodes the T5 prompts of its own batches (needs a T5 on every rank), "rank0" = rank 0
     encodes for all and scatters, "auto" = local when every rank has `pipe.text_encoder_2`, else rank0.
     Outputs: eval-schema items (Work.name set) are written as out_dir/full_images/<name> and out_dir/cropped_images/<name>
-    (or handed to save_full(work, full, cropped)); other items as out_dir/<index>.png (or save(index, cropped))."""
+    (or handed to save_full(work, full, cropped)); other items as out_dir/<index>.png (or save(index, cropped)).
+    mixed_pad: plan_batches' max_pad_fraction -- > 0 lets items of different sizes share a batch (pipe.call_mixed) as long as at
+    most that share of the batch's rows is padding; 0 (default) = same-geometry batches only."""
+    if mixed_pad > 0:            # refused before anything is prepared or encoded, not batch by batch inside the loop
+        if not hasattr(pipe, "call_mixed"):
+            raise ValueError("mixed_pad > 0 needs a pipeline with call_mixed (FluxFillPipeline)")
+        from .schedulers import StochasticRFOvershotDiscreteScheduler
+        if isinstance(getattr(pipe, "scheduler", None), StochasticRFOvershotDiscreteScheduler):
+            raise NotImplementedError("mixed_pad > 0 needs the Euler sampler: mixed-geometry batches carry per-sample coefficients only "
+                                      "in the fused Euler step (the AMO sampler's are per step); use mixed_pad=0")
     rank = dist.get_rank() if dist.is_initialized() else 0
     world = dist.get_world_size() if dist.is_initialized() else 1
     works, failed = [], []
@@ -195,7 +239,7 @@ def run_items(items: Sequence[Dict[str, Any]], pipe, out_dir: Optional[str], bat
             failed.append(i)
             if rank == 0:
                 print(f"item {i} failed in preparation: {e}")
-    plan = plan_batches(works, batch_size)
+    plan = plan_batches(works, batch_size, mixed_pad, text_tokens=max_sequence_length)
     rounds = (len(plan) + world - 1) // world
     if encode == "auto":
         has_t5 = 1 if (getattr(pipe, "text_encoder_2", None) is not None or getattr(pipe, "encodes_locally", False)) else 0
@@ -272,12 +316,19 @@ def run_items(items: Sequence[Dict[str, Any]], pipe, out_dir: Optional[str], bat
             boxes = [glyph.crop_box(w.size, w.meta) for w in mine.items]
             keep_full = any(w.name is not None for w in mine.items)   # eval schema: the uncropped result is an output too
             same_box = all(bx == boxes[0] for bx in boxes)      # one crop window for the whole batch: applied on the device
-            kw = dict(output_crop=boxes[0]) if same_box and not keep_full and getattr(pipe, "supports_output_crop", False) else {}
+            kw = (dict(output_crop=boxes[0]) if same_box and not keep_full and not mine.mixed and getattr(pipe, "supports_output_crop", False)
+                  else {})
             img_in, mask_in = _batch_inputs(mine.items, device)
-            images = pipe(height=mine.size[1], width=mine.size[0], image=img_in,
-                          mask_image=mask_in, num_inference_steps=num_inference_steps, generator=gens,
-                          max_sequence_length=max_sequence_length, guidance_scale=guidance_scale,
-                          prompt_embeds=pe_mine[:n], pooled_prompt_embeds=pooled1.expand(n, -1).contiguous(), **kw).images
+            if mine.mixed:          # items of different sizes: one padded forward per step, every item at its own size
+                images = pipe.call_mixed(image=img_in, mask_image=mask_in, sizes=[w.size for w in mine.items],
+                                         num_inference_steps=num_inference_steps, generator=gens,
+                                         max_sequence_length=max_sequence_length, guidance_scale=guidance_scale,
+                                         prompt_embeds=pe_mine[:n], pooled_prompt_embeds=pooled1.expand(n, -1).contiguous()).images
+            else:
+                images = pipe(height=mine.size[1], width=mine.size[0], image=img_in,
+                              mask_image=mask_in, num_inference_steps=num_inference_steps, generator=gens,
+                              max_sequence_length=max_sequence_length, guidance_scale=guidance_scale,
+                              prompt_embeds=pe_mine[:n], pooled_prompt_embeds=pooled1.expand(n, -1).contiguous(), **kw).images
             for w, img, bx in zip(mine.items, images, boxes):
                 cropped = img if kw else img.crop(bx)
                 if w.name is not None and (save_full is not None or (save is None and out_dir is not None)):

@@ -823,6 +823,10 @@ int joint_attention(const AttnArgs& a, hipStream_t st) {
     return fail("attention: strides must be multiples of 8 elements (q,k,v) / 4 (o)");
   if (((uintptr_t)a.q | (uintptr_t)a.k | (uintptr_t)a.v) % 16 || (uintptr_t)a.o % 8)
     return fail("attention: q/k/v must be 16-byte aligned, o 8-byte aligned");
+  // per-sample lengths (mixed-geometry batches) are a form of kernel 30 alone
+  if (a.seq_len && g_attn_waves != 30)
+    return fail("attention: seq_len (per-sample lengths) is served by kernel 30 only, attention_waves is %d", g_attn_waves);
+  if (a.seq_len && (uintptr_t)a.seq_len % 4) return fail("attention: seq_len must be 4-byte aligned");
 #ifdef TFX_BENCH
   if (g_attn_waves == 20 && !g_attn_abl) {   // half-tile software-pipelined kernel
     ProfScope prof(1, 4.0 * a.B * a.H * (double)a.N * a.N * HD, st);
@@ -841,6 +845,8 @@ int joint_attention(const AttnArgs& a, hipStream_t st) {
   // 2.23 GHz where 30 sustains 1.95) -- but ~9 % more wave cycles per tile (474 instructions against 358), and inside the DiT step
   // the clock is set by the power-capped GEMMs around it (~1.7 GHz): there cycles decide and 40 measures 2 % SLOWER per forward
   // (tools/dit_ab.py attention_waves=30,40: 481.5 vs 471.1 ms).  Kept selectable, not the default.
+  if (a.seq_len && !w4_ok)
+    return fail("attention: seq_len needs kernel 30's layout: 16-byte aligned output rows and one head's K / V rows addressable in 32 bits");
 #ifdef TFX_BENCH
   if (g_attn_waves == 40 && w4_ok) {     // same output-store and descriptor constraints as 30
     ProfScope prof(1, 4.0 * a.B * a.H * (double)a.N * a.N * HD, st);

@@ -74,12 +74,13 @@ static int attach_qkn(const char* who, GemmArgs& a, const tfx_qkn_args* q) {
     return fail("%s: norm weights and the rotary table must be 16-byte aligned", who);
   if (q->q0 < 0 || q->q1 < q->q0 || q->q1 > a.N || q->k0 < 0 || q->k1 < q->k0 || q->k1 > a.N || q->pos0 < 0)
     return fail("%s: column ranges outside [0, N)", who);
+  if (q->rope_bstride < 0) return fail("%s: rope_bstride must not be negative", who);
   if (a.epilogue != EPI_BIAS && a.epilogue != EPI_BIAS_GELU)
     return fail("%s: with q/k norm the epilogue must be 0 (bias) or 1 (bias + GELU from a column)", who);
   if (a.epilogue == EPI_BIAS) a.gelu_from_col = (a.N + 255) / 256 * 256;
   a.epilogue = EPI_BIAS_GELU;
   a.gate = nullptr; a.gate_bstride = 0; a.res = nullptr; a.ldr = 0; a.r_bstride = 0;
-  a.qkn_wq = q->norm_q; a.qkn_wk = q->norm_k; a.qkn_rope_cs = q->rope_cs; a.qkn_pos0 = q->pos0;
+  a.qkn_wq = q->norm_q; a.qkn_wk = q->norm_k; a.qkn_rope_cs = q->rope_cs; a.qkn_pos0 = q->pos0; a.qkn_rope_bstride = q->rope_bstride;
   a.qkn_q0 = q->q0; a.qkn_q1 = q->q1; a.qkn_k0 = q->k0; a.qkn_k1 = q->k1; a.qkn_eps = q->eps;
   return 0;
 }
@@ -189,6 +190,17 @@ int tfx_rmsnorm_rope(void* buf, int64_t ld, int64_t bstride, int32_t q_off, int3
                       eps, S(stream));
 }
 
+int tfx_rmsnorm_rope_batched(void* buf, int64_t ld, int64_t bstride, int32_t q_off, int32_t k_off, int32_t H, int32_t Ntok,
+                             int32_t T, int32_t B, const void* wq_img, const void* wk_img, const void* wq_txt,
+                             const void* wk_txt, const float* cos_tab, const float* sin_tab, int64_t tab_bstride, float eps,
+                             tfx_stream stream) {
+  if (!buf || !wq_img || !wk_img || !wq_txt || !wk_txt || !cos_tab || !sin_tab) return fail("tfx_rmsnorm_rope_batched: null pointer");
+  if (ld % 8 || bstride % 8 || q_off % 8 || k_off % 8) return fail("tfx_rmsnorm_rope_batched: offsets/strides must be multiples of 8");
+  if (tab_bstride < 0 || tab_bstride % 4) return fail("tfx_rmsnorm_rope_batched: tab_bstride must be a non-negative multiple of 4 floats");
+  return rmsnorm_rope_tab(buf, ld, bstride, q_off, k_off, H, Ntok, T, B, wq_img, wk_img, wq_txt, wk_txt, cos_tab, sin_tab,
+                          tab_bstride, eps, S(stream));
+}
+
 int tfx_rmsnorm_rope_qk(void* buf, int64_t ld, int64_t bstride, int32_t q_off, int32_t k_off, int32_t H, int32_t Ntok,
                         int32_t T, int32_t B, const void* wq_img, const void* wk_img, const void* wq_txt,
                         const void* wk_txt, const float* cos_tab, const float* sin_tab, float eps, tfx_stream stream) {
@@ -231,6 +243,7 @@ int tfx_joint_attention(const tfx_attn_args* g, tfx_stream stream) {
   a.q_bstride = g->q_bstride; a.k_bstride = g->k_bstride; a.v_bstride = g->v_bstride; a.o_bstride = g->o_bstride;
   a.B = g->B; a.H = g->H; a.N = g->N; a.scale = g->scale; a.score_bound = g->score_bound;
   a.workspace = g->workspace; a.workspace_bytes = g->workspace ? g->workspace_bytes : 0;
+  a.seq_len = g->seq_len;
   return joint_attention(a, S(stream));
 }
 
@@ -483,6 +496,8 @@ int step_check(const tfx_step_desc* s) {
   if (!s->mod_table || !s->mod_cur || !s->step_ptr) return fail("tfx_dit_step: null pointer in descriptor");
   if (s->dit.mod != s->mod_cur) return fail("tfx_dit_step: dit.mod must point at mod_cur (the rows the step selects)");
   if (s->sampler < 0 || s->sampler > 2) return fail("tfx_dit_step: sampler must be 0 (Euler), 1 (AMO) or 2 (Euler fused into proj_out)");
+  if (s->dit.seq_len && s->sampler != 2)
+    return fail("tfx_dit_step: dit.seq_len (mixed-geometry batch) needs sampler 2: only the fused Euler form carries per-sample coefficients");
   if (s->sampler == 2) {
     const char* g = (const char*)s->dit.euler_gate;
     if (!g || g < (const char*)s->mod_cur || g >= (const char*)s->mod_cur + s->mod_step_elems * 2)

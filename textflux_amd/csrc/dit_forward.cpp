@@ -47,6 +47,9 @@ struct Ctx {
   // RMSNorm + RoPE of q, k on a row group of y as a separate pass (projections that did not carry it in their epilogue)
   int norm_rope(const Rows& r, const void* nq, const void* nk, const void* nq_txt, const void* nk_txt) const {
     if (r.rows <= 0) return 0;
+    if (d.rope_bstride > 0)   // mixed-geometry batch: one table per sample
+      return rmsnorm_rope_tab(y.p + r.row0 * D7, D7, y_bs, 2 * D, 0, H, r.rows, r.split, B, nq, nk, r.split ? nq_txt : nq, r.split ? nk_txt : nk,
+                              d.cos_tab + (int64_t)r.row0 * 128, d.sin_tab + (int64_t)r.row0 * 128, d.rope_bstride * 128, eps, st);
     return rmsnorm_rope(y.p + r.row0 * D7, D7, y_bs, 2 * D, 0, H, r.rows, r.split, B, nq, nk, r.split ? nq_txt : nq, r.split ? nk_txt : nk,
                         d.cos_tab + (int64_t)r.row0 * 128, d.sin_tab + (int64_t)r.row0 * 128, eps, st);
   }
@@ -57,6 +60,7 @@ struct Ctx {
     a.q_bstride = a.k_bstride = a.v_bstride = a.o_bstride = y_bs;
     a.B = B; a.H = H; a.N = N; a.scale = 0.08838834764831845f /* 128^-0.5 */; a.score_bound = block_bound > 0.f ? block_bound : d.attn_score_bound;
     a.workspace = ws; a.workspace_bytes = ws_bytes;
+    a.seq_len = d.seq_len;
     return joint_attention(a, st);
   }
 };
@@ -92,9 +96,9 @@ struct Gemm {
     return *this;
   }
   // the launch with the fused per-head RMSNorm + RoPE on the k / q column ranges [0, D) / [2D, 3D) of a [k | v | q | ...] projection
-  GemmArgs with_qknorm(const void* wq, const void* wk, const float* cs, int pos0, int D, float eps) const {
+  GemmArgs with_qknorm(const void* wq, const void* wk, const float* cs, int64_t cs_bstride, int pos0, int D, float eps) const {
     GemmArgs q = a;
-    q.qkn_wq = wq; q.qkn_wk = wk; q.qkn_rope_cs = cs; q.qkn_pos0 = pos0;
+    q.qkn_wq = wq; q.qkn_wk = wk; q.qkn_rope_cs = cs; q.qkn_rope_bstride = cs_bstride; q.qkn_pos0 = pos0;
     q.qkn_k0 = 0; q.qkn_k1 = D; q.qkn_q0 = 2 * D; q.qkn_q1 = 3 * D; q.qkn_eps = eps;
     if (q.epilogue == EPI_BIAS) { q.epilogue = EPI_BIAS_GELU; q.gelu_from_col = 1 << 30; }   // bias only: GELU never starts
     return q;
@@ -187,7 +191,7 @@ struct Forward : Ctx {
   // that the LoRA tail launch is never K-sliced, so the epilogue rides on every adapted projection.
   bool carries_qknorm(Gemm& gm, int pos0, const void* nq, const void* nk) const {
     if (!d.rope_cs) return false;
-    const GemmArgs fused = gm.with_qknorm(nq, nk, d.rope_cs, pos0, D, eps);
+    const GemmArgs fused = gm.with_qknorm(nq, nk, d.rope_cs, d.rope_bstride, pos0, D, eps);
     if (!gm.adapted()) {
       if (gm.fp8_ready() && !g_fp8_fuse_qkn) return false;
       if (fused.split_row > 0 && !(fused.qkn_wq2 && fused.qkn_wk2)) return false;
@@ -309,6 +313,9 @@ int dit_forward(const tfx_dit_desc& d, hipStream_t st) {
   if (d.D != d.H * 128) return fail("dit_forward: inner dim %d != heads %d * 128", d.D, d.H);
   if (d.B <= 0 || d.S <= 0 || d.T < 0) return fail("dit_forward: bad B/S/T");
   if ((d.flags & 4) && (!d.q8 || !d.q8_scale)) return fail("dit_forward: fp8 flag set but the q8 workspace is null");
+  if (d.seq_len && d.rope_bstride <= 0)
+    return fail("dit_forward: seq_len (mixed-geometry batch) needs rope_bstride > 0: one rotary table per sample");
+  if (d.rope_bstride < 0) return fail("dit_forward: rope_bstride must not be negative");
   return Forward(d, st).forward();
 }
 

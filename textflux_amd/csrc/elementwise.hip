@@ -159,7 +159,7 @@ __global__ __launch_bounds__(256) void rmsnorm_rope_kernel(bf16_t* __restrict__ 
                                                            const bf16_t* __restrict__ wq_txt,
                                                            const bf16_t* __restrict__ wk_txt,
                                                            const float* __restrict__ cosT,
-                                                           const float* __restrict__ sinT, float eps) {
+                                                           const float* __restrict__ sinT, int64_t tab_bs, float eps) {
   // 16 lanes per token, HSPLIT lane groups share a token's heads: each lane keeps the token's cos / sin for its 8
   // positions and both norm weights in registers and walks over its share of the 2H head rows (q heads, then k heads),
   // so the rotary table is read once per token instead of once per head row (it was 2/3 of this kernel's L2 traffic).
@@ -171,8 +171,8 @@ __global__ __launch_bounds__(256) void rmsnorm_rope_kernel(bf16_t* __restrict__ 
   if (tokrow >= (int64_t)B * Ntok) return;
   const int b = (int)(tokrow / Ntok);
   const int n = (int)(tokrow - (int64_t)b * Ntok);
-  const float4* c4 = reinterpret_cast<const float4*>(cosT + (int64_t)n * 128 + sub * 8);
-  const float4* s4 = reinterpret_cast<const float4*>(sinT + (int64_t)n * 128 + sub * 8);
+  const float4* c4 = reinterpret_cast<const float4*>(cosT + b * tab_bs + (int64_t)n * 128 + sub * 8);
+  const float4* s4 = reinterpret_cast<const float4*>(sinT + b * tab_bs + (int64_t)n * 128 + sub * 8);
   const float4 ca = c4[0], cb = c4[1], sa = s4[0], sb = s4[1];
   const float cs[8] = {ca.x, ca.y, ca.z, ca.w, cb.x, cb.y, cb.z, cb.w};
   const float sn[8] = {sa.x, sa.y, sa.z, sa.w, sb.x, sb.y, sb.z, sb.w};
@@ -552,15 +552,21 @@ int ln_modulate_fp8(const void* x, void* q8, float* q8_scale, const void* shift,
   return check_launch("ln_modulate_fp8");
 }
 
-int rmsnorm_rope(void* buf, int64_t ld, int64_t bstride, int q_off, int k_off, int H, int Ntok, int T, int B,
-                 const void* wq_img, const void* wk_img, const void* wq_txt, const void* wk_txt, const float* cosT,
-                 const float* sinT, float eps, hipStream_t st) {
+// tab_bstride: floats between two batch samples' cos / sin tables (0 = one table for every sample)
+int rmsnorm_rope_tab(void* buf, int64_t ld, int64_t bstride, int q_off, int k_off, int H, int Ntok, int T, int B,
+                     const void* wq_img, const void* wk_img, const void* wq_txt, const void* wk_txt, const float* cosT,
+                     const float* sinT, int64_t tab_bstride, float eps, hipStream_t st) {
   const int64_t groups = (int64_t)B * Ntok * 4;   // 4 lane groups of 16 per token (HSPLIT in the kernel)
   if (groups == 0 || H == 0) return 0;
   rmsnorm_rope_kernel<<<dim3((unsigned)((groups + 15) / 16)), 256, 0, st>>>(
       (bf16_t*)buf, ld, bstride, q_off, k_off, H, Ntok, T, B, (const bf16_t*)wq_img, (const bf16_t*)wk_img,
-      (const bf16_t*)wq_txt, (const bf16_t*)wk_txt, cosT, sinT, eps);
+      (const bf16_t*)wq_txt, (const bf16_t*)wk_txt, cosT, sinT, tab_bstride, eps);
   return check_launch("rmsnorm_rope");
+}
+int rmsnorm_rope(void* buf, int64_t ld, int64_t bstride, int q_off, int k_off, int H, int Ntok, int T, int B,
+                 const void* wq_img, const void* wk_img, const void* wq_txt, const void* wk_txt, const float* cosT,
+                 const float* sinT, float eps, hipStream_t st) {
+  return rmsnorm_rope_tab(buf, ld, bstride, q_off, k_off, H, Ntok, T, B, wq_img, wk_img, wq_txt, wk_txt, cosT, sinT, 0, eps, st);
 }
 
 int sched_step(bool amo, const void* v, void* x, void* xin, int64_t ldxin, int C, int64_t rows, const float* coef,

@@ -76,7 +76,7 @@ struct GemmParams {
   int split_row; uint32_t w2_off;
   const bf16_t* bias2; const bf16_t* gate2; const bf16_t* nq_w2; const bf16_t* nk_w2;
   // fused per-head RMSNorm + RoPE of the q / k column ranges (QKN kernel instantiation; see GemmArgs)
-  const bf16_t* nq_w; const bf16_t* nk_w; const float* rope_cs; int rope_pos0, nq0, nq1, nk0, nk1; float n_eps;
+  const bf16_t* nq_w; const bf16_t* nk_w; const float* rope_cs; int64_t rope_bs; int rope_pos0, nq0, nq1, nk0, nk1; float n_eps;   // rope_bs: table rows between two batch samples' tables (0 = one shared table)
   // runtime LoRA tail (LORA kernel instantiation; see gemm8pp_kernel and LoraArgs): T lies t_off bytes above A with A's row pitch and
   // batch stride, the up-projection rows sit in W's rows at columns [K, K + 64 lora_rt)
   uint32_t t_off, t_seg; int lora_rt, seg_cols, nseg; uint32_t seg_mask;   // t_seg: bytes between the T blocks of two segments
@@ -401,7 +401,7 @@ __device__ __forceinline__ void tile_epilogue(f32x4 (&acc)[8][4], const GemmPara
     f32x4 csr[4][2];
     // round 6: through a buffer descriptor that starts at this wave's first table row (rows beyond M read zeros and are never stored):
     // one per-lane offset for the whole tile, the row block in the SCALAR offset -- no 64-bit address arithmetic per request
-    const auto rsrcT = uniform_rsrc(NORM ? p.rope_cs + (int64_t)(p.rope_pos0 + m0 + g * 128) * 128 : (const float*)p.C, NORM ? rows_ok * 512 : 0);
+    const auto rsrcT = uniform_rsrc(NORM ? p.rope_cs + (b * p.rope_bs + p.rope_pos0 + m0 + g * 128) * 128 : (const float*)p.C, NORM ? rows_ok * 512 : 0);
     const int cs_off = crow * 512 + (wc & 1) * 256 + cchunk * 32;
     auto load_cs = [&](int blk) {
 #pragma unroll
@@ -1411,7 +1411,7 @@ __global__ __launch_bounds__(256) void gemm4w_kernel(GemmParams p) {
             u32x4 val = *reinterpret_cast<const u32x4*>(stg + row * 256 + ((cchunk ^ (row & 15)) << 4));
             if (NORM) {
               const int mrow = min(m0w + blk * 32 + row, p.M - 1);
-              const float* cs = p.rope_cs + (int64_t)(p.rope_pos0 + mrow) * 128 + cchunk * 8;
+              const float* cs = p.rope_cs + (cur.b * p.rope_bs + p.rope_pos0 + mrow) * 128 + cchunk * 8;
               csr[0] = *reinterpret_cast<const f32x4*>(cs);
               csr[1] = *reinterpret_cast<const f32x4*>(cs + 4);
               const float rr_row = __shfl(rinv[blk * 2 + (itr >> 2)], row & 15, 64);
@@ -1697,7 +1697,7 @@ static GemmParams make_params(const GemmArgs& a) {
   p.split_row = a.split_row; p.w2_off = 0;
   p.bias2 = (const bf16_t*)a.bias2; p.gate2 = (const bf16_t*)a.gate2; p.nq_w2 = (const bf16_t*)a.qkn_wq2; p.nk_w2 = (const bf16_t*)a.qkn_wk2;
   if (a.split_row > 0) p.w2_off = (uint32_t)((const char*)a.W2 - (const char*)a.W);
-  p.nq_w = (const bf16_t*)a.qkn_wq; p.nk_w = (const bf16_t*)a.qkn_wk; p.rope_cs = a.qkn_rope_cs; p.rope_pos0 = a.qkn_pos0;
+  p.nq_w = (const bf16_t*)a.qkn_wq; p.nk_w = (const bf16_t*)a.qkn_wk; p.rope_cs = a.qkn_rope_cs; p.rope_bs = a.qkn_rope_bstride; p.rope_pos0 = a.qkn_pos0;
   p.nq0 = a.qkn_q0; p.nq1 = a.qkn_q1; p.nk0 = a.qkn_k0; p.nk1 = a.qkn_k1; p.n_eps = a.qkn_eps;
   p.t_off = 0; p.t_seg = 0; p.lora_rt = 0; p.seg_cols = 0; p.nseg = 0; p.seg_mask = 0;
   p.cscale = a.cscale;

@@ -98,6 +98,7 @@ struct GemmArgs {
   // (cos, sin) pairs qkn_rope_cs [tokens][64][2] fp32 at token qkn_pos0 + row; == rmsnorm_rope() applied afterwards
   const void* qkn_wq = nullptr; const void* qkn_wk = nullptr; const float* qkn_rope_cs = nullptr;
   int qkn_pos0 = 0, qkn_q0 = 0, qkn_q1 = 0, qkn_k0 = 0, qkn_k1 = 0; float qkn_eps = 1e-6f;
+  int64_t qkn_rope_bstride = 0;                       // table rows between two batch samples' rotary tables (0 = one table for every sample)
   // optional scratch for the K-sliced units (fp32 partials, 256 KiB per unit); without it few-tile GEMMs run unsplit
   void* workspace = nullptr; int64_t workspace_bytes = 0;
   // row-split weights (persistent MFMA kernel only; split_row a multiple of 256, 0 = off): tiles whose first row inside the batch
@@ -147,6 +148,7 @@ struct AttnArgs {
   float score_bound = 0.f;   // caller's promise |scale * q . k| <= score_bound (0 = unknown): see tfx_attn_args
   void* workspace = nullptr; // optional scratch (tfx_attn_args.workspace): lets the head-dim-128 kernel deal (item, key tile) units (stream-K)
   int64_t workspace_bytes = 0;
+  const int32_t* seq_len = nullptr;   // optional DEVICE int32 [B]: sample b's queries and keys are its first seq_len[b] rows (tfx_attn_args.seq_len)
 };
 int joint_attention(const AttnArgs& a, hipStream_t st);
 int joint_attention_hp(const AttnArgs& a, hipStream_t st);   // half-tile software-pipelined kernel (attention_hp.hip)
@@ -183,6 +185,10 @@ int layernorm_affine(const void* x, void* out, const void* gamma, const void* be
 int rmsnorm_rope(void* buf, int64_t ld, int64_t bstride, int q_off, int k_off, int H, int Ntok, int T, int B,
                  const void* wq_img, const void* wk_img, const void* wq_txt, const void* wk_txt, const float* cosT,
                  const float* sinT, float eps, hipStream_t st);
+// ... with one cos / sin table per batch sample, tab_bstride floats apart (mixed-geometry batches; 0 = rmsnorm_rope)
+int rmsnorm_rope_tab(void* buf, int64_t ld, int64_t bstride, int q_off, int k_off, int H, int Ntok, int T, int B,
+                     const void* wq_img, const void* wk_img, const void* wq_txt, const void* wk_txt, const float* cosT,
+                     const float* sinT, int64_t tab_bstride, float eps, hipStream_t st);
 int sched_step(bool amo, const void* v, void* x, void* xin, int64_t ldxin, int C, int64_t rows, const float* coef,
                const int* step_ptr, int step, const float* noise, hipStream_t st);
 int timestep_embedding(const float* t, void* out, int n, hipStream_t st);

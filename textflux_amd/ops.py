@@ -90,7 +90,13 @@ def gemm_qkn(a: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor], nor
     assert norm_q.dtype == norm_k.dtype == BF16 and norm_q.numel() == norm_k.numel() == 128 and rope_cs.dtype == torch.float32 and rope_cs.is_contiguous()
     ap, lda, abs_, M, batch = _rows_view(a)
     N, K = w.shape
-    assert a.shape[-1] == K and rope_cs.shape[-2:] == (64, 2) and rope_cs.shape[0] >= pos0 + M
+    assert a.shape[-1] == K and rope_cs.shape[-2:] == (64, 2)
+    rope_bstride = 0
+    if rope_cs.dim() == 4:      # [B, rows, 64, 2]: one table per batch sample (tfx_qkn_args.rope_bstride)
+        assert rope_cs.shape[0] == batch and rope_cs.shape[1] >= pos0 + M
+        rope_bstride = rope_cs.shape[1]
+    else:
+        assert rope_cs.shape[0] >= pos0 + M
     if out is None:
         out = torch.empty(*a.shape[:-1], N, dtype=BF16, device=a.device)
     cp, ldc, cbs, M2, b2 = _rows_view(out)
@@ -106,6 +112,7 @@ def gemm_qkn(a: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor], nor
     q = L.QknArgs()
     q.norm_q, q.norm_k, q.rope_cs = norm_q.data_ptr(), norm_k.data_ptr(), rope_cs.data_ptr()
     q.pos0, q.q0, q.q1, q.k0, q.k1, q.eps = pos0, q_range[0], q_range[1], k_range[0], k_range[1], eps
+    q.rope_bstride = rope_bstride
     L.check(L.lib().tfx_gemm_bf16_qkn(C.byref(g), C.byref(q), _stream()), "gemm_qkn")
     return out
 
@@ -276,10 +283,17 @@ def ln_modulate_fp8(x: torch.Tensor, shift: torch.Tensor, scale: torch.Tensor, e
 
 def rmsnorm_rope_(buf: torch.Tensor, q_off: int, k_off: int, H: int, T: int, wq_img, wk_img, wq_txt, wk_txt,
                   cos: torch.Tensor, sin: torch.Tensor, eps: float = 1e-6) -> torch.Tensor:
-    """In place on buf [B,N,ld]: q at columns q_off.., k at k_off.. (H heads of 128)."""
+    """In place on buf [B,N,ld]: q at columns q_off.., k at k_off.. (H heads of 128).  cos / sin [N, 128], or [B, N, 128]: one table
+    per batch sample (tfx_rmsnorm_rope_batched)."""
     _chk_dev(buf, wq_img, wk_img, wq_txt, wk_txt, cos, sin)
     assert buf.dim() == 3 and buf.dtype == BF16 and cos.dtype == torch.float32 and cos.is_contiguous() and sin.is_contiguous()
     B, N, _ = buf.shape
+    if cos.dim() == 3:
+        assert cos.shape == (B, N, 128) and sin.shape == cos.shape
+        L.check(L.lib().tfx_rmsnorm_rope_batched(buf.data_ptr(), buf.stride(1), buf.stride(0), q_off, k_off, H, N, T, B,
+                                                 wq_img.data_ptr(), wk_img.data_ptr(), wq_txt.data_ptr(), wk_txt.data_ptr(),
+                                                 cos.data_ptr(), sin.data_ptr(), cos.stride(0), eps, _stream()), "rmsnorm_rope_batched")
+        return buf
     assert cos.shape == (N, 128)
     L.check(L.lib().tfx_rmsnorm_rope(buf.data_ptr(), buf.stride(1), buf.stride(0), q_off, k_off, H, N, T, B,
                                      wq_img.data_ptr(), wk_img.data_ptr(), wq_txt.data_ptr(), wk_txt.data_ptr(),
@@ -304,11 +318,14 @@ def gate_residual(x: torch.Tensor, gate: torch.Tensor, res: torch.Tensor, out: O
 
 
 def attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, out: Optional[torch.Tensor] = None,
-              scale: Optional[float] = None, score_bound: float = 0.0, workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
+              scale: Optional[float] = None, score_bound: float = 0.0, workspace: Optional[torch.Tensor] = None,
+              seq_len: Optional[torch.Tensor] = None) -> torch.Tensor:
     """q,k,v: [B,N,H*128] (views with row/batch strides allowed) -> out [B,N,H*128].  score_bound: the caller's promise
     |scale * q . k| <= score_bound (0 = unknown), see tfx_attn_args.  workspace: optional device scratch (>= 69.2 MB) that lets the
-    kernel deal (item, key tile) units to the CUs (stream-K, tfx_attn_args.workspace)."""
-    _chk_dev(q, k, v, out, workspace)
+    kernel deal (item, key tile) units to the CUs (stream-K, tfx_attn_args.workspace).  seq_len: optional device int32 [B], sample b's
+    valid length (tfx_attn_args.seq_len): its first seq_len[b] queries attend to its first seq_len[b] keys, later rows of `out` are
+    not written."""
+    _chk_dev(q, k, v, out, workspace, seq_len)
     B, N, HD = q.shape
     H = HD // 128
     assert HD % 128 == 0 and q.dtype == BF16
@@ -323,6 +340,9 @@ def attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, out: Optional[t
     a.score_bound = float(score_bound)
     if workspace is not None:
         a.workspace, a.workspace_bytes = workspace.data_ptr(), workspace.numel() * workspace.element_size()
+    if seq_len is not None:
+        assert seq_len.dtype == torch.int32 and seq_len.is_contiguous() and seq_len.numel() == B
+        a.seq_len = seq_len.data_ptr()
     L.check(L.lib().tfx_joint_attention(C.byref(a), _stream()), "joint_attention")
     return out
 

@@ -16,7 +16,7 @@ import json
 import os
 import warnings
 from types import SimpleNamespace
-from typing import Any, Callable, Dict, List, Optional, Union
+from typing import Any, Callable, Dict, List, Optional, Tuple, Union
 
 import numpy as np
 import torch
@@ -56,6 +56,25 @@ def calculate_shift(image_seq_len, base_seq_len: int = 256, max_seq_len: int = 4
     m = (max_shift - base_shift) / (max_seq_len - base_seq_len)
     b = base_shift - m * base_seq_len
     return image_seq_len * m + b
+
+
+def per_sample_schedules(scheduler, image_seq_lens, num_inference_steps: int, sigmas=None, device="cpu"):
+    """The sigma schedule of every sample of a mixed-geometry batch: calculate_shift makes mu, and with it every sigma, a function of
+    the sample's own image token count (P:1980-1990), so sample b gets set_timesteps(sigmas=..., mu=calculate_shift(S_b)) of
+    `scheduler` -- what its single-image call would set.  Returns {"timesteps": [B][n] f32, "sigmas": [B][n + 1] f32 (host),
+    "dsigma": [B][n] f32, the bf16-exact Euler coefficients of coef_table}.  Host arithmetic; leaves `scheduler` set for the last
+    distinct length."""
+    sc = scheduler.config
+    base = np.linspace(1.0, 1 / num_inference_steps, num_inference_steps) if sigmas is None else sigmas
+    cache = {}
+    for S in image_seq_lens:
+        if S in cache:
+            continue
+        mu = calculate_shift(S, sc.base_image_seq_len, sc.max_image_seq_len, sc.base_shift, sc.max_shift)
+        ts, n = retrieve_timesteps(scheduler, num_inference_steps, "cpu", sigmas=base, mu=mu)
+        cache[S] = (ts.detach().float().cpu().clone(), scheduler._sigmas_host.clone(), scheduler.coef_table("cpu", BF16)[:n].clone())
+    pick = lambda k: torch.stack([cache[S][k] for S in image_seq_lens]).to(device)
+    return dict(timesteps=pick(0), sigmas=pick(1), dsigma=pick(2))
 
 
 def retrieve_timesteps(scheduler, num_inference_steps=None, device=None, timesteps=None, sigmas=None, **kwargs):
@@ -695,6 +714,141 @@ class FluxFillPipeline:
         finally:
             if lora_scale is not None:
                 self.transformer._write_scales(prev_lora_scale)
+
+    @torch.no_grad()
+    def call_mixed(self, prompt: Union[str, List[str]] = None, image=None, mask_image=None, sizes=None,
+                   prompt_2: Optional[Union[str, List[str]]] = None, num_inference_steps: int = 50,
+                   sigmas: Optional[List[float]] = None, guidance_scale: float = 30.0, generator=None,
+                   prompt_embeds: Optional[torch.Tensor] = None, pooled_prompt_embeds: Optional[torch.Tensor] = None,
+                   output_type: Optional[str] = "pil", return_dict: bool = True, callback_on_step_end: Optional[Callable] = None,
+                   max_sequence_length: int = 512, latents: Optional[List[torch.Tensor]] = None,
+                   masked_image_latents: Optional[List[torch.Tensor]] = None):
+        """One denoising run over samples of DIFFERENT sizes (no reference counterpart: the reference, like `__call__`, runs one
+        geometry per call).  image / mask_image: one entry per sample, sizes[b] = (width, height) of sample b (multiples of 16).
+        Every sample computes what its own single-image `__call__` computes -- its own latent noise and VAE posterior sample from
+        generator[b] (a list, or one generator used for every sample in turn), its own sigma schedule from calculate_shift(S_b)
+        (per_sample_schedules), its own rotary table -- but the transformer runs ONCE per step for all of them: rows are padded to
+        the longest sample (T + S a multiple of 256), tfx_dit_desc.seq_len keeps every sample's attention on its own rows, and one
+        session + captured step graph serves every mix of sizes up to its own.  The VAE runs per group of equal size.  Returns one
+        image per sample at its own size (a list; output_type "latent": the packed latents [S_b, C] per sample).  latents /
+        masked_image_latents: as in `__call__`, but one tensor [1, S_b, 64] / [1, S_b, 320] per sample (instead of image / mask_image).
+        Needs the flow-matching Euler scheduler with fuse_euler_step (only the fused Euler step carries per-sample coefficients) and
+        no step callback."""
+        sch, tr = self.scheduler, self.transformer
+        if isinstance(sch, StochasticRFOvershotDiscreteScheduler):
+            raise NotImplementedError("call_mixed: the AMO sampler is not supported in mixed-geometry batches (its coefficients and "
+                                      "noise are per step, not per sample); use the Euler scheduler or __call__")
+        if not isinstance(sch, FlowMatchEulerDiscreteScheduler) or not self.fuse_euler_step:
+            raise NotImplementedError("call_mixed needs FlowMatchEulerDiscreteScheduler with fuse_euler_step: only the Euler update "
+                                      "fused into proj_out carries per-sample coefficients")
+        if callback_on_step_end is not None:
+            raise NotImplementedError("call_mixed: a step callback wants the latents as one tensor every step, which the fused Euler "
+                                      "step of a mixed-geometry batch does not keep; use __call__")
+        from .transformer import EULER_PAD
+        if sizes is None or len(sizes) == 0:
+            raise ValueError("call_mixed: `sizes` = [(width, height), ...], one per sample")
+        B = len(sizes)
+        if masked_image_latents is None:
+            image, mask_image = list(image), list(mask_image)
+            if len(image) != B or len(mask_image) != B:
+                raise ValueError(f"call_mixed: {B} sizes but {len(image)} images / {len(mask_image)} masks")
+        elif len(masked_image_latents) != B or image is not None:
+            raise ValueError("call_mixed: pass either image + mask_image or one masked_image_latents tensor per sample")
+        if latents is not None and len(latents) != B:
+            raise ValueError(f"call_mixed: {B} sizes but {len(latents)} latents")
+        if isinstance(prompt, str):
+            prompt = [prompt] * B
+        if isinstance(prompt_2, str):
+            prompt_2 = [prompt_2] * B
+        self.check_inputs(prompt, prompt_2, None, None, prompt_embeds=prompt_embeds, pooled_prompt_embeds=pooled_prompt_embeds,
+                          max_sequence_length=max_sequence_length, image=image, mask_image=mask_image, masked_image_latents=None)
+        self._guidance_scale, self._joint_attention_kwargs, self._interrupt = guidance_scale, None, False
+        device = self._execution_device
+        dev = tr.device
+        prompt_embeds, pooled_prompt_embeds, text_ids = self.encode_prompt(
+            prompt=prompt, prompt_2=prompt_2, prompt_embeds=prompt_embeds, pooled_prompt_embeds=pooled_prompt_embeds, device=device,
+            max_sequence_length=max_sequence_length)
+        if prompt_embeds.shape[0] != B:
+            raise ValueError(f"call_mixed: {B} sizes but {prompt_embeds.shape[0]} prompts")
+        dtype = prompt_embeds.dtype
+        gens = list(generator) if isinstance(generator, (list, tuple)) else [generator] * B
+        if len(gens) != B:
+            raise ValueError(f"You have passed a list of generators of length {len(gens)}, but requested an effective batch size of {B}.")
+        C = self.vae.config.latent_channels * 4
+        if C != EULER_PAD or tr.out_channels != C:
+            raise NotImplementedError("call_mixed: the fused Euler step needs 64 packed latent channels")
+        # per sample, in the order of its single-image call: the latent noise first, then (per group) the VAE posterior sample
+        lats, ids = [], []
+        for b, ((w, h), g) in enumerate(zip(sizes, gens)):
+            l, i = self.prepare_latents(1, self.vae.config.latent_channels, h, w, dtype, device, g, None if latents is None else latents[b])
+            if l.shape[1] != i.shape[0]:
+                raise ValueError(f"call_mixed: latents of sample {b} have {l.shape[1]} rows, its size {(w, h)} has {i.shape[0]} tokens")
+            lats.append(l), ids.append(i)
+        groups: Dict[Tuple[int, int], List[int]] = {}
+        for b, wh in enumerate(sizes):
+            groups.setdefault(tuple(wh), []).append(b)
+        conds: List[Optional[torch.Tensor]] = [None] * B
+        for (w, h), members in groups.items():
+            if masked_image_latents is not None:
+                for b in members:
+                    conds[b] = masked_image_latents[b].reshape(-1, masked_image_latents[b].shape[-1])
+                    if conds[b].shape[0] != lats[b].shape[1]:
+                        raise ValueError(f"call_mixed: masked_image_latents of sample {b} have {conds[b].shape[0]} rows, expected {lats[b].shape[1]}")
+                continue
+            gg = [gens[b] for b in members]
+            cond, H, W = self._encode_conditioning([image[b] for b in members], [mask_image[b] for b in members], h, w, len(members), 1,
+                                                   dtype, device, None if gg[0] is None else gg)
+            if cond is None:
+                raise NotImplementedError("call_mixed: `image` must hold images, not VAE latents")
+            if cond.shape[1] != lats[members[0]].shape[1]:
+                raise ValueError(f"call_mixed: sample size {(w, h)} became {W}x{H} in preprocessing; pass images at their pipeline size")
+            for k, b in enumerate(members):
+                conds[b] = cond[k]
+        S_b = [l.shape[1] for l in lats]
+        T = prompt_embeds.shape[1]
+        N = (T + max(S_b) + 255) // 256 * 256        # whole GEMM tiles: the rounding costs no GEMM time and makes sessions reusable
+        S = N - T
+        ses = tr.session(B, S, T, mixed=True)
+        ses.set_conditioning(prompt_embeds.to(dev, BF16), text_ids, ids)
+        n = num_inference_steps if sigmas is None else len(sigmas)
+        tabs = per_sample_schedules(sch, S_b, n, sigmas)
+        self._num_timesteps = n
+        t_vals = torch.tensor([[self._timestep_chain(tabs["timesteps"][b, i], BF16) for b in range(B)] for i in range(n)], dtype=torch.float32)
+        g_rows = None
+        if tr.config.guidance_embeds:
+            g = float((torch.full([1], guidance_scale, dtype=torch.float32).to(BF16) * 1000).float())
+            g_rows = torch.full((n * B,), g, dtype=torch.float32, device=dev)
+        mod = torch.empty(n, B, tr.mod_len + EULER_PAD, dtype=BF16, device=dev)      # rows ordered (step, sample)
+        mod[:, :, :tr.mod_len] = tr.modulation(tr.temb(t_vals.reshape(-1).to(dev), g_rows, pooled_prompt_embeds.to(dev, BF16).repeat(n, 1))).view(n, B, tr.mod_len)
+        mod[:, :, tr.mod_len:] = tabs["dsigma"].t().contiguous().to(dev, BF16).view(n, B, 1)           # bf16-exact already (coef_table)
+        for b in range(B):          # x_embedder input [latents | masked_image_latents] of the valid rows; padding rows stay unspecified
+            ses.xin[b, :S_b[b], :C].copy_(lats[b][0].to(dev, BF16))
+            ses.xin[b, :S_b[b], C:].copy_(conds[b].to(dev, BF16))
+        sch._step_index = 0
+        with self.progress_bar(total=n) as bar:
+            if self._use_hip_graph and n > 1:
+                out = self._graph_loop(ses, mod, torch.empty(B, S, C, dtype=BF16, device=dev), tabs["dsigma"][0].to(dev), False, None, n, bar, True)
+            else:
+                for i in range(n):
+                    if self._interrupt:
+                        continue
+                    ses.run(mod[i], euler=True)
+                    sch._step_index += 1
+                    bar.update()
+                out = ops.copy_rows_(ses.xin[:, :, :C], torch.empty(B, S, C, dtype=BF16, device=dev))
+        results: List[Any] = [None] * B
+        for (w, h), members in groups.items():
+            lat = torch.stack([out[b, :S_b[b]] for b in members])
+            if output_type == "latent":
+                imgs = list(lat)
+            else:
+                imgs = self._decode_to_output(lat, h, w, output_type)
+            for k, b in enumerate(members):
+                results[b] = imgs[k]
+        self.maybe_free_model_hooks()
+        if not return_dict:
+            return (results,)
+        return FluxPipelineOutput(images=results)
 
     def _call_body(self, prompt, prompt_2, image, mask_image, masked_image_latents, height, width, num_inference_steps, sigmas,
                    guidance_scale, num_images_per_prompt, generator, latents, prompt_embeds, pooled_prompt_embeds, output_type,

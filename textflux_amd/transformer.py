@@ -496,11 +496,13 @@ class FluxTransformer2DModel:
         dbl, sgl = self.attn_score_bounds()
         return max(dbl + sgl, default=0.0)
 
-    def session(self, B: int, S: int, T: int) -> "DitSession":
+    def session(self, B: int, S: int, T: int, mixed: bool = False) -> "DitSession":
+        """mixed: a session for mixed-geometry batches -- S is the PADDED image row count, every sample has its own rotary tables and
+        its own valid length (DitSession.set_conditioning with a list of img_ids)."""
         self.attn_score_bounds()        # norm weights edited in place since the last call: new bounds, new session
         s = self._session
-        if s is None or (s.B, s.S, s.T) != (B, S, T):
-            s = self._session = DitSession(self, B, S, T)
+        if s is None or (s.B, s.S, s.T, s.mixed) != (B, S, T, bool(mixed)):
+            s = self._session = DitSession(self, B, S, T, mixed=mixed)
         return s
 
     @torch.no_grad()
@@ -549,10 +551,13 @@ class FluxTransformer2DModel:
 
 
 class DitSession:
-    """Device workspace + C descriptor for one (B, S, T) problem size."""
+    """Device workspace + C descriptor for one (B, S, T) problem size.  mixed: the samples of a batch may have different image
+    token counts S_b <= S (tfx_dit_desc.seq_len / rope_bstride): rows [T text | S_b image | padding], one rotary table and one
+    valid length per sample, both refreshed in place by set_conditioning -- one session (and its captured step graphs) serves every
+    mix of lengths up to its size."""
 
-    def __init__(self, model: FluxTransformer2DModel, B: int, S: int, T: int):
-        self.model, self.B, self.S, self.T = model, B, S, T
+    def __init__(self, model: FluxTransformer2DModel, B: int, S: int, T: int, mixed: bool = False):
+        self.model, self.B, self.S, self.T, self.mixed = model, B, S, T, bool(mixed)
         c, D, dev = model.config, model.inner_dim, model.device
         N = S + T
         self.N = N
@@ -579,9 +584,12 @@ class DitSession:
         self.gemm_ws = carve(off[5], (gws.value // 4,), torch.float32)
         # RoPE tables: allocated ONCE per session and refreshed in place -- captured step graphs bake these pointers
         # into the kernel arguments, so a new ids layout for the same (B, S, T) must not move them
-        self.cos = torch.empty(N, c.attention_head_dim, dtype=torch.float32, device=dev)
-        self.sin = torch.empty(N, c.attention_head_dim, dtype=torch.float32, device=dev)
-        self.rope_cs = torch.empty(N, c.attention_head_dim // 2, 2, dtype=torch.float32, device=dev)   # (cos_i, sin_i) pairs
+        tab = (B, N) if self.mixed else (N,)     # mixed-geometry batches: one table per sample
+        self.cos = torch.empty(*tab, c.attention_head_dim, dtype=torch.float32, device=dev)
+        self.sin = torch.empty(*tab, c.attention_head_dim, dtype=torch.float32, device=dev)
+        self.rope_cs = torch.empty(*tab, c.attention_head_dim // 2, 2, dtype=torch.float32, device=dev)   # (cos_i, sin_i) pairs
+        self.seq_len = torch.full((B,), N, dtype=torch.int32, device=dev) if self.mixed else None     # T + S_b, read by the attention kernel
+        self.img_lens = [S] * B                  # S_b of the current conditioning
         self._ids_key = None
         w = model.w
 
@@ -624,6 +632,8 @@ class DitSession:
         d.cos_tab, d.sin_tab = self.cos.data_ptr(), self.sin.data_ptr()
         d.rope_cs = self.rope_cs.data_ptr() if model.fuse_qk_norm_rope else None
         d.attn_score_bound = 0.0        # every block carries its own (ABI 6); no forward-wide promise on top
+        if self.mixed:
+            d.seq_len, d.rope_bstride = self.seq_len.data_ptr(), N
         if self.fp8:
             d.q8, d.q8_scale = self.q8.data_ptr(), self.q8_scale.data_ptr()
         # scratch for the split-K path of few-tile GEMMs (text stream, small batch x resolution): fp32 partials of at most
@@ -667,11 +677,38 @@ class DitSession:
         sd.sampler = 1 if is_amo else 2 if fuse_euler else 0
         return sd
 
-    def set_conditioning(self, prompt_embeds: torch.Tensor, txt_ids: torch.Tensor, img_ids: torch.Tensor) -> None:
-        """context_embedder(prompt_embeds) -> ctx0; RoPE tables for cat(txt_ids, img_ids)."""
+    def set_conditioning(self, prompt_embeds: torch.Tensor, txt_ids: torch.Tensor, img_ids) -> None:
+        """context_embedder(prompt_embeds) -> ctx0; RoPE tables for cat(txt_ids, img_ids).  A mixed session takes a list of B
+        img_ids tensors [S_b, 3], S_b <= S: sample b's table and its valid length T + S_b are written in place (table rows of the
+        padding are those of id 0; nothing reads them)."""
         m = self.model
         assert prompt_embeds.shape[:2] == (self.B, self.T)
         ops.gemm(prompt_embeds.contiguous(), m.w["context_embedder.w"], m.w["context_embedder.b"], out=self.ctx0)
+        if self.mixed:
+            if not isinstance(img_ids, (list, tuple)) or len(img_ids) != self.B:
+                raise ValueError(f"a mixed session takes a list of {self.B} img_ids tensors, one per sample")
+            txt = txt_ids.detach().float().cpu()
+            per = [i.detach().float().cpu() for i in img_ids]
+            if any(i.shape[0] < 1 or i.shape[0] > self.S for i in per):
+                raise ValueError(f"image token counts {[i.shape[0] for i in per]} outside [1, {self.S}]")
+            ids = torch.zeros(self.B, self.N, 3)
+            for b, i in enumerate(per):
+                ids[b, :self.T] = txt
+                ids[b, self.T:self.T + i.shape[0]] = i
+            lens = [i.shape[0] for i in per]
+            # the tables are refreshed unless the ids are the cached ones, element for element: a checksum over the whole batch would
+            # not see two samples of equal length swapping places (a 32 x 48 and a 48 x 32 grid), and each would keep the other's table
+            key = ("mixed", tuple(lens), ids)
+            old = self._ids_key
+            if not (isinstance(old, tuple) and old[:1] == ("mixed",) and old[1] == key[1] and torch.equal(old[2], ids)):
+                cos, sin = rope_tables(ids.view(-1, 3), m.config.axes_dims_rope)
+                self.cos.copy_(cos.view(self.B, self.N, -1))
+                self.sin.copy_(sin.view(self.B, self.N, -1))
+                self.rope_cs.copy_(torch.stack((cos[:, 0::2], sin[:, 0::2]), dim=-1).view(self.B, self.N, -1, 2))
+                self.seq_len.copy_(torch.tensor([self.T + n for n in lens], dtype=torch.int32))
+                self.img_lens = lens
+                self._ids_key = key
+            return
         ids = torch.cat((txt_ids.detach().float().cpu(), img_ids.detach().float().cpu()), dim=0)
         key = (ids.shape, float(ids.sum()), float((ids * torch.arange(1, 4)).sum()))
         if key != self._ids_key:
