@@ -33,7 +33,7 @@ const char* tfx_last_error(void);
  * two since ABI 6) and returns how many values there are.  A binding
  * compares them with its own view of this header BEFORE the first call that passes a struct: a library built from an older
  * header would otherwise ignore the tail fields of a grown struct silently (no reference counterpart: the reference has no FFI). */
-#define TFX_ABI_VERSION 10
+#define TFX_ABI_VERSION 11
 int tfx_abi_info(int32_t* out, int n);
 /* Writes the gcnArchName of the current device (e.g. "gfx950:sramecc+:xnack-") into buf.  Needs a GPU. */
 int tfx_query_arch(char* buf, int buflen);
@@ -373,6 +373,34 @@ int tfx_workspace_layout(int32_t B, int32_t S, int32_t T, int32_t D, int32_t fla
  *      tfx_dit_step_capture: records the same launches on `stream` (must not be the NULL stream) in thread-local capture
  *      mode and instantiates them; tfx_dit_step_replay launches the instantiated graph; tfx_graph_destroy frees it.
  *      All pointers of the descriptor are baked into the graph: they must stay valid (and unmoved) while it is replayed. */
+/* ABI 11, the first-block step cache (no reference counterpart; DESIGN.md section 4 "Step cache"): buffers of a step loop that may skip the
+ * block stack on steps whose first-block residual barely moved.  All four are bf16 [B][S, ld] over the IMAGE rows of the joint stream
+ * (row pitch ld >= D, batch stride bstride, both multiples of 8 elements, 16-byte aligned): x0 = hid[img] before block 0, overwritten
+ * by the first-block residual f; f_prev = f of the last computed step; h1 = hid[img] behind block 0; r = the residual of blocks
+ * 1 ... end of the last computed step.  partials: fp32 scratch of at least 2048 * B bytes (the per-workgroup sums of the metric);
+ * metric: DEVICE fp32 [B], the head phase's result.  Caller-owned like every other buffer. */
+typedef struct tfx_step_cache {
+  void* x0; void* f_prev; void* h1; void* r;
+  int64_t ld, bstride;
+  float* partials; int64_t partials_bytes;
+  float* metric;
+} tfx_step_cache;
+/* The three passes on their own (tfx_dit_step_run issues them for phases 1 - 3 of tfx_step_desc).  hid: the image rows of the joint
+ * stream as a strided view, bf16 [batch][rows, ldh] with batch stride h_bstride (inside tfx_dit_step_*: hid + T * D, D, (T + S) * D).
+ * D % 8 == 0, rows / batch / D positive, every pointer 16-byte aligned and every stride a multiple of 8 elements.
+ *   metric: f = bf16(f32(hid) - f32(x0)) (ONE rounding) written over x0;  h1 <- hid;  per sample b
+ *           metric[b] = sum |f32(f) - f32(f_prev)| / sum |f32(f_prev)|  (+inf when the denominator is 0).  fp32 sums with a partition
+ *           and an order that depend on (rows, D) alone -- per-workgroup partial sums, then one finishing workgroup per sample; no
+ *           atomics: the same inputs give the same bits on every run and every device.
+ *   store:  r <- bf16(f32(hid) - f32(h1));  f_prev <- x0 (which holds f).
+ *   apply:  hid <- bf16(f32(hid) + f32(r)). */
+int tfx_step_cache_metric(const void* hid, int64_t ldh, int64_t h_bstride, const tfx_step_cache* cache, int32_t rows, int32_t batch,
+                          int32_t D, tfx_stream stream);
+int tfx_step_cache_store(const void* hid, int64_t ldh, int64_t h_bstride, const tfx_step_cache* cache, int32_t rows, int32_t batch,
+                         int32_t D, tfx_stream stream);
+int tfx_step_cache_apply(void* hid, int64_t ldh, int64_t h_bstride, const tfx_step_cache* cache, int32_t rows, int32_t batch,
+                         int32_t D, tfx_stream stream);
+
 typedef struct tfx_step_desc {
   tfx_dit_desc dit;
   const void* mod_table; void* mod_cur; int64_t mod_step_elems;   /* elements per step = B * mod_len */
@@ -384,6 +412,16 @@ typedef struct tfx_step_desc {
                                                                       travels with its modulation rows: mod_step_elems covers it), the
                                                                       latents live in dit.xin[:, :, :out_channels]; `latents` / `coef` are
                                                                       not used -- copy the result out with tfx_copy_rows after the loop */
+  /* ABI 11, the step cache (NULL / 0 = one whole step, exactly the launches it always issued).  phase: 0 whole step | 1 head:
+   * select_step, x_embedder + ctx0 copy, x0 <- hid[img], block 0, the metric pass (cache->metric is then read by the HOST, which
+   * decides between the two tails) | 2 computed tail: blocks [1, n), norm_out / proj_out and the sampler update as in a whole step,
+   * then the store pass and the cursor advance | 3 cached tail: the apply pass, norm_out / proj_out and the sampler update with no
+   * block in between, the cursor advance; f_prev and r stay.  Phases 1 + 2 issue the launches of a whole step in the same order
+   * (the added passes write only the cache's own buffers): a loop that never takes phase 3 is bit-equal to the plain loop.
+   * Refused: a phase without cache; cache with dit.seq_len (padded rows of a mixed batch may hold NaN and would poison the sums);
+   * cache with dit.first_block / last_block / flags other than the whole forward (flags bit 2 is allowed); fewer than 2 blocks. */
+  const tfx_step_cache* cache;
+  int32_t phase;
 } tfx_step_desc;
 typedef void* tfx_graph;
 int tfx_dit_step_run(const tfx_step_desc* step, tfx_stream stream);
@@ -517,7 +555,9 @@ int tfx_mul_act(const void* a, int64_t lda, const void* b, int64_t ldb, void* ou
  *                         tiles, an item cut by a CU boundary is finished by a merge pass -- when tfx_attn_args.workspace is given
  *                         and the library's estimate says it pays (P1024 batch 8: -1.1 % per launch, 2048 x 1024 batch 1: -12 %,
  *                         1024 x 672 batch 1: -16 %); 2 = whenever admissible; 0 = whole items only: a sample's bits then do not
- *                         depend on how many samples share its batch (identical samples of ONE batch agree either way).
+ *                         depend on how many samples share its batch (identical samples of ONE batch agree either way).  (With the
+ *                         step cache of tfx_step_desc.phase in use, a sample's bits depend on its batch-mates in another way too:
+ *                         the caller skips a step for the whole batch, by the largest metric among its samples.)
  *      "attention_tail_split": 1 lets kernel 30 cut the q-tiles of a partly filled last round of workgroups into two key ranges
  *      (+ a merge kernel; faster at small batches, but a sample's bits then depend on the batch size: default 0).
  *      "gemm_group_m": row tiles per group of the GEMM tile order (default 0 = by shape: 1 for N <= 3072, else 4).

@@ -63,6 +63,27 @@ def run_inference(image_input, mask_input, words_input, num_steps=50, guidance_s
                 prompt=glyph.PROMPT_TEMPLATE2, prompt_2=prompt).images[0]
 
 
+def add_step_cache_args(ap):
+    """Not in the reference: the first-block step cache (FluxFillPipeline.enable_step_cache)."""
+    ap.add_argument("--step_cache", type=float, default=None, metavar="THR", help="skip the block stack on steps whose first-block residual "
+                    "moved by less than THR relative to the last computed step (no default: the value is a property of the checkpoint; 0 never skips)")
+    ap.add_argument("--step_cache_max_consecutive", type=int, default=None, metavar="K", help="at most K skipped steps in a row (with --step_cache)")
+
+
+def apply_step_cache_args(a, pipe):
+    if a.step_cache is None:
+        if a.step_cache_max_consecutive is not None:
+            raise SystemExit("--step_cache_max_consecutive needs --step_cache THR")
+        return pipe
+    return pipe.enable_step_cache(a.step_cache, max_consecutive=a.step_cache_max_consecutive)
+
+
+def report_step_cache(pipe):
+    rep = getattr(pipe, "step_cache_report", None)
+    if getattr(pipe, "_step_cache", None) is not None and rep:
+        print(f"Step cache: {sum(1 for r in rep if r['skipped'])} of {len(rep)} steps skipped")
+
+
 def process_normal_mode(image_path, mask_path, words_path, steps, guidance_scale, seed, pipe=None, out_dir="outputs_my"):
     scene, mask = Image.open(image_path).convert("RGB"), Image.open(mask_path).convert("RGB")
     words = glyph.read_words_from_text(words_path)
@@ -89,8 +110,11 @@ def main():
     ap.add_argument("--steps", type=int, default=30, help="Number of inference steps")
     ap.add_argument("--guidance-scale", type=float, default=30, help="Guidance scale value")
     ap.add_argument("--seed", type=int, default=42, help="Random seed")
+    add_step_cache_args(ap)
     a = ap.parse_args()
-    process_normal_mode(a.image, a.mask, a.words, a.steps, a.guidance_scale, a.seed)
+    pipe = apply_step_cache_args(a, load_flux_pipeline()) if a.step_cache is not None or a.step_cache_max_consecutive is not None else None
+    process_normal_mode(a.image, a.mask, a.words, a.steps, a.guidance_scale, a.seed, pipe=pipe)
+    report_step_cache(pipe)
     print("\nProcessing completed successfully!")
 
 

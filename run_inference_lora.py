@@ -47,14 +47,16 @@ def build_parser():
     ap.add_argument("--scheduler", type=str, default="default", help="parsed but unused, as in the reference (:538)")
     ap.add_argument("--lora_runtime", action="store_true", help="keep the LoRA as an unmerged runtime adapter instead of merging it at load")
     ap.add_argument("--lora_scale", type=float, default=1.0, help="strength of the LoRA (1.0 = as trained)")
+    base.add_step_cache_args(ap)
     return ap
 
 
 def main(argv=None):
     a = build_parser().parse_args(argv)
     base.scheduler_name = scheduler_name
-    base.process_normal_mode(a.image, a.mask, a.words, a.steps, a.guidance_scale, a.seed,
-                             pipe=load_flux_pipeline(a.lora_runtime, a.lora_scale))
+    pipe = base.apply_step_cache_args(a, load_flux_pipeline(a.lora_runtime, a.lora_scale))
+    base.process_normal_mode(a.image, a.mask, a.words, a.steps, a.guidance_scale, a.seed, pipe=pipe)
+    base.report_step_cache(pipe)
     print("\nProcessing completed successfully!")
 
 

@@ -69,6 +69,10 @@ def build_parser(lora: bool = False):
     ap.add_argument("--batch_size", type=int, default=8, help="same-geometry images per pipeline call")
     ap.add_argument("--mixed_pad", type=float, default=0.0, help="let images of different sizes share a batch while at most this share of "
                     "its transformer rows is padding (Euler sampler only; 0 = same-geometry batches only)")
+    ap.add_argument("--step_cache", type=float, default=None, metavar="THR", help="first-block step cache: skip the block stack on steps whose "
+                    "first-block residual moved by less than THR relative to the last computed step (no default: the value is a property "
+                    "of the checkpoint; 0 never skips)")
+    ap.add_argument("--step_cache_max_consecutive", type=int, default=None, metavar="K", help="at most K skipped steps in a row (with --step_cache)")
     ap.add_argument("--items", type=str, default=None, help="JSON list of {image, mask, text} instead of --json_path")
     ap.add_argument("--out", type=str, default=None, help="output folder of --items mode")
     ap.add_argument("--num_inference_steps", type=int, default=None, help=argparse.SUPPRESS)
@@ -120,6 +124,10 @@ def main(argv=None, lora: bool = False, script: str = __file__):
     a = build_parser(lora).parse_args(argv)
     if a.mixed_pad > 0 and a.scheduler == "overshoot":
         raise SystemExit("--mixed_pad needs the Euler sampler: mixed-geometry batches carry per-sample coefficients only in the fused Euler step")
+    if a.step_cache is None and a.step_cache_max_consecutive is not None:
+        raise SystemExit("--step_cache_max_consecutive needs --step_cache THR")
+    if a.step_cache is not None and a.mixed_pad > 0:
+        raise SystemExit("--step_cache does not serve mixed-geometry batches (--mixed_pad)")
     legacy = a.items is not None
     weights = a.lora_weights_path if lora else a.weights_path
     if not legacy and not (a.json_path and a.original_images_dir and weights):
@@ -179,7 +187,10 @@ def main(argv=None, lora: bool = False, script: str = __file__):
     pipe.enable_hip_graph(True)
     res = batch_driver.run_items(items, pipe, out_dir, batch_size=a.batch_size, num_inference_steps=steps,
                                  guidance_scale=a.guidance_scale, seed=a.seed, device=f"cuda:{local}", eval_cfg=eval_cfg,
-                                 mixed_pad=a.mixed_pad)
+                                 mixed_pad=a.mixed_pad,
+                                 step_cache=None if a.step_cache is None else dict(threshold=a.step_cache, max_consecutive=a.step_cache_max_consecutive))
+    if "steps_total" in res:
+        print(f"[rank {rank}] step cache: {res['steps_skipped']} of {res['steps_total']} steps skipped")
     print(f"[rank {rank}] {len(res['done'])} images written" + (f"; {len(res['all_done'])}/{len(items)} in total, "
           f"{res['batches']} batches in {res['rounds']} rounds, prompts encoded {res['encode']}" if rank == 0 else ""))
     if rank == 0:

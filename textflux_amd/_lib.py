@@ -21,7 +21,7 @@ c_void_p, c_int, c_int32, c_int64, c_float, c_char_p = C.c_void_p, C.c_int, C.c_
 # TFX_ABI_VERSION of the include/textflux_hip.h the ctypes mirrors below were written against (tests/test_capi_symbols.py asserts
 # that it equals the header's): the library's stamp is compared with THIS constant, so a binding copied without include/ still
 # loads, and a ctypes mirror edited without the header (or the other way round) fails a test instead of passing the check.
-ABI_VERSION = 10
+ABI_VERSION = 11
 
 
 class GemmArgs(C.Structure):
@@ -101,9 +101,15 @@ class DitDesc(C.Structure):
     ]
 
 
+class StepCache(C.Structure):
+    _fields_ = [("x0", c_void_p), ("f_prev", c_void_p), ("h1", c_void_p), ("r", c_void_p), ("ld", c_int64), ("bstride", c_int64),
+                ("partials", c_void_p), ("partials_bytes", c_int64), ("metric", c_void_p)]
+
+
 class StepDesc(C.Structure):
     _fields_ = [("dit", DitDesc), ("mod_table", c_void_p), ("mod_cur", c_void_p), ("mod_step_elems", c_int64),
-                ("step_ptr", c_void_p), ("latents", c_void_p), ("coef", c_void_p), ("noise", c_void_p), ("sampler", c_int32)]
+                ("step_ptr", c_void_p), ("latents", c_void_p), ("coef", c_void_p), ("noise", c_void_p), ("sampler", c_int32),
+                ("cache", C.POINTER(StepCache)), ("phase", c_int32)]
 
 
 # name -> (restype, argtypes); every symbol include/textflux_hip.h declares must appear here (tests check it)
@@ -154,6 +160,9 @@ SIGNATURES = {
     "tfx_dit_step_capture": (c_int, [C.POINTER(StepDesc), c_void_p, C.POINTER(c_void_p)]),
     "tfx_dit_step_replay": (c_int, [c_void_p, c_void_p]),
     "tfx_graph_destroy": (c_int, [c_void_p]),
+    "tfx_step_cache_metric": (c_int, [c_void_p, c_int64, c_int64, C.POINTER(StepCache), c_int32, c_int32, c_int32, c_void_p]),
+    "tfx_step_cache_store": (c_int, [c_void_p, c_int64, c_int64, C.POINTER(StepCache), c_int32, c_int32, c_int32, c_void_p]),
+    "tfx_step_cache_apply": (c_int, [c_void_p, c_int64, c_int64, C.POINTER(StepCache), c_int32, c_int32, c_int32, c_void_p]),
     "tfx_conv3x3_nhwc": (c_int, [c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_int32, c_int32,
                                  c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_int, c_void_p]),
     "tfx_conv3x3_pair_nhwc": (c_int, [c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_void_p]),

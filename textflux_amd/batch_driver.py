@@ -212,7 +212,8 @@ def _flag_min(v: int, device) -> int:
 def run_items(items: Sequence[Dict[str, Any]], pipe, out_dir: Optional[str], batch_size: int = 8, num_inference_steps: int = 30,
               guidance_scale: float = 30.0, seed: int = 42, device="cuda", loader: Optional[Callable] = None,
               save: Optional[Callable] = None, max_sequence_length: int = 512, eval_cfg: Optional[Dict[str, Any]] = None,
-              encode: str = "auto", save_full: Optional[Callable] = None, mixed_pad: float = 0.0) -> Dict[str, Any]:
+              encode: str = "auto", save_full: Optional[Callable] = None, mixed_pad: float = 0.0,
+              step_cache: Optional[Dict[str, Any]] = None) -> Dict[str, Any]:
     """Runs the whole list; returns {"done": [indices this rank wrote], "failed": [...], "all_done": [...] on rank 0,
     "encode": "local" | "rank0"}.  `pipe` needs `encode_prompt(prompt, prompt_2, ...)` and the FluxFillPipeline `__call__`.
     encode: "local" = every rank encodes the T5 prompts of its own batches (needs a T5 on every rank), "rank0" = rank 0
@@ -220,7 +221,28 @@ def run_items(items: Sequence[Dict[str, Any]], pipe, out_dir: Optional[str], bat
     Outputs: eval-schema items (Work.name set) are written as out_dir/full_images/<name> and out_dir/cropped_images/<name>
     (or handed to save_full(work, full, cropped)); other items as out_dir/<index>.png (or save(index, cropped)).
     mixed_pad: plan_batches' max_pad_fraction -- > 0 lets items of different sizes share a batch (pipe.call_mixed) as long as at
-    most that share of the batch's rows is padding; 0 (default) = same-geometry batches only."""
+    most that share of the batch's rows is padding; 0 (default) = same-geometry batches only.
+    step_cache: None, or the keyword arguments of pipe.enable_step_cache (threshold, skip_steps, max_consecutive): the first-block step
+    cache is switched on for the run (and off again afterwards); the result then carries "steps_skipped" / "steps_total" over this
+    rank's batches.  Each rank decides alone from its own batch's metrics; not with mixed_pad > 0."""
+    if step_cache is not None:
+        if mixed_pad > 0:
+            raise NotImplementedError("step_cache does not serve mixed-geometry batches (mixed_pad > 0)")
+        if not hasattr(pipe, "enable_step_cache"):
+            raise ValueError("step_cache needs a pipeline with enable_step_cache (FluxFillPipeline)")
+        pipe.enable_step_cache(**step_cache)
+        try:
+            return _run_items(items, pipe, out_dir, batch_size, num_inference_steps, guidance_scale, seed, device, loader, save,
+                              max_sequence_length, eval_cfg, encode, save_full, mixed_pad, count_steps=True)
+        finally:
+            pipe.disable_step_cache()
+    return _run_items(items, pipe, out_dir, batch_size, num_inference_steps, guidance_scale, seed, device, loader, save,
+                      max_sequence_length, eval_cfg, encode, save_full, mixed_pad)
+
+
+def _run_items(items, pipe, out_dir, batch_size, num_inference_steps, guidance_scale, seed, device, loader, save, max_sequence_length,
+               eval_cfg, encode, save_full, mixed_pad, count_steps: bool = False) -> Dict[str, Any]:
+    steps_skipped = steps_total = 0
     if mixed_pad > 0:            # refused before anything is prepared or encoded, not batch by batch inside the loop
         if not hasattr(pipe, "call_mixed"):
             raise ValueError("mixed_pad > 0 needs a pipeline with call_mixed (FluxFillPipeline)")
@@ -329,6 +351,10 @@ def run_items(items: Sequence[Dict[str, Any]], pipe, out_dir: Optional[str], bat
                               mask_image=mask_in, num_inference_steps=num_inference_steps, generator=gens,
                               max_sequence_length=max_sequence_length, guidance_scale=guidance_scale,
                               prompt_embeds=pe_mine[:n], pooled_prompt_embeds=pooled1.expand(n, -1).contiguous(), **kw).images
+            if count_steps:
+                rep = getattr(pipe, "step_cache_report", None) or []
+                steps_total += len(rep)
+                steps_skipped += sum(1 for r_ in rep if r_["skipped"])
             for w, img, bx in zip(mine.items, images, boxes):
                 cropped = img if kw else img.crop(bx)
                 if w.name is not None and (save_full is not None or (save is None and out_dir is not None)):
@@ -347,6 +373,8 @@ def run_items(items: Sequence[Dict[str, Any]], pipe, out_dir: Optional[str], bat
             print(f"[rank {rank}] batch of {n} at {mine.size} failed: {e}")
     # ---- summary on rank 0
     res: Dict[str, Any] = {"done": done, "failed": failed, "batches": len(plan), "rounds": rounds, "encode": encode}
+    if count_steps:
+        res["steps_skipped"], res["steps_total"] = steps_skipped, steps_total
     if grouped:
         cnt = torch.zeros(len(items) + 1, dtype=torch.int32, device=device)
         for i in done:

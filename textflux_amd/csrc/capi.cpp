@@ -288,6 +288,41 @@ int tfx_advance_step(int32_t* step_ptr, tfx_stream stream) {
   return advance_step(step_ptr, S(stream));
 }
 
+// tfx_step_cache + a view of hid -> StepCacheArgs, with the checks the three public passes share (and the step path's own use of them)
+static int step_cache_args(const char* who, const void* hid, int64_t ldh, int64_t hbs, const tfx_step_cache* c, int32_t rows, int32_t batch,
+                           int32_t D, StepCacheArgs& a) {
+  if (!hid || !c) return fail("%s: null pointer", who);
+  if (!c->x0 || !c->f_prev || !c->h1 || !c->r || !c->partials || !c->metric) return fail("%s: null pointer in tfx_step_cache", who);
+  if (rows <= 0 || batch <= 0 || D <= 0) return fail("%s: rows, batch and D must be positive", who);
+  if (D % 8) return fail("%s: D must be a multiple of 8", who);
+  if (ldh < D || c->ld < D || (ldh | hbs | c->ld | c->bstride) % 8) return fail("%s: row pitches must be >= D, and every stride a multiple of 8 elements", who);
+  if (batch > 1 && (hbs < (int64_t)rows * ldh || c->bstride < (int64_t)rows * c->ld)) return fail("%s: batch stride smaller than a sample", who);
+  if (((uintptr_t)hid | (uintptr_t)c->x0 | (uintptr_t)c->f_prev | (uintptr_t)c->h1 | (uintptr_t)c->r) % 16 || (uintptr_t)c->partials % 8)
+    return fail("%s: pointers must be 16-byte aligned", who);
+  if (c->partials_bytes < (int64_t)batch * step_cache_parts((int64_t)rows * (D / 8)) * 8)
+    return fail("%s: partials_bytes %lld is too small (2048 bytes per sample serve every shape)", who, (long long)c->partials_bytes);
+  a = StepCacheArgs{const_cast<void*>(hid), ldh, hbs, c->x0, c->f_prev, c->h1, c->r, c->ld, c->bstride, c->partials, c->metric, rows, batch, D};
+  return 0;
+}
+int tfx_step_cache_metric(const void* hid, int64_t ldh, int64_t h_bstride, const tfx_step_cache* cache, int32_t rows, int32_t batch,
+                          int32_t D, tfx_stream stream) {
+  StepCacheArgs a;
+  TRY(step_cache_args("tfx_step_cache_metric", hid, ldh, h_bstride, cache, rows, batch, D, a));
+  return step_cache_metric(a, S(stream));
+}
+int tfx_step_cache_store(const void* hid, int64_t ldh, int64_t h_bstride, const tfx_step_cache* cache, int32_t rows, int32_t batch,
+                         int32_t D, tfx_stream stream) {
+  StepCacheArgs a;
+  TRY(step_cache_args("tfx_step_cache_store", hid, ldh, h_bstride, cache, rows, batch, D, a));
+  return step_cache_store(a, S(stream));
+}
+int tfx_step_cache_apply(void* hid, int64_t ldh, int64_t h_bstride, const tfx_step_cache* cache, int32_t rows, int32_t batch, int32_t D,
+                         tfx_stream stream) {
+  StepCacheArgs a;
+  TRY(step_cache_args("tfx_step_cache_apply", hid, ldh, h_bstride, cache, rows, batch, D, a));
+  return step_cache_apply(a, S(stream));
+}
+
 int tfx_conv3x3_nhwc(const void* x, int32_t B, int32_t inH, int32_t inW, int32_t Cin, const void* w, const void* bias,
                      void* out, int32_t H, int32_t W, int32_t Cout, int32_t stride, int32_t up, int32_t pad_lo,
                      const void* res, const void* zero_page, int variant, tfx_stream stream) {
@@ -491,7 +526,7 @@ int64_t tfx_workspace_bytes(int32_t B, int32_t Sn, int32_t T, int32_t D, int32_t
 namespace {
 struct StepGraph { hipGraph_t graph; hipGraphExec_t exec; };
 
-int step_check(const tfx_step_desc* s) {
+int step_check_sampler(const tfx_step_desc* s) {
   if (!s) return fail("tfx_dit_step: null descriptor");
   if (!s->mod_table || !s->mod_cur || !s->step_ptr) return fail("tfx_dit_step: null pointer in descriptor");
   if (s->dit.mod != s->mod_cur) return fail("tfx_dit_step: dit.mod must point at mod_cur (the rows the step selects)");
@@ -511,14 +546,71 @@ int step_check(const tfx_step_desc* s) {
   return 0;
 }
 
-int step_enqueue(const tfx_step_desc& s, hipStream_t st) {
-  TRY(select_step(s.mod_table, s.mod_cur, s.mod_step_elems, s.step_ptr, st));
-  TRY(tfx_dit_forward(&s.dit, (tfx_stream)st));
-  if (s.sampler == 2) return advance_step(s.step_ptr, st);     // the update happened in proj_out's epilogue
-  const int64_t rows = (int64_t)s.dit.B * s.dit.S;
-  TRY(sched_step(s.sampler == 1, s.dit.out, s.latents, const_cast<void*>(s.dit.xin), s.dit.in_channels, s.dit.out_channels, rows,
-                 s.coef, s.step_ptr, 0, s.noise, st));
+// the image rows of the joint stream as the step cache's passes see them
+int step_cache_view(const tfx_step_desc& s, StepCacheArgs& a) {
+  const tfx_dit_desc& d = s.dit;
+  if (!d.hid) return fail("tfx_dit_step: null buffer in descriptor");
+  const int64_t N = (int64_t)d.S + d.T;
+  return step_cache_args("tfx_dit_step (step cache)", (const uint16_t*)d.hid + (int64_t)d.T * d.D, d.D, N * d.D, s.cache, d.S, d.B, d.D, a);
+}
+
+int step_check(const tfx_step_desc* s) {
+  TRY(step_check_sampler(s));
+  if (s->phase < 0 || s->phase > 3) return fail("tfx_dit_step: phase must be 0 (whole step), 1 (head), 2 (computed tail) or 3 (cached tail)");
+  if (s->phase && !s->cache) return fail("tfx_dit_step: phase %d needs a step cache (tfx_step_desc.cache is null)", s->phase);
+  if (!s->cache) return 0;
+  const tfx_dit_desc& d = s->dit;
+  if (d.seq_len) return fail("tfx_dit_step: the step cache cannot serve a mixed-geometry batch (dit.seq_len): padded rows may hold NaN and would poison the metric's sums");
+  const int nblk = d.n_double + d.n_single;
+  if (d.first_block > 0 || (d.last_block >= 0 && d.last_block < nblk) || (d.flags & ~4))
+    return fail("tfx_dit_step: the step cache needs the whole forward (first_block 0, last_block -1, flags 0 or 4); the phases choose the block ranges");
+  if (nblk < 2) return fail("tfx_dit_step: the step cache needs at least 2 blocks (n_double + n_single = %d)", nblk);
+  StepCacheArgs a;
+  return step_cache_view(*s, a);
+}
+
+// the scheduler update behind the final projection and the cursor advance: the end of a whole step and of both tails
+int step_finish(const tfx_step_desc& s, hipStream_t st, const StepCacheArgs* store) {
+  if (s.sampler != 2) {                                         // sampler 2: the update happened in proj_out's epilogue
+    const int64_t rows = (int64_t)s.dit.B * s.dit.S;
+    TRY(sched_step(s.sampler == 1, s.dit.out, s.latents, const_cast<void*>(s.dit.xin), s.dit.in_channels, s.dit.out_channels, rows,
+                   s.coef, s.step_ptr, 0, s.noise, st));
+  }
+  if (store) TRY(step_cache_store(*store, st));
   return advance_step(s.step_ptr, st);
+}
+
+// blocks [first, last) of the step's forward; flags: bit 0 no embedders, bit 1 no norm_out / proj_out (the fp8 bit rides along)
+int step_forward(const tfx_step_desc& s, int first, int last, int flags, hipStream_t st) {
+  tfx_dit_desc d = s.dit;
+  d.first_block = first; d.last_block = last; d.flags = (s.dit.flags & 4) | flags;
+  return tfx_dit_forward(&d, (tfx_stream)st);
+}
+
+int step_enqueue(const tfx_step_desc& s, hipStream_t st) {
+  if (s.phase == 0) {
+    TRY(select_step(s.mod_table, s.mod_cur, s.mod_step_elems, s.step_ptr, st));
+    TRY(tfx_dit_forward(&s.dit, (tfx_stream)st));
+    return step_finish(s, st, nullptr);
+  }
+  StepCacheArgs a;
+  TRY(step_cache_view(s, a));
+  const int nblk = s.dit.n_double + s.dit.n_single;
+  switch (s.phase) {
+    case 1:   // head: what a whole step issues up to and including block 0, with x0 taken between the embedders and the block
+      TRY(select_step(s.mod_table, s.mod_cur, s.mod_step_elems, s.step_ptr, st));
+      TRY(step_forward(s, 0, 0, 2, st));
+      TRY(step_cache_save(a, st));
+      TRY(step_forward(s, 0, 1, 3, st));
+      return step_cache_metric(a, st);
+    case 2:   // computed tail: the rest of the whole step, then r and f_prev
+      TRY(step_forward(s, 1, -1, 1, st));
+      return step_finish(s, st, &a);
+    default:  // 3, cached tail: the last computed step's residual stands in for blocks [1, n)
+      TRY(step_cache_apply(a, st));
+      TRY(step_forward(s, nblk, nblk, 1, st));
+      return step_finish(s, st, nullptr);
+  }
 }
 }  // namespace
 

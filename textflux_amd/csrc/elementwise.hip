@@ -668,6 +668,151 @@ int advance_step(int* step_ptr, hipStream_t st) {
   return check_launch("advance_step");
 }
 
+// ---------------------------------------------------------------------------------------------
+// The first-block step cache (no reference counterpart; DESIGN.md section 4 "Step cache").  Three HBM-bound passes over the image rows of the
+// joint stream: hid is a strided view [B][rows, ldh], the cache buffers are [B][rows, ld]; 16 bytes per lane and stream, grid-stride
+// loops over a sample's chunks with grid (parts, B), parts <= STEP_CACHE_MAX_PARTS.  Chunk i of a sample is row i / cpr, column block i % cpr.
+struct StepCacheIdx {
+  int cpr;
+  int64_t ldh, ld;
+  __device__ __forceinline__ void at(int64_t i, int64_t& h, int64_t& c) const {
+    const int64_t row = i / cpr;
+    const int col = (int)(i - row * cpr) * 8;
+    h = row * ldh + col;
+    c = row * ld + col;
+  }
+};
+
+// f = bf16(f32(hid) - f32(x0)) over x0 (one rounding), h1 <- hid, and this workgroup's share of num = sum |f - f_prev|, den = sum |f_prev|.
+// Summation order, fixed by (rows, D): a thread adds the 8 elements of its chunks i = part * 256 + tid, + parts * 256, ... in sequence; the 64
+// lanes of a wave are combined by the xor butterfly, the 4 waves as (w0 + w1) + (w2 + w3).  partials[b][part] = (num, den); no atomics.
+__global__ __launch_bounds__(256) void step_cache_metric_kernel(const bf16_t* __restrict__ hid, bf16_t* x0, const bf16_t* __restrict__ f_prev,
+                                                                bf16_t* __restrict__ h1, float* __restrict__ partials, int64_t hbs, int64_t bs,
+                                                                int64_t chunks, StepCacheIdx ix) {
+  const int b = blockIdx.y, tid = threadIdx.x;
+  hid += b * hbs; x0 += b * bs; f_prev += b * bs; h1 += b * bs;
+  float num = 0.f, den = 0.f;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + tid; i < chunks; i += (int64_t)gridDim.x * 256) {
+    int64_t ho, co;
+    ix.at(i, ho, co);
+    const u32x4 hv = *reinterpret_cast<const u32x4*>(hid + ho);
+    const u32x4 xv = *reinterpret_cast<const u32x4*>(x0 + co);
+    const u32x4 pv = *reinterpret_cast<const u32x4*>(f_prev + co);
+    float h[8], x[8], p[8], f[8];
+    unpack8(hv, h); unpack8(xv, x); unpack8(pv, p);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) f[e] = __fsub_rn(h[e], x[e]);
+    const u32x4 fv = pack8(f);
+    unpack8(fv, f);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      num = __fadd_rn(num, fabsf(__fsub_rn(f[e], p[e])));
+      den = __fadd_rn(den, fabsf(p[e]));
+    }
+    *reinterpret_cast<u32x4*>(x0 + co) = fv;
+    *reinterpret_cast<u32x4*>(h1 + co) = hv;
+  }
+  num = wave_sum(num);
+  den = wave_sum(den);
+  __shared__ float red[4][2];
+  if ((tid & 63) == 0) { red[tid >> 6][0] = num; red[tid >> 6][1] = den; }
+  __syncthreads();
+  if (tid == 0) {
+    float2 o;
+    o.x = (red[0][0] + red[1][0]) + (red[2][0] + red[3][0]);
+    o.y = (red[0][1] + red[1][1]) + (red[2][1] + red[3][1]);
+    *reinterpret_cast<float2*>(partials + ((int64_t)b * gridDim.x + blockIdx.x) * 2) = o;
+  }
+}
+// One 256-thread workgroup per sample: thread t holds partial t (zeros beyond `parts` <= 256), the same butterfly and wave order as above:
+// a tree of depth 8 whatever `parts` is.  metric[b] = num / den, +inf when den == 0.
+__global__ __launch_bounds__(256) void step_cache_finish_kernel(const float* __restrict__ partials, float* __restrict__ metric, int parts) {
+  const int b = blockIdx.x, tid = threadIdx.x;
+  float2 v = make_float2(0.f, 0.f);
+  if (tid < parts) v = *reinterpret_cast<const float2*>(partials + ((int64_t)b * parts + tid) * 2);
+  const float num = wave_sum(v.x), den = wave_sum(v.y);
+  __shared__ float red[4][2];
+  if ((tid & 63) == 0) { red[tid >> 6][0] = num; red[tid >> 6][1] = den; }
+  __syncthreads();
+  if (tid == 0) {
+    const float n = (red[0][0] + red[1][0]) + (red[2][0] + red[3][0]);
+    const float d = (red[0][1] + red[1][1]) + (red[2][1] + red[3][1]);
+    metric[b] = d == 0.f ? __builtin_inff() : __fdiv_rn(n, d);
+  }
+}
+// r <- bf16(f32(hid) - f32(h1)), f_prev <- x0 (the computed step's f)
+__global__ __launch_bounds__(256) void step_cache_store_kernel(const bf16_t* __restrict__ hid, const bf16_t* __restrict__ x0,
+                                                               bf16_t* __restrict__ f_prev, const bf16_t* __restrict__ h1, bf16_t* __restrict__ r,
+                                                               int64_t hbs, int64_t bs, int64_t chunks, StepCacheIdx ix) {
+  const int b = blockIdx.y;
+  hid += b * hbs; x0 += b * bs; f_prev += b * bs; h1 += b * bs; r += b * bs;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < chunks; i += (int64_t)gridDim.x * 256) {
+    int64_t ho, co;
+    ix.at(i, ho, co);
+    const u32x4 hv = *reinterpret_cast<const u32x4*>(hid + ho);
+    const u32x4 gv = *reinterpret_cast<const u32x4*>(h1 + co);
+    const u32x4 fv = *reinterpret_cast<const u32x4*>(x0 + co);
+    float h[8], g[8], o[8];
+    unpack8(hv, h); unpack8(gv, g);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) o[e] = __fsub_rn(h[e], g[e]);
+    *reinterpret_cast<u32x4*>(r + co) = pack8(o);
+    *reinterpret_cast<u32x4*>(f_prev + co) = fv;
+  }
+}
+// hid <- bf16(f32(hid) + f32(r))
+__global__ __launch_bounds__(256) void step_cache_apply_kernel(bf16_t* hid, const bf16_t* __restrict__ r, int64_t hbs, int64_t bs, int64_t chunks,
+                                                               StepCacheIdx ix) {
+  const int b = blockIdx.y;
+  hid += b * hbs; r += b * bs;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < chunks; i += (int64_t)gridDim.x * 256) {
+    int64_t ho, co;
+    ix.at(i, ho, co);
+    float h[8], g[8], o[8];
+    unpack8(*reinterpret_cast<const u32x4*>(hid + ho), h);
+    unpack8(*reinterpret_cast<const u32x4*>(r + co), g);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) o[e] = __fadd_rn(h[e], g[e]);
+    *reinterpret_cast<u32x4*>(hid + ho) = pack8(o);
+  }
+}
+
+static int step_cache_shape(const char* who, const StepCacheArgs& a) {
+  if (a.rows <= 0 || a.batch <= 0 || a.D <= 0 || a.D % 8) return fail("%s: rows, batch and D must be positive and D a multiple of 8", who);
+  if (a.batch > 65535) return fail("%s: batch %d exceeds 65535", who, a.batch);
+  if (a.ldh < a.D || a.ld < a.D || (a.ldh | a.hbs | a.ld | a.bs) % 8) return fail("%s: row pitches must be >= D, and every stride a multiple of 8 elements", who);
+  return 0;
+}
+int step_cache_save(const StepCacheArgs& a, hipStream_t st) {
+  if (int e = step_cache_shape("step_cache_save", a)) return e;
+  return copy_rows(a.hid, a.ldh, a.hbs, a.x0, a.ld, a.bs, a.rows, a.D, a.batch, st);
+}
+int step_cache_metric(const StepCacheArgs& a, hipStream_t st) {
+  if (int e = step_cache_shape("step_cache_metric", a)) return e;
+  const int64_t chunks = (int64_t)a.rows * (a.D / 8);
+  const int parts = step_cache_parts(chunks);
+  step_cache_metric_kernel<<<dim3(parts, a.batch), 256, 0, st>>>((const bf16_t*)a.hid, (bf16_t*)a.x0, (const bf16_t*)a.f_prev, (bf16_t*)a.h1,
+                                                                 a.partials, a.hbs, a.bs, chunks, StepCacheIdx{a.D / 8, a.ldh, a.ld});
+  if (int e = check_launch("step_cache_metric")) return e;
+  step_cache_finish_kernel<<<a.batch, 256, 0, st>>>(a.partials, a.metric, parts);
+  return check_launch("step_cache_finish");
+}
+int step_cache_store(const StepCacheArgs& a, hipStream_t st) {
+  if (int e = step_cache_shape("step_cache_store", a)) return e;
+  const int64_t chunks = (int64_t)a.rows * (a.D / 8);
+  step_cache_store_kernel<<<dim3(step_cache_parts(chunks), a.batch), 256, 0, st>>>((const bf16_t*)a.hid, (const bf16_t*)a.x0, (bf16_t*)a.f_prev,
+                                                                                   (const bf16_t*)a.h1, (bf16_t*)a.r, a.hbs, a.bs, chunks,
+                                                                                   StepCacheIdx{a.D / 8, a.ldh, a.ld});
+  return check_launch("step_cache_store");
+}
+int step_cache_apply(const StepCacheArgs& a, hipStream_t st) {
+  if (int e = step_cache_shape("step_cache_apply", a)) return e;
+  const int64_t chunks = (int64_t)a.rows * (a.D / 8);
+  step_cache_apply_kernel<<<dim3(step_cache_parts(chunks), a.batch), 256, 0, st>>>((bf16_t*)a.hid, (const bf16_t*)a.r, a.hbs, a.bs, chunks,
+                                                                                   StepCacheIdx{a.D / 8, a.ldh, a.ld});
+  return check_launch("step_cache_apply");
+}
+
 // ---- per-row absmax quantisation bf16 -> fp8 e4m3 (OCP): one 256-thread block per row, row cached in registers.
 // scale = absmax / 448, out = round_to_e4m3(x / scale); v_cvt_pk_fp8_f32 does not saturate (NaN above 448), hence the clamp.
 template <int VPT>   // 16-byte vectors (8 elements) per thread; K <= 256 * 8 * VPT

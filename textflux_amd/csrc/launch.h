@@ -227,6 +227,23 @@ int mul_act(const void* a, int64_t lda, const void* b, int64_t ldb, void* out, i
 int select_step(const void* table, void* cur, int64_t per_step_elems, int* step_ptr, hipStream_t st);
 int advance_step(int* step_ptr, hipStream_t st);
 
+// The first-block step cache (tfx_step_cache, DESIGN.md section 4 "Step cache"): hid = the image rows of the joint stream as a strided
+// view [batch][rows, ldh] (batch stride hbs), the cache's four bf16 buffers [batch][rows, ld] (batch stride bs).
+struct StepCacheArgs {
+  void* hid; int64_t ldh, hbs;
+  void* x0; void* f_prev; void* h1; void* r; int64_t ld, bs;
+  float* partials; float* metric;
+  int rows, batch, D;
+};
+// The partition of the metric's sums, a function of (rows, D) alone: workgroups per sample (each 256 threads, <= STEP_CACHE_MAX_PARTS) and
+// the 16-byte chunks one thread walks through in sequence.
+constexpr int STEP_CACHE_MAX_PARTS = 256;
+inline int step_cache_parts(int64_t chunks) { return (int)(chunks >= 256ll * STEP_CACHE_MAX_PARTS ? STEP_CACHE_MAX_PARTS : (chunks + 255) / 256); }
+int step_cache_save(const StepCacheArgs& a, hipStream_t st);     // x0 <- hid
+int step_cache_metric(const StepCacheArgs& a, hipStream_t st);   // f = bf16(hid - x0) over x0, h1 <- hid, metric[b] = sum|f - f_prev| / sum|f_prev|
+int step_cache_store(const StepCacheArgs& a, hipStream_t st);    // r <- bf16(hid - h1), f_prev <- x0
+int step_cache_apply(const StepCacheArgs& a, hipStream_t st);    // hid <- bf16(hid + r)
+
 // One DiT forward on the launchers above (dit_forward.cpp; tfx_dit_forward checks the descriptor's pointers in front of it) and its
 // process-wide A/B knobs (tfx_set_option fp8_fuse_qkn / ln_joint / gemm_group_streams, all default 1).
 int dit_forward(const tfx_dit_desc& d, hipStream_t st);

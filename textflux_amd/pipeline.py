@@ -135,6 +135,8 @@ class FluxFillPipeline:
         self._guidance_scale, self._joint_attention_kwargs, self._num_timesteps, self._interrupt = None, None, 0, False
         self._use_hip_graph = False
         self.fuse_euler_step = True     # Euler update in proj_out's GEMM epilogue (tfx_dit_desc.euler_gate); False = separate scheduler kernel
+        self._step_cache = None         # StepCacheConfig while enable_step_cache() is in force
+        self.step_cache_report = None   # per step of the last call with the cache: {"metric": [B floats], "skipped": bool}
 
     # ------------------------------------------------------------------ loading / placement
     @classmethod
@@ -531,6 +533,14 @@ class FluxFillPipeline:
             modx[:, :, :tr.mod_len] = mod
             modx[:, :, tr.mod_len:] = coef[:n].to(BF16).view(n, 1, 1)      # coef is already bf16-exact (coef_table)
             mod = modx
+        self.step_cache_report = None
+        if self._step_cache is not None:
+            if sch._step_index != 0:
+                warnings.warn("the step cache needs a loop that starts at step 0 (scheduler.begin_index is set): running every step in full")
+            else:
+                return self._cached_loop(ses, mod, latents, coef, is_amo, amo_noise, timesteps, progress_bar, fuse,
+                                         self._use_hip_graph and callback_on_step_end is None and n > 1, callback_on_step_end,
+                                         callback_tensor_inputs, prompt_embeds, text_ids, latent_image_ids)
         if self._use_hip_graph and callback_on_step_end is None and n > 1 and sch._step_index == 0:
             return self._graph_loop(ses, mod, latents, coef, is_amo, amo_noise, n, progress_bar, fuse)
         if fuse:
@@ -632,9 +642,122 @@ class FluxFillPipeline:
         self.scheduler._step_index = n
         return out
 
+    # ------------------------------------------------------------------ first-block step cache (DESIGN.md section 4 "Step cache")
+    def enable_step_cache(self, threshold, skip_steps=None, max_consecutive=None):
+        """Opt-in and approximate, like enable_fp8() (no reference counterpart: the reference runs every block on every step).  Every
+        step runs the embedders and block 0 and measures, per sample, how far the first block's residual moved since the last fully
+        computed step: metric = sum |f - f_prev| / sum |f_prev|.  When the largest metric of the batch is below `threshold`, blocks
+        1 ... n are not run: the last computed step's residual of those blocks is added instead, then norm_out / proj_out and the
+        sampler update as usual.  Step 0 is always computed; cache state never outlives a call.
+
+        threshold has NO default: a useful value is a property of the checkpoint.  To choose one, run with threshold=0 (which never
+        skips and is bit-equal to the plain loop) and read `pipe.step_cache_report`: per step {"metric": [B floats], "skipped": bool}.
+        skip_steps: an explicit set of steps to skip whatever their metric.  max_consecutive: at most this many threshold skips in a
+        row.  The batch's largest metric decides, so a sample's result depends on its batch-mates while the cache is on.  Not for
+        call_mixed (raises); a foreign scheduler object's loop ignores it with a warning; every rank of a multi-GPU run decides alone."""
+        from .step_cache import StepCacheConfig
+        self._step_cache = StepCacheConfig.make(threshold, skip_steps, max_consecutive)
+        return self
+
+    def disable_step_cache(self):
+        self._step_cache = None
+        return self
+
+    def _cached_loop(self, ses, mod, latents, coef, is_amo, amo_noise, timesteps, progress_bar, fuse, use_graph, callback_on_step_end,
+                     callback_tensor_inputs, prompt_embeds, text_ids, latent_image_ids):
+        """The step loop under the step cache, eager or as captured graphs: per step the head phase (tfx_step_desc.phase 1), one
+        read of the B metrics through pinned memory, the host decision (step_cache.decide), then the computed (2) or the cached (3)
+        tail.  Both forms issue the same C-level phases -- tfx_dit_step_run, or the replay of the graph captured from it -- so they
+        agree bit for bit; phases 1 + 2 are the launches of a whole step, so a run that never skips equals the plain loop."""
+        import ctypes as C
+        from . import _lib as L
+        from .step_cache import Decider
+        dev = latents.device
+        n = len(timesteps)
+        gb = ses.graph_buffers(n, coef.numel(), latents.shape)
+        gb["mod_table"][:n, :, :mod.shape[2]].copy_(mod)
+        gb["coef"][:coef.numel()].copy_(coef.reshape(-1))
+        gb["lat"].copy_(latents)
+        gb["step"].zero_()
+        cache = ses.step_cache()
+        ses.step_cache_reset()
+        internal_noise = is_amo and amo_noise is None
+        sds = {ph: ses.step_desc(gb, is_amo, fuse, phase=ph) for ph in (1, 2, 3)}
+        ses._mod_keepalive = gb["mod_cur"]
+        lib = L.lib()
+        decider = Decider(self._step_cache)
+        sch = self.scheduler
+        cur = torch.cuda.current_stream(dev)
+        side = ses.graph_stream()
+        side.wait_stream(cur)
+        with torch.cuda.stream(side):
+            st = side.cuda_stream
+            graphs = None           # {phase: handle} once captured; False: capture refused, eager phases
+
+            def run(ph):
+                if graphs:
+                    L.check(lib.tfx_dit_step_replay(graphs[ph], st), "dit_step_replay")
+                else:
+                    L.check(lib.tfx_dit_step_run(C.byref(sds[ph]), st), "dit_step_run")
+
+            for i, t in enumerate(timesteps):
+                if self._interrupt:
+                    continue
+                if internal_noise:
+                    gb["noise"].normal_()      # global device RNG, as the reference's randn_tensor(generator=None); not captured
+                elif is_amo:
+                    gb["noise"].copy_(amo_noise[i].to(dev, torch.float32))
+                run(1)
+                cache["metric_host"].copy_(cache["metric"], non_blocking=True)
+                side.synchronize()
+                run(3 if decider.step(i, cache["metric_host"].tolist()) else 2)
+                sch._step_index += 1
+                if use_graph and graphs is None:       # every kernel of the three phases has run eagerly by now (apply: at set-up)
+                    keys = {ph: (is_amo, fuse, "step_cache", ph) for ph in (1, 2, 3)}
+                    have = {ph: ses.graphs.get(k) for ph, k in keys.items()}
+                    if all(g is None for g in have.values()):
+                        side.synchronize()
+                        saved = [gb[k].clone() for k in ("lat", "step")] + [ses.xin.clone()]
+                        for ph in (1, 2, 3):
+                            h = C.c_void_p()
+                            if lib.tfx_dit_step_capture(C.byref(sds[ph]), st, C.byref(h)) != 0:
+                                warnings.warn(f"hipGraph capture of the denoising step failed ({lib.tfx_last_error().decode()}); "
+                                              "running the step loop eagerly")
+                                for g in have.values():
+                                    if g:
+                                        lib.tfx_graph_destroy(g)
+                                have = {p: False for p in have}
+                                break
+                            have[ph] = h.value
+                        # capture does not execute; keep the state explicit anyway
+                        gb["lat"].copy_(saved[0]); gb["step"].copy_(saved[1]); ses.xin.copy_(saved[2])
+                        for ph, k in keys.items():
+                            ses.graphs[k] = have[ph]
+                    graphs = have if all(have.values()) else False
+                if callback_on_step_end is not None:
+                    lat = gb["lat"]
+                    kw = {k: {"latents": lat, "prompt_embeds": prompt_embeds}[k] for k in callback_tensor_inputs}
+                    out = callback_on_step_end(self, i, t, kw) or {}
+                    new_lat = out.pop("latents", lat)
+                    if new_lat is not lat:
+                        lat.copy_(new_lat.to(dev, BF16))
+                        ops.scatter_cols_(lat, ses.xin, 0)
+                    new_pe = out.pop("prompt_embeds", prompt_embeds)
+                    if new_pe is not prompt_embeds:
+                        prompt_embeds = new_pe
+                        ses.set_conditioning(prompt_embeds.to(dev, BF16), text_ids, latent_image_ids)
+                progress_bar.update()
+            out = ops.copy_rows_(ses.xin[:, :, :latents.shape[2]], torch.empty_like(latents)) if fuse else gb["lat"].clone()
+        out.record_stream(cur)
+        cur.wait_stream(side)
+        self.step_cache_report = decider.report
+        return out
+
     def _generic_loop(self, latents, masked_image_latents, prompt_embeds, pooled, text_ids, latent_image_ids, timesteps,
                       guidance, callback_on_step_end, callback_tensor_inputs, progress_bar):
         """Reference-shaped loop (P:2077-2116) for foreign scheduler objects: transformer.forward + scheduler.step."""
+        if self._step_cache is not None:
+            warnings.warn("the step cache lives in the engine's step loop; the loop for a foreign scheduler object ignores it")
         for i, t in enumerate(timesteps):
             if self._interrupt:
                 continue
@@ -735,6 +858,9 @@ class FluxFillPipeline:
         Needs the flow-matching Euler scheduler with fuse_euler_step (only the fused Euler step carries per-sample coefficients) and
         no step callback."""
         sch, tr = self.scheduler, self.transformer
+        if self._step_cache is not None:
+            raise NotImplementedError("call_mixed: the step cache does not serve mixed-geometry batches (padded rows would enter the "
+                                      "metric's sums); disable_step_cache() or use __call__")
         if isinstance(sch, StochasticRFOvershotDiscreteScheduler):
             raise NotImplementedError("call_mixed: the AMO sampler is not supported in mixed-geometry batches (its coefficients and "
                                       "noise are per step, not per sample); use the Euler scheduler or __call__")

@@ -645,6 +645,7 @@ class DitSession:
             d.lora_t_xn, d.lora_t_y = self.workspace.data_ptr() + off[6], self.workspace.data_ptr() + off[7]
             d.lora_scale = lora["scale"].data_ptr()
             self.workspace[off[6]:].zero_()     # rows the down projections never write are read (and multiplied by zero rows of Bcat)
+        self.cache = None       # the step cache's buffers and tfx_step_cache, allocated by step_cache() when the cache is first used
         self.graphs = {}        # (sampler, ...) -> C-level step graph handle (tfx_dit_step_capture)
         self._gb = None
         self._gstream = None    # side stream the step graphs are captured / replayed on
@@ -662,9 +663,39 @@ class DitSession:
             self._gstream = torch.cuda.Stream(device=self.model.device)
         return self._gstream
 
-    def step_desc(self, gb, is_amo: bool, fuse_euler: bool = False) -> "L.StepDesc":
+    def step_cache(self) -> Dict[str, Any]:
+        """The first-block step cache of this session (tfx_step_cache; DESIGN.md section 4 "Step cache"): x0 / f_prev / h1 / r, bf16
+        [B, S, D] over the image rows, the metric's partial sums, the device metric [B] and its pinned host copy.  Allocated on first
+        use -- a session that never runs with the cache holds none of it -- and kept: captured phase graphs bake the pointers.  The
+        apply kernel runs once here on the cache's own (zeroed) buffers: a step graph may only hold kernels that were launched
+        eagerly before, and the first steps of a call need not take the cached tail."""
+        if self.cache is not None:
+            return self.cache
+        if self.mixed:
+            raise NotImplementedError("the step cache does not serve mixed-geometry sessions")
+        B, S, D, dev = self.B, self.S, self.model.inner_dim, self.model.device
+        bufs = {k: torch.zeros(B, S, D, dtype=BF16, device=dev) for k in ("x0", "f_prev", "h1", "r")}
+        partials = torch.zeros(B * 256 * 2, dtype=torch.float32, device=dev)
+        metric = torch.zeros(B, dtype=torch.float32, device=dev)
+        sc = L.StepCache()
+        for k, t in bufs.items():
+            setattr(sc, k, t.data_ptr())
+        sc.ld, sc.bstride = D, S * D
+        sc.partials, sc.partials_bytes, sc.metric = partials.data_ptr(), partials.numel() * 4, metric.data_ptr()
+        L.check(L.lib().tfx_step_cache_apply(bufs["h1"].data_ptr(), D, S * D, C.byref(sc), S, B, D, ops._stream()), "step_cache_apply")
+        self.cache = dict(bufs, partials=partials, metric=metric, metric_host=torch.zeros(B, dtype=torch.float32).pin_memory(), desc=sc)
+        return self.cache
+
+    def step_cache_reset(self) -> None:
+        """Start of a pipeline call: no computed step exists yet.  f_prev = 0 makes step 0's metric +inf (it is always computed)."""
+        c = self.step_cache()
+        c["f_prev"].zero_()
+        c["r"].zero_()
+
+    def step_desc(self, gb, is_amo: bool, fuse_euler: bool = False, phase: int = 0) -> "L.StepDesc":
         """tfx_step_desc of one denoising step over the persistent graph buffers `gb` (graph_buffers()).  fuse_euler: sampler 2 --
-        the step's dsigma row (the EULER_PAD columns behind each modulation row) gates proj_out's epilogue, the latents live in xin."""
+        the step's dsigma row (the EULER_PAD columns behind each modulation row) gates proj_out's epilogue, the latents live in xin.
+        phase 1 / 2 / 3: the head / computed tail / cached tail of a step under the step cache (tfx_step_desc.phase)."""
         d = self.desc
         d.mod, d.mod_bstride = gb["mod_cur"].data_ptr(), gb["mod_cur"].stride(0)
         d.first_block, d.last_block, d.flags = 0, -1, (4 if self.fp8 else 0)
@@ -675,6 +706,8 @@ class DitSession:
         sd.step_ptr, sd.latents = gb["step"].data_ptr(), gb["lat"].data_ptr()
         sd.coef, sd.noise = gb["coef"].data_ptr(), gb["noise"].data_ptr() if is_amo else None
         sd.sampler = 1 if is_amo else 2 if fuse_euler else 0
+        if phase:
+            sd.cache, sd.phase = C.pointer(self.step_cache()["desc"]), phase
         return sd
 
     def set_conditioning(self, prompt_embeds: torch.Tensor, txt_ids: torch.Tensor, img_ids) -> None:
