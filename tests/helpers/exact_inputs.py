@@ -1,0 +1,470 @@
+"""Inputs on which the matrix-pipe kernels have ONE correct answer per output element, and that answer restated on the CPU.
+
+Every generator draws from a seeded CPU torch.Generator and asserts its own exactness condition when called: operands whose
+products and partial sums are small integers (or dyadic fractions) are summed exactly by fp32 in EVERY order, so a GEMM, a
+convolution or an attention launch -- generic or MFMA, one tile or persistent, K-sliced or not, whole items or dealt units --
+must store one definite bf16 bit pattern per element, and so must the plain fp64 / integer restatement here.  No tolerance is
+budgeted for the summation order; assert_elementwise compares per element and names the tile of the first differences.
+
+Nothing in this file restates a kernel: the expected values come from torch matmul / conv2d / softmax in fp64 (or fp32 on
+integers, where fp32 is exact) and from torch's own bf16 operators for the rounding chains the C header documents.
+"""
+import functools
+import math
+
+import torch
+
+BF = torch.bfloat16
+F8 = torch.float8_e4m3fn
+GATES = (0.5, 0.75, 1.0, 1.5, 2.0)                      # epilogue 2: +- these
+NORM_WEIGHTS = (0.5, 0.75, 1.0, 1.25, 1.5)              # q / k RMSNorm weights
+ROPE_PAIRS = ((1.0, 0.0), (-1.0, 0.0), (0.0, 1.0), (0.0, -1.0), (0.5, 0.5), (0.5, -0.5), (-0.5, 0.5), (-0.5, -0.5))   # (cos, sin)
+ACC_LIMIT = 256                                         # every integer of magnitude <= 256 is a bf16 value
+
+
+def gen(seed: int) -> torch.Generator:
+    return torch.Generator().manual_seed(seed)
+
+
+def ternary(shape, seed: int, p_nonzero: float = 0.25) -> torch.Tensor:
+    """fp32 entries in {-1, 0, 1}: P(non-zero) = p_nonzero, both signs equally likely."""
+    u = torch.rand(shape, generator=gen(seed))
+    return torch.where(u < p_nonzero / 2, -1.0, torch.where(u < p_nonzero, 1.0, 0.0))
+
+
+def integers(shape, lo: int, hi: int, seed: int) -> torch.Tensor:
+    return torch.randint(lo, hi + 1, shape, generator=gen(seed)).float()
+
+
+def choice(values, shape, seed: int, signed: bool = False) -> torch.Tensor:
+    t = torch.tensor(values, dtype=torch.float32)[torch.randint(0, len(values), shape, generator=gen(seed))]
+    if signed:
+        t = t * torch.where(torch.rand(shape, generator=gen(seed + 7919)) < 0.5, -1.0, 1.0)
+    return t
+
+
+def arbitrary_bf16(shape, seed: int, scale: float = 1.0) -> torch.Tensor:
+    return (torch.randn(shape, generator=gen(seed)) * scale).to(BF)
+
+
+# --------------------------------------------------------------------------------------------------------- comparison
+def _ordered(t: torch.Tensor) -> torch.Tensor:
+    """bf16 bit patterns as integers that count bf16 steps: neighbours differ by one, +0 and -0 are both 0."""
+    bits = t.contiguous().view(torch.int16).to(torch.int32) & 0xFFFF
+    mag = bits & 0x7FFF
+    return torch.where((bits & 0x8000) != 0, -mag, mag)
+
+
+def mismatches(got: torch.Tensor, want: torch.Tensor, ulps: int = 0) -> torch.Tensor:
+    """bool mask of the elements of `got` more than `ulps` bf16 steps from `want` (fp32 tensors: any difference).  A NaN on either
+    side is a mismatch; +0 and -0 are the same value (torch.equal's convention)."""
+    assert got.shape == want.shape, (tuple(got.shape), tuple(want.shape))
+    assert got.dtype == want.dtype, (got.dtype, want.dtype)
+    if got.dtype == BF:
+        bad = (_ordered(got) - _ordered(want)).abs() > ulps
+    else:
+        assert ulps == 0, "steps are counted for bf16 only"
+        bad = got != want
+    return bad | torch.isnan(got) | torch.isnan(want)
+
+
+def assert_elementwise(got: torch.Tensor, want: torch.Tensor, what: str, ulps: int = 0, cap: float = None) -> int:
+    """Every element of got [.., rows, cols] within `ulps` bf16 steps of want (0: the same value).  cap: only with ulps > 0 -- at most
+    this share of the elements may differ from `want` at all.  Returns the number of elements that are not bit-equal.  The failure
+    message lists the first sixteen offenders as (batch, row, column), their 256 x 256 tile and the position inside it."""
+    got, want = got.detach().cpu(), want.detach().cpu()
+    bad = mismatches(got, want, ulps)
+    n_bad = int(bad.sum())
+    n_diff = n_bad if ulps == 0 else int(mismatches(got, want, 0).sum())
+    if n_bad == 0 and (cap is None or n_diff <= cap * got.numel()):
+        return n_diff
+    if n_bad == 0:
+        raise AssertionError(f"{what}: every element is within {ulps} bf16 step(s), but {n_diff} of {got.numel()} differ "
+                             f"({n_diff / got.numel():.3e}), more than the cap {cap:.3e}")
+    idx = bad.reshape(-1, *bad.shape[-2:]) if bad.dim() >= 2 else bad.reshape(1, 1, -1)
+    g3, w3 = got.reshape(idx.shape), want.reshape(idx.shape)
+    lines = []
+    for b, r, c in idx.nonzero()[:16].tolist():
+        lines.append(f"  (batch {b}, row {r}, col {c})  tile ({r // 256}, {c // 256}) at ({r % 256}, {c % 256}): "
+                     f"got {g3[b, r, c].item()!r}, want {w3[b, r, c].item()!r}")
+    rows = idx.any(-1).sum().item()
+    cols = idx.any(-2).sum().item() if idx.shape[-2] > 0 else 0
+    raise AssertionError(f"{what}: {n_bad} of {got.numel()} elements differ by more than {ulps} bf16 step(s) "
+                         f"({rows} rows and {cols} (batch, column) lines touched); first {len(lines)}:\n" + "\n".join(lines))
+
+
+# --------------------------------------------------------------------------------------------------------- GEMM
+def gemm_operands(B: int, M: int, N: int, K: int, seed: int, w_batched: bool = False, product: bool = True, p_nonzero: float = 0.25) -> dict:
+    """a [B, M, K], w [N, K] (or [B, N, K]) ternary-sparse bf16, bias [N] integers in [-8, 8]; acc = a w^T as fp64 integers (None when
+    product is False: shapes whose product the caller takes on the device).  Asserted: max|acc + bias| <= 256."""
+    a = ternary((B, M, K), seed + 1, p_nonzero)
+    w = ternary((B, N, K) if w_batched else (N, K), seed + 2, p_nonzero)
+    bias = integers((N,), -8, 8, seed + 3)
+    cs = dict(a=a.to(BF), w=w.to(BF), bias=bias.to(BF), acc=None)
+    if product:
+        acc = a.double() @ (w.double().transpose(-1, -2))
+        check_accumulators(acc, bias)
+        cs["acc"] = acc
+    return cs
+
+
+def check_accumulators(acc: torch.Tensor, bias: torch.Tensor = None) -> None:
+    """The exactness condition of the integer GEMM / convolution: integers, |acc| and |acc + bias| <= 256 (bias along the last axis)."""
+    assert bool((acc == acc.round()).all()), "accumulators must be integers"
+    top = acc.abs().max().item()
+    if bias is not None:
+        top = max(top, (acc + bias.to(acc.dtype)).abs().max().item())
+    assert top <= ACC_LIMIT, f"max|a w^T + bias| = {top} leaves the exact regime (<= {ACC_LIMIT})"
+
+
+def gates(B: int, N: int, seed: int) -> torch.Tensor:
+    return choice(GATES, (B, N), seed, signed=True).to(BF)
+
+
+def pow2(shape, lo: int, hi: int, seed: int) -> torch.Tensor:
+    return torch.exp2(torch.randint(lo, hi + 1, shape, generator=gen(seed)).float())
+
+
+def gelu_tanh64(x: torch.Tensor) -> torch.Tensor:
+    """F.gelu(x, approximate="tanh") in fp64 as x * sigmoid(2u), u = sqrt(2/pi) (x + 0.044715 x^3): the same function as
+    0.5 x (1 + tanh u) without the cancelling 1 + tanh(u) for very negative x (fp64 would return 0 where the value is 1e-30)."""
+    x = x.double()
+    u = math.sqrt(2.0 / math.pi) * (x + 0.044715 * x ** 3)
+    return x / (1.0 + torch.exp(-2.0 * u))
+
+
+def linear_bf16(acc: torch.Tensor, bias: torch.Tensor = None, row_scale: torch.Tensor = None, col_scale: torch.Tensor = None) -> torch.Tensor:
+    """bf16(acc * row_scale * col_scale + bias): the Linear's stored output, rounded ONCE from the exact value.  The value is asserted
+    to be an fp32 number, so the fp64 -> bf16 conversion rounds what the kernel's fp32 epilogue holds."""
+    v = acc.double()
+    if row_scale is not None:
+        v = v * row_scale.double()[..., None]
+    if col_scale is not None:
+        v = v * col_scale.double()
+    if bias is not None:
+        v = v + bias.double()
+    assert bool((v.float().double() == v).all()), "pre-rounding value must be exact in fp32"
+    return v.float().to(BF)
+
+
+def chain(epilogue: int, lin: torch.Tensor, res: torch.Tensor = None, gate: torch.Tensor = None, gelu_from_col: int = 0) -> torch.Tensor:
+    """The epilogue chains of include/textflux_hip.h on the Linear's bf16 output `lin` [B, M, N], with torch's bf16 operators (each
+    rounds once): 0 lin | 3 bf16(res + lin) | 2 bf16(res + bf16(gate * lin)) | 1 bf16(gelu_tanh(lin)) on columns >= gelu_from_col."""
+    assert lin.dtype == BF
+    if epilogue == 0:
+        return lin
+    if epilogue == 3:
+        return res + lin
+    if epilogue == 2:
+        return res + gate[:, None, :] * lin
+    if epilogue == 1:
+        out = lin.clone()
+        out[..., gelu_from_col:] = gelu_tanh64(lin[..., gelu_from_col:]).float().to(BF)
+        return out
+    raise ValueError(epilogue)
+
+
+def gelu_exact_mask(lin: torch.Tensor, gelu_from_col: int) -> torch.Tensor:
+    """Elements of an epilogue-1 output that must match bit for bit: the plain columns, and GELU columns whose value is 0 or x itself."""
+    m = torch.ones(lin.shape, dtype=torch.bool)
+    g = gelu_tanh64(lin[..., gelu_from_col:])
+    x = lin[..., gelu_from_col:].double()
+    m[..., gelu_from_col:] = (g == 0) | (g == x)
+    return m
+
+
+# --------------------------------------------------------------------------------------------------------- fp8
+def fp8_bytes(t: torch.Tensor) -> torch.Tensor:
+    """e4m3 bytes of values that e4m3 holds exactly (asserted)."""
+    q = t.float().to(F8)
+    assert bool((q.float() == t.float()).all()), "values must be e4m3 numbers"
+    return q.view(torch.uint8)
+
+
+def quantizable_rows(shape, seed: int):
+    """bf16 rows whose quantisation is known exactly: row r = 2^e_r * integers in [-8, 8] with one entry +-448, so the scale is 2^e_r
+    and the codes are the integers.  Returns (x bf16, codes uint8, scale fp32)."""
+    ints = integers(shape, -8, 8, seed)
+    pos = torch.randint(0, shape[-1], shape[:-1], generator=gen(seed + 1))
+    sign = torch.where(torch.rand(shape[:-1], generator=gen(seed + 2)) < 0.5, -448.0, 448.0)
+    ints.scatter_(-1, pos[..., None], sign[..., None])
+    scale = pow2(shape[:-1], -3, 3, seed + 3)
+    x = ints * scale[..., None]
+    assert bool((x.to(BF).float() == x).all())
+    return x.to(BF), fp8_bytes(ints), scale
+
+
+# --------------------------------------------------------------------------------------------------------- q / k norm + RoPE
+def rope_table(rows: int, seed: int, B: int = 0) -> torch.Tensor:
+    """fp32 [rows, 64, 2] (or [B, rows, 64, 2]) of (cos, sin) pairs drawn per (row, pair) from the eight dyadic pairs."""
+    shape = (B, rows, 64) if B else (rows, 64)
+    return torch.tensor(ROPE_PAIRS, dtype=torch.float32)[torch.randint(0, 8, shape, generator=gen(seed))].contiguous()
+
+
+def norm_weights(seed: int) -> torch.Tensor:
+    return choice(NORM_WEIGHTS, (128,), seed).to(BF)
+
+
+def qk_norm_rope(lin: torch.Tensor, ranges, weights, cs: torch.Tensor, eps: float = 1e-6, r_ulps: int = 0) -> torch.Tensor:
+    """Per-head RMSNorm * weight, then the interleaved-pair rotation, on the column ranges `ranges` = ((lo, hi), ...) of lin
+    [B, M, N] bf16 with `weights` = (w, ...) one bf16 [128] per range and cs [M, 64, 2] or [B, M, 64, 2]: the rounding points of
+    tfx_rmsnorm_rope -- bf16(x * r), bf16(.* w), bf16(rotation) -- with r = rsqrt(sum x^2 / 128 + eps): the argument in fp32, the root
+    in fp64 rounded once (torch.rsqrt in fp32 is asserted to lie within one step of it), so a device rsqrt that is accurate to one
+    step returns r or a neighbour.  r_ulps: move every row factor by that many fp32 steps (the measurement of the comparison's cap).
+    Asserted: |lin| <= 256, so the 128 squares sum exactly in fp32 (<= 2^23) in any order."""
+    assert lin.dtype == BF and lin.dim() == 3
+    out = lin.clone()
+    B, M, _ = lin.shape
+    cos, sin = cs[..., 0], cs[..., 1]
+    if cs.dim() == 3:
+        cos, sin = cos[None], sin[None]
+    cos, sin = cos[:, :, None, :], sin[:, :, None, :]                              # [B | 1, M, 1, 64]
+    for (lo, hi), w in zip(ranges, weights):
+        x = lin[..., lo:hi].float().view(B, M, (hi - lo) // 128, 128)
+        assert x.abs().max().item() <= ACC_LIMIT
+        ss = (x.double() ** 2).sum(-1, keepdim=True)
+        assert ss.max().item() <= 2 ** 23
+        arg = ss.float() * (1.0 / 128.0) + eps                                      # fp32, as the kernels form it (ss / 128 is exact)
+        r = (1.0 / torch.sqrt(arg.double())).float()                                # the correctly rounded fp32 factor ...
+        t = torch.rsqrt(arg)                                                        # ... which torch.rsqrt (1 / sqrt, two roundings) is one step from at most
+        assert bool(((r == t) | (torch.nextafter(r, t) == t)).all())
+        for _ in range(abs(r_ulps)):
+            r = torch.nextafter(r, torch.full_like(r, math.inf if r_ulps > 0 else 0.0))
+        y = ((x * r).to(BF).float() * w.float()).to(BF).float()
+        y0, y1 = y[..., 0::2], y[..., 1::2]
+        o0, o1 = y0 * cos - y1 * sin, y1 * cos + y0 * sin
+        for o, e in ((o0, y0.double() * cos.double() - y1.double() * sin.double()), (o1, y1.double() * cos.double() + y0.double() * sin.double())):
+            assert bool((o.double() == e).all()), "the rotation must be exact in fp32"
+        out[..., lo:hi] = torch.stack([o0, o1], -1).reshape(B, M, hi - lo).to(BF)
+    return out
+
+
+def expand_pairs(cs: torch.Tensor):
+    """(cos, sin) [.., rows, 128] as tfx_rmsnorm_rope reads them (every value twice) from a pair table [.., rows, 64, 2]."""
+    return cs[..., 0].repeat_interleave(2, -1).contiguous(), cs[..., 1].repeat_interleave(2, -1).contiguous()
+
+
+# --------------------------------------------------------------------------------------------------------- attention
+def _valid_lengths(B, N, lengths):
+    L = [N] * B if lengths is None else [int(x) for x in lengths]
+    assert len(L) == B and all(1 <= x <= N for x in L)
+    return L
+
+
+def _zero_sum_values(L: int, D: int, g: torch.Generator) -> torch.Tensor:
+    """z [L, D] of +-128: every column sums to zero -- L // 2 rows of random signs, their negatives, one zero row when L is odd --
+    with the rows in shuffled order."""
+    h = L // 2
+    s = torch.where(torch.rand(h, D, generator=g) < 0.5, -128.0, 128.0)
+    z = torch.cat([s, -s, torch.zeros(L - 2 * h, D)], 0)
+    return z[torch.randperm(L, generator=g)]
+
+
+@functools.lru_cache(maxsize=None)
+def uniform_attention(B: int, H: int, N: int, seed: int, lengths=None, D: int = 128, pad=float("nan"), nonzero_c: bool = False):
+    """q = 0 (every weight exactly 1), k arbitrary, v = c + z with integer c[b, h, d] in [-3, 3] and z = +-128 summing to zero over each
+    sample's valid keys.  Expected output: c in every valid row.  Rows >= lengths[b] of q / k / v hold `pad`.
+    Returns (q, k, v, want) as bf16 [B, N, H * D]; want's padding rows are NaN (the caller checks its own sentinel there).
+    Asserted: every value an integer bf16 holds, partial sums below 2^24, and one key more or less moves the result by more than a bf16 step."""
+    g = gen(seed)
+    L = _valid_lengths(B, N, lengths)
+    c = torch.randint(-3, 4, (B, 1, H, D), generator=g).float()
+    if nonzero_c:       # no value of v is 0 then (the zero row of an odd key count holds c): a selected v has a bf16 step to be exact within
+        c = torch.where(c == 0, torch.where(torch.rand(c.shape, generator=g) < 0.5, -1.0, 1.0), c)
+    q = torch.zeros(B, N, H, D)
+    k = torch.randn(B, N, H, D, generator=g)
+    v = torch.full((B, N, H, D), pad)
+    want = torch.full((B, N, H, D), float("nan"))
+    for b in range(B):
+        for h in range(H):
+            v[b, :L[b], h] = c[b, 0, h] + _zero_sum_values(L[b], D, g)
+        want[b, :L[b]] = c[b]
+        q[b, L[b]:], k[b, L[b]:] = pad, pad
+        vb = v[b, :L[b]]
+        assert bool((vb == vb.round()).all()) and vb.abs().max().item() <= 131 and bool((vb.to(BF).float() == vb).all())
+        assert L[b] * 131 < 2 ** 24 and bool((vb.sum(0) == L[b] * c[b, 0]).all())
+        assert 128.0 / L[b] > 2 ** -6, "a dropped key must move |c| <= 3 by more than one bf16 step (2^-6 in [2, 4))"
+    return tuple(t.reshape(B, N, H * D).to(BF) for t in (q, k, v, want))
+
+
+def selector_values(shape, g: torch.Generator) -> torch.Tensor:
+    """bf16 values with every mantissa and both signs, 0.5 <= |v| < 2: any two differ by less than 4, and half a bf16 step of the
+    smallest is 2^-10."""
+    mant = 1.0 + torch.randint(0, 128, shape, generator=g).float() / 128.0
+    e = torch.where(torch.rand(shape, generator=g) < 0.5, 0.5, 1.0)
+    return mant * e * torch.where(torch.rand(shape, generator=g) < 0.5, -1.0, 1.0)
+
+
+def selector_margin(qh: torch.Tensor, kh: torch.Tensor, pi: torch.Tensor, scale: float, causal: bool = False) -> float:
+    """n_keys * exp(-(own score - largest other score)) of one (sample, head): qh, kh [L, D] fp32 with integer-valued products."""
+    L = qh.shape[0]
+    s = (qh @ kh.T) * scale
+    own = s[torch.arange(L), pi].clone()
+    s[torch.arange(L), pi] = -math.inf
+    if causal:
+        s = s + torch.full((L, L), -math.inf).triu(1)
+    if L == 1:
+        return 0.0
+    gap = (own - s.max(-1).values).min().item()
+    return L * math.exp(-gap)
+
+
+@functools.lru_cache(maxsize=None)
+def selector_attention(B: int, H: int, N: int, seed: int, lengths=None, D: int = 128, mult: float = 3.0, scale: float = None,
+                       causal: bool = False, pad=float("nan")):
+    """k[j] = a random +-1 code of D entries, q[i] = mult * k[pi(i)] with one permutation pi of the valid rows per (sample, head)
+    (causal: a random map with pi(i) <= i), v = selector_values.  The chosen key's scaled score is mult * D * scale, the others are
+    mult * N(0, 1) * sqrt(D) * scale.  Expected output: v[pi(i)].
+    Asserted on the realised data, per (sample, head): n_keys * exp(-(own score - largest other score)) <= 2^-12.  The other keys
+    then move an output by at most 4 * 2^-12 = 2^-10 (values differ by < 4), half a bf16 step of the smallest |v| = 0.5, before
+    a softmax's own fp32 rounding (~2^-20): the stored bf16 is v[pi(i)].  Returns (q, k, v, want, max |scaled score|)."""
+    g = gen(seed)
+    scale = D ** -0.5 if scale is None else scale
+    L = _valid_lengths(B, N, lengths)
+    q, k, v = (torch.full((B, N, H, D), pad) for _ in range(3))
+    want = torch.full((B, N, H, D), float("nan"))
+    worst = 0.0
+    for b in range(B):
+        n = L[b]
+        for h in range(H):
+            code = torch.where(torch.rand(n, D, generator=g) < 0.5, -1.0, 1.0)
+            if causal:
+                pi = (torch.rand(n, generator=g) * (torch.arange(n) + 1)).long().clamp(max=n - 1)
+                pi = torch.minimum(pi, torch.arange(n))
+            else:
+                pi = torch.randperm(n, generator=g)
+            vals = selector_values((n, D), g)
+            k[b, :n, h], q[b, :n, h], v[b, :n, h], want[b, :n, h] = code, mult * code[pi], vals, vals[pi]
+            worst = max(worst, selector_margin(mult * code[pi], code, pi, scale, causal))
+    assert worst <= 2 ** -12, f"selector margin {worst:.3e} > 2^-12 at B {B} H {H} N {N} (lengths {lengths})"
+    return tuple(t.reshape(B, N, H * D).to(BF) for t in (q, k, v, want)) + (mult * D * scale,)
+
+
+@functools.lru_cache(maxsize=None)
+def bias_selector_attention(B: int, H: int, N: int, delta: int, seed: int, D: int = 64, peak: float = 24.0):
+    """attention64's relative bias as the selector: q = 0, rel_bias [H, 2N - 1] zero except `peak` at index delta + N - 1, so query i
+    puts weight 1 on key i + delta and exp(-peak) on every other one; v has uniform_attention's zero-sum structure with c != 0, so that
+    no v is 0 (a selected 0 would have to come out as exactly 0, which a running-maximum kernel that rescales its early keys' weights
+    by exp2 differences cannot promise and need not).  Expected: row i = v[i + delta] where that key exists (the others move it by
+    < N * exp(-24) * 262 = 5e-6, far inside half a bf16 step of |v| >= 1, 2^-9), else the uniform answer c.
+    Returns (q, k, v, rel_bias fp32, want)."""
+    assert -(N - 1) <= delta <= N - 1 and N * math.exp(-peak) * 262 < 2.0 ** -12
+    q, k, v, c = uniform_attention(B, H, N, seed, None, D, nonzero_c=True)
+    assert v.float().abs().min().item() >= 1.0
+    bias = torch.zeros(H, 2 * N - 1)
+    bias[:, delta + N - 1] = peak
+    want = c.clone()
+    lo, hi = max(0, -delta), min(N, N - delta)                                   # queries whose target exists
+    want[:, lo:hi] = v[:, lo + delta:hi + delta]
+    return q, k, v, bias, want
+
+
+def _softmax_times(s: torch.Tensor, v: torch.Tensor) -> torch.Tensor:
+    """softmax(s) v in fp64 as (exp(s - max) v) / sum exp(s - max): weights of exactly 1 then meet integer values in an exact sum
+    (torch.softmax divides first, and n * (1 / n) * c is not c)."""
+    p = torch.exp(s - s.max(-1, keepdim=True).values)
+    return (p @ v) / p.sum(-1, keepdim=True)
+
+
+def attention64_reference(q, k, v, scale, rel_bias=None, causal=False, D=64):
+    """fp64 softmax(scale q k^T + bias) v of bf16 [B, N, H * D] operands, rounded once."""
+    B, N, HD = q.shape
+    H = HD // D
+    qh, kh, vh = (t.double().view(B, N, H, D).transpose(1, 2) for t in (q, k, v))
+    s = (qh @ kh.transpose(-1, -2)) * scale
+    if rel_bias is not None:
+        idx = torch.arange(N)[None, :] - torch.arange(N)[:, None] + N - 1
+        s = s + rel_bias.double()[:, idx]
+    if causal:
+        s = s + torch.full((N, N), -math.inf, dtype=torch.float64).triu(1)
+    return _softmax_times(s, vh).transpose(1, 2).reshape(B, N, HD).float().to(BF)
+
+
+def attention_reference(q, k, v, lengths=None, D=128, scale=None):
+    """fp64 softmax attention over each sample's valid rows, rounded once; rows beyond a sample's length are NaN."""
+    B, N, HD = q.shape
+    H = HD // D
+    L = _valid_lengths(B, N, lengths)
+    out = torch.full((B, N, HD), float("nan"), dtype=torch.float64)
+    for b in range(B):
+        qh, kh, vh = (t[b, :L[b]].double().view(L[b], H, D).transpose(0, 1) for t in (q, k, v))
+        s = (qh @ kh.transpose(-1, -2)) * (D ** -0.5 if scale is None else scale)
+        out[b, :L[b]] = _softmax_times(s, vh).transpose(0, 1).reshape(L[b], HD)
+    return out.float().to(BF)
+
+
+# --------------------------------------------------------------------------------------------------------- convolution
+def conv_operands(B, H, W, Cin, Cout, seed, stride=1, up=1, with_res=False):
+    """x [B, Cin, H, W], w [Cout, Cin, 3, 3] ternary-sparse, integer bias; `want` = F.conv2d in fp64 on the NCHW view (nearest 2x
+    upsample first when up == 2; stride 2 pads (0, 1, 0, 1) as the VAE's downsample does), rounded once, then bf16(res + .) with a
+    residual.  Asserted: max|conv + bias| <= 256 before the residual.  Returns NHWC / KRSC bf16 operands and want [B, H', W', Cout]."""
+    F = torch.nn.functional
+    x, w, bias = ternary((B, Cin, H, W), seed + 1), ternary((Cout, Cin, 3, 3), seed + 2), integers((Cout,), -8, 8, seed + 3)
+    xin = F.interpolate(x.double(), scale_factor=2.0, mode="nearest") if up == 2 else x.double()
+    if stride == 2:
+        acc = F.conv2d(F.pad(xin, (0, 1, 0, 1)), w.double(), None, stride=2, padding=0)
+    else:
+        acc = F.conv2d(xin, w.double(), None, stride=1, padding=1)
+    acc = acc.permute(0, 2, 3, 1).contiguous()
+    check_accumulators(acc, bias)
+    lin = linear_bf16(acc, bias)
+    res = arbitrary_bf16(lin.shape, seed + 4) if with_res else None
+    return dict(x=x.permute(0, 2, 3, 1).contiguous().to(BF), w=w.permute(0, 2, 3, 1).contiguous().to(BF), bias=bias.to(BF), res=res,
+                acc=acc, want=(res + lin) if with_res else lin)
+
+
+# --------------------------------------------------------------------------------------------------------- the shapes of tests/test_exact_gpu.py
+# (tests/test_exact_inputs_cpu.py runs every generator at every one of them: a condition that fails must fail without a GPU)
+GEMM_EPI_SHAPES = [(2, 300, 264, 128), (3, 37, 72, 192), (1, 8, 64, 128), (2, 513, 520, 384)]          # (B, M, N, K)
+GEMM_KSLICE_KS = (1024, 1536, 2048, 3072)                                                              # (1, 300, 520, K)
+GEMM_TAIL_SHAPE = (1, 4096, 9216, 1024)
+# |lin| <= 71 at K <= 3072, and gate * lin is then a bf16 number for every gate of GATES: epilogue 2's intermediate rounding cannot be
+# seen.  At K = 12288 (std 28) a couple of dozen elements of this launch have a |lin| whose product with +-0.75 / +-1.5 needs a ninth bit.
+GEMM_ROUNDING_SHAPE = (1, 300, 264, 12288)
+QKN_SHARE_ONE_ULP = 0.0     # measured (tests/test_exact_inputs_cpu.py): q / k elements whose bits change when r moves one fp32 step
+GEMM_F32_SHAPES = [(1, 300, 520, 128), (2, 1015, 1015, 256)]
+GEMM_COLSCALE_SHAPES = [(1, 300, 264, 192), (2, 80, 384, 256)]
+GEMM_FP8_SHAPES = [(1, 512, 512, 256), (2, 1000, 3136, 512)]
+LORA_MS, LORA_NK, LORA_RS = (80, 1664), (768, 256), (128, 256)
+QKN_M, QKN_K, QKN_POS0, QKN_D = 2344, 256, 7, 3072
+ATTN_SHAPES = [(1, 1, 1), (2, 3, 8), (1, 2, 33), (1, 1, 64), (1, 1, 65), (2, 2, 96), (1, 3, 300), (2, 2, 1664)]      # (B, H, N)
+ATTN_PERSISTENT_SHAPES = [(16, 24, 50), (3, 24, 1100)]
+ATTN_STREAMK_SHAPE = (2, 5, 2304)
+ATTN_TAIL_SHAPE = (1, 24, 3100)
+ATTN_SEQ_LEN_CASES = [((4, 24, 1024), (1024, 777, 257, 64)), ((2, 2, 512), (512, 130))]
+ATTN64_NS, ATTN64_HS, ATTN64_MULT = (1, 40, 77, 129, 512), (2, 12), 6.0
+# (B, H, W, Cin, Cout, stride, up, pad_lo, with_res): the smallest rows of tests/test_vae_kernels_gpu.py's parametrisations
+CONV_CASES = [(2, 12, 20, 64, 64, 1, 1, 1, False), (1, 9, 7, 128, 72, 1, 1, 1, True), (2, 8, 6, 64, 128, 1, 2, 1, False),
+              (1, 16, 12, 64, 64, 2, 1, 0, False)]
+CONV_NARROW_CASES = [(2, 20, 24, 3, 64), (1, 9, 13, 16, 128)]                                           # (B, H, W, Cin, Cout)
+CONV_PAIR_CASES = [(2, 12, 20, 64, 128, False), (1, 9, 14, 128, 128, True)]                             # (B, H, W, Cin, Cout, with_res)
+
+
+def shape_seed(*shape) -> int:
+    s = 17
+    for x in shape:
+        s = (s * 1000003 + int(x)) % (2 ** 31 - 1)
+    return s
+
+
+def lora_case(M: int, N: int, K: int, R: int, B: int, nseg: int, seed: int, sets: int = 1) -> dict:
+    """Operands of tfx_gemm_bf16_lora in the exact regime: x [B, M, K], T [nseg][B, M, R] (one block per segment, its own seed), and per
+    weight set W [N, K] | Bm [N, R] with the rows of segment s drawn from that segment's seed.  acc[set][B, M, N] per segment mask is
+    taken with lora_acc.  Every operand is ternary-sparse: ONE exact accumulation over K + R."""
+    x = ternary((B, M, K), seed + 1)
+    T = torch.stack([ternary((B, M, R), seed + 100 + s) for s in range(nseg)])
+    W = torch.stack([ternary((N, K), seed + 200 + i) for i in range(sets)])
+    Bm = torch.stack([torch.cat([ternary((N // nseg, R), seed + 300 + 10 * i + s) for s in range(nseg)]) for i in range(sets)])
+    bias = torch.stack([integers((N,), -8, 8, seed + 400 + i) for i in range(sets)])
+    return dict(x=x, T=T, W=W, Bm=Bm, bias=bias, nseg=nseg, seg_cols=N // nseg)
+
+
+def lora_acc(cs: dict, mask: int, which: int = 0) -> torch.Tensor:
+    """x W^T + T_seg Bm^T over the segments of `mask`, fp64 integers [B, M, N], of weight set `which`; asserted <= 256 with the bias."""
+    acc = cs["x"].double() @ cs["W"][which].double().T
+    sc = cs["seg_cols"]
+    for s in range(cs["nseg"]):
+        if mask >> s & 1:
+            acc[..., s * sc:(s + 1) * sc] += cs["T"][s].double() @ cs["Bm"][which][s * sc:(s + 1) * sc].double().T
+    check_accumulators(acc, cs["bias"][which])
+    return acc

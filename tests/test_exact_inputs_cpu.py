@@ -1,0 +1,387 @@
+"""The exact-input constructions of tests/helpers/exact_inputs.py, proven without a GPU.
+
+Three things, for every shape tests/test_exact_gpu.py uses: each generator meets the exactness condition it asserts; each CPU
+restatement in fp64 rounds to the bits the construction claims (uniform attention -> c, selector -> v[pi], the integer GEMM and
+convolution chains); and assert_elementwise rejects every emulated kernel fault -- a dropped product, a dropped K-tile, a shifted
+bias chunk, another sample's gate, a missing rounding, a dropped / padded / swapped key, swapped heads, a shifted rotary pair.
+The faults are injected into the CPU computation; no kernel code is restated here."""
+import pytest
+import torch
+
+from tests.helpers import exact_inputs as X
+
+BF = torch.bfloat16
+
+
+def step(x):
+    """The next bf16 value away from zero."""
+    return (x.view(torch.int16) + 1).view(BF)
+
+
+def rejects(got, want, what, **kw):
+    with pytest.raises(AssertionError, match=what) as e:
+        X.assert_elementwise(got, want, what, **kw)
+    return str(e.value)
+
+
+# ------------------------------------------------------------------------------------------------ assert_elementwise itself
+def test_assert_elementwise_counts_steps_and_names_the_tile():
+    want = torch.tensor([[1.0, -2.0, 0.0, 300.0]], dtype=BF).repeat(600, 130)            # [600, 520]
+    assert X.assert_elementwise(want.clone(), want, "same") == 0
+    got = want.clone()
+    got[513, 261] = step(got[513, 261])
+    msg = rejects(got, want, "one step")
+    assert "1 of 312000" in msg and "(batch 0, row 513, col 261)" in msg and "tile (2, 1) at (1, 5)" in msg
+    assert X.assert_elementwise(got, want, "one step allowed", ulps=1) == 1
+    rejects(got, want, "capped", ulps=1, cap=1e-7)                                       # within a step, but more of them than the cap
+    got[513, 261] = step(got[513, 261])
+    rejects(got, want, "two steps", ulps=1)
+    z = torch.zeros(4, 8, dtype=BF)
+    assert X.assert_elementwise(-z, z, "signed zero") == 0                              # -0 == +0, as torch.equal has it
+    tiny = z.clone()
+    tiny[1, 1] = step(tiny[1, 1])                           # the smallest subnormal: one step from either zero
+    assert X.assert_elementwise(-tiny, tiny, "across zero", ulps=2) == 1
+    rejects(-tiny, tiny, "across zero", ulps=1)
+    nan = want.clone()
+    nan[0, 0] = float("nan")
+    rejects(nan, want, "NaN got", ulps=1)
+    rejects(nan, nan, "NaN both")
+    f = torch.arange(12.0).view(3, 4)
+    assert X.assert_elementwise(f.clone(), f, "fp32") == 0
+    rejects(f + 2 ** -20, f, "fp32")
+    msg = rejects(torch.ones(2, 3, 8, dtype=BF), torch.full((2, 3, 8), 2.0, dtype=BF), "batched")
+    assert "48 of 48" in msg and "(batch 1," not in msg.split("first 16")[0] and msg.count("\n") == 16
+
+
+# ------------------------------------------------------------------------------------------------ GEMM: conditions, chains, faults
+def all_gemm_shapes():
+    return (X.GEMM_EPI_SHAPES + [X.GEMM_ROUNDING_SHAPE] + [(1, 300, 520, K) for K in X.GEMM_KSLICE_KS] + [(2, 300, 520, 1024)] + X.GEMM_F32_SHAPES +
+            X.GEMM_COLSCALE_SHAPES + X.GEMM_FP8_SHAPES + [(1, X.QKN_M, 4 * X.QKN_D, X.QKN_K), (2, X.QKN_M, 3 * X.QKN_D, X.QKN_K)])
+
+
+@pytest.mark.parametrize("B,M,N,K", all_gemm_shapes())
+def test_gemm_generator_condition_holds(B, M, N, K):
+    cs = X.gemm_operands(B, M, N, K, X.shape_seed(B, M, N, K))
+    for t in (cs["a"], cs["w"]):
+        assert set(t.float().unique().tolist()) <= {-1.0, 0.0, 1.0} and 0.2 < (t != 0).float().mean().item() < 0.3
+    assert cs["bias"].float().abs().max().item() <= 8
+    assert torch.equal(cs["a"].float() @ cs["w"].float().T, cs["acc"].float())          # fp32 sums these integers exactly as well
+    X.fp8_bytes(cs["a"]), X.fp8_bytes(cs["w"])                                          # ... and every operand is an e4m3 number
+    if (B, M, N, K) in X.GEMM_F32_SHAPES[1:]:
+        X.gemm_operands(B, M, N, K, X.shape_seed(B, M, N, K), w_batched=True)
+
+
+def test_gemm_generator_condition_holds_at_the_sliced_last_round_shape():
+    B, M, N, K = X.GEMM_TAIL_SHAPE
+    cs = X.gemm_operands(B, M, N, K, X.shape_seed(B, M, N, K), product=False)
+    acc = cs["a"][0].float() @ cs["w"].float().T                                        # exact in fp32: integer partial sums <= K < 2^24
+    X.check_accumulators(acc, cs["bias"])
+    rows = torch.arange(0, M, 173)
+    assert torch.equal(acc[rows].double(), cs["a"][0, rows].double() @ cs["w"].double().T)
+
+
+def test_generator_refuses_a_shape_outside_the_exact_regime():
+    with pytest.raises(AssertionError, match="exact regime"):
+        X.check_accumulators(torch.full((2, 2), 250.0, dtype=torch.float64), torch.full((2,), 8.0))
+    with pytest.raises(AssertionError, match="exact regime"):
+        X.gemm_operands(1, 64, 64, 65536, 5, p_nonzero=1.0)                              # a shape / density added later cannot leave it silently
+    with pytest.raises(AssertionError, match="integers"):
+        X.check_accumulators(torch.full((2, 2), 0.5, dtype=torch.float64))
+
+
+@pytest.fixture(scope="module")
+def g():
+    """One GEMM case with every epilogue operand: (2, 300, 264, 128), the ragged shape of the GPU file."""
+    B, M, N, K = X.GEMM_EPI_SHAPES[0]
+    cs = X.gemm_operands(B, M, N, K, X.shape_seed(B, M, N, K))
+    cs.update(gate=X.gates(B, N, 11), res=X.arbitrary_bf16((B, M, N), 12), lin=X.linear_bf16(cs["acc"], cs["bias"].float()))
+    return cs
+
+
+def test_chains_are_the_documented_rounding_points(g):
+    lin, res, gate = g["lin"], g["res"], g["gate"]
+    assert torch.equal(lin.double(), g["acc"] + g["bias"].double())                      # bf16 holds every pre-activation exactly
+    assert torch.equal(X.chain(3, lin, res=res), (res.double() + lin.double()).float().to(BF))
+    prod = (gate.double()[:, None] * lin.double()).float().to(BF)
+    assert torch.equal(X.chain(2, lin, res=res, gate=gate), (res.double() + prod.double()).float().to(BF))
+    out = X.chain(1, lin, gelu_from_col=256)
+    assert torch.equal(out[..., :256], lin[..., :256])
+    ref = torch.nn.functional.gelu(lin[..., 256:].double(), approximate="tanh")
+    assert (X.gelu_tanh64(lin[..., 256:]) - ref).abs().max().item() < 1e-12              # the same function (where 1 + tanh does not cancel)
+    m = X.gelu_exact_mask(lin, 256)
+    assert m[..., :256].all() and 0 < m[..., 256:].float().mean().item() < 1
+    mg, lg = m[..., 256:], lin[..., 256:]
+    assert torch.equal(out[..., 256:][mg], torch.where(lg > 0, lg, torch.zeros_like(lg))[mg])       # exact cases: 0, or x itself
+    cscale = X.pow2((lin.shape[-1],), -3, 3, 13)
+    assert torch.equal(X.linear_bf16(g["acc"], col_scale=cscale).double(), g["acc"] * cscale.double())    # epilogue 4: exact
+
+
+def test_fault_one_product_dropped_from_one_element(g):
+    a, w = g["a"].double(), g["w"].double()
+    b, m, n = 1, 299, 263
+    k = (a[b, m] * w[n]).nonzero()[0].item()
+    acc = g["acc"].clone()
+    acc[b, m, n] -= a[b, m, k] * w[n, k]
+    msg = rejects(X.linear_bf16(acc, g["bias"].float()), g["lin"], "dropped product")
+    assert "1 of" in msg and "(batch 1, row 299, col 263)" in msg and "tile (1, 1) at (43, 7)" in msg
+    for epi in (2, 3):
+        rejects(X.chain(epi, X.linear_bf16(acc, g["bias"].float()), res=g["res"], gate=g["gate"]),
+                X.chain(epi, g["lin"], res=g["res"], gate=g["gate"]), "dropped product")
+
+
+def test_fault_one_k_tile_dropped_for_one_tile():
+    B, M, N, K = X.GEMM_EPI_SHAPES[3]
+    cs = X.gemm_operands(B, M, N, K, X.shape_seed(B, M, N, K))
+    a, w = cs["a"].double(), cs["w"].double()
+    acc = cs["acc"].clone()
+    acc[1, 256:512, 512:] -= a[1, 256:512, 320:384] @ w[512:, 320:384].T                 # K-tile 5 of tile (1, 2) of sample 1 (ragged in N)
+    msg = rejects(X.linear_bf16(acc, cs["bias"].float()), X.linear_bf16(cs["acc"], cs["bias"].float()), "dropped K-tile")
+    assert "tile (1, 2)" in msg and "tile (0," not in msg and "batch 0" not in msg
+
+
+def test_fault_bias_shifted_by_one_chunk(g):
+    bias = g["bias"].float().clone()
+    bias[256:264] = g["bias"].float()[248:256]                                           # the ragged edge's 8 columns read their neighbour's bias
+    assert not torch.equal(bias, g["bias"].float())
+    msg = rejects(X.linear_bf16(g["acc"], bias), g["lin"], "shifted bias")
+    assert "tile (0, 1)" in msg and "tile (0, 0)" not in msg
+
+
+def test_fault_gate_of_sample_0_used_for_sample_1(g):
+    gate = g["gate"].clone()
+    gate[1] = gate[0]
+    msg = rejects(X.chain(2, g["lin"], res=g["res"], gate=gate), X.chain(2, g["lin"], res=g["res"], gate=g["gate"]), "wrong gate")
+    assert "batch 0" not in msg
+
+
+def test_fault_intermediate_rounding_of_epilogue_2_omitted(g):
+    """gate * lin is a bf16 number while |lin| stays small (always at K <= 3072: `n` is 0 on the fixture's K = 128), so the rounding
+    point shows only at the K = 12288 shape the GPU file adds for it."""
+    once = (g["res"].double() + g["gate"].double()[:, None] * g["lin"].double()).float().to(BF)
+    assert X.mismatches(once, X.chain(2, g["lin"], res=g["res"], gate=g["gate"])).sum().item() == 0
+    B, M, N, K = X.GEMM_ROUNDING_SHAPE
+    cs = X.gemm_operands(B, M, N, K, X.shape_seed(B, M, N, K))
+    lin, gate, res = X.linear_bf16(cs["acc"], cs["bias"].float()), X.gates(B, N, 11), X.arbitrary_bf16((B, M, N), 12)
+    want = X.chain(2, lin, res=res, gate=gate)
+    once = (res.double() + gate.double()[:, None] * lin.double()).float().to(BF)
+    assert X.mismatches(once, want).sum().item() >= 10                                   # 22 of 79200 elements
+    rejects(once, want, "one rounding")
+    unrounded_gelu = X.gelu_tanh64(g["acc"] + g["bias"].double())                       # (bf16 holds the Linear exactly here: GELU's rounding point
+    assert torch.equal(unrounded_gelu.float().to(BF)[..., 256:], X.chain(1, g["lin"], gelu_from_col=256)[..., 256:])   # is not observable, by construction)
+
+
+def test_fp8_operands_and_quantisable_rows():
+    for shape in ((2, 37, 256), (1, 300, 512)):
+        x, codes, scale = X.quantizable_rows(shape, X.shape_seed(*shape))
+        assert torch.equal(x.float().abs().amax(-1) / 448.0, scale)                      # the header's scale, exactly a power of two
+        assert torch.equal((x.float() / scale[..., None]).to(X.F8).view(torch.uint8), codes)
+    B, M, N, K = X.GEMM_FP8_SHAPES[0]
+    cs = X.gemm_operands(B, M, N, K, X.shape_seed(B, M, N, K))
+    sa, sw = X.pow2((B, M), -3, 3, 1), X.pow2((N,), -3, 3, 2)
+    lin = X.linear_bf16(cs["acc"], cs["bias"].float(), row_scale=sa, col_scale=sw)
+    assert torch.equal(lin, (cs["acc"] * sa.double()[..., None] * sw.double() + cs["bias"].double()).float().to(BF))
+    sw2 = sw.clone()
+    sw2[8:16] = sw[0:8] * 2
+    rejects(X.linear_bf16(cs["acc"], cs["bias"].float(), row_scale=sa, col_scale=sw2), lin, "shifted channel scale")
+
+
+@pytest.mark.parametrize("M", X.LORA_MS)
+@pytest.mark.parametrize("R", X.LORA_RS)
+def test_lora_generator_condition_and_neighbour_sensitivity(M, R):
+    N, K = X.LORA_NK
+    cs = X.lora_case(M, N, K, R, 2, 3, X.shape_seed(M, N, K, R), sets=2)
+    full = X.lora_acc(cs, 0b111)
+    assert not torch.equal(full, X.lora_acc(cs, 0b101)) and torch.equal(full[..., :256], X.lora_acc(cs, 0b101)[..., :256])
+    X.lora_acc(cs, 0b111, which=1)
+    wrong = cs["x"].double() @ cs["W"][0].double().T                                    # every segment reads segment 0's T block
+    for s in range(3):
+        wrong[..., s * 256:(s + 1) * 256] += cs["T"][0].double() @ cs["Bm"][0][s * 256:(s + 1) * 256].double().T
+    msg = rejects(X.linear_bf16(wrong, cs["bias"][0]), X.linear_bf16(full, cs["bias"][0]), "neighbour's T")
+    assert ", 0) at" not in msg                                                          # segment 0 (column tile 0) is right
+
+
+# ------------------------------------------------------------------------------------------------ q / k norm + RoPE
+@pytest.fixture(scope="module")
+def qkn():
+    B, M, D, K = 2, 300, 256, X.QKN_K                                                    # two heads per range: same construction, small
+    cs = X.gemm_operands(B, M, 3 * D, K, 77)
+    cs.update(lin=X.linear_bf16(cs["acc"], cs["bias"].float()), wq=X.norm_weights(1), wk=X.norm_weights(2), tab=X.rope_table(M, 3, B=B),
+              ranges=((2 * D, 3 * D), (0, D)))
+    cs["want"] = X.qk_norm_rope(cs["lin"], cs["ranges"], (cs["wq"], cs["wk"]), cs["tab"])
+    return cs
+
+
+def test_rope_table_and_norm_inputs_are_dyadic_and_differ_everywhere(qkn):
+    tab = qkn["tab"]
+    assert tab.shape == (2, 300, 64, 2) and {tuple(p) for p in tab.view(-1, 2).tolist()} == set(X.ROPE_PAIRS)
+    assert (tab[:, :, 1:] != tab[:, :, :-1]).any(-1).float().mean().item() > 0.8       # neighbouring pairs differ: a shift is visible
+    assert set(qkn["wq"].float().tolist()) <= set(X.NORM_WEIGHTS)
+    cos, sin = X.expand_pairs(tab)
+    assert cos.shape == (2, 300, 128) and torch.equal(cos[..., 0::2], cos[..., 1::2]) and torch.equal(sin[..., 1::2], tab[..., 1])
+    assert torch.equal(qkn["want"][..., 256:512], qkn["lin"][..., 256:512])             # v columns untouched
+    assert not torch.equal(qkn["want"][..., :256], qkn["lin"][..., :256])
+
+
+def test_fault_one_rotary_pair_shifted_by_one(qkn):
+    tab = qkn["tab"].clone()
+    tab[1, 17] = torch.roll(tab[1, 17], 1, 0)
+    got = X.qk_norm_rope(qkn["lin"], qkn["ranges"], (qkn["wq"], qkn["wk"]), tab)
+    msg = rejects(got, qkn["want"], "shifted pair")
+    assert "(batch 1, row 17," in msg and "batch 0" not in msg
+    shared = X.qk_norm_rope(qkn["lin"], qkn["ranges"], (qkn["wq"], qkn["wk"]), qkn["tab"][0])          # sample 1 reads sample 0's table
+    assert "batch 0" not in rejects(shared, qkn["want"], "shared table")
+    rejects(X.qk_norm_rope(qkn["lin"], qkn["ranges"], (qkn["wk"], qkn["wq"]), qkn["tab"]), qkn["want"], "swapped norm weights")
+
+
+def qkn_sensitivity(lin, ranges, weights, tab):
+    """Share of the q / k elements whose bits change when every row factor moves by one fp32 step, either way."""
+    mid = X.qk_norm_rope(lin, ranges, weights, tab)
+    moved = torch.zeros(mid.shape, dtype=torch.bool)
+    for d in (-1, 1):
+        moved |= X.mismatches(X.qk_norm_rope(lin, ranges, weights, tab, r_ulps=d), mid)
+    n = sum(hi - lo for lo, hi in ranges) * lin.shape[0] * lin.shape[1]
+    return moved.sum().item() / n
+
+
+def test_qkn_cap_is_the_measured_one_ulp_sensitivity():
+    """The cap of the GPU comparison against the CPU restatement: at (M 2344, N 9216, K 256) the share of q / k elements whose stored
+    bits change when the row factor r moves by one fp32 step either way -- measured: 0 of 14.4 M (two steps: 47, 3.3e-6; eight: 2008).
+    The integer x of these inputs times a 24-bit r lands on a bf16 tie too rarely for one step to cross one.  X.QKN_SHARE_ONE_ULP is
+    what the GPU file multiplies by four; it must be this measurement."""
+    M, D, K = X.QKN_M, X.QKN_D, X.QKN_K
+    for B, N in ((1, 3 * D), (1, 4 * D)):
+        cs = X.gemm_operands(B, M, N, K, X.shape_seed(B, M, N, K))
+        lin = X.linear_bf16(cs["acc"], cs["bias"].float())
+        share = qkn_sensitivity(lin, ((2 * D, 3 * D), (0, D)), (X.norm_weights(1), X.norm_weights(2)),
+                                X.rope_table(M + X.QKN_POS0, 3)[X.QKN_POS0:])
+        print(f"q/k norm, N {N}: {share:.3e} of the elements change under one fp32 step of the row factor")
+        assert share == X.QKN_SHARE_ONE_ULP
+
+
+# ------------------------------------------------------------------------------------------------ attention
+def seq_cases():
+    return [(B, H, N, None) for B, H, N in X.ATTN_SHAPES + X.ATTN_PERSISTENT_SHAPES + [X.ATTN_STREAMK_SHAPE, X.ATTN_TAIL_SHAPE]] + \
+           [(B, H, N, L) for (B, H, N), L in X.ATTN_SEQ_LEN_CASES]
+
+
+@pytest.mark.parametrize("B,H,N,L", seq_cases())
+def test_attention_generator_conditions_hold(B, H, N, L):
+    seed = X.shape_seed(B, H, N)
+    q, k, v, want = X.uniform_attention(B, H, N, seed, L)
+    assert q.shape == (B, N, H * 128) and (q[:, :(min(L) if L else N)] == 0).all()
+    q, k, v, want, bound = X.selector_attention(B, H, N, seed, L)
+    assert bound < 35.0 and abs(bound - 33.94) < 0.01                                    # admissible for the reference-free stream
+    if L:
+        for b, n in enumerate(L):
+            assert torch.isnan(v[b, n:].float()).all() and torch.isnan(q[b, n:].float()).all() and torch.isfinite(want[b, :n].float()).all()
+
+
+def valid(t, L):
+    """The rows below each sample's length (beyond them both sides hold NaN, which never compares equal)."""
+    return t if L is None else torch.cat([t[b, :n] for b, n in enumerate(L)])
+
+
+@pytest.mark.parametrize("B,H,N,L", [(B, H, N, None) for B, H, N in X.ATTN_SHAPES] + [(2, 2, 512, (512, 130))])
+def test_attention_restatements_round_to_the_claimed_bits(B, H, N, L):
+    seed = X.shape_seed(B, H, N)
+    q, k, v, want = X.uniform_attention(B, H, N, seed, L)
+    got = X.attention_reference(q, k, v, L)
+    X.assert_elementwise(valid(got, L), valid(want, L), "uniform -> c")
+    if L:
+        assert torch.isnan(got[1, L[1]:].float()).all() and torch.isnan(want[1, L[1]:].float()).all()
+    q, k, v, want, _ = X.selector_attention(B, H, N, seed, L)
+    X.assert_elementwise(valid(X.attention_reference(q, k, v, L), L), valid(want, L), "selector -> v[pi]")
+
+
+@pytest.fixture(scope="module")
+def att():
+    """(1, 3, 300): ragged in the last 64-key tile (keys 256 .. 299), three heads."""
+    B, H, N = 1, 3, 300
+    seed = X.shape_seed(B, H, N)
+    return dict(u=X.uniform_attention(B, H, N, seed), s=X.selector_attention(B, H, N, seed), B=B, H=H, N=N)
+
+
+def test_fault_one_key_dropped_for_one_query_row(att):
+    for name in ("u", "s"):
+        q, k, v, want = att[name][:4]
+        got = want.clone()
+        i, h = 123, 1
+        sl = slice(h * 128, (h + 1) * 128)
+        s = (q[0, i, sl].double() @ k[0, :, sl].double().T) * 128 ** -0.5
+        drop = int(s.argmax()) if name == "s" else 40                                    # the selected key / any key of the uniform form
+        s[drop] = -float("inf")
+        got[0, i, sl] = (torch.softmax(s, -1) @ v[0, :, sl].double()).float().to(BF)
+        msg = rejects(got, want, "dropped key")
+        assert "128 of" in msg and "(batch 0, row 123, col 128)" in msg
+
+
+def test_fault_last_valid_key_of_the_ragged_tile_replaced_by_a_padding_row(att):
+    for pad in (0.0, 7.0):
+        for name in ("u", "s"):
+            q, k, v, want = att[name][:4]
+            k2, v2 = k.clone(), v.clone()
+            k2[0, 299], v2[0, 299] = pad, pad                                            # key 299 = row 43 of key tile 4 reads beyond the operand
+            rejects(X.attention_reference(q, k2, v2), want, "padding row")
+
+
+def test_fault_two_keys_swapped(att):
+    q, k, v, want = att["s"][:4]
+    k2 = k.clone()
+    k2[0, 10], k2[0, 270] = k[0, 270], k[0, 10]
+    msg = rejects(X.attention_reference(q, k2, v), want, "swapped keys")
+    assert "768 of" in msg                                                               # two query rows per head, every column
+
+
+def test_fault_two_heads_swapped(att):
+    for name in ("u", "s"):
+        want = att[name][3]
+        got = want.clone()
+        got[..., :128], got[..., 128:256] = want[..., 128:256], want[..., :128]
+        rejects(got, want, "swapped heads")
+
+
+def test_fault_value_column_misplaced(att):
+    want = att["u"][3]
+    got = want.clone()
+    got[..., 5], got[..., 6] = want[..., 6], want[..., 5]
+    q, k, v, w2 = att["s"][:4]
+    v2 = v.clone()
+    v2[..., 5], v2[..., 6] = v[..., 6], v[..., 5]
+    rejects(X.attention_reference(q, k, v2), w2, "swapped value columns")
+    assert (att["u"][3][0, 0, 5] != att["u"][3][0, 0, 6]) == bool(X.mismatches(got, want).any())
+
+
+# ------------------------------------------------------------------------------------------------ attention64
+@pytest.mark.parametrize("N", X.ATTN64_NS)
+@pytest.mark.parametrize("H", X.ATTN64_HS)
+def test_attention64_constructions(N, H):
+    B, seed = 2, X.shape_seed(2, H, N, 64)
+    q, k, v, want = X.uniform_attention(B, H, N, seed, None, 64)
+    X.assert_elementwise(X.attention64_reference(q, k, v, 0.125), want, "uniform")
+    for causal in (False, True):
+        q, k, v, want, _ = X.selector_attention(B, H, N, seed, None, 64, X.ATTN64_MULT, 0.125, causal)
+        X.assert_elementwise(X.attention64_reference(q, k, v, 0.125, causal=causal), want, f"selector causal={causal}")
+    for delta in sorted({-(N - 1), -1, 0, 1, N - 1}):
+        if abs(delta) > N - 1:
+            continue
+        q, k, v, bias, want = X.bias_selector_attention(B, H, N, delta, seed)
+        X.assert_elementwise(X.attention64_reference(q, k, v, 0.125, rel_bias=bias), want, f"bias selector delta={delta}")
+        if N > 2 and abs(delta) < N - 1:
+            off = torch.roll(bias, 1, 1)                                                 # the index formula off by one
+            rejects(X.attention64_reference(q, k, v, 0.125, rel_bias=off), want, "bias index")
+
+
+# ------------------------------------------------------------------------------------------------ convolution
+@pytest.mark.parametrize("B,H,W,Cin,Cout,stride,up,pad_lo,with_res", X.CONV_CASES)
+def test_conv_generator_condition_and_border_fault(B, H, W, Cin, Cout, stride, up, pad_lo, with_res):
+    cs = X.conv_operands(B, H, W, Cin, Cout, X.shape_seed(B, H, W, Cin, Cout), stride=stride, up=up, with_res=with_res)
+    assert cs["want"].shape[0] == B and cs["want"].shape[3] == Cout and cs["x"].shape == (B, H, W, Cin)
+    acc = cs["acc"].clone()                                                              # a border pixel takes a tap from outside the image
+    acc[0, 0, 0] += cs["w"][:, 0, 0, :].double() @ cs["x"][0, 0, 0].double()
+    lin = X.linear_bf16(acc, cs["bias"].float())
+    rejects((cs["res"] + lin) if with_res else lin, cs["want"], "border tap")
+
+
+@pytest.mark.parametrize("B,H,W,Cin,Cout", [c[:5] for c in X.CONV_NARROW_CASES + X.CONV_PAIR_CASES])
+def test_conv_generator_condition_holds_for_the_narrow_and_pair_cases(B, H, W, Cin, Cout):
+    X.conv_operands(B, H, W, Cin, Cout, X.shape_seed(B, H, W, Cin, Cout), with_res=True)
