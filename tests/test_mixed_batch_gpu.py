@@ -392,6 +392,29 @@ def test_call_mixed_matches_each_samples_own_oracle_run_and_reuses_session_and_g
         assert torch.equal(again[k], eager[i]), (k, i)
 
 
+def test_call_mixed_equals_the_python_issued_loop():
+    """Two samples on the two smallest grids, two steps: call_mixed -- eagerly and as a replayed step graph, both through
+    tfx_dit_step_run -- against the same launches issued from Python on a mixed session (helpers/plain_loop.py), bit for bit."""
+    from tests.helpers.plain_loop import mixed_fused_loop
+    c, n, grids = tc.TR_CFG, 2, GRIDS[:2]
+    pipe = make_pipe({k: v.to(BF) for k, v in fo.seeded_state_dict(c, 7).items()})
+    g = torch.Generator().manual_seed(6)
+    S_b = [h2 * w2 for h2, w2 in grids]
+    lat = [torch.randn(1, s, 64, generator=g).to(BF).cuda() for s in S_b]
+    mil = [torch.cat([torch.randn(1, s, 64, generator=g), (torch.randn(1, s, 256, generator=g) > 0).float()], -1).to(BF).cuda() for s in S_b]
+    pe = (torch.randn(2, T_TXT, c.joint_attention_dim, generator=g) * 0.1).to(BF).cuda()
+    pooled = torch.randn(2, c.pooled_projection_dim, generator=g).to(BF).cuda()
+    kw = dict(sizes=SIZES[:2], latents=lat, masked_image_latents=mil, prompt_embeds=pe, pooled_prompt_embeds=pooled,
+              num_inference_steps=n, guidance_scale=30.0, output_type="latent")
+    eager = pipe.call_mixed(**kw).images
+    ref = mixed_fused_loop(pipe, lat, mil, pe, pooled, grids, n)
+    graphed = pipe.enable_hip_graph(True).call_mixed(**kw).images
+    assert all(pipe.transformer._session.graphs.values()) and len(pipe.transformer._session.graphs) == 1
+    for b in range(2):
+        assert ref[b].shape == (S_b[b], 64) and torch.isfinite(ref[b].float()).all()
+        assert torch.equal(eager[b], ref[b]) and torch.equal(graphed[b], ref[b]), b
+
+
 def test_call_mixed_refuses_amo_and_callbacks():
     from textflux_amd.schedulers import StochasticRFOvershotDiscreteScheduler
     sd = {k: v.to(BF) for k, v in fo.seeded_state_dict(tc.TR_CFG, 7).items()}

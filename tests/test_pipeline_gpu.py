@@ -25,6 +25,13 @@ def mae(a, b):
     return (a.float().cpu() - b.float().cpu()).abs().mean().item()
 
 
+def python_issued_loop(pipe, g, **kw):
+    """tests/helpers/plain_loop.py on the g5 inputs (8 x 8 latent grid): the loop as Python-issued launches, the side that stays
+    independent of tfx_dit_step_run.  Call after a pipeline call: the scheduler holds its schedule."""
+    from tests.helpers.plain_loop import plain_loop
+    return plain_loop(pipe, g["latents"], g["masked_image_latents"], g["prompt_embeds"], g["pooled"], (8, 8), **kw)
+
+
 def make_pipe(sname, vae_seed=900):
     from textflux_amd.pipeline import FluxFillPipeline
     from textflux_amd.schedulers import FlowMatchEulerDiscreteScheduler, StochasticRFOvershotDiscreteScheduler
@@ -181,7 +188,8 @@ def test_lora_merge_matches_oracle_with_premerged_weights(tmp_path):
 
 @pytest.mark.parametrize("sname", ["euler", "amo"])
 def test_hip_graph_replay_is_bit_identical_to_eager_loop(golden, sname):
-    """One captured step graph (device-side step cursor) replayed for steps 1..n-1 == the eager launch sequence."""
+    """One captured step graph (device-side step cursor) replayed for steps 1..n-1 == the eager step == the launch sequence issued
+    from Python (Euler: fused into proj_out, the default; AMO: supplied noise)."""
     g = golden("g5_pipeline")
     eps = [g[f"amo.eps{i}"] for i in range(4)] if sname == "amo" else None
     kw = dict(prompt_embeds=g["prompt_embeds"].to(BF).cuda(), pooled_prompt_embeds=g["pooled"].to(BF).cuda(),
@@ -193,6 +201,7 @@ def test_hip_graph_replay_is_bit_identical_to_eager_loop(golden, sname):
     graphed = pipe(**kw).images          # captures
     again = pipe(**kw).images            # re-uses the cached graph
     assert torch.equal(eager, graphed) and torch.equal(eager, again)
+    assert torch.equal(eager, python_issued_loop(pipe, g, fused=sname == "euler", amo_noise=eps))
     assert mae(graphed, g[f"{sname}.bf16.final"]) < 1e-3
 
 
@@ -201,7 +210,7 @@ def test_euler_update_in_proj_out_epilogue_is_bit_identical_to_the_scheduler_ker
     applies x' = x + bf16(dsigma * bf16(v)) in place on the latent columns of the x_embedder input (tfx_dit_desc.euler_gate;
     no scheduler launch, no copy of the new latents into the next step's input).  Same rounding points as
     FlowMatchEulerDiscreteScheduler.step (scheduling_flow_match_euler_discrete.py:319-330) applied to the stored model output:
-    every step of the trajectory is bit-identical, eagerly and as a replayed step graph."""
+    every step of the trajectory is bit-identical, eagerly, as a replayed step graph and issued launch by launch from Python."""
     g = golden("g5_pipeline")
     kw = dict(prompt_embeds=g["prompt_embeds"].to(BF).cuda(), pooled_prompt_embeds=g["pooled"].to(BF).cuda(),
               latents=g["latents"].to(BF).cuda(), masked_image_latents=g["masked_image_latents"].to(BF).cuda(),
@@ -213,6 +222,7 @@ def test_euler_update_in_proj_out_epilogue_is_bit_identical_to_the_scheduler_ker
             pipe.fuse_euler_step = fuse
             pipe.enable_hip_graph(False)
             outs[(n, fuse, "eager")] = pipe(num_inference_steps=n, **kw).images
+            outs[(n, fuse, "python")] = python_issued_loop(pipe, g, fused=fuse)     # the same launches issued from Python (n = 1 never captures)
             pipe.enable_hip_graph(True)
             outs[(n, fuse, "graph")] = pipe(num_inference_steps=n, **kw).images
         ref = outs[(n, False, "eager")]
@@ -221,6 +231,22 @@ def test_euler_update_in_proj_out_epilogue_is_bit_identical_to_the_scheduler_ker
                 assert torch.equal(v, ref), k
     assert mae(outs[(4, True, "graph")], g["euler.bf16.final"]) < 1e-3
     assert pipe.transformer._session.desc.euler_gate is not None        # the last call really ran fused
+
+
+def test_step_callback_sees_the_python_issued_loops_latents_every_step(golden):
+    """A step callback keeps the loop eager and unfused (graphs on or off) and is handed the live latents: every step's clone equals
+    the Python-issued loop's latents after that step, bit for bit."""
+    g = golden("g5_pipeline")
+    pipe = make_pipe("euler").enable_hip_graph(True)
+    steps = []
+    out = pipe(prompt_embeds=g["prompt_embeds"].to(BF).cuda(), pooled_prompt_embeds=g["pooled"].to(BF).cuda(),
+               latents=g["latents"].to(BF).cuda(), masked_image_latents=g["masked_image_latents"].to(BF).cuda(),
+               height=128, width=128, num_inference_steps=4, guidance_scale=30.0, output_type="latent",
+               callback_on_step_end=lambda p, i, t, kw: steps.append(kw["latents"].clone()) or {}).images
+    mine = []
+    python_issued_loop(pipe, g, per_step=mine)
+    assert len(steps) == len(mine) == 4 and all(torch.equal(a, b) for a, b in zip(steps, mine)) and torch.equal(out, mine[-1])
+    assert not pipe.transformer._session.graphs                       # nothing was captured
 
 
 def test_hip_graph_amo_internal_noise_runs():
@@ -252,6 +278,8 @@ def test_fp8_call_matches_fp8_oracle_trajectory_and_graph_replay(golden):
         return {}
 
     out = pipe(callback_on_step_end=cb, callback_on_step_end_tensor_inputs=["latents"], **kw).images
+    mine = []
+    assert torch.equal(python_issued_loop(pipe, g, per_step=mine), out) and all(torch.equal(a, b) for a, b in zip(steps, mine))
     sd = {k: v.to(BF) for k, v in fo.seeded_state_dict(G3_CFG, 7).items()}
     with fo.fp8_block_linears():
         _, traj = po.denoise(sd, G3_CFG, g["latents"].to(BF), g["masked_image_latents"].to(BF), g["prompt_embeds"].to(BF),

@@ -211,38 +211,28 @@ def test_all_computed_equals_the_plain_loop(variant):
 
 def reference_with_schedule(pipe, grid, skip):
     """The loop with `skip` assembled from block-range forwards (DitSession.run: first_block / last_block / flags) and torch bf16
-    arithmetic for the residual and its re-use; Euler update by the separate scheduler kernel.  Call after a pipeline call at this
-    geometry: the scheduler then holds the call's timesteps and coefficients."""
-    from textflux_amd import ops
-    inp, tr, sch = inputs(grid), pipe.transformer, pipe.scheduler
-    S = inp["latents"].shape[1]
+    arithmetic for the residual and its re-use, inside helpers/plain_loop.py's loop: Euler update by the separate scheduler kernel.
+    Call after a pipeline call at this geometry: the scheduler then holds the call's timesteps and coefficients."""
+    from tests.helpers.plain_loop import plain_loop
+    inp = inputs(grid)
     nblk = tc.TR_CFG.num_layers + tc.TR_CFG.num_single_layers
-    ses = tr.session(B, S, T_TXT)
-    ids = pipe._prepare_latent_image_ids(B, *GRIDS[grid], "cuda", BF)
-    ses.set_conditioning(inp["prompt_embeds"], torch.zeros(T_TXT, 3), ids)
-    ts = sch.timesteps
-    assert len(ts) == N_STEPS
-    t_rows = torch.tensor([pipe._timestep_chain(t, BF) for t in ts], dtype=torch.float32).repeat_interleave(B).cuda()
-    g_rows = torch.full((N_STEPS * B,), float((torch.full([1], 30.0).to(BF) * 1000).float()), dtype=torch.float32, device="cuda")
-    mod = tr.modulation(tr.temb(t_rows, g_rows, inp["pooled_prompt_embeds"].repeat(N_STEPS, 1))).view(N_STEPS, B, tr.mod_len)
-    lat = inp["latents"].clone()
-    ops.scatter_cols_(lat, ses.xin, 0)
-    ops.scatter_cols_(inp["masked_image_latents"].contiguous(), ses.xin, 64)
-    coef = sch.coef_table("cuda", BF)
-    img = ses.hid[:, T_TXT:]
-    r = None
-    for i in range(N_STEPS):
-        ses.run(mod[i], 0, 0, flags=2)                        # embedders
-        ses.run(mod[i], 0, 1, flags=3)                        # block 0
+    assert len(pipe.scheduler.timesteps) == N_STEPS
+    state = {}
+
+    def forward(ses, mod_i, i):
+        img = ses.hid[:, T_TXT:]
+        ses.run(mod_i, 0, 0, flags=2)                         # embedders
+        ses.run(mod_i, 0, 1, flags=3)                         # block 0
         if i in skip:
-            img.copy_((img.float() + r.float()).to(BF))
-            v = ses.run(mod[i], nblk, nblk, flags=1)          # norm_out + proj_out
-        else:
-            h1 = img.clone()
-            v = ses.run(mod[i], 1, -1, flags=1)               # blocks 1 ... n, norm_out + proj_out
-            r = (img.float() - h1.float()).to(BF)
-        ops.euler_step_(v, lat, coef, step=i, xin=ses.xin)
-    return lat
+            img.copy_((img.float() + state["r"].float()).to(BF))
+            return ses.run(mod_i, nblk, nblk, flags=1)        # norm_out + proj_out
+        h1 = img.clone()
+        v = ses.run(mod_i, 1, -1, flags=1)                    # blocks 1 ... n, norm_out + proj_out
+        state["r"] = (img.float() - h1.float()).to(BF)
+        return v
+
+    return plain_loop(pipe, inp["latents"], inp["masked_image_latents"], inp["prompt_embeds"], inp["pooled_prompt_embeds"], GRIDS[grid],
+                      forward=forward)
 
 
 def test_explicit_schedule_equals_the_block_range_reference_and_resets_between_calls():

@@ -3,8 +3,9 @@ reference class (diffusers/src/diffusers/pipelines/flux/pipeline_flux_fill.py:13
 `run_inference.py`-style callers can switch by changing one import.
 
 What is different underneath:
-* the denoising loop never re-enters Python-level model code: per step it is ONE `tfx_dit_forward` + ONE fused
-  scheduler kernel that also writes the new latents into the next x_embedder input (no torch.cat per step, P:2085);
+* the denoising loop (step_loop.py) never re-enters Python-level model code: per step it is ONE `tfx_dit_step_run`, or the
+  replay of the graph captured from it -- the forward and a scheduler update that also writes the new latents into the next
+  x_embedder input (no torch.cat per step, P:2085);
 * context projection, RoPE tables and the time/guidance/pooled embedding -> AdaLN modulation of ALL steps are computed
   once before the loop (the reference recomputes them every step);
 * the AMO sampler's per-step host syncs are gone (coefficients tabulated on the host).
@@ -21,10 +22,10 @@ from typing import Any, Callable, Dict, List, Optional, Tuple, Union
 import numpy as np
 import torch
 
-from . import ops
+from . import ops, step_loop
 from .image_processor import VaeImageProcessor
 from .schedulers import FlowMatchEulerDiscreteScheduler, StochasticRFOvershotDiscreteScheduler
-from .transformer import FluxTransformer2DModel
+from .transformer import EULER_PAD, FluxTransformer2DModel
 
 BF16 = torch.bfloat16
 
@@ -497,150 +498,72 @@ class FluxFillPipeline:
         ts = t.detach().reshape(1).to("cpu", torch.float32).to(dtype)
         return float(((ts / 1000).to(dtype) * 1000).float())
 
-    def _engine_loop(self, latents, masked_image_latents, prompt_embeds, pooled, text_ids, latent_image_ids, timesteps,
-                     guidance_scale, callback_on_step_end, callback_tensor_inputs, amo_noise, progress_bar):
-        tr, sch = self.transformer, self.scheduler
+    def _modulation_table(self, timesteps, B, pooled, guidance_scale, dsigma=None):
+        """AdaLN modulation rows of ALL steps, [n, B, mod_len], rows ordered (step, sample).  timesteps: [n] (every sample on one
+        schedule) or [n, B] scheduler timesteps.  dsigma ([n] or [n, B], bf16-exact already: coef_table) -> [n, B, mod_len +
+        EULER_PAD]: the step's Euler coefficient travels behind its modulation rows and gates proj_out's epilogue
+        (tfx_dit_desc.euler_gate)."""
+        tr = self.transformer
         dev = tr.device
-        B, S, C = latents.shape
-        T = prompt_embeds.shape[1]
-        n = len(timesteps)
-        ses = tr.session(B, S, T)
-        ses.set_conditioning(prompt_embeds.to(dev, BF16), text_ids, latent_image_ids)
-        # conditioning of all steps at once: rows ordered (step, batch)
-        t_vals = [self._timestep_chain(t, BF16) for t in timesteps]
-        t_rows = torch.tensor(t_vals, dtype=torch.float32).repeat_interleave(B).to(dev)
+        t = timesteps.detach().to("cpu", torch.float32)
+        n = t.shape[0]
+        t_rows = torch.tensor([self._timestep_chain(x, BF16) for x in t.reshape(-1)], dtype=torch.float32).view(n, -1).expand(n, B)
         g_rows = None
         if tr.config.guidance_embeds:
             g = float((torch.full([1], guidance_scale, dtype=torch.float32).to(BF16) * 1000).float())  # P:2070, :1090
             g_rows = torch.full((n * B,), g, dtype=torch.float32, device=dev)
-        pooled_rows = pooled.to(dev, BF16).repeat(n, 1)
-        mod = tr.modulation(tr.temb(t_rows, g_rows, pooled_rows)).view(n, B, tr.mod_len)
-        # x_embedder input [latents | masked_image_latents]; the scheduler kernel keeps columns 0..C-1 up to date
-        latents = latents.to(dev, BF16).contiguous().clone()
-        ops.scatter_cols_(latents, ses.xin, 0)
-        ops.scatter_cols_(masked_image_latents.to(dev, BF16).contiguous(), ses.xin, C)
+        mod = tr.modulation(tr.temb(t_rows.reshape(-1).to(dev), g_rows, pooled.to(dev, BF16).repeat(n, 1))).view(n, B, tr.mod_len)
+        if dsigma is None:
+            return mod
+        modx = torch.empty(n, B, tr.mod_len + EULER_PAD, dtype=BF16, device=dev)
+        modx[:, :, :tr.mod_len] = mod
+        modx[:, :, tr.mod_len:] = dsigma.to(dev, BF16).reshape(n, -1, 1)
+        return modx
+
+    def _engine_loop(self, latents, masked_image_latents, prompt_embeds, pooled, text_ids, latent_image_ids, timesteps,
+                     guidance_scale, callback_on_step_end, callback_tensor_inputs, amo_noise, progress_bar):
+        """Session, conditioning, modulation table, x_embedder input, then the step loop (step_loop.denoise).  The loop starts at
+        step 0: _call_body sets the timesteps directly in front of it, which clears the scheduler's begin_index."""
+        tr, sch = self.transformer, self.scheduler
+        dev = tr.device
+        B, S, C = latents.shape
+        n = len(timesteps)
+        ses = tr.session(B, S, prompt_embeds.shape[1])
+        ses.set_conditioning(prompt_embeds.to(dev, BF16), text_ids, latent_image_ids)
         is_amo = isinstance(sch, StochasticRFOvershotDiscreteScheduler)
         coef = sch.coef_table(dev, BF16)
-        sch._step_index = 0 if sch.begin_index is None else sch.begin_index
-        # Euler update in proj_out's epilogue (north_star: "flow-matching Euler step fused into the residual add"): the step's
-        # bf16 dsigma travels as EULER_PAD extra columns of its modulation rows and gates the final projection; the latents
+        # Euler update in proj_out's epilogue (north_star: "flow-matching Euler step fused into the residual add"); the latents then
         # live in xin[:, :, :C].  Not with a step callback (it wants the latents as a tensor every step) and not for AMO.
-        from .transformer import EULER_PAD
-        fuse = (self.fuse_euler_step and not is_amo and callback_on_step_end is None and sch._step_index == 0 and C == EULER_PAD
-                and tr.out_channels == C)
-        if fuse:
-            modx = torch.empty(n, B, tr.mod_len + EULER_PAD, dtype=BF16, device=dev)
-            modx[:, :, :tr.mod_len] = mod
-            modx[:, :, tr.mod_len:] = coef[:n].to(BF16).view(n, 1, 1)      # coef is already bf16-exact (coef_table)
-            mod = modx
-        self.step_cache_report = None
-        if self._step_cache is not None:
-            if sch._step_index != 0:
-                warnings.warn("the step cache needs a loop that starts at step 0 (scheduler.begin_index is set): running every step in full")
-            else:
-                return self._cached_loop(ses, mod, latents, coef, is_amo, amo_noise, timesteps, progress_bar, fuse,
-                                         self._use_hip_graph and callback_on_step_end is None and n > 1, callback_on_step_end,
-                                         callback_tensor_inputs, prompt_embeds, text_ids, latent_image_ids)
-        if self._use_hip_graph and callback_on_step_end is None and n > 1 and sch._step_index == 0:
-            return self._graph_loop(ses, mod, latents, coef, is_amo, amo_noise, n, progress_bar, fuse)
-        if fuse:
-            for i, t in enumerate(timesteps):
-                if self._interrupt:
-                    continue
-                ses.run(mod[i], euler=True)
-                sch._step_index += 1
-                progress_bar.update()
-            return ops.copy_rows_(ses.xin[:, :, :C], torch.empty_like(latents))
-        for i, t in enumerate(timesteps):
-            if self._interrupt:
-                continue
-            v = ses.run(mod[i])
-            if is_amo:
-                eps = amo_noise[i] if amo_noise is not None else torch.randn(latents.shape, device=dev, dtype=torch.float32)
-                ops.amo_step_(v, latents, coef, eps.to(dev, torch.float32).contiguous(), step=sch._step_index, xin=ses.xin)
-            else:
-                ops.euler_step_(v, latents, coef, step=sch._step_index, xin=ses.xin)
-            sch._step_index += 1
-            if callback_on_step_end is not None:
-                kw = {k: {"latents": latents, "prompt_embeds": prompt_embeds}[k] for k in callback_tensor_inputs}
-                out = callback_on_step_end(self, i, t, kw) or {}
-                new_lat = out.pop("latents", latents)
-                if new_lat is not latents:
-                    latents = new_lat.to(dev, BF16).contiguous().clone()
-                    ops.scatter_cols_(latents, ses.xin, 0)
+        fuse = self.fuse_euler_step and not is_amo and callback_on_step_end is None and C == EULER_PAD and tr.out_channels == C
+        mod = self._modulation_table(timesteps, B, pooled, guidance_scale, coef[:n] if fuse else None)
+        # x_embedder input [latents | masked_image_latents]; the step keeps columns 0..C-1 up to date
+        latents = latents.to(dev, BF16).contiguous()
+        ops.scatter_cols_(latents, ses.xin, 0)
+        ops.scatter_cols_(masked_image_latents.to(dev, BF16).contiguous(), ses.xin, C)
+        on_step = None
+        if callback_on_step_end is not None:
+            def on_step(i, lat):     # lat: the live latents; what the callback returns goes back into the loop's state
+                nonlocal prompt_embeds
+                kw = {k: {"latents": lat, "prompt_embeds": prompt_embeds}[k] for k in callback_tensor_inputs}
+                out = callback_on_step_end(self, i, timesteps[i], kw) or {}
+                new_lat = out.pop("latents", lat)
+                if new_lat is not lat:
+                    lat.copy_(new_lat.to(dev, BF16))
+                    ops.scatter_cols_(lat, ses.xin, 0)
                 new_pe = out.pop("prompt_embeds", prompt_embeds)
                 if new_pe is not prompt_embeds:
                     prompt_embeds = new_pe
                     ses.set_conditioning(prompt_embeds.to(dev, BF16), text_ids, latent_image_ids)
-            progress_bar.update()
-        return latents
+        sch._step_index = 0
+        return step_loop.denoise(self, ses, mod, latents, coef, n, progress_bar, is_amo, fuse, amo_noise, on_step)
 
     def enable_hip_graph(self, on: bool = True):
         """Replay ONE captured hipGraph per denoising step (device-side step cursor: modulation rows and scheduler
         coefficients are selected by an int32 on the device, so the same graph serves every step).  Used when no
-        `callback_on_step_end` is given; results are bit-identical to the eager loop."""
+        `callback_on_step_end` is given and there is more than one step; the graph is captured from the step the eager form
+        runs (step_loop.run_steps), so the results are bit-identical."""
         self._use_hip_graph = bool(on)
         return self
-
-    def _graph_loop(self, ses, mod, latents, coef, is_amo, amo_noise, n, progress_bar, fuse=False):
-        """The loop as ONE captured step graph replayed n - 1 times (C ABI: tfx_dit_step_run / _capture / _replay; the
-        hipGraph API is driven by the library, not by torch).  Capture needs a non-NULL stream: the loop runs on the
-        session's side stream, fenced against the caller's current stream on both sides."""
-        import ctypes as C
-        from . import _lib as L
-        dev = latents.device
-        gb = ses.graph_buffers(n, coef.numel(), latents.shape)
-        gb["mod_table"][:n, :, :mod.shape[2]].copy_(mod)
-        gb["coef"][:coef.numel()].copy_(coef.reshape(-1))
-        gb["lat"].copy_(latents)
-        gb["step"].zero_()
-        internal_noise = is_amo and amo_noise is None
-        sd = ses.step_desc(gb, is_amo, fuse)
-        ses._mod_keepalive = gb["mod_cur"]
-        lib = L.lib()
-        cur = torch.cuda.current_stream(dev)
-        side = ses.graph_stream()
-        side.wait_stream(cur)
-        with torch.cuda.stream(side):
-            st = side.cuda_stream
-
-            def feed_noise(i):
-                if internal_noise:
-                    gb["noise"].normal_()      # global device RNG, as the reference's randn_tensor(generator=None); not captured
-                elif is_amo:
-                    gb["noise"].copy_(amo_noise[i].to(dev, torch.float32))
-
-            feed_noise(0)
-            L.check(lib.tfx_dit_step_run(C.byref(sd), st), "dit_step_run")     # eager step 0: also warms every kernel
-            progress_bar.update()
-            key = (is_amo, fuse)
-            g = ses.graphs.get(key)
-            if g is None:
-                side.synchronize()
-                saved = [gb[k].clone() for k in ("lat", "step")] + [ses.xin.clone()]     # (xin also holds the latents when fused)
-                h = C.c_void_p()
-                rc = lib.tfx_dit_step_capture(C.byref(sd), st, C.byref(h))
-                if rc != 0:     # capture refused (driver / runtime state): same kernels, launched eagerly
-                    warnings.warn(f"hipGraph capture of the denoising step failed ({lib.tfx_last_error().decode()}); "
-                                  "running the step loop eagerly")
-                    g = False
-                else:
-                    g = h.value
-                # capture does not execute; keep the state explicit anyway
-                gb["lat"].copy_(saved[0]); gb["step"].copy_(saved[1]); ses.xin.copy_(saved[2])
-                ses.graphs[key] = g
-            for i in range(1, n):
-                feed_noise(i)
-                if g is False:
-                    L.check(lib.tfx_dit_step_run(C.byref(sd), st), "dit_step_run")
-                else:
-                    L.check(lib.tfx_dit_step_replay(g, st), "dit_step_replay")
-                progress_bar.update()
-            out = ops.copy_rows_(ses.xin[:, :, :latents.shape[2]], torch.empty_like(latents)) if fuse else gb["lat"].clone()
-        out.record_stream(cur)
-        cur.wait_stream(side)
-        self.scheduler._step_index = n
-        return out
 
     # ------------------------------------------------------------------ first-block step cache (DESIGN.md section 4 "Step cache")
     def enable_step_cache(self, threshold, skip_steps=None, max_consecutive=None):
@@ -662,96 +585,6 @@ class FluxFillPipeline:
     def disable_step_cache(self):
         self._step_cache = None
         return self
-
-    def _cached_loop(self, ses, mod, latents, coef, is_amo, amo_noise, timesteps, progress_bar, fuse, use_graph, callback_on_step_end,
-                     callback_tensor_inputs, prompt_embeds, text_ids, latent_image_ids):
-        """The step loop under the step cache, eager or as captured graphs: per step the head phase (tfx_step_desc.phase 1), one
-        read of the B metrics through pinned memory, the host decision (step_cache.decide), then the computed (2) or the cached (3)
-        tail.  Both forms issue the same C-level phases -- tfx_dit_step_run, or the replay of the graph captured from it -- so they
-        agree bit for bit; phases 1 + 2 are the launches of a whole step, so a run that never skips equals the plain loop."""
-        import ctypes as C
-        from . import _lib as L
-        from .step_cache import Decider
-        dev = latents.device
-        n = len(timesteps)
-        gb = ses.graph_buffers(n, coef.numel(), latents.shape)
-        gb["mod_table"][:n, :, :mod.shape[2]].copy_(mod)
-        gb["coef"][:coef.numel()].copy_(coef.reshape(-1))
-        gb["lat"].copy_(latents)
-        gb["step"].zero_()
-        cache = ses.step_cache()
-        ses.step_cache_reset()
-        internal_noise = is_amo and amo_noise is None
-        sds = {ph: ses.step_desc(gb, is_amo, fuse, phase=ph) for ph in (1, 2, 3)}
-        ses._mod_keepalive = gb["mod_cur"]
-        lib = L.lib()
-        decider = Decider(self._step_cache)
-        sch = self.scheduler
-        cur = torch.cuda.current_stream(dev)
-        side = ses.graph_stream()
-        side.wait_stream(cur)
-        with torch.cuda.stream(side):
-            st = side.cuda_stream
-            graphs = None           # {phase: handle} once captured; False: capture refused, eager phases
-
-            def run(ph):
-                if graphs:
-                    L.check(lib.tfx_dit_step_replay(graphs[ph], st), "dit_step_replay")
-                else:
-                    L.check(lib.tfx_dit_step_run(C.byref(sds[ph]), st), "dit_step_run")
-
-            for i, t in enumerate(timesteps):
-                if self._interrupt:
-                    continue
-                if internal_noise:
-                    gb["noise"].normal_()      # global device RNG, as the reference's randn_tensor(generator=None); not captured
-                elif is_amo:
-                    gb["noise"].copy_(amo_noise[i].to(dev, torch.float32))
-                run(1)
-                cache["metric_host"].copy_(cache["metric"], non_blocking=True)
-                side.synchronize()
-                run(3 if decider.step(i, cache["metric_host"].tolist()) else 2)
-                sch._step_index += 1
-                if use_graph and graphs is None:       # every kernel of the three phases has run eagerly by now (apply: at set-up)
-                    keys = {ph: (is_amo, fuse, "step_cache", ph) for ph in (1, 2, 3)}
-                    have = {ph: ses.graphs.get(k) for ph, k in keys.items()}
-                    if all(g is None for g in have.values()):
-                        side.synchronize()
-                        saved = [gb[k].clone() for k in ("lat", "step")] + [ses.xin.clone()]
-                        for ph in (1, 2, 3):
-                            h = C.c_void_p()
-                            if lib.tfx_dit_step_capture(C.byref(sds[ph]), st, C.byref(h)) != 0:
-                                warnings.warn(f"hipGraph capture of the denoising step failed ({lib.tfx_last_error().decode()}); "
-                                              "running the step loop eagerly")
-                                for g in have.values():
-                                    if g:
-                                        lib.tfx_graph_destroy(g)
-                                have = {p: False for p in have}
-                                break
-                            have[ph] = h.value
-                        # capture does not execute; keep the state explicit anyway
-                        gb["lat"].copy_(saved[0]); gb["step"].copy_(saved[1]); ses.xin.copy_(saved[2])
-                        for ph, k in keys.items():
-                            ses.graphs[k] = have[ph]
-                    graphs = have if all(have.values()) else False
-                if callback_on_step_end is not None:
-                    lat = gb["lat"]
-                    kw = {k: {"latents": lat, "prompt_embeds": prompt_embeds}[k] for k in callback_tensor_inputs}
-                    out = callback_on_step_end(self, i, t, kw) or {}
-                    new_lat = out.pop("latents", lat)
-                    if new_lat is not lat:
-                        lat.copy_(new_lat.to(dev, BF16))
-                        ops.scatter_cols_(lat, ses.xin, 0)
-                    new_pe = out.pop("prompt_embeds", prompt_embeds)
-                    if new_pe is not prompt_embeds:
-                        prompt_embeds = new_pe
-                        ses.set_conditioning(prompt_embeds.to(dev, BF16), text_ids, latent_image_ids)
-                progress_bar.update()
-            out = ops.copy_rows_(ses.xin[:, :, :latents.shape[2]], torch.empty_like(latents)) if fuse else gb["lat"].clone()
-        out.record_stream(cur)
-        cur.wait_stream(side)
-        self.step_cache_report = decider.report
-        return out
 
     def _generic_loop(self, latents, masked_image_latents, prompt_embeds, pooled, text_ids, latent_image_ids, timesteps,
                       guidance, callback_on_step_end, callback_tensor_inputs, progress_bar):
@@ -870,7 +703,6 @@ class FluxFillPipeline:
         if callback_on_step_end is not None:
             raise NotImplementedError("call_mixed: a step callback wants the latents as one tensor every step, which the fused Euler "
                                       "step of a mixed-geometry batch does not keep; use __call__")
-        from .transformer import EULER_PAD
         if sizes is None or len(sizes) == 0:
             raise ValueError("call_mixed: `sizes` = [(width, height), ...], one per sample")
         B = len(sizes)
@@ -939,29 +771,13 @@ class FluxFillPipeline:
         n = num_inference_steps if sigmas is None else len(sigmas)
         tabs = per_sample_schedules(sch, S_b, n, sigmas)
         self._num_timesteps = n
-        t_vals = torch.tensor([[self._timestep_chain(tabs["timesteps"][b, i], BF16) for b in range(B)] for i in range(n)], dtype=torch.float32)
-        g_rows = None
-        if tr.config.guidance_embeds:
-            g = float((torch.full([1], guidance_scale, dtype=torch.float32).to(BF16) * 1000).float())
-            g_rows = torch.full((n * B,), g, dtype=torch.float32, device=dev)
-        mod = torch.empty(n, B, tr.mod_len + EULER_PAD, dtype=BF16, device=dev)      # rows ordered (step, sample)
-        mod[:, :, :tr.mod_len] = tr.modulation(tr.temb(t_vals.reshape(-1).to(dev), g_rows, pooled_prompt_embeds.to(dev, BF16).repeat(n, 1))).view(n, B, tr.mod_len)
-        mod[:, :, tr.mod_len:] = tabs["dsigma"].t().contiguous().to(dev, BF16).view(n, B, 1)           # bf16-exact already (coef_table)
+        mod = self._modulation_table(tabs["timesteps"].t(), B, pooled_prompt_embeds, guidance_scale, tabs["dsigma"].t())
         for b in range(B):          # x_embedder input [latents | masked_image_latents] of the valid rows; padding rows stay unspecified
             ses.xin[b, :S_b[b], :C].copy_(lats[b][0].to(dev, BF16))
             ses.xin[b, :S_b[b], C:].copy_(conds[b].to(dev, BF16))
         sch._step_index = 0
         with self.progress_bar(total=n) as bar:
-            if self._use_hip_graph and n > 1:
-                out = self._graph_loop(ses, mod, torch.empty(B, S, C, dtype=BF16, device=dev), tabs["dsigma"][0].to(dev), False, None, n, bar, True)
-            else:
-                for i in range(n):
-                    if self._interrupt:
-                        continue
-                    ses.run(mod[i], euler=True)
-                    sch._step_index += 1
-                    bar.update()
-                out = ops.copy_rows_(ses.xin[:, :, :C], torch.empty(B, S, C, dtype=BF16, device=dev))
+            out = step_loop.denoise(self, ses, mod, None, None, n, bar, fuse=True)
         results: List[Any] = [None] * B
         for (w, h), members in groups.items():
             lat = torch.stack([out[b, :S_b[b]] for b in members])
