@@ -485,6 +485,23 @@ int tfx_rgb_to_grey_u8(const void* rgb, void* out, int64_t pixels, tfx_stream st
  * out = clip8((2^21 + sum in * k) >> 22): integer arithmetic, bit-identical to Pillow. */
 int tfx_resample_u8(const void* in, void* out, const int32_t* bounds, const int32_t* coeffs, int32_t ksize, int64_t outer,
                     int32_t in_len, int32_t out_len, int32_t inner, tfx_stream stream);
+/* ---- paste-back (DESIGN.md section 4 "Paste-back"): the edited pixels go back into the ORIGINAL image under a feathered mask.
+ *      Added without a new TFX_ABI_VERSION: three new entry points, no stamped struct and no existing entry point changes, so a
+ *      caller built against the previous header finds everything it knew unchanged.  All tensors contiguous, batch-major, u8;
+ *      B, H, W (, C) >= 1; radius in [0, 255]; integer arithmetic throughout, so the results are exact.  `tmp` is the caller's
+ *      scratch of the mask's size; in, out and tmp are three different buffers.
+ * tfx_mask_dilate_u8: square max filter of a mask [B, H, W]: out[y, x] = max in[y', x'] over |y' - y| <= radius, |x' - x| <= radius,
+ *      the window clipped at the image border (x pass into tmp, y pass into out).  radius 0 copies. */
+int tfx_mask_dilate_u8(const void* in, void* out, void* tmp, int32_t B, int32_t H, int32_t W, int32_t radius, tfx_stream stream);
+/* tfx_mask_feather_u8: three box passes along x, then three along y, each rounding to u8.  One pass along an axis of length L with
+ *      n = 2 radius + 1: s = sum over k in [-radius, radius] of v[clamp(i + k, 0, L - 1)] (edge replicated), out = (2 s + n) / (2 n) in
+ *      integer division.  radius 0 copies; an all-255 (all-0) mask stays all-255 (all-0); the support grows by at most 3 radius
+ *      per axis. */
+int tfx_mask_feather_u8(const void* in, void* out, void* tmp, int32_t B, int32_t H, int32_t W, int32_t radius, tfx_stream stream);
+/* tfx_overlay_u8: orig, edit, out [B, H, W, C], alpha [B, H, W]: out = (orig (255 - a) + edit a + 127) / 255 in integer division:
+ *      a = 0 gives orig, a = 255 gives edit, and min(orig, edit) <= out <= max(orig, edit).  out may be orig (no other aliasing). */
+int tfx_overlay_u8(const void* orig, const void* edit, const void* alpha, void* out, int32_t B, int32_t H, int32_t W, int32_t C,
+                   tfx_stream stream);
 /* out[b, t, col0 + (i*8+j)*4 + py*2+px] = mask[(2ty+py)*8 + i, (2tx+px)*8 + j]  (P:1563-1580: 8x8 pixel blocks -> channels,
  * then _pack_latents), t = ty * (W/16) + tx, row stride ld. */
 int tfx_pack_mask(const void* mask, int32_t mask_dtype, void* out, int32_t B, int32_t H, int32_t W, int32_t mask_batch,

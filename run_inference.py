@@ -46,9 +46,12 @@ def use_overshoot_sampler(pipe):
     pipe.scheduler = sch
 
 
-def run_inference(image_input, mask_input, words_input, num_steps=50, guidance_scale=30, seed=42, pipe=None):
+def run_inference(image_input, mask_input, words_input, num_steps=50, guidance_scale=30, seed=42, pipe=None, paste_back=None):
+    """paste_back (not in the reference): None, or dict(dilate, feather) -- the result is then blended back into the input image under
+    the dilated and feathered mask and returned at the INPUT's size (FluxFillPipeline.paste_back) instead of at the pipeline's size."""
     image = (Image.open(image_input) if isinstance(image_input, str) else image_input).convert("RGB")
     mask = (Image.open(mask_input) if isinstance(mask_input, str) else mask_input).convert("RGB")
+    image_in, mask_in = image, mask
     new_w, new_h = glyph.pipe_size(image)
     image, mask = image.resize((new_w, new_h)), mask.resize((new_w, new_h))
     words = glyph.read_words_from_text(words_input) if isinstance(words_input, str) else list(words_input)
@@ -58,9 +61,32 @@ def run_inference(image_input, mask_input, words_input, num_steps=50, guidance_s
     generator = torch.Generator(device="cuda").manual_seed(int(seed))
     if scheduler_name == "overshoot":
         use_overshoot_sampler(pipe)
-    return pipe(height=new_h, width=new_w, image=image, mask_image=mask, num_inference_steps=num_steps,
-                generator=generator, max_sequence_length=512, guidance_scale=guidance_scale,
-                prompt=glyph.PROMPT_TEMPLATE2, prompt_2=prompt).images[0]
+    out = pipe(height=new_h, width=new_w, image=image, mask_image=mask, num_inference_steps=num_steps,
+               generator=generator, max_sequence_length=512, guidance_scale=guidance_scale,
+               prompt=glyph.PROMPT_TEMPLATE2, prompt_2=prompt).images[0]
+    if paste_back is None:
+        return out
+    pasted = pipe.paste_back(image_in, out, mask_in, **{k: v for k, v in paste_back.items() if k in ("dilate", "feather") and v is not None})
+    return Image.fromarray(pasted[0].cpu().numpy())
+
+
+def add_paste_back_args(ap):
+    """Not in the reference: paste-back and region editing (textflux_amd/paste_back.py)."""
+    ap.add_argument("--paste_back", action="store_true", help="return the ORIGINAL scene at its original size, changed only under the "
+                    "dilated and feathered mask, instead of the pipeline's own pixels at pipeline size")
+    ap.add_argument("--paste_dilate", type=int, default=16, metavar="N", help="grow the mask by N pixels before feathering (with --paste_back)")
+    ap.add_argument("--paste_feather", type=int, default=4, metavar="N", help="radius of the three box passes that soften the mask's edge (with --paste_back)")
+    ap.add_argument("--paste_region", action="store_true", help="edit only a region cut around the mask, not the whole scene (with --paste_back)")
+    ap.add_argument("--paste_region_max", type=int, default=1024, metavar="N", help="longer side the region is edited at (with --paste_region)")
+
+
+def paste_back_from_args(a):
+    """None, or the paste_back dict of batch_driver.run_items / process_normal_mode."""
+    if not a.paste_back:
+        if a.paste_region:
+            raise SystemExit("--paste_region needs --paste_back")
+        return None
+    return dict(dilate=a.paste_dilate, feather=a.paste_feather, region=dict(max_side=a.paste_region_max) if a.paste_region else None)
 
 
 def add_step_cache_args(ap):
@@ -84,14 +110,24 @@ def report_step_cache(pipe):
         print(f"Step cache: {sum(1 for r in rep if r['skipped'])} of {len(rep)} steps skipped")
 
 
-def process_normal_mode(image_path, mask_path, words_path, steps, guidance_scale, seed, pipe=None, out_dir="outputs_my"):
+def process_normal_mode(image_path, mask_path, words_path, steps, guidance_scale, seed, pipe=None, out_dir="outputs_my", paste_back=None):
+    """paste_back: None, or dict(dilate, feather, region) as in batch_driver.run_items -- the saved crop is then the original scene at
+    its original size with the edit pasted in; with a region only that part of the scene goes through the pipeline."""
     scene, mask = Image.open(image_path).convert("RGB"), Image.open(mask_path).convert("RGB")
     words = glyph.read_words_from_text(words_path)
+    work = None
+    if paste_back is not None:
+        from textflux_amd import batch_driver
+        cfg = batch_driver._paste_back_cfg(paste_back)
+        scene, mask, so, mo, reg = batch_driver._paste_back_inputs(scene, mask, cfg)
+        work = batch_driver.Work(0, None, None, "", {}, scene.size, orig_scene=so, orig_mask=mo, region=reg)
     print("Using multi-line text rendering mode" if len(words) > 1 else "Using single-line text rendering mode")
     combined, cmask, meta = glyph.compose(scene, mask, words)
     print("Starting inference...")
     full = run_inference(combined, cmask, words_path, num_steps=steps, guidance_scale=guidance_scale, seed=seed, pipe=pipe)
     cropped = full.crop(glyph.crop_box(full.size, meta))
+    if work is not None:
+        cropped = batch_driver._paste_into_original(pipe or load_flux_pipeline(), work, cropped, cfg)
     os.makedirs(os.path.join(out_dir, "crop"), exist_ok=True)
     n = 1
     while os.path.exists(os.path.join(out_dir, f"result_{n:04d}.png")):
@@ -102,7 +138,7 @@ def process_normal_mode(image_path, mask_path, words_path, steps, guidance_scale
     return cropped
 
 
-def main():
+def build_parser():
     ap = argparse.ArgumentParser(description="Flux Text Generation CLI")
     ap.add_argument("--image", type=str, required=True, help="Path to input image")
     ap.add_argument("--mask", type=str, required=True, help="Path to mask image")
@@ -111,9 +147,15 @@ def main():
     ap.add_argument("--guidance-scale", type=float, default=30, help="Guidance scale value")
     ap.add_argument("--seed", type=int, default=42, help="Random seed")
     add_step_cache_args(ap)
-    a = ap.parse_args()
+    add_paste_back_args(ap)
+    return ap
+
+
+def main(argv=None):
+    a = build_parser().parse_args(argv)
+    paste_back = paste_back_from_args(a)
     pipe = apply_step_cache_args(a, load_flux_pipeline()) if a.step_cache is not None or a.step_cache_max_consecutive is not None else None
-    process_normal_mode(a.image, a.mask, a.words, a.steps, a.guidance_scale, a.seed, pipe=pipe)
+    process_normal_mode(a.image, a.mask, a.words, a.steps, a.guidance_scale, a.seed, pipe=pipe, paste_back=paste_back)
     report_step_cache(pipe)
     print("\nProcessing completed successfully!")
 

@@ -73,6 +73,12 @@ def build_parser(lora: bool = False):
                     "first-block residual moved by less than THR relative to the last computed step (no default: the value is a property "
                     "of the checkpoint; 0 never skips)")
     ap.add_argument("--step_cache_max_consecutive", type=int, default=None, metavar="K", help="at most K skipped steps in a row (with --step_cache)")
+    ap.add_argument("--paste_back", action="store_true", help="cropped_images/ (and --items outputs) are the ORIGINAL scenes at their original "
+                    "size, changed only under the dilated and feathered mask, instead of the pipeline's own pixels at pipeline size")
+    ap.add_argument("--paste_dilate", type=int, default=16, metavar="N", help="grow the mask by N pixels before feathering (with --paste_back)")
+    ap.add_argument("--paste_feather", type=int, default=4, metavar="N", help="radius of the three box passes that soften the mask's edge (with --paste_back)")
+    ap.add_argument("--paste_region", action="store_true", help="edit only a region cut around the mask, not the whole scene (with --paste_back)")
+    ap.add_argument("--paste_region_max", type=int, default=1024, metavar="N", help="longer side the region is edited at (with --paste_region)")
     ap.add_argument("--items", type=str, default=None, help="JSON list of {image, mask, text} instead of --json_path")
     ap.add_argument("--out", type=str, default=None, help="output folder of --items mode")
     ap.add_argument("--num_inference_steps", type=int, default=None, help=argparse.SUPPRESS)
@@ -128,6 +134,12 @@ def main(argv=None, lora: bool = False, script: str = __file__):
         raise SystemExit("--step_cache_max_consecutive needs --step_cache THR")
     if a.step_cache is not None and a.mixed_pad > 0:
         raise SystemExit("--step_cache does not serve mixed-geometry batches (--mixed_pad)")
+    if a.paste_region and not a.paste_back:
+        raise SystemExit("--paste_region needs --paste_back")
+    if a.paste_back and a.mixed_pad > 0:
+        raise SystemExit("--paste_back does not serve mixed-geometry batches (--mixed_pad)")
+    paste_back = (dict(dilate=a.paste_dilate, feather=a.paste_feather, region=dict(max_side=a.paste_region_max) if a.paste_region else None)
+                  if a.paste_back else None)
     legacy = a.items is not None
     weights = a.lora_weights_path if lora else a.weights_path
     if not legacy and not (a.json_path and a.original_images_dir and weights):
@@ -187,7 +199,7 @@ def main(argv=None, lora: bool = False, script: str = __file__):
     pipe.enable_hip_graph(True)
     res = batch_driver.run_items(items, pipe, out_dir, batch_size=a.batch_size, num_inference_steps=steps,
                                  guidance_scale=a.guidance_scale, seed=a.seed, device=f"cuda:{local}", eval_cfg=eval_cfg,
-                                 mixed_pad=a.mixed_pad,
+                                 mixed_pad=a.mixed_pad, paste_back=paste_back,
                                  step_cache=None if a.step_cache is None else dict(threshold=a.step_cache, max_consecutive=a.step_cache_max_consecutive))
     if "steps_total" in res:
         print(f"[rank {rank}] step cache: {res['steps_skipped']} of {res['steps_total']} steps skipped")

@@ -48,6 +48,9 @@ class Work:
     size: Tuple[int, int]            # (width, height) given to the pipeline
     parts: Any = None                # (glyph, scene, mask uint8 arrays, horizontal): composed on the device per batch
     name: Optional[str] = None       # eval schema: base file name written under full_images/ and cropped_images/
+    orig_scene: Any = None           # paste-back only: the scene as loaded, uint8 [H, W, 3] ...
+    orig_mask: Any = None            # ... its RGB mask, uint8 [H, W, 3] ...
+    region: Any = None               # ... and the paste_back.Region of it that was edited (the whole image without `region`)
 
 
 @dataclass
@@ -63,8 +66,44 @@ def eval_item_complete(item: Dict[str, Any]) -> bool:
     return bool(ann) and bool(ann[0].get("text")) and bool(ann[0].get("polygon"))
 
 
+def _paste_back_cfg(paste_back: Dict[str, Any]) -> Dict[str, Any]:
+    """run_items' paste_back argument with its defaults filled in: dict(dilate, feather, region: None | dict(pad, min_side, max_side))."""
+    from . import paste_back as pb
+    unknown = set(paste_back) - {"dilate", "feather", "region"}
+    region = paste_back.get("region")
+    if region is not None:
+        unknown |= {f"region.{k}" for k in set(region) - {"pad", "min_side", "max_side"}}
+    if unknown:
+        raise ValueError(f"paste_back: unknown keys {sorted(unknown)}")
+    dilate, feather = paste_back.get("dilate"), paste_back.get("feather")
+    cfg = dict(dilate=pb.DILATE if dilate is None else int(dilate), feather=pb.FEATHER if feather is None else int(feather), region=None)
+    if not (0 <= cfg["dilate"] <= 255 and 0 <= cfg["feather"] <= 255):
+        raise ValueError("paste_back: dilate and feather must be in [0, 255]")
+    if region is not None:
+        cfg["region"] = {k: v for k, v in region.items() if v is not None}
+    return cfg
+
+
+def _paste_back_inputs(scene, mask, cfg: Dict[str, Any]):
+    """Paste-back: (scene, mask) PIL images handed to the usual preparation, and what the paste needs afterwards (the originals as
+    arrays, the edited Region).  Without `region` the preparation sees the images as they are; with it, the region's crop, resized
+    with PIL's bicubic to the region's editing size (tw, th) when that differs."""
+    import numpy as np
+    from PIL import Image
+    from . import paste_back as pb
+    so, mo = np.array(scene), np.array(mask)
+    if cfg["region"] is None:
+        return scene, mask, so, mo, pb.select_region(None, size=scene.size)
+    reg = pb.select_region(pb.grey_of(mo), cfg["dilate"], cfg["feather"], **cfg["region"])
+    box = (reg.x0, reg.y0, reg.x1, reg.y1)
+    s, m = scene.crop(box), mask.crop(box)
+    if s.size != (reg.tw, reg.th):
+        s, m = s.resize((reg.tw, reg.th), Image.BICUBIC), m.resize((reg.tw, reg.th), Image.BICUBIC)
+    return s, m, so, mo, reg
+
+
 def prepare_eval_item(index: int, item: Dict[str, Any], original_images_dir: str, font, text_height_ratio: float = 0.1667,
-                      loader: Optional[Callable] = None, device_compose: bool = False) -> Work:
+                      loader: Optional[Callable] = None, device_compose: bool = False, paste_back: Optional[Dict[str, Any]] = None) -> Work:
     """One `annos.json` entry -> Work (scripts/run_eval.py:76-112): scene = original_images_dir / img_name; mask = the first
     annotation's polygon filled white on black; glyph strip of height int(w * text_height_ratio) -- a fraction of the image
     WIDTH -- with the annotation's text, stacked on top with a black mask; pipeline size ((w // 32) * 32,
@@ -76,43 +115,53 @@ def prepare_eval_item(index: int, item: Dict[str, Any], original_images_dir: str
     text = ann["text"]
     scene = load(os.path.join(original_images_dir, item["img_name"])).convert("RGB")
     w, h = scene.size
+    m = glyph.fill_polygon(h, w, ann["polygon"])
+    extra = {}
+    if paste_back is not None:       # the strip, the stacking and the sizes below are then those of the edited region
+        scene, mk, so, mo, reg = _paste_back_inputs(scene, Image.fromarray(m), paste_back)
+        (w, h), m, extra = scene.size, np.array(mk), dict(orig_scene=so, orig_mask=mo, region=reg)
     strip = int(w * text_height_ratio)
     g = np.array(glyph.draw_glyph(font, text, w, strip))
-    m = glyph.fill_polygon(h, w, ann["polygon"])
     meta = dict(mode="singleline", direction="vertical", strip=strip, orig_h=h)
     size = ((w // 32) * 32, ((h + strip) // 32) * 32)
     prompt = glyph.generate_prompt([text])
     name = os.path.basename(item["img_name"])
     if device_compose:
-        return Work(index, None, None, prompt, meta, size, parts=(g, np.array(scene), m, False), name=name)
+        return Work(index, None, None, prompt, meta, size, parts=(g, np.array(scene), m, False), name=name, **extra)
     combined = Image.fromarray(np.vstack((g, np.array(scene))))
     cmask = Image.fromarray(np.vstack((np.zeros_like(g), m)))
-    return Work(index, combined.resize(size), cmask.resize(size), prompt, meta, size, name=name)
+    return Work(index, combined.resize(size), cmask.resize(size), prompt, meta, size, name=name, **extra)
 
 
 def prepare_item(index: int, item: Dict[str, Any], loader: Optional[Callable] = None, device_compose: bool = False,
-                 eval_cfg: Optional[Dict[str, Any]] = None) -> Work:
+                 eval_cfg: Optional[Dict[str, Any]] = None, paste_back: Optional[Dict[str, Any]] = None) -> Work:
     """Host-side preparation of one item (run_inference.py:395-467 up to the pipeline call).  With device_compose the
     stacking is left to the device when no resize is involved.  Items in the reference's `annos.json` schema (an `img_name`
-    key) go through prepare_eval_item with eval_cfg = dict(original_images_dir, font, text_height_ratio)."""
+    key) go through prepare_eval_item with eval_cfg = dict(original_images_dir, font, text_height_ratio).
+    paste_back (_paste_back_cfg's dict): the Work also keeps the scene and mask as loaded and the edited Region; with a `region` the
+    preparation below runs on that region's crop instead of the whole scene."""
     from PIL import Image
     if "img_name" in item:
         c = eval_cfg or {}
         return prepare_eval_item(index, item, c.get("original_images_dir", "."), c.get("font") or glyph.load_font(c.get("font_path")),
-                                 c.get("text_height_ratio", 0.1667), loader, device_compose)
+                                 c.get("text_height_ratio", 0.1667), loader, device_compose, paste_back)
     load = loader or (lambda p: Image.open(p))
     scene, mask = load(item["image"]).convert("RGB"), load(item["mask"]).convert("RGB")
+    extra = {}
+    if paste_back is not None:
+        scene, mask, so, mo, reg = _paste_back_inputs(scene, mask, paste_back)
+        extra = dict(orig_scene=so, orig_mask=mo, region=reg)
     words = glyph.read_words_from_text(item["text"])
     g, s_, m, horizontal, meta = glyph.compose_parts(scene, mask, words)
     H, W = (s_.shape[0], g.shape[1] + s_.shape[1]) if horizontal else (g.shape[0] + s_.shape[0], s_.shape[1])
     w, h = (W // 32) * 32, (H // 32) * 32
     prompt = glyph.generate_prompt(words)
     if device_compose:               # stacking, the resize to (w, h) and the grey mask happen on the device, per batch
-        return Work(index, None, None, prompt, meta, (w, h), parts=(g, s_, m, horizontal))
+        return Work(index, None, None, prompt, meta, (w, h), parts=(g, s_, m, horizontal), **extra)
     import numpy as np
     stack = np.hstack if horizontal else np.vstack
     combined, cmask = Image.fromarray(stack((g, s_))), Image.fromarray(stack((np.zeros_like(g), m)))
-    return Work(index, combined.resize((w, h)), cmask.resize((w, h)), prompt, meta, (w, h))
+    return Work(index, combined.resize((w, h)), cmask.resize((w, h)), prompt, meta, (w, h), **extra)
 
 
 def _batch_inputs(items: Sequence[Work], device):
@@ -140,6 +189,23 @@ def _batch_inputs(items: Sequence[Work], device):
             imgs.append(Image.fromarray(stack((g, s_))).resize(w.size))
             masks.append(Image.fromarray(stack((np.zeros_like(g), m))).resize(w.size))
     return imgs, masks
+
+
+def _paste_into_original(pipe, w: Work, cropped, cfg: Dict[str, Any]):
+    """The item's cropped result -> its original scene with the edited region pasted in (PIL image at the scene's size).  Only the
+    region's crop of the scene and mask and the cropped result visit the device (pipe.paste_back); the insertion into the copy of
+    the scene is a host slice assignment."""
+    import numpy as np
+    from PIL import Image
+    from . import paste_back as pb
+    reg = w.region
+    oc = w.orig_scene[reg.y0:reg.y1, reg.x0:reg.x1]
+    om = pb.grey_of(w.orig_mask[reg.y0:reg.y1, reg.x0:reg.x1])
+    pasted = pipe.paste_back(oc, cropped, om, dilate=cfg["dilate"], feather=cfg["feather"])
+    pasted = pasted.cpu().numpy() if isinstance(pasted, torch.Tensor) else np.asarray(pasted)
+    out = w.orig_scene.copy()
+    out[reg.y0:reg.y1, reg.x0:reg.x1] = pasted.reshape(oc.shape)
+    return Image.fromarray(out)
 
 
 def image_tokens(size: Tuple[int, int]) -> int:
@@ -213,7 +279,7 @@ def run_items(items: Sequence[Dict[str, Any]], pipe, out_dir: Optional[str], bat
               guidance_scale: float = 30.0, seed: int = 42, device="cuda", loader: Optional[Callable] = None,
               save: Optional[Callable] = None, max_sequence_length: int = 512, eval_cfg: Optional[Dict[str, Any]] = None,
               encode: str = "auto", save_full: Optional[Callable] = None, mixed_pad: float = 0.0,
-              step_cache: Optional[Dict[str, Any]] = None) -> Dict[str, Any]:
+              step_cache: Optional[Dict[str, Any]] = None, paste_back: Optional[Dict[str, Any]] = None) -> Dict[str, Any]:
     """Runs the whole list; returns {"done": [indices this rank wrote], "failed": [...], "all_done": [...] on rank 0,
     "encode": "local" | "rank0"}.  `pipe` needs `encode_prompt(prompt, prompt_2, ...)` and the FluxFillPipeline `__call__`.
     encode: "local" = every rank encodes the T5 prompts of its own batches (needs a T5 on every rank), "rank0" = rank 0
@@ -224,7 +290,19 @@ def run_items(items: Sequence[Dict[str, Any]], pipe, out_dir: Optional[str], bat
     most that share of the batch's rows is padding; 0 (default) = same-geometry batches only.
     step_cache: None, or the keyword arguments of pipe.enable_step_cache (threshold, skip_steps, max_consecutive): the first-block step
     cache is switched on for the run (and off again afterwards); the result then carries "steps_skipped" / "steps_total" over this
-    rank's batches.  Each rank decides alone from its own batch's metrics; not with mixed_pad > 0."""
+    rank's batches.  Each rank decides alone from its own batch's metrics; not with mixed_pad > 0.
+    paste_back: None (the outputs are the pipeline's own pixels at pipeline size), or dict(dilate, feather, region): every item's cropped
+    result is blended back into its ORIGINAL scene under the dilated and feathered mask (pipe.paste_back), and the image that is saved /
+    written as <index>.png / written under cropped_images/ / passed as `cropped` to save_full is that scene at its original size, changed
+    only near the mask (full_images/ stays the raw canvas).  region: None = the whole scene goes through the pipeline as before;
+    dict(pad, min_side, max_side) (paste_back.select_region) = only a region around the mask does, resized to at most max_side, so a
+    large photo costs what its mask's neighbourhood costs.  Not with mixed_pad > 0."""
+    if paste_back is not None:       # refused before anything is prepared or encoded
+        if mixed_pad > 0:
+            raise NotImplementedError("paste_back does not serve mixed-geometry batches (mixed_pad > 0)")
+        if not hasattr(pipe, "paste_back"):
+            raise ValueError("paste_back needs a pipeline with paste_back (FluxFillPipeline)")
+        paste_back = _paste_back_cfg(paste_back)
     if step_cache is not None:
         if mixed_pad > 0:
             raise NotImplementedError("step_cache does not serve mixed-geometry batches (mixed_pad > 0)")
@@ -233,15 +311,15 @@ def run_items(items: Sequence[Dict[str, Any]], pipe, out_dir: Optional[str], bat
         pipe.enable_step_cache(**step_cache)
         try:
             return _run_items(items, pipe, out_dir, batch_size, num_inference_steps, guidance_scale, seed, device, loader, save,
-                              max_sequence_length, eval_cfg, encode, save_full, mixed_pad, count_steps=True)
+                              max_sequence_length, eval_cfg, encode, save_full, mixed_pad, count_steps=True, paste_back=paste_back)
         finally:
             pipe.disable_step_cache()
     return _run_items(items, pipe, out_dir, batch_size, num_inference_steps, guidance_scale, seed, device, loader, save,
-                      max_sequence_length, eval_cfg, encode, save_full, mixed_pad)
+                      max_sequence_length, eval_cfg, encode, save_full, mixed_pad, paste_back=paste_back)
 
 
 def _run_items(items, pipe, out_dir, batch_size, num_inference_steps, guidance_scale, seed, device, loader, save, max_sequence_length,
-               eval_cfg, encode, save_full, mixed_pad, count_steps: bool = False) -> Dict[str, Any]:
+               eval_cfg, encode, save_full, mixed_pad, count_steps: bool = False, paste_back: Optional[Dict[str, Any]] = None) -> Dict[str, Any]:
     steps_skipped = steps_total = 0
     if mixed_pad > 0:            # refused before anything is prepared or encoded, not batch by batch inside the loop
         if not hasattr(pipe, "call_mixed"):
@@ -256,7 +334,7 @@ def _run_items(items, pipe, out_dir, batch_size, num_inference_steps, guidance_s
     for i, it in enumerate(items):
         try:
             works.append(prepare_item(i, it, loader, device_compose=bool(getattr(pipe, "supports_device_compose", False)),
-                                      eval_cfg=eval_cfg))
+                                      eval_cfg=eval_cfg, **({} if paste_back is None else dict(paste_back=paste_back))))
         except Exception as e:       # per-item failures do not stop the run (reference :195-198)
             failed.append(i)
             if rank == 0:
@@ -357,6 +435,8 @@ def _run_items(items, pipe, out_dir, batch_size, num_inference_steps, guidance_s
                 steps_skipped += sum(1 for r_ in rep if r_["skipped"])
             for w, img, bx in zip(mine.items, images, boxes):
                 cropped = img if kw else img.crop(bx)
+                if paste_back is not None:
+                    cropped = _paste_into_original(pipe, w, cropped, paste_back)
                 if w.name is not None and (save_full is not None or (save is None and out_dir is not None)):
                     if save_full is not None:
                         save_full(w, img, cropped)

@@ -389,6 +389,19 @@ int tfx_resample_u8(const void* in, void* out, const int32_t* bounds, const int3
   if (!in || !out || !bounds || !coeffs) return fail("tfx_resample_u8: null pointer");
   return resample_u8(in, out, bounds, coeffs, ksize, outer, in_len, out_len, inner, S(stream));
 }
+int tfx_mask_dilate_u8(const void* in, void* out, void* tmp, int32_t B, int32_t H, int32_t W, int32_t radius, tfx_stream stream) {
+  if (!in || !out || !tmp) return fail("tfx_mask_dilate_u8: null pointer");
+  return mask_dilate_u8(in, out, tmp, B, H, W, radius, S(stream));
+}
+int tfx_mask_feather_u8(const void* in, void* out, void* tmp, int32_t B, int32_t H, int32_t W, int32_t radius, tfx_stream stream) {
+  if (!in || !out || !tmp) return fail("tfx_mask_feather_u8: null pointer");
+  return mask_feather_u8(in, out, tmp, B, H, W, radius, S(stream));
+}
+int tfx_overlay_u8(const void* orig, const void* edit, const void* alpha, void* out, int32_t B, int32_t H, int32_t W, int32_t C,
+                   tfx_stream stream) {
+  if (!orig || !edit || !alpha || !out) return fail("tfx_overlay_u8: null pointer");
+  return overlay_u8(orig, edit, alpha, out, B, H, W, C, S(stream));
+}
 int tfx_pack_mask(const void* mask, int32_t mask_dtype, void* out, int32_t B, int32_t H, int32_t W, int32_t mask_batch,
                   int32_t binarize, int64_t ld, int32_t col0, tfx_stream stream) {
   if (!mask || !out) return fail("tfx_pack_mask: null pointer");

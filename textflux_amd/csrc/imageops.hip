@@ -360,6 +360,44 @@ __global__ __launch_bounds__(256) void resample_u8_kernel(const uint8_t* __restr
   out[i] = (uint8_t)(ss < 0 ? 0 : ss > 255 ? 255 : ss);
 }
 
+// ---- paste-back (DESIGN.md section 4 "Paste-back"): two window passes over a u8 mask and the blend, integer arithmetic only.
+// One pass along the middle axis of in [outer][len][inner] -> out, the layout resample_u8_kernel walks: the x pass of a
+// [B, H, W] mask is outer = B H, len = W, inner = 1, the y pass outer = B, len = H, inner = W.  One thread per output byte; a
+// wave's 64 threads read 64 neighbouring bytes per window step (x pass: overlapping, y pass: one row segment).
+//   OP 0 (dilate): max over |k| <= r, the window clipped at both ends of the axis.
+//   OP 1 (box):    s = sum over |k| <= r of v[clamp(p + k, 0, len - 1)] (edge replicated), out = (2 s + n) / (2 n), n = 2 r + 1
+//                  -- s <= 511 * 255, and the quotient is at most 255.
+template <int OP>
+__global__ __launch_bounds__(256) void window_pass_u8_kernel(const uint8_t* __restrict__ in, uint8_t* __restrict__ out, int64_t outer,
+                                                             int len, int64_t inner, int r) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= outer * len * inner) return;
+  const int64_t e = i % inner, op = i / inner;
+  const int p = (int)(op % len);
+  const uint8_t* src = in + (op / len) * len * inner + e;
+  if constexpr (OP == 0) {
+    const int lo = p - r < 0 ? 0 : p - r, hi = p + r > len - 1 ? len - 1 : p + r;
+    unsigned m = 0;
+    for (int k = lo; k <= hi; ++k) m = max(m, (unsigned)src[k * inner]);
+    out[i] = (uint8_t)m;
+  } else {
+    unsigned s = 0;
+    for (int k = p - r; k <= p + r; ++k) s += src[(int64_t)(k < 0 ? 0 : k > len - 1 ? len - 1 : k) * inner];
+    const unsigned n = 2u * r + 1u;
+    out[i] = (uint8_t)((2u * s + n) / (2u * n));
+  }
+}
+
+// out = (orig (255 - a) + edit a + 127) / 255 per channel, a = alpha of the pixel; out may be orig (each thread reads the byte it
+// writes, and no other), so neither carries __restrict__.
+__global__ __launch_bounds__(256) void overlay_u8_kernel(const uint8_t* orig, const uint8_t* __restrict__ edit,
+                                                         const uint8_t* __restrict__ alpha, uint8_t* out, int64_t n, int C) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const unsigned a = alpha[i / C];
+  out[i] = (uint8_t)((orig[i] * (255u - a) + edit[i] * a + 127u) / 255u);
+}
+
 int compose_canvas(const void* glyph, const void* scene, const void* smask, void* canvas, void* cmask, int B, int gh, int gw, int sh,
                    int sw, int dir, int mask_rgb, hipStream_t st) {
   if (dir != 0 && dir != 1) return fail("compose_canvas: direction 0 (vertical) or 1 (horizontal)");
@@ -384,6 +422,53 @@ int resample_u8(const void* in, void* out, const int* bounds, const int* coeffs,
   if (n <= 0) return 0;
   resample_u8_kernel<<<blocks_for(n), 256, 0, st>>>((const uint8_t*)in, (uint8_t*)out, bounds, coeffs, ksize, outer, in_len, out_len, inner);
   return check_launch("resample_u8");
+}
+
+static const int64_t kMaxBytes = (int64_t)1 << 38;   // one thread per byte, 256 per block: the grid stays below 2^31 blocks
+
+static int window_geometry(const char* what, int B, int H, int W, int radius) {
+  if (B < 1 || H < 1 || W < 1) return fail("%s: B, H, W must be at least 1", what);
+  if (radius < 0 || radius > 255) return fail("%s: radius must be in [0, 255]", what);
+  if ((int64_t)B * H * W > kMaxBytes) return fail("%s: more than 2^38 pixels", what);
+  return 0;
+}
+
+template <int OP>
+static void window_pass(const uint8_t* in, uint8_t* out, int B, int H, int W, int radius, bool along_x, hipStream_t st) {
+  const int64_t n = (int64_t)B * H * W;
+  if (along_x) window_pass_u8_kernel<OP><<<blocks_for(n), 256, 0, st>>>(in, out, (int64_t)B * H, W, 1, radius);
+  else window_pass_u8_kernel<OP><<<blocks_for(n), 256, 0, st>>>(in, out, B, H, W, radius);
+}
+
+int mask_dilate_u8(const void* in, void* out, void* tmp, int B, int H, int W, int radius, hipStream_t st) {
+  if (window_geometry("mask_dilate_u8", B, H, W, radius)) return 1;
+  if (in == out || in == tmp || out == tmp) return fail("mask_dilate_u8: in, out and tmp must be three different buffers");
+  window_pass<0>((const uint8_t*)in, (uint8_t*)tmp, B, H, W, radius, true, st);
+  window_pass<0>((const uint8_t*)tmp, (uint8_t*)out, B, H, W, radius, false, st);
+  return check_launch("mask_dilate_u8");
+}
+
+int mask_feather_u8(const void* in, void* out, void* tmp, int B, int H, int W, int radius, hipStream_t st) {
+  if (window_geometry("mask_feather_u8", B, H, W, radius)) return 1;
+  if (in == out || in == tmp || out == tmp) return fail("mask_feather_u8: in, out and tmp must be three different buffers");
+  const uint8_t* src = (const uint8_t*)in;
+  uint8_t* a = (uint8_t*)tmp;
+  uint8_t* b = (uint8_t*)out;
+  for (int pass = 0; pass < 6; ++pass) {       // x x x y y y; in -> tmp -> out -> tmp -> out -> tmp -> out
+    window_pass<1>(src, a, B, H, W, radius, pass < 3, st);
+    src = a;
+    uint8_t* t = a; a = b; b = t;
+  }
+  return check_launch("mask_feather_u8");
+}
+
+int overlay_u8(const void* orig, const void* edit, const void* alpha, void* out, int B, int H, int W, int C, hipStream_t st) {
+  if (B < 1 || H < 1 || W < 1 || C < 1) return fail("overlay_u8: B, H, W, C must be at least 1");
+  if (edit == out || alpha == out) return fail("overlay_u8: out may alias orig only");
+  const int64_t n = (int64_t)B * H * W * C;
+  if (n > kMaxBytes) return fail("overlay_u8: more than 2^38 bytes");
+  overlay_u8_kernel<<<blocks_for(n), 256, 0, st>>>((const uint8_t*)orig, (const uint8_t*)edit, (const uint8_t*)alpha, (uint8_t*)out, n, C);
+  return check_launch("overlay_u8");
 }
 
 int pack_mask(const void* mask, int mask_dtype, void* out, int B, int H, int W, int mask_b, int binarize, int64_t ld, int col0,

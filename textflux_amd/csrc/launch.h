@@ -206,6 +206,10 @@ int compose_canvas(const void* glyph, const void* scene, const void* smask, void
 int rgb_to_grey(const void* rgb, void* out, int64_t n, hipStream_t st);
 int resample_u8(const void* in, void* out, const int* bounds, const int* coeffs, int ksize, int64_t outer, int in_len, int out_len,
                 int inner, hipStream_t st);
+// paste-back: mask [B, H, W] u8 window passes (tmp: a third buffer of the mask's size) and the alpha blend of [B, H, W, C] u8 images
+int mask_dilate_u8(const void* in, void* out, void* tmp, int B, int H, int W, int radius, hipStream_t st);
+int mask_feather_u8(const void* in, void* out, void* tmp, int B, int H, int W, int radius, hipStream_t st);
+int overlay_u8(const void* orig, const void* edit, const void* alpha, void* out, int B, int H, int W, int C, hipStream_t st);
 int pack_mask(const void* mask, int mask_dtype, void* out, int B, int H, int W, int mask_b, int binarize, int64_t ld, int col0,
               hipStream_t st);
 int sample_pack(const void* moments, const void* eps, int eps_dtype, void* out, int B, int h, int w, int L, float shift,

@@ -677,6 +677,53 @@ def compose_canvas(glyph: torch.Tensor, scene: torch.Tensor, scene_mask_rgb: tor
     return canvas, cmask
 
 
+def _chk_mask_u8(mask: torch.Tensor, radius: int, what: str):
+    _chk_dev(mask)
+    if mask.dtype != torch.uint8 or mask.dim() != 3 or not mask.is_contiguous() or mask.numel() == 0:
+        raise ValueError(f"{what}: the mask must be a contiguous, non-empty uint8 [B, H, W] tensor, got {mask.dtype} {tuple(mask.shape)}")
+    if not 0 <= int(radius) <= 255:
+        raise ValueError(f"{what}: radius must be in [0, 255], got {radius}")
+
+
+def mask_dilate(mask: torch.Tensor, radius: int) -> torch.Tensor:
+    """Square max filter of a uint8 mask [B, H, W]: the maximum over the (2 radius + 1)^2 window, clipped at the image border
+    (tfx_mask_dilate_u8).  radius 0 copies."""
+    _chk_mask_u8(mask, radius, "mask_dilate")
+    out, tmp = torch.empty_like(mask), torch.empty_like(mask)
+    B, H, W = mask.shape
+    L.check(L.lib().tfx_mask_dilate_u8(mask.data_ptr(), out.data_ptr(), tmp.data_ptr(), B, H, W, int(radius), _stream()), "mask_dilate")
+    return out
+
+
+def mask_feather(mask: torch.Tensor, radius: int) -> torch.Tensor:
+    """Three box passes of width 2 radius + 1 along x, then three along y, over a uint8 mask [B, H, W]; edge replicated, every pass
+    rounded to uint8 (tfx_mask_feather_u8).  radius 0 copies."""
+    _chk_mask_u8(mask, radius, "mask_feather")
+    out, tmp = torch.empty_like(mask), torch.empty_like(mask)
+    B, H, W = mask.shape
+    L.check(L.lib().tfx_mask_feather_u8(mask.data_ptr(), out.data_ptr(), tmp.data_ptr(), B, H, W, int(radius), _stream()), "mask_feather")
+    return out
+
+
+def overlay(orig: torch.Tensor, edit: torch.Tensor, alpha: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """(orig (255 - alpha) + edit alpha + 127) // 255 of uint8 images [B, H, W, C] under a uint8 alpha [B, H, W] (tfx_overlay_u8).
+    out: None (a new tensor) or `orig` itself."""
+    _chk_dev(orig, edit, alpha, out)
+    for t in (orig, edit, alpha):
+        if t.dtype != torch.uint8 or not t.is_contiguous():
+            raise ValueError("overlay: orig, edit and alpha must be contiguous uint8 tensors")
+    if orig.dim() != 4 or orig.numel() == 0 or edit.shape != orig.shape or alpha.shape != orig.shape[:3]:
+        raise ValueError(f"overlay: orig / edit [B, H, W, C] and alpha [B, H, W] must agree, got {tuple(orig.shape)}, {tuple(edit.shape)}, "
+                         f"{tuple(alpha.shape)}")
+    if out is None:
+        out = torch.empty_like(orig)
+    elif out.shape != orig.shape or out.dtype != torch.uint8 or not out.is_contiguous():
+        raise ValueError("overlay: out must be a contiguous uint8 tensor of orig's shape")
+    B, H, W, Cc = orig.shape
+    L.check(L.lib().tfx_overlay_u8(orig.data_ptr(), edit.data_ptr(), alpha.data_ptr(), out.data_ptr(), B, H, W, Cc, _stream()), "overlay")
+    return out
+
+
 def pack_mask(mask: torch.Tensor, out: torch.Tensor, col0: int, B: int, H: int, W: int, binarize: bool = True) -> torch.Tensor:
     """out[b, :, col0 : col0 + 256] = packed mask (out: [B, S, ld] bf16)."""
     _chk_dev(mask, out)

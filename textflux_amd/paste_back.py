@@ -1,0 +1,119 @@
+"""Paste-back and region editing (DESIGN.md section 4 "Paste-back"): the pipeline's result goes back into the ORIGINAL image, at
+its original size, under a dilated and feathered mask, so that every pixel outside the edit keeps its bytes; and a large photo is
+edited through a region cut around the mask instead of being resized whole.
+
+No reference counterpart: FluxFillPipeline never calls its image processor's crop / overlay helpers (the idea is in
+diffusers/src/diffusers/image_processor.py: get_crop_region :293, blur :276, apply_overlay :773) and the reference's callers
+return the VAE round trip of the whole canvas.  The arithmetic here is this project's own, exact in integers:
+
+    alpha = feather(dilate(mask >= 128 ? 255 : 0, d), r)          ops.mask_dilate / ops.mask_feather
+    out   = (orig (255 - alpha) + edit alpha + 127) // 255        ops.overlay
+
+The feather's support grows by at most 3 r per axis, so alpha is 0 outside the mask dilated by d + 3 r; with d >= 3 r every
+original mask pixel has alpha = 255 (the seam lies outside the edited text).  The defaults satisfy that; they are a starting
+point, not a tuned value.
+"""
+from __future__ import annotations
+
+import math
+from typing import NamedTuple, Optional, Tuple
+
+import numpy as np
+import torch
+
+from . import ops
+
+DILATE, FEATHER = 16, 4
+PAD, MIN_SIDE, MAX_SIDE = 0.5, 256, 1024
+
+
+class Region(NamedTuple):
+    x0: int
+    y0: int
+    x1: int                          # half-open: columns [x0, x1), rows [y0, y1) of the original image
+    y1: int
+    tw: int                          # the size the crop is edited at (the crop's own size unless it exceeds max_side)
+    th: int
+
+
+def halo(dilate: int, feather: int) -> int:
+    """Pixels around the mask's bounding box that a region must keep: alpha's support (dilate + 3 feather) and one pixel of
+    alpha = 0, so that the region's border is untouched and the paste leaves no seam there."""
+    return int(dilate) + 3 * int(feather) + 1
+
+
+def _fit(lo: int, hi: int, size: int, min_side: int) -> Tuple[int, int]:
+    """One axis: grown symmetrically (floor on the low side) to min_side, then shifted -- not shrunk -- into [0, size)."""
+    if hi - lo < min_side:
+        lo -= (min_side - (hi - lo)) // 2
+        hi = lo + min_side
+    if hi - lo >= size:
+        return 0, size
+    if lo < 0:
+        lo, hi = 0, hi - lo
+    if hi > size:
+        lo, hi = lo - (hi - size), size
+    return lo, hi
+
+
+def select_region(mask_grey, dilate: int = DILATE, feather: int = FEATHER, pad: float = PAD, min_side: int = MIN_SIDE,
+                  max_side: int = MAX_SIDE, size: Optional[Tuple[int, int]] = None) -> Region:
+    """The rectangle of the original image that is edited.  mask_grey: host uint8 [H, W]; None with size = (W, H) is the whole image
+    at its own size, (0, 0, W, H, W, H).
+    Bounding box of the pixels >= 128 (none: ValueError), grown on every side by p = max(halo, ceil(pad * max(bw, bh))), each axis
+    then grown to min_side and shifted into the image (an axis longer than the image is the whole axis).  A region whose longer
+    side m exceeds max_side is edited at (max(32, w max_side // m), max(32, h max_side // m))."""
+    if mask_grey is None:
+        if size is None:
+            raise ValueError("select_region: the whole-image region needs size=(width, height)")
+        return Region(0, 0, int(size[0]), int(size[1]), int(size[0]), int(size[1]))
+    m = np.asarray(mask_grey)
+    if m.ndim != 2:
+        raise ValueError(f"select_region: the mask must be [H, W], got {m.shape}")
+    H, W = m.shape
+    on = m >= 128
+    rows, cols = np.flatnonzero(on.any(axis=1)), np.flatnonzero(on.any(axis=0))
+    if rows.size == 0:
+        raise ValueError("select_region: the mask is empty (no pixel >= 128)")
+    x0, x1, y0, y1 = int(cols[0]), int(cols[-1]) + 1, int(rows[0]), int(rows[-1]) + 1
+    p = max(halo(dilate, feather), int(math.ceil(pad * max(x1 - x0, y1 - y0))))
+    x0, x1 = _fit(x0 - p, x1 + p, W, min_side)
+    y0, y1 = _fit(y0 - p, y1 + p, H, min_side)
+    w, h = x1 - x0, y1 - y0
+    longer = max(w, h)
+    if longer > max_side:
+        return Region(x0, y0, x1, y1, max(32, w * max_side // longer), max(32, h * max_side // longer))
+    return Region(x0, y0, x1, y1, w, h)
+
+
+def alpha_mask(mask_grey: torch.Tensor, dilate: int = DILATE, feather: int = FEATHER) -> torch.Tensor:
+    """uint8 [B, H, W] grey mask on the device -> the blend weight: binarised at >= 128 (VaeImageProcessor.binarize of grey / 255 at
+    0.5), dilated, feathered."""
+    if mask_grey.dtype != torch.uint8 or mask_grey.dim() != 3:
+        raise ValueError(f"alpha_mask: the mask must be uint8 [B, H, W], got {mask_grey.dtype} {tuple(mask_grey.shape)}")
+    binary = (mask_grey >= 128).to(torch.uint8).mul_(255).contiguous()
+    return ops.mask_feather(ops.mask_dilate(binary, dilate), feather)
+
+
+def paste(original: torch.Tensor, edited: torch.Tensor, mask_grey: torch.Tensor, dilate: int = DILATE, feather: int = FEATHER) -> torch.Tensor:
+    """original uint8 [B, H, W, 3], edited uint8 [B, h, w, 3], mask_grey uint8 [B, H, W], all on the device -> [B, H, W, 3]: the edit,
+    resampled to (H, W) when its size differs (ops.resample_u8: Pillow's bicubic), blended over the original under alpha_mask computed at
+    the ORIGINAL resolution.  Outside the mask dilated by dilate + 3 feather the result is the original byte for byte; with
+    dilate >= 3 feather it is the resampled edit on every mask pixel."""
+    if original.dtype != torch.uint8 or original.dim() != 4 or edited.dtype != torch.uint8 or edited.dim() != 4:
+        raise ValueError("paste: original and edited must be uint8 [B, H, W, C]")
+    if edited.shape[0] != original.shape[0] or edited.shape[3] != original.shape[3] or mask_grey.shape != original.shape[:3]:
+        raise ValueError(f"paste: original {tuple(original.shape)}, edited {tuple(edited.shape)} and mask {tuple(mask_grey.shape)} do not agree")
+    original, edited = original.contiguous(), edited.contiguous()
+    if edited.shape[1:3] != original.shape[1:3]:
+        edited = ops.resample_u8(edited, (original.shape[1], original.shape[2]))
+    return ops.overlay(original, edited, alpha_mask(mask_grey.contiguous(), dilate, feather))
+
+
+def grey_of(mask) -> np.ndarray:
+    """Host uint8 [H, W] grey value of a mask given as a PIL image or an [H, W] / [H, W, 3] uint8 array: PIL's convert("L")."""
+    from PIL import Image
+    if isinstance(mask, Image.Image):
+        return np.array(mask.convert("L"))
+    m = np.asarray(mask)
+    return np.array(Image.fromarray(m).convert("L")) if m.ndim == 3 else m

@@ -116,6 +116,7 @@ class FluxFillPipeline:
     _callback_tensor_inputs = ["latents", "prompt_embeds"]
     supports_output_crop = True
     supports_device_compose = True   # image / mask_image may be uint8 device tensors [B, H, W, 3] / [B, H, W] (ops.compose_canvas)
+    supports_paste_back = True       # paste_back(): the result goes back into the original image under a feathered mask
     model_index_name = "model_index.json"
 
     def __init__(self, scheduler, vae, text_encoder, tokenizer, text_encoder_2, tokenizer_2,
@@ -585,6 +586,49 @@ class FluxFillPipeline:
     def disable_step_cache(self):
         self._step_cache = None
         return self
+
+    # ------------------------------------------------------------------ paste-back (DESIGN.md section 4 "Paste-back")
+    def paste_back(self, original, edited, mask, dilate: int = 16, feather: int = 4) -> torch.Tensor:
+        """The edited image blended into the ORIGINAL one, at the original's size, under the dilated and feathered mask
+        (textflux_amd/paste_back.py::paste): pixels outside the mask grown by dilate + 3 feather keep their bytes.  Opt-in, no reference
+        counterpart.  original / edited: a PIL image, a uint8 array or tensor [H, W, 3] / [B, H, W, 3], or a list of PIL images (edited
+        may have another size: it is resampled with Pillow's bicubic on the device); mask: the same forms, grey [H, W] or RGB (PIL's
+        "L" of it is taken).  Returns uint8 [B, H, W, 3] on the device."""
+        from . import paste_back as pb
+        dev = self._execution_device
+
+        def rgb(x):
+            if isinstance(x, torch.Tensor):
+                t = x
+            else:
+                xs = x if isinstance(x, (list, tuple)) else [x]
+                if all(hasattr(i, "convert") for i in xs):
+                    t = torch.from_numpy(np.stack([np.array(i.convert("RGB")) for i in xs]))
+                else:
+                    t = torch.from_numpy(np.ascontiguousarray(x))
+            t = t[None] if t.dim() == 3 else t
+            if t.dtype != torch.uint8 or t.dim() != 4 or t.shape[-1] != 3:
+                raise ValueError(f"paste_back: images must be uint8 [H, W, 3] or [B, H, W, 3], got {t.dtype} {tuple(t.shape)}")
+            return t.to(dev).contiguous()
+
+        def grey(x, hw):
+            if isinstance(x, torch.Tensor):
+                t = x
+            else:
+                xs = x if isinstance(x, (list, tuple)) else [x]
+                if all(hasattr(i, "convert") for i in xs):
+                    t = torch.from_numpy(np.stack([pb.grey_of(i) for i in xs]))
+                else:
+                    t = torch.from_numpy(np.ascontiguousarray(x))
+            if t.dtype != torch.uint8:
+                raise ValueError(f"paste_back: the mask must be uint8, got {t.dtype}")
+            t = t.to(dev)
+            if t.dim() == 4 or (t.dim() == 3 and t.shape[-1] == 3 and tuple(t.shape[:2]) == hw):   # RGB mask: PIL's "L" on the device
+                t = ops.rgb_to_grey(t.contiguous())
+            return (t[None] if t.dim() == 2 else t).contiguous()
+
+        original = rgb(original)
+        return pb.paste(original, rgb(edited), grey(mask, tuple(original.shape[1:3])), dilate, feather)
 
     def _generic_loop(self, latents, masked_image_latents, prompt_embeds, pooled, text_ids, latent_image_ids, timesteps,
                       guidance, callback_on_step_end, callback_tensor_inputs, progress_bar):
