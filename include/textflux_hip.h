@@ -502,6 +502,23 @@ int tfx_mask_feather_u8(const void* in, void* out, void* tmp, int32_t B, int32_t
  *      a = 0 gives orig, a = 255 gives edit, and min(orig, edit) <= out <= max(orig, edit).  out may be orig (no other aliasing). */
 int tfx_overlay_u8(const void* orig, const void* edit, const void* alpha, void* out, int32_t B, int32_t H, int32_t W, int32_t C,
                    tfx_stream stream);
+/* ---- colour-matched paste-back (DESIGN.md section 4 "Per-line edits"): a per-channel look-up table, fitted on the host from exact
+ *      moments, takes an edit's colours to those of the unchanged surroundings before the blend.  Added without a new
+ *      TFX_ABI_VERSION: two new entry points, no stamped struct and no existing entry point changes.  Tensors contiguous, batch-major,
+ *      u8 unless said otherwise; B, H, W >= 1, B <= 65535, C in 1..4; integer arithmetic throughout, so the results are exact.
+ * tfx_masked_moments_u8: a, b [B, H, W, C], weight [B, H, W] -> out u64 [B][C][5] = {n, sum a, sum b, sum a a, sum a b} over the pixels
+ *      of the sample whose weight != 0 (n is repeated per channel).  Every sum is 64-bit; no atomics: workgroups write partial sums
+ *      into `scratch`, one finishing workgroup per sample adds them, so the result does not depend on the partition.
+ *      TFX_MASKED_MOMENTS_SCRATCH_BYTES bytes of scratch per sample serve every shape; scratch_bytes < B times that is refused.  out and
+ *      scratch are 8-byte aligned. */
+#define TFX_MASKED_MOMENTS_SCRATCH_BYTES 34816
+int tfx_masked_moments_u8(const void* a, const void* b, const void* weight, void* out, void* scratch, int64_t scratch_bytes, int32_t B,
+                          int32_t H, int32_t W, int32_t C, tfx_stream stream);
+/* tfx_overlay_lut_u8: tfx_overlay_u8 with the edit sent through lut u8 [B][C][256] first:
+ *      out = (orig (255 - a) + lut[b][c][edit] a + 127) / 255 in integer division.  With the identity table it is tfx_overlay_u8 bit
+ *      for bit.  out may be orig (no other aliasing). */
+int tfx_overlay_lut_u8(const void* orig, const void* edit, const void* alpha, const void* lut, void* out, int32_t B, int32_t H, int32_t W,
+                       int32_t C, tfx_stream stream);
 /* out[b, t, col0 + (i*8+j)*4 + py*2+px] = mask[(2ty+py)*8 + i, (2tx+px)*8 + j]  (P:1563-1580: 8x8 pixel blocks -> channels,
  * then _pack_latents), t = ty * (W/16) + tx, row stride ld. */
 int tfx_pack_mask(const void* mask, int32_t mask_dtype, void* out, int32_t B, int32_t H, int32_t W, int32_t mask_batch,

@@ -48,9 +48,13 @@ def use_overshoot_sampler(pipe):
 
 def run_inference(image_input, mask_input, words_input, num_steps=50, guidance_scale=30, seed=42, pipe=None, paste_back=None):
     """paste_back (not in the reference): None, or dict(dilate, feather) -- the result is then blended back into the input image under
-    the dilated and feathered mask and returned at the INPUT's size (FluxFillPipeline.paste_back) instead of at the pipeline's size."""
+    the dilated and feathered mask and returned at the INPUT's size (FluxFillPipeline.paste_back) instead of at the pipeline's size.
+    With per_line=True in it (batch_driver.run_items' keys: region, color_match) the input is the plain scene and its mask: every text
+    line is edited through its own region with a single-line glyph strip and pasted into the scene (textflux_amd/per_line.py)."""
     image = (Image.open(image_input) if isinstance(image_input, str) else image_input).convert("RGB")
     mask = (Image.open(mask_input) if isinstance(mask_input, str) else mask_input).convert("RGB")
+    if paste_back is not None and paste_back.get("per_line"):
+        return run_inference_per_line(image, mask, words_input, num_steps, guidance_scale, seed, pipe, paste_back)[0]
     image_in, mask_in = image, mask
     new_w, new_h = glyph.pipe_size(image)
     image, mask = image.resize((new_w, new_h)), mask.resize((new_w, new_h))
@@ -70,6 +74,17 @@ def run_inference(image_input, mask_input, words_input, num_steps=50, guidance_s
     return Image.fromarray(pasted[0].cpu().numpy())
 
 
+def run_inference_per_line(image, mask, words_input, num_steps, guidance_scale, seed, pipe, paste_back):
+    """-> (the scene with every line pasted in, [each line's raw canvas]): run_inference's per_line path."""
+    from textflux_amd import batch_driver, per_line
+    cfg = batch_driver._paste_back_cfg(paste_back)
+    words = glyph.read_words_from_text(words_input) if isinstance(words_input, str) else list(words_input)
+    pipe = pipe or load_flux_pipeline()
+    if scheduler_name == "overshoot":
+        use_overshoot_sampler(pipe)
+    return per_line.edit_scene(pipe, image, mask, words, cfg, num_inference_steps=num_steps, guidance_scale=guidance_scale, seed=seed)
+
+
 def add_paste_back_args(ap):
     """Not in the reference: paste-back and region editing (textflux_amd/paste_back.py)."""
     ap.add_argument("--paste_back", action="store_true", help="return the ORIGINAL scene at its original size, changed only under the "
@@ -78,15 +93,30 @@ def add_paste_back_args(ap):
     ap.add_argument("--paste_feather", type=int, default=4, metavar="N", help="radius of the three box passes that soften the mask's edge (with --paste_back)")
     ap.add_argument("--paste_region", action="store_true", help="edit only a region cut around the mask, not the whole scene (with --paste_back)")
     ap.add_argument("--paste_region_max", type=int, default=1024, metavar="N", help="longer side the region is edited at (with --paste_region)")
+    ap.add_argument("--paste_per_line", action="store_true", help="edit every text line through a region of its own, with a single-line glyph "
+                    "strip, and paste all of them into the one scene (implies --paste_region; with --paste_back)")
+    ap.add_argument("--paste_color_match", action="store_true", help="match each pasted edit's colours to the original's on a ring just "
+                    "outside the blend (with --paste_back)")
+    ap.add_argument("--paste_color_ring", type=int, default=None, metavar="N", help="width of that ring in pixels, 1..255 (implies "
+                    "--paste_color_match; with --paste_back)")
 
 
 def paste_back_from_args(a):
-    """None, or the paste_back dict of batch_driver.run_items / process_normal_mode."""
+    """None, or the paste_back dict of batch_driver.run_items / process_normal_mode.  The per-line and colour keys appear only when
+    their flags were given."""
     if not a.paste_back:
-        if a.paste_region:
-            raise SystemExit("--paste_region needs --paste_back")
+        for flag in ("paste_region", "paste_per_line", "paste_color_match", "paste_color_ring"):
+            if getattr(a, flag, None) not in (None, False):
+                raise SystemExit(f"--{flag} needs --paste_back")
         return None
-    return dict(dilate=a.paste_dilate, feather=a.paste_feather, region=dict(max_side=a.paste_region_max) if a.paste_region else None)
+    pb = dict(dilate=a.paste_dilate, feather=a.paste_feather, region=dict(max_side=a.paste_region_max) if a.paste_region else None)
+    if getattr(a, "paste_per_line", False):
+        pb["per_line"] = True
+    if getattr(a, "paste_color_ring", None) is not None:
+        pb["color_match"] = dict(ring=a.paste_color_ring)
+    elif getattr(a, "paste_color_match", False):
+        pb["color_match"] = True
+    return pb
 
 
 def add_step_cache_args(ap):
@@ -116,6 +146,19 @@ def process_normal_mode(image_path, mask_path, words_path, steps, guidance_scale
     scene, mask = Image.open(image_path).convert("RGB"), Image.open(mask_path).convert("RGB")
     words = glyph.read_words_from_text(words_path)
     work = None
+    if paste_back is not None and paste_back.get("per_line"):
+        print(f"Using per-line region editing ({len(words)} text lines)")
+        pipe = pipe or load_flux_pipeline()
+        cropped, fulls = run_inference_per_line(scene, mask, words, steps, guidance_scale, seed, pipe, paste_back)
+        os.makedirs(os.path.join(out_dir, "crop"), exist_ok=True)
+        n = 1
+        while os.path.exists(os.path.join(out_dir, f"result_{n:04d}.png")):
+            n += 1
+        for k, full in enumerate(fulls):     # the raw canvases: line 0 under the usual name, line k after it as _line<k>
+            full.save(os.path.join(out_dir, f"result_{n:04d}.png" if k == 0 else f"result_{n:04d}_line{k}.png"))
+        cropped.save(os.path.join(out_dir, "crop", f"crop_{n:04d}.png"))
+        print(f"\nProcessing mode: per-line\nFull Result: {out_dir}/result_{n:04d}.png")
+        return cropped
     if paste_back is not None:
         from textflux_amd import batch_driver
         cfg = batch_driver._paste_back_cfg(paste_back)

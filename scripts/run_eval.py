@@ -79,6 +79,12 @@ def build_parser(lora: bool = False):
     ap.add_argument("--paste_feather", type=int, default=4, metavar="N", help="radius of the three box passes that soften the mask's edge (with --paste_back)")
     ap.add_argument("--paste_region", action="store_true", help="edit only a region cut around the mask, not the whole scene (with --paste_back)")
     ap.add_argument("--paste_region_max", type=int, default=1024, metavar="N", help="longer side the region is edited at (with --paste_region)")
+    ap.add_argument("--paste_per_line", action="store_true", help="edit every text line (every entry of `annotations`; every mask region of "
+                    "an --items entry) through a region of its own and paste all of them into the one scene (implies --paste_region; with --paste_back)")
+    ap.add_argument("--paste_color_match", action="store_true", help="match each pasted edit's colours to the original's on a ring just "
+                    "outside the blend (with --paste_back)")
+    ap.add_argument("--paste_color_ring", type=int, default=None, metavar="N", help="width of that ring in pixels, 1..255 (implies "
+                    "--paste_color_match; with --paste_back)")
     ap.add_argument("--items", type=str, default=None, help="JSON list of {image, mask, text} instead of --json_path")
     ap.add_argument("--out", type=str, default=None, help="output folder of --items mode")
     ap.add_argument("--num_inference_steps", type=int, default=None, help=argparse.SUPPRESS)
@@ -134,12 +140,17 @@ def main(argv=None, lora: bool = False, script: str = __file__):
         raise SystemExit("--step_cache_max_consecutive needs --step_cache THR")
     if a.step_cache is not None and a.mixed_pad > 0:
         raise SystemExit("--step_cache does not serve mixed-geometry batches (--mixed_pad)")
-    if a.paste_region and not a.paste_back:
-        raise SystemExit("--paste_region needs --paste_back")
+    for flag in ("paste_region", "paste_per_line", "paste_color_match", "paste_color_ring"):
+        if getattr(a, flag) not in (None, False) and not a.paste_back:
+            raise SystemExit(f"--{flag} needs --paste_back")
     if a.paste_back and a.mixed_pad > 0:
         raise SystemExit("--paste_back does not serve mixed-geometry batches (--mixed_pad)")
     paste_back = (dict(dilate=a.paste_dilate, feather=a.paste_feather, region=dict(max_side=a.paste_region_max) if a.paste_region else None)
                   if a.paste_back else None)
+    if a.paste_back and a.paste_per_line:
+        paste_back["per_line"] = True
+    if a.paste_back and (a.paste_color_match or a.paste_color_ring is not None):
+        paste_back["color_match"] = True if a.paste_color_ring is None else dict(ring=a.paste_color_ring)
     legacy = a.items is not None
     weights = a.lora_weights_path if lora else a.weights_path
     if not legacy and not (a.json_path and a.original_images_dir and weights):

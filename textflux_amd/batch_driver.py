@@ -51,6 +51,8 @@ class Work:
     orig_scene: Any = None           # paste-back only: the scene as loaded, uint8 [H, W, 3] ...
     orig_mask: Any = None            # ... its RGB mask, uint8 [H, W, 3] ...
     region: Any = None               # ... and the paste_back.Region of it that was edited (the whole image without `region`)
+    parent: Optional[int] = None     # per-line editing only (per_line.py): the index of the item this line belongs to ...
+    line: Optional[int] = None       # ... and the line's position in the item's split order
 
 
 @dataclass
@@ -67,9 +69,11 @@ def eval_item_complete(item: Dict[str, Any]) -> bool:
 
 
 def _paste_back_cfg(paste_back: Dict[str, Any]) -> Dict[str, Any]:
-    """run_items' paste_back argument with its defaults filled in: dict(dilate, feather, region: None | dict(pad, min_side, max_side))."""
+    """run_items' paste_back argument with its defaults filled in: dict(dilate, feather, region: None | dict(pad, min_side, max_side)),
+    and, only when the caller gave them, per_line: True (which implies a region: {} when absent) and color_match: paste_back.
+    color_match_cfg's dict(ring, gain, max_shift, min_pixels)."""
     from . import paste_back as pb
-    unknown = set(paste_back) - {"dilate", "feather", "region"}
+    unknown = set(paste_back) - {"dilate", "feather", "region", "per_line", "color_match"}
     region = paste_back.get("region")
     if region is not None:
         unknown |= {f"region.{k}" for k in set(region) - {"pad", "min_side", "max_side"}}
@@ -81,6 +85,20 @@ def _paste_back_cfg(paste_back: Dict[str, Any]) -> Dict[str, Any]:
         raise ValueError("paste_back: dilate and feather must be in [0, 255]")
     if region is not None:
         cfg["region"] = {k: v for k, v in region.items() if v is not None}
+    per_line, color_match = paste_back.get("per_line"), paste_back.get("color_match")
+    if per_line not in (None, False, True):
+        raise ValueError("paste_back: per_line must be True or False")
+    if per_line:
+        cfg["per_line"] = True
+        if cfg["region"] is None:
+            cfg["region"] = {}
+    if color_match is not None and color_match is not False:
+        if color_match is not True and not isinstance(color_match, dict):
+            raise ValueError("paste_back: color_match must be None, True or a dict")
+        try:
+            cfg["color_match"] = pb.color_match_cfg(color_match)
+        except ValueError as e:
+            raise ValueError(f"paste_back: {e}") from None
     return cfg
 
 
@@ -103,15 +121,17 @@ def _paste_back_inputs(scene, mask, cfg: Dict[str, Any]):
 
 
 def prepare_eval_item(index: int, item: Dict[str, Any], original_images_dir: str, font, text_height_ratio: float = 0.1667,
-                      loader: Optional[Callable] = None, device_compose: bool = False, paste_back: Optional[Dict[str, Any]] = None) -> Work:
+                      loader: Optional[Callable] = None, device_compose: bool = False, paste_back: Optional[Dict[str, Any]] = None,
+                      annotation: int = 0) -> Work:
     """One `annos.json` entry -> Work (scripts/run_eval.py:76-112): scene = original_images_dir / img_name; mask = the first
     annotation's polygon filled white on black; glyph strip of height int(w * text_height_ratio) -- a fraction of the image
     WIDTH -- with the annotation's text, stacked on top with a black mask; pipeline size ((w // 32) * 32,
-    ((h + strip) // 32) * 32); T5 prompt generate_prompt([text])."""
+    ((h + strip) // 32) * 32); T5 prompt generate_prompt([text]).  annotation: which entry of `annotations` (the reference, and
+    every caller but per-line editing, reads the first)."""
     import numpy as np
     from PIL import Image
     load = loader or (lambda p: Image.open(p))
-    ann = item["annotations"][0]
+    ann = item["annotations"][annotation]
     text = ann["text"]
     scene = load(os.path.join(original_images_dir, item["img_name"])).convert("RGB")
     w, h = scene.size
@@ -147,11 +167,17 @@ def prepare_item(index: int, item: Dict[str, Any], loader: Optional[Callable] = 
                                  c.get("text_height_ratio", 0.1667), loader, device_compose, paste_back)
     load = loader or (lambda p: Image.open(p))
     scene, mask = load(item["image"]).convert("RGB"), load(item["mask"]).convert("RGB")
+    return prepare_plain(index, scene, mask, glyph.read_words_from_text(item["text"]), device_compose, paste_back)
+
+
+def prepare_plain(index: int, scene, mask, words: Sequence[str], device_compose: bool = False,
+                  paste_back: Optional[Dict[str, Any]] = None) -> Work:
+    """prepare_item's rule for an {image, mask, text} item whose RGB scene and mask are loaded and whose text is split into words."""
+    from PIL import Image
     extra = {}
     if paste_back is not None:
         scene, mask, so, mo, reg = _paste_back_inputs(scene, mask, paste_back)
         extra = dict(orig_scene=so, orig_mask=mo, region=reg)
-    words = glyph.read_words_from_text(item["text"])
     g, s_, m, horizontal, meta = glyph.compose_parts(scene, mask, words)
     H, W = (s_.shape[0], g.shape[1] + s_.shape[1]) if horizontal else (g.shape[0] + s_.shape[0], s_.shape[1])
     w, h = (W // 32) * 32, (H // 32) * 32
@@ -201,7 +227,8 @@ def _paste_into_original(pipe, w: Work, cropped, cfg: Dict[str, Any]):
     reg = w.region
     oc = w.orig_scene[reg.y0:reg.y1, reg.x0:reg.x1]
     om = pb.grey_of(w.orig_mask[reg.y0:reg.y1, reg.x0:reg.x1])
-    pasted = pipe.paste_back(oc, cropped, om, dilate=cfg["dilate"], feather=cfg["feather"])
+    kw = dict(color_match=cfg["color_match"]) if cfg.get("color_match") else {}      # passed only then: older pipelines keep working
+    pasted = pipe.paste_back(oc, cropped, om, dilate=cfg["dilate"], feather=cfg["feather"], **kw)
     pasted = pasted.cpu().numpy() if isinstance(pasted, torch.Tensor) else np.asarray(pasted)
     out = w.orig_scene.copy()
     out[reg.y0:reg.y1, reg.x0:reg.x1] = pasted.reshape(oc.shape)
@@ -255,6 +282,19 @@ def plan_batches(works: Sequence[Work], batch_size: int, max_pad_fraction: float
     return out
 
 
+def rank_plans(works: Sequence[Work], world: int, batch_size: int, max_pad_fraction: float = 0.0, text_tokens: int = 512,
+               per_line: bool = False) -> List[List[Batch]]:
+    """plans[k][r] = the batch rank k runs in round r; deterministic, so every rank computes all of them.  Batches are dealt
+    round-robin: plans[k] = plan_batches(works)[k::world], i.e. plans[k][r] = plan[r world + k].  per_line: ITEMS are dealt round-robin
+    instead (in order of first appearance of Work.index) and each rank plans the lines of its own items, so all lines of an item run on
+    the rank that pastes them together."""
+    if not per_line:
+        plan = plan_batches(works, batch_size, max_pad_fraction, text_tokens)
+        return [plan[k::world] for k in range(world)]
+    owner = {idx: n % world for n, idx in enumerate(dict.fromkeys(w.index for w in works))}
+    return [plan_batches([w for w in works if owner[w.index] == k], batch_size, max_pad_fraction, text_tokens) for k in range(world)]
+
+
 def _scatter(rows: Optional[List[torch.Tensor]], shape, dtype, device) -> torch.Tensor:
     """Rank 0 passes one tensor per rank, every rank receives its own."""
     world = dist.get_world_size() if dist.is_initialized() else 1
@@ -296,7 +336,13 @@ def run_items(items: Sequence[Dict[str, Any]], pipe, out_dir: Optional[str], bat
     written as <index>.png / written under cropped_images/ / passed as `cropped` to save_full is that scene at its original size, changed
     only near the mask (full_images/ stays the raw canvas).  region: None = the whole scene goes through the pipeline as before;
     dict(pad, min_side, max_side) (paste_back.select_region) = only a region around the mask does, resized to at most max_side, so a
-    large photo costs what its mask's neighbourhood costs.  Not with mixed_pad > 0."""
+    large photo costs what its mask's neighbourhood costs.  Not with mixed_pad > 0.
+    Two more keys, both opt-in (DESIGN.md section 4 "Per-line edits"): per_line=True (implies region, {} when absent) edits every text
+    line of an item -- a connected region of the mask with its line of the text, or an entry of an eval item's `annotations` -- as a
+    single-line item of its own, with its own region, and pastes all of them into the one scene in split order (per_line.py); items
+    are then dealt to the ranks whole, and full_images/ holds line 0's raw canvas under <name>, line k >= 1 under <stem>_line<k><ext>
+    (save_full receives line 0's Work and canvas).  A failing line fails its item.  color_match=True | dict(ring, gain, max_shift,
+    min_pixels) matches each pasted edit's colours to the original's on a ring just outside the blend (paste_back.paste)."""
     if paste_back is not None:       # refused before anything is prepared or encoded
         if mixed_pad > 0:
             raise NotImplementedError("paste_back does not serve mixed-geometry batches (mixed_pad > 0)")
@@ -330,17 +376,26 @@ def _run_items(items, pipe, out_dir, batch_size, num_inference_steps, guidance_s
                                       "in the fused Euler step (the AMO sampler's are per step); use mixed_pad=0")
     rank = dist.get_rank() if dist.is_initialized() else 0
     world = dist.get_world_size() if dist.is_initialized() else 1
+    per_line = bool(paste_back and paste_back.get("per_line"))
     works, failed = [], []
+    lines: Dict[int, List[Work]] = {}        # per_line: item index -> its lines in split order; results[item][line] = (canvas, crop)
+    results: Dict[int, Dict[int, Any]] = {}
     for i, it in enumerate(items):
         try:
-            works.append(prepare_item(i, it, loader, device_compose=bool(getattr(pipe, "supports_device_compose", False)),
-                                      eval_cfg=eval_cfg, **({} if paste_back is None else dict(paste_back=paste_back))))
+            device_compose = bool(getattr(pipe, "supports_device_compose", False))
+            if per_line:
+                from . import per_line as pl
+                lines[i] = pl.prepare_lines(i, it, loader, device_compose, eval_cfg, paste_back)
+                works.extend(lines[i])
+            else:
+                works.append(prepare_item(i, it, loader, device_compose=device_compose,
+                                          eval_cfg=eval_cfg, **({} if paste_back is None else dict(paste_back=paste_back))))
         except Exception as e:       # per-item failures do not stop the run (reference :195-198)
             failed.append(i)
             if rank == 0:
                 print(f"item {i} failed in preparation: {e}")
-    plan = plan_batches(works, batch_size, mixed_pad, text_tokens=max_sequence_length)
-    rounds = (len(plan) + world - 1) // world
+    plans = rank_plans(works, world, batch_size, mixed_pad, max_sequence_length, per_line)
+    rounds = max(len(p) for p in plans)
     if encode == "auto":
         has_t5 = 1 if (getattr(pipe, "text_encoder_2", None) is not None or getattr(pipe, "encodes_locally", False)) else 0
         encode = "local" if _flag_min(has_t5, device) == 1 else "rank0"
@@ -377,7 +432,7 @@ def _run_items(items, pipe, out_dir, batch_size, num_inference_steps, guidance_s
         tdist._ran("broadcast")
     done: List[int] = []
     for r in range(rounds):
-        mine = plan[r * world + rank] if r * world + rank < len(plan) else None
+        mine = plans[rank][r] if r < len(plans[rank]) else None
         pe_mine, enc_ok = None, True
         if encode == "rank0":
             # ---- rank 0 encodes the T5 prompts of every rank's batch of this round (padded to batch_size rows, one more row
@@ -386,7 +441,7 @@ def _run_items(items, pipe, out_dir, batch_size, num_inference_steps, guidance_s
             if rank == 0:
                 rows = []
                 for k in range(world):
-                    b = plan[r * world + k] if r * world + k < len(plan) else None
+                    b = plans[k][r] if r < len(plans[k]) else None
                     buf = torch.zeros(batch_size + 1, T, J, dtype=dtype, device=device)
                     buf[batch_size, 0, 0] = 1
                     if b is not None:
@@ -397,7 +452,7 @@ def _run_items(items, pipe, out_dir, batch_size, num_inference_steps, guidance_s
                             buf[:len(prompts)] = pe.to(dtype)
                         except Exception as e:
                             buf[batch_size, 0, 0] = 0
-                            print(f"[rank 0] encoding the prompts of batch {r * world + k} failed: {e}")
+                            print(f"[rank 0] encoding the prompts of rank {k}'s batch of round {r} failed: {e}")
                     rows.append(buf)
             got = _scatter(rows, (batch_size + 1, T, J), dtype, device)
             pe_mine, enc_ok = got[:batch_size], bool(float(got[batch_size, 0, 0]) != 0)
@@ -435,6 +490,23 @@ def _run_items(items, pipe, out_dir, batch_size, num_inference_steps, guidance_s
                 steps_skipped += sum(1 for r_ in rep if r_["skipped"])
             for w, img, bx in zip(mine.items, images, boxes):
                 cropped = img if kw else img.crop(bx)
+                if per_line:         # kept until the item's last line is in; then all of them are pasted into the one scene
+                    got = results.setdefault(w.index, {})
+                    got[w.line] = (img, cropped)
+                    if w.index in failed or len(got) < len(lines[w.index]):
+                        continue
+                    try:
+                        from . import per_line as pl
+                        ws = lines[w.index]
+                        pasted = pl.compose_lines(pipe, ws, [got[x.line][1] for x in ws], paste_back)
+                        pl.write_item(ws, [got[x.line][0] for x in ws], pasted, out_dir, save, save_full)
+                        done.append(w.index)
+                    except Exception as e:
+                        failed.append(w.index)
+                        print(f"[rank {rank}] pasting the {len(lines[w.index])} lines of item {w.index} failed: {e}")
+                    finally:
+                        del results[w.index]
+                    continue
                 if paste_back is not None:
                     cropped = _paste_into_original(pipe, w, cropped, paste_back)
                 if w.name is not None and (save_full is not None or (save is None and out_dir is not None)):
@@ -449,10 +521,10 @@ def _run_items(items, pipe, out_dir, batch_size, num_inference_steps, guidance_s
                     cropped.save(os.path.join(out_dir, f"{w.index:06d}.png"))
                 done.append(w.index)
         except Exception as e:
-            failed.extend(w.index for w in mine.items)
+            failed.extend([i for i in dict.fromkeys(w.index for w in mine.items) if not (per_line and (i in failed or i in done))])
             print(f"[rank {rank}] batch of {n} at {mine.size} failed: {e}")
     # ---- summary on rank 0
-    res: Dict[str, Any] = {"done": done, "failed": failed, "batches": len(plan), "rounds": rounds, "encode": encode}
+    res: Dict[str, Any] = {"done": done, "failed": failed, "batches": sum(len(p) for p in plans), "rounds": rounds, "encode": encode}
     if count_steps:
         res["steps_skipped"], res["steps_total"] = steps_skipped, steps_total
     if grouped:

@@ -402,6 +402,17 @@ int tfx_overlay_u8(const void* orig, const void* edit, const void* alpha, void* 
   if (!orig || !edit || !alpha || !out) return fail("tfx_overlay_u8: null pointer");
   return overlay_u8(orig, edit, alpha, out, B, H, W, C, S(stream));
 }
+static_assert(TFX_MASKED_MOMENTS_SCRATCH_BYTES == MASKED_MOMENTS_SCRATCH_BYTES, "the header's scratch bound is the kernels'");
+int tfx_masked_moments_u8(const void* a, const void* b, const void* weight, void* out, void* scratch, int64_t scratch_bytes, int32_t B,
+                          int32_t H, int32_t W, int32_t C, tfx_stream stream) {
+  if (!a || !b || !weight || !out || !scratch) return fail("tfx_masked_moments_u8: null pointer");
+  return masked_moments_u8(a, b, weight, out, scratch, scratch_bytes, B, H, W, C, S(stream));
+}
+int tfx_overlay_lut_u8(const void* orig, const void* edit, const void* alpha, const void* lut, void* out, int32_t B, int32_t H, int32_t W,
+                       int32_t C, tfx_stream stream) {
+  if (!orig || !edit || !alpha || !lut || !out) return fail("tfx_overlay_lut_u8: null pointer");
+  return overlay_lut_u8(orig, edit, alpha, lut, out, B, H, W, C, S(stream));
+}
 int tfx_pack_mask(const void* mask, int32_t mask_dtype, void* out, int32_t B, int32_t H, int32_t W, int32_t mask_batch,
                   int32_t binarize, int64_t ld, int32_t col0, tfx_stream stream) {
   if (!mask || !out) return fail("tfx_pack_mask: null pointer");

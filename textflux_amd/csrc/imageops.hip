@@ -398,6 +398,135 @@ __global__ __launch_bounds__(256) void overlay_u8_kernel(const uint8_t* orig, co
   out[i] = (uint8_t)((orig[i] * (255u - a) + edit[i] * a + 127u) / 255u);
 }
 
+// ---- colour-matched paste-back (DESIGN.md section 4 "Per-line edits"): the moments a per-channel linear fit needs, and the blend
+// through the fitted look-up table.  Integer arithmetic only, every sum in 64 bits: exact, whatever the partition.
+constexpr int kMomentVals = 17;                      // n, then (sum a, sum b, sum a a, sum a b) per channel, C <= 4
+constexpr int kMomentParts = 256;                    // workgroups per sample at the most: the finishing workgroup has one thread for each
+static_assert((int64_t)kMomentParts * kMomentVals * 8 == MASKED_MOMENTS_SCRATCH_BYTES, "launch.h and the kernel disagree on the scratch bound");
+
+__device__ __forceinline__ uint64_t wave_sum_u64(uint64_t v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const uint32_t lo = __shfl_xor((uint32_t)v, o, 64), hi = __shfl_xor((uint32_t)(v >> 32), o, 64);
+    v += ((uint64_t)hi << 32) | lo;
+  }
+  return v;
+}
+// The workgroup's sum of each of the NV values its 256 threads hold: dst[k] = sum over the threads of acc[k] (plain stores).
+template <int NV>
+__device__ __forceinline__ void block_sum_u64(const uint64_t (&acc)[NV], uint64_t* __restrict__ dst) {
+  __shared__ uint64_t red[4][NV];
+  const int tid = threadIdx.x;
+#pragma unroll
+  for (int k = 0; k < NV; ++k) {
+    const uint64_t s = wave_sum_u64(acc[k]);
+    if ((tid & 63) == 0) red[tid >> 6][k] = s;
+  }
+  __syncthreads();
+  if (tid < NV) dst[tid] = (red[0][tid] + red[1][tid]) + (red[2][tid] + red[3][tid]);
+}
+// partials[b][part][0 .. 4 C] over the pixels of sample b with weight != 0 that workgroup `part` walks, four consecutive pixels per
+// thread and step.  VEC (H W a multiple of 4 and every base pointer 4-byte aligned): the four weights are one 32-bit load and the
+// 4 C bytes of a and of b are C 32-bit loads each; else byte loads, the last group cut at H W.
+template <int C, bool VEC>
+__global__ __launch_bounds__(256) void masked_moments_kernel(const uint8_t* __restrict__ a, const uint8_t* __restrict__ b,
+                                                             const uint8_t* __restrict__ weight, uint64_t* __restrict__ partials, int64_t hw) {
+  const int s = blockIdx.y;
+  a += (int64_t)s * hw * C; b += (int64_t)s * hw * C; weight += (int64_t)s * hw;
+  uint64_t acc[1 + 4 * C];
+#pragma unroll
+  for (int k = 0; k < 1 + 4 * C; ++k) acc[k] = 0;
+  const int64_t groups = (hw + 3) / 4;
+  for (int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x; g < groups; g += (int64_t)gridDim.x * 256) {
+    const int64_t p0 = g * 4;
+    uint8_t wv[4], av[4 * C], bv[4 * C];
+    if constexpr (VEC) {
+      const uint32_t w4 = *reinterpret_cast<const uint32_t*>(weight + p0);
+      if (w4 == 0) continue;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) wv[j] = (uint8_t)(w4 >> (8 * j));
+#pragma unroll
+      for (int q = 0; q < C; ++q) {
+        const uint32_t a4 = *reinterpret_cast<const uint32_t*>(a + p0 * C + 4 * q), b4 = *reinterpret_cast<const uint32_t*>(b + p0 * C + 4 * q);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) { av[4 * q + j] = (uint8_t)(a4 >> (8 * j)); bv[4 * q + j] = (uint8_t)(b4 >> (8 * j)); }
+      }
+    } else {
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const bool in = p0 + j < hw;
+        wv[j] = in ? weight[p0 + j] : (uint8_t)0;
+#pragma unroll
+        for (int c = 0; c < C; ++c) {
+          av[j * C + c] = wv[j] ? a[(p0 + j) * C + c] : (uint8_t)0;
+          bv[j * C + c] = wv[j] ? b[(p0 + j) * C + c] : (uint8_t)0;
+        }
+      }
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      if (!wv[j]) continue;
+      acc[0] += 1;
+#pragma unroll
+      for (int c = 0; c < C; ++c) {
+        const uint32_t x = av[j * C + c], y = bv[j * C + c];
+        acc[1 + 4 * c] += x; acc[2 + 4 * c] += y; acc[3 + 4 * c] += x * x; acc[4 + 4 * c] += x * y;
+      }
+    }
+  }
+  block_sum_u64<1 + 4 * C>(acc, partials + ((int64_t)s * gridDim.x + blockIdx.x) * kMomentVals);
+}
+// One 256-thread workgroup per sample: thread t holds partial t (zeros beyond `parts` <= 256); out[b][c] = {n, sum a, sum b, sum a a, sum a b}.
+template <int C>
+__global__ __launch_bounds__(256) void masked_moments_finish_kernel(const uint64_t* __restrict__ partials, uint64_t* __restrict__ out, int parts) {
+  const int s = blockIdx.x, tid = threadIdx.x;
+  uint64_t acc[1 + 4 * C];
+#pragma unroll
+  for (int k = 0; k < 1 + 4 * C; ++k) acc[k] = tid < parts ? partials[((int64_t)s * parts + tid) * kMomentVals + k] : 0;
+  __shared__ uint64_t tot[1 + 4 * C];
+  block_sum_u64<1 + 4 * C>(acc, tot);
+  __syncthreads();
+  if (tid < 5 * C) {
+    const int c = tid / 5, k = tid - 5 * c;
+    out[((int64_t)s * C + c) * 5 + k] = k == 0 ? tot[0] : tot[4 * c + k];
+  }
+}
+
+// out = (orig (255 - a) + lut[b][c][edit] a + 127) / 255: overlay_u8_kernel with the edit's byte sent through the table of its sample
+// and channel, which the workgroup keeps in LDS (256 C bytes).  n = H W C bytes per sample.  VEC (n a multiple of 4, orig / edit / out
+// 4-byte aligned): four consecutive bytes per thread and step, one 32-bit load of orig and of edit and one 32-bit store.  out may be
+// orig: a thread reads the bytes it writes, and no others.
+template <bool VEC>
+__global__ __launch_bounds__(256) void overlay_lut_u8_kernel(const uint8_t* orig, const uint8_t* __restrict__ edit, const uint8_t* __restrict__ alpha,
+                                                             const uint8_t* __restrict__ lut, uint8_t* out, int64_t n, int C) {
+  __shared__ uint8_t tab[4 * 256];
+  const int s = blockIdx.y;
+  for (int k = threadIdx.x; k < 256 * C; k += 256) tab[k] = lut[(int64_t)s * 256 * C + k];
+  __syncthreads();
+  orig += s * n; edit += s * n; out += s * n; alpha += s * (n / C);
+  if constexpr (VEC) {
+    for (int64_t i = ((int64_t)blockIdx.x * 256 + threadIdx.x) * 4; i < n; i += (int64_t)gridDim.x * 1024) {
+      const uint32_t o4 = *reinterpret_cast<const uint32_t*>(orig + i), e4 = *reinterpret_cast<const uint32_t*>(edit + i);
+      int64_t pix = i / C;
+      int c = (int)(i - pix * C);
+      uint32_t r4 = 0;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const unsigned al = alpha[pix], o = (o4 >> (8 * j)) & 255u, e = tab[c * 256 + ((e4 >> (8 * j)) & 255u)];
+        r4 |= ((o * (255u - al) + e * al + 127u) / 255u) << (8 * j);
+        if (++c == C) { c = 0; ++pix; }
+      }
+      *reinterpret_cast<uint32_t*>(out + i) = r4;
+    }
+  } else {
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
+      const int64_t pix = i / C;
+      const unsigned al = alpha[pix], e = tab[(int)(i - pix * C) * 256 + edit[i]];
+      out[i] = (uint8_t)((orig[i] * (255u - al) + e * al + 127u) / 255u);
+    }
+  }
+}
+
 int compose_canvas(const void* glyph, const void* scene, const void* smask, void* canvas, void* cmask, int B, int gh, int gw, int sh,
                    int sw, int dir, int mask_rgb, hipStream_t st) {
   if (dir != 0 && dir != 1) return fail("compose_canvas: direction 0 (vertical) or 1 (horizontal)");
@@ -469,6 +598,57 @@ int overlay_u8(const void* orig, const void* edit, const void* alpha, void* out,
   if (n > kMaxBytes) return fail("overlay_u8: more than 2^38 bytes");
   overlay_u8_kernel<<<blocks_for(n), 256, 0, st>>>((const uint8_t*)orig, (const uint8_t*)edit, (const uint8_t*)alpha, (uint8_t*)out, n, C);
   return check_launch("overlay_u8");
+}
+
+static inline bool aligned4(const void* p) { return ((uintptr_t)p & 3) == 0; }
+
+template <int C>
+static void masked_moments_launch(const uint8_t* a, const uint8_t* b, const uint8_t* w, uint64_t* out, uint64_t* scratch, int B, int64_t hw,
+                                  hipStream_t st) {
+  const int64_t groups = (hw + 3) / 4;
+  const int parts = (int)(groups >= 256ll * kMomentParts ? kMomentParts : (groups + 255) / 256);
+  if (hw % 4 == 0 && aligned4(a) && aligned4(b) && aligned4(w)) masked_moments_kernel<C, true><<<dim3(parts, B), 256, 0, st>>>(a, b, w, scratch, hw);
+  else masked_moments_kernel<C, false><<<dim3(parts, B), 256, 0, st>>>(a, b, w, scratch, hw);
+  masked_moments_finish_kernel<C><<<B, 256, 0, st>>>(scratch, out, parts);
+}
+
+int masked_moments_u8(const void* a, const void* b, const void* weight, void* out, void* scratch, int64_t scratch_bytes, int B, int H, int W,
+                      int C, hipStream_t st) {
+  if (B < 1 || H < 1 || W < 1) return fail("masked_moments_u8: B, H, W must be at least 1");
+  if (C < 1 || C > 4) return fail("masked_moments_u8: 1..4 channels");
+  if (B > 65535) return fail("masked_moments_u8: batch %d exceeds 65535", B);
+  if ((int64_t)H * W * C > kMaxBytes) return fail("masked_moments_u8: more than 2^38 bytes per sample");
+  if (scratch_bytes < (int64_t)B * MASKED_MOMENTS_SCRATCH_BYTES)
+    return fail("masked_moments_u8: scratch of %lld bytes, needs %lld per sample", (long long)scratch_bytes, (long long)MASKED_MOMENTS_SCRATCH_BYTES);
+  if (((uintptr_t)out | (uintptr_t)scratch) & 7) return fail("masked_moments_u8: out and scratch must be 8-byte aligned");
+  const uint8_t *pa = (const uint8_t*)a, *pb = (const uint8_t*)b, *pw = (const uint8_t*)weight;
+  uint64_t *po = (uint64_t*)out, *ps = (uint64_t*)scratch;
+  const int64_t hw = (int64_t)H * W;
+  switch (C) {
+    case 1: masked_moments_launch<1>(pa, pb, pw, po, ps, B, hw, st); break;
+    case 2: masked_moments_launch<2>(pa, pb, pw, po, ps, B, hw, st); break;
+    case 3: masked_moments_launch<3>(pa, pb, pw, po, ps, B, hw, st); break;
+    default: masked_moments_launch<4>(pa, pb, pw, po, ps, B, hw, st); break;
+  }
+  return check_launch("masked_moments_u8");
+}
+
+int overlay_lut_u8(const void* orig, const void* edit, const void* alpha, const void* lut, void* out, int B, int H, int W, int C, hipStream_t st) {
+  if (B < 1 || H < 1 || W < 1) return fail("overlay_lut_u8: B, H, W must be at least 1");
+  if (C < 1 || C > 4) return fail("overlay_lut_u8: 1..4 channels");
+  if (B > 65535) return fail("overlay_lut_u8: batch %d exceeds 65535", B);
+  if (edit == out || alpha == out || lut == out) return fail("overlay_lut_u8: out may alias orig only");
+  const int64_t n = (int64_t)H * W * C;
+  if (n > kMaxBytes) return fail("overlay_lut_u8: more than 2^38 bytes per sample");
+  const bool vec = n % 4 == 0 && aligned4(orig) && aligned4(edit) && aligned4(out);
+  const int64_t per_block = vec ? 1024 : 256;
+  const int64_t want = (n + per_block - 1) / per_block;
+  const unsigned grid = (unsigned)(want > 4096 ? 4096 : want);      // grid-stride beyond: the table is loaded once per workgroup
+  if (vec) overlay_lut_u8_kernel<true><<<dim3(grid, B), 256, 0, st>>>((const uint8_t*)orig, (const uint8_t*)edit, (const uint8_t*)alpha,
+                                                                      (const uint8_t*)lut, (uint8_t*)out, n, C);
+  else overlay_lut_u8_kernel<false><<<dim3(grid, B), 256, 0, st>>>((const uint8_t*)orig, (const uint8_t*)edit, (const uint8_t*)alpha,
+                                                                   (const uint8_t*)lut, (uint8_t*)out, n, C);
+  return check_launch("overlay_lut_u8");
 }
 
 int pack_mask(const void* mask, int mask_dtype, void* out, int B, int H, int W, int mask_b, int binarize, int64_t ld, int col0,

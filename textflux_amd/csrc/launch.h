@@ -210,6 +210,12 @@ int resample_u8(const void* in, void* out, const int* bounds, const int* coeffs,
 int mask_dilate_u8(const void* in, void* out, void* tmp, int B, int H, int W, int radius, hipStream_t st);
 int mask_feather_u8(const void* in, void* out, void* tmp, int B, int H, int W, int radius, hipStream_t st);
 int overlay_u8(const void* orig, const void* edit, const void* alpha, void* out, int B, int H, int W, int C, hipStream_t st);
+// colour-matched paste-back: out u64 [B][C][5] = {n, sum a, sum b, sum a a, sum a b} over the pixels with weight != 0 (scratch: partial
+// sums of up to 256 workgroups per sample, 17 u64 each), and the blend with the edit sent through lut u8 [B][C][256]
+constexpr int64_t MASKED_MOMENTS_SCRATCH_BYTES = 256 * 17 * 8;   // per sample
+int masked_moments_u8(const void* a, const void* b, const void* weight, void* out, void* scratch, int64_t scratch_bytes, int B, int H, int W,
+                      int C, hipStream_t st);
+int overlay_lut_u8(const void* orig, const void* edit, const void* alpha, const void* lut, void* out, int B, int H, int W, int C, hipStream_t st);
 int pack_mask(const void* mask, int mask_dtype, void* out, int B, int H, int W, int mask_b, int binarize, int64_t ld, int col0,
               hipStream_t st);
 int sample_pack(const void* moments, const void* eps, int eps_dtype, void* out, int B, int h, int w, int L, float shift,

@@ -724,6 +724,50 @@ def overlay(orig: torch.Tensor, edit: torch.Tensor, alpha: torch.Tensor, out: Op
     return out
 
 
+MASKED_MOMENTS_SCRATCH_BYTES = 34816     # include/textflux_hip.h: TFX_MASKED_MOMENTS_SCRATCH_BYTES, per sample
+
+
+def masked_moments(a: torch.Tensor, b: torch.Tensor, weight: torch.Tensor) -> torch.Tensor:
+    """int64 [B, C, 5] = (n, sum a, sum b, sum a a, sum a b) per sample and channel over the pixels whose weight is not 0, of uint8 images
+    a, b [B, H, W, C] (C in 1..4) under a uint8 weight [B, H, W] (tfx_masked_moments_u8).  Exact: integer sums, 64-bit throughout."""
+    _chk_dev(a, b, weight)
+    for t in (a, b, weight):
+        if t.dtype != torch.uint8 or not t.is_contiguous():
+            raise ValueError("masked_moments: a, b and weight must be contiguous uint8 tensors")
+    if a.dim() != 4 or a.numel() == 0 or not 1 <= a.shape[3] <= 4 or b.shape != a.shape or weight.shape != a.shape[:3]:
+        raise ValueError(f"masked_moments: a / b [B, H, W, C <= 4] and weight [B, H, W] must agree, got {tuple(a.shape)}, {tuple(b.shape)}, "
+                         f"{tuple(weight.shape)}")
+    B, H, W, Cc = a.shape
+    out = torch.empty(B, Cc, 5, dtype=torch.int64, device=a.device)
+    scratch = torch.empty(B * MASKED_MOMENTS_SCRATCH_BYTES // 8, dtype=torch.int64, device=a.device)
+    L.check(L.lib().tfx_masked_moments_u8(a.data_ptr(), b.data_ptr(), weight.data_ptr(), out.data_ptr(), scratch.data_ptr(),
+                                          scratch.numel() * 8, B, H, W, Cc, _stream()), "masked_moments")
+    return out
+
+
+def overlay_lut(orig: torch.Tensor, edit: torch.Tensor, alpha: torch.Tensor, lut: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """ops.overlay with the edit sent through a per-sample, per-channel table first: (orig (255 - alpha) + lut[b, c, edit] alpha + 127) // 255
+    of uint8 images [B, H, W, C] (C in 1..4) under a uint8 alpha [B, H, W], lut uint8 [B, C, 256] (tfx_overlay_lut_u8).
+    out: None (a new tensor) or `orig` itself."""
+    _chk_dev(orig, edit, alpha, lut, out)
+    for t in (orig, edit, alpha, lut):
+        if t.dtype != torch.uint8 or not t.is_contiguous():
+            raise ValueError("overlay_lut: orig, edit, alpha and lut must be contiguous uint8 tensors")
+    if orig.dim() != 4 or orig.numel() == 0 or not 1 <= orig.shape[3] <= 4 or edit.shape != orig.shape or alpha.shape != orig.shape[:3]:
+        raise ValueError(f"overlay_lut: orig / edit [B, H, W, C <= 4] and alpha [B, H, W] must agree, got {tuple(orig.shape)}, "
+                         f"{tuple(edit.shape)}, {tuple(alpha.shape)}")
+    B, H, W, Cc = orig.shape
+    if tuple(lut.shape) != (B, Cc, 256):
+        raise ValueError(f"overlay_lut: lut must be [{B}, {Cc}, 256], got {tuple(lut.shape)}")
+    if out is None:
+        out = torch.empty_like(orig)
+    elif out.shape != orig.shape or out.dtype != torch.uint8 or not out.is_contiguous():
+        raise ValueError("overlay_lut: out must be a contiguous uint8 tensor of orig's shape")
+    L.check(L.lib().tfx_overlay_lut_u8(orig.data_ptr(), edit.data_ptr(), alpha.data_ptr(), lut.data_ptr(), out.data_ptr(), B, H, W, Cc,
+                                       _stream()), "overlay_lut")
+    return out
+
+
 def pack_mask(mask: torch.Tensor, out: torch.Tensor, col0: int, B: int, H: int, W: int, binarize: bool = True) -> torch.Tensor:
     """out[b, :, col0 : col0 + 256] = packed mask (out: [B, S, ld] bf16)."""
     _chk_dev(mask, out)

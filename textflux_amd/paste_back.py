@@ -12,6 +12,13 @@ return the VAE round trip of the whole canvas.  The arithmetic here is this proj
 The feather's support grows by at most 3 r per axis, so alpha is 0 outside the mask dilated by d + 3 r; with d >= 3 r every
 original mask pixel has alpha = 255 (the seam lies outside the edited text).  The defaults satisfy that; they are a starting
 point, not a tuned value.
+
+Colour matching (opt-in, paste(color_match=...); DESIGN.md section 4 "Per-line edits"): before the blend the edit goes through a per-channel
+look-up table, the least-squares line from the edit's colours to the original's on a ring just outside alpha's support:
+
+    moments = (n, sum a, sum b, sum a a, sum a b) over ring_mask(alpha)    ops.masked_moments (exact 64-bit integer sums)
+    lut     = fit_luts(moments)                                            host, Python integers up to the division
+    out     = (orig (255 - alpha) + lut[edit] alpha + 127) // 255          ops.overlay_lut
 """
 from __future__ import annotations
 
@@ -95,19 +102,96 @@ def alpha_mask(mask_grey: torch.Tensor, dilate: int = DILATE, feather: int = FEA
     return ops.mask_feather(ops.mask_dilate(binary, dilate), feather)
 
 
-def paste(original: torch.Tensor, edited: torch.Tensor, mask_grey: torch.Tensor, dilate: int = DILATE, feather: int = FEATHER) -> torch.Tensor:
+# Colour matching (DESIGN.md section 4 "Per-line edits"): the ring's width, the clamps of the fitted gain and of a table entry's shift,
+# and the fewest ring pixels a fit is trusted with.  A starting point, not a tuned value and no quality claim.
+RING, GAIN, MAX_SHIFT, MIN_PIXELS = 24, (0.8, 1.25), 32, 256
+
+
+def color_match_cfg(color_match) -> dict:
+    """paste's color_match argument (True or a dict of ring, gain, max_shift, min_pixels) with its defaults filled in and checked."""
+    cm = {} if color_match is True else dict(color_match)
+    unknown = set(cm) - {"ring", "gain", "max_shift", "min_pixels"}
+    if unknown:
+        raise ValueError(f"color_match: unknown keys {sorted(unknown)}")
+    ring = RING if cm.get("ring") is None else int(cm["ring"])
+    gain = GAIN if cm.get("gain") is None else (float(cm["gain"][0]), float(cm["gain"][1]))
+    max_shift = MAX_SHIFT if cm.get("max_shift") is None else int(cm["max_shift"])
+    min_pixels = MIN_PIXELS if cm.get("min_pixels") is None else int(cm["min_pixels"])
+    if not 1 <= ring <= 255:
+        raise ValueError("color_match: ring must be in [1, 255]")
+    if not 0 < gain[0] <= gain[1]:
+        raise ValueError("color_match: gain must be (lo, hi) with 0 < lo <= hi")
+    if not 0 <= max_shift <= 255 or min_pixels < 1:
+        raise ValueError("color_match: max_shift must be in [0, 255] and min_pixels at least 1")
+    return dict(ring=ring, gain=gain, max_shift=max_shift, min_pixels=min_pixels)
+
+
+def ring_mask(alpha: torch.Tensor, ring: int = RING) -> torch.Tensor:
+    """uint8 [B, H, W] blend weight -> 255 on the pixels within `ring` (square window) of alpha's support that are not in it, else 0:
+    support = 255 where alpha > 0, ring = mask_dilate(support, ring) with the support's own pixels cleared.  These pixels lie just
+    outside the blend, where the edit shows unchanged scene content."""
+    if alpha.dtype != torch.uint8 or alpha.dim() != 3:
+        raise ValueError(f"ring_mask: alpha must be uint8 [B, H, W], got {alpha.dtype} {tuple(alpha.shape)}")
+    if not 1 <= int(ring) <= 255:
+        raise ValueError(f"ring_mask: ring must be in [1, 255], got {ring}")
+    support = (alpha > 0).to(torch.uint8).mul_(255).contiguous()
+    return ops.mask_dilate(support, int(ring)).masked_fill_(support > 0, 0)
+
+
+def fit_luts(moments, gain: Tuple[float, float] = GAIN, max_shift: int = MAX_SHIFT, min_pixels: int = MIN_PIXELS) -> np.ndarray:
+    """moments int [B, C, 5] = (n, sum a, sum b, sum a a, sum a b) with a the edit and b the colour reference (ops.masked_moments) ->
+    uint8 [B, C, 256] tables t with t[a] ~ b, the least-squares line b = g a + o per (sample, channel), on the host:
+    den = n sum aa - (sum a)^2 in Python integers; the identity table when n < min_pixels or den <= 0; else
+    g = (n sum ab - sum a sum b) / den clamped to `gain`, o = (sum b - g sum a) / n in float64, and
+    t[v] = floor(g v + o + 0.5) clamped to [v - max_shift, v + max_shift], then to [0, 255]."""
+    m = moments.cpu().numpy() if isinstance(moments, torch.Tensor) else np.asarray(moments)
+    if m.ndim != 3 or m.shape[2] != 5:
+        raise ValueError(f"fit_luts: moments must be [B, C, 5], got {m.shape}")
+    v = np.arange(256, dtype=np.float64)
+    ident = np.arange(256, dtype=np.int64)
+    out = np.empty(m.shape[:2] + (256,), np.uint8)
+    for b in range(m.shape[0]):
+        for c in range(m.shape[1]):
+            n, sa, sb, saa, sab = (int(x) for x in m[b, c])
+            den = n * saa - sa * sa
+            if n < min_pixels or den <= 0:
+                out[b, c] = ident
+                continue
+            g = min(max((n * sab - sa * sb) / den, float(gain[0])), float(gain[1]))
+            o = (sb - g * sa) / n
+            t = np.floor(g * v + o + 0.5).astype(np.int64)
+            t = np.minimum(np.maximum(t, ident - int(max_shift)), ident + int(max_shift))
+            out[b, c] = np.clip(t, 0, 255)
+    return out
+
+
+def paste(original: torch.Tensor, edited: torch.Tensor, mask_grey: torch.Tensor, dilate: int = DILATE, feather: int = FEATHER,
+          color_match=None, color_ref: Optional[torch.Tensor] = None) -> torch.Tensor:
     """original uint8 [B, H, W, 3], edited uint8 [B, h, w, 3], mask_grey uint8 [B, H, W], all on the device -> [B, H, W, 3]: the edit,
     resampled to (H, W) when its size differs (ops.resample_u8: Pillow's bicubic), blended over the original under alpha_mask computed at
     the ORIGINAL resolution.  Outside the mask dilated by dilate + 3 feather the result is the original byte for byte; with
-    dilate >= 3 feather it is the resampled edit on every mask pixel."""
+    dilate >= 3 feather it is the resampled edit on every mask pixel.
+    color_match: None, or True / dict(ring, gain, max_shift, min_pixels): the resampled edit goes through a per-channel table fitted
+    (fit_luts) on the ring just outside the blend (ring_mask) to the colours of color_ref (uint8 [B, H, W, 3]; None: `original`) before
+    it is blended (ops.overlay_lut).  The alpha is the same, so the bytes outside the grown mask are still the original's."""
     if original.dtype != torch.uint8 or original.dim() != 4 or edited.dtype != torch.uint8 or edited.dim() != 4:
         raise ValueError("paste: original and edited must be uint8 [B, H, W, C]")
     if edited.shape[0] != original.shape[0] or edited.shape[3] != original.shape[3] or mask_grey.shape != original.shape[:3]:
         raise ValueError(f"paste: original {tuple(original.shape)}, edited {tuple(edited.shape)} and mask {tuple(mask_grey.shape)} do not agree")
+    if color_match is None and color_ref is not None:
+        raise ValueError("paste: color_ref needs color_match")
     original, edited = original.contiguous(), edited.contiguous()
     if edited.shape[1:3] != original.shape[1:3]:
         edited = ops.resample_u8(edited, (original.shape[1], original.shape[2]))
-    return ops.overlay(original, edited, alpha_mask(mask_grey.contiguous(), dilate, feather))
+    alpha = alpha_mask(mask_grey.contiguous(), dilate, feather)
+    if color_match is None:
+        return ops.overlay(original, edited, alpha)
+    cm = color_match_cfg(color_match)
+    ref = original if color_ref is None else color_ref.contiguous()
+    if ref.shape != original.shape or ref.dtype != torch.uint8:
+        raise ValueError(f"paste: color_ref must be uint8 of original's shape {tuple(original.shape)}, got {ref.dtype} {tuple(ref.shape)}")
+    luts = fit_luts(ops.masked_moments(edited, ref, ring_mask(alpha, cm["ring"])), cm["gain"], cm["max_shift"], cm["min_pixels"])
+    return ops.overlay_lut(original, edited, alpha, torch.from_numpy(luts).to(original.device))
 
 
 def grey_of(mask) -> np.ndarray:

@@ -588,12 +588,14 @@ class FluxFillPipeline:
         return self
 
     # ------------------------------------------------------------------ paste-back (DESIGN.md section 4 "Paste-back")
-    def paste_back(self, original, edited, mask, dilate: int = 16, feather: int = 4) -> torch.Tensor:
+    def paste_back(self, original, edited, mask, dilate: int = 16, feather: int = 4, color_match=None, color_ref=None) -> torch.Tensor:
         """The edited image blended into the ORIGINAL one, at the original's size, under the dilated and feathered mask
         (textflux_amd/paste_back.py::paste): pixels outside the mask grown by dilate + 3 feather keep their bytes.  Opt-in, no reference
         counterpart.  original / edited: a PIL image, a uint8 array or tensor [H, W, 3] / [B, H, W, 3], or a list of PIL images (edited
         may have another size: it is resampled with Pillow's bicubic on the device); mask: the same forms, grey [H, W] or RGB (PIL's
-        "L" of it is taken).  Returns uint8 [B, H, W, 3] on the device."""
+        "L" of it is taken).  color_match: None, or True / dict(ring, gain, max_shift, min_pixels): the edit's colours are matched to
+        those of color_ref (the forms of `original`, at its size; None: `original`) on a ring just outside the blend before the blend
+        (paste_back.paste).  Returns uint8 [B, H, W, 3] on the device."""
         from . import paste_back as pb
         dev = self._execution_device
 
@@ -628,7 +630,10 @@ class FluxFillPipeline:
             return (t[None] if t.dim() == 2 else t).contiguous()
 
         original = rgb(original)
-        return pb.paste(original, rgb(edited), grey(mask, tuple(original.shape[1:3])), dilate, feather)
+        if color_match is None and color_ref is None:
+            return pb.paste(original, rgb(edited), grey(mask, tuple(original.shape[1:3])), dilate, feather)
+        return pb.paste(original, rgb(edited), grey(mask, tuple(original.shape[1:3])), dilate, feather, color_match=color_match,
+                        color_ref=None if color_ref is None else rgb(color_ref))
 
     def _generic_loop(self, latents, masked_image_latents, prompt_embeds, pooled, text_ids, latent_image_ids, timesteps,
                       guidance, callback_on_step_end, callback_tensor_inputs, progress_bar):
