@@ -519,6 +519,23 @@ int tfx_masked_moments_u8(const void* a, const void* b, const void* weight, void
  *      for bit.  out may be orig (no other aliasing). */
 int tfx_overlay_lut_u8(const void* orig, const void* edit, const void* alpha, const void* lut, void* out, int32_t B, int32_t H, int32_t W,
                        int32_t C, tfx_stream stream);
+/* ---- rectified per-line edits (DESIGN.md section 4 "Rectified lines"): a slanted text line is cut as an oriented rectangle, edited
+ *      upright and warped back.  Added without a new TFX_ABI_VERSION: one new entry point, no stamped struct and no existing entry point
+ *      changes.  Tensors contiguous, batch-major; B, H, W, out_h, out_w >= 1, B <= 65535, C in 1..4; in, out and coverage are three
+ *      different buffers; m and taps are 8-byte aligned DEVICE pointers.  Integer arithmetic throughout, so the results are exact.
+ * tfx_warp_affine_u8: in u8 [B, H, W, C] -> out u8 [B, out_h, out_w, C]; out[b, j, i, c] is in[b] sampled at the affine image of the
+ *      destination pixel (i, j) under m i64 [B][6] (one matrix per sample), in Q16 and 64-bit integers:
+ *          X = m0 i + m1 j + m2,  Y = m3 i + m4 j + m5     (the caller folds the pixel-centre offsets into m2, m5 and keeps |X|, |Y| < 2^62)
+ *          xi = X >> 16 (arithmetic shift: floor), fx = (X >> 8) & 255; yi, fy from Y alike
+ *          acc = sum over r, k in 0..3 of taps[fy][r] taps[fx][k] in[b, clamp(yi - 1 + r, 0, H - 1), clamp(xi - 1 + k, 0, W - 1), c]
+ *          out = clamp((acc + 2^27) >> 28, 0, 255)
+ *      taps i16 [256][4]: row f holds the weights of the four taps at distances 1 + t, t, 1 - t, 2 - t for t = f / 256, with 14
+ *      fractional bits; every row sums to exactly 1 << 14 (the Catmull-Rom table of textflux_amd/rectify.py::catmull_rom_taps), so a
+ *      constant image stays that constant.  The indices are clamped (edge replicate): no read leaves `in`, whatever m holds.
+ *      coverage (may be NULL) u8 [B, out_h, out_w] = 255 where 0 <= xi < W and 0 <= yi < H, else 0: whether the sample position lies in
+ *      the image. */
+int tfx_warp_affine_u8(const void* in, void* out, void* coverage, int32_t B, int32_t H, int32_t W, int32_t C, int32_t out_h, int32_t out_w,
+                       const int64_t* m, const int16_t* taps, tfx_stream stream);
 /* out[b, t, col0 + (i*8+j)*4 + py*2+px] = mask[(2ty+py)*8 + i, (2tx+px)*8 + j]  (P:1563-1580: 8x8 pixel blocks -> channels,
  * then _pack_latents), t = ty * (W/16) + tx, row stride ld. */
 int tfx_pack_mask(const void* mask, int32_t mask_dtype, void* out, int32_t B, int32_t H, int32_t W, int32_t mask_batch,

@@ -49,7 +49,7 @@ def use_overshoot_sampler(pipe):
 def run_inference(image_input, mask_input, words_input, num_steps=50, guidance_scale=30, seed=42, pipe=None, paste_back=None):
     """paste_back (not in the reference): None, or dict(dilate, feather) -- the result is then blended back into the input image under
     the dilated and feathered mask and returned at the INPUT's size (FluxFillPipeline.paste_back) instead of at the pipeline's size.
-    With per_line=True in it (batch_driver.run_items' keys: region, color_match) the input is the plain scene and its mask: every text
+    With per_line=True in it (batch_driver.run_items' keys: region, color_match, rectify) the input is the plain scene and its mask: every text
     line is edited through its own region with a single-line glyph strip and pasted into the scene (textflux_amd/per_line.py)."""
     image = (Image.open(image_input) if isinstance(image_input, str) else image_input).convert("RGB")
     mask = (Image.open(mask_input) if isinstance(mask_input, str) else mask_input).convert("RGB")
@@ -99,11 +99,33 @@ def add_paste_back_args(ap):
                     "outside the blend (with --paste_back)")
     ap.add_argument("--paste_color_ring", type=int, default=None, metavar="N", help="width of that ring in pixels, 1..255 (implies "
                     "--paste_color_match; with --paste_back)")
+    ap.add_argument("--paste_rectify", action="store_true", help="edit a slanted text line upright: cut it as an oriented rectangle, warp it "
+                    "upright, edit it and warp the result back (with --paste_back --paste_per_line)")
+    ap.add_argument("--paste_rectify_min_angle", type=float, default=None, metavar="DEG", help="smallest slant that is rectified, default 5 "
+                    "(implies --paste_rectify)")
+    ap.add_argument("--paste_rectify_max_angle", type=float, default=None, metavar="DEG", help="largest slant that is rectified, default 45 "
+                    "(implies --paste_rectify)")
+
+
+RECTIFY_FLAGS = ("paste_rectify", "paste_rectify_min_angle", "paste_rectify_max_angle")
+
+
+def rectify_from_args(a):
+    """None, or the `rectify` value of the paste_back dict (True, or a dict of the angles that were given).  The flags are refused
+    without --paste_back --paste_per_line."""
+    given = [f for f in RECTIFY_FLAGS if getattr(a, f, None) not in (None, False)]
+    if not given:
+        return None
+    if not (a.paste_back and getattr(a, "paste_per_line", False)):
+        raise SystemExit(f"--{given[0]} needs --paste_back --paste_per_line")
+    angles = {k: getattr(a, "paste_rectify_" + k) for k in ("min_angle", "max_angle") if getattr(a, "paste_rectify_" + k) is not None}
+    return angles or True
 
 
 def paste_back_from_args(a):
     """None, or the paste_back dict of batch_driver.run_items / process_normal_mode.  The per-line and colour keys appear only when
     their flags were given."""
+    rectify = rectify_from_args(a)
     if not a.paste_back:
         for flag in ("paste_region", "paste_per_line", "paste_color_match", "paste_color_ring"):
             if getattr(a, flag, None) not in (None, False):
@@ -116,6 +138,8 @@ def paste_back_from_args(a):
         pb["color_match"] = dict(ring=a.paste_color_ring)
     elif getattr(a, "paste_color_match", False):
         pb["color_match"] = True
+    if rectify is not None:
+        pb["rectify"] = rectify
     return pb
 
 

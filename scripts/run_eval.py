@@ -85,6 +85,12 @@ def build_parser(lora: bool = False):
                     "outside the blend (with --paste_back)")
     ap.add_argument("--paste_color_ring", type=int, default=None, metavar="N", help="width of that ring in pixels, 1..255 (implies "
                     "--paste_color_match; with --paste_back)")
+    ap.add_argument("--paste_rectify", action="store_true", help="edit a slanted text line upright: cut it as an oriented rectangle, warp it "
+                    "upright, edit it and warp the result back (with --paste_back --paste_per_line)")
+    ap.add_argument("--paste_rectify_min_angle", type=float, default=None, metavar="DEG", help="smallest slant that is rectified, default 5 "
+                    "(implies --paste_rectify)")
+    ap.add_argument("--paste_rectify_max_angle", type=float, default=None, metavar="DEG", help="largest slant that is rectified, default 45 "
+                    "(implies --paste_rectify)")
     ap.add_argument("--items", type=str, default=None, help="JSON list of {image, mask, text} instead of --json_path")
     ap.add_argument("--out", type=str, default=None, help="output folder of --items mode")
     ap.add_argument("--num_inference_steps", type=int, default=None, help=argparse.SUPPRESS)
@@ -151,6 +157,12 @@ def main(argv=None, lora: bool = False, script: str = __file__):
         paste_back["per_line"] = True
     if a.paste_back and (a.paste_color_match or a.paste_color_ring is not None):
         paste_back["color_match"] = True if a.paste_color_ring is None else dict(ring=a.paste_color_ring)
+    rectify_given = [f for f in ("paste_rectify", "paste_rectify_min_angle", "paste_rectify_max_angle") if getattr(a, f) not in (None, False)]
+    if rectify_given:
+        if not (a.paste_back and a.paste_per_line):
+            raise SystemExit(f"--{rectify_given[0]} needs --paste_back --paste_per_line")
+        angles = {k: getattr(a, "paste_rectify_" + k) for k in ("min_angle", "max_angle") if getattr(a, "paste_rectify_" + k) is not None}
+        paste_back["rectify"] = angles or True
     legacy = a.items is not None
     weights = a.lora_weights_path if lora else a.weights_path
     if not legacy and not (a.json_path and a.original_images_dir and weights):

@@ -53,6 +53,8 @@ class Work:
     region: Any = None               # ... and the paste_back.Region of it that was edited (the whole image without `region`)
     parent: Optional[int] = None     # per-line editing only (per_line.py): the index of the item this line belongs to ...
     line: Optional[int] = None       # ... and the line's position in the item's split order
+    rect: Any = None                 # rectified lines only (rectify.py): the oriented rectify.Rect that was edited upright; `region` is then
+                                     # the scene window it is pasted into
 
 
 @dataclass
@@ -71,9 +73,10 @@ def eval_item_complete(item: Dict[str, Any]) -> bool:
 def _paste_back_cfg(paste_back: Dict[str, Any]) -> Dict[str, Any]:
     """run_items' paste_back argument with its defaults filled in: dict(dilate, feather, region: None | dict(pad, min_side, max_side)),
     and, only when the caller gave them, per_line: True (which implies a region: {} when absent) and color_match: paste_back.
-    color_match_cfg's dict(ring, gain, max_shift, min_pixels)."""
+    color_match_cfg's dict(ring, gain, max_shift, min_pixels), and rectify: rectify.rectify_cfg's dict(min_angle, max_angle, min_aspect)
+    (needs per_line)."""
     from . import paste_back as pb
-    unknown = set(paste_back) - {"dilate", "feather", "region", "per_line", "color_match"}
+    unknown = set(paste_back) - {"dilate", "feather", "region", "per_line", "color_match", "rectify"}
     region = paste_back.get("region")
     if region is not None:
         unknown |= {f"region.{k}" for k in set(region) - {"pad", "min_side", "max_side"}}
@@ -99,6 +102,17 @@ def _paste_back_cfg(paste_back: Dict[str, Any]) -> Dict[str, Any]:
             cfg["color_match"] = pb.color_match_cfg(color_match)
         except ValueError as e:
             raise ValueError(f"paste_back: {e}") from None
+    rectify = paste_back.get("rectify")
+    if rectify is not None and rectify is not False:
+        if rectify is not True and not isinstance(rectify, dict):
+            raise ValueError("paste_back: rectify must be None, True or a dict")
+        if not per_line:
+            raise ValueError("paste_back: rectify needs per_line=True (only single-line edits are rectified)")
+        from . import rectify as rc
+        try:
+            cfg["rectify"] = rc.rectify_cfg(rectify)
+        except ValueError as e:
+            raise ValueError(f"paste_back: {e}") from None
     return cfg
 
 
@@ -120,14 +134,57 @@ def _paste_back_inputs(scene, mask, cfg: Dict[str, Any]):
     return s, m, so, mo, reg
 
 
+def _host_u8(x):
+    """A warp's result (device tensor or array, with or without the batch axis of one) as a host uint8 array [H, W, C]."""
+    import numpy as np
+    a = x.cpu().numpy() if isinstance(x, torch.Tensor) else np.asarray(x)
+    return np.ascontiguousarray(a[0] if a.ndim == 4 else a)
+
+
+def _rectified_inputs(scene, mask, cfg: Dict[str, Any], warp: Callable):
+    """_paste_back_inputs for a line that is edited upright (DESIGN.md section 4 "Rectified lines"), or None when the line stays on
+    the unrectified path (rectify.plan).  -> (scene, mask, originals, Region, Rect): the scene and the RGB mask warped into the oriented
+    rectangle's upright frame (rw, rh) by `warp` (the pipeline's warp_affine: the device kernel; nothing is resampled in a rotated frame
+    on the host), the mask binarised at >= 128, both resized to the editing size (tw, th) with PIL's bicubic when that differs.  The
+    Region is the scene window the result is pasted into: the rectangle's bounding box cut at the image."""
+    import numpy as np
+    from PIL import Image
+    from . import paste_back as pb
+    from . import rectify as rc
+    so, mo = np.array(scene), np.array(mask)
+    rect = rc.plan(pb.grey_of(mo), cfg)
+    if rect is None:
+        return None
+    x0, y0, x1, y1 = rc.rect_window(rect, scene.size)
+    fwd, _ = rc.matrices(rect)
+    s = _host_u8(warp(so, fwd, (rect.rh, rect.rw)))
+    m = np.where(_host_u8(warp(mo if mo.ndim == 3 else mo[:, :, None], fwd, (rect.rh, rect.rw))) >= 128, 255, 0).astype(np.uint8)
+    s, m = Image.fromarray(s), Image.fromarray(m if mo.ndim == 3 else m[:, :, 0])
+    if s.size != (rect.tw, rect.th):
+        s, m = s.resize((rect.tw, rect.th), Image.BICUBIC), m.resize((rect.tw, rect.th), Image.BICUBIC)
+    return s, m, so, mo, pb.Region(x0, y0, x1, y1, rect.tw, rect.th), rect
+
+
+def _edit_inputs(scene, mask, cfg: Dict[str, Any], warp: Optional[Callable]):
+    """(scene, mask, the Work's paste-back fields): _rectified_inputs where the cfg asks for it, a warp is at hand and the line
+    qualifies; _paste_back_inputs otherwise."""
+    got = _rectified_inputs(scene, mask, cfg, warp) if (warp is not None and cfg.get("rectify")) else None
+    if got is not None:
+        scene, mask, so, mo, reg, rect = got
+        return scene, mask, dict(orig_scene=so, orig_mask=mo, region=reg, rect=rect)
+    scene, mask, so, mo, reg = _paste_back_inputs(scene, mask, cfg)
+    return scene, mask, dict(orig_scene=so, orig_mask=mo, region=reg)
+
+
 def prepare_eval_item(index: int, item: Dict[str, Any], original_images_dir: str, font, text_height_ratio: float = 0.1667,
                       loader: Optional[Callable] = None, device_compose: bool = False, paste_back: Optional[Dict[str, Any]] = None,
-                      annotation: int = 0) -> Work:
+                      annotation: int = 0, warp: Optional[Callable] = None) -> Work:
     """One `annos.json` entry -> Work (scripts/run_eval.py:76-112): scene = original_images_dir / img_name; mask = the first
     annotation's polygon filled white on black; glyph strip of height int(w * text_height_ratio) -- a fraction of the image
     WIDTH -- with the annotation's text, stacked on top with a black mask; pipeline size ((w // 32) * 32,
     ((h + strip) // 32) * 32); T5 prompt generate_prompt([text]).  annotation: which entry of `annotations` (the reference, and
-    every caller but per-line editing, reads the first)."""
+    every caller but per-line editing, reads the first).  warp: the pipeline's warp_affine, given by per-line editing when
+    paste_back["rectify"] is set: a slanted line is then edited upright (_rectified_inputs)."""
     import numpy as np
     from PIL import Image
     load = loader or (lambda p: Image.open(p))
@@ -138,8 +195,8 @@ def prepare_eval_item(index: int, item: Dict[str, Any], original_images_dir: str
     m = glyph.fill_polygon(h, w, ann["polygon"])
     extra = {}
     if paste_back is not None:       # the strip, the stacking and the sizes below are then those of the edited region
-        scene, mk, so, mo, reg = _paste_back_inputs(scene, Image.fromarray(m), paste_back)
-        (w, h), m, extra = scene.size, np.array(mk), dict(orig_scene=so, orig_mask=mo, region=reg)
+        scene, mk, extra = _edit_inputs(scene, Image.fromarray(m), paste_back, warp)
+        (w, h), m = scene.size, np.array(mk)
     strip = int(w * text_height_ratio)
     g = np.array(glyph.draw_glyph(font, text, w, strip))
     meta = dict(mode="singleline", direction="vertical", strip=strip, orig_h=h)
@@ -171,13 +228,13 @@ def prepare_item(index: int, item: Dict[str, Any], loader: Optional[Callable] = 
 
 
 def prepare_plain(index: int, scene, mask, words: Sequence[str], device_compose: bool = False,
-                  paste_back: Optional[Dict[str, Any]] = None) -> Work:
-    """prepare_item's rule for an {image, mask, text} item whose RGB scene and mask are loaded and whose text is split into words."""
+                  paste_back: Optional[Dict[str, Any]] = None, warp: Optional[Callable] = None) -> Work:
+    """prepare_item's rule for an {image, mask, text} item whose RGB scene and mask are loaded and whose text is split into words.
+    warp: as in prepare_eval_item."""
     from PIL import Image
     extra = {}
     if paste_back is not None:
-        scene, mask, so, mo, reg = _paste_back_inputs(scene, mask, paste_back)
-        extra = dict(orig_scene=so, orig_mask=mo, region=reg)
+        scene, mask, extra = _edit_inputs(scene, mask, paste_back, warp)
     g, s_, m, horizontal, meta = glyph.compose_parts(scene, mask, words)
     H, W = (s_.shape[0], g.shape[1] + s_.shape[1]) if horizontal else (g.shape[0] + s_.shape[0], s_.shape[1])
     w, h = (W // 32) * 32, (H // 32) * 32
@@ -342,13 +399,19 @@ def run_items(items: Sequence[Dict[str, Any]], pipe, out_dir: Optional[str], bat
     single-line item of its own, with its own region, and pastes all of them into the one scene in split order (per_line.py); items
     are then dealt to the ranks whole, and full_images/ holds line 0's raw canvas under <name>, line k >= 1 under <stem>_line<k><ext>
     (save_full receives line 0's Work and canvas).  A failing line fails its item.  color_match=True | dict(ring, gain, max_shift,
-    min_pixels) matches each pasted edit's colours to the original's on a ring just outside the blend (paste_back.paste)."""
+    min_pixels) matches each pasted edit's colours to the original's on a ring just outside the blend (paste_back.paste).
+    rectify=True | dict(min_angle, max_angle, min_aspect) (with per_line; DESIGN.md section 4 "Rectified lines"): a line whose
+    minimum-area rectangle is slanted by min_angle..max_angle degrees (defaults 5 and 45) and at least min_aspect (1.5) times as long
+    as thick is cut as an oriented rectangle, warped upright on the device (pipe.warp_affine), edited upright and warped back into the
+    scene under the same alpha; every other line is edited as without the key."""
     if paste_back is not None:       # refused before anything is prepared or encoded
         if mixed_pad > 0:
             raise NotImplementedError("paste_back does not serve mixed-geometry batches (mixed_pad > 0)")
         if not hasattr(pipe, "paste_back"):
             raise ValueError("paste_back needs a pipeline with paste_back (FluxFillPipeline)")
         paste_back = _paste_back_cfg(paste_back)
+        if paste_back.get("rectify") and not hasattr(pipe, "warp_affine"):
+            raise ValueError("paste_back: rectify needs a pipeline with warp_affine (FluxFillPipeline)")
     if step_cache is not None:
         if mixed_pad > 0:
             raise NotImplementedError("step_cache does not serve mixed-geometry batches (mixed_pad > 0)")
@@ -385,7 +448,8 @@ def _run_items(items, pipe, out_dir, batch_size, num_inference_steps, guidance_s
             device_compose = bool(getattr(pipe, "supports_device_compose", False))
             if per_line:
                 from . import per_line as pl
-                lines[i] = pl.prepare_lines(i, it, loader, device_compose, eval_cfg, paste_back)
+                lines[i] = pl.prepare_lines(i, it, loader, device_compose, eval_cfg, paste_back,
+                                            warp=pipe.warp_affine if paste_back.get("rectify") else None)
                 works.extend(lines[i])
             else:
                 works.append(prepare_item(i, it, loader, device_compose=device_compose,

@@ -527,6 +527,62 @@ __global__ __launch_bounds__(256) void overlay_lut_u8_kernel(const uint8_t* orig
   }
 }
 
+// ---- rectified per-line edits (DESIGN.md section 4 "Rectified lines"): out[b, j, i, :] = in[b] sampled at the affine image of the
+// destination pixel (i, j), 4 x 4 Catmull-Rom taps, edge replicated.  Integer arithmetic only (include/textflux_hip.h spells it out),
+// so the result is exact.  One 256-thread workgroup per 32 x 8 destination tile: its rotated source footprint is a compact patch
+// of about 40 x 25 pixels that stays in cache.  The sample's matrix sits at an address that is uniform over the workgroup, so it is
+// read once per workgroup, not once per thread.  Every index is clamped into the image in 64 bits before it is narrowed: whatever the
+// matrix holds, no load leaves `in`.
+template <int C>
+__global__ __launch_bounds__(256) void warp_affine_u8_kernel(const uint8_t* __restrict__ in, uint8_t* __restrict__ out,
+                                                             uint8_t* __restrict__ coverage, int H, int W, int out_h, int out_w,
+                                                             const int64_t* __restrict__ m, const int16_t* __restrict__ taps) {
+  const int b = blockIdx.z;
+  const int64_t* mb = m + (int64_t)b * 6;
+  const int64_t m0 = mb[0], m1 = mb[1], m2 = mb[2], m3 = mb[3], m4 = mb[4], m5 = mb[5];
+  const int i = blockIdx.x * 32 + (threadIdx.x & 31), j = blockIdx.y * 8 + (threadIdx.x >> 5);
+  if (i >= out_w || j >= out_h) return;
+  const int64_t X = m0 * i + m1 * j + m2, Y = m3 * i + m4 * j + m5;        // Q16
+  const int64_t xi = X >> 16, yi = Y >> 16;
+  const int16_t* tx = taps + ((X >> 8) & 255) * 4;
+  const int16_t* ty = taps + ((Y >> 8) & 255) * 4;
+  int cx[4];
+  int64_t row[4];
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const int64_t x = xi - 1 + k, y = yi - 1 + k;
+    cx[k] = (int)(x < 0 ? 0 : x > W - 1 ? W - 1 : x) * C;
+    row[k] = (y < 0 ? 0 : y > H - 1 ? H - 1 : y) * (int64_t)W * C;
+  }
+  const uint8_t* src = in + (int64_t)b * H * W * C;
+  int64_t acc[C];
+#pragma unroll
+  for (int c = 0; c < C; ++c) acc[c] = 0;
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    const uint8_t* p = src + row[r];
+    int s[C];                        // |sum of a row's taps times a byte| < 2^23: 32 bits hold it; the same integer as the 64-bit sum
+#pragma unroll
+    for (int c = 0; c < C; ++c) s[c] = 0;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const int wx = tx[k];
+#pragma unroll
+      for (int c = 0; c < C; ++c) s[c] += wx * (int)p[cx[k] + c];
+    }
+    const int64_t wy = ty[r];
+#pragma unroll
+    for (int c = 0; c < C; ++c) acc[c] += wy * s[c];
+  }
+  const int64_t o = ((int64_t)b * out_h + j) * out_w + i;
+#pragma unroll
+  for (int c = 0; c < C; ++c) {
+    const int64_t v = (acc[c] + ((int64_t)1 << 27)) >> 28;
+    out[o * C + c] = (uint8_t)(v < 0 ? 0 : v > 255 ? 255 : v);
+  }
+  if (coverage) coverage[o] = (xi >= 0 && xi < W && yi >= 0 && yi < H) ? 255 : 0;
+}
+
 int compose_canvas(const void* glyph, const void* scene, const void* smask, void* canvas, void* cmask, int B, int gh, int gw, int sh,
                    int sw, int dir, int mask_rgb, hipStream_t st) {
   if (dir != 0 && dir != 1) return fail("compose_canvas: direction 0 (vertical) or 1 (horizontal)");
@@ -649,6 +705,27 @@ int overlay_lut_u8(const void* orig, const void* edit, const void* alpha, const 
   else overlay_lut_u8_kernel<false><<<dim3(grid, B), 256, 0, st>>>((const uint8_t*)orig, (const uint8_t*)edit, (const uint8_t*)alpha,
                                                                    (const uint8_t*)lut, (uint8_t*)out, n, C);
   return check_launch("overlay_lut_u8");
+}
+
+int warp_affine_u8(const void* in, void* out, void* coverage, int B, int H, int W, int C, int out_h, int out_w, const int64_t* m,
+                   const int16_t* taps, hipStream_t st) {
+  if (B < 1 || H < 1 || W < 1 || out_h < 1 || out_w < 1) return fail("warp_affine_u8: B, H, W, out_h, out_w must be at least 1");
+  if (C < 1 || C > 4) return fail("warp_affine_u8: 1..4 channels");
+  if (B > 65535) return fail("warp_affine_u8: batch %d exceeds 65535", B);
+  if ((out_h + 7) / 8 > 65535) return fail("warp_affine_u8: out_h %d exceeds 524280", out_h);
+  if ((int64_t)H * W * C > kMaxBytes || (int64_t)out_h * out_w * C > kMaxBytes) return fail("warp_affine_u8: more than 2^38 bytes per sample");
+  if (in == out || in == coverage || out == coverage) return fail("warp_affine_u8: in, out and coverage must be different buffers");
+  if (((uintptr_t)m | (uintptr_t)taps) & 7) return fail("warp_affine_u8: m and taps must be 8-byte aligned");
+  const dim3 grid((out_w + 31) / 32, (out_h + 7) / 8, B);
+  const uint8_t* pi = (const uint8_t*)in;
+  uint8_t *po = (uint8_t*)out, *pc = (uint8_t*)coverage;
+  switch (C) {
+    case 1: warp_affine_u8_kernel<1><<<grid, 256, 0, st>>>(pi, po, pc, H, W, out_h, out_w, m, taps); break;
+    case 2: warp_affine_u8_kernel<2><<<grid, 256, 0, st>>>(pi, po, pc, H, W, out_h, out_w, m, taps); break;
+    case 3: warp_affine_u8_kernel<3><<<grid, 256, 0, st>>>(pi, po, pc, H, W, out_h, out_w, m, taps); break;
+    default: warp_affine_u8_kernel<4><<<grid, 256, 0, st>>>(pi, po, pc, H, W, out_h, out_w, m, taps); break;
+  }
+  return check_launch("warp_affine_u8");
 }
 
 int pack_mask(const void* mask, int mask_dtype, void* out, int B, int H, int W, int mask_b, int binarize, int64_t ld, int col0,

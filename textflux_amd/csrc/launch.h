@@ -216,6 +216,10 @@ constexpr int64_t MASKED_MOMENTS_SCRATCH_BYTES = 256 * 17 * 8;   // per sample
 int masked_moments_u8(const void* a, const void* b, const void* weight, void* out, void* scratch, int64_t scratch_bytes, int B, int H, int W,
                       int C, hipStream_t st);
 int overlay_lut_u8(const void* orig, const void* edit, const void* alpha, const void* lut, void* out, int B, int H, int W, int C, hipStream_t st);
+// rectified per-line edits: out [B, out_h, out_w, C] u8 = in [B, H, W, C] sampled at the Q16 affine image (m i64 [B][6], device) of every
+// destination pixel, 4 x 4 taps from the i16 [256][4] table (device), edge replicated; coverage [B, out_h, out_w] u8 or NULL
+int warp_affine_u8(const void* in, void* out, void* coverage, int B, int H, int W, int C, int out_h, int out_w, const int64_t* m,
+                   const int16_t* taps, hipStream_t st);
 int pack_mask(const void* mask, int mask_dtype, void* out, int B, int H, int W, int mask_b, int binarize, int64_t ld, int col0,
               hipStream_t st);
 int sample_pack(const void* moments, const void* eps, int eps_dtype, void* out, int B, int h, int w, int L, float shift,

@@ -768,6 +768,39 @@ def overlay_lut(orig: torch.Tensor, edit: torch.Tensor, alpha: torch.Tensor, lut
     return out
 
 
+_WARP_TAPS = {}
+
+
+def warp_affine_u8(x: torch.Tensor, m, out_size, coverage: bool = False):
+    """uint8 [B, H, W, C] (C in 1..4) -> [B, out_h, out_w, C]: every destination pixel (i, j) is x[b] sampled at its Q16 affine image
+    under m (int64 [B, 6] or [6], tensor or array: one matrix per sample, or one for all), 4 x 4 Catmull-Rom taps, edge replicated, in
+    integer arithmetic (tfx_warp_affine_u8; include/textflux_hip.h has the arithmetic, rectify.matrices builds m).  out_size =
+    (out_h, out_w).  coverage: also return uint8 [B, out_h, out_w], 255 where the sample position lies inside the image."""
+    _chk_dev(x)
+    if x.dtype != torch.uint8 or x.dim() != 4 or not x.is_contiguous() or x.numel() == 0 or not 1 <= x.shape[3] <= 4:
+        raise ValueError(f"warp_affine_u8: x must be a contiguous, non-empty uint8 [B, H, W, C <= 4] tensor, got {x.dtype} {tuple(x.shape)}")
+    B, H, W, Cc = x.shape
+    Ho, Wo = (int(v) for v in out_size)
+    if Ho < 1 or Wo < 1:
+        raise ValueError(f"warp_affine_u8: out_size must be (out_h, out_w) with both at least 1, got {tuple(out_size)}")
+    if not isinstance(m, torch.Tensor):
+        import numpy as np
+        m = torch.from_numpy(np.ascontiguousarray(m))
+    if m.dtype != torch.int64 or m.numel() not in (6, 6 * B) or m.shape[-1] != 6:
+        raise ValueError(f"warp_affine_u8: m must be int64 [{B}, 6] or [6], got {m.dtype} {tuple(m.shape)}")
+    m = m.reshape(-1, 6).expand(B, 6).to(x.device).contiguous()
+    key = str(x.device)
+    if key not in _WARP_TAPS:
+        from .rectify import catmull_rom_taps
+        _WARP_TAPS[key] = torch.from_numpy(catmull_rom_taps()).to(x.device)
+    taps = _WARP_TAPS[key]
+    out = torch.empty(B, Ho, Wo, Cc, dtype=torch.uint8, device=x.device)
+    cov = torch.empty(B, Ho, Wo, dtype=torch.uint8, device=x.device) if coverage else None
+    L.check(L.lib().tfx_warp_affine_u8(x.data_ptr(), out.data_ptr(), _p(cov), B, H, W, Cc, Ho, Wo, m.data_ptr(), taps.data_ptr(),
+                                       _stream()), "warp_affine_u8")
+    return (out, cov) if coverage else out
+
+
 def pack_mask(mask: torch.Tensor, out: torch.Tensor, col0: int, B: int, H: int, W: int, binarize: bool = True) -> torch.Tensor:
     """out[b, :, col0 : col0 + 256] = packed mask (out: [B, S, ld] bf16)."""
     _chk_dev(mask, out)

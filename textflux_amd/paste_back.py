@@ -166,14 +166,19 @@ def fit_luts(moments, gain: Tuple[float, float] = GAIN, max_shift: int = MAX_SHI
 
 
 def paste(original: torch.Tensor, edited: torch.Tensor, mask_grey: torch.Tensor, dilate: int = DILATE, feather: int = FEATHER,
-          color_match=None, color_ref: Optional[torch.Tensor] = None) -> torch.Tensor:
+          color_match=None, color_ref: Optional[torch.Tensor] = None, rect=None, origin: Tuple[int, int] = (0, 0)) -> torch.Tensor:
     """original uint8 [B, H, W, 3], edited uint8 [B, h, w, 3], mask_grey uint8 [B, H, W], all on the device -> [B, H, W, 3]: the edit,
     resampled to (H, W) when its size differs (ops.resample_u8: Pillow's bicubic), blended over the original under alpha_mask computed at
     the ORIGINAL resolution.  Outside the mask dilated by dilate + 3 feather the result is the original byte for byte; with
     dilate >= 3 feather it is the resampled edit on every mask pixel.
     color_match: None, or True / dict(ring, gain, max_shift, min_pixels): the resampled edit goes through a per-channel table fitted
     (fit_luts) on the ring just outside the blend (ring_mask) to the colours of color_ref (uint8 [B, H, W, 3]; None: `original`) before
-    it is blended (ops.overlay_lut).  The alpha is the same, so the bytes outside the grown mask are still the original's."""
+    it is blended (ops.overlay_lut).  The alpha is the same, so the bytes outside the grown mask are still the original's.
+    rect (a rectify.Rect; DESIGN.md section 4 "Rectified lines"): `edited` is the UPRIGHT result of a rectified line and `original` the
+    scene window whose top-left pixel is scene pixel `origin`.  The edit is resampled to the rectangle's own size (rh, rw) and warped
+    into the window (ops.warp_affine_u8 under rectify.matrices' upright -> scene matrix) instead of being resized to it; the alpha is
+    still that of mask_grey, the line's ORIGINAL mask, so the bytes outside the grown mask stay the original's; with color_match the
+    ring is cut to the pixels the warp covered (their sample position lies inside the upright crop)."""
     if original.dtype != torch.uint8 or original.dim() != 4 or edited.dtype != torch.uint8 or edited.dim() != 4:
         raise ValueError("paste: original and edited must be uint8 [B, H, W, C]")
     if edited.shape[0] != original.shape[0] or edited.shape[3] != original.shape[3] or mask_grey.shape != original.shape[:3]:
@@ -181,7 +186,13 @@ def paste(original: torch.Tensor, edited: torch.Tensor, mask_grey: torch.Tensor,
     if color_match is None and color_ref is not None:
         raise ValueError("paste: color_ref needs color_match")
     original, edited = original.contiguous(), edited.contiguous()
-    if edited.shape[1:3] != original.shape[1:3]:
+    covered = None
+    if rect is not None:
+        from . import rectify
+        if tuple(edited.shape[1:3]) != (rect.rh, rect.rw):
+            edited = ops.resample_u8(edited, (rect.rh, rect.rw))
+        edited, covered = ops.warp_affine_u8(edited, rectify.matrices(rect, origin)[1], (original.shape[1], original.shape[2]), coverage=True)
+    elif edited.shape[1:3] != original.shape[1:3]:
         edited = ops.resample_u8(edited, (original.shape[1], original.shape[2]))
     alpha = alpha_mask(mask_grey.contiguous(), dilate, feather)
     if color_match is None:
@@ -190,7 +201,10 @@ def paste(original: torch.Tensor, edited: torch.Tensor, mask_grey: torch.Tensor,
     ref = original if color_ref is None else color_ref.contiguous()
     if ref.shape != original.shape or ref.dtype != torch.uint8:
         raise ValueError(f"paste: color_ref must be uint8 of original's shape {tuple(original.shape)}, got {ref.dtype} {tuple(ref.shape)}")
-    luts = fit_luts(ops.masked_moments(edited, ref, ring_mask(alpha, cm["ring"])), cm["gain"], cm["max_shift"], cm["min_pixels"])
+    ring = ring_mask(alpha, cm["ring"])
+    if covered is not None:
+        ring = ring & covered
+    luts = fit_luts(ops.masked_moments(edited, ref, ring), cm["gain"], cm["max_shift"], cm["min_pixels"])
     return ops.overlay_lut(original, edited, alpha, torch.from_numpy(luts).to(original.device))
 
 

@@ -588,14 +588,17 @@ class FluxFillPipeline:
         return self
 
     # ------------------------------------------------------------------ paste-back (DESIGN.md section 4 "Paste-back")
-    def paste_back(self, original, edited, mask, dilate: int = 16, feather: int = 4, color_match=None, color_ref=None) -> torch.Tensor:
+    def paste_back(self, original, edited, mask, dilate: int = 16, feather: int = 4, color_match=None, color_ref=None, rect=None,
+                   origin=(0, 0)) -> torch.Tensor:
         """The edited image blended into the ORIGINAL one, at the original's size, under the dilated and feathered mask
         (textflux_amd/paste_back.py::paste): pixels outside the mask grown by dilate + 3 feather keep their bytes.  Opt-in, no reference
         counterpart.  original / edited: a PIL image, a uint8 array or tensor [H, W, 3] / [B, H, W, 3], or a list of PIL images (edited
         may have another size: it is resampled with Pillow's bicubic on the device); mask: the same forms, grey [H, W] or RGB (PIL's
         "L" of it is taken).  color_match: None, or True / dict(ring, gain, max_shift, min_pixels): the edit's colours are matched to
         those of color_ref (the forms of `original`, at its size; None: `original`) on a ring just outside the blend before the blend
-        (paste_back.paste).  Returns uint8 [B, H, W, 3] on the device."""
+        (paste_back.paste).  rect (a rectify.Rect) with origin: `edited` is the upright result of a rectified line and `original` the scene
+        window at `origin`; the edit is warped into the window before the blend (paste_back.paste).  Returns uint8 [B, H, W, 3] on the
+        device."""
         from . import paste_back as pb
         dev = self._execution_device
 
@@ -630,10 +633,22 @@ class FluxFillPipeline:
             return (t[None] if t.dim() == 2 else t).contiguous()
 
         original = rgb(original)
+        kw = {} if rect is None else dict(rect=rect, origin=origin)
         if color_match is None and color_ref is None:
-            return pb.paste(original, rgb(edited), grey(mask, tuple(original.shape[1:3])), dilate, feather)
+            return pb.paste(original, rgb(edited), grey(mask, tuple(original.shape[1:3])), dilate, feather, **kw)
         return pb.paste(original, rgb(edited), grey(mask, tuple(original.shape[1:3])), dilate, feather, color_match=color_match,
-                        color_ref=None if color_ref is None else rgb(color_ref))
+                        color_ref=None if color_ref is None else rgb(color_ref), **kw)
+
+    # ------------------------------------------------------------------ rectified lines (DESIGN.md section 4 "Rectified lines")
+    def warp_affine(self, image, m, out_size, coverage: bool = False):
+        """A uint8 image (array or tensor, [H, W, C] or [B, H, W, C], C in 1..4) sampled under the Q16 affine matrix m (int64 [6] or
+        [B, 6]; rectify.matrices) into out_size = (out_h, out_w) on the device (ops.warp_affine_u8): the resampler of the rectified
+        per-line path.  Returns uint8 [B, out_h, out_w, C] on the device, with coverage=True also the coverage [B, out_h, out_w]."""
+        t = image if isinstance(image, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(image))
+        t = t[None] if t.dim() == 3 else t
+        if t.dtype != torch.uint8 or t.dim() != 4:
+            raise ValueError(f"warp_affine: the image must be uint8 [H, W, C] or [B, H, W, C], got {t.dtype} {tuple(t.shape)}")
+        return ops.warp_affine_u8(t.to(self._execution_device).contiguous(), m, out_size, coverage=coverage)
 
     def _generic_loop(self, latents, masked_image_latents, prompt_embeds, pooled, text_ids, latent_image_ids, timesteps,
                       guidance, callback_on_step_end, callback_tensor_inputs, progress_bar):

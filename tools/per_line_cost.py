@@ -1,13 +1,16 @@
 #!/usr/bin/env python3
-"""What a multi-line scene costs on each of its four paths (DESIGN.md section 4 "Per-line edits"), on one GPU, in ONE process:
+"""What a multi-line scene costs on each of its five paths (DESIGN.md section 4 "Per-line edits"), on one GPU, in ONE process:
 
     canvas            today's multi-line canvas: all lines rendered onto a full-size glyph image stacked with the scene
     region            today's paste_back region: the bounding box of ALL lines together
     per_line          paste_back per_line: one single-line strip edit per line, each through its own region
     per_line_color    the same with color_match
+    per_line_rectify  per_line with rectify: a slanted line is edited upright (DESIGN.md section 4 "Rectified lines"); on a scene
+                      without a slanted line it is per_line
 
-Scenes: glyph.synthetic_case(1024, 1024, multiline=True) (two lines, 768 and 512 px wide), and a 2048 x 1536 photo with two lines in
-opposite corners, neither wider than a quarter of the photo.  Full depth, random weights (as bench.py), 30 Euler steps, step graphs
+Scenes: glyph.synthetic_case(1024, 1024, multiline=True) (two lines, 768 and 512 px wide), a 2048 x 1536 photo with two lines in
+opposite corners, neither wider than a quarter of the photo, and ("slanted", not in the default set) that photo with its second line
+turned by 25 degrees.  Full depth, random weights (as bench.py), 30 Euler steps, step graphs
 on; random stand-ins for the prompt embeddings (no text encoder runs: it costs the same in every arm).  The arms alternate, each
 `--reps` times after one warm-up pass; the wall clock of the whole run_items call is recorded (device synchronised on both sides),
 and device-event timings of the two colour-matching kernels at each scene's first line's region.  Every run goes into the output
@@ -17,7 +20,7 @@ medians smaller than the larger of their spreads is reported as "no difference".
 The first two arms are the same commit's unchanged paths.  Image content on random weights says nothing about quality; this tool
 claims none.
 
-    python tools/per_line_cost.py [--scenes 1024 2048] [--steps 30] [--reps 2] [--layers 19 38] [--out profiles/per_line_cost.json]"""
+    python tools/per_line_cost.py [--scenes 1024 2048 slanted] [--steps 30] [--reps 2] [--layers 19 38] [--out profiles/per_line_cost.json]"""
 import argparse
 import json
 import os
@@ -31,7 +34,8 @@ REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, REPO)
 sys.path.insert(0, os.path.join(REPO, "tools"))
 
-ARMS = {"canvas": None, "region": dict(region={}), "per_line": dict(per_line=True), "per_line_color": dict(per_line=True, color_match=True)}
+ARMS = {"canvas": None, "region": dict(region={}), "per_line": dict(per_line=True), "per_line_color": dict(per_line=True, color_match=True),
+        "per_line_rectify": dict(per_line=True, rectify=True)}
 
 
 def scenes(which):
@@ -46,11 +50,21 @@ def scenes(which):
         m[128:224, 128:640] = 255                 # 512 x 96, top left
         m[1312:1408, 1472:1920] = 255             # 448 x 96, bottom right
         out["2048x1536"] = (scene, Image.fromarray(m).convert("RGB"), words)
+    if "slanted" in which:
+        import math
+        from PIL import ImageDraw
+        scene, _, words = glyph.synthetic_case(2048, 1536, multiline=True)
+        im = Image.new("L", (2048, 1536), 0)
+        d = ImageDraw.Draw(im)
+        d.rectangle((128, 128, 639, 223), fill=255)                              # 512 x 96, top left, level
+        c, s = math.cos(math.radians(25)), math.sin(math.radians(25))
+        d.polygon([(1600 + u * c - v * s, 1200 + u * s + v * c) for u, v in ((-224, -48), (224, -48), (224, 48), (-224, 48))], fill=255)
+        out["2048x1536_slanted"] = (scene, im.convert("RGB"), words)             # 448 x 96 at 25 degrees, bottom right
     return out
 
 
-def token_arithmetic(scene, mask, words):
-    """Image tokens of every arm's pipeline calls, from the preparation alone."""
+def token_arithmetic(scene, mask, words, warp=None):
+    """Image tokens of every arm's pipeline calls, from the preparation alone (warp: the pipeline's warp_affine, for the rectified arm)."""
     from textflux_amd import batch_driver as bd
     from textflux_amd import per_line as pl
     item = dict(image="s", mask="m", text="\n".join(words))
@@ -59,7 +73,7 @@ def token_arithmetic(scene, mask, words):
     out = {}
     for arm, pb in ARMS.items():
         if pb is not None and pb.get("per_line"):
-            works = pl.prepare_lines(0, item, load, True, None, cfg(pb))
+            works = pl.prepare_lines(0, item, load, True, None, cfg(pb), warp=warp if pb.get("rectify") else None)
         else:
             works = [bd.prepare_item(0, item, load, device_compose=True, **({} if pb is None else dict(paste_back=cfg(pb))))]
         toks = [bd.image_tokens(w.size) for w in works]
@@ -88,7 +102,7 @@ def kernel_times(scene, mask, words, iters=20, warmup=3):
 
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
-    ap.add_argument("--scenes", nargs="*", default=["1024", "2048"], choices=["1024", "2048"])
+    ap.add_argument("--scenes", nargs="*", default=["1024", "2048"], choices=["1024", "2048", "slanted"])
     ap.add_argument("--steps", type=int, default=30)
     ap.add_argument("--reps", type=int, default=2)
     ap.add_argument("--layers", type=int, nargs=2, default=[19, 38])
@@ -108,7 +122,7 @@ def main():
             json.dump(out, f, indent=1)
 
     for name, (scene, mask, words) in scenes(a.scenes).items():
-        sc = out["scenes"][name] = dict(words=words, arithmetic=token_arithmetic(scene, mask, words),
+        sc = out["scenes"][name] = dict(words=words, arithmetic=token_arithmetic(scene, mask, words, pipe.warp_affine),
                                         kernels=kernel_times(scene, mask, words), runs={arm: [] for arm in a.arms})
         item = [dict(image="s", mask="m", text="\n".join(words))]
         load = lambda p: scene if p == "s" else mask
