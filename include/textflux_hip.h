@@ -536,6 +536,28 @@ int tfx_overlay_lut_u8(const void* orig, const void* edit, const void* alpha, co
  *      the image. */
 int tfx_warp_affine_u8(const void* in, void* out, void* coverage, int32_t B, int32_t H, int32_t W, int32_t C, int32_t out_h, int32_t out_w,
                        const int64_t* m, const int16_t* taps, tfx_stream stream);
+/* ---- perspective per-line edits (DESIGN.md section 4 "Perspective lines"): a text line seen at an angle is cut as a quadrilateral,
+ *      edited upright and warped back under a homography.  Added without a new TFX_ABI_VERSION: one new entry point, no stamped struct
+ *      and no existing entry point changes.  The tensor contract is tfx_warp_affine_u8's: contiguous, batch-major; B, H, W, out_h,
+ *      out_w >= 1, B <= 65535, C in 1..4; in, out and coverage are three different buffers; m and taps are 8-byte aligned DEVICE
+ *      pointers; taps is the same i16 [256][4] table.  Integer arithmetic throughout, so the results are exact.
+ * tfx_warp_perspective_u8: in u8 [B, H, W, C] -> out u8 [B, out_h, out_w, C] (coverage: NULL or u8 [B, out_h, out_w]) under
+ *      m i64 [B][9] (one matrix per sample).  Per destination pixel (i, j), in 64-bit integers:
+ *          Nx = m0 i + m1 j + m2,  Ny = m3 i + m4 j + m5,  D = m6 i + m7 j + m8
+ *          D <= 0:  out = 0 on every channel, coverage = 0, and NO read of `in`         (the pixel lies at or behind the horizon)
+ *          D >  0:  PX = floor((Nx * 256) / D),  PY = floor((Ny * 256) / D)             (floor, not truncation: a negative numerator
+ *                   rounds DOWN; Nx * 256 is formed with wrapping, as an unsigned shift left by 8 does)
+ *                   xi = PX >> 8, fx = PX & 255; yi, fy from PY alike
+ *                   acc = sum over r, k in 0..3 of taps[fy][r] taps[fx][k] in[b, clamp(yi - 1 + r, 0, H - 1), clamp(xi - 1 + k, 0, W - 1), c]
+ *                   out = clamp((acc + 2^27) >> 28, 0, 255);  coverage = 255 where 0 <= xi < W and 0 <= yi < H, else 0
+ *                   -- from xi, fx, yi, fy on exactly as in tfx_warp_affine_u8.
+ *      The caller keeps |Nx|, |Ny| < 2^54 and 0 < D < 2^54 over the destination wherever it wants a defined pixel (the * 256 then stays
+ *      inside 64 bits).  Whatever m holds the call is memory-safe: the products wrap, the division is guarded by D <= 0, and the indices are
+ *      clamped in 64 bits before they are narrowed, so no read leaves `in`.
+ *      Affine embedding: with m6 = m7 = 0, m8 = 2^16 and m0..m5 a Q16 affine matrix the result is tfx_warp_affine_u8's bit for bit
+ *      (floor(X 256 / 2^16) = X >> 8). */
+int tfx_warp_perspective_u8(const void* in, void* out, void* coverage, int32_t B, int32_t H, int32_t W, int32_t C, int32_t out_h,
+                            int32_t out_w, const int64_t* m, const int16_t* taps, tfx_stream stream);
 /* out[b, t, col0 + (i*8+j)*4 + py*2+px] = mask[(2ty+py)*8 + i, (2tx+px)*8 + j]  (P:1563-1580: 8x8 pixel blocks -> channels,
  * then _pack_latents), t = ty * (W/16) + tx, row stride ld. */
 int tfx_pack_mask(const void* mask, int32_t mask_dtype, void* out, int32_t B, int32_t H, int32_t W, int32_t mask_batch,

@@ -91,6 +91,12 @@ def build_parser(lora: bool = False):
                     "(implies --paste_rectify)")
     ap.add_argument("--paste_rectify_max_angle", type=float, default=None, metavar="DEG", help="largest slant that is rectified, default 45 "
                     "(implies --paste_rectify)")
+    ap.add_argument("--paste_perspective", action="store_true", help="edit a text line seen in perspective upright: cut it as a quadrilateral, "
+                    "warp it upright under a homography, edit it and warp the result back (with --paste_back --paste_per_line)")
+    ap.add_argument("--paste_perspective_max_fit", type=float, default=None, metavar="F", help="largest quad area / minimum-area rectangle "
+                    "area that still counts as perspective, default 0.9 (implies --paste_perspective)")
+    ap.add_argument("--paste_perspective_max_taper", type=float, default=None, metavar="R", help="largest ratio of opposite sides, default 4 "
+                    "(implies --paste_perspective)")
     ap.add_argument("--items", type=str, default=None, help="JSON list of {image, mask, text} instead of --json_path")
     ap.add_argument("--out", type=str, default=None, help="output folder of --items mode")
     ap.add_argument("--num_inference_steps", type=int, default=None, help=argparse.SUPPRESS)
@@ -163,6 +169,13 @@ def main(argv=None, lora: bool = False, script: str = __file__):
             raise SystemExit(f"--{rectify_given[0]} needs --paste_back --paste_per_line")
         angles = {k: getattr(a, "paste_rectify_" + k) for k in ("min_angle", "max_angle") if getattr(a, "paste_rectify_" + k) is not None}
         paste_back["rectify"] = angles or True
+    perspective_given = [f for f in ("paste_perspective", "paste_perspective_max_fit", "paste_perspective_max_taper")
+                         if getattr(a, f) not in (None, False)]
+    if perspective_given:
+        if not (a.paste_back and a.paste_per_line):
+            raise SystemExit(f"--{perspective_given[0]} needs --paste_back --paste_per_line")
+        limits = {k: getattr(a, "paste_perspective_" + k) for k in ("max_fit", "max_taper") if getattr(a, "paste_perspective_" + k) is not None}
+        paste_back["perspective"] = limits or True
     legacy = a.items is not None
     weights = a.lora_weights_path if lora else a.weights_path
     if not legacy and not (a.json_path and a.original_images_dir and weights):

@@ -53,8 +53,8 @@ class Work:
     region: Any = None               # ... and the paste_back.Region of it that was edited (the whole image without `region`)
     parent: Optional[int] = None     # per-line editing only (per_line.py): the index of the item this line belongs to ...
     line: Optional[int] = None       # ... and the line's position in the item's split order
-    rect: Any = None                 # rectified lines only (rectify.py): the oriented rectify.Rect that was edited upright; `region` is then
-                                     # the scene window it is pasted into
+    rect: Any = None                 # rectified lines only (rectify.py): the oriented rectify.Rect that was edited upright; perspective lines
+                                     # only (perspective.py): the perspective.Quad that was.  `region` is then the scene window it is pasted into
 
 
 @dataclass
@@ -73,10 +73,10 @@ def eval_item_complete(item: Dict[str, Any]) -> bool:
 def _paste_back_cfg(paste_back: Dict[str, Any]) -> Dict[str, Any]:
     """run_items' paste_back argument with its defaults filled in: dict(dilate, feather, region: None | dict(pad, min_side, max_side)),
     and, only when the caller gave them, per_line: True (which implies a region: {} when absent) and color_match: paste_back.
-    color_match_cfg's dict(ring, gain, max_shift, min_pixels), and rectify: rectify.rectify_cfg's dict(min_angle, max_angle, min_aspect)
-    (needs per_line)."""
+    color_match_cfg's dict(ring, gain, max_shift, min_pixels), rectify: rectify.rectify_cfg's dict(min_angle, max_angle, min_aspect)
+    and perspective: perspective.perspective_cfg's dict(max_fit, max_taper, min_aspect, max_angle) (both need per_line)."""
     from . import paste_back as pb
-    unknown = set(paste_back) - {"dilate", "feather", "region", "per_line", "color_match", "rectify"}
+    unknown = set(paste_back) - {"dilate", "feather", "region", "per_line", "color_match", "rectify", "perspective"}
     region = paste_back.get("region")
     if region is not None:
         unknown |= {f"region.{k}" for k in set(region) - {"pad", "min_side", "max_side"}}
@@ -113,6 +113,17 @@ def _paste_back_cfg(paste_back: Dict[str, Any]) -> Dict[str, Any]:
             cfg["rectify"] = rc.rectify_cfg(rectify)
         except ValueError as e:
             raise ValueError(f"paste_back: {e}") from None
+    perspective = paste_back.get("perspective")
+    if perspective is not None and perspective is not False:
+        if perspective is not True and not isinstance(perspective, dict):
+            raise ValueError("paste_back: perspective must be None, True or a dict")
+        if not per_line:
+            raise ValueError("paste_back: perspective needs per_line=True (only single-line edits are cut as quads)")
+        from . import perspective as ps
+        try:
+            cfg["perspective"] = ps.perspective_cfg(perspective)
+        except ValueError as e:
+            raise ValueError(f"paste_back: {e}") from None
     return cfg
 
 
@@ -141,6 +152,20 @@ def _host_u8(x):
     return np.ascontiguousarray(a[0] if a.ndim == 4 else a)
 
 
+def _warped_inputs(so, mo, warp: Callable, fwd, size, edit_size):
+    """The scene and the RGB mask warped into an upright frame `size` = (w, h) under `fwd` by `warp` (the device kernel), the mask
+    binarised at >= 128, both resized to edit_size with PIL's bicubic when that differs -> (scene, mask) as PIL images."""
+    import numpy as np
+    from PIL import Image
+    w, h = size
+    s = _host_u8(warp(so, fwd, (h, w)))
+    m = np.where(_host_u8(warp(mo if mo.ndim == 3 else mo[:, :, None], fwd, (h, w))) >= 128, 255, 0).astype(np.uint8)
+    s, m = Image.fromarray(s), Image.fromarray(m if mo.ndim == 3 else m[:, :, 0])
+    if s.size != tuple(edit_size):
+        s, m = s.resize(tuple(edit_size), Image.BICUBIC), m.resize(tuple(edit_size), Image.BICUBIC)
+    return s, m
+
+
 def _rectified_inputs(scene, mask, cfg: Dict[str, Any], warp: Callable):
     """_paste_back_inputs for a line that is edited upright (DESIGN.md section 4 "Rectified lines"), or None when the line stays on
     the unrectified path (rectify.plan).  -> (scene, mask, originals, Region, Rect): the scene and the RGB mask warped into the oriented
@@ -148,7 +173,6 @@ def _rectified_inputs(scene, mask, cfg: Dict[str, Any], warp: Callable):
     on the host), the mask binarised at >= 128, both resized to the editing size (tw, th) with PIL's bicubic when that differs.  The
     Region is the scene window the result is pasted into: the rectangle's bounding box cut at the image."""
     import numpy as np
-    from PIL import Image
     from . import paste_back as pb
     from . import rectify as rc
     so, mo = np.array(scene), np.array(mask)
@@ -156,19 +180,33 @@ def _rectified_inputs(scene, mask, cfg: Dict[str, Any], warp: Callable):
     if rect is None:
         return None
     x0, y0, x1, y1 = rc.rect_window(rect, scene.size)
-    fwd, _ = rc.matrices(rect)
-    s = _host_u8(warp(so, fwd, (rect.rh, rect.rw)))
-    m = np.where(_host_u8(warp(mo if mo.ndim == 3 else mo[:, :, None], fwd, (rect.rh, rect.rw))) >= 128, 255, 0).astype(np.uint8)
-    s, m = Image.fromarray(s), Image.fromarray(m if mo.ndim == 3 else m[:, :, 0])
-    if s.size != (rect.tw, rect.th):
-        s, m = s.resize((rect.tw, rect.th), Image.BICUBIC), m.resize((rect.tw, rect.th), Image.BICUBIC)
+    s, m = _warped_inputs(so, mo, warp, rc.matrices(rect)[0], (rect.rw, rect.rh), (rect.tw, rect.th))
     return s, m, so, mo, pb.Region(x0, y0, x1, y1, rect.tw, rect.th), rect
 
 
-def _edit_inputs(scene, mask, cfg: Dict[str, Any], warp: Optional[Callable]):
-    """(scene, mask, the Work's paste-back fields): _rectified_inputs where the cfg asks for it, a warp is at hand and the line
-    qualifies; _paste_back_inputs otherwise."""
-    got = _rectified_inputs(scene, mask, cfg, warp) if (warp is not None and cfg.get("rectify")) else None
+def _perspective_inputs(scene, mask, cfg: Dict[str, Any], warp_quad: Callable):
+    """_rectified_inputs for a line seen in perspective (DESIGN.md section 4 "Perspective lines"), or None when the line stays on the
+    other paths (perspective.plan).  -> (scene, mask, originals, Region, Quad): the scene and the RGB mask warped into the quad's upright
+    crop (rw, rh) by `warp_quad` (the pipeline's warp_perspective), prepared as _rectified_inputs does.  The Region is the scene window the
+    result is pasted into: the crop's footprint's bounding box cut at the image."""
+    import numpy as np
+    from . import paste_back as pb
+    from . import perspective as ps
+    so, mo = np.array(scene), np.array(mask)
+    quad = ps.plan(pb.grey_of(mo), cfg)
+    if quad is None:
+        return None
+    x0, y0, x1, y1 = ps.quad_window(quad, scene.size)
+    s, m = _warped_inputs(so, mo, warp_quad, ps.matrices(quad)[0], (quad.rw, quad.rh), (quad.tw, quad.th))
+    return s, m, so, mo, pb.Region(x0, y0, x1, y1, quad.tw, quad.th), quad
+
+
+def _edit_inputs(scene, mask, cfg: Dict[str, Any], warp: Optional[Callable], warp_quad: Optional[Callable] = None):
+    """(scene, mask, the Work's paste-back fields): _perspective_inputs where the cfg asks for it, a perspective warp is at hand and the
+    line qualifies; otherwise _rectified_inputs under the same three conditions; _paste_back_inputs otherwise."""
+    got = _perspective_inputs(scene, mask, cfg, warp_quad) if (warp_quad is not None and cfg.get("perspective")) else None
+    if got is None:
+        got = _rectified_inputs(scene, mask, cfg, warp) if (warp is not None and cfg.get("rectify")) else None
     if got is not None:
         scene, mask, so, mo, reg, rect = got
         return scene, mask, dict(orig_scene=so, orig_mask=mo, region=reg, rect=rect)
@@ -178,13 +216,14 @@ def _edit_inputs(scene, mask, cfg: Dict[str, Any], warp: Optional[Callable]):
 
 def prepare_eval_item(index: int, item: Dict[str, Any], original_images_dir: str, font, text_height_ratio: float = 0.1667,
                       loader: Optional[Callable] = None, device_compose: bool = False, paste_back: Optional[Dict[str, Any]] = None,
-                      annotation: int = 0, warp: Optional[Callable] = None) -> Work:
+                      annotation: int = 0, warp: Optional[Callable] = None, warp_quad: Optional[Callable] = None) -> Work:
     """One `annos.json` entry -> Work (scripts/run_eval.py:76-112): scene = original_images_dir / img_name; mask = the first
     annotation's polygon filled white on black; glyph strip of height int(w * text_height_ratio) -- a fraction of the image
     WIDTH -- with the annotation's text, stacked on top with a black mask; pipeline size ((w // 32) * 32,
     ((h + strip) // 32) * 32); T5 prompt generate_prompt([text]).  annotation: which entry of `annotations` (the reference, and
     every caller but per-line editing, reads the first).  warp: the pipeline's warp_affine, given by per-line editing when
-    paste_back["rectify"] is set: a slanted line is then edited upright (_rectified_inputs)."""
+    paste_back["rectify"] is set: a slanted line is then edited upright (_rectified_inputs).  warp_quad: the pipeline's
+    warp_perspective, given when paste_back["perspective"] is set: a line seen in perspective is then cut as a quad (_perspective_inputs)."""
     import numpy as np
     from PIL import Image
     load = loader or (lambda p: Image.open(p))
@@ -195,7 +234,7 @@ def prepare_eval_item(index: int, item: Dict[str, Any], original_images_dir: str
     m = glyph.fill_polygon(h, w, ann["polygon"])
     extra = {}
     if paste_back is not None:       # the strip, the stacking and the sizes below are then those of the edited region
-        scene, mk, extra = _edit_inputs(scene, Image.fromarray(m), paste_back, warp)
+        scene, mk, extra = _edit_inputs(scene, Image.fromarray(m), paste_back, warp, warp_quad)
         (w, h), m = scene.size, np.array(mk)
     strip = int(w * text_height_ratio)
     g = np.array(glyph.draw_glyph(font, text, w, strip))
@@ -228,13 +267,14 @@ def prepare_item(index: int, item: Dict[str, Any], loader: Optional[Callable] = 
 
 
 def prepare_plain(index: int, scene, mask, words: Sequence[str], device_compose: bool = False,
-                  paste_back: Optional[Dict[str, Any]] = None, warp: Optional[Callable] = None) -> Work:
+                  paste_back: Optional[Dict[str, Any]] = None, warp: Optional[Callable] = None,
+                  warp_quad: Optional[Callable] = None) -> Work:
     """prepare_item's rule for an {image, mask, text} item whose RGB scene and mask are loaded and whose text is split into words.
-    warp: as in prepare_eval_item."""
+    warp, warp_quad: as in prepare_eval_item."""
     from PIL import Image
     extra = {}
     if paste_back is not None:
-        scene, mask, extra = _edit_inputs(scene, mask, paste_back, warp)
+        scene, mask, extra = _edit_inputs(scene, mask, paste_back, warp, warp_quad)
     g, s_, m, horizontal, meta = glyph.compose_parts(scene, mask, words)
     H, W = (s_.shape[0], g.shape[1] + s_.shape[1]) if horizontal else (g.shape[0] + s_.shape[0], s_.shape[1])
     w, h = (W // 32) * 32, (H // 32) * 32
@@ -403,7 +443,10 @@ def run_items(items: Sequence[Dict[str, Any]], pipe, out_dir: Optional[str], bat
     rectify=True | dict(min_angle, max_angle, min_aspect) (with per_line; DESIGN.md section 4 "Rectified lines"): a line whose
     minimum-area rectangle is slanted by min_angle..max_angle degrees (defaults 5 and 45) and at least min_aspect (1.5) times as long
     as thick is cut as an oriented rectangle, warped upright on the device (pipe.warp_affine), edited upright and warped back into the
-    scene under the same alpha; every other line is edited as without the key."""
+    scene under the same alpha; every other line is edited as without the key.
+    perspective=True | dict(max_fit, max_taper, min_aspect, max_angle) (with per_line; DESIGN.md section 4 "Perspective lines"): a line
+    whose outline is a tapering quadrilateral (perspective.is_perspective) is cut through the homography of that quad, warped upright on
+    the device (pipe.warp_perspective), edited upright and warped back under the same alpha.  It is tried before rectify; both may be set."""
     if paste_back is not None:       # refused before anything is prepared or encoded
         if mixed_pad > 0:
             raise NotImplementedError("paste_back does not serve mixed-geometry batches (mixed_pad > 0)")
@@ -412,6 +455,8 @@ def run_items(items: Sequence[Dict[str, Any]], pipe, out_dir: Optional[str], bat
         paste_back = _paste_back_cfg(paste_back)
         if paste_back.get("rectify") and not hasattr(pipe, "warp_affine"):
             raise ValueError("paste_back: rectify needs a pipeline with warp_affine (FluxFillPipeline)")
+        if paste_back.get("perspective") and not hasattr(pipe, "warp_perspective"):
+            raise ValueError("paste_back: perspective needs a pipeline with warp_perspective (FluxFillPipeline)")
     if step_cache is not None:
         if mixed_pad > 0:
             raise NotImplementedError("step_cache does not serve mixed-geometry batches (mixed_pad > 0)")
@@ -449,7 +494,8 @@ def _run_items(items, pipe, out_dir, batch_size, num_inference_steps, guidance_s
             if per_line:
                 from . import per_line as pl
                 lines[i] = pl.prepare_lines(i, it, loader, device_compose, eval_cfg, paste_back,
-                                            warp=pipe.warp_affine if paste_back.get("rectify") else None)
+                                            warp=pipe.warp_affine if paste_back.get("rectify") else None,
+                                            warp_quad=pipe.warp_perspective if paste_back.get("perspective") else None)
                 works.extend(lines[i])
             else:
                 works.append(prepare_item(i, it, loader, device_compose=device_compose,

@@ -533,19 +533,13 @@ __global__ __launch_bounds__(256) void overlay_lut_u8_kernel(const uint8_t* orig
 // of about 40 x 25 pixels that stays in cache.  The sample's matrix sits at an address that is uniform over the workgroup, so it is
 // read once per workgroup, not once per thread.  Every index is clamped into the image in 64 bits before it is narrowed: whatever the
 // matrix holds, no load leaves `in`.
+// warp_sample_u8: the part both warps share.  One destination pixel (its C bytes at `dst`, its coverage byte at `cov` unless NULL) from
+// the sample `src` [H, W, C] at the integer position (xi, yi) with the fractions fx, fy in 0..255.
 template <int C>
-__global__ __launch_bounds__(256) void warp_affine_u8_kernel(const uint8_t* __restrict__ in, uint8_t* __restrict__ out,
-                                                             uint8_t* __restrict__ coverage, int H, int W, int out_h, int out_w,
-                                                             const int64_t* __restrict__ m, const int16_t* __restrict__ taps) {
-  const int b = blockIdx.z;
-  const int64_t* mb = m + (int64_t)b * 6;
-  const int64_t m0 = mb[0], m1 = mb[1], m2 = mb[2], m3 = mb[3], m4 = mb[4], m5 = mb[5];
-  const int i = blockIdx.x * 32 + (threadIdx.x & 31), j = blockIdx.y * 8 + (threadIdx.x >> 5);
-  if (i >= out_w || j >= out_h) return;
-  const int64_t X = m0 * i + m1 * j + m2, Y = m3 * i + m4 * j + m5;        // Q16
-  const int64_t xi = X >> 16, yi = Y >> 16;
-  const int16_t* tx = taps + ((X >> 8) & 255) * 4;
-  const int16_t* ty = taps + ((Y >> 8) & 255) * 4;
+__device__ __forceinline__ void warp_sample_u8(const uint8_t* __restrict__ src, int H, int W, int64_t xi, int64_t yi, int fx, int fy,
+                                               const int16_t* __restrict__ taps, uint8_t* __restrict__ dst, uint8_t* __restrict__ cov) {
+  const int16_t* tx = taps + fx * 4;
+  const int16_t* ty = taps + fy * 4;
   int cx[4];
   int64_t row[4];
 #pragma unroll
@@ -554,7 +548,6 @@ __global__ __launch_bounds__(256) void warp_affine_u8_kernel(const uint8_t* __re
     cx[k] = (int)(x < 0 ? 0 : x > W - 1 ? W - 1 : x) * C;
     row[k] = (y < 0 ? 0 : y > H - 1 ? H - 1 : y) * (int64_t)W * C;
   }
-  const uint8_t* src = in + (int64_t)b * H * W * C;
   int64_t acc[C];
 #pragma unroll
   for (int c = 0; c < C; ++c) acc[c] = 0;
@@ -574,13 +567,60 @@ __global__ __launch_bounds__(256) void warp_affine_u8_kernel(const uint8_t* __re
 #pragma unroll
     for (int c = 0; c < C; ++c) acc[c] += wy * s[c];
   }
-  const int64_t o = ((int64_t)b * out_h + j) * out_w + i;
 #pragma unroll
   for (int c = 0; c < C; ++c) {
     const int64_t v = (acc[c] + ((int64_t)1 << 27)) >> 28;
-    out[o * C + c] = (uint8_t)(v < 0 ? 0 : v > 255 ? 255 : v);
+    dst[c] = (uint8_t)(v < 0 ? 0 : v > 255 ? 255 : v);
   }
-  if (coverage) coverage[o] = (xi >= 0 && xi < W && yi >= 0 && yi < H) ? 255 : 0;
+  if (cov) *cov = (xi >= 0 && xi < W && yi >= 0 && yi < H) ? 255 : 0;
+}
+
+template <int C>
+__global__ __launch_bounds__(256) void warp_affine_u8_kernel(const uint8_t* __restrict__ in, uint8_t* __restrict__ out,
+                                                             uint8_t* __restrict__ coverage, int H, int W, int out_h, int out_w,
+                                                             const int64_t* __restrict__ m, const int16_t* __restrict__ taps) {
+  const int b = blockIdx.z;
+  const int64_t* mb = m + (int64_t)b * 6;
+  const int64_t m0 = mb[0], m1 = mb[1], m2 = mb[2], m3 = mb[3], m4 = mb[4], m5 = mb[5];
+  const int i = blockIdx.x * 32 + (threadIdx.x & 31), j = blockIdx.y * 8 + (threadIdx.x >> 5);
+  if (i >= out_w || j >= out_h) return;
+  const int64_t X = m0 * i + m1 * j + m2, Y = m3 * i + m4 * j + m5;        // Q16
+  const int64_t o = ((int64_t)b * out_h + j) * out_w + i;
+  warp_sample_u8<C>(in + (int64_t)b * H * W * C, H, W, X >> 16, Y >> 16, (int)((X >> 8) & 255), (int)((Y >> 8) & 255), taps, out + o * C,
+                    coverage ? coverage + o : nullptr);
+}
+
+// ---- perspective per-line edits (DESIGN.md section 4 "Perspective lines"): the same resampler under a homography.  Per destination
+// pixel two rational positions Nx / D, Ny / D, brought to 8 fractional bits by a FLOOR division in 64-bit integers (the header spells
+// it out), then warp_sample_u8.  At or behind the horizon (D <= 0) the pixel is 0 with coverage 0 and `in` is not read.  The launch
+// shape is the affine kernel's.  Memory-safe whatever m holds: the linear forms and the * 256 wrap in unsigned arithmetic (no undefined
+// signed overflow), D > 0 rules out the two faulting divisions (by 0, INT64_MIN / -1), and warp_sample_u8 clamps in 64 bits.
+// Two plain 64-bit divisions per pixel: measured beside the affine warp by tools/perspective_cost.py.
+__device__ __forceinline__ int64_t floor_div_pos(int64_t n, int64_t d) {     // floor(n / d) for d > 0; C++ truncates towards zero
+  const int64_t q = n / d;
+  return (n % d < 0) ? q - 1 : q;
+}
+
+template <int C>
+__global__ __launch_bounds__(256) void warp_perspective_u8_kernel(const uint8_t* __restrict__ in, uint8_t* __restrict__ out,
+                                                                  uint8_t* __restrict__ coverage, int H, int W, int out_h, int out_w,
+                                                                  const int64_t* __restrict__ m, const int16_t* __restrict__ taps) {
+  const int b = blockIdx.z;
+  const uint64_t* mb = (const uint64_t*)m + (int64_t)b * 9;
+  const uint64_t i = blockIdx.x * 32 + (threadIdx.x & 31), j = blockIdx.y * 8 + (threadIdx.x >> 5);
+  if (i >= (uint64_t)out_w || j >= (uint64_t)out_h) return;
+  const uint64_t Nx = mb[0] * i + mb[1] * j + mb[2], Ny = mb[3] * i + mb[4] * j + mb[5];
+  const int64_t D = (int64_t)(mb[6] * i + mb[7] * j + mb[8]);
+  const int64_t o = ((int64_t)b * out_h + (int64_t)j) * out_w + (int64_t)i;
+  if (D <= 0) {
+#pragma unroll
+    for (int c = 0; c < C; ++c) out[o * C + c] = 0;
+    if (coverage) coverage[o] = 0;
+    return;
+  }
+  const int64_t PX = floor_div_pos((int64_t)(Nx << 8), D), PY = floor_div_pos((int64_t)(Ny << 8), D);
+  warp_sample_u8<C>(in + (int64_t)b * H * W * C, H, W, PX >> 8, PY >> 8, (int)(PX & 255), (int)(PY & 255), taps, out + o * C,
+                    coverage ? coverage + o : nullptr);
 }
 
 int compose_canvas(const void* glyph, const void* scene, const void* smask, void* canvas, void* cmask, int B, int gh, int gw, int sh,
@@ -726,6 +766,27 @@ int warp_affine_u8(const void* in, void* out, void* coverage, int B, int H, int 
     default: warp_affine_u8_kernel<4><<<grid, 256, 0, st>>>(pi, po, pc, H, W, out_h, out_w, m, taps); break;
   }
   return check_launch("warp_affine_u8");
+}
+
+int warp_perspective_u8(const void* in, void* out, void* coverage, int B, int H, int W, int C, int out_h, int out_w, const int64_t* m,
+                        const int16_t* taps, hipStream_t st) {
+  if (B < 1 || H < 1 || W < 1 || out_h < 1 || out_w < 1) return fail("warp_perspective_u8: B, H, W, out_h, out_w must be at least 1");
+  if (C < 1 || C > 4) return fail("warp_perspective_u8: 1..4 channels");
+  if (B > 65535) return fail("warp_perspective_u8: batch %d exceeds 65535", B);
+  if ((out_h + 7) / 8 > 65535) return fail("warp_perspective_u8: out_h %d exceeds 524280", out_h);
+  if ((int64_t)H * W * C > kMaxBytes || (int64_t)out_h * out_w * C > kMaxBytes) return fail("warp_perspective_u8: more than 2^38 bytes per sample");
+  if (in == out || in == coverage || out == coverage) return fail("warp_perspective_u8: in, out and coverage must be different buffers");
+  if (((uintptr_t)m | (uintptr_t)taps) & 7) return fail("warp_perspective_u8: m and taps must be 8-byte aligned");
+  const dim3 grid((out_w + 31) / 32, (out_h + 7) / 8, B);
+  const uint8_t* pi = (const uint8_t*)in;
+  uint8_t *po = (uint8_t*)out, *pc = (uint8_t*)coverage;
+  switch (C) {
+    case 1: warp_perspective_u8_kernel<1><<<grid, 256, 0, st>>>(pi, po, pc, H, W, out_h, out_w, m, taps); break;
+    case 2: warp_perspective_u8_kernel<2><<<grid, 256, 0, st>>>(pi, po, pc, H, W, out_h, out_w, m, taps); break;
+    case 3: warp_perspective_u8_kernel<3><<<grid, 256, 0, st>>>(pi, po, pc, H, W, out_h, out_w, m, taps); break;
+    default: warp_perspective_u8_kernel<4><<<grid, 256, 0, st>>>(pi, po, pc, H, W, out_h, out_w, m, taps); break;
+  }
+  return check_launch("warp_perspective_u8");
 }
 
 int pack_mask(const void* mask, int mask_dtype, void* out, int B, int H, int W, int mask_b, int binarize, int64_t ld, int col0,

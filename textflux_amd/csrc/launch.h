@@ -220,6 +220,10 @@ int overlay_lut_u8(const void* orig, const void* edit, const void* alpha, const 
 // destination pixel, 4 x 4 taps from the i16 [256][4] table (device), edge replicated; coverage [B, out_h, out_w] u8 or NULL
 int warp_affine_u8(const void* in, void* out, void* coverage, int B, int H, int W, int C, int out_h, int out_w, const int64_t* m,
                    const int16_t* taps, hipStream_t st);
+// perspective per-line edits: the same under a homography m i64 [B][9] (device): positions Nx / D, Ny / D by floor division to 8
+// fractional bits; D <= 0 writes 0 with coverage 0 and reads nothing
+int warp_perspective_u8(const void* in, void* out, void* coverage, int B, int H, int W, int C, int out_h, int out_w, const int64_t* m,
+                        const int16_t* taps, hipStream_t st);
 int pack_mask(const void* mask, int mask_dtype, void* out, int B, int H, int W, int mask_b, int binarize, int64_t ld, int col0,
               hipStream_t st);
 int sample_pack(const void* moments, const void* eps, int eps_dtype, void* out, int B, int h, int w, int L, float shift,

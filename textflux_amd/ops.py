@@ -771,24 +771,26 @@ def overlay_lut(orig: torch.Tensor, edit: torch.Tensor, alpha: torch.Tensor, lut
 _WARP_TAPS = {}
 
 
-def warp_affine_u8(x: torch.Tensor, m, out_size, coverage: bool = False):
-    """uint8 [B, H, W, C] (C in 1..4) -> [B, out_h, out_w, C]: every destination pixel (i, j) is x[b] sampled at its Q16 affine image
-    under m (int64 [B, 6] or [6], tensor or array: one matrix per sample, or one for all), 4 x 4 Catmull-Rom taps, edge replicated, in
-    integer arithmetic (tfx_warp_affine_u8; include/textflux_hip.h has the arithmetic, rectify.matrices builds m).  out_size =
-    (out_h, out_w).  coverage: also return uint8 [B, out_h, out_w], 255 where the sample position lies inside the image."""
+def _warp_u8(name: str, n: int, x: torch.Tensor, m, out_size, coverage: bool, host_check=None):
+    """warp_affine_u8 / warp_perspective_u8: the checks, the tap table and the call of tfx_<name> with n matrix entries per sample.
+    host_check(matrices [k, n] as a host array, out_h, out_w): applied when m arrives as a host array."""
     _chk_dev(x)
     if x.dtype != torch.uint8 or x.dim() != 4 or not x.is_contiguous() or x.numel() == 0 or not 1 <= x.shape[3] <= 4:
-        raise ValueError(f"warp_affine_u8: x must be a contiguous, non-empty uint8 [B, H, W, C <= 4] tensor, got {x.dtype} {tuple(x.shape)}")
+        raise ValueError(f"{name}: x must be a contiguous, non-empty uint8 [B, H, W, C <= 4] tensor, got {x.dtype} {tuple(x.shape)}")
     B, H, W, Cc = x.shape
     Ho, Wo = (int(v) for v in out_size)
     if Ho < 1 or Wo < 1:
-        raise ValueError(f"warp_affine_u8: out_size must be (out_h, out_w) with both at least 1, got {tuple(out_size)}")
+        raise ValueError(f"{name}: out_size must be (out_h, out_w) with both at least 1, got {tuple(out_size)}")
+    host = None
     if not isinstance(m, torch.Tensor):
         import numpy as np
-        m = torch.from_numpy(np.ascontiguousarray(m))
-    if m.dtype != torch.int64 or m.numel() not in (6, 6 * B) or m.shape[-1] != 6:
-        raise ValueError(f"warp_affine_u8: m must be int64 [{B}, 6] or [6], got {m.dtype} {tuple(m.shape)}")
-    m = m.reshape(-1, 6).expand(B, 6).to(x.device).contiguous()
+        host = np.ascontiguousarray(m)
+        m = torch.from_numpy(host)
+    if m.dtype != torch.int64 or m.numel() not in (n, n * B) or m.shape[-1] != n:
+        raise ValueError(f"{name}: m must be int64 [{B}, {n}] or [{n}], got {m.dtype} {tuple(m.shape)}")
+    if host is not None and host_check is not None:
+        host_check(host.reshape(-1, n), Ho, Wo)
+    m = m.reshape(-1, n).expand(B, n).to(x.device).contiguous()
     key = str(x.device)
     if key not in _WARP_TAPS:
         from .rectify import catmull_rom_taps
@@ -796,9 +798,38 @@ def warp_affine_u8(x: torch.Tensor, m, out_size, coverage: bool = False):
     taps = _WARP_TAPS[key]
     out = torch.empty(B, Ho, Wo, Cc, dtype=torch.uint8, device=x.device)
     cov = torch.empty(B, Ho, Wo, dtype=torch.uint8, device=x.device) if coverage else None
-    L.check(L.lib().tfx_warp_affine_u8(x.data_ptr(), out.data_ptr(), _p(cov), B, H, W, Cc, Ho, Wo, m.data_ptr(), taps.data_ptr(),
-                                       _stream()), "warp_affine_u8")
+    L.check(getattr(L.lib(), "tfx_" + name)(x.data_ptr(), out.data_ptr(), _p(cov), B, H, W, Cc, Ho, Wo, m.data_ptr(), taps.data_ptr(),
+                                            _stream()), name)
     return (out, cov) if coverage else out
+
+
+def warp_affine_u8(x: torch.Tensor, m, out_size, coverage: bool = False):
+    """uint8 [B, H, W, C] (C in 1..4) -> [B, out_h, out_w, C]: every destination pixel (i, j) is x[b] sampled at its Q16 affine image
+    under m (int64 [B, 6] or [6], tensor or array: one matrix per sample, or one for all), 4 x 4 Catmull-Rom taps, edge replicated, in
+    integer arithmetic (tfx_warp_affine_u8; include/textflux_hip.h has the arithmetic, rectify.matrices builds m).  out_size =
+    (out_h, out_w).  coverage: also return uint8 [B, out_h, out_w], 255 where the sample position lies inside the image."""
+    return _warp_u8("warp_affine_u8", 6, x, m, out_size, coverage)
+
+
+def _perspective_magnitudes(m, out_h: int, out_w: int) -> None:
+    """tfx_warp_perspective_u8's magnitude contract, in Python integers: the three forms are linear in (i, j), so over the destination
+    their extremes lie at its four corner pixels.  D <= 0 is allowed (defined: the pixel is 0 and uncovered)."""
+    lim = 1 << 54
+    for row in m.tolist():
+        for i, j in ((0, 0), (out_w - 1, 0), (0, out_h - 1), (out_w - 1, out_h - 1)):
+            nx, ny, d = (row[k] * i + row[k + 1] * j + row[k + 2] for k in (0, 3, 6))
+            if abs(nx) >= lim or abs(ny) >= lim or d >= lim:
+                raise ValueError(f"warp_perspective_u8: |Nx|, |Ny| and D must stay below 2^54 over the destination; at pixel ({i}, {j}) "
+                                 f"they are {nx}, {ny}, {d}")
+
+
+def warp_perspective_u8(x: torch.Tensor, m, out_size, coverage: bool = False):
+    """warp_affine_u8 under a homography: every destination pixel (i, j) is x[b] sampled at (Nx / D, Ny / D) with Nx = m0 i + m1 j + m2,
+    Ny = m3 i + m4 j + m5, D = m6 i + m7 j + m8 (m int64 [B, 9] or [9], tensor or array), the quotients floored to 8 fractional bits;
+    a pixel with D <= 0 is 0 and uncovered (tfx_warp_perspective_u8; include/textflux_hip.h has the arithmetic, perspective.matrices
+    builds m).  A host array is checked against the magnitude contract (|Nx|, |Ny|, D < 2^54 at the destination's corners: ValueError);
+    a device tensor is taken as it is, which is memory-safe but leaves such pixels undefined."""
+    return _warp_u8("warp_perspective_u8", 9, x, m, out_size, coverage, _perspective_magnitudes)
 
 
 def pack_mask(mask: torch.Tensor, out: torch.Tensor, col0: int, B: int, H: int, W: int, binarize: bool = True) -> torch.Tensor:

@@ -178,7 +178,9 @@ def paste(original: torch.Tensor, edited: torch.Tensor, mask_grey: torch.Tensor,
     scene window whose top-left pixel is scene pixel `origin`.  The edit is resampled to the rectangle's own size (rh, rw) and warped
     into the window (ops.warp_affine_u8 under rectify.matrices' upright -> scene matrix) instead of being resized to it; the alpha is
     still that of mask_grey, the line's ORIGINAL mask, so the bytes outside the grown mask stay the original's; with color_match the
-    ring is cut to the pixels the warp covered (their sample position lies inside the upright crop)."""
+    ring is cut to the pixels the warp covered (their sample position lies inside the upright crop).
+    rect may also be a perspective.Quad (DESIGN.md section 4 "Perspective lines"): the same, with the edit resampled to the quad's crop
+    (rh, rw) and warped by ops.warp_perspective_u8 under perspective.matrices' upright -> scene homography."""
     if original.dtype != torch.uint8 or original.dim() != 4 or edited.dtype != torch.uint8 or edited.dim() != 4:
         raise ValueError("paste: original and edited must be uint8 [B, H, W, C]")
     if edited.shape[0] != original.shape[0] or edited.shape[3] != original.shape[3] or mask_grey.shape != original.shape[:3]:
@@ -188,10 +190,14 @@ def paste(original: torch.Tensor, edited: torch.Tensor, mask_grey: torch.Tensor,
     original, edited = original.contiguous(), edited.contiguous()
     covered = None
     if rect is not None:
-        from . import rectify
+        from . import perspective, rectify
         if tuple(edited.shape[1:3]) != (rect.rh, rect.rw):
             edited = ops.resample_u8(edited, (rect.rh, rect.rw))
-        edited, covered = ops.warp_affine_u8(edited, rectify.matrices(rect, origin)[1], (original.shape[1], original.shape[2]), coverage=True)
+        size = (original.shape[1], original.shape[2])
+        if isinstance(rect, perspective.Quad):
+            edited, covered = ops.warp_perspective_u8(edited, perspective.matrices(rect, origin)[1], size, coverage=True)
+        else:
+            edited, covered = ops.warp_affine_u8(edited, rectify.matrices(rect, origin)[1], size, coverage=True)
     elif edited.shape[1:3] != original.shape[1:3]:
         edited = ops.resample_u8(edited, (original.shape[1], original.shape[2]))
     alpha = alpha_mask(mask_grey.contiguous(), dilate, feather)
