@@ -558,6 +558,34 @@ int tfx_warp_affine_u8(const void* in, void* out, void* coverage, int32_t B, int
  *      (floor(X 256 / 2^16) = X >> 8). */
 int tfx_warp_perspective_u8(const void* in, void* out, void* coverage, int32_t B, int32_t H, int32_t W, int32_t C, int32_t out_h,
                             int32_t out_w, const int64_t* m, const int16_t* taps, tfx_stream stream);
+/* ---- curved per-line edits (DESIGN.md section 4 "Curved lines"): a text line along a bend is cut along its own centre line, edited
+ *      upright and warped back; no single matrix expresses a bend, so this warp reads its source positions from a coarse control grid.
+ *      With shift = 0 it is a general per-pixel remap.  Added without a new TFX_ABI_VERSION: one new entry point, no stamped struct and
+ *      no existing entry point changes.  The tensor contract is tfx_warp_affine_u8's: contiguous, batch-major; B, H, W, out_h, out_w >= 1,
+ *      B <= 65535, C in 1..4; in, out and coverage are three different buffers; coverage may be NULL; grid and taps are 8-byte aligned
+ *      DEVICE pointers; taps is the same i16 [256][4] table.  Integer arithmetic throughout, so the results are exact.
+ * tfx_warp_grid_u8: in u8 [B, H, W, C] -> out u8 [B, out_h, out_w, C] (coverage: NULL or u8 [B, out_h, out_w]) under
+ *      grid i64 [B][gh][gw][2], shift in 0..5, c = 1 << shift the cell size in destination pixels,
+ *          gh = ((out_h - 1) >> shift) + 2,  gw = ((out_w - 1) >> shift) + 2
+ *      node (r, q) = the Q16 source position (x, y) of destination pixel (q c, r c); the pixel-centre convention is the affine warp's (the
+ *      caller folds it in).  Per destination pixel (i, j), in 64-bit integers:
+ *          gx = i >> shift, gy = j >> shift, ax = i & (c - 1), ay = j & (c - 1)
+ *          g00 = node (gy, gx), g01 = node (gy, gx + 1), g10 = node (gy + 1, gx), g11 = node (gy + 1, gx + 1)
+ *          the x of any of the four == INT64_MIN:  out = 0 on every channel, coverage = 0, and NO read of `in`   (the pixel has no source:
+ *                   the perspective kernel's horizon rule)
+ *          otherwise:  X = ((c - ax)(c - ay) g00x + ax (c - ay) g01x + (c - ax) ay g10x + ax ay g11x) >> (2 shift)    (an ARITHMETIC
+ *                   shift: it floors; products and sums are formed with wrapping, as unsigned arithmetic does);  Y alike from the y's
+ *                   xi = X >> 16, fx = (X >> 8) & 255; yi, fy from Y alike
+ *                   acc = sum over r, k in 0..3 of taps[fy][r] taps[fx][k] in[b, clamp(yi - 1 + r, 0, H - 1), clamp(xi - 1 + k, 0, W - 1), c]
+ *                   out = clamp((acc + 2^27) >> 28, 0, 255);  coverage = 255 where 0 <= xi < W and 0 <= yi < H, else 0
+ *                   -- from X, Y on exactly as in tfx_warp_affine_u8.
+ *      The caller keeps |g| < 2^50 on every unmarked component: the four weights sum to c^2 <= 2^10, so the sum stays inside 64 bits.
+ *      Whatever the grid holds the call is memory-safe: node indices lie inside [gh][gw] by the construction of gh and gw, the products
+ *      wrap, and the sample indices are clamped in 64 bits before they are narrowed, so no read leaves `in` or `grid`.
+ *      Affine embedding: nodes that hold a Q16 affine matrix evaluated at their pixels interpolate it exactly (the weighted sum is
+ *      c^2 X with no remainder), so the result is tfx_warp_affine_u8's bit for bit at every shift. */
+int tfx_warp_grid_u8(const void* in, void* out, void* coverage, int32_t B, int32_t H, int32_t W, int32_t C, int32_t out_h, int32_t out_w,
+                     const int64_t* grid, int32_t shift, const int16_t* taps, tfx_stream stream);
 /* out[b, t, col0 + (i*8+j)*4 + py*2+px] = mask[(2ty+py)*8 + i, (2tx+px)*8 + j]  (P:1563-1580: 8x8 pixel blocks -> channels,
  * then _pack_latents), t = ty * (W/16) + tx, row stride ld. */
 int tfx_pack_mask(const void* mask, int32_t mask_dtype, void* out, int32_t B, int32_t H, int32_t W, int32_t mask_batch,

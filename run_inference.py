@@ -49,7 +49,7 @@ def use_overshoot_sampler(pipe):
 def run_inference(image_input, mask_input, words_input, num_steps=50, guidance_scale=30, seed=42, pipe=None, paste_back=None):
     """paste_back (not in the reference): None, or dict(dilate, feather) -- the result is then blended back into the input image under
     the dilated and feathered mask and returned at the INPUT's size (FluxFillPipeline.paste_back) instead of at the pipeline's size.
-    With per_line=True in it (batch_driver.run_items' keys: region, color_match, rectify, perspective) the input is the plain scene and its mask: every text
+    With per_line=True in it (batch_driver.run_items' keys: region, color_match, rectify, perspective, curve) the input is the plain scene and its mask: every text
     line is edited through its own region with a single-line glyph strip and pasted into the scene (textflux_amd/per_line.py)."""
     image = (Image.open(image_input) if isinstance(image_input, str) else image_input).convert("RGB")
     mask = (Image.open(mask_input) if isinstance(mask_input, str) else mask_input).convert("RGB")
@@ -111,6 +111,12 @@ def add_paste_back_args(ap):
                     "area that still counts as perspective, default 0.9 (implies --paste_perspective)")
     ap.add_argument("--paste_perspective_max_taper", type=float, default=None, metavar="R", help="largest ratio of opposite sides, default 4 "
                     "(implies --paste_perspective)")
+    ap.add_argument("--paste_curve", action="store_true", help="edit a text line along a bend upright: cut it as a ribbon around its centre "
+                    "line, warp it upright through a control grid, edit it and warp the result back (with --paste_back --paste_per_line)")
+    ap.add_argument("--paste_curve_min_bend", type=float, default=None, metavar="F", help="smallest sagitta / thickness that counts as "
+                    "curved, default 0.2 (implies --paste_curve)")
+    ap.add_argument("--paste_curve_max_squeeze", type=float, default=None, metavar="F", help="largest crop reach / radius of curvature, "
+                    "default 0.75 (implies --paste_curve)")
 
 
 RECTIFY_FLAGS = ("paste_rectify", "paste_rectify_min_angle", "paste_rectify_max_angle")
@@ -143,10 +149,25 @@ def perspective_from_args(a):
     return limits or True
 
 
+CURVE_FLAGS = ("paste_curve", "paste_curve_min_bend", "paste_curve_max_squeeze")
+
+
+def curve_from_args(a):
+    """None, or the `curve` value of the paste_back dict (True, or a dict of the limits that were given).  The flags are refused without
+    --paste_back --paste_per_line."""
+    given = [f for f in CURVE_FLAGS if getattr(a, f, None) not in (None, False)]
+    if not given:
+        return None
+    if not (a.paste_back and getattr(a, "paste_per_line", False)):
+        raise SystemExit(f"--{given[0]} needs --paste_back --paste_per_line")
+    limits = {k: getattr(a, "paste_curve_" + k) for k in ("min_bend", "max_squeeze") if getattr(a, "paste_curve_" + k) is not None}
+    return limits or True
+
+
 def paste_back_from_args(a):
     """None, or the paste_back dict of batch_driver.run_items / process_normal_mode.  The per-line and colour keys appear only when
     their flags were given."""
-    rectify, perspective = rectify_from_args(a), perspective_from_args(a)
+    rectify, perspective, curve = rectify_from_args(a), perspective_from_args(a), curve_from_args(a)
     if not a.paste_back:
         for flag in ("paste_region", "paste_per_line", "paste_color_match", "paste_color_ring"):
             if getattr(a, flag, None) not in (None, False):
@@ -163,6 +184,8 @@ def paste_back_from_args(a):
         pb["rectify"] = rectify
     if perspective is not None:
         pb["perspective"] = perspective
+    if curve is not None:
+        pb["curve"] = curve
     return pb
 
 

@@ -97,6 +97,12 @@ def build_parser(lora: bool = False):
                     "area that still counts as perspective, default 0.9 (implies --paste_perspective)")
     ap.add_argument("--paste_perspective_max_taper", type=float, default=None, metavar="R", help="largest ratio of opposite sides, default 4 "
                     "(implies --paste_perspective)")
+    ap.add_argument("--paste_curve", action="store_true", help="edit a text line along a bend upright: cut it as a ribbon around its centre "
+                    "line, warp it upright through a control grid, edit it and warp the result back (with --paste_back --paste_per_line)")
+    ap.add_argument("--paste_curve_min_bend", type=float, default=None, metavar="F", help="smallest sagitta / thickness that counts as "
+                    "curved, default 0.2 (implies --paste_curve)")
+    ap.add_argument("--paste_curve_max_squeeze", type=float, default=None, metavar="F", help="largest crop reach / radius of curvature, "
+                    "default 0.75 (implies --paste_curve)")
     ap.add_argument("--items", type=str, default=None, help="JSON list of {image, mask, text} instead of --json_path")
     ap.add_argument("--out", type=str, default=None, help="output folder of --items mode")
     ap.add_argument("--num_inference_steps", type=int, default=None, help=argparse.SUPPRESS)
@@ -176,6 +182,12 @@ def main(argv=None, lora: bool = False, script: str = __file__):
             raise SystemExit(f"--{perspective_given[0]} needs --paste_back --paste_per_line")
         limits = {k: getattr(a, "paste_perspective_" + k) for k in ("max_fit", "max_taper") if getattr(a, "paste_perspective_" + k) is not None}
         paste_back["perspective"] = limits or True
+    curve_given = [f for f in ("paste_curve", "paste_curve_min_bend", "paste_curve_max_squeeze") if getattr(a, f) not in (None, False)]
+    if curve_given:
+        if not (a.paste_back and a.paste_per_line):
+            raise SystemExit(f"--{curve_given[0]} needs --paste_back --paste_per_line")
+        limits = {k: getattr(a, "paste_curve_" + k) for k in ("min_bend", "max_squeeze") if getattr(a, "paste_curve_" + k) is not None}
+        paste_back["curve"] = limits or True
     legacy = a.items is not None
     weights = a.lora_weights_path if lora else a.weights_path
     if not legacy and not (a.json_path and a.original_images_dir and weights):

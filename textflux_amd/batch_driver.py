@@ -54,7 +54,8 @@ class Work:
     parent: Optional[int] = None     # per-line editing only (per_line.py): the index of the item this line belongs to ...
     line: Optional[int] = None       # ... and the line's position in the item's split order
     rect: Any = None                 # rectified lines only (rectify.py): the oriented rectify.Rect that was edited upright; perspective lines
-                                     # only (perspective.py): the perspective.Quad that was.  `region` is then the scene window it is pasted into
+                                     # only (perspective.py): the perspective.Quad that was; curved lines only (curve.py): the curve.Ribbon.
+                                     # `region` is then the scene window it is pasted into
 
 
 @dataclass
@@ -74,9 +75,10 @@ def _paste_back_cfg(paste_back: Dict[str, Any]) -> Dict[str, Any]:
     """run_items' paste_back argument with its defaults filled in: dict(dilate, feather, region: None | dict(pad, min_side, max_side)),
     and, only when the caller gave them, per_line: True (which implies a region: {} when absent) and color_match: paste_back.
     color_match_cfg's dict(ring, gain, max_shift, min_pixels), rectify: rectify.rectify_cfg's dict(min_angle, max_angle, min_aspect)
-    and perspective: perspective.perspective_cfg's dict(max_fit, max_taper, min_aspect, max_angle) (both need per_line)."""
+    perspective: perspective.perspective_cfg's dict(max_fit, max_taper, min_aspect, max_angle) and curve: curve.curve_cfg's
+    dict(min_bend, max_squeeze, max_turn, min_aspect, min_fill, max_angle) (all three need per_line)."""
     from . import paste_back as pb
-    unknown = set(paste_back) - {"dilate", "feather", "region", "per_line", "color_match", "rectify", "perspective"}
+    unknown = set(paste_back) - {"dilate", "feather", "region", "per_line", "color_match", "rectify", "perspective", "curve"}
     region = paste_back.get("region")
     if region is not None:
         unknown |= {f"region.{k}" for k in set(region) - {"pad", "min_side", "max_side"}}
@@ -122,6 +124,17 @@ def _paste_back_cfg(paste_back: Dict[str, Any]) -> Dict[str, Any]:
         from . import perspective as ps
         try:
             cfg["perspective"] = ps.perspective_cfg(perspective)
+        except ValueError as e:
+            raise ValueError(f"paste_back: {e}") from None
+    curve = paste_back.get("curve")
+    if curve is not None and curve is not False:
+        if curve is not True and not isinstance(curve, dict):
+            raise ValueError("paste_back: curve must be None, True or a dict")
+        if not per_line:
+            raise ValueError("paste_back: curve needs per_line=True (only single-line edits are cut as ribbons)")
+        from . import curve as cv
+        try:
+            cfg["curve"] = cv.curve_cfg(curve)
         except ValueError as e:
             raise ValueError(f"paste_back: {e}") from None
     return cfg
@@ -201,10 +214,32 @@ def _perspective_inputs(scene, mask, cfg: Dict[str, Any], warp_quad: Callable):
     return s, m, so, mo, pb.Region(x0, y0, x1, y1, quad.tw, quad.th), quad
 
 
-def _edit_inputs(scene, mask, cfg: Dict[str, Any], warp: Optional[Callable], warp_quad: Optional[Callable] = None):
-    """(scene, mask, the Work's paste-back fields): _perspective_inputs where the cfg asks for it, a perspective warp is at hand and the
-    line qualifies; otherwise _rectified_inputs under the same three conditions; _paste_back_inputs otherwise."""
-    got = _perspective_inputs(scene, mask, cfg, warp_quad) if (warp_quad is not None and cfg.get("perspective")) else None
+def _curved_inputs(scene, mask, cfg: Dict[str, Any], warp_grid: Callable):
+    """_rectified_inputs for a line along a bend (DESIGN.md section 4 "Curved lines"), or None when the line stays on the other paths
+    (curve.plan).  -> (scene, mask, originals, Region, Ribbon): the scene and the RGB mask warped into the ribbon's upright crop (rw, rh)
+    by `warp_grid` (the pipeline's warp_grid) under the forward control grid, prepared as _rectified_inputs does.  The Region is the scene
+    window the result is pasted into: the crop's footprint's bounding box cut at the image."""
+    import numpy as np
+    from . import curve as cv
+    from . import paste_back as pb
+    so, mo = np.array(scene), np.array(mask)
+    ribbon = cv.plan(pb.grey_of(mo), cfg)
+    if ribbon is None:
+        return None
+    x0, y0, x1, y1 = cv.ribbon_window(ribbon, scene.size)
+    s, m = _warped_inputs(so, mo, lambda x, g, size: warp_grid(x, g, ribbon.shift, size), cv.forward_grid(ribbon), (ribbon.rw, ribbon.rh),
+                          (ribbon.tw, ribbon.th))
+    return s, m, so, mo, pb.Region(x0, y0, x1, y1, ribbon.tw, ribbon.th), ribbon
+
+
+def _edit_inputs(scene, mask, cfg: Dict[str, Any], warp: Optional[Callable], warp_quad: Optional[Callable] = None,
+                 warp_grid: Optional[Callable] = None):
+    """(scene, mask, the Work's paste-back fields): _curved_inputs where the cfg asks for it, a grid warp is at hand and the line
+    qualifies; otherwise _perspective_inputs, then _rectified_inputs, each under the same three conditions; _paste_back_inputs
+    otherwise."""
+    got = _curved_inputs(scene, mask, cfg, warp_grid) if (warp_grid is not None and cfg.get("curve")) else None
+    if got is None:
+        got = _perspective_inputs(scene, mask, cfg, warp_quad) if (warp_quad is not None and cfg.get("perspective")) else None
     if got is None:
         got = _rectified_inputs(scene, mask, cfg, warp) if (warp is not None and cfg.get("rectify")) else None
     if got is not None:
@@ -216,14 +251,17 @@ def _edit_inputs(scene, mask, cfg: Dict[str, Any], warp: Optional[Callable], war
 
 def prepare_eval_item(index: int, item: Dict[str, Any], original_images_dir: str, font, text_height_ratio: float = 0.1667,
                       loader: Optional[Callable] = None, device_compose: bool = False, paste_back: Optional[Dict[str, Any]] = None,
-                      annotation: int = 0, warp: Optional[Callable] = None, warp_quad: Optional[Callable] = None) -> Work:
+                      annotation: int = 0, warp: Optional[Callable] = None, warp_quad: Optional[Callable] = None,
+                      warp_grid: Optional[Callable] = None) -> Work:
     """One `annos.json` entry -> Work (scripts/run_eval.py:76-112): scene = original_images_dir / img_name; mask = the first
     annotation's polygon filled white on black; glyph strip of height int(w * text_height_ratio) -- a fraction of the image
     WIDTH -- with the annotation's text, stacked on top with a black mask; pipeline size ((w // 32) * 32,
     ((h + strip) // 32) * 32); T5 prompt generate_prompt([text]).  annotation: which entry of `annotations` (the reference, and
     every caller but per-line editing, reads the first).  warp: the pipeline's warp_affine, given by per-line editing when
     paste_back["rectify"] is set: a slanted line is then edited upright (_rectified_inputs).  warp_quad: the pipeline's
-    warp_perspective, given when paste_back["perspective"] is set: a line seen in perspective is then cut as a quad (_perspective_inputs)."""
+    warp_perspective, given when paste_back["perspective"] is set: a line seen in perspective is then cut as a quad (_perspective_inputs).
+    warp_grid: the pipeline's warp_grid, given when paste_back["curve"] is set: a line along a bend is then cut as a ribbon
+    (_curved_inputs)."""
     import numpy as np
     from PIL import Image
     load = loader or (lambda p: Image.open(p))
@@ -234,7 +272,7 @@ def prepare_eval_item(index: int, item: Dict[str, Any], original_images_dir: str
     m = glyph.fill_polygon(h, w, ann["polygon"])
     extra = {}
     if paste_back is not None:       # the strip, the stacking and the sizes below are then those of the edited region
-        scene, mk, extra = _edit_inputs(scene, Image.fromarray(m), paste_back, warp, warp_quad)
+        scene, mk, extra = _edit_inputs(scene, Image.fromarray(m), paste_back, warp, warp_quad, warp_grid)
         (w, h), m = scene.size, np.array(mk)
     strip = int(w * text_height_ratio)
     g = np.array(glyph.draw_glyph(font, text, w, strip))
@@ -268,13 +306,13 @@ def prepare_item(index: int, item: Dict[str, Any], loader: Optional[Callable] = 
 
 def prepare_plain(index: int, scene, mask, words: Sequence[str], device_compose: bool = False,
                   paste_back: Optional[Dict[str, Any]] = None, warp: Optional[Callable] = None,
-                  warp_quad: Optional[Callable] = None) -> Work:
+                  warp_quad: Optional[Callable] = None, warp_grid: Optional[Callable] = None) -> Work:
     """prepare_item's rule for an {image, mask, text} item whose RGB scene and mask are loaded and whose text is split into words.
-    warp, warp_quad: as in prepare_eval_item."""
+    warp, warp_quad, warp_grid: as in prepare_eval_item."""
     from PIL import Image
     extra = {}
     if paste_back is not None:
-        scene, mask, extra = _edit_inputs(scene, mask, paste_back, warp, warp_quad)
+        scene, mask, extra = _edit_inputs(scene, mask, paste_back, warp, warp_quad, warp_grid)
     g, s_, m, horizontal, meta = glyph.compose_parts(scene, mask, words)
     H, W = (s_.shape[0], g.shape[1] + s_.shape[1]) if horizontal else (g.shape[0] + s_.shape[0], s_.shape[1])
     w, h = (W // 32) * 32, (H // 32) * 32
@@ -446,7 +484,11 @@ def run_items(items: Sequence[Dict[str, Any]], pipe, out_dir: Optional[str], bat
     scene under the same alpha; every other line is edited as without the key.
     perspective=True | dict(max_fit, max_taper, min_aspect, max_angle) (with per_line; DESIGN.md section 4 "Perspective lines"): a line
     whose outline is a tapering quadrilateral (perspective.is_perspective) is cut through the homography of that quad, warped upright on
-    the device (pipe.warp_perspective), edited upright and warped back under the same alpha.  It is tried before rectify; both may be set."""
+    the device (pipe.warp_perspective), edited upright and warped back under the same alpha.  It is tried before rectify; both may be set.
+    curve=True | dict(min_bend, max_squeeze, max_turn, min_aspect, min_fill, max_angle) (with per_line; DESIGN.md section 4 "Curved
+    lines"): a line whose centre line bends (curve.is_curved) is cut as a ribbon around that centre line, warped upright on the device
+    through a control grid (pipe.warp_grid), edited upright and warped back under the same alpha.  It is tried first; all three may be
+    set."""
     if paste_back is not None:       # refused before anything is prepared or encoded
         if mixed_pad > 0:
             raise NotImplementedError("paste_back does not serve mixed-geometry batches (mixed_pad > 0)")
@@ -457,6 +499,8 @@ def run_items(items: Sequence[Dict[str, Any]], pipe, out_dir: Optional[str], bat
             raise ValueError("paste_back: rectify needs a pipeline with warp_affine (FluxFillPipeline)")
         if paste_back.get("perspective") and not hasattr(pipe, "warp_perspective"):
             raise ValueError("paste_back: perspective needs a pipeline with warp_perspective (FluxFillPipeline)")
+        if paste_back.get("curve") and not hasattr(pipe, "warp_grid"):
+            raise ValueError("paste_back: curve needs a pipeline with warp_grid (FluxFillPipeline)")
     if step_cache is not None:
         if mixed_pad > 0:
             raise NotImplementedError("step_cache does not serve mixed-geometry batches (mixed_pad > 0)")
@@ -495,7 +539,8 @@ def _run_items(items, pipe, out_dir, batch_size, num_inference_steps, guidance_s
                 from . import per_line as pl
                 lines[i] = pl.prepare_lines(i, it, loader, device_compose, eval_cfg, paste_back,
                                             warp=pipe.warp_affine if paste_back.get("rectify") else None,
-                                            warp_quad=pipe.warp_perspective if paste_back.get("perspective") else None)
+                                            warp_quad=pipe.warp_perspective if paste_back.get("perspective") else None,
+                                            warp_grid=pipe.warp_grid if paste_back.get("curve") else None)
                 works.extend(lines[i])
             else:
                 works.append(prepare_item(i, it, loader, device_compose=device_compose,

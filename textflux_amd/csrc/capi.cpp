@@ -423,6 +423,11 @@ int tfx_warp_perspective_u8(const void* in, void* out, void* coverage, int32_t B
   if (!in || !out || !m || !taps) return fail("tfx_warp_perspective_u8: null pointer");
   return warp_perspective_u8(in, out, coverage, B, H, W, C, out_h, out_w, m, taps, S(stream));
 }
+int tfx_warp_grid_u8(const void* in, void* out, void* coverage, int32_t B, int32_t H, int32_t W, int32_t C, int32_t out_h, int32_t out_w,
+                     const int64_t* grid, int32_t shift, const int16_t* taps, tfx_stream stream) {
+  if (!in || !out || !grid || !taps) return fail("tfx_warp_grid_u8: null pointer");
+  return warp_grid_u8(in, out, coverage, B, H, W, C, out_h, out_w, grid, shift, taps, S(stream));
+}
 int tfx_pack_mask(const void* mask, int32_t mask_dtype, void* out, int32_t B, int32_t H, int32_t W, int32_t mask_batch,
                   int32_t binarize, int64_t ld, int32_t col0, tfx_stream stream) {
   if (!mask || !out) return fail("tfx_pack_mask: null pointer");

@@ -623,6 +623,43 @@ __global__ __launch_bounds__(256) void warp_perspective_u8_kernel(const uint8_t*
                     coverage ? coverage + o : nullptr);
 }
 
+// ---- curved per-line edits (DESIGN.md section 4 "Curved lines"): the same resampler under a coarse control grid, which is also the
+// set's general remap (shift = 0: one node per pixel).  grid i64 [B][gh][gw][2] holds the Q16 source position (x, y) of every
+// destination pixel (q << shift, r << shift); a pixel's position is the bilinear blend of the four nodes around it, with integer
+// weights that sum to 4^shift, floored by an arithmetic shift (the header spells it out), then warp_sample_u8.  A pixel one of whose
+// four nodes carries INT64_MIN in x has no source: 0, coverage 0, `in` is not read.  The launch shape is the affine kernel's; the four
+// nodes of a 32 x 8 tile's pixels are a few cache lines that the tile's lanes share.  Memory-safe whatever the grid holds: gh and gw
+// are sized so that node (gy + 1, gx + 1) exists for every destination pixel, products and sums wrap in unsigned arithmetic, and
+// warp_sample_u8 clamps in 64 bits.
+template <int C>
+__global__ __launch_bounds__(256) void warp_grid_u8_kernel(const uint8_t* __restrict__ in, uint8_t* __restrict__ out,
+                                                           uint8_t* __restrict__ coverage, int H, int W, int out_h, int out_w,
+                                                           const int64_t* __restrict__ grid, int shift, const int16_t* __restrict__ taps) {
+  const int b = blockIdx.z;
+  const int i = blockIdx.x * 32 + (threadIdx.x & 31), j = blockIdx.y * 8 + (threadIdx.x >> 5);
+  if (i >= out_w || j >= out_h) return;
+  const int64_t gh = ((out_h - 1) >> shift) + 2, gw = ((out_w - 1) >> shift) + 2;
+  const int cell = 1 << shift;
+  const int gx = i >> shift, gy = j >> shift;
+  const uint64_t ax = i & (cell - 1), ay = j & (cell - 1), bx = cell - ax, by = cell - ay;
+  const uint64_t* g0 = (const uint64_t*)grid + (((int64_t)b * gh + gy) * gw + gx) * 2;        // g00, g01 = g0 + 2
+  const uint64_t* g1 = g0 + gw * 2;                                                            // g10, g11 = g1 + 2
+  const uint64_t x00 = g0[0], y00 = g0[1], x01 = g0[2], y01 = g0[3], x10 = g1[0], y10 = g1[1], x11 = g1[2], y11 = g1[3];
+  const int64_t o = ((int64_t)b * out_h + j) * out_w + i;
+  const uint64_t none = (uint64_t)1 << 63;                                                     // INT64_MIN
+  if (x00 == none || x01 == none || x10 == none || x11 == none) {
+#pragma unroll
+    for (int c = 0; c < C; ++c) out[o * C + c] = 0;
+    if (coverage) coverage[o] = 0;
+    return;
+  }
+  const uint64_t w00 = bx * by, w01 = ax * by, w10 = bx * ay, w11 = ax * ay;
+  const int64_t X = (int64_t)(w00 * x00 + w01 * x01 + w10 * x10 + w11 * x11) >> (2 * shift);   // Q16, floored
+  const int64_t Y = (int64_t)(w00 * y00 + w01 * y01 + w10 * y10 + w11 * y11) >> (2 * shift);
+  warp_sample_u8<C>(in + (int64_t)b * H * W * C, H, W, X >> 16, Y >> 16, (int)((X >> 8) & 255), (int)((Y >> 8) & 255), taps, out + o * C,
+                    coverage ? coverage + o : nullptr);
+}
+
 int compose_canvas(const void* glyph, const void* scene, const void* smask, void* canvas, void* cmask, int B, int gh, int gw, int sh,
                    int sw, int dir, int mask_rgb, hipStream_t st) {
   if (dir != 0 && dir != 1) return fail("compose_canvas: direction 0 (vertical) or 1 (horizontal)");
@@ -787,6 +824,28 @@ int warp_perspective_u8(const void* in, void* out, void* coverage, int B, int H,
     default: warp_perspective_u8_kernel<4><<<grid, 256, 0, st>>>(pi, po, pc, H, W, out_h, out_w, m, taps); break;
   }
   return check_launch("warp_perspective_u8");
+}
+
+int warp_grid_u8(const void* in, void* out, void* coverage, int B, int H, int W, int C, int out_h, int out_w, const int64_t* grid,
+                 int shift, const int16_t* taps, hipStream_t st) {
+  if (B < 1 || H < 1 || W < 1 || out_h < 1 || out_w < 1) return fail("warp_grid_u8: B, H, W, out_h, out_w must be at least 1");
+  if (C < 1 || C > 4) return fail("warp_grid_u8: 1..4 channels");
+  if (shift < 0 || shift > 5) return fail("warp_grid_u8: shift %d outside 0..5", shift);
+  if (B > 65535) return fail("warp_grid_u8: batch %d exceeds 65535", B);
+  if ((out_h + 7) / 8 > 65535) return fail("warp_grid_u8: out_h %d exceeds 524280", out_h);
+  if ((int64_t)H * W * C > kMaxBytes || (int64_t)out_h * out_w * C > kMaxBytes) return fail("warp_grid_u8: more than 2^38 bytes per sample");
+  if (in == out || in == coverage || out == coverage) return fail("warp_grid_u8: in, out and coverage must be different buffers");
+  if (((uintptr_t)grid | (uintptr_t)taps) & 7) return fail("warp_grid_u8: grid and taps must be 8-byte aligned");
+  const dim3 blocks((out_w + 31) / 32, (out_h + 7) / 8, B);
+  const uint8_t* pi = (const uint8_t*)in;
+  uint8_t *po = (uint8_t*)out, *pc = (uint8_t*)coverage;
+  switch (C) {
+    case 1: warp_grid_u8_kernel<1><<<blocks, 256, 0, st>>>(pi, po, pc, H, W, out_h, out_w, grid, shift, taps); break;
+    case 2: warp_grid_u8_kernel<2><<<blocks, 256, 0, st>>>(pi, po, pc, H, W, out_h, out_w, grid, shift, taps); break;
+    case 3: warp_grid_u8_kernel<3><<<blocks, 256, 0, st>>>(pi, po, pc, H, W, out_h, out_w, grid, shift, taps); break;
+    default: warp_grid_u8_kernel<4><<<blocks, 256, 0, st>>>(pi, po, pc, H, W, out_h, out_w, grid, shift, taps); break;
+  }
+  return check_launch("warp_grid_u8");
 }
 
 int pack_mask(const void* mask, int mask_dtype, void* out, int B, int H, int W, int mask_b, int binarize, int64_t ld, int col0,

@@ -224,6 +224,11 @@ int warp_affine_u8(const void* in, void* out, void* coverage, int B, int H, int 
 // fractional bits; D <= 0 writes 0 with coverage 0 and reads nothing
 int warp_perspective_u8(const void* in, void* out, void* coverage, int B, int H, int W, int C, int out_h, int out_w, const int64_t* m,
                         const int16_t* taps, hipStream_t st);
+// curved per-line edits: the same under a control grid i64 [B][gh][gw][2] (device) of Q16 source positions, one node per
+// (1 << shift) destination pixels, blended bilinearly in integers; a pixel next to a node whose x is INT64_MIN writes 0 with coverage 0
+// and reads nothing
+int warp_grid_u8(const void* in, void* out, void* coverage, int B, int H, int W, int C, int out_h, int out_w, const int64_t* grid,
+                 int shift, const int16_t* taps, hipStream_t st);
 int pack_mask(const void* mask, int mask_dtype, void* out, int B, int H, int W, int mask_b, int binarize, int64_t ld, int col0,
               hipStream_t st);
 int sample_pack(const void* moments, const void* eps, int eps_dtype, void* out, int B, int h, int w, int L, float shift,

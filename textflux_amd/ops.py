@@ -832,6 +832,56 @@ def warp_perspective_u8(x: torch.Tensor, m, out_size, coverage: bool = False):
     return _warp_u8("warp_perspective_u8", 9, x, m, out_size, coverage, _perspective_magnitudes)
 
 
+GRID_NONE = -(1 << 63)               # warp_grid_u8: a node whose x is this marks "no source" (INT64_MIN)
+
+
+def warp_grid_u8(x: torch.Tensor, grid, shift: int, out_size, coverage: bool = False):
+    """warp_affine_u8 under a control grid, and the general remap (shift = 0): every destination pixel (i, j) is x[b] sampled at the
+    bilinear blend of the four grid nodes around it.  grid: int64 [gh, gw, 2] (one grid for the batch) or [B, gh, gw, 2], a device tensor
+    or a host array, gh = ((out_h - 1) >> shift) + 2, gw = ((out_w - 1) >> shift) + 2; node (r, q) is the Q16 source position (x, y) of
+    destination pixel (q << shift, r << shift); shift in 0..5.  A pixel one of whose four nodes has x = GRID_NONE is 0 and uncovered
+    (tfx_warp_grid_u8; include/textflux_hip.h has the arithmetic, curve.grids builds the grids).  A host grid is checked against the
+    magnitude contract (every value the marker or below 2^50 in magnitude: ValueError); a device tensor is taken as it is, which is
+    memory-safe but leaves such pixels undefined."""
+    _chk_dev(x)
+    if x.dtype != torch.uint8 or x.dim() != 4 or not x.is_contiguous() or x.numel() == 0 or not 1 <= x.shape[3] <= 4:
+        raise ValueError(f"warp_grid_u8: x must be a contiguous, non-empty uint8 [B, H, W, C <= 4] tensor, got {x.dtype} {tuple(x.shape)}")
+    B, H, W, Cc = x.shape
+    Ho, Wo = (int(v) for v in out_size)
+    if Ho < 1 or Wo < 1:
+        raise ValueError(f"warp_grid_u8: out_size must be (out_h, out_w) with both at least 1, got {tuple(out_size)}")
+    if isinstance(shift, bool) or int(shift) != shift or not 0 <= int(shift) <= 5:
+        raise ValueError(f"warp_grid_u8: shift must be an integer in 0..5, got {shift!r}")
+    shift = int(shift)
+    gh, gw = ((Ho - 1) >> shift) + 2, ((Wo - 1) >> shift) + 2
+    host = None
+    if not isinstance(grid, torch.Tensor):
+        import numpy as np
+        host = np.ascontiguousarray(grid)
+        if host.dtype != np.int64:
+            raise ValueError(f"warp_grid_u8: grid must be int64, got {host.dtype}")
+        grid = torch.from_numpy(host)
+    if grid.dtype != torch.int64 or tuple(grid.shape) not in ((gh, gw, 2), (B, gh, gw, 2)):
+        raise ValueError(f"warp_grid_u8: grid must be int64 [{gh}, {gw}, 2] or [{B}, {gh}, {gw}, 2] for out_size {(Ho, Wo)} at shift {shift}, "
+                         f"got {grid.dtype} {tuple(grid.shape)}")
+    if host is not None:
+        import numpy as np
+        bad = (host != GRID_NONE) & ((host >= 1 << 50) | (host <= -(1 << 50)))
+        if bad.any():
+            raise ValueError(f"warp_grid_u8: every grid value must be the marker or below 2^50 in magnitude; {int(bad.sum())} are not")
+    grid = grid.reshape(-1, gh, gw, 2).expand(B, gh, gw, 2).to(x.device).contiguous()
+    key = str(x.device)
+    if key not in _WARP_TAPS:
+        from .rectify import catmull_rom_taps
+        _WARP_TAPS[key] = torch.from_numpy(catmull_rom_taps()).to(x.device)
+    taps = _WARP_TAPS[key]
+    out = torch.empty(B, Ho, Wo, Cc, dtype=torch.uint8, device=x.device)
+    cov = torch.empty(B, Ho, Wo, dtype=torch.uint8, device=x.device) if coverage else None
+    L.check(L.lib().tfx_warp_grid_u8(x.data_ptr(), out.data_ptr(), _p(cov), B, H, W, Cc, Ho, Wo, grid.data_ptr(), shift, taps.data_ptr(),
+                                     _stream()), "warp_grid_u8")
+    return (out, cov) if coverage else out
+
+
 def pack_mask(mask: torch.Tensor, out: torch.Tensor, col0: int, B: int, H: int, W: int, binarize: bool = True) -> torch.Tensor:
     """out[b, :, col0 : col0 + 256] = packed mask (out: [B, S, ld] bf16)."""
     _chk_dev(mask, out)

@@ -180,7 +180,8 @@ def paste(original: torch.Tensor, edited: torch.Tensor, mask_grey: torch.Tensor,
     still that of mask_grey, the line's ORIGINAL mask, so the bytes outside the grown mask stay the original's; with color_match the
     ring is cut to the pixels the warp covered (their sample position lies inside the upright crop).
     rect may also be a perspective.Quad (DESIGN.md section 4 "Perspective lines"): the same, with the edit resampled to the quad's crop
-    (rh, rw) and warped by ops.warp_perspective_u8 under perspective.matrices' upright -> scene homography."""
+    (rh, rw) and warped by ops.warp_perspective_u8 under perspective.matrices' upright -> scene homography.
+    Or a curve.Ribbon (DESIGN.md section 4 "Curved lines"): the same through ops.warp_grid_u8 under curve.grids' backward grid."""
     if original.dtype != torch.uint8 or original.dim() != 4 or edited.dtype != torch.uint8 or edited.dim() != 4:
         raise ValueError("paste: original and edited must be uint8 [B, H, W, C]")
     if edited.shape[0] != original.shape[0] or edited.shape[3] != original.shape[3] or mask_grey.shape != original.shape[:3]:
@@ -190,11 +191,13 @@ def paste(original: torch.Tensor, edited: torch.Tensor, mask_grey: torch.Tensor,
     original, edited = original.contiguous(), edited.contiguous()
     covered = None
     if rect is not None:
-        from . import perspective, rectify
+        from . import curve, perspective, rectify
         if tuple(edited.shape[1:3]) != (rect.rh, rect.rw):
             edited = ops.resample_u8(edited, (rect.rh, rect.rw))
         size = (original.shape[1], original.shape[2])
-        if isinstance(rect, perspective.Quad):
+        if isinstance(rect, curve.Ribbon):
+            edited, covered = ops.warp_grid_u8(edited, curve.backward_grid(rect, origin, size), rect.shift, size, coverage=True)
+        elif isinstance(rect, perspective.Quad):
             edited, covered = ops.warp_perspective_u8(edited, perspective.matrices(rect, origin)[1], size, coverage=True)
         else:
             edited, covered = ops.warp_affine_u8(edited, rectify.matrices(rect, origin)[1], size, coverage=True)

@@ -39,19 +39,22 @@ def split_lines(mask, texts: Sequence[str], min_area: int = 50) -> List[Tuple[in
 
 
 def prepare_scene_lines(index: int, scene, mask, texts: Sequence[str], cfg: Dict[str, Any], device_compose: bool = False,
-                        warp: Optional[Callable] = None, warp_quad: Optional[Callable] = None) -> List[Any]:
+                        warp: Optional[Callable] = None, warp_quad: Optional[Callable] = None,
+                        warp_grid: Optional[Callable] = None) -> List[Any]:
     """The single-line Works of one {scene, mask, texts} item (PIL RGB images): per line of split_lines, batch_driver.prepare_plain on
     the line's mask alone with the line's one text -- the region of that mask (paste_back.select_region), its crop resized as
     _paste_back_inputs does, a glyph strip at the region's width (glyph.render_single_line), prompt generate_prompt([text]), meta of
     mode singleline.  Work.parent = index, Work.line = the position in the list.  No line at all: ValueError.
     warp (the pipeline's warp_affine; with cfg["rectify"]): a slanted line is cut as an oriented rectangle and prepared upright
     (batch_driver._rectified_inputs); its Work then carries `rect`.  warp_quad (the pipeline's warp_perspective; with
-    cfg["perspective"]): a line seen in perspective is cut as a quad instead (batch_driver._perspective_inputs); `rect` is then its Quad."""
+    cfg["perspective"]): a line seen in perspective is cut as a quad instead (batch_driver._perspective_inputs); `rect` is then its Quad.
+    warp_grid (the pipeline's warp_grid; with cfg["curve"]): a line along a bend is cut as a ribbon (batch_driver._curved_inputs), which
+    is tried first; `rect` is then its Ribbon."""
     from PIL import Image
     from . import batch_driver as bd
     works = []
     for _, text, lm in split_lines(mask, texts):
-        w = bd.prepare_plain(index, scene, Image.fromarray(lm), [text], device_compose, cfg, warp=warp, warp_quad=warp_quad)
+        w = bd.prepare_plain(index, scene, Image.fromarray(lm), [text], device_compose, cfg, warp=warp, warp_quad=warp_quad, warp_grid=warp_grid)
         w.parent, w.line = index, len(works)
         works.append(w)
     if not works:
@@ -60,10 +63,11 @@ def prepare_scene_lines(index: int, scene, mask, texts: Sequence[str], cfg: Dict
 
 
 def prepare_lines(index: int, item: Dict[str, Any], loader: Optional[Callable], device_compose: bool, eval_cfg: Optional[Dict[str, Any]],
-                  cfg: Dict[str, Any], warp: Optional[Callable] = None, warp_quad: Optional[Callable] = None) -> List[Any]:
+                  cfg: Dict[str, Any], warp: Optional[Callable] = None, warp_quad: Optional[Callable] = None,
+                  warp_grid: Optional[Callable] = None) -> List[Any]:
     """One item of batch_driver.run_items -> its lines as Works.  {image, mask, text} items: prepare_scene_lines.  `annos.json` items:
     every entry of `annotations` with a text and a polygon is a line (batch_driver.prepare_eval_item of that entry).  warp,
-    warp_quad: as in prepare_scene_lines."""
+    warp_quad, warp_grid: as in prepare_scene_lines."""
     from PIL import Image
     from . import batch_driver as bd
     if "img_name" in item:
@@ -74,7 +78,7 @@ def prepare_lines(index: int, item: Dict[str, Any], loader: Optional[Callable], 
             if not (ann.get("text") and str(ann["text"]).strip() and ann.get("polygon")):
                 continue
             w = bd.prepare_eval_item(index, item, c.get("original_images_dir", "."), font, c.get("text_height_ratio", 0.1667), loader,
-                                     device_compose, cfg, annotation=k, warp=warp, warp_quad=warp_quad)
+                                     device_compose, cfg, annotation=k, warp=warp, warp_quad=warp_quad, warp_grid=warp_grid)
             w.parent, w.line = index, len(works)
             works.append(w)
         if not works:
@@ -82,7 +86,7 @@ def prepare_lines(index: int, item: Dict[str, Any], loader: Optional[Callable], 
         return works
     load = loader or (lambda p: Image.open(p))
     scene, mask = load(item["image"]).convert("RGB"), load(item["mask"]).convert("RGB")
-    return prepare_scene_lines(index, scene, mask, glyph.read_words_from_text(item["text"]), cfg, device_compose, warp, warp_quad)
+    return prepare_scene_lines(index, scene, mask, glyph.read_words_from_text(item["text"]), cfg, device_compose, warp, warp_quad, warp_grid)
 
 
 def compose_lines(pipe, lines: Sequence[Any], crops: Sequence[Any], cfg: Dict[str, Any]):
@@ -91,8 +95,8 @@ def compose_lines(pipe, lines: Sequence[Any], crops: Sequence[Any], cfg: Dict[st
     region) is written back into the copy.  With cfg["color_match"] the call also gets color_match and color_ref = the ORIGINAL pixels
     of the region: each edit was generated from the original scene, so that is what its ring shows (another line's old text inside the
     ring appears in both; what was pasted in since does not).  The two are passed only then.
-    A rectified or perspective line (Work.rect: a Rect or a Quad) is pasted into its window `region`, the bounding box of the oriented
-    rectangle or of the quad's crop cut at the image: the call
+    A rectified, perspective or curved line (Work.rect: a Rect, a Quad or a Ribbon) is pasted into its window `region`, the bounding box
+    of the oriented rectangle or of the upright crop's footprint cut at the image: the call
     also gets rect and origin = the window's top-left scene pixel, and the pipeline warps the upright result into the window before
     the blend (paste_back.paste).  These two are passed only for such lines: a pipeline that predates them serves all others."""
     import torch
@@ -151,9 +155,12 @@ def edit_scene(pipe, scene, mask, texts: Sequence[str], cfg: Dict[str, Any], num
         raise ValueError("paste_back: rectify needs a pipeline with warp_affine (FluxFillPipeline)")
     if cfg.get("perspective") and not hasattr(pipe, "warp_perspective"):
         raise ValueError("paste_back: perspective needs a pipeline with warp_perspective (FluxFillPipeline)")
+    if cfg.get("curve") and not hasattr(pipe, "warp_grid"):
+        raise ValueError("paste_back: curve needs a pipeline with warp_grid (FluxFillPipeline)")
     lines = prepare_scene_lines(0, scene.convert("RGB"), mask.convert("RGB"), texts, cfg,
                                 warp=pipe.warp_affine if cfg.get("rectify") else None,
-                                warp_quad=pipe.warp_perspective if cfg.get("perspective") else None)
+                                warp_quad=pipe.warp_perspective if cfg.get("perspective") else None,
+                                warp_grid=pipe.warp_grid if cfg.get("curve") else None)
     fulls: Dict[int, Any] = {}
     for batch in bd.plan_batches(lines, len(lines)):
         n = len(batch.items)

@@ -596,7 +596,7 @@ class FluxFillPipeline:
         may have another size: it is resampled with Pillow's bicubic on the device); mask: the same forms, grey [H, W] or RGB (PIL's
         "L" of it is taken).  color_match: None, or True / dict(ring, gain, max_shift, min_pixels): the edit's colours are matched to
         those of color_ref (the forms of `original`, at its size; None: `original`) on a ring just outside the blend before the blend
-        (paste_back.paste).  rect (a rectify.Rect or a perspective.Quad) with origin: `edited` is the upright result of a rectified line and `original` the scene
+        (paste_back.paste).  rect (a rectify.Rect, a perspective.Quad or a curve.Ribbon) with origin: `edited` is the upright result of a rectified line and `original` the scene
         window at `origin`; the edit is warped into the window before the blend (paste_back.paste).  Returns uint8 [B, H, W, 3] on the
         device."""
         from . import paste_back as pb
@@ -660,6 +660,17 @@ class FluxFillPipeline:
         if t.dtype != torch.uint8 or t.dim() != 4:
             raise ValueError(f"warp_perspective: the image must be uint8 [H, W, C] or [B, H, W, C], got {t.dtype} {tuple(t.shape)}")
         return ops.warp_perspective_u8(t.to(self._execution_device).contiguous(), m, out_size, coverage=coverage)
+
+    # ------------------------------------------------------------------ curved lines (DESIGN.md section 4 "Curved lines")
+    def warp_grid(self, image, grid, shift, out_size, coverage: bool = False):
+        """warp_affine under a control grid: grid is int64 [gh, gw, 2] or [B, gh, gw, 2] of Q16 source positions, one node per
+        (1 << shift) destination pixels (curve.grids; ops.warp_grid_u8), the resampler of the curved per-line path and, at shift = 0, a
+        per-pixel remap.  Returns uint8 [B, out_h, out_w, C] on the device, with coverage=True also the coverage [B, out_h, out_w]."""
+        t = image if isinstance(image, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(image))
+        t = t[None] if t.dim() == 3 else t
+        if t.dtype != torch.uint8 or t.dim() != 4:
+            raise ValueError(f"warp_grid: the image must be uint8 [H, W, C] or [B, H, W, C], got {t.dtype} {tuple(t.shape)}")
+        return ops.warp_grid_u8(t.to(self._execution_device).contiguous(), grid, shift, out_size, coverage=coverage)
 
     def _generic_loop(self, latents, masked_image_latents, prompt_embeds, pooled, text_ids, latent_image_ids, timesteps,
                       guidance, callback_on_step_end, callback_tensor_inputs, progress_bar):
