@@ -519,6 +519,40 @@ int tfx_masked_moments_u8(const void* a, const void* b, const void* weight, void
  *      for bit.  out may be orig (no other aliasing). */
 int tfx_overlay_lut_u8(const void* orig, const void* edit, const void* alpha, const void* lut, void* out, int32_t B, int32_t H, int32_t W,
                        int32_t C, tfx_stream stream);
+/* ---- seamless paste (DESIGN.md section 4 "Seamless paste"): before the blend the edit is corrected by a membrane, the difference
+ *      ref - edit known just outside the blend and interpolated smoothly across alpha's support by a pull-push pyramid, so that the edit
+ *      meets the scene at the seam and keeps its own gradients inside.  Added without a new TFX_ABI_VERSION: two new entry points (one of
+ *      them host arithmetic), no stamped struct and no existing entry point changes.  Tensors contiguous, batch-major, u8; B, H, W >= 1,
+ *      B <= 65535, C in 1..4; smooth and max_shift in [0, 255]; integer arithmetic throughout, so the results are exact.
+ * tfx_seamless_workspace_bytes: the bytes of `workspace` the call below needs for this geometry (host arithmetic, no device is touched);
+ *      -1 with tfx_last_error for a geometry outside the contract.
+ * tfx_seamless_overlay_u8: orig, ref, edit, out [B, H, W, C], alpha [B, H, W], covered [B, H, W] or NULL, lut [B][C][256] or NULL.  Per
+ *      sample and channel, in integers (// is floor division, >> an arithmetic shift):
+ *          e = lut[b][c][edit] with a table, else edit
+ *          free  = alpha > 0;   known = alpha == 0 and (covered == NULL or covered != 0);   the rest is neither
+ *          level 0 (H, W):  v = (ref - e) * 64 on the known pixels (|v| <= 16320: i16), filled = known
+ *          pull, level l (h, w) -> l + 1 ((h + 1) / 2, (w + 1) / 2), until the level is 1 x 1: of a coarse pixel's up to four in-bounds
+ *                   children the n filled ones with the sum s of their values: filled iff n > 0, value (2 s + n) // (2 n), 0 when n = 0
+ *          top:     an unfilled 1 x 1 level holds 0 (nothing known: the membrane is 0 everywhere)
+ *          push, top down: every unfilled pixel (y, x) of level l takes the 2x upsample of the completed level l + 1 (hc, wc) = c:
+ *                   i = y >> 1, i2 = clamp(i + (y & 1 ? 1 : -1), 0, hc - 1);  j, j2 alike from x
+ *                   v = (9 c[i, j] + 3 c[i, j2] + 3 c[i2, j] + c[i2, j2] + 8) >> 4;   filled pixels keep their values
+ *          smooth:  `smooth` Jacobi sweeps at level 0 between two buffers (no pixel depends on the update order): a free pixel becomes
+ *                   (N + S + E + W + 2) >> 2, a neighbour outside the window counting as the pixel's own value; all others stay
+ *          apply:   d = clamp((v + 32) >> 6, -max_shift, max_shift),  e' = clamp(e + d, 0, 255)
+ *                   out = (orig (255 - a) + e' a + 127) / 255 where a = alpha > 0,  out = orig where alpha == 0
+ *      Hence, exactly: a difference that is one constant k on the known set gives v = 64 k everywhere; every v lies between the least and
+ *      the greatest known value; max_shift = 0 is tfx_overlay_lut_u8 (tfx_overlay_u8 without a table) bit for bit, and so is a call with
+ *      nothing known; alpha == 0 everywhere gives orig.  ref is the image the difference is taken against: orig itself, or, when the edit
+ *      was generated from an earlier state of the scene than the one it is blended over, that earlier state.
+ *      out may be orig and ref may be orig (no other aliasing).  workspace: 16-byte aligned, workspace_bytes at least
+ *      tfx_seamless_workspace_bytes(B, H, W, C), else the call is refused; nothing in it survives the call.  No atomics; every launch
+ *      goes on `stream`.  Every neighbour index is clamped as written above and every offset that can pass 2^31 is formed in 64 bits, so
+ *      the call is memory-safe whatever the masks hold. */
+int64_t tfx_seamless_workspace_bytes(int32_t B, int32_t H, int32_t W, int32_t C);
+int tfx_seamless_overlay_u8(const void* orig, const void* ref, const void* edit, const void* alpha, const void* covered, const void* lut,
+                            void* out, void* workspace, int64_t workspace_bytes, int32_t B, int32_t H, int32_t W, int32_t C, int32_t smooth,
+                            int32_t max_shift, tfx_stream stream);
 /* ---- rectified per-line edits (DESIGN.md section 4 "Rectified lines"): a slanted text line is cut as an oriented rectangle, edited
  *      upright and warped back.  Added without a new TFX_ABI_VERSION: one new entry point, no stamped struct and no existing entry point
  *      changes.  Tensors contiguous, batch-major; B, H, W, out_h, out_w >= 1, B <= 65535, C in 1..4; in, out and coverage are three

@@ -49,7 +49,8 @@ def use_overshoot_sampler(pipe):
 def run_inference(image_input, mask_input, words_input, num_steps=50, guidance_scale=30, seed=42, pipe=None, paste_back=None):
     """paste_back (not in the reference): None, or dict(dilate, feather) -- the result is then blended back into the input image under
     the dilated and feathered mask and returned at the INPUT's size (FluxFillPipeline.paste_back) instead of at the pipeline's size.
-    With per_line=True in it (batch_driver.run_items' keys: region, color_match, rectify, perspective, curve) the input is the plain scene and its mask: every text
+    seamless in it (True or dict(smooth, max_shift)) is handed to that paste.
+    With per_line=True in it (batch_driver.run_items' keys: region, color_match, rectify, perspective, curve, seamless) the input is the plain scene and its mask: every text
     line is edited through its own region with a single-line glyph strip and pasted into the scene (textflux_amd/per_line.py)."""
     image = (Image.open(image_input) if isinstance(image_input, str) else image_input).convert("RGB")
     mask = (Image.open(mask_input) if isinstance(mask_input, str) else mask_input).convert("RGB")
@@ -70,7 +71,7 @@ def run_inference(image_input, mask_input, words_input, num_steps=50, guidance_s
                prompt=glyph.PROMPT_TEMPLATE2, prompt_2=prompt).images[0]
     if paste_back is None:
         return out
-    pasted = pipe.paste_back(image_in, out, mask_in, **{k: v for k, v in paste_back.items() if k in ("dilate", "feather") and v is not None})
+    pasted = pipe.paste_back(image_in, out, mask_in, **{k: v for k, v in paste_back.items() if k in ("dilate", "feather", "seamless") and v is not None})
     return Image.fromarray(pasted[0].cpu().numpy())
 
 
@@ -117,6 +118,12 @@ def add_paste_back_args(ap):
                     "curved, default 0.2 (implies --paste_curve)")
     ap.add_argument("--paste_curve_max_squeeze", type=float, default=None, metavar="F", help="largest crop reach / radius of curvature, "
                     "default 0.75 (implies --paste_curve)")
+    ap.add_argument("--paste_seamless", action="store_true", help="add a pull-push membrane to each pasted edit before the blend, so that it meets "
+                    "the scene at the seam (with --paste_back)")
+    ap.add_argument("--paste_seamless_smooth", type=int, default=None, metavar="N", help="Jacobi sweeps after the push, 0..255, default 8 "
+                    "(implies --paste_seamless)")
+    ap.add_argument("--paste_seamless_max_shift", type=int, default=None, metavar="N", help="largest correction in grey levels, 0..255, "
+                    "default 32 (implies --paste_seamless)")
 
 
 RECTIFY_FLAGS = ("paste_rectify", "paste_rectify_min_angle", "paste_rectify_max_angle")
@@ -164,10 +171,25 @@ def curve_from_args(a):
     return limits or True
 
 
+SEAMLESS_FLAGS = ("paste_seamless", "paste_seamless_smooth", "paste_seamless_max_shift")
+
+
+def seamless_from_args(a):
+    """None, or the `seamless` value of the paste_back dict (True, or a dict of the values that were given).  The flags are refused
+    without --paste_back."""
+    given = [f for f in SEAMLESS_FLAGS if getattr(a, f, None) not in (None, False)]
+    if not given:
+        return None
+    if not a.paste_back:
+        raise SystemExit(f"--{given[0]} needs --paste_back")
+    values = {k: getattr(a, "paste_seamless_" + k) for k in ("smooth", "max_shift") if getattr(a, "paste_seamless_" + k) is not None}
+    return values or True
+
+
 def paste_back_from_args(a):
-    """None, or the paste_back dict of batch_driver.run_items / process_normal_mode.  The per-line and colour keys appear only when
-    their flags were given."""
-    rectify, perspective, curve = rectify_from_args(a), perspective_from_args(a), curve_from_args(a)
+    """None, or the paste_back dict of batch_driver.run_items / process_normal_mode.  The per-line, colour and seamless keys appear only
+    when their flags were given."""
+    rectify, perspective, curve, seamless = rectify_from_args(a), perspective_from_args(a), curve_from_args(a), seamless_from_args(a)
     if not a.paste_back:
         for flag in ("paste_region", "paste_per_line", "paste_color_match", "paste_color_ring"):
             if getattr(a, flag, None) not in (None, False):
@@ -186,6 +208,8 @@ def paste_back_from_args(a):
         pb["perspective"] = perspective
     if curve is not None:
         pb["curve"] = curve
+    if seamless is not None:
+        pb["seamless"] = seamless
     return pb
 
 

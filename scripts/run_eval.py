@@ -103,6 +103,12 @@ def build_parser(lora: bool = False):
                     "curved, default 0.2 (implies --paste_curve)")
     ap.add_argument("--paste_curve_max_squeeze", type=float, default=None, metavar="F", help="largest crop reach / radius of curvature, "
                     "default 0.75 (implies --paste_curve)")
+    ap.add_argument("--paste_seamless", action="store_true", help="add a pull-push membrane to each pasted edit before the blend, so that it meets "
+                    "the scene at the seam (with --paste_back)")
+    ap.add_argument("--paste_seamless_smooth", type=int, default=None, metavar="N", help="Jacobi sweeps after the push, 0..255, default 8 "
+                    "(implies --paste_seamless)")
+    ap.add_argument("--paste_seamless_max_shift", type=int, default=None, metavar="N", help="largest correction in grey levels, 0..255, "
+                    "default 32 (implies --paste_seamless)")
     ap.add_argument("--items", type=str, default=None, help="JSON list of {image, mask, text} instead of --json_path")
     ap.add_argument("--out", type=str, default=None, help="output folder of --items mode")
     ap.add_argument("--num_inference_steps", type=int, default=None, help=argparse.SUPPRESS)
@@ -188,6 +194,12 @@ def main(argv=None, lora: bool = False, script: str = __file__):
             raise SystemExit(f"--{curve_given[0]} needs --paste_back --paste_per_line")
         limits = {k: getattr(a, "paste_curve_" + k) for k in ("min_bend", "max_squeeze") if getattr(a, "paste_curve_" + k) is not None}
         paste_back["curve"] = limits or True
+    seamless_given = [f for f in ("paste_seamless", "paste_seamless_smooth", "paste_seamless_max_shift") if getattr(a, f) not in (None, False)]
+    if seamless_given:
+        if not a.paste_back:
+            raise SystemExit(f"--{seamless_given[0]} needs --paste_back")
+        values = {k: getattr(a, "paste_seamless_" + k) for k in ("smooth", "max_shift") if getattr(a, "paste_seamless_" + k) is not None}
+        paste_back["seamless"] = values or True
     legacy = a.items is not None
     weights = a.lora_weights_path if lora else a.weights_path
     if not legacy and not (a.json_path and a.original_images_dir and weights):

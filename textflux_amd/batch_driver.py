@@ -76,9 +76,10 @@ def _paste_back_cfg(paste_back: Dict[str, Any]) -> Dict[str, Any]:
     and, only when the caller gave them, per_line: True (which implies a region: {} when absent) and color_match: paste_back.
     color_match_cfg's dict(ring, gain, max_shift, min_pixels), rectify: rectify.rectify_cfg's dict(min_angle, max_angle, min_aspect)
     perspective: perspective.perspective_cfg's dict(max_fit, max_taper, min_aspect, max_angle) and curve: curve.curve_cfg's
-    dict(min_bend, max_squeeze, max_turn, min_aspect, min_fill, max_angle) (all three need per_line)."""
+    dict(min_bend, max_squeeze, max_turn, min_aspect, min_fill, max_angle) (all three need per_line), and seamless: paste_back.
+    seamless_cfg's dict(smooth, max_shift)."""
     from . import paste_back as pb
-    unknown = set(paste_back) - {"dilate", "feather", "region", "per_line", "color_match", "rectify", "perspective", "curve"}
+    unknown = set(paste_back) - {"dilate", "feather", "region", "per_line", "color_match", "rectify", "perspective", "curve", "seamless"}
     region = paste_back.get("region")
     if region is not None:
         unknown |= {f"region.{k}" for k in set(region) - {"pad", "min_side", "max_side"}}
@@ -102,6 +103,14 @@ def _paste_back_cfg(paste_back: Dict[str, Any]) -> Dict[str, Any]:
             raise ValueError("paste_back: color_match must be None, True or a dict")
         try:
             cfg["color_match"] = pb.color_match_cfg(color_match)
+        except ValueError as e:
+            raise ValueError(f"paste_back: {e}") from None
+    seamless = paste_back.get("seamless")
+    if seamless is not None and seamless is not False:
+        if seamless is not True and not isinstance(seamless, dict):
+            raise ValueError("paste_back: seamless must be None, True or a dict")
+        try:
+            cfg["seamless"] = pb.seamless_cfg(seamless)
         except ValueError as e:
             raise ValueError(f"paste_back: {e}") from None
     rectify = paste_back.get("rectify")
@@ -363,6 +372,8 @@ def _paste_into_original(pipe, w: Work, cropped, cfg: Dict[str, Any]):
     oc = w.orig_scene[reg.y0:reg.y1, reg.x0:reg.x1]
     om = pb.grey_of(w.orig_mask[reg.y0:reg.y1, reg.x0:reg.x1])
     kw = dict(color_match=cfg["color_match"]) if cfg.get("color_match") else {}      # passed only then: older pipelines keep working
+    if cfg.get("seamless"):
+        kw["seamless"] = cfg["seamless"]
     pasted = pipe.paste_back(oc, cropped, om, dilate=cfg["dilate"], feather=cfg["feather"], **kw)
     pasted = pasted.cpu().numpy() if isinstance(pasted, torch.Tensor) else np.asarray(pasted)
     out = w.orig_scene.copy()
@@ -488,7 +499,12 @@ def run_items(items: Sequence[Dict[str, Any]], pipe, out_dir: Optional[str], bat
     curve=True | dict(min_bend, max_squeeze, max_turn, min_aspect, min_fill, max_angle) (with per_line; DESIGN.md section 4 "Curved
     lines"): a line whose centre line bends (curve.is_curved) is cut as a ribbon around that centre line, warped upright on the device
     through a control grid (pipe.warp_grid), edited upright and warped back under the same alpha.  It is tried first; all three may be
-    set."""
+    set.
+    seamless=True | dict(smooth, max_shift) (DESIGN.md section 4 "Seamless paste"; with or without per_line, region and the three
+    warps): the final blend of every paste adds a membrane to the edit first -- its difference to the original scene, known just outside
+    the blend, interpolated across the blend's support by a pull-push pyramid, smoothed by `smooth` Jacobi sweeps (default 8) and clamped
+    to +- max_shift grey levels (default 32) -- so that the edit meets the scene at the seam; with color_match the table is fitted as
+    before and the membrane removes what it leaves.  The bytes outside the grown mask stay the original's."""
     if paste_back is not None:       # refused before anything is prepared or encoded
         if mixed_pad > 0:
             raise NotImplementedError("paste_back does not serve mixed-geometry batches (mixed_pad > 0)")

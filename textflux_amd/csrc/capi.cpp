@@ -413,6 +413,13 @@ int tfx_overlay_lut_u8(const void* orig, const void* edit, const void* alpha, co
   if (!orig || !edit || !alpha || !lut || !out) return fail("tfx_overlay_lut_u8: null pointer");
   return overlay_lut_u8(orig, edit, alpha, lut, out, B, H, W, C, S(stream));
 }
+int64_t tfx_seamless_workspace_bytes(int32_t B, int32_t H, int32_t W, int32_t C) { return seamless_workspace_bytes(B, H, W, C); }
+int tfx_seamless_overlay_u8(const void* orig, const void* ref, const void* edit, const void* alpha, const void* covered, const void* lut,
+                            void* out, void* workspace, int64_t workspace_bytes, int32_t B, int32_t H, int32_t W, int32_t C, int32_t smooth,
+                            int32_t max_shift, tfx_stream stream) {
+  if (!orig || !ref || !edit || !alpha || !out || !workspace) return fail("tfx_seamless_overlay_u8: null pointer");
+  return seamless_overlay_u8(orig, ref, edit, alpha, covered, lut, out, workspace, workspace_bytes, B, H, W, C, smooth, max_shift, S(stream));
+}
 int tfx_warp_affine_u8(const void* in, void* out, void* coverage, int32_t B, int32_t H, int32_t W, int32_t C, int32_t out_h, int32_t out_w,
                        const int64_t* m, const int16_t* taps, tfx_stream stream) {
   if (!in || !out || !m || !taps) return fail("tfx_warp_affine_u8: null pointer");

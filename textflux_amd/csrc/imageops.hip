@@ -527,6 +527,187 @@ __global__ __launch_bounds__(256) void overlay_lut_u8_kernel(const uint8_t* orig
   }
 }
 
+// ---- seamless paste (DESIGN.md section 4 "Seamless paste"): a membrane v (i16, 6 fractional bits, C values per pixel) that equals
+// ref - edit on the known pixels (alpha == 0 and covered) and is interpolated across alpha's support by a pull-push pyramid, then
+// smoothed by Jacobi sweeps and added to the edit before the blend.  include/textflux_hip.h spells the arithmetic out; it is integer
+// arithmetic only, so the result is exact.  Level l of a sample is (values i16 [h][w][C], flags u8 [h][w]); flag bit 0 = filled (at
+// level 0: known), bit 1 (level 0 only) = free (alpha > 0).  One thread per pixel and all its channels; blockIdx.y = the sample in
+// the per-level kernels.  Every neighbour index is clamped into its level, so no access leaves the workspace whatever the masks hold.
+constexpr int kSeamFilled = 1, kSeamFree = 2;
+constexpr int kSeamTopPixels = 2048;                 // the levels from the first one whose whole pyramid has at most this many pixels up to 1 x 1 are one launch, in LDS
+constexpr int kSeamTopLevels = 16;                   // 2048 pixels halve to one in at most 12 levels
+constexpr int kSeamMaxLevels = 33;                   // a side below 2^31 halves (rounding up) to 1 in at most 31 steps
+
+__device__ __forceinline__ int seam_floor_div(int n, int d) {                // floor(n / d) for d > 0
+  const int q = n / d;
+  return (n % d < 0) ? q - 1 : q;
+}
+
+// Coarse pixel (y, x) of the level (hc, wc) from its up to four in-bounds, filled children in the fine level (h, w).
+template <int C>
+__device__ __forceinline__ void seam_pull_px(const int16_t* fv, const uint8_t* ff, int h, int w, int16_t* cv, uint8_t* cf, int wc, int y, int x) {
+  int n = 0, s[C];
+#pragma unroll
+  for (int c = 0; c < C; ++c) s[c] = 0;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const int yy = 2 * y + (k >> 1), xx = 2 * x + (k & 1);
+    if (yy >= h || xx >= w) continue;
+    const int64_t p = (int64_t)yy * w + xx;
+    if (!(ff[p] & kSeamFilled)) continue;
+    ++n;
+#pragma unroll
+    for (int c = 0; c < C; ++c) s[c] += fv[p * C + c];
+  }
+  const int64_t o = (int64_t)y * wc + x;
+  cf[o] = n > 0 ? kSeamFilled : 0;
+#pragma unroll
+  for (int c = 0; c < C; ++c) cv[o * C + c] = (int16_t)(n > 0 ? seam_floor_div(2 * s[c] + n, 2 * n) : 0);
+}
+
+// Unfilled fine pixel (y, x) of the level (h, w) from the complete coarse level (hc, wc): the 2x upsample with weights 9 3 3 1.
+template <int C>
+__device__ __forceinline__ void seam_push_px(int16_t* fv, const uint8_t* ff, int w, const int16_t* cv, int hc, int wc, int y, int x) {
+  const int64_t p = (int64_t)y * w + x;
+  if (ff[p] & kSeamFilled) return;
+  const int i = y >> 1, j = x >> 1;
+  int i2 = i + ((y & 1) ? 1 : -1), j2 = j + ((x & 1) ? 1 : -1);
+  i2 = i2 < 0 ? 0 : i2 > hc - 1 ? hc - 1 : i2;
+  j2 = j2 < 0 ? 0 : j2 > wc - 1 ? wc - 1 : j2;
+  const int64_t a = ((int64_t)i * wc + j) * C, b = ((int64_t)i * wc + j2) * C, d = ((int64_t)i2 * wc + j) * C, e = ((int64_t)i2 * wc + j2) * C;
+#pragma unroll
+  for (int c = 0; c < C; ++c) fv[p * C + c] = (int16_t)((9 * cv[a + c] + 3 * cv[b + c] + 3 * cv[d + c] + cv[e + c] + 8) >> 4);
+}
+
+// Level 0: flags, and v = (ref - lut[edit]) * 64 on the known pixels, 0 elsewhere.  hw = H W pixels per sample.
+template <int C>
+__global__ __launch_bounds__(256) void seam_init_kernel(const uint8_t* __restrict__ ref, const uint8_t* __restrict__ edit,
+                                                        const uint8_t* __restrict__ alpha, const uint8_t* __restrict__ covered,
+                                                        const uint8_t* __restrict__ lut, int16_t* __restrict__ v, uint8_t* __restrict__ flags,
+                                                        int64_t hw) {
+  __shared__ uint8_t tab[C * 256];
+  const int s = blockIdx.y;
+  if (lut) {
+    for (int k = threadIdx.x; k < 256 * C; k += 256) tab[k] = lut[(int64_t)s * 256 * C + k];
+    __syncthreads();
+  }
+  const int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (p >= hw) return;
+  const int64_t q = s * hw + p;
+  const unsigned a = alpha[q];
+  const bool known = a == 0 && (!covered || covered[q] != 0);
+  flags[q] = (uint8_t)((known ? kSeamFilled : 0) | (a > 0 ? kSeamFree : 0));
+#pragma unroll
+  for (int c = 0; c < C; ++c) {
+    const int e = lut ? tab[c * 256 + edit[q * C + c]] : edit[q * C + c];
+    v[q * C + c] = (int16_t)(known ? ((int)ref[q * C + c] - e) * 64 : 0);
+  }
+}
+
+template <int C>
+__global__ __launch_bounds__(256) void seam_pull_kernel(const int16_t* __restrict__ fv, const uint8_t* __restrict__ ff, int h, int w,
+                                                        int16_t* __restrict__ cv, uint8_t* __restrict__ cf) {
+  const int hc = (h + 1) / 2, wc = (w + 1) / 2;
+  const int64_t n = (int64_t)hc * wc, k = (int64_t)blockIdx.x * 256 + threadIdx.x, s = blockIdx.y;
+  if (k >= n) return;
+  const int64_t fn = (int64_t)h * w;
+  seam_pull_px<C>(fv + s * fn * C, ff + s * fn, h, w, cv + s * n * C, cf + s * n, wc, (int)(k / wc), (int)(k % wc));
+}
+
+template <int C>
+__global__ __launch_bounds__(256) void seam_push_kernel(int16_t* __restrict__ fv, const uint8_t* __restrict__ ff, int h, int w,
+                                                        const int16_t* __restrict__ cv) {
+  const int hc = (h + 1) / 2, wc = (w + 1) / 2;
+  const int64_t n = (int64_t)h * w, k = (int64_t)blockIdx.x * 256 + threadIdx.x, s = blockIdx.y;
+  if (k >= n) return;
+  seam_push_px<C>(fv + s * n * C, ff + s * n, w, cv + s * (int64_t)hc * wc * C, hc, wc, (int)(k / w), (int)(k % w));
+}
+
+// The small levels in one launch: one workgroup per sample loads the level (h, w) (its pyramid up to 1 x 1 has at most kSeamTopPixels
+// pixels: the launcher picks it so), pulls up to 1 x 1 and pushes back down in LDS, and stores the completed level.  An unfilled 1 x 1
+// top holds 0 (seam_pull_px writes 0 there, seam_init_kernel when the image itself is 1 x 1).
+template <int C>
+__global__ __launch_bounds__(256) void seam_top_kernel(int16_t* __restrict__ gv, const uint8_t* __restrict__ gf, int h, int w) {
+  __shared__ int16_t sv[kSeamTopPixels * C];
+  __shared__ uint8_t sf[kSeamTopPixels];
+  int lh[kSeamTopLevels], lw[kSeamTopLevels], lo[kSeamTopLevels];
+  int L = 0;
+  lh[0] = h; lw[0] = w; lo[0] = 0;
+  while ((lh[L] > 1 || lw[L] > 1) && L < kSeamTopLevels - 1) {
+    lh[L + 1] = (lh[L] + 1) / 2; lw[L + 1] = (lw[L] + 1) / 2; lo[L + 1] = lo[L] + lh[L] * lw[L];
+    ++L;
+  }
+  const int n0 = h * w, tid = threadIdx.x;
+  gv += (int64_t)blockIdx.x * n0 * C;
+  gf += (int64_t)blockIdx.x * n0;
+  for (int k = tid; k < n0; k += 256) sf[k] = gf[k];
+  for (int k = tid; k < n0 * C; k += 256) sv[k] = gv[k];
+  __syncthreads();
+  for (int l = 0; l < L; ++l) {
+    const int wc = lw[l + 1], nc = lh[l + 1] * wc;
+    for (int k = tid; k < nc; k += 256)
+      seam_pull_px<C>(sv + lo[l] * C, sf + lo[l], lh[l], lw[l], sv + lo[l + 1] * C, sf + lo[l + 1], wc, k / wc, k % wc);
+    __syncthreads();
+  }
+  for (int l = L - 1; l >= 0; --l) {
+    const int wf = lw[l], nf = lh[l] * wf;
+    for (int k = tid; k < nf; k += 256) seam_push_px<C>(sv + lo[l] * C, sf + lo[l], wf, sv + lo[l + 1] * C, lh[l + 1], lw[l + 1], k / wf, k % wf);
+    __syncthreads();
+  }
+  for (int k = tid; k < n0 * C; k += 256) gv[k] = sv[k];
+}
+
+// One Jacobi sweep at level 0, src -> dst (two buffers: no pixel depends on the update order): free pixels become
+// (N + S + E + W + 2) >> 2 with a neighbour outside the window counted as the centre; all others are copied.
+template <int C>
+__global__ __launch_bounds__(256) void seam_smooth_kernel(const int16_t* __restrict__ src, int16_t* __restrict__ dst,
+                                                          const uint8_t* __restrict__ flags, int H, int W) {
+  const int64_t hw = (int64_t)H * W, p = (int64_t)blockIdx.x * 256 + threadIdx.x, s = blockIdx.y;
+  if (p >= hw) return;
+  src += s * hw * C; dst += s * hw * C;
+  if (!(flags[s * hw + p] & kSeamFree)) {
+#pragma unroll
+    for (int c = 0; c < C; ++c) dst[p * C + c] = src[p * C + c];
+    return;
+  }
+  const int y = (int)(p / W), x = (int)(p % W);
+  const int64_t pn = y > 0 ? p - W : p, ps = y < H - 1 ? p + W : p, pw = x > 0 ? p - 1 : p, pe = x < W - 1 ? p + 1 : p;
+#pragma unroll
+  for (int c = 0; c < C; ++c) dst[p * C + c] = (int16_t)((src[pn * C + c] + src[ps * C + c] + src[pe * C + c] + src[pw * C + c] + 2) >> 2);
+}
+
+// out = orig where alpha == 0, else (orig (255 - a) + e' a + 127) / 255 with e' = clamp(lut[edit] + clamp((v + 32) >> 6, -max_shift,
+// max_shift), 0, 255).  out may be orig (a thread reads the bytes it writes, and no others), so neither carries __restrict__.
+template <int C>
+__global__ __launch_bounds__(256) void seam_apply_kernel(const uint8_t* orig, const uint8_t* __restrict__ edit, const uint8_t* __restrict__ alpha,
+                                                         const uint8_t* __restrict__ lut, const int16_t* __restrict__ v, uint8_t* out, int64_t hw,
+                                                         int max_shift) {
+  __shared__ uint8_t tab[C * 256];
+  const int s = blockIdx.y;
+  if (lut) {
+    for (int k = threadIdx.x; k < 256 * C; k += 256) tab[k] = lut[(int64_t)s * 256 * C + k];
+    __syncthreads();
+  }
+  const int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (p >= hw) return;
+  const int64_t q = s * hw + p;
+  const unsigned a = alpha[q];
+#pragma unroll
+  for (int c = 0; c < C; ++c) {
+    const unsigned o = orig[q * C + c];
+    unsigned r = o;
+    if (a > 0) {
+      int e = lut ? tab[c * 256 + edit[q * C + c]] : edit[q * C + c];
+      int d = ((int)v[q * C + c] + 32) >> 6;
+      d = d < -max_shift ? -max_shift : d > max_shift ? max_shift : d;
+      e += d;
+      e = e < 0 ? 0 : e > 255 ? 255 : e;
+      r = (o * (255u - a) + (unsigned)e * a + 127u) / 255u;
+    }
+    out[q * C + c] = (uint8_t)r;
+  }
+}
+
 // ---- rectified per-line edits (DESIGN.md section 4 "Rectified lines"): out[b, j, i, :] = in[b] sampled at the affine image of the
 // destination pixel (i, j), 4 x 4 Catmull-Rom taps, edge replicated.  Integer arithmetic only (include/textflux_hip.h spells it out),
 // so the result is exact.  One 256-thread workgroup per 32 x 8 destination tile: its rotated source footprint is a compact patch
@@ -782,6 +963,96 @@ int overlay_lut_u8(const void* orig, const void* edit, const void* alpha, const 
   else overlay_lut_u8_kernel<false><<<dim3(grid, B), 256, 0, st>>>((const uint8_t*)orig, (const uint8_t*)edit, (const uint8_t*)alpha,
                                                                    (const uint8_t*)lut, (uint8_t*)out, n, C);
   return check_launch("overlay_lut_u8");
+}
+
+// The seamless paste's workspace: per level the values i16 [B][h][w][C] and the flags u8 [B][h][w], level 0 with a second value buffer
+// for the Jacobi ping-pong; every part starts at a multiple of 16 bytes.  Host arithmetic only.
+struct SeamLayout {
+  int levels;                                        // level `levels - 1` is 1 x 1
+  int h[kSeamMaxLevels], w[kSeamMaxLevels];
+  int64_t v[kSeamMaxLevels], f[kSeamMaxLevels], v0b, bytes;
+  int top;                                           // the level seam_top_kernel starts from
+};
+
+static int seam_geometry(const char* what, int B, int H, int W, int C) {
+  if (B < 1 || H < 1 || W < 1) return fail("%s: B, H, W must be at least 1", what);
+  if (C < 1 || C > 4) return fail("%s: 1..4 channels", what);
+  if (B > 65535) return fail("%s: batch %d exceeds 65535", what, B);
+  if ((int64_t)H * W * C > kMaxBytes) return fail("%s: more than 2^38 bytes per sample", what);
+  return 0;
+}
+
+static void seam_layout(int B, int H, int W, int C, SeamLayout* L) {
+  auto up16 = [](int64_t n) { return (n + 15) & ~(int64_t)15; };
+  int n = 0;
+  L->h[0] = H; L->w[0] = W;
+  while (L->h[n] > 1 || L->w[n] > 1) {
+    L->h[n + 1] = (L->h[n] + 1) / 2; L->w[n + 1] = (L->w[n] + 1) / 2;
+    ++n;
+  }
+  L->levels = n + 1;
+  int64_t off = 0, tail = 0;
+  L->top = n;
+  for (int l = n; l >= 0; --l) {                     // the lowest level whose pyramid fits seam_top_kernel's LDS
+    tail += (int64_t)L->h[l] * L->w[l];
+    if (tail <= kSeamTopPixels && n - l < kSeamTopLevels) L->top = l;
+  }
+  for (int l = 0; l <= n; ++l) {
+    const int64_t px = (int64_t)B * L->h[l] * L->w[l];
+    L->v[l] = off; off += up16(px * C * 2);
+    if (l == 0) { L->v0b = off; off += up16(px * C * 2); }
+    L->f[l] = off; off += up16(px);
+  }
+  L->bytes = off;
+}
+
+int64_t seamless_workspace_bytes(int B, int H, int W, int C) {
+  if (seam_geometry("seamless_workspace_bytes", B, H, W, C)) return -1;
+  SeamLayout L;
+  seam_layout(B, H, W, C, &L);
+  return L.bytes;
+}
+
+template <int C>
+static void seamless_launch(const uint8_t* orig, const uint8_t* ref, const uint8_t* edit, const uint8_t* alpha, const uint8_t* covered,
+                            const uint8_t* lut, uint8_t* out, char* ws, const SeamLayout& L, int B, int smooth, int max_shift, hipStream_t st) {
+  auto V = [&](int l) { return (int16_t*)(ws + L.v[l]); };
+  auto F = [&](int l) { return (uint8_t*)(ws + L.f[l]); };
+  auto grid = [&](int l) { return dim3(blocks_for((int64_t)L.h[l] * L.w[l]), B); };
+  const int64_t hw = (int64_t)L.h[0] * L.w[0];
+  seam_init_kernel<C><<<grid(0), 256, 0, st>>>(ref, edit, alpha, covered, lut, V(0), F(0), hw);
+  for (int l = 0; l < L.top; ++l) seam_pull_kernel<C><<<grid(l + 1), 256, 0, st>>>(V(l), F(l), L.h[l], L.w[l], V(l + 1), F(l + 1));
+  seam_top_kernel<C><<<B, 256, 0, st>>>(V(L.top), F(L.top), L.h[L.top], L.w[L.top]);
+  for (int l = L.top - 1; l >= 0; --l) seam_push_kernel<C><<<grid(l), 256, 0, st>>>(V(l), F(l), L.h[l], L.w[l], V(l + 1));
+  int16_t *cur = V(0), *other = (int16_t*)(ws + L.v0b);
+  for (int k = 0; k < smooth; ++k) {
+    seam_smooth_kernel<C><<<grid(0), 256, 0, st>>>(cur, other, F(0), L.h[0], L.w[0]);
+    int16_t* t = cur; cur = other; other = t;
+  }
+  seam_apply_kernel<C><<<grid(0), 256, 0, st>>>(orig, edit, alpha, lut, cur, out, hw, max_shift);
+}
+
+int seamless_overlay_u8(const void* orig, const void* ref, const void* edit, const void* alpha, const void* covered, const void* lut, void* out,
+                        void* workspace, int64_t workspace_bytes, int B, int H, int W, int C, int smooth, int max_shift, hipStream_t st) {
+  if (seam_geometry("seamless_overlay_u8", B, H, W, C)) return 1;
+  if (smooth < 0 || smooth > 255) return fail("seamless_overlay_u8: smooth must be in [0, 255]");
+  if (max_shift < 0 || max_shift > 255) return fail("seamless_overlay_u8: max_shift must be in [0, 255]");
+  if (edit == out || alpha == out || covered == out || lut == out || workspace == out || (ref == out && ref != orig))
+    return fail("seamless_overlay_u8: out may alias orig only");
+  SeamLayout L;
+  seam_layout(B, H, W, C, &L);
+  if (workspace_bytes < L.bytes)
+    return fail("seamless_overlay_u8: workspace of %lld bytes, needs %lld (tfx_seamless_workspace_bytes)", (long long)workspace_bytes, (long long)L.bytes);
+  if ((uintptr_t)workspace & 15) return fail("seamless_overlay_u8: workspace must be 16-byte aligned");
+  const uint8_t *po = (const uint8_t*)orig, *pr = (const uint8_t*)ref, *pe = (const uint8_t*)edit, *pa = (const uint8_t*)alpha,
+                *pc = (const uint8_t*)covered, *pl = (const uint8_t*)lut;
+  switch (C) {
+    case 1: seamless_launch<1>(po, pr, pe, pa, pc, pl, (uint8_t*)out, (char*)workspace, L, B, smooth, max_shift, st); break;
+    case 2: seamless_launch<2>(po, pr, pe, pa, pc, pl, (uint8_t*)out, (char*)workspace, L, B, smooth, max_shift, st); break;
+    case 3: seamless_launch<3>(po, pr, pe, pa, pc, pl, (uint8_t*)out, (char*)workspace, L, B, smooth, max_shift, st); break;
+    default: seamless_launch<4>(po, pr, pe, pa, pc, pl, (uint8_t*)out, (char*)workspace, L, B, smooth, max_shift, st); break;
+  }
+  return check_launch("seamless_overlay_u8");
 }
 
 int warp_affine_u8(const void* in, void* out, void* coverage, int B, int H, int W, int C, int out_h, int out_w, const int64_t* m,

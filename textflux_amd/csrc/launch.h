@@ -216,6 +216,11 @@ constexpr int64_t MASKED_MOMENTS_SCRATCH_BYTES = 256 * 17 * 8;   // per sample
 int masked_moments_u8(const void* a, const void* b, const void* weight, void* out, void* scratch, int64_t scratch_bytes, int B, int H, int W,
                       int C, hipStream_t st);
 int overlay_lut_u8(const void* orig, const void* edit, const void* alpha, const void* lut, void* out, int B, int H, int W, int C, hipStream_t st);
+// seamless paste: the blend of overlay_lut_u8 (lut may be NULL) with a pull-push membrane of ref - edit, known where alpha == 0 (and
+// covered != 0 when given), added to the edit first; workspace: seamless_workspace_bytes (host arithmetic; -1 on bad geometry)
+int64_t seamless_workspace_bytes(int B, int H, int W, int C);
+int seamless_overlay_u8(const void* orig, const void* ref, const void* edit, const void* alpha, const void* covered, const void* lut, void* out,
+                        void* workspace, int64_t workspace_bytes, int B, int H, int W, int C, int smooth, int max_shift, hipStream_t st);
 // rectified per-line edits: out [B, out_h, out_w, C] u8 = in [B, H, W, C] sampled at the Q16 affine image (m i64 [B][6], device) of every
 // destination pixel, 4 x 4 taps from the i16 [256][4] table (device), edge replicated; coverage [B, out_h, out_w] u8 or NULL
 int warp_affine_u8(const void* in, void* out, void* coverage, int B, int H, int W, int C, int out_h, int out_w, const int64_t* m,

@@ -768,6 +768,40 @@ def overlay_lut(orig: torch.Tensor, edit: torch.Tensor, alpha: torch.Tensor, lut
     return out
 
 
+def seamless_overlay(orig: torch.Tensor, ref: torch.Tensor, edit: torch.Tensor, alpha: torch.Tensor, covered: Optional[torch.Tensor] = None,
+                     lut: Optional[torch.Tensor] = None, smooth: int = 8, max_shift: int = 32, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """ops.overlay_lut (ops.overlay without a table) with a membrane added to the edit first (tfx_seamless_overlay_u8; DESIGN.md section 4
+    "Seamless paste"): the difference ref - lut[edit], known where alpha == 0 (and covered != 0 when given), is interpolated across
+    alpha's support by a pull-push pyramid, smoothed by `smooth` Jacobi sweeps and clamped to +- max_shift grey levels.  uint8 images
+    orig, ref, edit [B, H, W, C] (C in 1..4; ref may be orig), uint8 alpha and covered [B, H, W], lut uint8 [B, C, 256].  Exact: integer
+    arithmetic.  out: None (a new tensor) or `orig` itself."""
+    _chk_dev(orig, ref, edit, alpha, covered, lut, out)
+    for t in (orig, ref, edit, alpha, covered, lut):
+        if t is not None and (t.dtype != torch.uint8 or not t.is_contiguous()):
+            raise ValueError("seamless_overlay: orig, ref, edit, alpha, covered and lut must be contiguous uint8 tensors")
+    if (orig.dim() != 4 or orig.numel() == 0 or not 1 <= orig.shape[3] <= 4 or edit.shape != orig.shape or ref.shape != orig.shape
+            or alpha.shape != orig.shape[:3] or (covered is not None and covered.shape != alpha.shape)):
+        raise ValueError(f"seamless_overlay: orig / ref / edit [B, H, W, C <= 4] and alpha / covered [B, H, W] must agree, got {tuple(orig.shape)}, "
+                         f"{tuple(ref.shape)}, {tuple(edit.shape)}, {tuple(alpha.shape)}" + ("" if covered is None else f", {tuple(covered.shape)}"))
+    B, H, W, Cc = orig.shape
+    if lut is not None and tuple(lut.shape) != (B, Cc, 256):
+        raise ValueError(f"seamless_overlay: lut must be [{B}, {Cc}, 256], got {tuple(lut.shape)}")
+    if not (0 <= int(smooth) <= 255 and 0 <= int(max_shift) <= 255):
+        raise ValueError(f"seamless_overlay: smooth and max_shift must be in [0, 255], got {smooth}, {max_shift}")
+    if out is None:
+        out = torch.empty_like(orig)
+    elif out.shape != orig.shape or out.dtype != torch.uint8 or not out.is_contiguous():
+        raise ValueError("seamless_overlay: out must be a contiguous uint8 tensor of orig's shape")
+    need = L.lib().tfx_seamless_workspace_bytes(B, H, W, Cc)
+    L.check(1 if need < 0 else 0, "seamless_overlay")
+    ws = torch.empty((need + 7) // 8, dtype=torch.int64, device=orig.device)
+    ptr = lambda t: None if t is None else t.data_ptr()
+    L.check(L.lib().tfx_seamless_overlay_u8(orig.data_ptr(), ref.data_ptr(), edit.data_ptr(), alpha.data_ptr(), ptr(covered), ptr(lut),
+                                            out.data_ptr(), ws.data_ptr(), ws.numel() * 8, B, H, W, Cc, int(smooth), int(max_shift),
+                                            _stream()), "seamless_overlay")
+    return out
+
+
 _WARP_TAPS = {}
 
 

@@ -19,6 +19,10 @@ look-up table, the least-squares line from the edit's colours to the original's 
     moments = (n, sum a, sum b, sum a a, sum a b) over ring_mask(alpha)    ops.masked_moments (exact 64-bit integer sums)
     lut     = fit_luts(moments)                                            host, Python integers up to the division
     out     = (orig (255 - alpha) + lut[edit] alpha + 127) // 255          ops.overlay_lut
+
+Seamless paste (opt-in, paste(seamless=...); DESIGN.md section 4 "Seamless paste"): the final blend becomes ops.seamless_overlay, which
+first adds a membrane to the (table-mapped) edit: the difference to the scene, known just outside the blend, interpolated across alpha's
+support by a pull-push pyramid, so that the edit meets the scene at the seam and keeps its own gradients inside.
 """
 from __future__ import annotations
 
@@ -126,6 +130,26 @@ def color_match_cfg(color_match) -> dict:
     return dict(ring=ring, gain=gain, max_shift=max_shift, min_pixels=min_pixels)
 
 
+# Seamless paste (DESIGN.md section 4 "Seamless paste"): the Jacobi sweeps after the push and the clamp of the correction in grey levels.
+# A starting point, not a tuned value and no quality claim.
+SEAMLESS_SMOOTH, SEAMLESS_MAX_SHIFT = 8, 32
+
+
+def seamless_cfg(seamless) -> dict:
+    """paste's seamless argument (True or a dict of smooth, max_shift) with its defaults filled in and checked."""
+    if seamless is not True and not isinstance(seamless, dict):
+        raise ValueError("seamless: must be True or a dict")
+    sm = {} if seamless is True else dict(seamless)
+    unknown = set(sm) - {"smooth", "max_shift"}
+    if unknown:
+        raise ValueError(f"seamless: unknown keys {sorted(unknown)}")
+    smooth = SEAMLESS_SMOOTH if sm.get("smooth") is None else int(sm["smooth"])
+    max_shift = SEAMLESS_MAX_SHIFT if sm.get("max_shift") is None else int(sm["max_shift"])
+    if not 0 <= smooth <= 255 or not 0 <= max_shift <= 255:
+        raise ValueError("seamless: smooth and max_shift must be in [0, 255]")
+    return dict(smooth=smooth, max_shift=max_shift)
+
+
 def ring_mask(alpha: torch.Tensor, ring: int = RING) -> torch.Tensor:
     """uint8 [B, H, W] blend weight -> 255 on the pixels within `ring` (square window) of alpha's support that are not in it, else 0:
     support = 255 where alpha > 0, ring = mask_dilate(support, ring) with the support's own pixels cleared.  These pixels lie just
@@ -166,7 +190,7 @@ def fit_luts(moments, gain: Tuple[float, float] = GAIN, max_shift: int = MAX_SHI
 
 
 def paste(original: torch.Tensor, edited: torch.Tensor, mask_grey: torch.Tensor, dilate: int = DILATE, feather: int = FEATHER,
-          color_match=None, color_ref: Optional[torch.Tensor] = None, rect=None, origin: Tuple[int, int] = (0, 0)) -> torch.Tensor:
+          color_match=None, color_ref: Optional[torch.Tensor] = None, rect=None, origin: Tuple[int, int] = (0, 0), seamless=None) -> torch.Tensor:
     """original uint8 [B, H, W, 3], edited uint8 [B, h, w, 3], mask_grey uint8 [B, H, W], all on the device -> [B, H, W, 3]: the edit,
     resampled to (H, W) when its size differs (ops.resample_u8: Pillow's bicubic), blended over the original under alpha_mask computed at
     the ORIGINAL resolution.  Outside the mask dilated by dilate + 3 feather the result is the original byte for byte; with
@@ -181,13 +205,19 @@ def paste(original: torch.Tensor, edited: torch.Tensor, mask_grey: torch.Tensor,
     ring is cut to the pixels the warp covered (their sample position lies inside the upright crop).
     rect may also be a perspective.Quad (DESIGN.md section 4 "Perspective lines"): the same, with the edit resampled to the quad's crop
     (rh, rw) and warped by ops.warp_perspective_u8 under perspective.matrices' upright -> scene homography.
-    Or a curve.Ribbon (DESIGN.md section 4 "Curved lines"): the same through ops.warp_grid_u8 under curve.grids' backward grid."""
+    Or a curve.Ribbon (DESIGN.md section 4 "Curved lines"): the same through ops.warp_grid_u8 under curve.grids' backward grid.
+    seamless: None, or True / dict(smooth, max_shift) (DESIGN.md section 4 "Seamless paste"): the final blend is ops.seamless_overlay
+    instead: the difference between color_ref (None: `original`) and the edit -- after the table, when color_match is set too -- is
+    taken on the pixels with alpha == 0 (that the warp covered, when there was one), interpolated across alpha's support and added to
+    the edit before the blend.  The alpha is the same, so the bytes outside the grown mask are still the original's.  color_ref may then
+    be given without color_match.  Without the key the calls are those above, unchanged."""
     if original.dtype != torch.uint8 or original.dim() != 4 or edited.dtype != torch.uint8 or edited.dim() != 4:
         raise ValueError("paste: original and edited must be uint8 [B, H, W, C]")
     if edited.shape[0] != original.shape[0] or edited.shape[3] != original.shape[3] or mask_grey.shape != original.shape[:3]:
         raise ValueError(f"paste: original {tuple(original.shape)}, edited {tuple(edited.shape)} and mask {tuple(mask_grey.shape)} do not agree")
-    if color_match is None and color_ref is not None:
+    if color_match is None and seamless is None and color_ref is not None:
         raise ValueError("paste: color_ref needs color_match")
+    sm = None if seamless is None else seamless_cfg(seamless)
     original, edited = original.contiguous(), edited.contiguous()
     covered = None
     if rect is not None:
@@ -204,17 +234,22 @@ def paste(original: torch.Tensor, edited: torch.Tensor, mask_grey: torch.Tensor,
     elif edited.shape[1:3] != original.shape[1:3]:
         edited = ops.resample_u8(edited, (original.shape[1], original.shape[2]))
     alpha = alpha_mask(mask_grey.contiguous(), dilate, feather)
-    if color_match is None:
+    if color_match is None and sm is None:
         return ops.overlay(original, edited, alpha)
-    cm = color_match_cfg(color_match)
+    cm = None if color_match is None else color_match_cfg(color_match)
     ref = original if color_ref is None else color_ref.contiguous()
     if ref.shape != original.shape or ref.dtype != torch.uint8:
         raise ValueError(f"paste: color_ref must be uint8 of original's shape {tuple(original.shape)}, got {ref.dtype} {tuple(ref.shape)}")
+    if cm is None:
+        return ops.seamless_overlay(original, ref, edited, alpha, covered=covered, smooth=sm["smooth"], max_shift=sm["max_shift"])
     ring = ring_mask(alpha, cm["ring"])
     if covered is not None:
         ring = ring & covered
     luts = fit_luts(ops.masked_moments(edited, ref, ring), cm["gain"], cm["max_shift"], cm["min_pixels"])
-    return ops.overlay_lut(original, edited, alpha, torch.from_numpy(luts).to(original.device))
+    luts = torch.from_numpy(luts).to(original.device)
+    if sm is not None:
+        return ops.seamless_overlay(original, ref, edited, alpha, covered=covered, lut=luts, smooth=sm["smooth"], max_shift=sm["max_shift"])
+    return ops.overlay_lut(original, edited, alpha, luts)
 
 
 def grey_of(mask) -> np.ndarray:
