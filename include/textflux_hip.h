@@ -152,6 +152,14 @@ int tfx_ln_modulate_fp8(const void* x, int64_t ldx, int64_t x_bstride, void* q8,
 int tfx_ln_modulate(const void* x, int64_t ldx, int64_t x_bstride, void* out, int64_t ldo, int64_t o_bstride,
                     const void* shift, const void* scale, int64_t mod_bstride, int32_t rows_per_batch, int32_t batch,
                     int32_t D, float eps, tfx_stream stream);
+/* The same pass with two modulations: rows < split_row of every sample take (shift2, scale2), the others (shift, scale), all four
+ * [batch][D] with stride mod_bstride -- the text and image streams of a double block, laid out as joint [text | image] rows, in one
+ * launch (what tfx_dit_forward runs).  Bit-identical to two tfx_ln_modulate calls on the two row ranges.  0 <= split_row <=
+ * rows_per_batch; shift2 / scale2 may be NULL when split_row == 0.  Added without a new TFX_ABI_VERSION: one new entry point, no
+ * stamped struct and no existing entry point changes. */
+int tfx_ln_modulate_split(const void* x, int64_t ldx, int64_t x_bstride, void* out, int64_t ldo, int64_t o_bstride,
+                          const void* shift, const void* scale, const void* shift2, const void* scale2, int32_t split_row,
+                          int64_t mod_bstride, int32_t rows_per_batch, int32_t batch, int32_t D, float eps, tfx_stream stream);
 
 /* ---- per-head RMSNorm * weight, then RoPE, in place on the q and k column ranges of a fused projection buffer
  *      [B][Ntok, ld] (heads of 128) (FluxAttnProcessor2_0, D/models/attention_processor.py:2001-2004, 2023-2037;
@@ -448,7 +456,9 @@ int tfx_conv3x3_nhwc(const void* x, int32_t B, int32_t inH, int32_t inW, int32_t
 int tfx_conv3x3_pair_nhwc(const void* x, int32_t B, int32_t H, int32_t W, int32_t Cin, const void* w_pair, const void* bias_pair,
                           void* out, int32_t Cout, const void* res, const void* zero_page, tfx_stream stream);
 /* GroupNorm(groups, eps, affine) followed by SiLU when silu != 0, x/out [B, HW, C] NHWC.  workspace: fp32
- * [B * (ceil(HW/1024) + 1) * groups * 2]. */
+ * [B * (ceil(HW/1024) + 1) * groups * 2]: the per-chunk partial sums [B, ceil(HW/1024), groups, 2] (sum, sum of squares), then the
+ * statistics [B, groups, 2] = (mean, rstd = rsqrt(var + eps)) the normalisation used, left there for the caller to read.
+ * groups in [1, 64], C a multiple of 8 and of groups, C / groups a multiple of 4, C / 8 a divisor of 256. */
 int tfx_groupnorm_nhwc(const void* x, void* out, const void* gamma, const void* beta, float* workspace, int32_t B,
                        int64_t HW, int32_t C, int32_t groups, float eps, int32_t silu, tfx_stream stream);
 

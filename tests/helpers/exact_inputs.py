@@ -18,6 +18,7 @@ BF = torch.bfloat16
 F8 = torch.float8_e4m3fn
 GATES = (0.5, 0.75, 1.0, 1.5, 2.0)                      # epilogue 2: +- these
 NORM_WEIGHTS = (0.5, 0.75, 1.0, 1.25, 1.5)              # q / k RMSNorm weights
+NORM_SHIFTS = (0.125, 0.375, 0.625, 0.875, 1.125)       # GroupNorm beta: no magnitude of NORM_WEIGHTS, so +-gamma + beta never cancels
 ROPE_PAIRS = ((1.0, 0.0), (-1.0, 0.0), (0.0, 1.0), (0.0, -1.0), (0.5, 0.5), (0.5, -0.5), (-0.5, 0.5), (-0.5, -0.5))   # (cos, sin)
 ACC_LIMIT = 256                                         # every integer of magnitude <= 256 is a bf16 value
 
@@ -411,6 +412,238 @@ def conv_operands(B, H, W, Cin, Cout, seed, stride=1, up=1, with_res=False):
     res = arbitrary_bf16(lin.shape, seed + 4) if with_res else None
     return dict(x=x.permute(0, 2, 3, 1).contiguous().to(BF), w=w.permute(0, 2, 3, 1).contiguous().to(BF), bias=bias.to(BF), res=res,
                 acc=acc, want=(res + lin) if with_res else lin)
+
+
+# --------------------------------------------------------------------------------------------------------- rows with exact statistics
+def zero_sum_rows(shape, D: int, seed: int, amp: int, offset: int = 0) -> torch.Tensor:
+    """fp32 [*shape, D] of integers: every row is D / 2 draws from [-amp, amp] and their negatives in a shuffled order, plus the integer
+    `offset`, so a row's sum is exactly offset * D.  Asserted: every value is a bf16 number, amp * D + |offset| * D < 2^24 (every partial
+    sum of a row is an integer fp32 holds) and sum (x - offset)^2 < 2^24, and so is sum x^2.  Then the mean (= offset), the centred values
+    and either sum of squares are exact in fp32 in EVERY summation order: the one freedom left to a kernel is the fp32 row factor."""
+    assert D % 2 == 0 and amp * D + abs(offset) * D < 2 ** 24
+    g = gen(seed)
+    rows = int(torch.Size(shape).numel())
+    h = torch.randint(-amp, amp + 1, (rows, D // 2), generator=g).float()
+    z = torch.cat([h, -h], 1)
+    z = torch.gather(z, 1, torch.rand(rows, D, generator=g).argsort(1))
+    x = (z + float(offset)).view(*shape, D)
+    assert bool((x.to(BF).float() == x).all()), "every value must be a bf16 number"
+    assert bool((x.double().sum(-1) == offset * D).all())
+    assert ((x.double() - offset) ** 2).sum(-1).max().item() < 2 ** 24 and (x.double() ** 2).sum(-1).max().item() < 2 ** 24
+    return x
+
+
+def zero_sum_groups(B: int, HW: int, C: int, groups: int, seed: int, offset: int = 0) -> torch.Tensor:
+    """fp32 [B, HW, C] (NHWC): the HW * C / groups values of every (sample, group) are a zero_sum_rows row (+ offset) whose amplitude
+    is 2, 4 or 8 by (sample, group), so that neighbouring groups have clearly different statistics."""
+    cpg = C // groups
+    n = HW * cpg
+    x = torch.empty(B, HW, C)
+    for i, amp in enumerate((2, 4, 8)):
+        rows = zero_sum_rows((B, groups), n, seed + i, amp, offset)                     # [B, groups, n]
+        pick = (torch.arange(B)[:, None] * 5 + torch.arange(groups)[None, :]) % 3 == i
+        blk = rows.view(B, groups, HW, cpg).permute(0, 2, 1, 3)                         # [B, HW, groups, cpg]
+        x.view(B, HW, groups, cpg)[:] = torch.where(pick[:, None, :, None], blk, x.view(B, HW, groups, cpg)) if i else blk
+    return x
+
+
+def nudge(r: torch.Tensor, ulps: int) -> torch.Tensor:
+    """r (fp32, positive) moved by `ulps` fp32 steps (negative: towards zero)."""
+    for _ in range(abs(ulps)):
+        r = torch.nextafter(r, torch.full_like(r, math.inf if ulps > 0 else 0.0))
+    return r
+
+
+def row_factor(arg: torch.Tensor) -> torch.Tensor:
+    """rsqrt(arg) of an fp32 argument: the root in fp64 rounded once, asserted to lie within one fp32 step of torch.rsqrt -- a device
+    rsqrt that is accurate to one step returns it or a neighbour."""
+    assert arg.dtype == torch.float32 and bool((arg > 0).all())
+    r = (1.0 / torch.sqrt(arg.double())).float()
+    t = torch.rsqrt(arg)
+    assert bool(((r == t) | (torch.nextafter(r, t) == t)).all())
+    return r
+
+
+def layernorm_factor(x: torch.Tensor, eps: float):
+    """(mean, r) [.., 1] fp32 of zero_sum_rows rows as the LayerNorm kernels form them: mean = sum / D, r = rsqrt(sum (x - mean)^2 / D +
+    eps) with the quotient and the sum each rounded to fp32 once.  Asserted: the mean and the sum of squares are integers below 2^24."""
+    D = x.shape[-1]
+    mean = x.double().mean(-1, keepdim=True)
+    ss = ((x.double() - mean) ** 2).sum(-1, keepdim=True)
+    assert bool((mean == mean.round()).all()) and bool((ss == ss.round()).all()) and ss.max().item() < 2 ** 24
+    return mean.float(), row_factor(ss.float() / float(D) + eps)
+
+
+def ln_modulate_chain(x, shift, scale, mean, r, split_row: int = 0, shift2=None, scale2=None) -> torch.Tensor:
+    """tfx_ln_modulate on x [B, R, D] with shift / scale bf16 [B, D] and the row statistics mean, r [B, R, 1] fp32, with torch's operators
+    and the kernel's rounding points: xn = bf16((x - mean) * r), t = bf16(1 + scale), out = bf16(bf16(xn * t) + shift).  Rows below
+    split_row of every sample take (shift2, scale2)."""
+    assert shift.dtype == BF and scale.dtype == BF
+    xn = ((x.float() - mean) * r).to(BF)
+    out = xn * (1 + scale)[:, None, :] + shift[:, None, :]
+    if split_row > 0:
+        out[:, :split_row] = xn[:, :split_row] * (1 + scale2)[:, None, :] + shift2[:, None, :]
+    return out
+
+
+def cancels(x, gamma, beta, mean, r) -> bool:
+    """True when some (x - mean) * r * gamma + beta nearly cancels.  Two steps of r and the rounding of the product move the sum by under
+    2^-21 |t gamma|; that has to stay inside a bf16 step (2^-8) of the result, or no tolerance counted in bf16 steps describes what a
+    correct kernel may store (a row whose variance is a square integer has a rational-looking r, and k * r * gamma == -beta happens)."""
+    tg = (x.float() - mean) * r * gamma.float()
+    return bool(((tg + beta.float()).abs() < 2.0 ** -12 * tg.abs()).any())
+
+
+def layernorm_affine_chain(x, gamma, beta, mean, r, fused: bool = False) -> torch.Tensor:
+    """tfx_layernorm: bf16((x - mean) * r * gamma + beta), fp32 and ONE bf16 rounding.  fused: the last multiply-add as one fma (the
+    compiler may contract it): t * gamma + beta is exact in fp64 (24 + 8 bits against a dyadic beta), rounded to fp32 once."""
+    t = (x.float() - mean) * r
+    assert not cancels(x, gamma, beta, mean, r), "t * gamma + beta cancels"
+    if fused:
+        v = t.double() * gamma.double() + beta.double()
+        assert bool(((v - beta.double()) == t.double() * gamma.double()).all())
+        return v.float().to(BF)
+    return (t * gamma.float() + beta.float()).to(BF)
+
+
+def groupnorm_stats(x: torch.Tensor, groups: int, eps: float):
+    """fp64 (mean, var, rstd) [B, groups] of x [B, HW, C] NHWC.  Asserted: a group's sum and sum of squares are integers below 2^24."""
+    B, HW, C = x.shape
+    v = x.double().view(B, HW, groups, C // groups).permute(0, 2, 1, 3).reshape(B, groups, -1)
+    s, q = v.sum(-1), (v ** 2).sum(-1)
+    assert q.max().item() < 2 ** 24 and s.abs().max().item() < 2 ** 24
+    mean = s / v.shape[-1]
+    var = q / v.shape[-1] - mean ** 2
+    return mean, var, 1.0 / torch.sqrt(var.clamp(min=0) + torch.tensor(eps, dtype=torch.float32).double())     # eps as the fp32 number the kernel adds
+
+
+def silu64(y: torch.Tensor) -> torch.Tensor:
+    return y.double() / (1.0 + torch.exp(-y.double()))
+
+
+def groupnorm_chain(x, gamma, beta, mean, rstd, groups: int, silu: bool, fused: bool = False) -> torch.Tensor:
+    """tfx_groupnorm_nhwc on x [B, HW, C] with the statistics mean, rstd fp32 [B, groups]: y = bf16((x - mean) * rstd * gamma + beta),
+    fp32 and one rounding (fused: as layernorm_affine_chain), then bf16(silu(y)) from fp64."""
+    B, HW, C = x.shape
+    cpg = C // groups
+    m = mean.float().repeat_interleave(cpg, 1)[:, None, :]
+    r = rstd.float().repeat_interleave(cpg, 1)[:, None, :]
+    y = layernorm_affine_chain(x, gamma, beta, m, r, fused)
+    return silu64(y).float().to(BF) if silu else y
+
+
+def settled(v64: torch.Tensor, rel: float) -> torch.Tensor:
+    """Elements of an fp64 result whose bf16 rounding does not change when the value moves by `rel` of itself either way."""
+    return (v64 * (1 - rel)).float().to(BF) == (v64 * (1 + rel)).float().to(BF)
+
+
+def t5_factor(x: torch.Tensor, eps: float) -> torch.Tensor:
+    """r [rows, 1] fp32 of T5LayerNorm as the kernel forms it: rsqrt(sum x^2 / D + eps).  Asserted: the sum is an integer below 2^24."""
+    ss = (x.double() ** 2).sum(-1, keepdim=True)
+    assert bool((ss == ss.round()).all()) and ss.max().item() < 2 ** 24
+    return row_factor(ss.float() / float(x.shape[-1]) + eps)
+
+
+def t5_rmsnorm_chain(x, w, r) -> torch.Tensor:
+    """tfx_rmsnorm: bf16(w * bf16(x * r)), x fp32 or bf16."""
+    return w * (x.float() * r).to(BF)
+
+
+def quick_gelu_chain(a: torch.Tensor) -> torch.Tensor:
+    """CLIP's x * sigmoid(1.702 x) on bf16 op by op -- bf16(1.702 x), bf16(sigmoid(.)), bf16(x * .) -- each step from fp64."""
+    u = (torch.tensor(1.702, dtype=torch.float32).double() * a.double()).float().to(BF)     # 1.702 as the fp32 constant of the product
+    sg = (1.0 / (1.0 + torch.exp(-u.double()))).float().to(BF)
+    return (a.double() * sg.double()).float().to(BF)
+
+
+def euler_chain(v, x, dsigma: float) -> torch.Tensor:
+    """FlowMatchEulerDiscreteScheduler.step on bf16 tensors: bf16(f32(x) + bf16(dsigma * v))."""
+    return (x.float() + torch.tensor(dsigma, dtype=BF) * v).to(BF)
+
+
+def amo_chain(v, x, noise, dt: float, a: float, b: float) -> torch.Tensor:
+    """StochasticRFOvershotDiscreteScheduler.step on bf16 tensors: bf16((f32(x) + bf16(dt * (-v))) * a + noise * b), a, b, noise fp32."""
+    x_over = x.float() + torch.tensor(dt, dtype=BF) * (-v)
+    return (x_over * torch.tensor(a, dtype=torch.float32) + noise * torch.tensor(b, dtype=torch.float32)).to(BF)
+
+
+def softmax_rows64(s: torch.Tensor, scale: float) -> torch.Tensor:
+    return torch.softmax(s.double() * float(torch.tensor(scale, dtype=torch.float32)), -1).float().to(BF)
+
+
+# The caps of tests/test_exact_rows_gpu.py.  Each *_SHARE is the share of the output elements of that file's cases whose stored bits change
+# when the row factor moves within what a correct kernel may return; tests/test_exact_inputs_cpu.py measures each and asserts it equal to the
+# constant.  The GPU tests compare with ulps=1 and cap = 4 * SHARE (the factor the q / k norm test argues for); a cap of 0 is bit-equality.
+#   LayerNorm + modulation, affine LayerNorm, T5 RMSNorm: the argument of the root -- an exact integer sum, one correctly rounded division
+#     by D, one correctly rounded + eps -- is the same fp32 number in every summation order, so r = rsqrt(arg) from a root accurate to one
+#     step is row_factor(arg) or a neighbour: ONE step either way.
+#   GroupNorm: TWO steps.  The kernel multiplies the exact sums by inv_count = fp32(1 / count), a rounded float unless count is a power of
+#     two (relative error <= 2^-24 in var, half of it in rstd: up to one step where the mantissa of rstd is near 2), and rsqrtf adds a step
+#     of its own.
+#   The two one-rounding forms (affine LayerNorm, GroupNorm) also count the elements on which the fused and the unfused evaluation of the
+#     final multiply-add differ: the compiler may contract it.
+LN_DS = (8, 504, 512, 520, 1544, 3064, 3072)            # 1 chunk | 63 of 64 lanes | one full round | round 1 with one lane | round 3 partly | round 5 short of one lane | all full
+LN_ROWS = (1, 3, 4, 5, 37)                              # below, at and above the four rows of a workgroup
+LN_OFFSETS = (0, 3)
+LN_AMP = 8
+LN_SPLIT_DS, LN_SPLIT_ROWS, LN_SPLIT_R = (520, 3072), (0, 1, 5, 37), 37
+LNA_DS, LNA_ROWS = (8, 520, 768, 3064), (1, 5, 77)
+GN_CASES = [(128, 32, 1), (128, 32, 1023), (128, 32, 1024), (128, 32, 1025), (256, 64, 8193), (512, 32, 300), (64, 4, 2100)]   # (C, groups, HW)
+GN_OFFSET_CASE = (128, 32, 1024)                        # count 4096, a power of two: mean = s * inv_count is exact with the offset 3
+T5_DS, T5_ROWS = (8, 100, 4096), (1, 5)
+LN_SHARE = 0.0
+LN_AFFINE_SHARE = 35 / 361880
+GN_SHARE = 167 / 5557504
+T5_SHARE = 0.0
+
+
+def ln_case(B: int, R: int, D: int, offset: int) -> dict:
+    """One LayerNorm + modulation case of the GPU file: x, the [B, 6 * D] modulation table its shift / scale (and shift2 / scale2) are
+    slices of, and the row statistics."""
+    seed = shape_seed(B, R, D, offset)
+    x = zero_sum_rows((B, R), D, seed, LN_AMP, offset)
+    mean, r = layernorm_factor(x, 1e-6)
+    return dict(x=x, mod=arbitrary_bf16((B, 6 * D), seed + 1, 0.5), mean=mean, r=r)
+
+
+def mod_slices(mod: torch.Tensor, D: int):
+    """(shift, scale, shift2, scale2): chunks 0, 1, 3, 4 of the six of an AdaLayerNormZero table."""
+    return mod[:, :D], mod[:, D:2 * D], mod[:, 3 * D:4 * D], mod[:, 4 * D:5 * D]
+
+
+def lna_case(rows: int, D: int) -> dict:
+    """x rows (offset 3 at 5 rows), dyadic gamma / beta; the first of sixteen seeds whose outputs do not cancel (see cancels)."""
+    for attempt in range(16):
+        seed = shape_seed(rows, D, 77 + attempt)
+        x = zero_sum_rows((rows,), D, seed, LN_AMP, 3 if rows == 5 else 0)
+        mean, r = layernorm_factor(x, 1e-5)
+        gamma, beta = choice(NORM_WEIGHTS, (D,), seed + 1, signed=True).to(BF), choice(NORM_WEIGHTS, (D,), seed + 2, signed=True).to(BF)
+        if not cancels(x, gamma, beta, mean, r):
+            return dict(x=x, gamma=gamma, beta=beta, mean=mean, r=r)
+    raise AssertionError(f"no seed without a cancelling output at rows {rows} D {D}")
+
+
+def gn_case(C: int, groups: int, HW: int, B: int = 2) -> dict:
+    """x [B, HW, C] zero-sum per (sample, group) (offset 3 at GN_OFFSET_CASE), dyadic gamma / beta, and the fp64 statistics."""
+    cpg = C // groups
+    for attempt in range(16):
+        seed = shape_seed(C, groups, HW, attempt)
+        x = zero_sum_groups(B, HW, C, groups, seed, 3 if (C, groups, HW) == GN_OFFSET_CASE else 0)
+        mean, var, rstd = groupnorm_stats(x, groups, 1e-6)
+        # a group of four values of one magnitude (HW = 1) normalises to +-1 / sqrt(1 + eps / a^2): with |beta| == |gamma| the output would be
+        # the rounding residue of gamma - gamma; beta's magnitudes are not gamma's, and a seed that still cancels somewhere is passed over
+        gamma, beta = choice(NORM_WEIGHTS, (C,), seed + 11, signed=True).to(BF), choice(NORM_SHIFTS, (C,), seed + 12, signed=True).to(BF)
+        if not cancels(x, gamma, beta, mean.float().repeat_interleave(cpg, 1)[:, None, :], rstd.float().repeat_interleave(cpg, 1)[:, None, :]):
+            return dict(x=x, gamma=gamma, beta=beta, mean=mean, rstd=rstd)
+    raise AssertionError(f"no seed without a cancelling output at C {C} groups {groups} HW {HW}")
+
+
+def t5_case(rows: int, D: int, f32: bool) -> dict:
+    """x integers (|x| <= 60 as fp32, <= 8 as bf16), w arbitrary bf16 near 1."""
+    seed = shape_seed(rows, D, int(f32))
+    x = zero_sum_rows((rows,), D, seed, 60 if f32 else LN_AMP)
+    w = (1 + 0.25 * torch.randn(D, generator=gen(seed + 1))).to(BF)
+    return dict(x=x if f32 else x.to(BF), w=w, r=t5_factor(x, 1e-6))
 
 
 # --------------------------------------------------------------------------------------------------------- the shapes of tests/test_exact_gpu.py

@@ -385,3 +385,154 @@ def test_conv_generator_condition_and_border_fault(B, H, W, Cin, Cout, stride, u
 @pytest.mark.parametrize("B,H,W,Cin,Cout", [c[:5] for c in X.CONV_NARROW_CASES + X.CONV_PAIR_CASES])
 def test_conv_generator_condition_holds_for_the_narrow_and_pair_cases(B, H, W, Cin, Cout):
     X.conv_operands(B, H, W, Cin, Cout, X.shape_seed(B, H, W, Cin, Cout), with_res=True)
+
+
+# ------------------------------------------------------------------------------------------------ rows with exact statistics
+def test_zero_sum_rows_meet_their_conditions_in_every_summation_order():
+    for D, offset in ((8, 0), (520, 3), (3072, 3), (100, 0)):
+        x = X.zero_sum_rows((2, 5), D, X.shape_seed(D, offset), X.LN_AMP, offset)
+        assert x.shape == (2, 5, D) and bool((x == x.round()).all()) and x.abs().max().item() <= X.LN_AMP + offset
+        assert x.unique().numel() > 8 and not torch.equal(x[0, 0], x[0, 1])
+        for order in (torch.arange(D), torch.arange(D - 1, -1, -1), torch.randperm(D, generator=X.gen(1))):     # fp32, three orders
+            assert bool((x[..., order].cumsum(-1)[..., -1] == offset * D).all())
+            assert torch.equal(((x - offset) ** 2)[..., order].cumsum(-1)[..., -1].double(), ((x.double() - offset) ** 2).sum(-1))
+        mean, r = X.layernorm_factor(x, 1e-6)
+        assert bool((mean == offset).all()) and r.shape == (2, 5, 1)
+    with pytest.raises(AssertionError):
+        X.zero_sum_rows((1,), 1 << 20, 1, 16)                                             # partial sums would leave 2^24
+    with pytest.raises(AssertionError, match="bf16 number"):
+        X.zero_sum_rows((1,), 8, 1, 300, 1)
+
+
+@pytest.mark.parametrize("C,groups,HW", X.GN_CASES)
+def test_zero_sum_groups_meet_their_conditions(C, groups, HW):
+    cs = X.gn_case(C, groups, HW)
+    off = 3.0 if (C, groups, HW) == X.GN_OFFSET_CASE else 0.0
+    assert bool((cs["mean"] == off).all()) and cs["x"].shape == (2, HW, C)
+    assert bool((cs["x"].to(BF).float() == cs["x"]).all())
+    if HW > 1:
+        assert cs["rstd"].unique().numel() > groups                                      # the statistics tell the (sample, group) pairs apart
+    if off:
+        n = HW * C // groups
+        assert n & (n - 1) == 0 and float(torch.tensor(1.0 / n, dtype=torch.float32)) * n == 1.0
+
+
+def test_chains_are_the_kernels_rounding_points_and_reject_the_faults_they_are_there_for():
+    B, R, D = 2, 5, 520
+    cs = X.ln_case(B, R, D, 3)
+    x, mean, r = cs["x"], cs["mean"], cs["r"]
+    sh, sc, sh2, sc2 = X.mod_slices(cs["mod"], D)
+    want = X.ln_modulate_chain(x, sh, sc, mean, r)
+    xn = ((x.double() - mean.double()) * r.double()).float().to(BF)                       # fp64 restatement, rounded where the chain rounds
+    t = (1.0 + sc.double()).float().to(BF)
+    prod = (xn.double() * t.double()[:, None]).float().to(BF)
+    assert torch.equal(want, (prod.double() + sh.double()[:, None]).float().to(BF))
+    split = X.ln_modulate_chain(x, sh, sc, mean, r, 2, sh2, sc2)
+    assert torch.equal(split[:, 2:], want[:, 2:]) and torch.equal(split[:, :2], X.ln_modulate_chain(x, sh2, sc2, mean, r)[:, :2])
+    rejects(split, want, "second modulation")
+    # (1 + scale) not rounded to bf16 before the product
+    loose = (xn.float() * (1.0 + sc.float())[:, None]).to(BF) + sh[:, None]
+    rejects(loose, want, "unrounded scale term")
+    # 1 / D taken from a chunk count padded to the next 64 chunks: the mean of the offset rows moves
+    Dp = (D // 8 + 63) // 64 * 64 * 8
+    rejects(X.ln_modulate_chain(x, sh, sc, mean * (D / Dp), r), want, "padded D")
+    rejects(X.ln_modulate_chain(x, sh, sc, mean, r * (D / Dp) ** 0.5), want, "padded D in the variance")
+    # the last chunk of a row taken from its clamped neighbour
+    x2 = x.clone()
+    x2[..., D - 8:] = x[..., D - 16:D - 8]
+    rejects(X.ln_modulate_chain(x2, sh, sc, mean, r), want, "clamped chunk")
+    la = X.lna_case(5, 520)
+    w = X.layernorm_affine_chain(la["x"], la["gamma"], la["beta"], la["mean"], la["r"])
+    e = ((la["x"].double() - la["mean"].double()) * la["r"].double()).float().double() * la["gamma"].double()
+    assert torch.equal(w, (e.float().double() + la["beta"].double()).float().to(BF))
+    rejects(((la["x"] - la["mean"]) * la["r"]).to(BF) * la["gamma"] + la["beta"], w, "three roundings")
+    tc = X.t5_case(5, 100, True)
+    w = X.t5_rmsnorm_chain(tc["x"], tc["w"], tc["r"])
+    assert torch.equal(w, (tc["w"].double() * (tc["x"].double() * tc["r"].double()).float().to(BF).double()).float().to(BF))
+    rejects((tc["w"].float() * (tc["x"] * tc["r"])).to(BF), w, "one rounding")
+
+
+def test_groupnorm_chain_and_the_second_group_slot():
+    C, groups, HW = 256, 64, 300
+    cs = X.gn_case(C, groups, HW)
+    mean, rstd = cs["mean"].float(), cs["rstd"].float()
+    want = X.groupnorm_chain(cs["x"], cs["gamma"], cs["beta"], mean, rstd, groups, False)
+    ref = torch.nn.functional.group_norm(cs["x"].double().permute(0, 2, 1), groups, cs["gamma"].double(), cs["beta"].double(), 1e-6).permute(0, 2, 1)
+    X.assert_elementwise(want, ref.float().to(BF), "chain vs F.group_norm in fp64", ulps=1, cap=1e-3)
+    bad = rstd.clone()
+    bad[:, 32:] = 1.0                                                                    # groups 32 .. 63 never finalised
+    msg = rejects(X.groupnorm_chain(cs["x"], cs["gamma"], cs["beta"], mean, bad, groups, False), want, "second slot")
+    assert "col 128)" in msg or "col 129)" in msg or "col 13" in msg
+    y = X.groupnorm_chain(cs["x"], cs["gamma"], cs["beta"], mean, rstd, groups, True)
+    assert torch.equal(y, torch.nn.functional.silu(want.double()).float().to(BF))
+    sure = X.settled(X.silu64(want), 2.0 ** -18)
+    assert 0.99 < sure.float().mean().item() <= 1.0
+
+
+def _moved(chain, r, steps):
+    """bool mask: elements whose bits change when r moves by up to `steps` fp32 steps either way."""
+    mid = chain(r)
+    moved = torch.zeros(mid.shape, dtype=torch.bool)
+    for d in range(1, steps + 1):
+        for sgn in (-1, 1):
+            moved |= X.mismatches(chain(X.nudge(r, sgn * d)), mid)
+    return mid, moved
+
+
+def test_ln_share_is_the_measured_one_step_sensitivity():
+    """Every (D, rows, offset) of the GPU file, B = 2, amp 8, split and plain (the same arithmetic per row)."""
+    n = m = 0
+    for D in X.LN_DS:
+        for R in X.LN_ROWS:
+            for off in X.LN_OFFSETS:
+                cs = X.ln_case(2, R, D, off)
+                sh, sc, _, _ = X.mod_slices(cs["mod"], D)
+                mid, moved = _moved(lambda r: X.ln_modulate_chain(cs["x"], sh, sc, cs["mean"], r), cs["r"], 1)
+                n, m = n + mid.numel(), m + int(moved.sum())
+    print(f"ln_modulate: {m} of {n} elements ({m / n:.3e}) change under one fp32 step of the row factor")
+    assert m / n == X.LN_SHARE
+
+
+def test_ln_affine_share_is_the_measured_sensitivity():
+    n = m = 0
+    for D in X.LNA_DS:
+        for rows in X.LNA_ROWS:
+            cs = X.lna_case(rows, D)
+            f = lambda r, fused=False: X.layernorm_affine_chain(cs["x"], cs["gamma"], cs["beta"], cs["mean"], r, fused)
+            mid, moved = _moved(f, cs["r"], 1)
+            moved |= X.mismatches(f(cs["r"], True), mid)
+            n, m = n + mid.numel(), m + int(moved.sum())
+    print(f"layernorm (affine): {m} of {n} elements ({m / n:.3e}) change under one fp32 step of the row factor or the contracted multiply-add")
+    assert m / n == X.LN_AFFINE_SHARE
+
+
+def test_gn_share_is_the_measured_sensitivity():
+    n = m = 0
+    for C, groups, HW in X.GN_CASES:
+        cs = X.gn_case(C, groups, HW)
+        f = lambda r, fused=False: X.groupnorm_chain(cs["x"], cs["gamma"], cs["beta"], cs["mean"], r, groups, False, fused)
+        mid, moved = _moved(f, cs["rstd"].float(), 2)
+        moved |= X.mismatches(f(cs["rstd"].float(), True), mid)
+        n, m = n + mid.numel(), m + int(moved.sum())
+    print(f"groupnorm: {m} of {n} elements ({m / n:.3e}) change under two fp32 steps of rstd or the contracted multiply-add")
+    assert m / n == X.GN_SHARE
+
+
+def test_t5_share_is_the_measured_one_step_sensitivity():
+    n = m = 0
+    for D in X.T5_DS:
+        for rows in X.T5_ROWS:
+            for f32 in (True, False):
+                cs = X.t5_case(rows, D, f32)
+                mid, moved = _moved(lambda r: X.t5_rmsnorm_chain(cs["x"], cs["w"], r), cs["r"], 1)
+                n, m = n + mid.numel(), m + int(moved.sum())
+    print(f"T5 rmsnorm: {m} of {n} elements ({m / n:.3e}) change under one fp32 step of the row factor")
+    assert m / n == X.T5_SHARE
+
+
+def test_scheduler_chains_are_the_reference_steps():
+    from oracle import sched_oracle as so
+    g = X.gen(5)
+    v, x, eps = X.arbitrary_bf16((37, 64), 1), X.arbitrary_bf16((37, 64), 2), torch.randn(37, 64, generator=g)
+    ds = torch.tensor(-0.03125)
+    assert torch.equal(X.euler_chain(v, x, -0.03125), so.euler_step(v, x, torch.tensor(1.0), torch.tensor(1.0) + ds))

@@ -174,6 +174,14 @@ int tfx_ln_modulate(const void* x, int64_t ldx, int64_t x_bstride, void* out, in
                      S(stream));
 }
 
+int tfx_ln_modulate_split(const void* x, int64_t ldx, int64_t x_bstride, void* out, int64_t ldo, int64_t o_bstride,
+                          const void* shift, const void* scale, const void* shift2, const void* scale2, int32_t split_row,
+                          int64_t mod_bstride, int32_t rows_per_batch, int32_t batch, int32_t D, float eps, tfx_stream stream) {
+  if (!x || !out || !shift || !scale) return fail("tfx_ln_modulate_split: null pointer");
+  return ln_modulate_split(x, out, shift, scale, shift2, scale2, split_row, mod_bstride, rows_per_batch, batch, D, ldx, x_bstride, ldo,
+                           o_bstride, eps, S(stream));
+}
+
 int tfx_layernorm(const void* x, int64_t ldx, void* out, int64_t ldo, const void* gamma, const void* beta, int64_t rows,
                   int32_t D, float eps, tfx_stream stream) {
   if (!x || !out || !gamma || !beta) return fail("tfx_layernorm: null pointer");

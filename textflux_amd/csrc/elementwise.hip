@@ -491,10 +491,16 @@ __global__ void advance_step_kernel(int* step_ptr) { *step_ptr += 1; }
 static int g_ln_prefetch = 2;
 void set_ln_prefetch(int v) { g_ln_prefetch = v; }
 static bool ln_prefetch_for(int64_t rows) { return g_ln_prefetch == 1 || (g_ln_prefetch == 2 && rows <= 16384); }
+// D == 0 passes D % 8 and the kernel's clamped chunk index min(.., nchunk - 1) would then be -1; a negative extent would size the grid
+static int ln_shape(const char* who, int64_t rows_per_batch, int64_t batch, int D) {
+  if (D <= 0 || D % 8 || D > 6 * 512) return fail("%s: D must be a positive multiple of 8 and <= 3072", who);
+  if (rows_per_batch < 0 || batch < 0) return fail("%s: negative row or batch count", who);
+  return 0;
+}
 int ln_modulate(const void* x, void* out, const void* shift, const void* scale, int64_t mod_bstride,
                 int rows_per_batch, int batch, int D, int64_t ldx, int64_t x_bstride, int64_t ldo,
                 int64_t o_bstride, float eps, hipStream_t st) {
-  if (D % 8 || D > 6 * 512) return fail("ln_modulate: D must be a multiple of 8 and <= 3072");
+  if (int e = ln_shape("ln_modulate", rows_per_batch, batch, D)) return e;
   const int64_t rows = (int64_t)rows_per_batch * batch;
   if (rows == 0) return 0;
   if (ln_prefetch_for(rows))
@@ -514,7 +520,7 @@ int ln_modulate(const void* x, void* out, const void* shift, const void* scale, 
 int ln_modulate_split(const void* x, void* out, const void* shift, const void* scale, const void* shift2, const void* scale2,
                       int split_row, int64_t mod_bstride, int rows_per_batch, int batch, int D, int64_t ldx, int64_t x_bstride, int64_t ldo,
                       int64_t o_bstride, float eps, hipStream_t st) {
-  if (D % 8 || D > 6 * 512) return fail("ln_modulate: D must be a multiple of 8 and <= 3072");
+  if (int e = ln_shape("ln_modulate_split", rows_per_batch, batch, D)) return e;
   if (split_row < 0 || split_row > rows_per_batch || (split_row > 0 && (!shift2 || !scale2))) return fail("ln_modulate_split: split_row / second modulation");
   const int64_t rows = (int64_t)rows_per_batch * batch;
   if (rows == 0) return 0;
@@ -531,8 +537,8 @@ int ln_modulate_split(const void* x, void* out, const void* shift, const void* s
 
 int layernorm_affine(const void* x, void* out, const void* gamma, const void* beta, int64_t rows, int D, int64_t ldx, int64_t ldo,
                      float eps, hipStream_t st) {
-  if (D % 8 || D > 6 * 512) return fail("layernorm: D must be a multiple of 8 and <= 3072");
-  if (rows <= 0) return 0;
+  if (int e = ln_shape("layernorm", rows, 1, D)) return e;
+  if (rows == 0) return 0;
   ln_modulate_kernel<6, false, true><<<dim3((unsigned)((rows + 3) / 4)), 256, 0, st>>>(
       (const bf16_t*)x, (bf16_t*)out, (const bf16_t*)beta, (const bf16_t*)gamma, 0, (int)std::min<int64_t>(rows, 1 << 30), rows, D,
       ldx, 0, ldo, 0, eps);
@@ -542,7 +548,7 @@ int layernorm_affine(const void* x, void* out, const void* gamma, const void* be
 int ln_modulate_fp8(const void* x, void* q8, float* q8_scale, const void* shift, const void* scale, int64_t mod_bstride,
                     int rows_per_batch, int batch, int D, int64_t ldx, int64_t x_bstride, int64_t ldq, int64_t q_bstride,
                     int64_t s_bstride, float eps, hipStream_t st) {
-  if (D % 8 || D > 6 * 512) return fail("ln_modulate_fp8: D must be a multiple of 8 and <= 3072");
+  if (int e = ln_shape("ln_modulate_fp8", rows_per_batch, batch, D)) return e;
   if (ldq % 8 || q_bstride % 8 || (uintptr_t)q8 % 8) return fail("ln_modulate_fp8: e4m3 rows must be 8-byte aligned");
   const int64_t rows = (int64_t)rows_per_batch * batch;
   if (rows == 0) return 0;
@@ -571,7 +577,9 @@ int rmsnorm_rope(void* buf, int64_t ld, int64_t bstride, int q_off, int k_off, i
 
 int sched_step(bool amo, const void* v, void* x, void* xin, int64_t ldxin, int C, int64_t rows, const float* coef,
                const int* step_ptr, int step, const float* noise, hipStream_t st) {
-  if (C % 8) return fail("sched_step: C must be a multiple of 8");
+  if (C <= 0 || C % 8) return fail("sched_step: C must be a positive multiple of 8");
+  if (rows < 0) return fail("sched_step: negative row count");
+  if (xin && (ldxin % 8 || ldxin < C)) return fail("sched_step: ldxin must be a multiple of 8 and >= C");   // 16-byte stores into xin rows
   const int64_t nch = rows * C / 8;
   if (nch == 0) return 0;
   dim3 grid((unsigned)((nch + 255) / 256));
@@ -587,6 +595,7 @@ int sched_step(bool amo, const void* v, void* x, void* xin, int64_t ldxin, int C
 }
 
 int timestep_embedding(const float* t, void* out, int n, hipStream_t st) {
+  if (n < 0) return fail("timestep_embedding: negative n");
   if (n == 0) return 0;
   timestep_embedding_kernel<<<n, 128, 0, st>>>(t, (bf16_t*)out, n);
   return check_launch("timestep_embedding");
@@ -639,7 +648,10 @@ int blend_edge(const void* a, int64_t a_bs, int64_t a_ts, int64_t a_us, void* b,
 }
 int groupnorm_silu_nhwc(const void* x, void* out, const void* gamma, const void* beta, float* ws, int B, int64_t HW,
                         int C, int groups, float eps, bool silu, hipStream_t st) {
+  if (C <= 0 || groups <= 0) return fail("groupnorm: C and groups must be positive");    // before C % groups
   if (C % 8 || groups > 64 || C % groups || (C / groups) % 4 || 256 % (C / 8)) return fail("groupnorm: unsupported C / groups");
+  if (B < 0 || HW < 0 || B > 65535) return fail("groupnorm: B must be in [0, 65535] and HW >= 0");
+  if (B == 0 || HW == 0) return 0;
   const int nchunk = (int)((HW + GN_CHUNK_PIX - 1) / GN_CHUNK_PIX);
   float* part = ws;                                   // [B, nchunk, groups, 2]
   float* stat = ws + (int64_t)B * nchunk * groups * 2; // [B, groups, 2]

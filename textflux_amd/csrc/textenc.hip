@@ -220,7 +220,8 @@ int rmsnorm(const void* x, int x_dtype, int64_t ldx, const void* w, void* out, i
 }
 
 int gather_rows(const void* table, const int64_t* ids, void* out, int64_t n, int D, int64_t vocab, hipStream_t st) {
-  if (D % 8) return fail("gather_rows: D must be a multiple of 8");
+  if (D <= 0 || D % 8) return fail("gather_rows: D must be a positive multiple of 8");
+  if (vocab <= 0) return fail("gather_rows: vocab must be positive");   // the clamp to [0, vocab) would read row -1
   if (n <= 0) return 0;
   const int64_t total = n * (D / 8);
   gather_rows_kernel<<<(unsigned)((total + 255) / 256), 256, 0, st>>>((const bf16_t*)table, ids, (bf16_t*)out, n, D, vocab);

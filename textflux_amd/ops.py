@@ -240,43 +240,60 @@ def gemm_fp8(a: torch.Tensor, a_scale: torch.Tensor, w: torch.Tensor, w_scale: t
 
 
 def ln_modulate(x: torch.Tensor, shift: torch.Tensor, scale: torch.Tensor, out: Optional[torch.Tensor] = None,
-                eps: float = 1e-6) -> torch.Tensor:
-    """LayerNorm(x) * (1 + scale[b]) + shift[b];  x [B,R,D], shift/scale [B,D] (row-strided views allowed)."""
-    _chk_dev(x, shift, scale, out)
+                eps: float = 1e-6, split_row: Optional[int] = None, shift2: Optional[torch.Tensor] = None,
+                scale2: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """LayerNorm(x) * (1 + scale[b]) + shift[b];  x [B,R,D], shift/scale [B,D] (row-strided views allowed).
+    split_row: rows < split_row of every sample take (shift2, scale2) instead (tfx_ln_modulate_split: the joint [text | image] rows)."""
+    _chk_dev(x, shift, scale, out, shift2, scale2)
     assert x.dim() == 3 and x.dtype == BF16
     if out is None:
         out = torch.empty_like(x)
     xp, ldx, xbs, R, B = _rows_view(x)
     op, ldo, obs, _, _ = _rows_view(out)
     assert shift.stride(-1) == 1 and scale.stride(-1) == 1 and shift.stride(0) == scale.stride(0)
-    L.check(L.lib().tfx_ln_modulate(xp, ldx, xbs, op, ldo, obs, shift.data_ptr(), scale.data_ptr(), shift.stride(0),
-                                    R, B, x.shape[-1], eps, _stream()), "ln_modulate")
+    if split_row is None:
+        assert shift2 is None and scale2 is None
+        L.check(L.lib().tfx_ln_modulate(xp, ldx, xbs, op, ldo, obs, shift.data_ptr(), scale.data_ptr(), shift.stride(0),
+                                        R, B, x.shape[-1], eps, _stream()), "ln_modulate")
+        return out
+    for t in (shift2, scale2):
+        assert t is None or (t.stride(-1) == 1 and t.stride(0) == shift.stride(0))
+    L.check(L.lib().tfx_ln_modulate_split(xp, ldx, xbs, op, ldo, obs, shift.data_ptr(), scale.data_ptr(), _p(shift2), _p(scale2),
+                                          int(split_row), shift.stride(0), R, B, x.shape[-1], eps, _stream()), "ln_modulate_split")
     return out
 
 
 def layernorm(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, eps: float = 1e-5, out: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """nn.LayerNorm with elementwise affine over the last dim of x [.., D] bf16 (contiguous rows): one bf16 rounding."""
+    """nn.LayerNorm with elementwise affine over the last dim of x [.., D] bf16: one bf16 rounding.  x and out are contiguous, or
+    2-D row-strided views [rows, D]."""
     _chk_dev(x, gamma, beta, out)
-    assert x.dtype == BF16 and gamma.dtype == BF16 and beta.dtype == BF16 and x.is_contiguous()
+    assert x.dtype == BF16 and gamma.dtype == BF16 and beta.dtype == BF16
     D = x.shape[-1]
     assert gamma.numel() == D and beta.numel() == D
     if out is None:
-        out = torch.empty_like(x)
-    L.check(L.lib().tfx_layernorm(x.data_ptr(), D, out.data_ptr(), D, gamma.data_ptr(), beta.data_ptr(), x.numel() // D, D, eps,
+        out = torch.empty(x.shape, dtype=BF16, device=x.device)
+    assert out.dtype == BF16 and out.shape == x.shape
+    ld = [D if t.is_contiguous() else t.stride(0) for t in (x, out)]
+    assert all(t.is_contiguous() or (t.dim() == 2 and t.stride(1) == 1) for t in (x, out))
+    L.check(L.lib().tfx_layernorm(x.data_ptr(), ld[0], out.data_ptr(), ld[1], gamma.data_ptr(), beta.data_ptr(), x.numel() // D, D, eps,
                                   _stream()), "layernorm")
     return out
 
 
-def ln_modulate_fp8(x: torch.Tensor, shift: torch.Tensor, scale: torch.Tensor, eps: float = 1e-6):
-    """ln_modulate followed by quantize_rows_fp8 in one pass: returns (q uint8 [B,R,D], scale f32 [B,R])."""
-    _chk_dev(x, shift, scale)
+def ln_modulate_fp8(x: torch.Tensor, shift: torch.Tensor, scale: torch.Tensor, eps: float = 1e-6,
+                    out: Optional[torch.Tensor] = None, scale_out: Optional[torch.Tensor] = None):
+    """ln_modulate followed by quantize_rows_fp8 in one pass: returns (q uint8 [B,R,D], scale f32 [B,R]).  out / scale_out: views to
+    write them into (out row / batch strided, scale_out batch strided)."""
+    _chk_dev(x, shift, scale, out, scale_out)
     assert x.dim() == 3 and x.dtype == BF16
     xp, ldx, xbs, R, B = _rows_view(x)
     D = x.shape[-1]
-    q = torch.empty(B, R, D, dtype=torch.uint8, device=x.device)
-    qs = torch.empty(B, R, dtype=torch.float32, device=x.device)
+    q = torch.empty(B, R, D, dtype=torch.uint8, device=x.device) if out is None else out
+    qs = torch.empty(B, R, dtype=torch.float32, device=x.device) if scale_out is None else scale_out
+    assert q.dtype == torch.uint8 and q.shape == (B, R, D) and q.stride(2) == 1
+    assert qs.dtype == torch.float32 and qs.shape == (B, R) and (R == 0 or qs.stride(1) == 1)
     assert shift.stride(-1) == 1 and scale.stride(-1) == 1 and shift.stride(0) == scale.stride(0)
-    L.check(L.lib().tfx_ln_modulate_fp8(xp, ldx, xbs, q.data_ptr(), D, R * D, qs.data_ptr(), R, shift.data_ptr(),
+    L.check(L.lib().tfx_ln_modulate_fp8(xp, ldx, xbs, q.data_ptr(), q.stride(1), q.stride(0), qs.data_ptr(), qs.stride(0), shift.data_ptr(),
                                         scale.data_ptr(), shift.stride(0), R, B, D, eps, _stream()), "ln_modulate_fp8")
     return q, qs
 
@@ -1051,11 +1068,13 @@ def rmsnorm(x: torch.Tensor, w: torch.Tensor, eps: float, out: Optional[torch.Te
     return out
 
 
-def gather_rows(table: torch.Tensor, ids: torch.Tensor) -> torch.Tensor:
-    _chk_dev(table, ids)
+def gather_rows(table: torch.Tensor, ids: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    _chk_dev(table, ids, out)
     assert table.dtype == BF16 and table.is_contiguous() and ids.dtype == torch.int64
     ids = ids.contiguous().view(-1)
-    out = torch.empty(ids.numel(), table.shape[1], dtype=BF16, device=table.device)
+    if out is None:
+        out = torch.empty(ids.numel(), table.shape[1], dtype=BF16, device=table.device)
+    assert out.dtype == BF16 and out.shape == (ids.numel(), table.shape[1]) and out.is_contiguous()
     L.check(L.lib().tfx_gather_rows(table.data_ptr(), ids.data_ptr(), out.data_ptr(), ids.numel(), table.shape[1],
                                     table.shape[0], _stream()), "gather_rows")
     return out
@@ -1070,20 +1089,27 @@ def add_into_f32_(x32: torch.Tensor, y: torch.Tensor, assign: bool = False) -> t
     return x32
 
 
-def mul(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
+def _act_out(a: torch.Tensor, out: Optional[torch.Tensor]) -> torch.Tensor:
+    if out is None:
+        return torch.empty(a.shape, dtype=BF16, device=a.device)
+    assert out.dtype == BF16 and out.shape == a.shape and out.stride(1) == 1
+    return out
+
+
+def mul(a: torch.Tensor, b: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """a * b for bf16 [rows, cols] row-strided views."""
-    _chk_dev(a, b)
+    _chk_dev(a, b, out)
     assert a.dim() == 2 and a.shape == b.shape and a.stride(1) == 1 and b.stride(1) == 1 and a.dtype == BF16
-    out = torch.empty(a.shape, dtype=BF16, device=a.device)
+    out = _act_out(a, out)
     L.check(L.lib().tfx_mul_act(a.data_ptr(), a.stride(0), b.data_ptr(), b.stride(0), out.data_ptr(), out.stride(0), a.shape[0],
                                 a.shape[1], 0, _stream()), "mul")
     return out
 
 
-def quick_gelu(a: torch.Tensor) -> torch.Tensor:
-    _chk_dev(a)
+def quick_gelu(a: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    _chk_dev(a, out)
     assert a.dim() == 2 and a.stride(1) == 1 and a.dtype == BF16
-    out = torch.empty(a.shape, dtype=BF16, device=a.device)
+    out = _act_out(a, out)
     L.check(L.lib().tfx_mul_act(a.data_ptr(), a.stride(0), None, 0, out.data_ptr(), out.stride(0), a.shape[0], a.shape[1], 1,
                                 _stream()), "quick_gelu")
     return out
