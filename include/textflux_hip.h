@@ -563,6 +563,31 @@ int64_t tfx_seamless_workspace_bytes(int32_t B, int32_t H, int32_t W, int32_t C)
 int tfx_seamless_overlay_u8(const void* orig, const void* ref, const void* edit, const void* alpha, const void* covered, const void* lut,
                             void* out, void* workspace, int64_t workspace_bytes, int32_t B, int32_t H, int32_t W, int32_t C, int32_t smooth,
                             int32_t max_shift, tfx_stream stream);
+/* ---- grain match (DESIGN.md section 4 "Grain match"): a pasted edit is cleaner than the photo around it; the noise level of both is
+ *      estimated from the histogram of a high-pass residual, and the missing variance is added as hashed white grain under the blend's
+ *      alpha.  Added without a new TFX_ABI_VERSION: two new entry points, no stamped struct and no existing entry point changes.  Tensors
+ *      contiguous, batch-major, u8 unless said otherwise; B, H, W >= 1, B <= 65535, C in 1..4; integer arithmetic throughout, so the
+ *      results are exact.  Every neighbour index is clamped and every offset that can pass 2^31 is formed in 64 bits; every launch goes on
+ *      `stream`.
+ * tfx_highpass_hist_u8: img [B, H, W, C], sel [B, H, W] -> out u32 [B][C][1024].  A pixel is selected when lo <= sel <= hi.  For every
+ *      selected pixel and channel v = |16 p - sum w p'| with w = [1 2 1] x [1 2 1] over the 3 x 3 neighbourhood, its indices clamped to the
+ *      image (edge replicated), and out[b][c][min(v, 1023)] += 1.  The call zeroes out itself (4-byte aligned; no aliasing with img or
+ *      sel); nothing selected gives all zeros; each channel's bins sum to the number of selected pixels.  Workgroups count in LDS and add
+ *      their bins with integer atomics, so the result does not depend on the partition.  H W < 2^32 (the counts are 32-bit). */
+int tfx_highpass_hist_u8(const void* img, const void* sel, int32_t lo, int32_t hi, void* out, int32_t B, int32_t H, int32_t W, int32_t C,
+                         tfx_stream stream);
+/* tfx_grain_u8: img, out [B, H, W, C], alpha [B, H, W], gain i32 [B][C] and origin i32 [B][2] = (x, y) (NULL: (0, 0)) DEVICE pointers.  Per
+ *      byte, with x = origin_x + column and y = origin_y + row, the pixel's SCENE coordinates, all in uint32 wrap-around arithmetic:
+ *          mix(h): h ^= h >> 16; h *= 0x7feb352d; h ^= h >> 15; h *= 0x846ca68b; h ^= h >> 16
+ *          h = mix(mix(x * 0x9E3779B1 + y * 0x85EBCA77 + c * 0xC2B2AE3D) ^ seed)
+ *          n = (h & 255) + ((h >> 8) & 255) + ((h >> 16) & 255) + (h >> 24) - 510        in [-510, 510], standard deviation 147.8005
+ *          d = floor((n gain[b][c] alpha + 255 * 32768) / (255 * 65536))                  floor division in 64 bits
+ *          out = clamp(img + d, 0, 255)
+ *      gain is sigma / 147.8005 in Q16, in [0, 65536]: the caller refuses what lies outside (ops.grain does); the kernel clamps it into
+ *      that range.  Hence, exactly: alpha == 0 leaves the byte unchanged, gain == 0 copies, and the grain of a scene pixel does not depend
+ *      on the window that contains it.  out may be img (no other aliasing). */
+int tfx_grain_u8(const void* img, const void* alpha, const int32_t* gain, const int32_t* origin, uint32_t seed, void* out, int32_t B,
+                 int32_t H, int32_t W, int32_t C, tfx_stream stream);
 /* ---- rectified per-line edits (DESIGN.md section 4 "Rectified lines"): a slanted text line is cut as an oriented rectangle, edited
  *      upright and warped back.  Added without a new TFX_ABI_VERSION: one new entry point, no stamped struct and no existing entry point
  *      changes.  Tensors contiguous, batch-major; B, H, W, out_h, out_w >= 1, B <= 65535, C in 1..4; in, out and coverage are three

@@ -49,8 +49,9 @@ def use_overshoot_sampler(pipe):
 def run_inference(image_input, mask_input, words_input, num_steps=50, guidance_scale=30, seed=42, pipe=None, paste_back=None):
     """paste_back (not in the reference): None, or dict(dilate, feather) -- the result is then blended back into the input image under
     the dilated and feathered mask and returned at the INPUT's size (FluxFillPipeline.paste_back) instead of at the pipeline's size.
-    seamless in it (True or dict(smooth, max_shift)) is handed to that paste.
-    With per_line=True in it (batch_driver.run_items' keys: region, color_match, rectify, perspective, curve, seamless) the input is the plain scene and its mask: every text
+    seamless (True or dict(smooth, max_shift)) and grain (True or dict(ring, max_sigma, strength, min_pixels, seed)) in it are handed to
+    that paste.
+    With per_line=True in it (batch_driver.run_items' keys: region, color_match, rectify, perspective, curve, seamless, grain) the input is the plain scene and its mask: every text
     line is edited through its own region with a single-line glyph strip and pasted into the scene (textflux_amd/per_line.py)."""
     image = (Image.open(image_input) if isinstance(image_input, str) else image_input).convert("RGB")
     mask = (Image.open(mask_input) if isinstance(mask_input, str) else mask_input).convert("RGB")
@@ -71,7 +72,7 @@ def run_inference(image_input, mask_input, words_input, num_steps=50, guidance_s
                prompt=glyph.PROMPT_TEMPLATE2, prompt_2=prompt).images[0]
     if paste_back is None:
         return out
-    pasted = pipe.paste_back(image_in, out, mask_in, **{k: v for k, v in paste_back.items() if k in ("dilate", "feather", "seamless") and v is not None})
+    pasted = pipe.paste_back(image_in, out, mask_in, **{k: v for k, v in paste_back.items() if k in ("dilate", "feather", "seamless", "grain") and v is not None})
     return Image.fromarray(pasted[0].cpu().numpy())
 
 
@@ -124,6 +125,13 @@ def add_paste_back_args(ap):
                     "(implies --paste_seamless)")
     ap.add_argument("--paste_seamless_max_shift", type=int, default=None, metavar="N", help="largest correction in grey levels, 0..255, "
                     "default 32 (implies --paste_seamless)")
+    ap.add_argument("--paste_grain", action="store_true", help="give each pasted edit the noise level of the scene around it: hashed white "
+                    "grain under the blend's alpha (with --paste_back)")
+    ap.add_argument("--paste_grain_max_sigma", type=float, default=None, metavar="F", help="largest standard deviation that is added, in grey "
+                    "levels, 0..64, default 6 (implies --paste_grain)")
+    ap.add_argument("--paste_grain_strength", type=float, default=None, metavar="F", help="share of the missing noise that is added, 0..4, "
+                    "default 1 (implies --paste_grain)")
+    ap.add_argument("--paste_grain_seed", type=int, default=None, metavar="N", help="seed of the grain's hash, default 0 (implies --paste_grain)")
 
 
 RECTIFY_FLAGS = ("paste_rectify", "paste_rectify_min_angle", "paste_rectify_max_angle")
@@ -186,10 +194,26 @@ def seamless_from_args(a):
     return values or True
 
 
+GRAIN_FLAGS = ("paste_grain", "paste_grain_max_sigma", "paste_grain_strength", "paste_grain_seed")
+
+
+def grain_from_args(a):
+    """None, or the `grain` value of the paste_back dict (True, or a dict of the values that were given).  The flags are refused without
+    --paste_back."""
+    given = [f for f in GRAIN_FLAGS if getattr(a, f, None) is not None and getattr(a, f) is not False]      # a seed or a strength of 0 is given
+    if not given:
+        return None
+    if not a.paste_back:
+        raise SystemExit(f"--{given[0]} needs --paste_back")
+    values = {k: getattr(a, "paste_grain_" + k) for k in ("max_sigma", "strength", "seed") if getattr(a, "paste_grain_" + k) is not None}
+    return values or True
+
+
 def paste_back_from_args(a):
-    """None, or the paste_back dict of batch_driver.run_items / process_normal_mode.  The per-line, colour and seamless keys appear only
-    when their flags were given."""
+    """None, or the paste_back dict of batch_driver.run_items / process_normal_mode.  The per-line, colour, seamless and grain keys appear
+    only when their flags were given."""
     rectify, perspective, curve, seamless = rectify_from_args(a), perspective_from_args(a), curve_from_args(a), seamless_from_args(a)
+    grain = grain_from_args(a)
     if not a.paste_back:
         for flag in ("paste_region", "paste_per_line", "paste_color_match", "paste_color_ring"):
             if getattr(a, flag, None) not in (None, False):
@@ -210,6 +234,8 @@ def paste_back_from_args(a):
         pb["curve"] = curve
     if seamless is not None:
         pb["seamless"] = seamless
+    if grain is not None:
+        pb["grain"] = grain
     return pb
 
 

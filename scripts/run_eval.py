@@ -109,6 +109,13 @@ def build_parser(lora: bool = False):
                     "(implies --paste_seamless)")
     ap.add_argument("--paste_seamless_max_shift", type=int, default=None, metavar="N", help="largest correction in grey levels, 0..255, "
                     "default 32 (implies --paste_seamless)")
+    ap.add_argument("--paste_grain", action="store_true", help="give each pasted edit the noise level of the scene around it: hashed white "
+                    "grain under the blend's alpha (with --paste_back)")
+    ap.add_argument("--paste_grain_max_sigma", type=float, default=None, metavar="F", help="largest standard deviation that is added, in grey "
+                    "levels, 0..64, default 6 (implies --paste_grain)")
+    ap.add_argument("--paste_grain_strength", type=float, default=None, metavar="F", help="share of the missing noise that is added, 0..4, "
+                    "default 1 (implies --paste_grain)")
+    ap.add_argument("--paste_grain_seed", type=int, default=None, metavar="N", help="seed of the grain's hash, default 0 (implies --paste_grain)")
     ap.add_argument("--items", type=str, default=None, help="JSON list of {image, mask, text} instead of --json_path")
     ap.add_argument("--out", type=str, default=None, help="output folder of --items mode")
     ap.add_argument("--num_inference_steps", type=int, default=None, help=argparse.SUPPRESS)
@@ -200,6 +207,13 @@ def main(argv=None, lora: bool = False, script: str = __file__):
             raise SystemExit(f"--{seamless_given[0]} needs --paste_back")
         values = {k: getattr(a, "paste_seamless_" + k) for k in ("smooth", "max_shift") if getattr(a, "paste_seamless_" + k) is not None}
         paste_back["seamless"] = values or True
+    grain_given = [f for f in ("paste_grain", "paste_grain_max_sigma", "paste_grain_strength", "paste_grain_seed")
+                   if getattr(a, f) is not None and getattr(a, f) is not False]             # a seed or a strength of 0 is given
+    if grain_given:
+        if not a.paste_back:
+            raise SystemExit(f"--{grain_given[0]} needs --paste_back")
+        values = {k: getattr(a, "paste_grain_" + k) for k in ("max_sigma", "strength", "seed") if getattr(a, "paste_grain_" + k) is not None}
+        paste_back["grain"] = values or True
     legacy = a.items is not None
     weights = a.lora_weights_path if lora else a.weights_path
     if not legacy and not (a.json_path and a.original_images_dir and weights):

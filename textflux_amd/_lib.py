@@ -185,6 +185,8 @@ SIGNATURES = {
     "tfx_seamless_workspace_bytes": (c_int64, [c_int32, c_int32, c_int32, c_int32]),
     "tfx_seamless_overlay_u8": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_int32,
                                         c_int32, c_int32, c_int32, c_int32, c_void_p]),
+    "tfx_highpass_hist_u8": (c_int, [c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p]),
+    "tfx_grain_u8": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, C.c_uint32, c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p]),
     "tfx_warp_affine_u8": (c_int, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p]),
     "tfx_warp_perspective_u8": (c_int, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p]),
     "tfx_warp_grid_u8": (c_int, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p, c_int32, c_void_p,

@@ -76,10 +76,11 @@ def _paste_back_cfg(paste_back: Dict[str, Any]) -> Dict[str, Any]:
     and, only when the caller gave them, per_line: True (which implies a region: {} when absent) and color_match: paste_back.
     color_match_cfg's dict(ring, gain, max_shift, min_pixels), rectify: rectify.rectify_cfg's dict(min_angle, max_angle, min_aspect)
     perspective: perspective.perspective_cfg's dict(max_fit, max_taper, min_aspect, max_angle) and curve: curve.curve_cfg's
-    dict(min_bend, max_squeeze, max_turn, min_aspect, min_fill, max_angle) (all three need per_line), and seamless: paste_back.
-    seamless_cfg's dict(smooth, max_shift)."""
+    dict(min_bend, max_squeeze, max_turn, min_aspect, min_fill, max_angle) (all three need per_line), seamless: paste_back.
+    seamless_cfg's dict(smooth, max_shift) and grain: paste_back.grain_cfg's dict(ring, max_sigma, strength, min_pixels, seed)."""
     from . import paste_back as pb
-    unknown = set(paste_back) - {"dilate", "feather", "region", "per_line", "color_match", "rectify", "perspective", "curve", "seamless"}
+    unknown = set(paste_back) - {"dilate", "feather", "region", "per_line", "color_match", "rectify", "perspective", "curve", "seamless",
+                                  "grain"}
     region = paste_back.get("region")
     if region is not None:
         unknown |= {f"region.{k}" for k in set(region) - {"pad", "min_side", "max_side"}}
@@ -111,6 +112,14 @@ def _paste_back_cfg(paste_back: Dict[str, Any]) -> Dict[str, Any]:
             raise ValueError("paste_back: seamless must be None, True or a dict")
         try:
             cfg["seamless"] = pb.seamless_cfg(seamless)
+        except ValueError as e:
+            raise ValueError(f"paste_back: {e}") from None
+    grain = paste_back.get("grain")
+    if grain is not None and grain is not False:
+        if grain is not True and not isinstance(grain, dict):
+            raise ValueError("paste_back: grain must be None, True or a dict")
+        try:
+            cfg["grain"] = pb.grain_cfg(grain)
         except ValueError as e:
             raise ValueError(f"paste_back: {e}") from None
     rectify = paste_back.get("rectify")
@@ -374,6 +383,8 @@ def _paste_into_original(pipe, w: Work, cropped, cfg: Dict[str, Any]):
     kw = dict(color_match=cfg["color_match"]) if cfg.get("color_match") else {}      # passed only then: older pipelines keep working
     if cfg.get("seamless"):
         kw["seamless"] = cfg["seamless"]
+    if cfg.get("grain"):                             # the grain is anchored at scene positions: the region's own place in the scene
+        kw.update(grain=cfg["grain"], origin=(reg.x0, reg.y0))
     pasted = pipe.paste_back(oc, cropped, om, dilate=cfg["dilate"], feather=cfg["feather"], **kw)
     pasted = pasted.cpu().numpy() if isinstance(pasted, torch.Tensor) else np.asarray(pasted)
     out = w.orig_scene.copy()
@@ -504,7 +515,11 @@ def run_items(items: Sequence[Dict[str, Any]], pipe, out_dir: Optional[str], bat
     warps): the final blend of every paste adds a membrane to the edit first -- its difference to the original scene, known just outside
     the blend, interpolated across the blend's support by a pull-push pyramid, smoothed by `smooth` Jacobi sweeps (default 8) and clamped
     to +- max_shift grey levels (default 32) -- so that the edit meets the scene at the seam; with color_match the table is fitted as
-    before and the membrane removes what it leaves.  The bytes outside the grown mask stay the original's."""
+    before and the membrane removes what it leaves.  The bytes outside the grown mask stay the original's.
+    grain=True | dict(ring, max_sigma, strength, min_pixels, seed) (DESIGN.md section 4 "Grain match"; with or without the keys above):
+    after the final blend of every paste the noise level of the original scene on a ring just outside the blend and that of the pasted
+    pixels are estimated, and the missing variance -- at most max_sigma grey levels (default 6), times strength (default 1) -- is added
+    as hashed white grain under the same alpha, anchored at scene positions.  The bytes outside the grown mask stay the original's."""
     if paste_back is not None:       # refused before anything is prepared or encoded
         if mixed_pad > 0:
             raise NotImplementedError("paste_back does not serve mixed-geometry batches (mixed_pad > 0)")

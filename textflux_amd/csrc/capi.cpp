@@ -428,6 +428,16 @@ int tfx_seamless_overlay_u8(const void* orig, const void* ref, const void* edit,
   if (!orig || !ref || !edit || !alpha || !out || !workspace) return fail("tfx_seamless_overlay_u8: null pointer");
   return seamless_overlay_u8(orig, ref, edit, alpha, covered, lut, out, workspace, workspace_bytes, B, H, W, C, smooth, max_shift, S(stream));
 }
+int tfx_highpass_hist_u8(const void* img, const void* sel, int32_t lo, int32_t hi, void* out, int32_t B, int32_t H, int32_t W, int32_t C,
+                         tfx_stream stream) {
+  if (!img || !sel || !out) return fail("tfx_highpass_hist_u8: null pointer");
+  return highpass_hist_u8(img, sel, lo, hi, out, B, H, W, C, S(stream));
+}
+int tfx_grain_u8(const void* img, const void* alpha, const int32_t* gain, const int32_t* origin, uint32_t seed, void* out, int32_t B,
+                 int32_t H, int32_t W, int32_t C, tfx_stream stream) {
+  if (!img || !alpha || !gain || !out) return fail("tfx_grain_u8: null pointer");
+  return grain_u8(img, alpha, gain, origin, seed, out, B, H, W, C, S(stream));
+}
 int tfx_warp_affine_u8(const void* in, void* out, void* coverage, int32_t B, int32_t H, int32_t W, int32_t C, int32_t out_h, int32_t out_w,
                        const int64_t* m, const int16_t* taps, tfx_stream stream) {
   if (!in || !out || !m || !taps) return fail("tfx_warp_affine_u8: null pointer");

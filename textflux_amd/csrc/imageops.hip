@@ -1055,6 +1055,117 @@ int seamless_overlay_u8(const void* orig, const void* ref, const void* edit, con
   return check_launch("seamless_overlay_u8");
 }
 
+// ---- grain match (DESIGN.md section 4 "Grain match"): the histogram of a high-pass residual, from whose median the host estimates a
+// noise level, and hashed white grain added under alpha.  Integer arithmetic only: counts and bytes are exact, whatever the partition.
+constexpr int kHistBins = 1024;
+constexpr int kHistParts = 256;                      // workgroups per sample at the most; grid-stride beyond
+
+// out[b][c][min(|16 p - sum w p'|, 1023)] += 1 over the pixels of sample b with lo <= sel <= hi, w = [1 2 1] x [1 2 1] over the 3 x 3
+// neighbourhood with its indices clamped to the image.  One thread per pixel and step; the workgroup counts into its own histogram in
+// LDS (4 C KiB) and adds the bins it touched to `out` (zeroed by the caller on the same stream) with integer atomics: sums of integers,
+// so the order does not matter.
+template <int C>
+__global__ __launch_bounds__(256) void highpass_hist_kernel(const uint8_t* __restrict__ img, const uint8_t* __restrict__ sel, int lo, int hi,
+                                                            uint32_t* __restrict__ out, int H, int W) {
+  __shared__ uint32_t hist[C * kHistBins];
+  for (int k = threadIdx.x; k < C * kHistBins; k += 256) hist[k] = 0;
+  __syncthreads();
+  const int s = blockIdx.y;
+  const int64_t hw = (int64_t)H * W;
+  img += (int64_t)s * hw * C; sel += (int64_t)s * hw;
+  for (int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x; p < hw; p += (int64_t)gridDim.x * 256) {
+    const int m = sel[p];
+    if (m < lo || m > hi) continue;
+    const int y = (int)(p / W), x = (int)(p - (int64_t)y * W);
+    const int64_t r0 = (int64_t)(y > 0 ? y - 1 : 0) * W, r1 = (int64_t)y * W, r2 = (int64_t)(y < H - 1 ? y + 1 : y) * W;
+    const int x0 = x > 0 ? x - 1 : 0, x2 = x < W - 1 ? x + 1 : x;
+#pragma unroll
+    for (int c = 0; c < C; ++c) {
+      auto at = [&](int64_t row, int col) { return (int)img[(row + col) * C + c]; };
+      const int blur = at(r0, x0) + 2 * at(r0, x) + at(r0, x2) + 2 * at(r1, x0) + 4 * at(r1, x) + 2 * at(r1, x2) + at(r2, x0) + 2 * at(r2, x) + at(r2, x2);
+      int v = 16 * at(r1, x) - blur;
+      v = v < 0 ? -v : v;
+      atomicAdd(&hist[c * kHistBins + (v > kHistBins - 1 ? kHistBins - 1 : v)], 1u);
+    }
+  }
+  __syncthreads();
+  out += (int64_t)s * C * kHistBins;
+  for (int k = threadIdx.x; k < C * kHistBins; k += 256)
+    if (hist[k]) atomicAdd(&out[k], hist[k]);
+}
+
+__device__ __forceinline__ uint32_t grain_mix(uint32_t h) {
+  h ^= h >> 16; h *= 0x7feb352du; h ^= h >> 15; h *= 0x846ca68bu; h ^= h >> 16;
+  return h;
+}
+
+// out = clamp(img + d, 0, 255), d = floor((n gain[b][c] alpha + 255 * 32768) / (255 * 65536)) with n in [-510, 510] the sum of the four
+// bytes of a hash of the pixel's SCENE position (origin + its place in the window), its channel and the seed, less 510.  One thread per
+// byte; n = H W C bytes per sample.  out may be img: a thread reads the byte it writes, and no other.  A gain outside [0, 65536] is the
+// caller's to refuse; it is clamped here so that the numerator stays within the bound the floor division below relies on.
+__global__ __launch_bounds__(256) void grain_u8_kernel(const uint8_t* img, const uint8_t* __restrict__ alpha, const int32_t* __restrict__ gain,
+                                                       const int32_t* __restrict__ origin, uint32_t seed, uint8_t* out, int64_t n, int W, int C) {
+  const int s = blockIdx.y;
+  img += s * n; out += s * n; alpha += s * (n / C);
+  const uint32_t ox = origin ? (uint32_t)origin[2 * s] : 0u, oy = origin ? (uint32_t)origin[2 * s + 1] : 0u;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
+    const int64_t pix = i / C;
+    const int c = (int)(i - pix * C);
+    const int64_t row = pix / W;
+    const uint32_t x = ox + (uint32_t)(pix - row * W), y = oy + (uint32_t)row;
+    int g = gain[s * C + c];
+    g = g < 0 ? 0 : g > 65536 ? 65536 : g;
+    const uint32_t h = grain_mix(grain_mix(x * 0x9E3779B1u + y * 0x85EBCA77u + (uint32_t)c * 0xC2B2AE3Du) ^ seed);
+    const int nz = (int)((h & 255u) + ((h >> 8) & 255u) + ((h >> 16) & 255u) + (h >> 24)) - 510;
+    // floor division of a numerator that may be negative: |n gain alpha| <= 510 * 65536 * 255 = 510 den, so adding 510 den makes it
+    // positive and takes exactly 510 off the quotient
+    constexpr uint64_t den = 255ull * 65536ull;
+    const int64_t num = (int64_t)nz * g * (int)alpha[pix] + 255 * 32768;
+    const int d = (int)((uint64_t)(num + (int64_t)(510 * den)) / den) - 510;
+    const int v = (int)img[i] + d;
+    out[i] = (uint8_t)(v < 0 ? 0 : v > 255 ? 255 : v);
+  }
+}
+
+static int grain_geometry(const char* what, int B, int H, int W, int C) {
+  if (B < 1 || H < 1 || W < 1) return fail("%s: B, H, W must be at least 1", what);
+  if (C < 1 || C > 4) return fail("%s: 1..4 channels", what);
+  if (B > 65535) return fail("%s: batch %d exceeds 65535", what, B);
+  if ((int64_t)H * W * C > kMaxBytes) return fail("%s: more than 2^38 bytes per sample", what);
+  return 0;
+}
+
+int highpass_hist_u8(const void* img, const void* sel, int lo, int hi, void* out, int B, int H, int W, int C, hipStream_t st) {
+  if (grain_geometry("highpass_hist_u8", B, H, W, C)) return 1;
+  const int64_t hw = (int64_t)H * W;
+  if (hw > 0xffffffffll) return fail("highpass_hist_u8: more than 2^32 - 1 pixels per sample (the counts are 32-bit)");
+  if ((uintptr_t)out & 3) return fail("highpass_hist_u8: out must be 4-byte aligned");
+  if (out == img || out == sel) return fail("highpass_hist_u8: out may alias neither img nor sel");
+  if (hipMemsetAsync(out, 0, (size_t)B * C * kHistBins * 4, st) != hipSuccess) return fail("highpass_hist_u8: clearing out failed");
+  const int64_t want = (hw + 255) / 256;
+  const dim3 grid((unsigned)(want > kHistParts ? kHistParts : want), B);
+  const uint8_t *pi = (const uint8_t*)img, *ps = (const uint8_t*)sel;
+  switch (C) {
+    case 1: highpass_hist_kernel<1><<<grid, 256, 0, st>>>(pi, ps, lo, hi, (uint32_t*)out, H, W); break;
+    case 2: highpass_hist_kernel<2><<<grid, 256, 0, st>>>(pi, ps, lo, hi, (uint32_t*)out, H, W); break;
+    case 3: highpass_hist_kernel<3><<<grid, 256, 0, st>>>(pi, ps, lo, hi, (uint32_t*)out, H, W); break;
+    default: highpass_hist_kernel<4><<<grid, 256, 0, st>>>(pi, ps, lo, hi, (uint32_t*)out, H, W); break;
+  }
+  return check_launch("highpass_hist_u8");
+}
+
+int grain_u8(const void* img, const void* alpha, const int* gain, const int* origin, uint32_t seed, void* out, int B, int H, int W, int C,
+             hipStream_t st) {
+  if (grain_geometry("grain_u8", B, H, W, C)) return 1;
+  if (alpha == out || (const void*)gain == out || (origin && (const void*)origin == out)) return fail("grain_u8: out may alias img only");
+  if (((uintptr_t)gain | (uintptr_t)origin) & 3) return fail("grain_u8: gain and origin must be 4-byte aligned");
+  const int64_t n = (int64_t)H * W * C;
+  const int64_t want = (n + 255) / 256;
+  const dim3 grid((unsigned)(want > 4096 ? 4096 : want), B);          // grid-stride beyond, as overlay_lut_u8
+  grain_u8_kernel<<<grid, 256, 0, st>>>((const uint8_t*)img, (const uint8_t*)alpha, gain, origin, seed, (uint8_t*)out, n, W, C);
+  return check_launch("grain_u8");
+}
+
 int warp_affine_u8(const void* in, void* out, void* coverage, int B, int H, int W, int C, int out_h, int out_w, const int64_t* m,
                    const int16_t* taps, hipStream_t st) {
   if (B < 1 || H < 1 || W < 1 || out_h < 1 || out_w < 1) return fail("warp_affine_u8: B, H, W, out_h, out_w must be at least 1");

@@ -221,6 +221,12 @@ int overlay_lut_u8(const void* orig, const void* edit, const void* alpha, const 
 int64_t seamless_workspace_bytes(int B, int H, int W, int C);
 int seamless_overlay_u8(const void* orig, const void* ref, const void* edit, const void* alpha, const void* covered, const void* lut, void* out,
                         void* workspace, int64_t workspace_bytes, int B, int H, int W, int C, int smooth, int max_shift, hipStream_t st);
+// grain match: out u32 [B][C][1024] = the histogram of |16 p - [1 2 1] x [1 2 1] p| (last bin: 1023 and above) over the pixels with
+// lo <= sel <= hi (the call zeroes out), and hashed white grain of gain i32 [B][C] (Q16 of sigma / 147.8, device) added under alpha at
+// the scene position origin i32 [B][2] (device, or NULL) + the pixel's place in the window
+int highpass_hist_u8(const void* img, const void* sel, int lo, int hi, void* out, int B, int H, int W, int C, hipStream_t st);
+int grain_u8(const void* img, const void* alpha, const int* gain, const int* origin, uint32_t seed, void* out, int B, int H, int W, int C,
+             hipStream_t st);
 // rectified per-line edits: out [B, out_h, out_w, C] u8 = in [B, H, W, C] sampled at the Q16 affine image (m i64 [B][6], device) of every
 // destination pixel, 4 x 4 taps from the i16 [256][4] table (device), edge replicated; coverage [B, out_h, out_w] u8 or NULL
 int warp_affine_u8(const void* in, void* out, void* coverage, int B, int H, int W, int C, int out_h, int out_w, const int64_t* m,

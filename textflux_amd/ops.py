@@ -6,8 +6,10 @@ tensors that alias / own the outputs.  Inputs must live on a ROCm device; bf16 u
 from __future__ import annotations
 
 import ctypes as C
+import math
 from typing import Optional
 
+import numpy as np
 import torch
 
 from . import _lib as L
@@ -816,6 +818,69 @@ def seamless_overlay(orig: torch.Tensor, ref: torch.Tensor, edit: torch.Tensor, 
     L.check(L.lib().tfx_seamless_overlay_u8(orig.data_ptr(), ref.data_ptr(), edit.data_ptr(), alpha.data_ptr(), ptr(covered), ptr(lut),
                                             out.data_ptr(), ws.data_ptr(), ws.numel() * 8, B, H, W, Cc, int(smooth), int(max_shift),
                                             _stream()), "seamless_overlay")
+    return out
+
+
+HIGHPASS_BINS = 1024                     # include/textflux_hip.h: tfx_highpass_hist_u8's bins per (sample, channel)
+GRAIN_SIGMA0 = math.sqrt(4 * (256 ** 2 - 1) / 12)      # standard deviation of tfx_grain_u8's n: the sum of four uniform bytes, 147.8005
+
+
+def highpass_hist(img: torch.Tensor, sel: torch.Tensor, lo: int = 255, hi: int = 255, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """int32 [B, C, 1024]: per sample and channel the histogram of v = |16 p - sum w p'|, w = [1 2 1] x [1 2 1] over the edge-replicated
+    3 x 3 neighbourhood, over the pixels of a uint8 image [B, H, W, C] (C in 1..4) whose uint8 sel [B, H, W] lies in [lo, hi]; v of 1023
+    and above shares the last bin (tfx_highpass_hist_u8).  Exact: integer counts.  out: None (a new tensor) or an int32 [B, C, 1024]
+    tensor, which the call zeroes itself."""
+    _chk_dev(img, sel, out)
+    for t in (img, sel):
+        if t.dtype != torch.uint8 or not t.is_contiguous():
+            raise ValueError("highpass_hist: img and sel must be contiguous uint8 tensors")
+    if img.dim() != 4 or img.numel() == 0 or not 1 <= img.shape[3] <= 4 or sel.shape != img.shape[:3]:
+        raise ValueError(f"highpass_hist: img [B, H, W, C <= 4] and sel [B, H, W] must agree, got {tuple(img.shape)}, {tuple(sel.shape)}")
+    if not (0 <= int(lo) <= 255 and 0 <= int(hi) <= 255):
+        raise ValueError(f"highpass_hist: lo and hi must be in [0, 255], got {lo}, {hi}")
+    B, H, W, Cc = img.shape
+    if out is None:
+        out = torch.empty(B, Cc, HIGHPASS_BINS, dtype=torch.int32, device=img.device)
+    elif tuple(out.shape) != (B, Cc, HIGHPASS_BINS) or out.dtype != torch.int32 or not out.is_contiguous():
+        raise ValueError(f"highpass_hist: out must be a contiguous int32 [{B}, {Cc}, {HIGHPASS_BINS}] tensor")
+    L.check(L.lib().tfx_highpass_hist_u8(img.data_ptr(), sel.data_ptr(), int(lo), int(hi), out.data_ptr(), B, H, W, Cc, _stream()),
+            "highpass_hist")
+    return out
+
+
+def grain(img: torch.Tensor, alpha: torch.Tensor, gain, origin=None, seed: int = 0, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Hashed white grain added to a uint8 image [B, H, W, C] (C in 1..4) under a uint8 alpha [B, H, W] (tfx_grain_u8): per byte
+    clamp(img + floor((n gain[b, c] alpha + 255 * 32768) / (255 * 65536)), 0, 255), n in [-510, 510] a hash of the pixel's scene position,
+    channel and seed with standard deviation GRAIN_SIGMA0.  gain: integers [B, C] (a host array or a tensor) = sigma / GRAIN_SIGMA0 in
+    Q16, each in [0, 65536]; origin: None, (x, y), or integers [B, 2]: the scene position of the window's top-left pixel (taken modulo
+    2^32); seed: taken modulo 2^32.  alpha == 0 leaves a byte unchanged and gain == 0 copies.  Exact: integer arithmetic.
+    out: None (a new tensor) or `img` itself."""
+    _chk_dev(img, alpha, out)
+    for t in (img, alpha):
+        if t.dtype != torch.uint8 or not t.is_contiguous():
+            raise ValueError("grain: img and alpha must be contiguous uint8 tensors")
+    if img.dim() != 4 or img.numel() == 0 or not 1 <= img.shape[3] <= 4 or alpha.shape != img.shape[:3]:
+        raise ValueError(f"grain: img [B, H, W, C <= 4] and alpha [B, H, W] must agree, got {tuple(img.shape)}, {tuple(alpha.shape)}")
+    B, H, W, Cc = img.shape
+    g = np.asarray(gain.cpu() if isinstance(gain, torch.Tensor) else gain)
+    if g.shape != (B, Cc) or g.dtype.kind not in "iu":
+        raise ValueError(f"grain: gain must be integers [{B}, {Cc}], got {g.dtype} {g.shape}")
+    if g.min() < 0 or g.max() > 65536:
+        raise ValueError(f"grain: every gain must be in [0, 65536], got [{int(g.min())}, {int(g.max())}]")
+    o = None
+    if origin is not None:
+        o = np.asarray(origin.cpu() if isinstance(origin, torch.Tensor) else origin)
+        if o.dtype.kind not in "iu" or o.shape not in ((2,), (B, 2)):
+            raise ValueError(f"grain: origin must be integers (x, y) or [{B}, 2], got {o.dtype} {o.shape}")
+        o = np.broadcast_to(o.astype(np.int64), (B, 2))
+        o = torch.from_numpy((((o + 2 ** 31) % 2 ** 32) - 2 ** 31).astype(np.int32)).to(img.device)
+    if out is None:
+        out = torch.empty_like(img)
+    elif out.shape != img.shape or out.dtype != torch.uint8 or not out.is_contiguous():
+        raise ValueError("grain: out must be a contiguous uint8 tensor of img's shape")
+    gd = torch.from_numpy(np.ascontiguousarray(g.astype(np.int32))).to(img.device)
+    L.check(L.lib().tfx_grain_u8(img.data_ptr(), alpha.data_ptr(), gd.data_ptr(), _p(o), int(seed) % 2 ** 32, out.data_ptr(), B, H, W, Cc,
+                                 _stream()), "grain")
     return out
 
 

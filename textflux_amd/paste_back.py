@@ -23,6 +23,13 @@ look-up table, the least-squares line from the edit's colours to the original's 
 Seamless paste (opt-in, paste(seamless=...); DESIGN.md section 4 "Seamless paste"): the final blend becomes ops.seamless_overlay, which
 first adds a membrane to the (table-mapped) edit: the difference to the scene, known just outside the blend, interpolated across alpha's
 support by a pull-push pyramid, so that the edit meets the scene at the seam and keeps its own gradients inside.
+
+Grain match (opt-in, paste(grain=...); DESIGN.md section 4 "Grain match"): after the final blend the pasted pixels get the scene's noise level:
+
+    hist  = histogram of |16 p - [1 2 1] x [1 2 1] p|                      ops.highpass_hist (exact integer counts)
+    sigma = 1.4826 / sqrt(164) * lower median of hist                      host: on the ring for the scene, where alpha == 255 for the edit
+    gain  = min(strength sqrt(sigma_scene^2 - sigma_edit^2), max_sigma)    host, in Q16 of the hash's own standard deviation
+    out   = clamp(result + grain(scene position, channel, seed) gain alpha)  ops.grain
 """
 from __future__ import annotations
 
@@ -150,6 +157,76 @@ def seamless_cfg(seamless) -> dict:
     return dict(smooth=smooth, max_shift=max_shift)
 
 
+# Grain match (DESIGN.md section 4 "Grain match"): the largest standard deviation that is ever added, in grey levels, and the share of the
+# missing noise that is.  The ring and the fewest pixels an estimate is trusted with are colour matching's.  A starting point, not a tuned
+# value and no quality claim.
+GRAIN_MAX_SIGMA, GRAIN_STRENGTH = 6.0, 1.0
+# Grey levels of noise per histogram bin: a Gaussian's sigma is 1.4826 times the median of its absolute value (the MAD estimate), and the
+# filter 16 delta - [1 2 1] x [1 2 1] turns white noise of sigma s into noise of sigma s sqrt(164) (its L2 norm: 12^2 + 4 2^2 + 4 1^2 = 164).
+GRAIN_K = 1.4826 / math.sqrt(164.0)
+
+
+def grain_cfg(grain) -> dict:
+    """paste's grain argument (True or a dict of ring, max_sigma, strength, min_pixels, seed) with its defaults filled in and checked."""
+    if grain is not True and not isinstance(grain, dict):
+        raise ValueError("grain: must be True or a dict")
+    gr = {} if grain is True else dict(grain)
+    unknown = set(gr) - {"ring", "max_sigma", "strength", "min_pixels", "seed"}
+    if unknown:
+        raise ValueError(f"grain: unknown keys {sorted(unknown)}")
+    ring = RING if gr.get("ring") is None else int(gr["ring"])
+    max_sigma = GRAIN_MAX_SIGMA if gr.get("max_sigma") is None else float(gr["max_sigma"])
+    strength = GRAIN_STRENGTH if gr.get("strength") is None else float(gr["strength"])
+    min_pixels = MIN_PIXELS if gr.get("min_pixels") is None else int(gr["min_pixels"])
+    seed = 0 if gr.get("seed") is None else int(gr["seed"])
+    if not 1 <= ring <= 255:
+        raise ValueError("grain: ring must be in [1, 255]")
+    if not 0.0 <= max_sigma <= 64.0:                 # also refuses NaN
+        raise ValueError("grain: max_sigma must be in [0, 64]")
+    if not 0.0 <= strength <= 4.0:
+        raise ValueError("grain: strength must be in [0, 4]")
+    if min_pixels < 1 or not 0 <= seed < 2 ** 32:
+        raise ValueError("grain: min_pixels must be at least 1 and seed in [0, 2^32)")
+    return dict(ring=ring, max_sigma=max_sigma, strength=strength, min_pixels=min_pixels, seed=seed)
+
+
+def _hist(hist) -> np.ndarray:
+    h = hist.cpu().numpy() if isinstance(hist, torch.Tensor) else np.asarray(hist)
+    if h.ndim != 3 or h.shape[2] != ops.HIGHPASS_BINS:
+        raise ValueError(f"noise_sigma: the histogram must be [B, C, {ops.HIGHPASS_BINS}], got {h.shape}")
+    return h.astype(np.int64)
+
+
+def noise_sigma(hist) -> np.ndarray:
+    """hist int [B, C, 1024] (ops.highpass_hist) -> float64 [B, C], the noise level in grey levels: GRAIN_K m with m the lower median of the
+    residual's magnitude, the smallest bin whose cumulative count reaches (n + 1) // 2 (0 for an empty histogram).  Edges and glyph
+    strokes are outliers of the magnitude; the median ignores them while they cover less than half of the counted pixels."""
+    h = _hist(hist)
+    cum = np.cumsum(h, axis=2)
+    target = (cum[:, :, -1] + 1) // 2
+    return GRAIN_K * (cum < target[:, :, None]).sum(axis=2).astype(np.float64)
+
+
+def grain_levels(hist_scene, hist_edit, cfg=True) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """(sigma_scene, sigma_edit, sigma_add), float64 [B, C] each, of the two histograms under grain_cfg(cfg): noise_sigma of both and the
+    standard deviation of the grain that is added, min(strength sqrt(sigma_scene^2 - sigma_edit^2), max_sigma); 0 where either histogram
+    counts fewer than min_pixels pixels or the edit is already at least as noisy as the scene (nothing is denoised)."""
+    cfg = grain_cfg(cfg)
+    hs, he = _hist(hist_scene), _hist(hist_edit)
+    if hs.shape != he.shape:
+        raise ValueError(f"grain_levels: the histograms must agree, got {hs.shape} and {he.shape}")
+    ss, se = noise_sigma(hs), noise_sigma(he)
+    add = np.minimum(cfg["strength"] * np.sqrt(np.maximum(ss * ss - se * se, 0.0)), cfg["max_sigma"])
+    trusted = (hs.sum(axis=2) >= cfg["min_pixels"]) & (he.sum(axis=2) >= cfg["min_pixels"]) & (ss > se)
+    return ss, se, np.where(trusted, add, 0.0)
+
+
+def grain_gains(hist_scene, hist_edit, cfg=True) -> np.ndarray:
+    """int32 [B, C]: ops.grain's gain for grain_levels' sigma_add, floor(sigma_add / ops.GRAIN_SIGMA0 * 65536 + 0.5) in float64."""
+    add = grain_levels(hist_scene, hist_edit, cfg)[2]
+    return np.floor(add / ops.GRAIN_SIGMA0 * 65536.0 + 0.5).astype(np.int32)
+
+
 def ring_mask(alpha: torch.Tensor, ring: int = RING) -> torch.Tensor:
     """uint8 [B, H, W] blend weight -> 255 on the pixels within `ring` (square window) of alpha's support that are not in it, else 0:
     support = 255 where alpha > 0, ring = mask_dilate(support, ring) with the support's own pixels cleared.  These pixels lie just
@@ -190,7 +267,8 @@ def fit_luts(moments, gain: Tuple[float, float] = GAIN, max_shift: int = MAX_SHI
 
 
 def paste(original: torch.Tensor, edited: torch.Tensor, mask_grey: torch.Tensor, dilate: int = DILATE, feather: int = FEATHER,
-          color_match=None, color_ref: Optional[torch.Tensor] = None, rect=None, origin: Tuple[int, int] = (0, 0), seamless=None) -> torch.Tensor:
+          color_match=None, color_ref: Optional[torch.Tensor] = None, rect=None, origin: Tuple[int, int] = (0, 0), seamless=None,
+          grain=None) -> torch.Tensor:
     """original uint8 [B, H, W, 3], edited uint8 [B, h, w, 3], mask_grey uint8 [B, H, W], all on the device -> [B, H, W, 3]: the edit,
     resampled to (H, W) when its size differs (ops.resample_u8: Pillow's bicubic), blended over the original under alpha_mask computed at
     the ORIGINAL resolution.  Outside the mask dilated by dilate + 3 feather the result is the original byte for byte; with
@@ -210,14 +288,21 @@ def paste(original: torch.Tensor, edited: torch.Tensor, mask_grey: torch.Tensor,
     instead: the difference between color_ref (None: `original`) and the edit -- after the table, when color_match is set too -- is
     taken on the pixels with alpha == 0 (that the warp covered, when there was one), interpolated across alpha's support and added to
     the edit before the blend.  The alpha is the same, so the bytes outside the grown mask are still the original's.  color_ref may then
-    be given without color_match.  Without the key the calls are those above, unchanged."""
+    be given without color_match.  Without the key the calls are those above, unchanged.
+    grain: None, or True / dict(ring, max_sigma, strength, min_pixels, seed) (DESIGN.md section 4 "Grain match"): after the final blend
+    above, the noise level of color_ref (None: `original`) on the ring just outside the blend (cut to what the warp covered) and that of
+    the result where alpha == 255 are estimated (ops.highpass_hist, noise_sigma) and the missing variance is added as hashed white grain
+    under alpha (grain_gains, ops.grain), anchored at the scene position `origin` + the pixel's place in the window.  The alpha is the
+    same, so the bytes outside the grown mask are still the original's.  color_ref may then be given without color_match.  Without the
+    key the calls are those above, unchanged."""
     if original.dtype != torch.uint8 or original.dim() != 4 or edited.dtype != torch.uint8 or edited.dim() != 4:
         raise ValueError("paste: original and edited must be uint8 [B, H, W, C]")
     if edited.shape[0] != original.shape[0] or edited.shape[3] != original.shape[3] or mask_grey.shape != original.shape[:3]:
         raise ValueError(f"paste: original {tuple(original.shape)}, edited {tuple(edited.shape)} and mask {tuple(mask_grey.shape)} do not agree")
-    if color_match is None and seamless is None and color_ref is not None:
+    if color_match is None and seamless is None and grain is None and color_ref is not None:
         raise ValueError("paste: color_ref needs color_match")
     sm = None if seamless is None else seamless_cfg(seamless)
+    gr = None if grain is None else grain_cfg(grain)
     original, edited = original.contiguous(), edited.contiguous()
     covered = None
     if rect is not None:
@@ -234,22 +319,36 @@ def paste(original: torch.Tensor, edited: torch.Tensor, mask_grey: torch.Tensor,
     elif edited.shape[1:3] != original.shape[1:3]:
         edited = ops.resample_u8(edited, (original.shape[1], original.shape[2]))
     alpha = alpha_mask(mask_grey.contiguous(), dilate, feather)
-    if color_match is None and sm is None:
+    if color_match is None and sm is None and gr is None:
         return ops.overlay(original, edited, alpha)
     cm = None if color_match is None else color_match_cfg(color_match)
     ref = original if color_ref is None else color_ref.contiguous()
     if ref.shape != original.shape or ref.dtype != torch.uint8:
         raise ValueError(f"paste: color_ref must be uint8 of original's shape {tuple(original.shape)}, got {ref.dtype} {tuple(ref.shape)}")
-    if cm is None:
-        return ops.seamless_overlay(original, ref, edited, alpha, covered=covered, smooth=sm["smooth"], max_shift=sm["max_shift"])
-    ring = ring_mask(alpha, cm["ring"])
-    if covered is not None:
-        ring = ring & covered
-    luts = fit_luts(ops.masked_moments(edited, ref, ring), cm["gain"], cm["max_shift"], cm["min_pixels"])
-    luts = torch.from_numpy(luts).to(original.device)
-    if sm is not None:
-        return ops.seamless_overlay(original, ref, edited, alpha, covered=covered, lut=luts, smooth=sm["smooth"], max_shift=sm["max_shift"])
-    return ops.overlay_lut(original, edited, alpha, luts)
+    rings = {}
+
+    def ring_of(width):                              # colour matching and the grain match share the ring when their widths agree
+        if width not in rings:
+            rings[width] = ring_mask(alpha, width) if covered is None else ring_mask(alpha, width) & covered
+        return rings[width]
+
+    if cm is None and sm is None:
+        result = ops.overlay(original, edited, alpha)
+    elif cm is None:
+        result = ops.seamless_overlay(original, ref, edited, alpha, covered=covered, smooth=sm["smooth"], max_shift=sm["max_shift"])
+    else:
+        luts = fit_luts(ops.masked_moments(edited, ref, ring_of(cm["ring"])), cm["gain"], cm["max_shift"], cm["min_pixels"])
+        luts = torch.from_numpy(luts).to(original.device)
+        if sm is not None:
+            result = ops.seamless_overlay(original, ref, edited, alpha, covered=covered, lut=luts, smooth=sm["smooth"], max_shift=sm["max_shift"])
+        else:
+            result = ops.overlay_lut(original, edited, alpha, luts)
+    if gr is None:
+        return result
+    gains = grain_gains(ops.highpass_hist(ref, ring_of(gr["ring"]), 255, 255), ops.highpass_hist(result, alpha, 255, 255), gr)
+    if not gains.any():
+        return result                                # nothing to add: the scene is no noisier than the edit, or too few pixels to tell
+    return ops.grain(result, alpha, gains, origin, gr["seed"], out=result)
 
 
 def grey_of(mask) -> np.ndarray:

@@ -96,7 +96,9 @@ def compose_lines(pipe, lines: Sequence[Any], crops: Sequence[Any], cfg: Dict[st
     of the region: each edit was generated from the original scene, so that is what its ring shows (another line's old text inside the
     ring appears in both; what was pasted in since does not).  The two are passed only then.  With cfg["seamless"] the call gets
     seamless and, for the same reason, the same color_ref (the membrane's difference is taken against the original region); passed
-    only then.
+    only then.  With cfg["grain"] the call gets grain, origin = the region's top-left scene pixel (the grain is anchored at scene
+    positions) and the same color_ref (the scene's noise level is measured on the original region, not on grain an earlier line's paste
+    added); passed only then.
     A rectified, perspective or curved line (Work.rect: a Rect, a Quad or a Ribbon) is pasted into its window `region`, the bounding box
     of the oriented rectangle or of the upright crop's footprint cut at the image: the call
     also gets rect and origin = the window's top-left scene pixel, and the pipeline warps the upright result into the window before
@@ -114,6 +116,8 @@ def compose_lines(pipe, lines: Sequence[Any], crops: Sequence[Any], cfg: Dict[st
             kw = dict(color_match=cfg["color_match"], color_ref=np.ascontiguousarray(w.orig_scene[reg.y0:reg.y1, reg.x0:reg.x1]))
         if cfg.get("seamless"):
             kw.update(seamless=cfg["seamless"], color_ref=np.ascontiguousarray(w.orig_scene[reg.y0:reg.y1, reg.x0:reg.x1]))
+        if cfg.get("grain"):
+            kw.update(grain=cfg["grain"], origin=(reg.x0, reg.y0), color_ref=np.ascontiguousarray(w.orig_scene[reg.y0:reg.y1, reg.x0:reg.x1]))
         if w.rect is not None:
             kw.update(rect=w.rect, origin=(reg.x0, reg.y0))
         pasted = pipe.paste_back(cur, cropped, om, dilate=cfg["dilate"], feather=cfg["feather"], **kw)
