@@ -588,6 +588,32 @@ int tfx_highpass_hist_u8(const void* img, const void* sel, int32_t lo, int32_t h
  *      on the window that contains it.  out may be img (no other aliasing). */
 int tfx_grain_u8(const void* img, const void* alpha, const int32_t* gain, const int32_t* origin, uint32_t seed, void* out, int32_t B,
                  int32_t H, int32_t W, int32_t C, tfx_stream stream);
+/* ---- grain spectrum (DESIGN.md section 4 "Grain spectrum"): camera noise after demosaicing and JPEG is correlated over two or three
+ *      pixels and mostly shared by the channels; white grain is neither.  The blur and the shared part are estimated from histograms at two
+ *      neighbour distances and of the channel sum, and the grain is shaped to match.  Added without a new TFX_ABI_VERSION: two new entry
+ *      points, no stamped struct and no existing entry point changes.  Geometry, alignment and aliasing rules as in the grain match above.
+ * tfx_highpass_hist_step_u8: img [B, H, W, C], sel [B, H, W] -> out u32 [B][C + 1][1024]; step in 1..8.  For every pixel with
+ *      lo <= sel <= hi and every channel r_c = 16 p - sum w p'(x +- step, y +- step), w = [1 2 1] x [1 2 1] with the eight neighbours taken
+ *      at distance step (the a-trous form), their indices clamped to the image, and out[b][c][min(|r_c|, 1023)] += 1; row C counts the
+ *      signed residuals summed over the channels: out[b][C][min(|sum_c r_c|, 1023)] += 1.  The call zeroes out itself; nothing selected
+ *      gives all zeros; every row sums to the number of selected pixels; counted in LDS and added with integer atomics, so the result does
+ *      not depend on the partition.  With step == 1 rows 0..C-1 are tfx_highpass_hist_u8's, bit for bit. */
+int tfx_highpass_hist_step_u8(const void* img, const void* sel, int32_t lo, int32_t hi, int32_t step, void* out, int32_t B, int32_t H, int32_t W,
+                              int32_t C, tfx_stream stream);
+/* tfx_grain_shaped_u8: as tfx_grain_u8, with shape i32 [B][2] = (s, lam) a DEVICE pointer, s in [0, 64], lam in [0, 256], and gain in
+ *      [0, 2^18].  With n(x, y, c) the hash of tfx_grain_u8 and nL(x, y) = n(x, y, 255), a channel index that no image channel has, at SCENE
+ *      coordinates in uint32 wrap-around arithmetic (neighbours are never clamped to the window):
+ *          m(x, y, c) = (256 - lam) n(x, y, c) + lam nL(x, y)                                   Q8, |m| <= 130560
+ *          k = [s, 256 - 2 s, s]
+ *          f(x, y, c) = sum over dy, dx in {-1, 0, 1} of k[dy + 1] k[dx + 1] m(x + dx, y + dy, c)   Q24, 64 bits
+ *          d = floor((f gain[b][c] alpha + 255 * 2^39) / (255 * 2^40))                          floor division in 64 bits
+ *          out = clamp(img + d, 0, 255)
+ *      |f gain alpha| <= 130560 * 2^16 * 2^18 * 255 < 2^59.  The caller refuses gain, s and lam outside their ranges (ops.grain_shaped
+ *      does); the kernel clamps them into them.  Hence, exactly: (s, lam) = (0, 0) with gain <= 65536 is tfx_grain_u8 (the 2^24 cancels
+ *      in the floor division), alpha == 0 leaves the byte unchanged, gain == 0 copies, and the grain of a scene pixel does not depend on
+ *      the window that contains it, the window's border included.  out may be img (no other aliasing). */
+int tfx_grain_shaped_u8(const void* img, const void* alpha, const int32_t* gain, const int32_t* shape, const int32_t* origin, uint32_t seed,
+                        void* out, int32_t B, int32_t H, int32_t W, int32_t C, tfx_stream stream);
 /* ---- rectified per-line edits (DESIGN.md section 4 "Rectified lines"): a slanted text line is cut as an oriented rectangle, edited
  *      upright and warped back.  Added without a new TFX_ABI_VERSION: one new entry point, no stamped struct and no existing entry point
  *      changes.  Tensors contiguous, batch-major; B, H, W, out_h, out_w >= 1, B <= 65535, C in 1..4; in, out and coverage are three

@@ -132,6 +132,10 @@ def add_paste_back_args(ap):
     ap.add_argument("--paste_grain_strength", type=float, default=None, metavar="F", help="share of the missing noise that is added, 0..4, "
                     "default 1 (implies --paste_grain)")
     ap.add_argument("--paste_grain_seed", type=int, default=None, metavar="N", help="seed of the grain's hash, default 0 (implies --paste_grain)")
+    ap.add_argument("--paste_grain_spectrum", action="store_true", help="also give the grain the shape of the scene's noise: blurred over "
+                    "neighbouring pixels and shared between the channels as far as the scene's is (implies --paste_grain)")
+    ap.add_argument("--paste_grain_max_blur", type=int, default=None, metavar="N", help="largest side tap of the grain's 3-tap blur in 1/256, "
+                    "0..64, default 64 (implies --paste_grain_spectrum)")
 
 
 RECTIFY_FLAGS = ("paste_rectify", "paste_rectify_min_angle", "paste_rectify_max_angle")
@@ -194,18 +198,23 @@ def seamless_from_args(a):
     return values or True
 
 
-GRAIN_FLAGS = ("paste_grain", "paste_grain_max_sigma", "paste_grain_strength", "paste_grain_seed")
+GRAIN_FLAGS = ("paste_grain", "paste_grain_max_sigma", "paste_grain_strength", "paste_grain_seed", "paste_grain_spectrum",
+               "paste_grain_max_blur")
 
 
 def grain_from_args(a):
-    """None, or the `grain` value of the paste_back dict (True, or a dict of the values that were given).  The flags are refused without
-    --paste_back."""
+    """None, or the `grain` value of the paste_back dict (True, or a dict of the values that were given; its `spectrum` is True or
+    dict(max_blur)).  The flags are refused without --paste_back."""
     given = [f for f in GRAIN_FLAGS if getattr(a, f, None) is not None and getattr(a, f) is not False]      # a seed or a strength of 0 is given
     if not given:
         return None
     if not a.paste_back:
         raise SystemExit(f"--{given[0]} needs --paste_back")
     values = {k: getattr(a, "paste_grain_" + k) for k in ("max_sigma", "strength", "seed") if getattr(a, "paste_grain_" + k) is not None}
+    if getattr(a, "paste_grain_max_blur", None) is not None:
+        values["spectrum"] = dict(max_blur=a.paste_grain_max_blur)
+    elif getattr(a, "paste_grain_spectrum", False):
+        values["spectrum"] = True
     return values or True
 
 

@@ -116,6 +116,10 @@ def build_parser(lora: bool = False):
     ap.add_argument("--paste_grain_strength", type=float, default=None, metavar="F", help="share of the missing noise that is added, 0..4, "
                     "default 1 (implies --paste_grain)")
     ap.add_argument("--paste_grain_seed", type=int, default=None, metavar="N", help="seed of the grain's hash, default 0 (implies --paste_grain)")
+    ap.add_argument("--paste_grain_spectrum", action="store_true", help="also give the grain the shape of the scene's noise: blurred over "
+                    "neighbouring pixels and shared between the channels as far as the scene's is (implies --paste_grain)")
+    ap.add_argument("--paste_grain_max_blur", type=int, default=None, metavar="N", help="largest side tap of the grain's 3-tap blur in 1/256, "
+                    "0..64, default 64 (implies --paste_grain_spectrum)")
     ap.add_argument("--items", type=str, default=None, help="JSON list of {image, mask, text} instead of --json_path")
     ap.add_argument("--out", type=str, default=None, help="output folder of --items mode")
     ap.add_argument("--num_inference_steps", type=int, default=None, help=argparse.SUPPRESS)
@@ -207,12 +211,17 @@ def main(argv=None, lora: bool = False, script: str = __file__):
             raise SystemExit(f"--{seamless_given[0]} needs --paste_back")
         values = {k: getattr(a, "paste_seamless_" + k) for k in ("smooth", "max_shift") if getattr(a, "paste_seamless_" + k) is not None}
         paste_back["seamless"] = values or True
-    grain_given = [f for f in ("paste_grain", "paste_grain_max_sigma", "paste_grain_strength", "paste_grain_seed")
-                   if getattr(a, f) is not None and getattr(a, f) is not False]             # a seed or a strength of 0 is given
+    grain_given = [f for f in ("paste_grain", "paste_grain_max_sigma", "paste_grain_strength", "paste_grain_seed", "paste_grain_spectrum",
+                               "paste_grain_max_blur")
+                   if getattr(a, f) is not None and getattr(a, f) is not False]             # a seed, a strength or a blur of 0 is given
     if grain_given:
         if not a.paste_back:
             raise SystemExit(f"--{grain_given[0]} needs --paste_back")
         values = {k: getattr(a, "paste_grain_" + k) for k in ("max_sigma", "strength", "seed") if getattr(a, "paste_grain_" + k) is not None}
+        if a.paste_grain_max_blur is not None:
+            values["spectrum"] = dict(max_blur=a.paste_grain_max_blur)
+        elif a.paste_grain_spectrum:
+            values["spectrum"] = True
         paste_back["grain"] = values or True
     legacy = a.items is not None
     weights = a.lora_weights_path if lora else a.weights_path

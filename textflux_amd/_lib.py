@@ -187,6 +187,9 @@ SIGNATURES = {
                                         c_int32, c_int32, c_int32, c_int32, c_void_p]),
     "tfx_highpass_hist_u8": (c_int, [c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p]),
     "tfx_grain_u8": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, C.c_uint32, c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p]),
+    "tfx_highpass_hist_step_u8": (c_int, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p]),
+    "tfx_grain_shaped_u8": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, C.c_uint32, c_void_p, c_int32, c_int32, c_int32, c_int32,
+                                    c_void_p]),
     "tfx_warp_affine_u8": (c_int, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p]),
     "tfx_warp_perspective_u8": (c_int, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p]),
     "tfx_warp_grid_u8": (c_int, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p, c_int32, c_void_p,

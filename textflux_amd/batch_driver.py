@@ -77,7 +77,8 @@ def _paste_back_cfg(paste_back: Dict[str, Any]) -> Dict[str, Any]:
     color_match_cfg's dict(ring, gain, max_shift, min_pixels), rectify: rectify.rectify_cfg's dict(min_angle, max_angle, min_aspect)
     perspective: perspective.perspective_cfg's dict(max_fit, max_taper, min_aspect, max_angle) and curve: curve.curve_cfg's
     dict(min_bend, max_squeeze, max_turn, min_aspect, min_fill, max_angle) (all three need per_line), seamless: paste_back.
-    seamless_cfg's dict(smooth, max_shift) and grain: paste_back.grain_cfg's dict(ring, max_sigma, strength, min_pixels, seed)."""
+    seamless_cfg's dict(smooth, max_shift) and grain: paste_back.grain_cfg's dict(ring, max_sigma, strength, min_pixels, seed) with, only
+    when the caller gave it, spectrum: dict(max_blur, luma)."""
     from . import paste_back as pb
     unknown = set(paste_back) - {"dilate", "feather", "region", "per_line", "color_match", "rectify", "perspective", "curve", "seamless",
                                   "grain"}
@@ -519,7 +520,10 @@ def run_items(items: Sequence[Dict[str, Any]], pipe, out_dir: Optional[str], bat
     grain=True | dict(ring, max_sigma, strength, min_pixels, seed) (DESIGN.md section 4 "Grain match"; with or without the keys above):
     after the final blend of every paste the noise level of the original scene on a ring just outside the blend and that of the pasted
     pixels are estimated, and the missing variance -- at most max_sigma grey levels (default 6), times strength (default 1) -- is added
-    as hashed white grain under the same alpha, anchored at scene positions.  The bytes outside the grown mask stay the original's."""
+    as hashed white grain under the same alpha, anchored at scene positions.  The bytes outside the grown mask stay the original's.
+    With grain=dict(spectrum=True | dict(max_blur, luma), ...) (DESIGN.md section 4 "Grain spectrum") the grain is blurred over
+    neighbouring pixels (a 3-tap kernel whose side tap is at most max_blur / 256, default 64) and, with luma (default True), shared
+    between the channels, as far as the scene's own noise on the ring is."""
     if paste_back is not None:       # refused before anything is prepared or encoded
         if mixed_pad > 0:
             raise NotImplementedError("paste_back does not serve mixed-geometry batches (mixed_pad > 0)")

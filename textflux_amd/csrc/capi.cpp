@@ -438,6 +438,16 @@ int tfx_grain_u8(const void* img, const void* alpha, const int32_t* gain, const 
   if (!img || !alpha || !gain || !out) return fail("tfx_grain_u8: null pointer");
   return grain_u8(img, alpha, gain, origin, seed, out, B, H, W, C, S(stream));
 }
+int tfx_highpass_hist_step_u8(const void* img, const void* sel, int32_t lo, int32_t hi, int32_t step, void* out, int32_t B, int32_t H, int32_t W,
+                              int32_t C, tfx_stream stream) {
+  if (!img || !sel || !out) return fail("tfx_highpass_hist_step_u8: null pointer");
+  return highpass_hist_step_u8(img, sel, lo, hi, step, out, B, H, W, C, S(stream));
+}
+int tfx_grain_shaped_u8(const void* img, const void* alpha, const int32_t* gain, const int32_t* shape, const int32_t* origin, uint32_t seed,
+                        void* out, int32_t B, int32_t H, int32_t W, int32_t C, tfx_stream stream) {
+  if (!img || !alpha || !gain || !shape || !out) return fail("tfx_grain_shaped_u8: null pointer");
+  return grain_shaped_u8(img, alpha, gain, shape, origin, seed, out, B, H, W, C, S(stream));
+}
 int tfx_warp_affine_u8(const void* in, void* out, void* coverage, int32_t B, int32_t H, int32_t W, int32_t C, int32_t out_h, int32_t out_w,
                        const int64_t* m, const int16_t* taps, tfx_stream stream) {
   if (!in || !out || !m || !taps) return fail("tfx_warp_affine_u8: null pointer");

@@ -1060,15 +1060,17 @@ int seamless_overlay_u8(const void* orig, const void* ref, const void* edit, con
 constexpr int kHistBins = 1024;
 constexpr int kHistParts = 256;                      // workgroups per sample at the most; grid-stride beyond
 
-// out[b][c][min(|16 p - sum w p'|, 1023)] += 1 over the pixels of sample b with lo <= sel <= hi, w = [1 2 1] x [1 2 1] over the 3 x 3
-// neighbourhood with its indices clamped to the image.  One thread per pixel and step; the workgroup counts into its own histogram in
-// LDS (4 C KiB) and adds the bins it touched to `out` (zeroed by the caller on the same stream) with integer atomics: sums of integers,
-// so the order does not matter.
-template <int C>
+// out[b][c][min(|r_c|, 1023)] += 1 over the pixels of sample b with lo <= sel <= hi, r_c = 16 p - sum w p', w = [1 2 1] x [1 2 1] over the
+// eight neighbours at distance `step` (1: the 3 x 3 neighbourhood; more: the a-trous form) with their indices clamped to the image.
+// kSum adds row C, the histogram of min(|sum_c r_c|, 1023) over the same pixels.  One thread per pixel and step of the grid; the
+// workgroup counts into its own histogram in LDS (4 KiB per row) and adds the bins it touched to `out` (zeroed by the caller on the same
+// stream) with integer atomics: sums of integers, so the order does not matter.
+template <int C, bool kSum>
 __global__ __launch_bounds__(256) void highpass_hist_kernel(const uint8_t* __restrict__ img, const uint8_t* __restrict__ sel, int lo, int hi,
-                                                            uint32_t* __restrict__ out, int H, int W) {
-  __shared__ uint32_t hist[C * kHistBins];
-  for (int k = threadIdx.x; k < C * kHistBins; k += 256) hist[k] = 0;
+                                                            int step, uint32_t* __restrict__ out, int H, int W) {
+  constexpr int kRows = C + (kSum ? 1 : 0);
+  __shared__ uint32_t hist[kRows * kHistBins];
+  for (int k = threadIdx.x; k < kRows * kHistBins; k += 256) hist[k] = 0;
   __syncthreads();
   const int s = blockIdx.y;
   const int64_t hw = (int64_t)H * W;
@@ -1077,26 +1079,38 @@ __global__ __launch_bounds__(256) void highpass_hist_kernel(const uint8_t* __res
     const int m = sel[p];
     if (m < lo || m > hi) continue;
     const int y = (int)(p / W), x = (int)(p - (int64_t)y * W);
-    const int64_t r0 = (int64_t)(y > 0 ? y - 1 : 0) * W, r1 = (int64_t)y * W, r2 = (int64_t)(y < H - 1 ? y + 1 : y) * W;
-    const int x0 = x > 0 ? x - 1 : 0, x2 = x < W - 1 ? x + 1 : x;
+    const int64_t r0 = (int64_t)(y >= step ? y - step : 0) * W, r1 = (int64_t)y * W, r2 = (int64_t)(y < H - step ? y + step : H - 1) * W;
+    const int x0 = x >= step ? x - step : 0, x2 = x < W - step ? x + step : W - 1;
+    int sum = 0;
 #pragma unroll
     for (int c = 0; c < C; ++c) {
       auto at = [&](int64_t row, int col) { return (int)img[(row + col) * C + c]; };
       const int blur = at(r0, x0) + 2 * at(r0, x) + at(r0, x2) + 2 * at(r1, x0) + 4 * at(r1, x) + 2 * at(r1, x2) + at(r2, x0) + 2 * at(r2, x) + at(r2, x2);
       int v = 16 * at(r1, x) - blur;
+      sum += v;
       v = v < 0 ? -v : v;
       atomicAdd(&hist[c * kHistBins + (v > kHistBins - 1 ? kHistBins - 1 : v)], 1u);
     }
+    if (kSum) {
+      sum = sum < 0 ? -sum : sum;
+      atomicAdd(&hist[C * kHistBins + (sum > kHistBins - 1 ? kHistBins - 1 : sum)], 1u);
+    }
   }
   __syncthreads();
-  out += (int64_t)s * C * kHistBins;
-  for (int k = threadIdx.x; k < C * kHistBins; k += 256)
+  out += (int64_t)s * kRows * kHistBins;
+  for (int k = threadIdx.x; k < kRows * kHistBins; k += 256)
     if (hist[k]) atomicAdd(&out[k], hist[k]);
 }
 
 __device__ __forceinline__ uint32_t grain_mix(uint32_t h) {
   h ^= h >> 16; h *= 0x7feb352du; h ^= h >> 15; h *= 0x846ca68bu; h ^= h >> 16;
   return h;
+}
+
+// n in [-510, 510] of scene position (x, y), channel c and the seed (include/textflux_hip.h: tfx_grain_u8)
+__device__ __forceinline__ int grain_noise(uint32_t x, uint32_t y, uint32_t c, uint32_t seed) {
+  const uint32_t h = grain_mix(grain_mix(x * 0x9E3779B1u + y * 0x85EBCA77u + c * 0xC2B2AE3Du) ^ seed);
+  return (int)((h & 255u) + ((h >> 8) & 255u) + ((h >> 16) & 255u) + (h >> 24)) - 510;
 }
 
 // out = clamp(img + d, 0, 255), d = floor((n gain[b][c] alpha + 255 * 32768) / (255 * 65536)) with n in [-510, 510] the sum of the four
@@ -1115,8 +1129,7 @@ __global__ __launch_bounds__(256) void grain_u8_kernel(const uint8_t* img, const
     const uint32_t x = ox + (uint32_t)(pix - row * W), y = oy + (uint32_t)row;
     int g = gain[s * C + c];
     g = g < 0 ? 0 : g > 65536 ? 65536 : g;
-    const uint32_t h = grain_mix(grain_mix(x * 0x9E3779B1u + y * 0x85EBCA77u + (uint32_t)c * 0xC2B2AE3Du) ^ seed);
-    const int nz = (int)((h & 255u) + ((h >> 8) & 255u) + ((h >> 16) & 255u) + (h >> 24)) - 510;
+    const int nz = grain_noise(x, y, (uint32_t)c, seed);
     // floor division of a numerator that may be negative: |n gain alpha| <= 510 * 65536 * 255 = 510 den, so adding 510 den makes it
     // positive and takes exactly 510 off the quotient
     constexpr uint64_t den = 255ull * 65536ull;
@@ -1124,6 +1137,75 @@ __global__ __launch_bounds__(256) void grain_u8_kernel(const uint8_t* img, const
     const int d = (int)((uint64_t)(num + (int64_t)(510 * den)) / den) - 510;
     const int v = (int)img[i] + d;
     out[i] = (uint8_t)(v < 0 ? 0 : v > 255 ? 255 : v);
+  }
+}
+
+// ---- grain spectrum (DESIGN.md section 4 "Grain spectrum"): the same grain, correlated over neighbouring pixels by a 3 x 3 blur and
+// over the channels by a share of one common field.  A workgroup takes a 64 x 16 tile; its 256 threads are 64 columns by 4 rows.
+constexpr int kShapeTW = 64, kShapeTH = 16;
+constexpr int kShapeHW = kShapeTW + 2, kShapeHH = kShapeTH + 2;      // the tile with its one-pixel halo
+constexpr int kShapeParts = 2048;                    // workgroups per sample at the most (256 CUs x 8 resident); each goes on to further tiles
+
+// out = clamp(img + d, 0, 255), d = floor((f gain[b][c] alpha + 255 * 2^39) / (255 * 2^40)), f the [s, 256 - 2 s, s] x [s, 256 - 2 s, s]
+// blur of m = (256 - lam) n(x, y, c) + lam n(x, y, 255) over the SCENE positions around the pixel (uint32 wrap-around, never clamped to
+// the window: the halo is hashed, not read, so a pixel's grain does not depend on the window).  m of the tile and its halo is hashed
+// into LDS once (66 x 18 x C ints, 19 KiB at the most) and filtered from there: lanes of a wave read consecutive dwords of one row.
+// The rows pass fits 32 bits (|.| <= 256 * 130560); the columns pass and the product with gain and alpha take 64.  out may be img: a
+// thread reads the byte it writes, and no other.  gain, s and lam are clamped into [0, 2^18], [0, 64] and [0, 256], the bounds the
+// floor division relies on; the caller refuses what lies outside.
+template <int C>
+__global__ __launch_bounds__(256) void grain_shaped_kernel(const uint8_t* img, const uint8_t* __restrict__ alpha, const int32_t* __restrict__ gain,
+                                                           const int32_t* __restrict__ shape, const int32_t* __restrict__ origin, uint32_t seed,
+                                                           uint8_t* out, int H, int W, int tiles_x, int64_t tiles) {
+  __shared__ int m[C][kShapeHH * kShapeHW];
+  const int b = blockIdx.y;
+  const int64_t hw = (int64_t)H * W;
+  img += b * hw * C; out += b * hw * C; alpha += b * hw;
+  const uint32_t ox = origin ? (uint32_t)origin[2 * b] : 0u, oy = origin ? (uint32_t)origin[2 * b + 1] : 0u;
+  int s = shape[2 * b], lam = shape[2 * b + 1], g[C];
+  s = s < 0 ? 0 : s > 64 ? 64 : s;
+  lam = lam < 0 ? 0 : lam > 256 ? 256 : lam;
+#pragma unroll
+  for (int c = 0; c < C; ++c) {
+    g[c] = gain[b * C + c];
+    g[c] = g[c] < 0 ? 0 : g[c] > (1 << 18) ? (1 << 18) : g[c];
+  }
+  const int k0 = s, k1 = 256 - 2 * s;
+  const int tx = threadIdx.x & (kShapeTW - 1), ty = threadIdx.x / kShapeTW;
+  for (int64_t t = blockIdx.x; t < tiles; t += gridDim.x) {
+    const int tile_y = (int)(t / tiles_x), x0 = (int)(t - (int64_t)tile_y * tiles_x) * kShapeTW, y0 = tile_y * kShapeTH;
+    for (int k = threadIdx.x; k < kShapeHH * kShapeHW; k += 256) {
+      const int hy = k / kShapeHW, hx = k - hy * kShapeHW;
+      const uint32_t x = ox + (uint32_t)(x0 + hx - 1), y = oy + (uint32_t)(y0 + hy - 1);
+      const int shared = lam * grain_noise(x, y, 255u, seed);
+#pragma unroll
+      for (int c = 0; c < C; ++c) m[c][k] = (256 - lam) * grain_noise(x, y, (uint32_t)c, seed) + shared;
+    }
+    __syncthreads();
+    const int x = x0 + tx;
+    if (x < W) {
+      for (int r = ty; r < kShapeTH && y0 + r < H; r += 256 / kShapeTW) {
+        const int64_t pix = (int64_t)(y0 + r) * W + x;
+        const int a = alpha[pix];
+#pragma unroll
+        for (int c = 0; c < C; ++c) {
+          const int* p = &m[c][r * kShapeHW + tx];                    // the halo's row r is the scene row above the pixel's
+          const int h0 = k0 * (p[0] + p[2]) + k1 * p[1];
+          const int h1 = k0 * (p[kShapeHW] + p[kShapeHW + 2]) + k1 * p[kShapeHW + 1];
+          const int h2 = k0 * (p[2 * kShapeHW] + p[2 * kShapeHW + 2]) + k1 * p[2 * kShapeHW + 1];
+          const int64_t f = (int64_t)k0 * ((int64_t)h0 + h2) + (int64_t)k1 * h1;
+          // floor division of a numerator that may be negative: |f gain alpha| <= 130560 * 2^16 * 2^18 * 255 < 2041 den, so adding
+          // 2048 den makes it positive (and stays below 2^63) and takes exactly 2048 off the quotient; den = 255 * 2^40, and
+          // floor(floor(v / 2^40) / 255) = floor(v / den) for v >= 0, which leaves a 32-bit division
+          constexpr int64_t den = 255ll << 40;
+          const int64_t num = f * (int64_t)(g[c] * a) + (255ll << 39);
+          const int d = (int)((uint32_t)((uint64_t)(num + 2048 * den) >> 40) / 255u) - 2048;
+          const int v = (int)img[pix * C + c] + d;
+          out[pix * C + c] = (uint8_t)(v < 0 ? 0 : v > 255 ? 255 : v);
+        }
+      }
+    }
+    __syncthreads();                                                  // before the next tile's hashes replace m
   }
 }
 
@@ -1135,23 +1217,35 @@ static int grain_geometry(const char* what, int B, int H, int W, int C) {
   return 0;
 }
 
-int highpass_hist_u8(const void* img, const void* sel, int lo, int hi, void* out, int B, int H, int W, int C, hipStream_t st) {
-  if (grain_geometry("highpass_hist_u8", B, H, W, C)) return 1;
+// both histogram entry points: kSum false is tfx_highpass_hist_u8 (C rows, step 1), true tfx_highpass_hist_step_u8 (C + 1 rows)
+template <bool kSum>
+static int highpass_hist(const char* what, const void* img, const void* sel, int lo, int hi, int step, void* out, int B, int H, int W, int C,
+                         hipStream_t st) {
+  if (grain_geometry(what, B, H, W, C)) return 1;
+  if (step < 1 || step > 8) return fail("%s: step must be in 1..8, got %d", what, step);
   const int64_t hw = (int64_t)H * W;
-  if (hw > 0xffffffffll) return fail("highpass_hist_u8: more than 2^32 - 1 pixels per sample (the counts are 32-bit)");
-  if ((uintptr_t)out & 3) return fail("highpass_hist_u8: out must be 4-byte aligned");
-  if (out == img || out == sel) return fail("highpass_hist_u8: out may alias neither img nor sel");
-  if (hipMemsetAsync(out, 0, (size_t)B * C * kHistBins * 4, st) != hipSuccess) return fail("highpass_hist_u8: clearing out failed");
+  if (hw > 0xffffffffll) return fail("%s: more than 2^32 - 1 pixels per sample (the counts are 32-bit)", what);
+  if ((uintptr_t)out & 3) return fail("%s: out must be 4-byte aligned", what);
+  if (out == img || out == sel) return fail("%s: out may alias neither img nor sel", what);
+  if (hipMemsetAsync(out, 0, (size_t)B * (C + (kSum ? 1 : 0)) * kHistBins * 4, st) != hipSuccess) return fail("%s: clearing out failed", what);
   const int64_t want = (hw + 255) / 256;
   const dim3 grid((unsigned)(want > kHistParts ? kHistParts : want), B);
   const uint8_t *pi = (const uint8_t*)img, *ps = (const uint8_t*)sel;
   switch (C) {
-    case 1: highpass_hist_kernel<1><<<grid, 256, 0, st>>>(pi, ps, lo, hi, (uint32_t*)out, H, W); break;
-    case 2: highpass_hist_kernel<2><<<grid, 256, 0, st>>>(pi, ps, lo, hi, (uint32_t*)out, H, W); break;
-    case 3: highpass_hist_kernel<3><<<grid, 256, 0, st>>>(pi, ps, lo, hi, (uint32_t*)out, H, W); break;
-    default: highpass_hist_kernel<4><<<grid, 256, 0, st>>>(pi, ps, lo, hi, (uint32_t*)out, H, W); break;
+    case 1: highpass_hist_kernel<1, kSum><<<grid, 256, 0, st>>>(pi, ps, lo, hi, step, (uint32_t*)out, H, W); break;
+    case 2: highpass_hist_kernel<2, kSum><<<grid, 256, 0, st>>>(pi, ps, lo, hi, step, (uint32_t*)out, H, W); break;
+    case 3: highpass_hist_kernel<3, kSum><<<grid, 256, 0, st>>>(pi, ps, lo, hi, step, (uint32_t*)out, H, W); break;
+    default: highpass_hist_kernel<4, kSum><<<grid, 256, 0, st>>>(pi, ps, lo, hi, step, (uint32_t*)out, H, W); break;
   }
-  return check_launch("highpass_hist_u8");
+  return check_launch(what);
+}
+
+int highpass_hist_u8(const void* img, const void* sel, int lo, int hi, void* out, int B, int H, int W, int C, hipStream_t st) {
+  return highpass_hist<false>("highpass_hist_u8", img, sel, lo, hi, 1, out, B, H, W, C, st);
+}
+
+int highpass_hist_step_u8(const void* img, const void* sel, int lo, int hi, int step, void* out, int B, int H, int W, int C, hipStream_t st) {
+  return highpass_hist<true>("highpass_hist_step_u8", img, sel, lo, hi, step, out, B, H, W, C, st);
 }
 
 int grain_u8(const void* img, const void* alpha, const int* gain, const int* origin, uint32_t seed, void* out, int B, int H, int W, int C,
@@ -1164,6 +1258,25 @@ int grain_u8(const void* img, const void* alpha, const int* gain, const int* ori
   const dim3 grid((unsigned)(want > 4096 ? 4096 : want), B);          // grid-stride beyond, as overlay_lut_u8
   grain_u8_kernel<<<grid, 256, 0, st>>>((const uint8_t*)img, (const uint8_t*)alpha, gain, origin, seed, (uint8_t*)out, n, W, C);
   return check_launch("grain_u8");
+}
+
+int grain_shaped_u8(const void* img, const void* alpha, const int* gain, const int* shape, const int* origin, uint32_t seed, void* out, int B,
+                    int H, int W, int C, hipStream_t st) {
+  if (grain_geometry("grain_shaped_u8", B, H, W, C)) return 1;
+  if (alpha == out || (const void*)gain == out || (const void*)shape == out || (origin && (const void*)origin == out))
+    return fail("grain_shaped_u8: out may alias img only");
+  if (((uintptr_t)gain | (uintptr_t)shape | (uintptr_t)origin) & 3) return fail("grain_shaped_u8: gain, shape and origin must be 4-byte aligned");
+  const int tiles_x = (W + kShapeTW - 1) / kShapeTW;
+  const int64_t tiles = (int64_t)tiles_x * ((H + kShapeTH - 1) / kShapeTH);
+  const dim3 grid((unsigned)(tiles > kShapeParts ? kShapeParts : tiles), B);
+  const uint8_t *pi = (const uint8_t*)img, *pa = (const uint8_t*)alpha;
+  switch (C) {
+    case 1: grain_shaped_kernel<1><<<grid, 256, 0, st>>>(pi, pa, gain, shape, origin, seed, (uint8_t*)out, H, W, tiles_x, tiles); break;
+    case 2: grain_shaped_kernel<2><<<grid, 256, 0, st>>>(pi, pa, gain, shape, origin, seed, (uint8_t*)out, H, W, tiles_x, tiles); break;
+    case 3: grain_shaped_kernel<3><<<grid, 256, 0, st>>>(pi, pa, gain, shape, origin, seed, (uint8_t*)out, H, W, tiles_x, tiles); break;
+    default: grain_shaped_kernel<4><<<grid, 256, 0, st>>>(pi, pa, gain, shape, origin, seed, (uint8_t*)out, H, W, tiles_x, tiles); break;
+  }
+  return check_launch("grain_shaped_u8");
 }
 
 int warp_affine_u8(const void* in, void* out, void* coverage, int B, int H, int W, int C, int out_h, int out_w, const int64_t* m,

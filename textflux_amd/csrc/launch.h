@@ -227,6 +227,12 @@ int seamless_overlay_u8(const void* orig, const void* ref, const void* edit, con
 int highpass_hist_u8(const void* img, const void* sel, int lo, int hi, void* out, int B, int H, int W, int C, hipStream_t st);
 int grain_u8(const void* img, const void* alpha, const int* gain, const int* origin, uint32_t seed, void* out, int B, int H, int W, int C,
              hipStream_t st);
+// grain spectrum: the histogram with its eight neighbours at distance step in 1..8 and one more row, that of the residuals summed over
+// the channels (out u32 [B][C + 1][1024]), and the grain blurred by [s, 256 - 2 s, s] squared and mixed with a share lam / 256 of one
+// field common to the channels (shape i32 [B][2] = (s, lam), device; gain in [0, 2^18])
+int highpass_hist_step_u8(const void* img, const void* sel, int lo, int hi, int step, void* out, int B, int H, int W, int C, hipStream_t st);
+int grain_shaped_u8(const void* img, const void* alpha, const int* gain, const int* shape, const int* origin, uint32_t seed, void* out, int B,
+                    int H, int W, int C, hipStream_t st);
 // rectified per-line edits: out [B, out_h, out_w, C] u8 = in [B, H, W, C] sampled at the Q16 affine image (m i64 [B][6], device) of every
 // destination pixel, 4 x 4 taps from the i16 [256][4] table (device), edge replicated; coverage [B, out_h, out_w] u8 or NULL
 int warp_affine_u8(const void* in, void* out, void* coverage, int B, int H, int W, int C, int out_h, int out_w, const int64_t* m,

@@ -830,21 +830,43 @@ def highpass_hist(img: torch.Tensor, sel: torch.Tensor, lo: int = 255, hi: int =
     3 x 3 neighbourhood, over the pixels of a uint8 image [B, H, W, C] (C in 1..4) whose uint8 sel [B, H, W] lies in [lo, hi]; v of 1023
     and above shares the last bin (tfx_highpass_hist_u8).  Exact: integer counts.  out: None (a new tensor) or an int32 [B, C, 1024]
     tensor, which the call zeroes itself."""
+    out = _hist_args("highpass_hist", img, sel, lo, hi, 0, out)
+    B, H, W, Cc = img.shape
+    L.check(L.lib().tfx_highpass_hist_u8(img.data_ptr(), sel.data_ptr(), int(lo), int(hi), out.data_ptr(), B, H, W, Cc, _stream()),
+            "highpass_hist")
+    return out
+
+
+def highpass_hist_step(img: torch.Tensor, sel: torch.Tensor, lo: int = 255, hi: int = 255, step: int = 1,
+                       out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """int32 [B, C + 1, 1024] (tfx_highpass_hist_step_u8): rows 0..C-1 are highpass_hist's with the eight neighbours taken at distance
+    `step` in 1..8 (the a-trous form; step 1: highpass_hist itself, bit for bit), row C is the histogram of |sum over the channels of the
+    signed residuals| over the same pixels.  Exact: integer counts.  out: None (a new tensor) or an int32 [B, C + 1, 1024] tensor, which
+    the call zeroes itself."""
+    if int(step) != step or not 1 <= int(step) <= 8:
+        raise ValueError(f"highpass_hist_step: step must be an integer in 1..8, got {step}")
+    out = _hist_args("highpass_hist_step", img, sel, lo, hi, 1, out)
+    B, H, W, Cc = img.shape
+    L.check(L.lib().tfx_highpass_hist_step_u8(img.data_ptr(), sel.data_ptr(), int(lo), int(hi), int(step), out.data_ptr(), B, H, W, Cc,
+                                              _stream()), "highpass_hist_step")
+    return out
+
+
+def _hist_args(name, img, sel, lo, hi, extra_rows, out):
+    """The checks both histograms make before they launch -> out (made when None): int32 [B, C + extra_rows, 1024]."""
     _chk_dev(img, sel, out)
     for t in (img, sel):
         if t.dtype != torch.uint8 or not t.is_contiguous():
-            raise ValueError("highpass_hist: img and sel must be contiguous uint8 tensors")
+            raise ValueError(f"{name}: img and sel must be contiguous uint8 tensors")
     if img.dim() != 4 or img.numel() == 0 or not 1 <= img.shape[3] <= 4 or sel.shape != img.shape[:3]:
-        raise ValueError(f"highpass_hist: img [B, H, W, C <= 4] and sel [B, H, W] must agree, got {tuple(img.shape)}, {tuple(sel.shape)}")
+        raise ValueError(f"{name}: img [B, H, W, C <= 4] and sel [B, H, W] must agree, got {tuple(img.shape)}, {tuple(sel.shape)}")
     if not (0 <= int(lo) <= 255 and 0 <= int(hi) <= 255):
-        raise ValueError(f"highpass_hist: lo and hi must be in [0, 255], got {lo}, {hi}")
-    B, H, W, Cc = img.shape
+        raise ValueError(f"{name}: lo and hi must be in [0, 255], got {lo}, {hi}")
+    B, rows = img.shape[0], img.shape[3] + extra_rows
     if out is None:
-        out = torch.empty(B, Cc, HIGHPASS_BINS, dtype=torch.int32, device=img.device)
-    elif tuple(out.shape) != (B, Cc, HIGHPASS_BINS) or out.dtype != torch.int32 or not out.is_contiguous():
-        raise ValueError(f"highpass_hist: out must be a contiguous int32 [{B}, {Cc}, {HIGHPASS_BINS}] tensor")
-    L.check(L.lib().tfx_highpass_hist_u8(img.data_ptr(), sel.data_ptr(), int(lo), int(hi), out.data_ptr(), B, H, W, Cc, _stream()),
-            "highpass_hist")
+        out = torch.empty(B, rows, HIGHPASS_BINS, dtype=torch.int32, device=img.device)
+    elif tuple(out.shape) != (B, rows, HIGHPASS_BINS) or out.dtype != torch.int32 or not out.is_contiguous():
+        raise ValueError(f"{name}: out must be a contiguous int32 [{B}, {rows}, {HIGHPASS_BINS}] tensor")
     return out
 
 
@@ -855,33 +877,65 @@ def grain(img: torch.Tensor, alpha: torch.Tensor, gain, origin=None, seed: int =
     Q16, each in [0, 65536]; origin: None, (x, y), or integers [B, 2]: the scene position of the window's top-left pixel (taken modulo
     2^32); seed: taken modulo 2^32.  alpha == 0 leaves a byte unchanged and gain == 0 copies.  Exact: integer arithmetic.
     out: None (a new tensor) or `img` itself."""
+    g, o, out = _grain_args("grain", img, alpha, gain, 65536, origin, out)
+    B, H, W, Cc = img.shape
+    gd = torch.from_numpy(g).to(img.device)
+    L.check(L.lib().tfx_grain_u8(img.data_ptr(), alpha.data_ptr(), gd.data_ptr(), _p(o), int(seed) % 2 ** 32, out.data_ptr(), B, H, W, Cc,
+                                 _stream()), "grain")
+    return out
+
+
+GRAIN_MAX_BLUR, GRAIN_MAX_GAIN = 64, 2 ** 18      # tfx_grain_shaped_u8: the largest s, and the largest gain (blurred grain is weaker)
+
+
+def grain_shaped(img: torch.Tensor, alpha: torch.Tensor, gain, shape, origin=None, seed: int = 0,
+                 out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """grain() with the noise correlated over neighbouring pixels and over the channels (tfx_grain_shaped_u8): per byte
+    clamp(img + floor((f gain[b, c] alpha + 255 * 2^39) / (255 * 2^40)), 0, 255), f the [s, 256 - 2 s, s] x [s, 256 - 2 s, s] blur, over
+    SCENE positions, of (256 - lam) n(x, y, c) + lam n(x, y, 255).  shape: integers [B, 2] or (s, lam), s in [0, 64] and lam in [0, 256];
+    gain: as grain's, each in [0, 2^18]; origin, seed, out: as grain's.  (s, lam) = (0, 0) with gains up to 65536 is grain(), bit for
+    bit; the grain of a scene pixel does not depend on the window.  Exact: integer arithmetic."""
+    g, o, out = _grain_args("grain_shaped", img, alpha, gain, GRAIN_MAX_GAIN, origin, out)
+    B, H, W, Cc = img.shape
+    sh = np.asarray(shape.cpu() if isinstance(shape, torch.Tensor) else shape)
+    if sh.dtype.kind not in "iu" or sh.shape not in ((2,), (B, 2)):
+        raise ValueError(f"grain_shaped: shape must be integers (s, lam) or [{B}, 2], got {sh.dtype} {sh.shape}")
+    sh = np.ascontiguousarray(np.broadcast_to(sh, (B, 2)).astype(np.int64))
+    if sh.min() < 0 or sh[:, 0].max() > GRAIN_MAX_BLUR or sh[:, 1].max() > 256:
+        raise ValueError(f"grain_shaped: s must be in [0, {GRAIN_MAX_BLUR}] and lam in [0, 256], got {sh.tolist()}")
+    gd, sd = torch.from_numpy(g).to(img.device), torch.from_numpy(sh.astype(np.int32)).to(img.device)
+    L.check(L.lib().tfx_grain_shaped_u8(img.data_ptr(), alpha.data_ptr(), gd.data_ptr(), sd.data_ptr(), _p(o), int(seed) % 2 ** 32,
+                                        out.data_ptr(), B, H, W, Cc, _stream()), "grain_shaped")
+    return out
+
+
+def _grain_args(name, img, alpha, gain, max_gain, origin, out):
+    """The checks both grains make before they launch -> (gain as a contiguous int32 host array [B, C], origin as an int32 device tensor
+    [B, 2] or None, out (made when None))."""
     _chk_dev(img, alpha, out)
     for t in (img, alpha):
         if t.dtype != torch.uint8 or not t.is_contiguous():
-            raise ValueError("grain: img and alpha must be contiguous uint8 tensors")
+            raise ValueError(f"{name}: img and alpha must be contiguous uint8 tensors")
     if img.dim() != 4 or img.numel() == 0 or not 1 <= img.shape[3] <= 4 or alpha.shape != img.shape[:3]:
-        raise ValueError(f"grain: img [B, H, W, C <= 4] and alpha [B, H, W] must agree, got {tuple(img.shape)}, {tuple(alpha.shape)}")
+        raise ValueError(f"{name}: img [B, H, W, C <= 4] and alpha [B, H, W] must agree, got {tuple(img.shape)}, {tuple(alpha.shape)}")
     B, H, W, Cc = img.shape
     g = np.asarray(gain.cpu() if isinstance(gain, torch.Tensor) else gain)
     if g.shape != (B, Cc) or g.dtype.kind not in "iu":
-        raise ValueError(f"grain: gain must be integers [{B}, {Cc}], got {g.dtype} {g.shape}")
-    if g.min() < 0 or g.max() > 65536:
-        raise ValueError(f"grain: every gain must be in [0, 65536], got [{int(g.min())}, {int(g.max())}]")
+        raise ValueError(f"{name}: gain must be integers [{B}, {Cc}], got {g.dtype} {g.shape}")
+    if g.min() < 0 or g.max() > max_gain:
+        raise ValueError(f"{name}: every gain must be in [0, {max_gain}], got [{int(g.min())}, {int(g.max())}]")
     o = None
     if origin is not None:
         o = np.asarray(origin.cpu() if isinstance(origin, torch.Tensor) else origin)
         if o.dtype.kind not in "iu" or o.shape not in ((2,), (B, 2)):
-            raise ValueError(f"grain: origin must be integers (x, y) or [{B}, 2], got {o.dtype} {o.shape}")
+            raise ValueError(f"{name}: origin must be integers (x, y) or [{B}, 2], got {o.dtype} {o.shape}")
         o = np.broadcast_to(o.astype(np.int64), (B, 2))
         o = torch.from_numpy((((o + 2 ** 31) % 2 ** 32) - 2 ** 31).astype(np.int32)).to(img.device)
     if out is None:
         out = torch.empty_like(img)
     elif out.shape != img.shape or out.dtype != torch.uint8 or not out.is_contiguous():
-        raise ValueError("grain: out must be a contiguous uint8 tensor of img's shape")
-    gd = torch.from_numpy(np.ascontiguousarray(g.astype(np.int32))).to(img.device)
-    L.check(L.lib().tfx_grain_u8(img.data_ptr(), alpha.data_ptr(), gd.data_ptr(), _p(o), int(seed) % 2 ** 32, out.data_ptr(), B, H, W, Cc,
-                                 _stream()), "grain")
-    return out
+        raise ValueError(f"{name}: out must be a contiguous uint8 tensor of img's shape")
+    return np.ascontiguousarray(g.astype(np.int32)), o, out
 
 
 _WARP_TAPS = {}

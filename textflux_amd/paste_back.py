@@ -30,9 +30,18 @@ Grain match (opt-in, paste(grain=...); DESIGN.md section 4 "Grain match"): after
     sigma = 1.4826 / sqrt(164) * lower median of hist                      host: on the ring for the scene, where alpha == 255 for the edit
     gain  = min(strength sqrt(sigma_scene^2 - sigma_edit^2), max_sigma)    host, in Q16 of the hash's own standard deviation
     out   = clamp(result + grain(scene position, channel, seed) gain alpha)  ops.grain
+
+Grain spectrum (opt-in, grain=dict(spectrum=...); DESIGN.md section 4 "Grain spectrum"): the grain also gets the SHAPE of the scene's noise:
+
+    h1, h2 = the histogram with its neighbours at distance 1 and 2, and of the channel sum     ops.highpass_hist_step
+    s      = the [s, 256 - 2 s, s] blur whose model ratio is nearest to median(h2) / median(h1)   host: grain_shape
+    lam    = the share of one field common to the channels, from the channel sum's median      host: grain_shape
+    gain   = sigma_add / w(s, lam), its true deviation held below max_sigma                    host: grain_shaped_gains
+    out    = clamp(result + blurred, channel-mixed grain gain alpha)                           ops.grain_shaped
 """
 from __future__ import annotations
 
+import functools
 import math
 from typing import NamedTuple, Optional, Tuple
 
@@ -167,13 +176,29 @@ GRAIN_K = 1.4826 / math.sqrt(164.0)
 
 
 def grain_cfg(grain) -> dict:
-    """paste's grain argument (True or a dict of ring, max_sigma, strength, min_pixels, seed) with its defaults filled in and checked."""
+    """paste's grain argument (True or a dict of ring, max_sigma, strength, min_pixels, seed, spectrum) with its defaults filled in and
+    checked.  spectrum (DESIGN.md section 4 "Grain spectrum"): True or a dict of max_blur (0..64, default 64) and luma (a bool, default
+    True); the result carries the key only when the caller gave it."""
     if grain is not True and not isinstance(grain, dict):
         raise ValueError("grain: must be True or a dict")
     gr = {} if grain is True else dict(grain)
-    unknown = set(gr) - {"ring", "max_sigma", "strength", "min_pixels", "seed"}
+    unknown = set(gr) - {"ring", "max_sigma", "strength", "min_pixels", "seed", "spectrum"}
     if unknown:
         raise ValueError(f"grain: unknown keys {sorted(unknown)}")
+    spectrum = gr.pop("spectrum", None)
+    if spectrum is not None and spectrum is not False:
+        if spectrum is not True and not isinstance(spectrum, dict):
+            raise ValueError("grain: spectrum must be True or a dict")
+        sp = {} if spectrum is True else dict(spectrum)
+        if set(sp) - {"max_blur", "luma"}:
+            raise ValueError(f"grain: unknown spectrum keys {sorted(set(sp) - {'max_blur', 'luma'})}")
+        max_blur = ops.GRAIN_MAX_BLUR if sp.get("max_blur") is None else sp["max_blur"]
+        luma = True if sp.get("luma") is None else sp["luma"]
+        if isinstance(max_blur, bool) or not isinstance(max_blur, (int, np.integer)) or not 0 <= max_blur <= ops.GRAIN_MAX_BLUR:
+            raise ValueError(f"grain: spectrum max_blur must be an integer in [0, {ops.GRAIN_MAX_BLUR}]")
+        if not isinstance(luma, (bool, np.bool_)):
+            raise ValueError("grain: spectrum luma must be a bool")
+        return dict(grain_cfg(gr or True), spectrum=dict(max_blur=int(max_blur), luma=bool(luma)))
     ring = RING if gr.get("ring") is None else int(gr["ring"])
     max_sigma = GRAIN_MAX_SIGMA if gr.get("max_sigma") is None else float(gr["max_sigma"])
     strength = GRAIN_STRENGTH if gr.get("strength") is None else float(gr["strength"])
@@ -225,6 +250,91 @@ def grain_gains(hist_scene, hist_edit, cfg=True) -> np.ndarray:
     """int32 [B, C]: ops.grain's gain for grain_levels' sigma_add, floor(sigma_add / ops.GRAIN_SIGMA0 * 65536 + 0.5) in float64."""
     add = grain_levels(hist_scene, hist_edit, cfg)[2]
     return np.floor(add / ops.GRAIN_SIGMA0 * 65536.0 + 0.5).astype(np.int32)
+
+
+# Grain spectrum (DESIGN.md section 4 "Grain spectrum").  ops.grain_shaped blurs unit white noise by K = k x k / 65536, k = [s, 256 - 2 s, s],
+# whose autocorrelation is A_s(du, dv) = a(du) a(dv) with a(d) = sum_i k[i] k[i + d] / 65536.  The high-pass 16 delta - [1 2 1] x [1 2 1]
+# with its neighbours at distance m, h_m, then sees the variance V_m(s) = sum over u, v of h_m[u] h_m[v] A_s(u - v); V_1(0) = 164.
+@functools.lru_cache(maxsize=None)                   # 65 x 2 values, asked for on every paste: the device waits for the host meanwhile
+def _highpass_variance(s: int, m: int) -> float:
+    k = (s, 256 - 2 * s, s)
+    a = {d: sum(k[i] * k[i + d] for i in range(3) if 0 <= i + d < 3) / 65536.0 for d in range(-2, 3)}
+    h = {(m * dx, m * dy): -float((2 - abs(dx)) * (2 - abs(dy))) for dy in (-1, 0, 1) for dx in (-1, 0, 1)}
+    h[(0, 0)] += 16.0
+    return sum(hu * hv * a.get(ux - vx, 0.0) * a.get(uy - vy, 0.0) for (ux, uy), hu in h.items() for (vx, vy), hv in h.items())
+
+
+def grain_q_model(s: int) -> float:
+    """sqrt(V_2(s) / V_1(s)): how much larger the step-2 residual of grain blurred by s is than its step-1 residual.  1 for white noise
+    (s = 0), rising with s to 1.926 at 64."""
+    return math.sqrt(_highpass_variance(s, 2) / _highpass_variance(s, 1))
+
+
+def grain_shape_levels(s: int, lam: int) -> Tuple[float, float]:
+    """(w, t) of ops.grain_shaped driven by unit white noise: w the level the step-1 estimator (noise_sigma) reads, its white
+    equivalent, and t the true standard deviation.  (1, 1) at (0, 0)."""
+    mix = math.sqrt((256 - lam) ** 2 + lam ** 2) / 256.0
+    return math.sqrt(_highpass_variance(s, 1) / 164.0) * mix, (s * s + (256 - 2 * s) ** 2 + s * s) / 65536.0 * mix
+
+
+@functools.lru_cache(maxsize=None)
+def _shape_models(max_blur: int) -> Tuple[np.ndarray, np.ndarray]:
+    """(grain_q_model of s = 0..max_blur, the channels' correlation lam^2 / ((256 - lam)^2 + lam^2) of lam = 0..256), float64."""
+    lams = np.arange(257, dtype=np.float64)
+    return np.array([grain_q_model(s) for s in range(max_blur + 1)]), lams ** 2 / ((256.0 - lams) ** 2 + lams ** 2)
+
+
+def _median_bin(h: np.ndarray) -> np.ndarray:
+    """int [..., 1024] -> the lower median bin, as noise_sigma's."""
+    cum = np.cumsum(h, axis=-1)
+    return (cum < ((cum[..., -1] + 1) // 2)[..., None]).sum(axis=-1)
+
+
+def grain_shape(h1, h2, cfg=True) -> np.ndarray:
+    """int32 [B, 2] = (s, lam), ops.grain_shaped's shape, from the SCENE ring's histograms at steps 1 and 2 (ops.highpass_hist_step,
+    int [B, C + 1, 1024]) under grain_cfg(cfg).
+    s: rows 0..C-1 pooled over the channels, M1 and M2 their lower median bins, q = M2 / M1; the s in 0..max_blur whose grain_q_model is
+    nearest to q (ties: the smaller); 0 when q <= 1, M1 = 0 or either pooled histogram counts fewer than min_pixels C.
+    lam: with M_c the step-1 median bins of rows 0..C-1 and M_S that of row C (the channel sum),
+    rho = clamp((M_S^2 - sum M_c^2) / ((sum M_c)^2 - sum M_c^2), 0, 1), the share of the variance that the channels have in common; the
+    lam in 0..256 whose lam^2 / ((256 - lam)^2 + lam^2) is nearest to rho (ties: the smaller); 0 when C = 1, the denominator is 0 or
+    luma is False."""
+    cfg = grain_cfg(cfg)
+    sp = cfg.get("spectrum") or dict(max_blur=ops.GRAIN_MAX_BLUR, luma=True)
+    h1, h2 = _hist(h1), _hist(h2)
+    if h1.shape != h2.shape or h1.shape[1] < 2:
+        raise ValueError(f"grain_shape: the histograms must be [B, C + 1, {ops.HIGHPASS_BINS}] and agree, got {h1.shape} and {h2.shape}")
+    B, C = h1.shape[0], h1.shape[1] - 1
+    q_model, rho_model = _shape_models(sp["max_blur"])
+    pooled1, pooled2 = h1[:, :C].sum(axis=1), h2[:, :C].sum(axis=1)
+    m1, m2, mc = _median_bin(pooled1), _median_bin(pooled2), _median_bin(h1).astype(np.float64)
+    out = np.zeros((B, 2), np.int32)
+    for b in range(B):
+        trusted = min(int(pooled1[b].sum()), int(pooled2[b].sum())) >= cfg["min_pixels"] * C
+        if trusted and m1[b] > 0 and m2[b] > m1[b]:
+            out[b, 0] = int(np.argmin(np.abs(q_model - float(m2[b]) / float(m1[b]))))
+        own = float((mc[b, :C] ** 2).sum())
+        den = float(mc[b, :C].sum()) ** 2 - own
+        if C > 1 and sp["luma"] and den > 0:
+            rho = min(max((mc[b, C] ** 2 - own) / den, 0.0), 1.0)
+            out[b, 1] = int(np.argmin(np.abs(rho_model - rho)))
+    return out
+
+
+def grain_shaped_gains(hist_scene, hist_edit, shape, cfg=True) -> np.ndarray:
+    """int32 [B, C]: ops.grain_shaped's gain.  sigma_add is grain_levels' of rows 0..C-1 of the two step-1 histograms (int
+    [B, C + 1, 1024]): the missing level as the step-1 high-pass sees it.  Grain of shape (s, lam) and input level L reads as L w there
+    and has the true deviation L t (grain_shape_levels), so L = sigma_add / w, brought down to max_sigma / t where its true deviation
+    would pass max_sigma; gain = floor(L / ops.GRAIN_SIGMA0 * 65536 + 0.5), at most 2^18."""
+    cfg = grain_cfg(cfg)
+    hs, he = _hist(hist_scene), _hist(hist_edit)
+    add = grain_levels(hs[:, :-1], he[:, :-1], cfg)[2]
+    out = np.zeros(add.shape, np.int32)
+    for b, (s, lam) in enumerate(np.asarray(shape).tolist()):
+        w, t = grain_shape_levels(s, lam)
+        level = np.minimum(add[b] / w, cfg["max_sigma"] / t)
+        out[b] = np.minimum(np.floor(level / ops.GRAIN_SIGMA0 * 65536.0 + 0.5), ops.GRAIN_MAX_GAIN).astype(np.int32)
+    return out
 
 
 def ring_mask(alpha: torch.Tensor, ring: int = RING) -> torch.Tensor:
@@ -294,7 +404,11 @@ def paste(original: torch.Tensor, edited: torch.Tensor, mask_grey: torch.Tensor,
     the result where alpha == 255 are estimated (ops.highpass_hist, noise_sigma) and the missing variance is added as hashed white grain
     under alpha (grain_gains, ops.grain), anchored at the scene position `origin` + the pixel's place in the window.  The alpha is the
     same, so the bytes outside the grown mask are still the original's.  color_ref may then be given without color_match.  Without the
-    key the calls are those above, unchanged."""
+    key the calls are those above, unchanged.
+    grain=dict(spectrum=True | dict(max_blur, luma), ...) (DESIGN.md section 4 "Grain spectrum"): the three histograms become
+    ops.highpass_hist_step (the ring at steps 1 and 2, the result at step 1), grain_shape estimates the scene noise's blur and the share
+    its channels have in common, and ops.grain_shaped adds grain of that shape at grain_shaped_gains' level.  Without the sub-key the
+    grain's calls are those above, unchanged; with max_blur=0, luma=False the bytes are."""
     if original.dtype != torch.uint8 or original.dim() != 4 or edited.dtype != torch.uint8 or edited.dim() != 4:
         raise ValueError("paste: original and edited must be uint8 [B, H, W, C]")
     if edited.shape[0] != original.shape[0] or edited.shape[3] != original.shape[3] or mask_grey.shape != original.shape[:3]:
@@ -345,6 +459,14 @@ def paste(original: torch.Tensor, edited: torch.Tensor, mask_grey: torch.Tensor,
             result = ops.overlay_lut(original, edited, alpha, luts)
     if gr is None:
         return result
+    if "spectrum" in gr:
+        ring = ring_of(gr["ring"])
+        h1, h2 = ops.highpass_hist_step(ref, ring, 255, 255, 1), ops.highpass_hist_step(ref, ring, 255, 255, 2)
+        shape = grain_shape(h1, h2, gr)
+        gains = grain_shaped_gains(h1, ops.highpass_hist_step(result, alpha, 255, 255, 1), shape, gr)
+        if not gains.any():
+            return result
+        return ops.grain_shaped(result, alpha, gains, shape, origin, gr["seed"], out=result)
     gains = grain_gains(ops.highpass_hist(ref, ring_of(gr["ring"]), 255, 255), ops.highpass_hist(result, alpha, 255, 255), gr)
     if not gains.any():
         return result                                # nothing to add: the scene is no noisier than the edit, or too few pixels to tell
