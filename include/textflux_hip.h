@@ -164,7 +164,8 @@ int tfx_ln_modulate_split(const void* x, int64_t ldx, int64_t x_bstride, void* o
 /* ---- per-head RMSNorm * weight, then RoPE, in place on the q and k column ranges of a fused projection buffer
  *      [B][Ntok, ld] (heads of 128) (FluxAttnProcessor2_0, D/models/attention_processor.py:2001-2004, 2023-2037;
  *      RMSNorm D/models/normalization.py:534-549; apply_rotary_emb D/models/embeddings.py:899-918).
- *      Rows < T use w*_txt (norm_added_q/k), rows >= T use w*_img (norm_q/k).  cos/sin: fp32 [Ntok,128]. */
+ *      Rows < T use w*_txt (norm_added_q/k), rows >= T use w*_img (norm_q/k).  cos/sin: fp32 [Ntok,128].
+ *      buf, the four weights and both tables 16-byte aligned; H, Ntok, T, B >= 0 (an empty extent returns 0). */
 int tfx_rmsnorm_rope(void* buf, int64_t ld, int64_t bstride, int32_t q_off, int32_t k_off, int32_t H, int32_t Ntok,
                      int32_t T, int32_t B, const void* wq_img, const void* wk_img, const void* wq_txt,
                      const void* wk_txt, const float* cos_tab, const float* sin_tab, float eps, tfx_stream stream);
@@ -250,12 +251,13 @@ int tfx_amo_step(const void* v, void* x, void* xin, int64_t ldxin, int32_t C, in
 int tfx_timestep_embedding(const float* t, void* out /* [n,256] = cos|sin */, int32_t n, tfx_stream stream);
 int tfx_silu(const void* a, void* out, int64_t n, tfx_stream stream);
 int tfx_add(const void* a, const void* b, void* out, int64_t n, tfx_stream stream);
-/* dst[r, col0 : col0+C] = src[r, :]  (initial fill of the x_embedder input; C, col0, ld multiples of 8) */
+/* dst[r, col0 : col0+C] = src[r, :]  (initial fill of the x_embedder input; C, col0, ld multiples of 8; src, dst 16-byte aligned) */
 int tfx_scatter_cols(const void* src, void* dst, int64_t rows, int32_t C, int64_t ld, int32_t col0, tfx_stream stream);
-/* generic strided 2-D copy dst[b][r, 0:cols] = src[b][r, 0:cols]  (cols % 8 == 0) */
+/* generic strided 2-D copy dst[b][r, 0:cols] = src[b][r, 0:cols]  (cols % 8 == 0; src, dst 16-byte aligned) */
 int tfx_copy_rows(const void* src, int64_t src_ld, int64_t src_bstride, void* dst, int64_t dst_ld, int64_t dst_bstride,
                   int32_t rows, int32_t cols, int32_t batch, tfx_stream stream);
-/* device-side step cursor for single-graph replay: cur[:] = table[*step_ptr][:]; *step_ptr += 1 */
+/* device-side step cursor for single-graph replay: cur[:] = table[*step_ptr][:] (tfx_select_step; per_step_elems a non-negative
+ * multiple of 8, table and cur 16-byte aligned), *step_ptr += 1 (tfx_advance_step) */
 int tfx_select_step(const void* table, void* cur, int64_t per_step_elems, int32_t* step_ptr, tfx_stream stream);
 int tfx_advance_step(int32_t* step_ptr, tfx_stream stream);
 
@@ -691,7 +693,7 @@ int tfx_pack_mask(const void* mask, int32_t mask_dtype, void* out, int32_t B, in
 int tfx_vae_sample_pack(const void* moments, const void* eps, int32_t eps_dtype, void* out, int32_t B, int32_t h, int32_t w,
                         int32_t L, float shift, float scale, int64_t ld, int32_t col0, tfx_stream stream);
 /* latents [B, (h/2)(w/2), >= 4L] (row stride ld) -> z [B, h, w, L] NHWC bf16 = latents / scale + shift, un-patchified
- * (P:1752-1765, 2126-2127): the decoder input. */
+ * (P:1752-1765, 2126-2127): the decoder input.  ld >= 4L. */
 int tfx_unpack_latents(const void* latents, int64_t ld, void* out, int32_t B, int32_t h, int32_t w, int32_t L, float shift,
                        float scale, tfx_stream stream);
 /* x [B, H, W, Cs] NHWC bf16 (first C channels), window rows [y0, y0 + Hc) x columns [x0, x0 + Wc) -> mode 0 NCHW bf16 |
@@ -702,7 +704,8 @@ int tfx_postprocess(const void* x, void* out, int32_t B, int32_t H, int32_t W, i
 /* helpers of the VAE mid-block attention (one head of dim C over h*w tokens, AttnProcessor2_0,
  * D/models/attention_processor.py:2799-2881): out[b][c, n] = in[b][n, c]; p[r, :N] = bf16(softmax(scale * s[r, :N])) with
  * s fp32 (row stride lds) from tfx_gemm_bf16_f32 and p bf16 (row stride ldp), fp32 statistics -- what a flash kernel
- * keeps in registers, here through HBM because one head of dim 512 does not fit the 128-wide attention kernel. */
+ * keeps in registers, here through HBM because one head of dim 512 does not fit the 128-wide attention kernel.
+ * tfx_transpose: ldi >= C, ldo >= N, batch <= 65535. */
 int tfx_transpose(const void* in, int64_t ldi, int64_t in_bstride, void* out, int64_t ldo, int64_t out_bstride, int32_t N,
                   int32_t C, int32_t batch, tfx_stream stream);
 int tfx_row_softmax(const float* s, int64_t lds, void* p, int64_t ldp, int32_t rows, int32_t N, float scale, tfx_stream stream);

@@ -701,3 +701,159 @@ def lora_acc(cs: dict, mask: int, which: int = 0) -> torch.Tensor:
             acc[..., s * sc:(s + 1) * sc] += cs["T"][s].double() @ cs["Bm"][which][s * sc:(s + 1) * sc].double().T
     check_accumulators(acc, cs["bias"][which])
     return acc
+
+
+# --------------------------------------------------------------------------------------------------------- tests/test_exact_layout_gpu.py
+# rmsnorm_rope on its own: integer x (the 128 squares sum exactly in any order), four non-dyadic weights, real rotary tables.  That leaves a
+# kernel the row factor (one fp32 step of row_factor either way) and the evaluation of y_i * c + (-y_{i+1}) * s: two rounded products, or a
+# fused multiply-add with either product inside.  ROPE_SHARE is the share of q / k elements of ALL the cases below whose bits change under
+# any of these; tests/test_exact_inputs_cpu.py measures it, the GPU file compares with ulps=1 and cap = 4 * ROPE_SHARE over all cases.
+ROPE_HS = (1, 3, 5, 13, 24)         # 2H head rows over four lane groups: two empty | 2 each | 3, 3 (across q/k), 3, 1 | 7, 7, 7, 5 (a second round of six) | 12 each
+ROPE_TOKENS = ((1, 1), (2, 5), (1, 37))     # (B, Ntok): one token | a workgroup's four tokens span both samples | ten workgroups, the last with one token
+ROPE_AMP = 16
+ROPE_SHARE = 14 / 2037248
+
+
+def rope_ts(Ntok: int):
+    """Text-row counts of a case: none | the switch inside a workgroup's four tokens | all (Ntok = 1: the same as 2, run once)."""
+    return tuple(sorted({0, 2, Ntok} if Ntok > 1 else {0, 2}))
+
+
+def rope_tables(B: int, Ntok: int, per_sample: bool):
+    """(cos, sin) fp32 [Ntok, 128] (per_sample: [B, Ntok, 128], the samples' tables differ) from the reference's FluxPosEmbed on the ids
+    of an image grid: windows of the 8 x 8 latent grid's row-major (0, row, column) ids."""
+    from oracle import flux_oracle as fo
+    from oracle import pipeline_oracle as po
+    ids = po.latent_image_ids(8, 8)
+    tabs = [fo.flux_pos_embed(ids[3 + 19 * b:3 + 19 * b + Ntok]) for b in range(B if per_sample else 1)]
+    cos, sin = (torch.stack([t[i] for t in tabs]).contiguous() for i in (0, 1))
+    assert cos.dtype == torch.float32 and cos.shape[-2:] == (Ntok, 128)
+    assert not per_sample or B == 1 or not torch.equal(cos[0], cos[1])
+    return (cos, sin) if per_sample else (cos[0], sin[0])
+
+
+@functools.lru_cache(maxsize=None)
+def rope_case(H: int, B: int, Ntok: int, T: int, per_sample: bool) -> dict:
+    """x [B, Ntok, 2H, 128] integers in [-16, 16] (head rows: q heads, then k heads), the four weights (wq_img, wk_img, wq_txt, wk_txt),
+    the tables, the per-row weight w [B, Ntok, 2H, 128] the kernel is to pick (text below T, k from head row H) and the row factor r."""
+    seed = shape_seed(H, B, Ntok, T, int(per_sample))
+    x = integers((B, Ntok, 2 * H, 128), -ROPE_AMP, ROPE_AMP, seed)
+    ws = tuple((1 + 0.1 * torch.randn(128, generator=gen(seed + 1 + i))).to(BF) for i in range(4))
+    assert len({tuple(w.tolist()) for w in ws}) == 4
+    cos, sin = rope_tables(B, Ntok, per_sample)
+    ss = (x.double() ** 2).sum(-1, keepdim=True)
+    assert ss.max().item() <= 2 ** 23 and ss.min().item() > 0
+    r = row_factor(ss.float() * (1.0 / 128.0) + 1e-6)           # ss / 128 is exact, so a contracted ss * (1 / 128) + eps is the same number
+    return dict(x=x, ws=ws, cos=cos, sin=sin, r=r, w=rope_pick_weights(ws, B, Ntok, H, T))
+
+
+def rope_pick_weights(ws, B: int, Ntok: int, H: int, T: int) -> torch.Tensor:
+    """w [B, Ntok, 2H, 128] from ws = (wq_img, wk_img, wq_txt, wk_txt): rows n < T take the text pair, head rows >= H the k weight."""
+    txt = (torch.arange(Ntok) < T)[None, :, None, None]
+    is_k = (torch.arange(2 * H) >= H)[None, None, :, None]
+    img_w = torch.where(is_k, ws[1].float(), ws[0].float())
+    txt_w = torch.where(is_k, ws[3].float(), ws[2].float())
+    return torch.where(txt, txt_w, img_w).expand(B, Ntok, 2 * H, 128).to(BF)
+
+
+def _exact_sum(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
+    """a + b of fp64 tensors, asserted exact in fp64 (so that rounding it to fp32 rounds the true sum once)."""
+    s = a + b
+    assert bool(((s - a) == b).all()) and bool(((s - b) == a).all()), "the fp64 sum of the two terms must be exact"
+    return s
+
+
+def _mul_add(a, b, c, d, order: int) -> torch.Tensor:
+    """fp32 a * b + c * d of bf16-valued a, c and fp32 b, d (fp64 tensors; every product is exact in fp64).  order 0: both products
+    rounded to fp32, then added; 1: fma(a, b, fp32(c * d)); 2: fma(c, d, fp32(a * b))."""
+    p, q = a * b, c * d
+    if order == 0:
+        return p.float() + q.float()
+    if order == 1:
+        return _exact_sum(p, q.float().double()).float()
+    return _exact_sum(q, p.float().double()).float()
+
+
+def rms_rope_chain(x, w, cos, sin, r, order: int = 0) -> torch.Tensor:
+    """tfx_rmsnorm_rope on head rows x [B, Ntok, R, 128] with the per-row weight w (bf16, same shape), tables [Ntok, 128] or [B, Ntok, 128]
+    as the kernel reads them and the row factor r [B, Ntok, R, 1]: y = bf16(bf16(x * r) * w), then per pair (i, i + 1)
+    o_i = y_i * cos_i + (-y_{i+1}) * sin_i, o_{i+1} = y_{i+1} * cos_{i+1} + y_i * sin_{i+1} in fp32, rounded to bf16 once.  order: how the
+    fp32 expression is evaluated, see _mul_add (a compiler may contract either product into the add)."""
+    assert w.dtype == BF and cos.dtype == torch.float32 and r.dtype == torch.float32
+    y = ((x.float() * r).to(BF).float() * w.float()).to(BF).double()
+    c, s = (t.double()[None, :, None, :] if t.dim() == 2 else t.double()[:, :, None, :] for t in (cos, sin))
+    y0, y1 = y[..., 0::2], y[..., 1::2]
+    o0 = _mul_add(y0, c[..., 0::2], -y1, s[..., 0::2], order)
+    o1 = _mul_add(y1, c[..., 1::2], y0, s[..., 1::2], order)
+    return torch.stack([o0, o1], -1).flatten(-2).to(BF)
+
+
+def rope_cases():
+    """Every (H, B, Ntok, T, per_sample) of the GPU file (each is run in both column orders: the same arithmetic)."""
+    return [(H, B, N, T, ps) for H in ROPE_HS for B, N in ROPE_TOKENS for T in rope_ts(N) for ps in ((False, True) if B > 1 else (False,))]
+
+
+# --- timestep embedding
+TIMESTEPS = (0.0, 1e-3, 0.5, 1.0, 17.25, 999.0, 1000.0)
+
+
+def timestep_window(t: torch.Tensor):
+    """(lo, hi) bf16 [n, 256] a correct tfx_timestep_embedding row lies between, elementwise: e_j the reference's fp32 exponent (the
+    operations of oracle.flux_oracle.timestep_embedding in their order), f_j = fp32(exp64(e_j)), a = fp32(t * f_j), want = cos64(a) |
+    sin64(a), lo / hi = bf16(want -+ delta) with delta = |a| * 2^-20 + 2^-22: sixteen fp32 steps of the frequency, where a working expf,
+    the product and sinf / cosf need one or two."""
+    half = 128
+    e = -math.log(10000) * torch.arange(0, half, dtype=torch.float32) / half
+    f = torch.exp(e.double()).float()
+    a = (t.float()[:, None] * f[None, :]).double()
+    want = torch.cat([torch.cos(a), torch.sin(a)], -1)
+    delta = torch.cat([a.abs(), a.abs()], -1) * 2.0 ** -20 + 2.0 ** -22
+    return (want - delta).float().to(BF), (want + delta).float().to(BF)
+
+
+def assert_in_window(got: torch.Tensor, lo: torch.Tensor, hi: torch.Tensor, what: str) -> None:
+    got = got.detach().cpu()
+    assert got.dtype == BF and got.shape == lo.shape
+    bad = ~((got.float() >= lo.float()) & (got.float() <= hi.float()))              # a NaN is outside
+    if bad.any():
+        i, j = bad.nonzero()[0].tolist()
+        raise AssertionError(f"{what}: {int(bad.sum())} of {got.numel()} elements outside their window; first (row {i}, col {j}): got "
+                             f"{got[i, j].item()!r}, window [{lo[i, j].item()!r}, {hi[i, j].item()!r}]")
+
+
+# --- sample_pack
+SAMPLE_PACK_CASES = ((1, 2, 2, 2), (2, 6, 10, 16))                                       # (B, h, w, L)
+SAMPLE_PACK_LOGVARS = (-40.0, -30.0, 20.0, 25.0)
+
+
+def sample_pack_case(B: int, h: int, w: int, L: int) -> dict:
+    """mean, logvar bf16 [B, L, h, w] (NCHW; logvar holds the four values around the clamp and ordinary ones), eps bf16, and an fp32 eps
+    that bf16 does not hold."""
+    seed = shape_seed(B, h, w, L)
+    mean, eps = arbitrary_bf16((B, L, h, w), seed), arbitrary_bf16((B, L, h, w), seed + 1)
+    logvar = (torch.randn(B, L, h, w, generator=gen(seed + 2)) * 2.0 - 1.0).to(BF)
+    flat = logvar.view(-1)
+    flat[torch.randperm(flat.numel(), generator=gen(seed + 3))[:4]] = torch.tensor(SAMPLE_PACK_LOGVARS, dtype=BF)
+    eps32 = torch.randn(B, L, h, w, generator=gen(seed + 4))
+    assert not torch.equal(eps32.to(BF).float(), eps32)
+    return dict(mean=mean, logvar=logvar, eps=eps, eps32=eps32)
+
+
+def sample_pack_std64(logvar: torch.Tensor) -> torch.Tensor:
+    """exp64(bf16(0.5 * clamp(logvar, -30, 20))): the one transcendental of the chain (0.5 * lv is exact)."""
+    return torch.exp((0.5 * torch.clamp(logvar, -30.0, 20.0)).double())
+
+
+def sample_pack_chain(mean, std, eps, shift: float, scale: float) -> torch.Tensor:
+    """[B, S, 4L] bf16 = pack(bf16(bf16(z - shift) * scale)), z = bf16(mean + bf16(std * eps)) with torch's bf16 operators (eps None: the
+    mode, z = mean); the two scalars as the reference's device kernels apply them (dev_scalar of tests/test_imageops_gpu.py)."""
+    from oracle import pipeline_oracle as po
+    from tests.test_imageops_gpu import dev_scalar
+    assert mean.dtype == BF and (eps is None or (std.dtype == BF and eps.dtype == BF))
+    z = mean if eps is None else mean + std * eps
+    return po.pack_latents(dev_scalar(dev_scalar(z, "sub", shift), "mul", scale))
+
+
+def bf16_neighbour(t: torch.Tensor, d: int) -> torch.Tensor:
+    """The bf16 value d steps away in magnitude (positive finite t)."""
+    return (t.contiguous().view(torch.int16) + d).view(BF)

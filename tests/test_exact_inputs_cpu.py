@@ -536,3 +536,80 @@ def test_scheduler_chains_are_the_reference_steps():
     v, x, eps = X.arbitrary_bf16((37, 64), 1), X.arbitrary_bf16((37, 64), 2), torch.randn(37, 64, generator=g)
     ds = torch.tensor(-0.03125)
     assert torch.equal(X.euler_chain(v, x, -0.03125), so.euler_step(v, x, torch.tensor(1.0), torch.tensor(1.0) + ds))
+
+
+# ------------------------------------------------------------------------------------------------ tests/test_exact_layout_gpu.py
+def test_rope_share_is_the_measured_sensitivity():
+    """Every case of the GPU file: the q / k elements whose bits change when the row factor moves one fp32 step either way, or when either
+    product of the rotation is contracted into the add."""
+    n = m = 0
+    for case in X.rope_cases():
+        cs = X.rope_case(*case)
+        f = lambda r, order=0: X.rms_rope_chain(cs["x"], cs["w"], cs["cos"], cs["sin"], r, order)
+        mid, moved = _moved(f, cs["r"], 1)
+        for order in (1, 2):
+            moved |= X.mismatches(f(cs["r"], order), mid)
+        n, m = n + mid.numel(), m + int(moved.sum())
+    print(f"rmsnorm_rope: {m} of {n} elements ({m / n:.3e}) change under one fp32 step of the row factor or a contracted rotation")
+    assert m / n == X.ROPE_SHARE
+
+
+def test_rope_chain_is_the_reference_and_the_tables_are_not_dyadic():
+    """On one case: the chain is the reference's rms_norm + apply_rope to a bf16 step (the reference rounds the same points; its fp32 rsqrt and
+    rotation may differ in the last place), and most of the table is neither 0, +-1 nor +-0.5."""
+    from oracle import flux_oracle as fo
+    H, B, N, T = 5, 2, 5, 0
+    cs = X.rope_case(H, B, N, T, True)
+    want = X.rms_rope_chain(cs["x"], cs["w"], cs["cos"], cs["sin"], cs["r"])
+    assert ((cs["cos"].abs() != 1) & (cs["cos"].abs() != 0.5) & (cs["cos"] != 0)).float().mean().item() > 0.6
+    for b in range(B):
+        for k, wt in ((0, cs["ws"][0]), (1, cs["ws"][1])):
+            x = cs["x"][b, :, k * H:(k + 1) * H].to(BF).permute(1, 0, 2)[None]                        # [1, H, N, 128]
+            ref = fo.apply_rope(fo.rms_norm(x, wt), cs["cos"][b], cs["sin"][b])
+            X.assert_elementwise(want[b, :, k * H:(k + 1) * H].permute(1, 0, 2), ref[0], "chain against the oracle", ulps=1)
+
+
+def test_fault_rope_weight_of_the_other_stream_or_the_other_projection():
+    H, B, N, T = 5, 2, 5, 2
+    cs = X.rope_case(H, B, N, T, False)
+    f = lambda w: X.rms_rope_chain(cs["x"], w, cs["cos"], cs["sin"], cs["r"])
+    want = f(cs["w"])
+    flat = lambda t: t.reshape(B, N, -1)
+    msg = rejects(flat(f(X.rope_pick_weights(cs["ws"], B, N, H, T + 1))), flat(want), "text weights for an image row", ulps=1)
+    assert "row 2," in msg and "row 1," not in msg and "row 3," not in msg
+    wrong = cs["w"].clone()
+    wrong[1, 4, H - 1] = cs["w"][1, 4, H]                                                            # the last q head of one token takes the k weight
+    msg = rejects(flat(f(wrong)), flat(want), "k weight for a q row", ulps=1)
+    assert "(batch 1, row 4," in msg and "batch 0" not in msg
+
+
+def test_timestep_window_admits_the_oracle_and_rejects_a_zeroed_sine_half():
+    from oracle import flux_oracle as fo
+    t = torch.tensor(X.TIMESTEPS)
+    lo, hi = X.timestep_window(t)
+    emb = fo.timestep_embedding(t).to(BF)
+    X.assert_in_window(emb, lo, hi, "oracle")
+    assert bool((emb[0, :128] == 1).all()) and bool((emb[0, 128:] == 0).all())           # t = 0: 1 .. 1 | 0 .. 0, which the GPU file asserts on its own
+    zeroed = emb.clone()
+    zeroed[:, 128:] = 0
+    with pytest.raises(AssertionError, match=r"zeroed sines.*first \(row 1, col 128\)"):                   # t = 1e-3: sines of 1e-3 .. 1e-7
+        X.assert_in_window(zeroed, lo, hi, "zeroed sines")
+    with pytest.raises(AssertionError, match="zeroed sines"):
+        X.assert_in_window(zeroed[1:2], lo[1:2], hi[1:2], "zeroed sines")
+    shifted = emb.clone()
+    shifted[:, 128:] = torch.roll(emb[:, 128:], 1, 1)                                                  # the wrong j
+    with pytest.raises(AssertionError, match="wrong j"):
+        X.assert_in_window(shifted[1:2], lo[1:2], hi[1:2], "wrong j")
+
+
+def test_sample_pack_inputs_are_settled_almost_everywhere():
+    """The GPU check is bit-equality where exp64 is settled at 2^-18 and admits the neighbours of std elsewhere: the exception must be rare."""
+    n = m = 0
+    for case in X.SAMPLE_PACK_CASES:
+        cs = X.sample_pack_case(*case)
+        for v in X.SAMPLE_PACK_LOGVARS:
+            assert bool((cs["logvar"] == v).any())
+        sure = X.settled(X.sample_pack_std64(cs["logvar"]), 2.0 ** -18)
+        n, m = n + sure.numel(), m + int(sure.sum())
+    print(f"sample_pack: exp settled on {m} of {n} elements")
+    assert m / n > 0.99

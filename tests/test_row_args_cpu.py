@@ -91,3 +91,61 @@ def test_text_encoder_helpers_refuse_what_they_cannot_index(lib):
     assert lib.tfx_mul_act(BUF, 8, BUF, 8, BUF, 8, 0, 8, 0, None) == 0
     assert lib.tfx_add_into_f32(BUF, BUF, 0, 0, None) == 0
     assert lib.tfx_row_softmax(BUF, 8, BUF, 8, 0, 8, 1.0, None) == 0
+
+
+# ---------------------------------------------------------------------------------------------------- layout, rotary and step-cursor entries
+ODD = BUF + 8              # 8-byte aligned only: a pointer the 16-byte vector loads and stores of these kernels cannot take
+
+
+def rope(lib, batched, H=2, Ntok=4, T=0, B=1, buf=BUF, w=(BUF, BUF, BUF, BUF), cos=BUF, sin=BUF):
+    tail = (0, 1e-6, None) if batched else (1e-6, None)
+    f = lib.tfx_rmsnorm_rope_batched if batched else lib.tfx_rmsnorm_rope
+    return f(buf, 1024, 4096, 0, 512, H, Ntok, T, B, *w, cos, sin, *tail)
+
+
+@pytest.mark.parametrize("batched", (False, True))
+def test_rmsnorm_rope_refuses_negative_extents_and_pointers_its_vector_loads_cannot_take(lib, batched):
+    for kw in (dict(H=-1), dict(Ntok=-4), dict(B=-1), dict(T=-1)):              # a negative Ntok sized the grid from a negative count
+        refused(lib, rope(lib, batched, **kw), b"negative H, Ntok, B or T")
+    for kw in (dict(buf=ODD), dict(cos=ODD), dict(sin=ODD)) + tuple(dict(w=(BUF,) * i + (ODD,) + (BUF,) * (3 - i)) for i in range(4)):
+        refused(lib, rope(lib, batched, **kw), b"16-byte aligned")
+    assert rope(lib, batched, H=0) == 0 and rope(lib, batched, Ntok=0) == 0 and rope(lib, batched, B=0) == 0
+
+
+def test_scatter_cols_and_copy_rows_refuse_negative_counts_and_unaligned_pointers(lib):
+    scatter = lambda rows=4, src=BUF, dst=BUF: lib.tfx_scatter_cols(src, dst, rows, 64, 384, 64, None)
+    copy = lambda rows=4, batch=2, src=BUF, dst=BUF: lib.tfx_copy_rows(src, 64, 512, dst, 384, 4096, rows, 64, batch, None)
+    refused(lib, scatter(rows=-1), b"negative row count")
+    refused(lib, scatter(src=ODD), b"16-byte aligned")
+    refused(lib, scatter(dst=ODD), b"16-byte aligned")
+    assert scatter(rows=0) == 0
+    refused(lib, copy(rows=-1), b"negative row or batch count")
+    refused(lib, copy(batch=-2), b"negative row or batch count")
+    refused(lib, copy(src=ODD), b"16-byte aligned")
+    refused(lib, copy(dst=ODD), b"16-byte aligned")
+    assert copy(rows=0) == 0 and copy(batch=0) == 0
+
+
+def test_unpack_latents_refuses_a_row_pitch_below_its_columns(lib):
+    unpack = lambda ld, L=16, B=2: lib.tfx_unpack_latents(BUF, ld, BUF, B, 4, 6, L, 0.1159, 0.3611, None)
+    for ld in (63, 56, 0, -64):
+        refused(lib, unpack(ld), b"ld must be >= 4 L")
+    assert unpack(64, B=0) == 0 and unpack(384, B=0) == 0
+
+
+def test_transpose_refuses_a_batch_beyond_the_grid_and_pitches_below_the_extents(lib):
+    tr = lambda N=100, C=72, batch=2, ldi=72, ldo=100: lib.tfx_transpose(BUF, ldi, 1 << 16, BUF, ldo, 1 << 16, N, C, batch, None)
+    refused(lib, tr(batch=65536), b"batch must be <= 65535")
+    refused(lib, tr(ldi=71), b"ldi must be >= C and ldo >= N")
+    refused(lib, tr(ldo=99), b"ldi must be >= C and ldo >= N")
+    assert tr(N=0) == 0 and tr(C=0) == 0 and tr(batch=0) == 0
+
+
+def test_select_step_refuses_a_negative_size_and_unaligned_pointers(lib):
+    sel = lambda per=64, table=BUF, cur=BUF, ptr=BUF: lib.tfx_select_step(table, cur, per, ptr, None)
+    refused(lib, sel(per=-8), b"negative per-step size")
+    refused(lib, sel(per=12), b"multiple of 8")
+    refused(lib, sel(table=ODD), b"16-byte aligned")
+    refused(lib, sel(cur=ODD), b"16-byte aligned")
+    refused(lib, sel(ptr=BUF + 2), b"step_ptr 4-byte")
+    assert sel(per=0) == 0 and sel(per=0, ptr=BUF + 4) == 0

@@ -12,6 +12,10 @@ namespace {
 
 inline hipStream_t S(tfx_stream s) { return (hipStream_t)s; }
 
+// true when one of the pointers is not 16-byte aligned (the kernels behind the entries that ask read and write 16-byte vectors)
+template <typename... P>
+inline bool misaligned16(P... p) { return (((uintptr_t)p | ...) % 16) != 0; }
+
 #define TRY(x)            \
   do {                    \
     if (int _e = (x)) return _e; \
@@ -194,6 +198,8 @@ int tfx_rmsnorm_rope(void* buf, int64_t ld, int64_t bstride, int32_t q_off, int3
                      const void* wk_txt, const float* cos_tab, const float* sin_tab, float eps, tfx_stream stream) {
   if (!buf || !wq_img || !wk_img || !wq_txt || !wk_txt || !cos_tab || !sin_tab) return fail("tfx_rmsnorm_rope: null pointer");
   if (ld % 8 || bstride % 8 || q_off % 8 || k_off % 8) return fail("tfx_rmsnorm_rope: offsets/strides must be multiples of 8");
+  if (H < 0 || Ntok < 0 || B < 0 || T < 0) return fail("tfx_rmsnorm_rope: negative H, Ntok, B or T");
+  if (misaligned16(buf, wq_img, wk_img, wq_txt, wk_txt, cos_tab, sin_tab)) return fail("tfx_rmsnorm_rope: pointers must be 16-byte aligned");
   return rmsnorm_rope(buf, ld, bstride, q_off, k_off, H, Ntok, T, B, wq_img, wk_img, wq_txt, wk_txt, cos_tab, sin_tab,
                       eps, S(stream));
 }
@@ -204,6 +210,8 @@ int tfx_rmsnorm_rope_batched(void* buf, int64_t ld, int64_t bstride, int32_t q_o
                              tfx_stream stream) {
   if (!buf || !wq_img || !wk_img || !wq_txt || !wk_txt || !cos_tab || !sin_tab) return fail("tfx_rmsnorm_rope_batched: null pointer");
   if (ld % 8 || bstride % 8 || q_off % 8 || k_off % 8) return fail("tfx_rmsnorm_rope_batched: offsets/strides must be multiples of 8");
+  if (H < 0 || Ntok < 0 || B < 0 || T < 0) return fail("tfx_rmsnorm_rope_batched: negative H, Ntok, B or T");
+  if (misaligned16(buf, wq_img, wk_img, wq_txt, wk_txt, cos_tab, sin_tab)) return fail("tfx_rmsnorm_rope_batched: pointers must be 16-byte aligned");
   if (tab_bstride < 0 || tab_bstride % 4) return fail("tfx_rmsnorm_rope_batched: tab_bstride must be a non-negative multiple of 4 floats");
   return rmsnorm_rope_tab(buf, ld, bstride, q_off, k_off, H, Ntok, T, B, wq_img, wk_img, wq_txt, wk_txt, cos_tab, sin_tab,
                           tab_bstride, eps, S(stream));
@@ -280,15 +288,21 @@ int tfx_add(const void* a, const void* b, void* out, int64_t n, tfx_stream strea
 }
 int tfx_scatter_cols(const void* src, void* dst, int64_t rows, int32_t C, int64_t ld, int32_t col0, tfx_stream stream) {
   if (!src || !dst) return fail("tfx_scatter_cols: null pointer");
+  if (rows < 0) return fail("tfx_scatter_cols: negative row count");
+  if (misaligned16(src, dst)) return fail("tfx_scatter_cols: pointers must be 16-byte aligned");
   return scatter_cols(src, dst, rows, C, ld, col0, S(stream));
 }
 int tfx_copy_rows(const void* src, int64_t src_ld, int64_t src_bstride, void* dst, int64_t dst_ld, int64_t dst_bstride,
                   int32_t rows, int32_t cols, int32_t batch, tfx_stream stream) {
   if (!src || !dst) return fail("tfx_copy_rows: null pointer");
+  if (rows < 0 || batch < 0) return fail("tfx_copy_rows: negative row or batch count");
+  if (misaligned16(src, dst)) return fail("tfx_copy_rows: pointers must be 16-byte aligned");
   return copy_rows(src, src_ld, src_bstride, dst, dst_ld, dst_bstride, rows, cols, batch, S(stream));
 }
 int tfx_select_step(const void* table, void* cur, int64_t per_step_elems, int32_t* step_ptr, tfx_stream stream) {
   if (!table || !cur || !step_ptr) return fail("tfx_select_step: null pointer");
+  if (per_step_elems < 0) return fail("tfx_select_step: negative per-step size");
+  if (misaligned16(table, cur) || (uintptr_t)step_ptr % 4) return fail("tfx_select_step: table and cur must be 16-byte aligned, step_ptr 4-byte");
   return select_step(table, cur, per_step_elems, step_ptr, S(stream));
 }
 int tfx_advance_step(int32_t* step_ptr, tfx_stream stream) {
@@ -476,6 +490,7 @@ int tfx_vae_sample_pack(const void* moments, const void* eps, int32_t eps_dtype,
 int tfx_unpack_latents(const void* latents, int64_t ld, void* out, int32_t B, int32_t h, int32_t w, int32_t L, float shift,
                        float scale, tfx_stream stream) {
   if (!latents || !out) return fail("tfx_unpack_latents: null pointer");
+  if (L > 0 && ld < 4 * (int64_t)L) return fail("tfx_unpack_latents: ld must be >= 4 L, the columns a token row holds");
   return unpack_latents(latents, ld, out, B, h, w, L, shift, scale, S(stream));
 }
 int tfx_postprocess(const void* x, void* out, int32_t B, int32_t H, int32_t W, int32_t Cs, int32_t C, int32_t mode, int32_t denorm,
@@ -486,6 +501,8 @@ int tfx_postprocess(const void* x, void* out, int32_t B, int32_t H, int32_t W, i
 int tfx_transpose(const void* in, int64_t ldi, int64_t in_bstride, void* out, int64_t ldo, int64_t out_bstride, int32_t N,
                   int32_t C, int32_t batch, tfx_stream stream) {
   if (!in || !out) return fail("tfx_transpose: null pointer");
+  if (batch > 65535) return fail("tfx_transpose: batch must be <= 65535 (gridDim.z)");
+  if (N > 0 && C > 0 && (ldi < C || ldo < N)) return fail("tfx_transpose: ldi must be >= C and ldo >= N");
   return transpose_bf16(in, ldi, in_bstride, out, ldo, out_bstride, N, C, batch, S(stream));
 }
 int tfx_row_softmax(const float* s, int64_t lds, void* p, int64_t ldp, int32_t rows, int32_t N, float scale, tfx_stream stream) {

@@ -668,8 +668,9 @@ int groupnorm_silu_nhwc(const void* x, void* out, const void* gamma, const void*
   return check_launch("groupnorm_silu_nhwc");
 }
 int select_step(const void* table, void* cur, int64_t per_step_elems, int* step_ptr, hipStream_t st) {
-  if (per_step_elems % 8) return fail("select_step: per-step size must be a multiple of 8 elements");
+  if (per_step_elems < 0 || per_step_elems % 8) return fail("select_step: per-step size must be a non-negative multiple of 8 elements");
   const int64_t ch = per_step_elems / 8;
+  if (ch == 0) return 0;
   unsigned grid = (unsigned)((ch + 255) / 256);
   if (grid > 2048) grid = 2048;
   select_step_kernel<<<grid, 256, 0, st>>>((const bf16_t*)table, (bf16_t*)cur, ch, step_ptr, 0);
