@@ -237,7 +237,7 @@ def test_mixed_forward_equals_each_sample_alone(ops):
         for b, p in enumerate(perm):
             assert torch.equal(out[b, :xs[p].shape[1]], alone[p]), (b, p)
     finally:
-        ops.set_option("gemm_splitk", 1)
+        ops.set_option("gemm_splitk", 2)      # the library's default (gemm.hip: g_gemm_splitk)
         ops.set_option("attention_streamk", 1)
 
 
@@ -278,7 +278,7 @@ def test_mixed_session_refreshes_tables_when_equal_length_samples_swap_places(op
             for k, i in enumerate(order):
                 assert torch.equal(out[k, :S1], alone[i]), (order, k)
     finally:
-        ops.set_option("gemm_splitk", 1)
+        ops.set_option("gemm_splitk", 2)      # the library's default (gemm.hip: g_gemm_splitk)
         ops.set_option("attention_streamk", 1)
 
 
@@ -298,7 +298,7 @@ def test_mixed_forward_with_fp8_linears(ops):
             assert e <= 3e-2, (b, e)
             assert torch.equal(mixed[b], alone[b]), b
     finally:
-        ops.set_option("gemm_splitk", 1)
+        ops.set_option("gemm_splitk", 2)      # the library's default (gemm.hip: g_gemm_splitk)
         ops.set_option("attention_streamk", 1)
 
 

@@ -716,7 +716,8 @@ class DitSession:
         padding are those of id 0; nothing reads them)."""
         m = self.model
         assert prompt_embeds.shape[:2] == (self.B, self.T)
-        ops.gemm(prompt_embeds.contiguous(), m.w["context_embedder.w"], m.w["context_embedder.b"], out=self.ctx0)
+        if self.T > 0:      # a session without text rows (tfx_dit_desc.T = 0) has nothing to embed, and no launch takes an empty operand
+            ops.gemm(prompt_embeds.contiguous(), m.w["context_embedder.w"], m.w["context_embedder.b"], out=self.ctx0)
         if self.mixed:
             if not isinstance(img_ids, (list, tuple)) or len(img_ids) != self.B:
                 raise ValueError(f"a mixed session takes a list of {self.B} img_ids tensors, one per sample")
