@@ -6,8 +6,11 @@ convolution or an attention launch -- generic or MFMA, one tile or persistent, K
 must store one definite bf16 bit pattern per element, and so must the plain fp64 / integer restatement here.  No tolerance is
 budgeted for the summation order; assert_elementwise compares per element and names the tile of the first differences.
 
-Nothing in this file restates a kernel: the expected values come from torch matmul / conv2d / softmax in fp64 (or fp32 on
-integers, where fp32 is exact) and from torch's own bf16 operators for the rounding chains the C header documents.
+No expected value here comes from a restated kernel: they come from torch matmul / conv2d / softmax in fp64 (or fp32 on
+integers, where fp32 is exact) and from torch's own bf16 operators for the rounding chains the C header documents.  Two host
+restatements exist beside them: guarded_walk (the guarded attention kernel's reference policy, for the CPU tests that show the dyadic
+cases drive it and for their fault injection -- the dyadic form's expected value is a plain weighted sum) and attention64_graded_chain
+(attention64's rounding points, the one form whose expected value is a chain).
 """
 import functools
 import math
@@ -392,6 +395,349 @@ def attention_reference(q, k, v, lengths=None, D=128, scale=None):
         s = (qh @ kh.transpose(-1, -2)) * (D ** -0.5 if scale is None else scale)
         out[b, :L[b]] = _softmax_times(s, vh).transpose(0, 1).reshape(L[b], HD)
     return out.float().to(BF)
+
+
+# --------------------------------------------------------------------------------------------------------- attention, dyadic form
+# Every softmax weight an exact power of two, every row sum a power of two, v integer: the scores and the reference offset, exp2f of an
+# integer, the bf16 packing of the weights, P.V and the row sums, the exp2f(-d) rescale of a reference move, the merge weights and
+# inv = 1 / l all have exactly representable fp32 results, and the one rounding is the final bf16 pack of o * inv, whose argument is exact.
+# attention_w4.hip passes a.scale * 1.4426950408889634f to its kernels, which pre-scale q with it: DYADIC_SCALE = 0.125 ln 2 rounded to
+# fp32 makes that product exactly 0.125f, so q = 8.0 at one head-dim index d and 0 elsewhere gives the exp2-domain score k[j][d] itself.
+DYADIC_SCALE = float.fromhex("0x1.62e43p-4")            # 0.08664339780807495
+DYADIC_DEPTH = 16                                       # no weight below 2^-16 of its column's sum
+DYADIC_FAMILIES = ("bounded", "far")                    # |score| <= 50 (both streams) | also columns near -200 and near +250 (guarded only)
+DYADIC_KINDS = ("ascending", "descending", "shuffled", "spike", "block")    # key order of a column's weights, see dyadic_attention
+DYADIC_SETS = 8                                         # exponent multisets per key count; a column takes one of them
+W4_TILE, W4_UNIT, W4_ROWS, W4_THR = 64, 32, 32, 4.0     # attention_w4.hip: keys per tile (W4_KV) | per pipeline step (a 32 x 32 MFMA block) |
+#                                                         query rows of a q-block (one wave's any-row vote) | W4_THR
+
+
+def _split_multiset(n: int, g: torch.Generator, root: int = 0, floor: int = 0) -> list:
+    """n exponents e with sum 2^-e = 2^-root exactly: start from {root}, replace one e by two e + 1, n - 1 times, never beyond
+    DYADIC_DEPTH.  The leaf to split is uniform among those that may split, except that leaves above `floor` go first (shallowest first):
+    with n >= 2^(floor - root) every exponent ends at `floor` or deeper.  Returned sorted ascending."""
+    cnt = [0] * (DYADIC_DEPTH + 1)
+    cnt[root] = 1
+    assert 1 <= n <= 2 ** (DYADIC_DEPTH - root)
+    u = torch.rand(max(n - 1, 1), generator=g).tolist()
+    for i in range(n - 1):
+        shallow = next((e for e in range(root, floor) if cnt[e]), None)
+        if shallow is None:
+            t = u[i] * sum(cnt[:DYADIC_DEPTH])
+            for e in range(DYADIC_DEPTH):
+                t -= cnt[e]
+                if t < 0:
+                    break
+            else:
+                e = max(e for e in range(DYADIC_DEPTH) if cnt[e])
+        else:
+            e = shallow
+        cnt[e] -= 1
+        cnt[e + 1] += 2
+    out = [e for e in range(DYADIC_DEPTH + 1) for _ in range(cnt[e])]
+    assert len(out) == n and sum(2 ** (DYADIC_DEPTH - e) for e in out) == 2 ** (DYADIC_DEPTH - root)
+    return out
+
+
+def dyadic_column(h: int, rows: torch.Tensor) -> torch.Tensor:
+    """d(h, i): the head-dim index query row i of head h selects -- (2h + 1) i + 5h mod 128: all 128 indices over any 128 consecutive
+    rows, and neighbouring rows differ."""
+    return ((2 * h + 1) * rows + 5 * h) % 128
+
+
+def dyadic_offsets(b: int, h: int, family: str) -> torch.Tensor:
+    """c_d [128] integers: a column's scores are c_d - e, e in [0, 16].  bounded: c_d in [-34, 50], so |score| <= 50 (50 ln 2 = 34.7 <= 35,
+    the score_bound the reference-free stream is given).  far: every third column near -200 (the first tile must pin), every third near
+    +250, the rest as bounded."""
+    d = torch.arange(128)
+    c = (d * 29 + h * 13 + b * 7) % 85 - 34
+    if family == "far":
+        c = torch.where(d % 3 == 0, -184 - (d + h) % 7, torch.where(d % 3 == 1, 256 - (d + b) % 21, c))
+    else:
+        assert family == "bounded"
+    return c
+
+
+def dyadic_kind(h: int, d: torch.Tensor) -> torch.Tensor:
+    return (d + h) % len(DYADIC_KINDS)
+
+
+def _dyadic_exponents(L: int, b: int, h: int, g: torch.Generator, pool, spikes) -> torch.Tensor:
+    """E [128, L] int64: column d's exponents along the keys, in the order its kind asks for."""
+    d = torch.arange(128)
+    sets = torch.tensor(pool)[(d * 3 + h + b) % DYADIC_SETS]                    # [128, L] sorted ascending (weights descending)
+    kind = dyadic_kind(h, d)
+    perm = torch.rand(128, L, generator=g).argsort(1)
+    E = torch.gather(sets, 1, perm)                                              # shuffled
+    E = torch.where((kind == 0)[:, None], sets.flip(1), E)                       # weights ascending along the keys
+    E = torch.where((kind == 1)[:, None], sets, E)
+    ustart = W4_UNIT * ((L - 1) // W4_UNIT)                                      # the last 32-key step of the last tile
+    for c in d[kind == 3].tolist():                                              # the one large weight sits in the last step
+        rest = torch.tensor(spikes[c % len(spikes)])[perm[c][perm[c] < L - 1]] if L > 1 else torch.empty(0, dtype=torch.long)
+        pos = ustart + (c * 7) % (L - ustart)
+        E[c] = torch.cat([rest[:pos], torch.tensor([1 if L > 1 else 0]), rest[pos:]])
+    G = max(1, L // 8)
+    for c in d[kind == 4].tolist():                                              # the G largest weights as one run, its place by column
+        rest = sets[c, G:][perm[c][perm[c] < L - G] if L > G else slice(0, 0)]
+        pos = ((c * 37 + 11 * h + 5 * b) % 97) * (L - G) // 96 if L > G else 0
+        pos = min(pos, L - G)
+        E[c] = torch.cat([rest[:pos], sets[c, :G].flip(0), rest[pos:]])
+    return E
+
+
+@functools.lru_cache(maxsize=None)
+def _dyadic_parts(B: int, H: int, N: int, seed: int, lengths):
+    """What the families share: the valid lengths, the exponents E[(b, h)] int8 [128, L_b] and the values [B, N, H, 128]."""
+    g = gen(seed)
+    L = _valid_lengths(B, N, lengths)
+    pools = {n: [_split_multiset(n, g) for _ in range(DYADIC_SETS)] for n in sorted(set(L))}
+    spikes = {n: [_split_multiset(n - 1, g, 1, 6) for _ in range(2)] if n > 1 else [[]] for n in sorted(set(L))}
+    vals = torch.randint(1, 65, (B, N, H, 128), generator=g).float() * torch.where(torch.rand(B, N, H, 128, generator=g) < 0.5, -1.0, 1.0)
+    E = {(b, h): _dyadic_exponents(L[b], b, h, g, pools[L[b]], spikes[L[b]]).to(torch.int8) for b in range(B) for h in range(H)}
+    return L, E, vals
+
+
+@functools.lru_cache(maxsize=None)
+def dyadic_attention(B: int, H: int, N: int, seed: int, lengths=None, family: str = "bounded", D: int = 128, pad=float("nan")):
+    """q[i] = 8.0 at index d(h, i) (dyadic_column), k[j][d] = c_d - e[j][d], v non-zero integers in [-64, 64] (every head its own): with
+    scale = DYADIC_SCALE query i's exp2-domain scores are column d(h, i) of k, its weights 2^-e[j][d] up to the common 2^c_d.
+    Every column's exponents are a multiset with sum 2^-e = 1 exactly (_split_multiset; DYADIC_SETS of them per key count, built over each
+    sample's own L keys), laid along the keys by the column's kind (d + h) mod 5:
+      ascending   the weights grow along the keys: the guarded kernel's reference has to move again and again
+      descending  the first unit holds the maximum: the reference never moves
+      shuffled
+      spike       one weight of 1/2 in the last 32-key step of the last (ragged) tile, every other at most 2^-6 (given >= 33 keys): every
+                  earlier tile's maximum is >= 5 below it, more than W4_THR.  (An exponent of 0 beside other keys would make the sum 2.)
+      block       the L / 8 largest weights as one run at a place that depends on the column, so that the key ranges of a tail split or a
+                  stream-K deal end with different references
+    and offset by c_d (dyadic_offsets, by `family`; the families share exponents and values).  Expected output: sum_j 2^-e[j][d(i)] v[j]
+    in fp64 (exact), rounded to bf16 once.
+    Returns (q, k, v, want) bf16 [B, N, H * D]; rows >= lengths[b] of q / k / v hold `pad`, of want NaN.
+    Asserted: every score an integer of magnitude <= 256 (<= 50 in the bounded family); every column sums to 1; for every row
+    sum_j 2^(16 - e_j) |v_j| < 2^24, so every partial sum, in any order and against any reference, is an fp32 number; the expected value
+    is an fp32 number."""
+    assert D == 128
+    L, Es, vals = _dyadic_parts(B, H, N, seed, lengths)
+    q, k, v = (torch.full((B, N, H, D), pad) for _ in range(3))
+    want = torch.full((B, N, H, D), float("nan"))
+    for b in range(B):
+        n = L[b]
+        rows = torch.arange(n)
+        for h in range(H):
+            E = Es[b, h].long()
+            c = dyadic_offsets(b, h, family)
+            w = torch.exp2(-E.double())                                          # [128, n]
+            s = c[:, None] - E
+            assert bool((w.sum(1) == 1.0).all()) and int(E.min()) >= 0 and int(E.max()) <= DYADIC_DEPTH
+            assert int(s.abs().max()) <= (50 if family == "bounded" else ACC_LIMIT)
+            vh = vals[b, :n, h].double()
+            assert float((torch.exp2(16.0 - E.double()) @ vh.abs()).max()) < 2 ** 24
+            col = w @ vh                                                         # [128, D], exact
+            assert bool((col.float().double() == col).all())
+            dm = dyadic_column(h, rows)
+            qh = torch.zeros(n, D)
+            qh[rows, dm] = 8.0
+            q[b, :n, h], k[b, :n, h], v[b, :n, h], want[b, :n, h] = qh, s.T.float(), vals[b, :n, h], col[dm].float()
+    out = tuple(t.reshape(B, N, H * D).to(BF) for t in (q, k, v, want))
+    assert all(bool((t.float().nan_to_num(0.0) == r.reshape(B, N, H * D).nan_to_num(0.0)).all()) for t, r in zip(out[:3], (q, k, v)))
+    return out
+
+
+def dyadic_scores(k: torch.Tensor, b: int, h: int, L: int, rows: torch.Tensor = None) -> torch.Tensor:
+    """fp64 [rows, L]: the exp2-domain scores of head h of sample b of a dyadic_attention k -- q.k * scale log2 e = k[j][d(h, i)]."""
+    rows = torch.arange(L) if rows is None else rows
+    return k[b, :L, h * 128:(h + 1) * 128].double()[:, dyadic_column(h, rows)].T.contiguous()
+
+
+def guarded_walk(s: torch.Tensor, v: torch.Tensor = None, fault: dict = None) -> dict:
+    """attn_w4_kernel<0>'s reference policy and arithmetic restated on the host in fp64 (exact on dyadic inputs): s [R, K] exp2-domain
+    scores of R consecutive query rows that start a q-block (W4_ROWS rows: one wave's vote) over the K keys of one key range, v [K, D].
+    Keys go by units of W4_UNIT (two per W4_TILE-key tile).  The first unit pins every row's reference m to the unit's maximum.  A later
+    unit moves the references of a q-block when ANY of its rows has a maximum more than W4_THR above its reference: every row of the block
+    then moves by max(excess, 0) = d, rescales what it has accumulated by 2^-d and shifts the unit's scores by d.  Weights are 2^(s - m).
+    Returns o [R, D], l [R], m [R] (un-normalised, as a tail-split / stream-K piece leaves them), moves [R] (moves with d != 0),
+    late [R] (those inside the last tile) and events [(unit, q-block)] of the moves.
+    fault (the tests' fault injection, one unit `unit` and q-block `block`): kind "skip_rescale" the rescale left out | "rescale_other"
+    applied to the neighbouring q-block's rows instead | "no_shift" the unit's scores not shifted | "double" (tile, row): the weights of
+    one row doubled in one tile."""
+    R, K = s.shape
+    s = s.double()
+    grp = torch.arange(R) // W4_ROWS
+    ng = int(grp[-1]) + 1
+    m, l, moves, late = torch.zeros(R, dtype=torch.float64), torch.zeros(R, dtype=torch.float64), torch.zeros(R, dtype=torch.long), torch.zeros(R, dtype=torch.long)
+    o = None if v is None else torch.zeros(R, v.shape[1], dtype=torch.float64)
+    events = []
+    nu = (K + W4_UNIT - 1) // W4_UNIT
+    last_tile = (K - 1) // W4_TILE
+    kind = fault["kind"] if fault else None
+    for u in range(nu):
+        su = s[:, u * W4_UNIT:min(K, (u + 1) * W4_UNIT)]                         # keys >= K are masked: they are not there
+        mx = (su - m[:, None]).max(1).values
+        if u == 0:
+            d = mx
+        else:
+            take = torch.zeros(ng, dtype=torch.bool)
+            take[grp[mx > W4_THR]] = True
+            d = torch.where(take[grp], mx.clamp(min=0.0), torch.zeros_like(mx))
+            moved = d != 0
+            moves += moved
+            if u // 2 == last_tile:
+                late += moved
+            events += [(u, int(x)) for x in grp[moved].unique()]
+        m_old = m
+        m = m + d
+        assert bool((m.float().to(BF).double() == m).all()), "a reference must be a bf16 number"
+        f = torch.exp2(-d) if u else torch.ones_like(d)
+        shift = m
+        if fault and fault.get("unit") == u and kind in ("skip_rescale", "rescale_other", "no_shift"):
+            mine = grp == fault["block"]
+            if kind == "no_shift":
+                shift = torch.where(mine, m_old, m)
+            else:
+                if kind == "rescale_other":
+                    other = grp == (fault["block"] ^ 1)
+                    assert int(mine.sum()) == W4_ROWS and int(other.sum()) == W4_ROWS
+                    g2 = torch.ones_like(f)
+                    g2[other] = f[mine]
+                    f = torch.where(mine, torch.ones_like(f), f) * g2
+                else:
+                    f = torch.where(mine, torch.ones_like(f), f)
+        p = torch.exp2(su - shift[:, None])
+        if kind == "double" and u // 2 == fault["tile"]:
+            p[fault["row"]] *= 2.0
+        l = l * f + p.sum(1)
+        if o is not None:
+            o = o * f[:, None] + p @ v[u * W4_UNIT:u * W4_UNIT + su.shape[1]].double()
+    return dict(o=o, l=l, m=m, moves=moves, late=late, events=events)
+
+
+def merge_pieces(pieces, wrong=None) -> torch.Tensor:
+    """attn_w4_merge_kernel / attn_w4_merge_sk_kernel: O = sum_r o_r 2^(m_r - m) / sum_r l_r 2^(m_r - m), m = max_r m_r, rounded to bf16
+    once.  wrong = (r, r2): piece r weighted with piece r2's reference (fault injection)."""
+    m = torch.stack([p["m"] for p in pieces]).max(0).values
+    acc, l = 0.0, 0.0
+    for r, p in enumerate(pieces):
+        w = torch.exp2(pieces[wrong[1]]["m"] - m) if wrong and wrong[0] == r else torch.exp2(p["m"] - m)
+        acc, l = acc + p["o"] * w[:, None], l + p["l"] * w
+    return finish_rows(acc, l)
+
+
+def finish_rows(o: torch.Tensor, l: torch.Tensor) -> torch.Tensor:
+    """bf16(o * (1 / l)) of exact fp64 accumulators."""
+    return (o * (1.0 / l)[:, None]).float().to(BF)
+
+
+def sk_bound(c: int, group: int, share: int, nkv: int, total: int) -> int:
+    """attention_w4.hip::w4_sk_bound: boundary c of a sample's dealt tail units, snapped to the item boundary when it would leave a piece
+    shorter than four tiles."""
+    if c >= group:
+        return total
+    p = c * share
+    if p >= total:
+        return total
+    r = p % nkv
+    if r < 4:
+        p -= r
+    elif r > nkv - 4:
+        p += nkv - r
+    return min(p, total)
+
+
+def streamk_pieces(H: int, N: int, B: int, cus: int, item: int):
+    """Key-tile ranges [(t0, t1), ...] of tail item `item` (an index among the dealt items of one sample) of a stream-K launch on `cus`
+    CUs (a multiple of eight), or None when attention_w4.hip::joint_attention_w4 would not deal this shape there."""
+    group, nkv, Tp = cus // B, (N + W4_TILE - 1) // W4_TILE, H * ((N + 255) // 256)
+    R = Tp - (Tp // group) * group
+    share = (R * nkv + group - 1) // group if R else 0
+    if not (R > 0 and nkv >= 16 and share * 6 >= nkv and share >= 8):
+        return None
+    total = R * nkv
+    cuts = sorted({sk_bound(c, group, share, nkv, total) for c in range(group + 1)} | {item * nkv, (item + 1) * nkv})
+    cuts = [p - item * nkv for p in cuts if item * nkv <= p <= (item + 1) * nkv]
+    return list(zip(cuts[:-1], cuts[1:]))
+
+
+# --------------------------------------------------------------------------------------------------------- attention64, graded form
+# tfx_attention64 multiplies by `scale`, adds the bias and only then multiplies by log2 e in fp32: its exp2-domain scores are no integers
+# for any scale, so the dyadic form is not available.  The graded form gives it small-integer NATURAL scores that grow along the keys, so
+# that the running maximum moves (alpha != 1) in most 32-key blocks, and a restatement that follows the kernel's rounding points.
+# ATTN64_GRADED_SHARE: the share of the output elements of all the cases whose bf16 value changes when every exponential (weights and
+# alpha) and the row sum of the restatement move by one fp32 step either way; tests/test_exact_inputs_cpu.py measures it, the GPU test
+# compares with ulps=1 and allows 4 * ATTN64_GRADED_SHARE of all elements to differ at all.
+ATTN64_GRADED_MODES = ("plain", "causal", "bias")
+ATTN64_GRADED_SHARE = 243 / 4080384
+
+
+@functools.lru_cache(maxsize=None)
+def graded_attention64(B: int, H: int, N: int, seed: int, mode: str = "plain", D: int = 64):
+    """q[i] = 8.0 at index (2h + 1) i + 5h mod 64 (scale 0.125: the natural score is k[j][d]), k[j][d] = j // g_d + ((7 j + d) mod 3) - 1 -
+    top_d with g_d in (8, 16, 24, 32) by column: integers that rise by a unit every g_d keys, so the maximum of nearly every 32-key block
+    exceeds the one before, jittered so that a block's weights are not monotone; top_d keeps |k| <= 72.
+    v: integers of magnitude 1 .. 64, one sign per column.  mode "bias": an integer rel_bias [H, 2N - 1] in [-3, 3] (fp32) is returned as well, else None.
+    Returns (q, k, v, rel_bias); the expected value comes from attention64_graded_chain."""
+    assert mode in ATTN64_GRADED_MODES
+    g = gen(seed)
+    j, d = torch.arange(N)[:, None], torch.arange(D)[None, :]
+    gd = torch.tensor((8, 16, 24, 32))[(d + d // 4) % 4]
+    q, k = torch.zeros(B, N, H, D), torch.zeros(B, N, H, D)
+    for b in range(B):
+        for h in range(H):
+            kk = j // gd + (7 * j + d + h + b) % 3 - 1
+            k[b, :, h] = (kk - (kk.max(0, keepdim=True).values - (d + h) % 9)).float()
+            q[b, torch.arange(N), h, ((2 * h + 1) * torch.arange(N) + 5 * h) % D] = 8.0
+    assert k.abs().max().item() <= 72
+    # one sign per (sample, head, column): an output is then a weighted mean of values of one sign, |out| >= 1.  With mixed signs some of
+    # the 4 million outputs cancel to 1e-5 of the sum of |p v|, and the fp32 roundings of the accumulation (2^-24 of THAT sum) are more
+    # than a bf16 step of such a result: no tolerance counted in bf16 steps would describe a correct kernel there
+    v = torch.randint(1, 65, (B, N, H, D), generator=g).float() * torch.where(torch.rand(B, 1, H, D, generator=g) < 0.5, -1.0, 1.0)
+    bias = torch.randint(-3, 4, (H, 2 * N - 1), generator=g).float() if mode == "bias" else None
+    return tuple(t.reshape(B, N, H * D).to(BF) for t in (q, k, v)) + (bias,)
+
+
+def attention64_graded_chain(q, k, v, scale: float, rel_bias=None, causal: bool = False, exp_ulps: int = 0, sum_ulps: int = 0, D: int = 64):
+    """attn64_kernel (textenc.hip) restated with its rounding points, everything between them in fp64.  Per query row and 32-key block:
+    s = fp32((scale q.k + bias) * fp32(log2 e)) (the natural score must be an integer: asserted), keys >= N or beyond a causal row -inf;
+    m = the running maximum after the block; alpha = fp32(exp2(fp32(m_before - m))); p = fp32(exp2(fp32(s - m))); l = l * alpha + sum p
+    (the UNROUNDED weights); o = o * alpha + bf16(p) . v.  At the end inv = fp32(1 / fp32(l)), out = bf16(fp32(fp32(o) * inv)).
+    exp_ulps / sum_ulps: every exponential (p and alpha) / the final row sum moved by that many fp32 steps (the cap's measurement)."""
+    B, N, HD = q.shape
+    H = HD // D
+    log2e = torch.tensor(1.4426950408889634, dtype=torch.float32)
+    qh, kh, vh = (t.double().view(B, N, H, D).transpose(1, 2) for t in (q, k, v))       # [B, H, N, D]
+    nat = (qh @ kh.transpose(-1, -2)) * scale
+    if rel_bias is not None:
+        idx = torch.arange(N)[None, :] - torch.arange(N)[:, None] + N - 1
+        nat = nat + rel_bias.double()[:, idx]
+    assert bool((nat == nat.round()).all()) and nat.abs().max().item() < 2 ** 10
+    s = nat.float() * log2e                                                               # one fp32 rounding
+    if causal:
+        s = s + torch.full((N, N), -math.inf).triu(1)
+    m = torch.full((B, H, N), -math.inf)
+    l = torch.zeros(B, H, N, dtype=torch.float64)
+    o = torch.zeros(B, H, N, D, dtype=torch.float64)
+
+    def ex(x):                                                                            # fp32 exp2 of an fp32 argument, moved by exp_ulps
+        r = torch.exp2(x.double()).float()
+        return nudge(r, exp_ulps) if exp_ulps else r
+    for kb in range((N + 31) // 32):
+        sb = s[..., kb * 32:(kb + 1) * 32]
+        m_new = torch.maximum(m, sb.max(-1).values)
+        m_use = torch.where(m_new == -math.inf, torch.zeros_like(m_new), m_new)
+        alpha = ex(m - m_use).double()
+        p = ex(sb - m_use[..., None])
+        l = l * alpha + p.double().sum(-1)
+        o = o * alpha[..., None] + p.to(BF).double() @ vh[:, :, kb * 32:(kb + 1) * 32]
+        m = m_new
+    lf = l.float()
+    if sum_ulps:
+        lf = nudge(lf, sum_ulps)
+    inv = (1.0 / lf.double()).float()
+    out = (o.float().double() * inv.double()[..., None]).float().to(BF)
+    return out.transpose(1, 2).reshape(B, N, HD)
+
+
+def attention64_graded_cases():
+    return [(N, H, mode) for N in ATTN64_NS for H in ATTN64_HS for mode in ATTN64_GRADED_MODES]
 
 
 # --------------------------------------------------------------------------------------------------------- convolution

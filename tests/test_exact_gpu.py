@@ -439,6 +439,109 @@ def test_attention_seq_len_is_exact_and_leaves_the_padding_alone(ops, shape, len
             X.assert_elementwise(out, expect, f"attention seq_len {lengths} {name} form, score_bound {bound}")
 
 
+# ----------------------------------------------------------------------------------------------------------------- attention, dyadic form
+# Every softmax weight a power of two, every row sum a power of two, v integer (X.dyadic_attention): the scores, exp2f of an integer, the
+# bf16 weights, P.V and the row sums, the exp2f(-d) rescale of a reference move, the merge weights and 1 / l are all exact in fp32, and the
+# one rounding is the final bf16 pack -- `ulps=0` in any summation order, with any reference policy and any split into pieces.  Unlike the
+# uniform and the selector form this one sees the softmax arithmetic: a reference move whose rescale is lost or lands on the other q-block,
+# unshifted scores, a merge weight, a masked key admitted with a small weight (tests/test_exact_inputs_cpu.py injects each of them into the
+# host restatement and shows that the expected bits change, and that the cases do move the reference and do merge unequal pieces).
+def check_dyadic(ops, B, H, N, what, streamk_tail=0, **kw):
+    """Both streams on the bounded family (|score| <= 50, 50 ln 2 <= 35), the guarded one also on the far family (columns near -200 and
+    near +250); the form asserted from the counters."""
+    seed = X.shape_seed(B, H, N)
+    for family, streams in (("bounded", ((0.0, "w4_guarded"), (35.0, "w4_reference_free"))), ("far", ((0.0, "w4_guarded"),))):
+        q, k, v, want = X.dyadic_attention(B, H, N, seed, None, family)
+        for bound, mode in streams:
+            ops.attention_mode_counts(reset=True)
+            got = fused_attention(ops, q, k, v, scale=X.DYADIC_SCALE, score_bound=bound, **kw)
+            counts = ops.attention_mode_counts()
+            assert counts[mode] == 1 and sum(counts[m] for m in ops.ATTENTION_MODES[:8]) == 1 and counts["streamk_tail"] == streamk_tail, counts
+            X.assert_elementwise(got, want, f"attention {what} ({B}, {H}, {N}) dyadic form, {family} family, score_bound {bound}")
+
+
+@pytest.mark.parametrize("B,H,N", X.ATTN_SHAPES)
+def test_attention_dyadic_form(ops, B, H, N):
+    """The default launch.  The columns' key orders make the guarded kernel's reference move repeatedly (ascending weights), never
+    (descending), inside the ragged last tile by more than W4_THR (the late spike), and the far family makes the first unit pin it at
+    -200 and +250; the reference-free stream has to place graded scores of +-50 without a reference."""
+    check_dyadic(ops, B, H, N, "default launch")
+
+
+@pytest.mark.parametrize("B,H,N", X.ATTN_PERSISTENT_SHAPES)
+def test_attention_dyadic_persistent_item_walk(ops, B, H, N):
+    items = B * H * ((N + 255) // 256)
+    if items <= grid_of_device():
+        pytest.skip(f"{items} items do not exceed this device's {grid_of_device()} workgroups: no item walk")
+    try:
+        for pers in (1, 0):
+            ops.set_option("attention_persistent", pers)
+            check_dyadic(ops, B, H, N, f"attention_persistent {pers}")
+    finally:
+        ops.set_option("attention_persistent", 1)
+
+
+def test_attention_dyadic_streamk_dealing(ops):
+    """The dealt pieces of an item end with different references in most rows (the block columns put their largest weights at a place of
+    their own), so attn_w4_merge_sk_kernel's exp2f(m_part - m) weights are powers of two other than 1 on the guarded stream.  Admission
+    rule as in test_attention_streamk_dealing_is_exact."""
+    B, H, N = X.ATTN_STREAMK_SHAPE
+    group, nkv, Tp = grid_of_device() // B, (N + 63) // 64, H * ((N + 255) // 256)
+    R = Tp - (Tp // group) * group
+    share = (R * nkv + group - 1) // group if R else 0
+    if not (R > 0 and nkv >= 16 and share * 6 >= nkv and share >= 8):
+        pytest.skip(f"{Tp} items per sample on groups of {group} CUs: nothing to deal")
+    ws = torch.empty(72 << 20, dtype=torch.uint8, device="cuda")
+    try:
+        ops.set_option("attention_streamk", 2)
+        check_dyadic(ops, B, H, N, "stream-K", streamk_tail=1, workspace=ws)
+    finally:
+        ops.set_option("attention_streamk", 1)
+
+
+def test_attention_dyadic_tail_split(ops):
+    """attn_w4_merge_kernel on halves whose references differ either way.  Plan as in test_attention_tail_split_is_exact."""
+    B, H, N = X.ATTN_TAIL_SHAPE
+    C = torch.cuda.get_device_properties(0).multi_processor_count
+    T, nkv = B * H * ((N + 255) // 256), (N + 63) // 64
+    tail = T % C
+    m = (tail + B - 1) // B
+    if not (tail and T >= C and m * B * 2 <= C + 8 and nkv >= 48 and m < H * ((N + 255) // 256)):
+        pytest.skip(f"{T} items on {C} CUs: the tail split is not taken")
+    try:
+        ops.set_option("attention_tail_split", 1)
+        check_dyadic(ops, B, H, N, "tail split")
+    finally:
+        ops.set_option("attention_tail_split", 0)
+        ops.release_scratch()
+
+
+@pytest.mark.parametrize("shape,lengths", X.ATTN_SEQ_LEN_CASES)
+def test_attention_dyadic_seq_len(ops, shape, lengths):
+    """Per-sample lengths: every sample's multisets are built over its own L keys, NaN in every padding row of q, k and v; rows >= L keep
+    the sentinel the output was filled with."""
+    B, H, N = shape
+    sl = torch.tensor(lengths, dtype=torch.int32, device="cuda")
+    seed = X.shape_seed(B, H, N)
+    for family, streams in (("bounded", ((0.0, "w4_guarded"), (35.0, "w4_reference_free"))), ("far", ((0.0, "w4_guarded"),))):
+        q, k, v, want = X.dyadic_attention(B, H, N, seed, lengths, family)
+        for b, L in enumerate(lengths):
+            assert not torch.isnan(want[b, :L].float()).any() and torch.isnan(want[b, L:].float()).all()
+        expect = torch.where(torch.isnan(want), torch.full_like(want, SENTINEL), want)
+        HD = H * 128
+        for bound, mode in streams:
+            # the blocks' [k | v | q] layout, the output in place over q, whose padding rows hold the sentinel (k / v keep their NaN rows,
+            # so they are compared as bits)
+            y = torch.cat([k, v, torch.where(torch.isnan(q), torch.full_like(q, SENTINEL), q)], -1).cuda()
+            kv_before = y[:, :, :2 * HD].clone()
+            ops.attention_mode_counts(reset=True)
+            ops.attention(y[:, :, 2 * HD:], y[:, :, :HD], y[:, :, HD:2 * HD], out=y[:, :, 2 * HD:], scale=X.DYADIC_SCALE, score_bound=bound, seq_len=sl)
+            counts = ops.attention_mode_counts()
+            assert counts[mode] == 1 and counts["streamk_tail"] == 0, counts
+            assert torch.equal(y[:, :, :2 * HD].contiguous().view(torch.int16), kv_before.view(torch.int16)), "k / v columns were written"
+            X.assert_elementwise(y[:, :, 2 * HD:], expect, f"attention seq_len {lengths} dyadic form, {family} family, score_bound {bound}")
+
+
 # ----------------------------------------------------------------------------------------------------------------- attention64
 def pitched(t, extra=24):
     """t on the device as a view with a row pitch of its own."""
@@ -472,6 +575,24 @@ def test_attention64_exact_forms(ops, N, H):
             continue
         q, k, v, bias, want = X.bias_selector_attention(B, H, N, delta, seed)
         X.assert_elementwise(run_attention64(ops, q, k, v, rel_bias=bias.cuda()), want, f"attention64 bias selector delta {delta} N {N} H {H}")
+
+
+def test_attention64_graded_form(ops):
+    """Graded weights through attn64_kernel's online rescale: natural scores that are small integers rising along the keys (one-hot q times
+    8, scale 0.125), plain, causal and with an integer rel_bias, so that the running maximum moves and alpha != 1 in most 32-key blocks.
+    The kernel multiplies by log2 e after the bias, so its exp2-domain scores are no integers and nothing is exact; the expected value is
+    X.attention64_graded_chain, the kernel's rounding points (the maximum in force at each block, the bf16 weights under an unrounded
+    sum, alpha) with fp64 in between.  Every element within one bf16 step, and over all cases at most 4 * X.ATTN64_GRADED_SHARE of the
+    elements different at all -- the share the CPU measures for one fp32 step of every exponential and of the row sum."""
+    n = diff = 0
+    for N, H, mode in X.attention64_graded_cases():
+        q, k, v, bias = X.graded_attention64(2, H, N, X.shape_seed(2, H, N, 64, 1), mode)
+        want = X.attention64_graded_chain(q, k, v, 0.125, rel_bias=bias, causal=mode == "causal")
+        kw = dict(causal=True) if mode == "causal" else dict(rel_bias=bias.cuda()) if mode == "bias" else {}
+        d = X.assert_elementwise(run_attention64(ops, q, k, v, **kw), want, f"attention64 graded {mode} N {N} H {H}", ulps=1)
+        n, diff = n + want.numel(), diff + d
+    print(f"attention64 graded: {diff} of {n} elements differ from the chain; cap {4 * X.ATTN64_GRADED_SHARE * n:.1f}")
+    assert diff <= 4 * X.ATTN64_GRADED_SHARE * n
 
 
 # ----------------------------------------------------------------------------------------------------------------- convolutions

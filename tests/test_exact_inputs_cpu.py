@@ -4,7 +4,10 @@ Three things, for every shape tests/test_exact_gpu.py uses: each generator meets
 restatement in fp64 rounds to the bits the construction claims (uniform attention -> c, selector -> v[pi], the integer GEMM and
 convolution chains); and assert_elementwise rejects every emulated kernel fault -- a dropped product, a dropped K-tile, a shifted
 bias chunk, another sample's gate, a missing rounding, a dropped / padded / swapped key, swapped heads, a shifted rotary pair.
-The faults are injected into the CPU computation; no kernel code is restated here."""
+The faults are injected into the CPU computation; no kernel code is restated here, with one exception: the dyadic attention form
+(power-of-two softmax weights) is there to see the guarded kernel's reference moves and the merges of key ranges, so its faults -- a lost
+or misplaced rescale, unshifted scores, a merge weight, an admitted masked key, doubled weights -- are injected into X.guarded_walk, the
+host restatement of that kernel's reference policy, which is itself checked against the form's policy-free expected value."""
 import pytest
 import torch
 
@@ -351,6 +354,224 @@ def test_fault_value_column_misplaced(att):
     assert (att["u"][3][0, 0, 5] != att["u"][3][0, 0, 6]) == bool(X.mismatches(got, want).any())
 
 
+# ------------------------------------------------------------------------------------------------ attention, dyadic form
+def test_dyadic_scale_times_log2e_is_an_eighth_in_fp32():
+    scale = torch.tensor(X.DYADIC_SCALE, dtype=torch.float32)
+    assert scale.item() == X.DYADIC_SCALE and X.DYADIC_SCALE == 0.08664339780807495
+    assert (scale * torch.tensor(1.4426950408889634, dtype=torch.float32)).item() == 0.125
+    ks = torch.arange(-256, 257).float().to(BF)
+    assert bool(((ks.float() * 8.0 * 0.125).to(BF) == ks).all())                         # bf16(q * scale_log2e) = 1.0 keeps every k
+
+
+def head(t, b, h, L):
+    return t[b, :L, h * 128:(h + 1) * 128]
+
+
+@pytest.mark.parametrize("family", X.DYADIC_FAMILIES)
+@pytest.mark.parametrize("B,H,N,L", seq_cases())
+def test_dyadic_generator_conditions_hold(B, H, N, L, family):
+    q, k, v, want = X.dyadic_attention(B, H, N, X.shape_seed(B, H, N), L, family)
+    assert q.shape == k.shape == v.shape == want.shape == (B, N, H * 128)
+    lens = L or (N,) * B
+    far = False
+    for b, n in enumerate(lens):
+        for t in (q, k, v, want):
+            assert torch.isnan(t[b, n:].float()).all() and torch.isfinite(t[b, :n].float()).all()
+        for h in range(H):
+            qh, kh, vh = (head(t, b, h, n).double() for t in (q, k, v))
+            dm = X.dyadic_column(h, torch.arange(n))
+            assert bool((qh.sum(1) == 8.0).all()) and bool((qh[torch.arange(n), dm] == 8.0).all())          # one-hot times 8
+            assert bool((dm[1:] != dm[:-1]).all()) and len(set(dm.tolist())) == min(n, 128)
+            assert bool((kh == kh.round()).all()) and kh.abs().max().item() <= (50 if family == "bounded" else 256)
+            far = far or (kh.max().item() > 200 and kh.min().item() < -180)
+            c = X.dyadic_offsets(b, h, family).double()
+            e = c[None, :] - kh                                                                              # [n, 128]
+            assert e.min().item() >= 0 and e.max().item() <= X.DYADIC_DEPTH
+            assert bool((torch.exp2(-e).sum(0) == 1.0).all())                                                # every column sums to exactly 1
+            assert bool((vh == vh.round()).all()) and vh.abs().min().item() >= 1 and vh.abs().max().item() <= 64
+            assert (torch.exp2(16.0 - e).T @ vh.abs()).max().item() < 2 ** 24
+        if H > 1 and n > 1:
+            assert not torch.equal(head(v, b, 0, n), head(v, b, 1, n))
+    assert far == (family == "far")
+
+
+def exp2_softmax(q, k, v, b, h, L):
+    """softmax in the exp2 domain, fp64: exact on dyadic inputs (weights 2^(s - max), integer v, a power-of-two row sum)."""
+    s = (head(q, b, h, L).double() @ head(k, b, h, L).double().T) * 0.125
+    p = torch.exp2(s - s.max(-1, keepdim=True).values)
+    return ((p @ head(v, b, h, L).double()) / p.sum(-1, keepdim=True)).float().to(BF)
+
+
+@pytest.mark.parametrize("family", X.DYADIC_FAMILIES)
+@pytest.mark.parametrize("B,H,N,L", [(B, H, N, None) for B, H, N in X.ATTN_SHAPES] + [(2, 2, 512, (512, 130))])
+def test_dyadic_want_is_the_exact_softmax(B, H, N, L, family):
+    """`want` (column sums of 2^-e v) against a plain softmax over q, k, v: bit for bit in the exp2 domain, where fp64 is exact, and within
+    one bf16 step of the natural-exponential fp64 softmax (many expected values are ties of the bf16 rounding: dyadic fractions)."""
+    q, k, v, want = X.dyadic_attention(B, H, N, X.shape_seed(B, H, N), L, family)
+    for b, n in enumerate(L or (N,) * B):
+        for h in range(H):
+            X.assert_elementwise(exp2_softmax(q, k, v, b, h, n), head(want, b, h, n), f"exp2-domain softmax, sample {b} head {h}")
+    ref, w = valid(X.attention_reference(q, k, v, L, scale=X.DYADIC_SCALE), L), valid(want, L)
+    zero = w == 0                                                                        # an exact cancellation: fp64's exp leaves ~1e-8 there
+    assert not bool((X.mismatches(ref, w, 1) & ~zero).any()) and (ref.float().abs() * zero).max().item() < 2.0 ** -20
+
+
+def walk_rows(k, v, b, h, L, rows, keys=None, **kw):
+    s = X.dyadic_scores(k, b, h, L, rows)
+    vh = head(v, b, h, L).double()
+    if keys is not None:
+        s, vh = s[:, keys[0]:keys[1]], vh[keys[0]:keys[1]]
+    return X.guarded_walk(s, vh, **kw)
+
+
+@pytest.mark.parametrize("B,H,N", [s for s in X.ATTN_SHAPES + X.ATTN_PERSISTENT_SHAPES + [X.ATTN_STREAMK_SHAPE, X.ATTN_TAIL_SHAPE] if s[2] >= 33])
+def test_dyadic_cases_move_the_guarded_reference(B, H, N):
+    """The restated policy on the last head of the last sample (its first 256 rows): finishing its accumulators gives `want`; some rows
+    never move (the descending columns); from five tiles on some rows move at least twice; and some move inside the last tile -- the
+    ragged one wherever N is no multiple of 64 (the spike columns; at N = 33 the single tile's second unit holds the spike)."""
+    for family in X.DYADIC_FAMILIES:
+        q, k, v, want = X.dyadic_attention(B, H, N, X.shape_seed(B, H, N), None, family)
+        rows = torch.arange(min(N, 256))
+        w = walk_rows(k, v, B - 1, H - 1, N, rows)
+        X.assert_elementwise(X.finish_rows(w["o"], w["l"]), head(want, B - 1, H - 1, N)[rows], f"restated guarded kernel {family}")
+        assert int((w["moves"] == 0).sum()) > 0 and int((w["late"] > 0).sum()) > 0
+        kinds = X.dyadic_kind(H - 1, X.dyadic_column(H - 1, rows))
+        assert int(w["moves"][kinds == 1].sum()) == 0                                    # descending columns never move
+        if N >= 300:
+            assert int(w["moves"].max()) >= 2
+            assert int(w["moves"][kinds == 0].min()) >= 2                                # ascending columns: repeatedly
+            spike = head(k, B - 1, H - 1, N).double()[:, X.dyadic_column(H - 1, rows[kinds == 3])]          # [N, spike rows]
+            last = 64 * ((N - 1) // 64)
+            assert bool((spike[last:].max(0).values - spike[:last].max(0).values >= 5).all())               # more than W4_THR above every earlier tile
+
+
+def test_dyadic_lengths_move_the_reference_per_sample():
+    (B, H, N), L = X.ATTN_SEQ_LEN_CASES[0]
+    q, k, v, want = X.dyadic_attention(B, H, N, X.shape_seed(B, H, N), L, "far")
+    for b, n in enumerate(L):
+        rows = torch.arange(min(n, 64))
+        w = walk_rows(k, v, b, 5, n, rows)
+        X.assert_elementwise(X.finish_rows(w["o"], w["l"]), head(want, b, 5, n)[rows], f"sample {b}")
+        assert int(w["moves"].max()) >= (2 if n > 64 else 1)
+
+
+def pieces_of(k, v, b, h, N, rows, tiles):
+    return [walk_rows(k, v, b, h, N, rows, keys=(t0 * 64, min(N, t1 * 64))) for t0, t1 in tiles]
+
+
+def test_dyadic_tail_split_pieces_end_with_different_references():
+    """(1, 24, 3100) on 256 CUs: the last 56 (head, q-tile) pairs are cut at key tile 24 of 49 (joint_attention_w4).  Head 23, q-tile 0."""
+    B, H, N = X.ATTN_TAIL_SHAPE
+    nkv = (N + 63) // 64
+    for family in X.DYADIC_FAMILIES:
+        q, k, v, want = X.dyadic_attention(B, H, N, X.shape_seed(B, H, N), None, family)
+        rows = torch.arange(256)
+        ps = pieces_of(k, v, 0, H - 1, N, rows, [(0, nkv // 2), (nkv // 2, nkv)])
+        X.assert_elementwise(X.merge_pieces(ps), head(want, 0, H - 1, N)[rows], "merged halves")
+        differ = ps[0]["m"] != ps[1]["m"]
+        assert int(differ.sum()) >= 128 and int((ps[0]["m"] > ps[1]["m"]).sum()) > 0 and int((ps[0]["m"] < ps[1]["m"]).sum()) > 0
+        rejects(X.merge_pieces(ps, wrong=(0, 1)), head(want, 0, H - 1, N)[rows], "merged halves")
+
+
+def test_dyadic_streamk_pieces_end_with_different_references():
+    """(2, 5, 2304) on 256 CUs: all 45 items of a sample are dealt in ranges of 13 key tiles (share), boundaries snapped by w4_sk_bound."""
+    B, H, N = X.ATTN_STREAMK_SHAPE
+    nqb = (N + 255) // 256
+    q, k, v, want = X.dyadic_attention(B, H, N, X.shape_seed(B, H, N), None, "bounded")
+    cut = 0
+    for item in (0, 7, 22, 44):
+        tiles = X.streamk_pieces(H, N, B, 256, item)
+        assert tiles is not None and tiles[0][0] == 0 and tiles[-1][1] == (N + 63) // 64 and len(tiles) <= 8
+        h, rows = item // nqb, (item % nqb) * 256 + torch.arange(256)
+        ps = pieces_of(k, v, 1, h, N, rows, tiles)
+        X.assert_elementwise(X.merge_pieces(ps), head(want, 1, h, N)[rows], f"merged pieces of item {item}")
+        if len(tiles) > 1:
+            cut += 1
+            ms = torch.stack([p["m"] for p in ps])
+            assert int((ms.max(0).values != ms.min(0).values).sum()) >= 128
+            rejects(X.merge_pieces(ps, wrong=(len(ps) - 1, 0)), head(want, 1, h, N)[rows], "merged pieces")
+    assert cut >= 3
+
+
+@pytest.fixture(scope="module")
+def dy():
+    """(1, 3, 300), bounded family, head 1, all rows padded to whole q-blocks by the kernel's row clamp: ragged in the last tile (keys 256 .. 299)."""
+    B, H, N, h = 1, 3, 300, 1
+    q, k, v, want = X.dyadic_attention(B, H, N, X.shape_seed(B, H, N), None, "bounded")
+    rows = torch.arange(320).clamp(max=N - 1)
+    s, vh = X.dyadic_scores(k, 0, h, N, rows), head(v, 0, h, N).double()
+    base = X.guarded_walk(s, vh)
+    wh = head(want, 0, h, N)[rows]
+    X.assert_elementwise(X.finish_rows(base["o"], base["l"]), wh, "the restatement itself")
+    return dict(s=s, v=vh, want=wh, base=base, rows=rows, h=h, N=N)
+
+
+def faulted(dy, what, s=None, v=None, **fault):
+    w = X.guarded_walk(dy["s"] if s is None else s, dy["v"] if v is None else v, fault or None)
+    return rejects(X.finish_rows(w["o"], w["l"]), dy["want"], what)
+
+
+def a_move(dy, nth=0):
+    """(unit, q-block) of a reference move of a whole-row q-block that is not the very first after the pin."""
+    ev = [(u, g) for u, g in dy["base"]["events"] if u >= 2 and g < 8]
+    assert len(ev) > 4
+    return ev[len(ev) // 2 + nth]
+
+
+def test_fault_reference_move_without_the_rescale(dy):
+    u, g = a_move(dy)
+    faulted(dy, "skipped rescale", kind="skip_rescale", unit=u, block=g)
+
+
+def test_fault_rescale_applied_to_the_other_q_block(dy):
+    u, g = a_move(dy)
+    faulted(dy, "rescale of the other q-block", kind="rescale_other", unit=u, block=g)
+
+
+def test_fault_scores_not_shifted_after_a_move(dy):
+    u, g = a_move(dy)
+    faulted(dy, "unshifted scores", kind="no_shift", unit=u, block=g)
+
+
+def test_fault_merge_piece_weighted_with_another_reference(dy):
+    ps = [X.guarded_walk(dy["s"][:, a:b], dy["v"][a:b]) for a, b in ((0, 128), (128, 300))]
+    X.assert_elementwise(X.merge_pieces(ps), dy["want"], "merge")
+    rejects(X.merge_pieces(ps, wrong=(1, 0)), dy["want"], "merge")
+
+
+def test_fault_first_masked_key_admitted_with_a_graded_weight(dy):
+    """Key 300, the first masked key of the ragged tile, as a key its column could hold: weight 2^-9 of the row's sum, beside the graded
+    weights of keys 288 .. 299."""
+    c = X.dyadic_offsets(0, dy["h"], "bounded").double()[X.dyadic_column(dy["h"], dy["rows"])]
+    s = torch.cat([dy["s"], (c - 9.0)[:, None]], 1)
+    v = torch.cat([dy["v"], torch.full((1, 128), 64.0, dtype=torch.float64)], 0)
+    faulted(dy, "admitted masked key", s=s, v=v)
+
+
+def test_fault_two_keys_with_different_exponents_swapped(dy):
+    s = dy["s"].clone()
+    i = 77
+    j1, j2 = 290, int((s[i] != s[i, 290]).nonzero()[0])
+    s[i, j1], s[i, j2] = dy["s"][i, j2], dy["s"][i, j1]
+    msg = faulted(dy, "swapped keys", s=s)
+    assert "(batch 0, row 77," in msg
+
+
+def test_fault_weights_of_one_row_doubled_in_one_tile(dy):
+    for tile in (0, 2, 4):
+        msg = faulted(dy, "doubled weights", kind="double", tile=tile, row=133)
+        assert "(batch 0, row 133," in msg and "1 rows" in msg
+
+
+def test_a_constant_added_to_a_rows_scores_is_invisible_to_the_dyadic_form(dy):
+    """What the form cannot see (a wrong constant in every score of a row cancels in the normalisation); the selector form's margin does."""
+    s = dy["s"].clone()
+    s[40] += 3.0
+    s[200] -= 7.0
+    w = X.guarded_walk(s, dy["v"])
+    X.assert_elementwise(X.finish_rows(w["o"], w["l"]), dy["want"], "shifted row")
+
+
 # ------------------------------------------------------------------------------------------------ attention64
 @pytest.mark.parametrize("N", X.ATTN64_NS)
 @pytest.mark.parametrize("H", X.ATTN64_HS)
@@ -369,6 +590,47 @@ def test_attention64_constructions(N, H):
         if N > 2 and abs(delta) < N - 1:
             off = torch.roll(bias, 1, 1)                                                 # the index formula off by one
             rejects(X.attention64_reference(q, k, v, 0.125, rel_bias=off), want, "bias index")
+
+
+def graded64(N, H, mode):
+    q, k, v, bias = X.graded_attention64(2, H, N, X.shape_seed(2, H, N, 64, 1), mode)
+    return q, k, v, dict(rel_bias=bias, causal=mode == "causal")
+
+
+@pytest.mark.parametrize("N,H,mode", X.attention64_graded_cases())
+def test_attention64_graded_form_grades_and_its_chain_is_the_softmax(N, H, mode):
+    """Natural scores are small integers; the maximum of most 32-key blocks exceeds every block before it (alpha != 1); the restatement
+    with the kernel's rounding points is the fp64 softmax up to the bf16 rounding of its weights (2^-9 of each, |v| <= 64: 0.125) and the
+    final rounding (2^-9 |out| <= 0.125); another mask or a shifted bias index is another answer."""
+    q, k, v, kw = graded64(N, H, mode)
+    s = (q.double().view(2, N, H, 64).transpose(1, 2) @ k.double().view(2, N, H, 64).transpose(1, 2).transpose(-1, -2)) * 0.125
+    assert bool((s == s.round()).all()) and s.abs().max().item() <= 72
+    nb = (N + 31) // 32
+    if nb > 1 and mode == "plain":
+        bm = torch.stack([s[..., kb * 32:(kb + 1) * 32].max(-1).values for kb in range(nb)], -1).cummax(-1).values
+        assert (bm[..., 1:] > bm[..., :-1]).double().mean().item() > 0.5
+    chain = X.attention64_graded_chain(q, k, v, 0.125, **kw)
+    ref = X.attention64_reference(q, k, v, 0.125, **kw)
+    assert (chain.float() - ref.float()).abs().max().item() <= 0.25
+    if N > 2:
+        bias = torch.roll(kw["rel_bias"], 1, 1) if mode == "bias" else None
+        other = X.attention64_graded_chain(q, k, v, 0.125, rel_bias=bias, causal=mode != "causal")
+        assert int(X.mismatches(other, chain, 1).sum()) > 0
+
+
+def test_attention64_graded_share_is_the_measured_sensitivity():
+    """Every exponential of the chain (weights and alpha) and the final row sum moved by one fp32 step, in each of the eight sign
+    combinations: the share of all the cases' output elements whose bf16 value changes under any of them."""
+    n = m = 0
+    for N, H, mode in X.attention64_graded_cases():
+        q, k, v, kw = graded64(N, H, mode)
+        mid = X.attention64_graded_chain(q, k, v, 0.125, **kw)
+        moved = torch.zeros(mid.shape, dtype=torch.bool)
+        for e, s in ((1, 0), (-1, 0), (0, 1), (0, -1), (1, 1), (1, -1), (-1, 1), (-1, -1)):
+            moved |= X.mismatches(X.attention64_graded_chain(q, k, v, 0.125, exp_ulps=e, sum_ulps=s, **kw), mid)
+        n, m = n + mid.numel(), m + int(moved.sum())
+    print(f"attention64 graded: {m} of {n} elements ({m / n:.3e}) change under one fp32 step of the exponentials and the row sum")
+    assert m / n == X.ATTN64_GRADED_SHARE
 
 
 # ------------------------------------------------------------------------------------------------ convolution
