@@ -246,6 +246,16 @@ int tfx_euler_step(const void* v, void* x, void* xin, int64_t ldxin, int32_t C, 
                    const int32_t* step_ptr, int32_t step, tfx_stream stream);
 int tfx_amo_step(const void* v, void* x, void* xin, int64_t ldxin, int32_t C, int64_t rows, const float* coef,
                  const int32_t* step_ptr, int32_t step, const float* noise, tfx_stream stream);
+/* ---- second-order multistep sampler (DESIGN.md section 4 "Multistep sampler"; no reference counterpart): the Adams-Bashforth
+ *      update on the same layout, with the same xin mirror and step index as the two steps above.  Added without a new
+ *      TFX_ABI_VERSION: three new entry points (this one and tfx_dit_step_run_multistep / tfx_dit_step_capture_multistep below), no
+ *      stamped struct and no existing entry point changes.  coef fp32 [n_steps][2], (c0, c1) = coef[2 step], coef[2 step + 1];
+ *      v_prev bf16 [rows, C], the previous step's model output, caller-owned, not NULL and aliasing neither v nor x:
+ *        step 0:  x <- bf16( f32(x) + c0 f32(v) )                          v_prev is not read (a fresh buffer may hold NaN)
+ *        step s:  x <- bf16( f32(x) + (c0 f32(v) + c1 f32(v_prev)) )       each product and sum rounded to fp32 on its own
+ *      then v_prev <- v.  C a positive multiple of 8, rows >= 0 (rows C == 0 launches nothing), ldxin % 8 == 0 and ldxin >= C. */
+int tfx_multistep_step(const void* v, void* x, void* xin, int64_t ldxin, int32_t C, int64_t rows, const float* coef,
+                       const int32_t* step_ptr, int32_t step, void* v_prev, tfx_stream stream);
 
 /* ---- small ops of the conditioning path (CombinedTimestepGuidanceTextProjEmbeddings, D/models/embeddings.py:1327-1339) */
 int tfx_timestep_embedding(const float* t, void* out /* [n,256] = cos|sin */, int32_t n, tfx_stream stream);
@@ -438,6 +448,14 @@ int tfx_dit_step_run(const tfx_step_desc* step, tfx_stream stream);
 int tfx_dit_step_capture(const tfx_step_desc* step, tfx_stream stream, tfx_graph* out);
 int tfx_dit_step_replay(tfx_graph graph, tfx_stream stream);
 int tfx_graph_destroy(tfx_graph graph);
+/* The same step with the second-order multistep update (tfx_multistep_step) where sampler 0 launches tfx_euler_step: `step` is a
+ * sampler 0 descriptor (latents, coef, dit.out; neither dit.seq_len nor dit.euler_gate) whose coef is the multistep table
+ * [n_steps][2]; v_prev bf16 [B*S, out_channels] is the caller's history buffer, aliasing neither latents nor dit.out.  Every
+ * other launch, the phases of the step cache and the graph handle (tfx_dit_step_replay / tfx_graph_destroy) are those of
+ * tfx_dit_step_run / tfx_dit_step_capture; one graph serves every step, step 0 included (the kernel branches on the device's step
+ * index).  The history travels beside the descriptor, so tfx_step_desc and TFX_ABI_VERSION stay as they are. */
+int tfx_dit_step_run_multistep(const tfx_step_desc* step, void* v_prev, tfx_stream stream);
+int tfx_dit_step_capture_multistep(const tfx_step_desc* step, void* v_prev, tfx_stream stream, tfx_graph* out);
 
 /* ---- VAE ends (AutoencoderKL, D/models/autoencoders/autoencoder_kl.py:263-332) on NHWC bf16 activations -------------
  * 3x3 convolution as an implicit GEMM on the MFMA kernel (ResnetBlock2D convs D/models/resnet.py:327-366, Upsample2D

@@ -17,10 +17,10 @@ from PIL import Image
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 from textflux_amd import glyph
 from textflux_amd.pipeline import FluxFillPipeline
-from textflux_amd.schedulers import StochasticRFOvershotDiscreteScheduler
+from textflux_amd.schedulers import FlowMatchMultistepScheduler, StochasticRFOvershotDiscreteScheduler
 from textflux_amd.transformer import FluxTransformer2DModel
 
-scheduler_name = "default"  # "overshoot" or "default" (module-level switch, as in the reference :16)
+scheduler_name = "default"  # "overshoot" or "default" (module-level switch, as in the reference :16); "multistep": --multistep
 BASE = os.environ.get("TEXTFLUX_BASE", "./models/FLUX.1-Fill-dev")
 TRANSFORMER = os.environ.get("TEXTFLUX_TRANSFORMER", "./models/textflux-beta/transformer")
 
@@ -46,6 +46,19 @@ def use_overshoot_sampler(pipe):
     pipe.scheduler = sch
 
 
+def use_multistep_sampler(pipe):
+    """Not in the reference: swap in the second-order multistep sampler (textflux_amd/schedulers.py: FlowMatchMultistepScheduler) on
+    the current scheduler's config.  One model evaluation per step, like Euler; meant for fewer steps, with no quality claim."""
+    pipe.scheduler = FlowMatchMultistepScheduler.from_config(pipe.scheduler.config)
+
+
+def apply_scheduler_name(pipe):
+    if scheduler_name == "overshoot":
+        use_overshoot_sampler(pipe)
+    elif scheduler_name == "multistep":
+        use_multistep_sampler(pipe)
+
+
 def run_inference(image_input, mask_input, words_input, num_steps=50, guidance_scale=30, seed=42, pipe=None, paste_back=None):
     """paste_back (not in the reference): None, or dict(dilate, feather) -- the result is then blended back into the input image under
     the dilated and feathered mask and returned at the INPUT's size (FluxFillPipeline.paste_back) instead of at the pipeline's size.
@@ -65,8 +78,7 @@ def run_inference(image_input, mask_input, words_input, num_steps=50, guidance_s
     print("Generated prompt:", prompt)
     pipe = pipe or load_flux_pipeline()
     generator = torch.Generator(device="cuda").manual_seed(int(seed))
-    if scheduler_name == "overshoot":
-        use_overshoot_sampler(pipe)
+    apply_scheduler_name(pipe)
     out = pipe(height=new_h, width=new_w, image=image, mask_image=mask, num_inference_steps=num_steps,
                generator=generator, max_sequence_length=512, guidance_scale=guidance_scale,
                prompt=glyph.PROMPT_TEMPLATE2, prompt_2=prompt).images[0]
@@ -82,8 +94,7 @@ def run_inference_per_line(image, mask, words_input, num_steps, guidance_scale, 
     cfg = batch_driver._paste_back_cfg(paste_back)
     words = glyph.read_words_from_text(words_input) if isinstance(words_input, str) else list(words_input)
     pipe = pipe or load_flux_pipeline()
-    if scheduler_name == "overshoot":
-        use_overshoot_sampler(pipe)
+    apply_scheduler_name(pipe)
     return per_line.edit_scene(pipe, image, mask, words, cfg, num_inference_steps=num_steps, guidance_scale=guidance_scale, seed=seed)
 
 
@@ -318,14 +329,19 @@ def build_parser():
     ap.add_argument("--steps", type=int, default=30, help="Number of inference steps")
     ap.add_argument("--guidance-scale", type=float, default=30, help="Guidance scale value")
     ap.add_argument("--seed", type=int, default=42, help="Random seed")
+    ap.add_argument("--multistep", action="store_true", help="sample with the second-order multistep sampler instead of Euler (not in "
+                    "the reference; one model evaluation per step, meant for fewer --steps)")
     add_step_cache_args(ap)
     add_paste_back_args(ap)
     return ap
 
 
 def main(argv=None):
+    global scheduler_name
     a = build_parser().parse_args(argv)
     paste_back = paste_back_from_args(a)
+    if a.multistep:
+        scheduler_name = "multistep"
     pipe = apply_step_cache_args(a, load_flux_pipeline()) if a.step_cache is not None or a.step_cache_max_consecutive is not None else None
     process_normal_mode(a.image, a.mask, a.words, a.steps, a.guidance_scale, a.seed, pipe=pipe, paste_back=paste_back)
     report_step_cache(pipe)

@@ -4,7 +4,7 @@
 
     python scripts/run_eval.py --json_path annos.json --original_images_dir imgs/ --weights_path models/textflux/transformer \
         [--output_dir visualization_results --font_path resource/font/Arial-Unicode-Regular.ttf --text_height_ratio 0.1667
-         --steps 30 --guidance_scale 30 --seed 42 --num_gpus 4 --scheduler "" | overshoot]
+         --steps 30 --guidance_scale 30 --seed 42 --num_gpus 4 --scheduler "" | overshoot | multistep]
 
 `annos.json` = {"data_list": [{"img_name": ..., "annotations": [{"text": ..., "polygon": [[x, y], ...]}, ...]}, ...]}; per item
 the first annotation is used: polygon -> white-on-black mask, glyph strip of height int(width * text_height_ratio) stacked on
@@ -64,7 +64,7 @@ def build_parser(lora: bool = False):
     ap.add_argument("--guidance_scale", type=float, default=30, help="Guidance scale")
     ap.add_argument("--seed", type=int, default=42, help="Random seed")
     ap.add_argument("--num_gpus", type=int, default=4, help="Number of GPUs to use")
-    ap.add_argument("--scheduler", type=str, default="overshoot" if lora else "", help='Sampler, None or "overshoot"')
+    ap.add_argument("--scheduler", type=str, default="overshoot" if lora else "", help='Sampler, None, "overshoot" or "multistep" (second order, not in the reference)')
     # not in the reference: batching, and the {image, mask, text} list interface of the earlier rounds
     ap.add_argument("--batch_size", type=int, default=8, help="same-geometry images per pipeline call")
     ap.add_argument("--mixed_pad", type=float, default=0.0, help="let images of different sizes share a batch while at most this share of "
@@ -169,7 +169,7 @@ def load_lora_transformer(lora_weights_path, base_transformer=None, lora_runtime
 
 def main(argv=None, lora: bool = False, script: str = __file__):
     a = build_parser(lora).parse_args(argv)
-    if a.mixed_pad > 0 and a.scheduler == "overshoot":
+    if a.mixed_pad > 0 and a.scheduler in ("overshoot", "multistep"):
         raise SystemExit("--mixed_pad needs the Euler sampler: mixed-geometry batches carry per-sample coefficients only in the fused Euler step")
     if a.step_cache is None and a.step_cache_max_consecutive is not None:
         raise SystemExit("--step_cache_max_consecutive needs --step_cache THR")
@@ -279,6 +279,8 @@ def main(argv=None, lora: bool = False, script: str = __file__):
         pipe = ri.load_flux_pipeline(text_encoders=True)     # every rank encodes its own prompts: no rank-0 straggler
     if a.scheduler == "overshoot":
         ri.use_overshoot_sampler(pipe)
+    elif a.scheduler == "multistep":
+        ri.use_multistep_sampler(pipe)
     pipe.enable_hip_graph(True)
     res = batch_driver.run_items(items, pipe, out_dir, batch_size=a.batch_size, num_inference_steps=steps,
                                  guidance_scale=a.guidance_scale, seed=a.seed, device=f"cuda:{local}", eval_cfg=eval_cfg,

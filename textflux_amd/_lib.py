@@ -147,6 +147,8 @@ SIGNATURES = {
                                c_void_p]),
     "tfx_amo_step": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_int64, c_void_p, c_void_p, c_int32,
                              c_void_p, c_void_p]),
+    "tfx_multistep_step": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_int64, c_void_p, c_void_p, c_int32,
+                                   c_void_p, c_void_p]),
     "tfx_timestep_embedding": (c_int, [c_void_p, c_void_p, c_int32, c_void_p]),
     "tfx_silu": (c_int, [c_void_p, c_void_p, c_int64, c_void_p]),
     "tfx_add": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
@@ -162,6 +164,8 @@ SIGNATURES = {
     "tfx_dit_step_capture": (c_int, [C.POINTER(StepDesc), c_void_p, C.POINTER(c_void_p)]),
     "tfx_dit_step_replay": (c_int, [c_void_p, c_void_p]),
     "tfx_graph_destroy": (c_int, [c_void_p]),
+    "tfx_dit_step_run_multistep": (c_int, [C.POINTER(StepDesc), c_void_p, c_void_p]),
+    "tfx_dit_step_capture_multistep": (c_int, [C.POINTER(StepDesc), c_void_p, c_void_p, C.POINTER(c_void_p)]),
     "tfx_step_cache_metric": (c_int, [c_void_p, c_int64, c_int64, C.POINTER(StepCache), c_int32, c_int32, c_int32, c_void_p]),
     "tfx_step_cache_store": (c_int, [c_void_p, c_int64, c_int64, C.POINTER(StepCache), c_int32, c_int32, c_int32, c_void_p]),
     "tfx_step_cache_apply": (c_int, [c_void_p, c_int64, c_int64, C.POINTER(StepCache), c_int32, c_int32, c_int32, c_void_p]),

@@ -557,10 +557,13 @@ def _run_items(items, pipe, out_dir, batch_size, num_inference_steps, guidance_s
     if mixed_pad > 0:            # refused before anything is prepared or encoded, not batch by batch inside the loop
         if not hasattr(pipe, "call_mixed"):
             raise ValueError("mixed_pad > 0 needs a pipeline with call_mixed (FluxFillPipeline)")
-        from .schedulers import StochasticRFOvershotDiscreteScheduler
+        from .schedulers import FlowMatchMultistepScheduler, StochasticRFOvershotDiscreteScheduler
         if isinstance(getattr(pipe, "scheduler", None), StochasticRFOvershotDiscreteScheduler):
             raise NotImplementedError("mixed_pad > 0 needs the Euler sampler: mixed-geometry batches carry per-sample coefficients only "
                                       "in the fused Euler step (the AMO sampler's are per step); use mixed_pad=0")
+        if isinstance(getattr(pipe, "scheduler", None), FlowMatchMultistepScheduler):
+            raise NotImplementedError("mixed_pad > 0 needs the Euler sampler: mixed-geometry batches carry per-sample coefficients only "
+                                      "in the fused Euler step (the multistep sampler's are per step); use mixed_pad=0")
     rank = dist.get_rank() if dist.is_initialized() else 0
     world = dist.get_world_size() if dist.is_initialized() else 1
     per_line = bool(paste_back and paste_back.get("per_line"))

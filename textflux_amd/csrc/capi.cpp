@@ -274,6 +274,11 @@ int tfx_amo_step(const void* v, void* x, void* xin, int64_t ldxin, int32_t C, in
   return sched_step(true, v, x, xin, ldxin, C, rows, coef, step_ptr, step, noise, S(stream));
 }
 
+int tfx_multistep_step(const void* v, void* x, void* xin, int64_t ldxin, int32_t C, int64_t rows, const float* coef,
+                       const int32_t* step_ptr, int32_t step, void* v_prev, tfx_stream stream) {
+  return multistep_step(v, x, xin, ldxin, C, rows, coef, step_ptr, step, v_prev, S(stream));
+}
+
 int tfx_timestep_embedding(const float* t, void* out, int32_t n, tfx_stream stream) {
   if (!t || !out) return fail("tfx_timestep_embedding: null pointer");
   return timestep_embedding(t, out, n, S(stream));
@@ -660,10 +665,14 @@ int step_check(const tfx_step_desc* s) {
   return step_cache_view(*s, a);
 }
 
-// the scheduler update behind the final projection and the cursor advance: the end of a whole step and of both tails
-int step_finish(const tfx_step_desc& s, hipStream_t st, const StepCacheArgs* store) {
-  if (s.sampler != 2) {                                         // sampler 2: the update happened in proj_out's epilogue
-    const int64_t rows = (int64_t)s.dit.B * s.dit.S;
+// the scheduler update behind the final projection and the cursor advance: the end of a whole step and of both tails.
+// v_prev: the multistep entry points' history buffer -- the second-order update then stands where sampler 0 launches Euler's
+int step_finish(const tfx_step_desc& s, hipStream_t st, const StepCacheArgs* store, void* v_prev) {
+  const int64_t rows = (int64_t)s.dit.B * s.dit.S;
+  if (v_prev) {
+    TRY(multistep_step(s.dit.out, s.latents, const_cast<void*>(s.dit.xin), s.dit.in_channels, s.dit.out_channels, rows, s.coef,
+                       s.step_ptr, 0, v_prev, st));
+  } else if (s.sampler != 2) {                                  // sampler 2: the update happened in proj_out's epilogue
     TRY(sched_step(s.sampler == 1, s.dit.out, s.latents, const_cast<void*>(s.dit.xin), s.dit.in_channels, s.dit.out_channels, rows,
                    s.coef, s.step_ptr, 0, s.noise, st));
   }
@@ -678,11 +687,11 @@ int step_forward(const tfx_step_desc& s, int first, int last, int flags, hipStre
   return tfx_dit_forward(&d, (tfx_stream)st);
 }
 
-int step_enqueue(const tfx_step_desc& s, hipStream_t st) {
+int step_enqueue(const tfx_step_desc& s, hipStream_t st, void* v_prev) {
   if (s.phase == 0) {
     TRY(select_step(s.mod_table, s.mod_cur, s.mod_step_elems, s.step_ptr, st));
     TRY(tfx_dit_forward(&s.dit, (tfx_stream)st));
-    return step_finish(s, st, nullptr);
+    return step_finish(s, st, nullptr, v_prev);
   }
   StepCacheArgs a;
   TRY(step_cache_view(s, a));
@@ -696,29 +705,31 @@ int step_enqueue(const tfx_step_desc& s, hipStream_t st) {
       return step_cache_metric(a, st);
     case 2:   // computed tail: the rest of the whole step, then r and f_prev
       TRY(step_forward(s, 1, -1, 1, st));
-      return step_finish(s, st, &a);
+      return step_finish(s, st, &a, v_prev);
     default:  // 3, cached tail: the last computed step's residual stands in for blocks [1, n)
       TRY(step_cache_apply(a, st));
       TRY(step_forward(s, nblk, nblk, 1, st));
-      return step_finish(s, st, nullptr);
+      return step_finish(s, st, nullptr, v_prev);
   }
 }
-}  // namespace
 
-int tfx_dit_step_run(const tfx_step_desc* s, tfx_stream stream) {
+// the multistep entry points take sampler 0's descriptor (latents, coef, dit.out; neither seq_len nor euler_gate) and the history
+int step_check_multistep(const tfx_step_desc* s, const void* v_prev) {
   TRY(step_check(s));
-  return step_enqueue(*s, S(stream));
+  if (s->sampler != 0) return fail("tfx_dit_step (multistep): sampler must be 0: the second-order update stands where the unfused Euler launch does");
+  if (!v_prev) return fail("tfx_dit_step (multistep): the history buffer v_prev is null");
+  if (v_prev == s->latents || v_prev == s->dit.out) return fail("tfx_dit_step (multistep): v_prev must not alias latents or dit.out");
+  return 0;
 }
 
-int tfx_dit_step_capture(const tfx_step_desc* s, tfx_stream stream, tfx_graph* out) {
-  TRY(step_check(s));
+int step_capture(const tfx_step_desc* s, void* v_prev, tfx_stream stream, tfx_graph* out) {
   if (!out) return fail("tfx_dit_step_capture: null output handle");
   if (!stream) return fail("tfx_dit_step_capture: the NULL stream cannot be captured; pass a created stream");
   hipStream_t st = S(stream);
   (void)attention_w4_prepare(st);   // the attention kernel's scratch (of this stream) cannot be allocated inside a capture
   hipError_t e = hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal);
   if (e != hipSuccess) return fail("tfx_dit_step_capture: hipStreamBeginCapture: %s", hipGetErrorString(e));
-  const int rc = step_enqueue(*s, st);
+  const int rc = step_enqueue(*s, st, v_prev);
   hipGraph_t g = nullptr;
   e = hipStreamEndCapture(st, &g);
   if (rc) { if (g) (void)hipGraphDestroy(g); return rc; }    // last error already set by the failing launcher
@@ -728,6 +739,27 @@ int tfx_dit_step_capture(const tfx_step_desc* s, tfx_stream stream, tfx_graph* o
   if (e != hipSuccess) { (void)hipGraphDestroy(g); return fail("tfx_dit_step_capture: hipGraphInstantiate: %s", hipGetErrorString(e)); }
   *out = new StepGraph{g, x};
   return 0;
+}
+}  // namespace
+
+int tfx_dit_step_run(const tfx_step_desc* s, tfx_stream stream) {
+  TRY(step_check(s));
+  return step_enqueue(*s, S(stream), nullptr);
+}
+
+int tfx_dit_step_capture(const tfx_step_desc* s, tfx_stream stream, tfx_graph* out) {
+  TRY(step_check(s));
+  return step_capture(s, nullptr, stream, out);
+}
+
+int tfx_dit_step_run_multistep(const tfx_step_desc* s, void* v_prev, tfx_stream stream) {
+  TRY(step_check_multistep(s, v_prev));
+  return step_enqueue(*s, S(stream), v_prev);
+}
+
+int tfx_dit_step_capture_multistep(const tfx_step_desc* s, void* v_prev, tfx_stream stream, tfx_graph* out) {
+  TRY(step_check_multistep(s, v_prev));
+  return step_capture(s, v_prev, stream, out);
 }
 
 int tfx_dit_step_replay(tfx_graph graph, tfx_stream stream) {

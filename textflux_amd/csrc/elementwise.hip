@@ -260,6 +260,45 @@ __global__ __launch_bounds__(256) void sched_step_kernel(const bf16_t* __restric
   }
 }
 
+// Second-order multistep (Adams-Bashforth) update, same layout and xin mirror as sched_step_kernel; no reference counterpart
+// (DESIGN.md section 4 "Multistep sampler").  coef fp32 [n_steps][2]:
+//   step 0:  x' = bf16( f32(x) + c0 * f32(v) )                       v_prev is NOT read: a fresh history holds arbitrary bits
+//   step s:  x' = bf16( f32(x) + (c0 * f32(v) + c1 * f32(v_prev)) )  (NaN included, and 0 * NaN would poison the state)
+// every product and sum rounded on its own (_rn, no FMA), one rounding to bf16; then v_prev <- v.  The branch on s is uniform.
+__global__ __launch_bounds__(256) void multistep_step_kernel(const bf16_t* __restrict__ v, bf16_t* __restrict__ x,
+                                                             bf16_t* __restrict__ xin, int64_t ldxin, int C,
+                                                             int64_t nchunks, const float* __restrict__ coef,
+                                                             const int* __restrict__ step_ptr, int step,
+                                                             bf16_t* __restrict__ v_prev) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= nchunks) return;
+  const int s = step_ptr ? *step_ptr : step;
+  const float c0 = coef[2 * s];
+  const u32x4 vraw = *reinterpret_cast<const u32x4*>(v + i * 8);
+  float vv[8], xx[8], o[8];
+  unpack8(vraw, vv);
+  unpack8(*reinterpret_cast<const u32x4*>(x + i * 8), xx);
+  if (s == 0) {
+#pragma unroll
+    for (int j = 0; j < 8; ++j) o[j] = __fadd_rn(xx[j], __fmul_rn(c0, vv[j]));
+  } else {
+    const float c1 = coef[2 * s + 1];
+    float pp[8];
+    unpack8(*reinterpret_cast<const u32x4*>(v_prev + i * 8), pp);
+#pragma unroll
+    for (int j = 0; j < 8; ++j) o[j] = __fadd_rn(xx[j], __fadd_rn(__fmul_rn(c0, vv[j]), __fmul_rn(c1, pp[j])));
+  }
+  const u32x4 packed = pack8(o);
+  *reinterpret_cast<u32x4*>(v_prev + i * 8) = vraw;
+  *reinterpret_cast<u32x4*>(x + i * 8) = packed;
+  if (xin) {
+    const int64_t e0 = i * 8;
+    const int64_t row = e0 / C;
+    const int col = (int)(e0 - row * C);
+    *reinterpret_cast<u32x4*>(xin + row * ldxin + col) = packed;
+  }
+}
+
 // Sinusoidal timestep embedding, flip_sin_to_cos=True, downscale_freq_shift=0, dim 256, fp32 -> bf16
 // (get_timestep_embedding, D/models/embeddings.py:27-78 as configured at :1322).  out[n, 256] = cos | sin.
 __global__ void timestep_embedding_kernel(const float* __restrict__ t, bf16_t* __restrict__ out, int n) {
@@ -592,6 +631,23 @@ int sched_step(bool amo, const void* v, void* x, void* xin, int64_t ldxin, int C
                                                    step_ptr, step, nullptr);
   }
   return check_launch("sched_step");
+}
+
+int multistep_step(const void* v, void* x, void* xin, int64_t ldxin, int C, int64_t rows, const float* coef,
+                   const int* step_ptr, int step, void* v_prev, hipStream_t st) {
+  if (C <= 0 || C % 8) return fail("multistep_step: C must be a positive multiple of 8");
+  if (rows < 0) return fail("multistep_step: negative row count");
+  if (xin && (ldxin % 8 || ldxin < C)) return fail("multistep_step: ldxin must be a multiple of 8 and >= C");   // 16-byte stores into xin rows
+  const int64_t nch = rows * C / 8;
+  if (nch == 0) return 0;                               // nothing to update: the pointers of empty tensors mean nothing
+  if (!v || !x || !coef) return fail("multistep_step: null pointer");
+  if (!v_prev) return fail("multistep_step: the history buffer v_prev is null");
+  const char *h = (const char*)v_prev, *pv = (const char*)v, *px = (const char*)x;
+  const int64_t bytes = nch * 16;
+  if ((h < pv + bytes && pv < h + bytes) || (h < px + bytes && px < h + bytes)) return fail("multistep_step: v_prev must not alias v or x");
+  multistep_step_kernel<<<dim3((unsigned)((nch + 255) / 256)), 256, 0, st>>>((const bf16_t*)v, (bf16_t*)x, (bf16_t*)xin, ldxin, C, nch,
+                                                                             coef, step_ptr, step, (bf16_t*)v_prev);
+  return check_launch("multistep_step");
 }
 
 int timestep_embedding(const float* t, void* out, int n, hipStream_t st) {

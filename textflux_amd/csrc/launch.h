@@ -191,6 +191,9 @@ int rmsnorm_rope_tab(void* buf, int64_t ld, int64_t bstride, int q_off, int k_of
                      const float* sinT, int64_t tab_bstride, float eps, hipStream_t st);
 int sched_step(bool amo, const void* v, void* x, void* xin, int64_t ldxin, int C, int64_t rows, const float* coef,
                const int* step_ptr, int step, const float* noise, hipStream_t st);
+// second-order multistep update (coef fp32 [n_steps][2]); v_prev bf16 [rows, C] is read from step 1 on and then holds v
+int multistep_step(const void* v, void* x, void* xin, int64_t ldxin, int C, int64_t rows, const float* coef,
+                   const int* step_ptr, int step, void* v_prev, hipStream_t st);
 int timestep_embedding(const float* t, void* out, int n, hipStream_t st);
 int silu_bf16(const void* a, void* out, int64_t n, hipStream_t st);
 int add_bf16(const void* a, const void* b, void* out, int64_t n, hipStream_t st);

@@ -392,6 +392,24 @@ def amo_step_(v: torch.Tensor, x: torch.Tensor, coef: torch.Tensor, noise: torch
     return x
 
 
+def multistep_step_(v: torch.Tensor, x: torch.Tensor, coef: torch.Tensor, v_prev: torch.Tensor, step: int = 0,
+                    step_ptr: Optional[torch.Tensor] = None, xin: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Second-order multistep update of x in place (tfx_multistep_step): coef fp32 [n, 2]; v_prev, the previous step's model
+    output, is read from step 1 on and holds v afterwards."""
+    _chk_dev(v, x, coef, v_prev, step_ptr, xin)
+    if v.dtype != BF16 or x.dtype != BF16 or v_prev.dtype != BF16 or (xin is not None and xin.dtype != BF16):
+        raise TypeError("multistep_step_: the HIP scheduler kernels operate on bf16 latents / model outputs")
+    assert v.is_contiguous() and x.is_contiguous() and v_prev.is_contiguous() and coef.is_contiguous() and coef.dtype == torch.float32
+    assert v.numel() == x.numel() == v_prev.numel()
+    Cc = x.shape[-1]
+    rows = x.numel() // Cc if Cc else 0
+    if step_ptr is None and not 0 <= step < coef.numel() // 2:
+        raise ValueError(f"multistep_step_: step {step} outside the coefficient table of {coef.numel() // 2} steps")
+    L.check(L.lib().tfx_multistep_step(v.data_ptr(), x.data_ptr(), _p(xin), xin.stride(-2) if xin is not None else 0, Cc,
+                                       rows, coef.data_ptr(), _p(step_ptr), step, v_prev.data_ptr(), _stream()), "multistep_step")
+    return x
+
+
 def timestep_embedding(t: torch.Tensor) -> torch.Tensor:
     _chk_dev(t)
     t = t.contiguous().float()

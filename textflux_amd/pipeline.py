@@ -24,7 +24,7 @@ import torch
 
 from . import ops, step_loop
 from .image_processor import VaeImageProcessor
-from .schedulers import FlowMatchEulerDiscreteScheduler, StochasticRFOvershotDiscreteScheduler
+from .schedulers import FlowMatchEulerDiscreteScheduler, FlowMatchMultistepScheduler, StochasticRFOvershotDiscreteScheduler
 from .transformer import EULER_PAD, FluxTransformer2DModel
 
 BF16 = torch.bfloat16
@@ -532,10 +532,11 @@ class FluxFillPipeline:
         ses = tr.session(B, S, prompt_embeds.shape[1])
         ses.set_conditioning(prompt_embeds.to(dev, BF16), text_ids, latent_image_ids)
         is_amo = isinstance(sch, StochasticRFOvershotDiscreteScheduler)
+        multistep = isinstance(sch, FlowMatchMultistepScheduler)    # unfused: its [n, 2] table, the history in the session
         coef = sch.coef_table(dev, BF16)
         # Euler update in proj_out's epilogue (north_star: "flow-matching Euler step fused into the residual add"); the latents then
         # live in xin[:, :, :C].  Not with a step callback (it wants the latents as a tensor every step) and not for AMO.
-        fuse = self.fuse_euler_step and not is_amo and callback_on_step_end is None and C == EULER_PAD and tr.out_channels == C
+        fuse = self.fuse_euler_step and not is_amo and not multistep and callback_on_step_end is None and C == EULER_PAD and tr.out_channels == C
         mod = self._modulation_table(timesteps, B, pooled, guidance_scale, coef[:n] if fuse else None)
         # x_embedder input [latents | masked_image_latents]; the step keeps columns 0..C-1 up to date
         latents = latents.to(dev, BF16).contiguous()
@@ -556,7 +557,7 @@ class FluxFillPipeline:
                     prompt_embeds = new_pe
                     ses.set_conditioning(prompt_embeds.to(dev, BF16), text_ids, latent_image_ids)
         sch._step_index = 0
-        return step_loop.denoise(self, ses, mod, latents, coef, n, progress_bar, is_amo, fuse, amo_noise, on_step)
+        return step_loop.denoise(self, ses, mod, latents, coef, n, progress_bar, is_amo, fuse, amo_noise, on_step, multistep)
 
     def enable_hip_graph(self, on: bool = True):
         """Replay ONE captured hipGraph per denoising step (device-side step cursor: modulation rows and scheduler
@@ -792,6 +793,10 @@ class FluxFillPipeline:
         if isinstance(sch, StochasticRFOvershotDiscreteScheduler):
             raise NotImplementedError("call_mixed: the AMO sampler is not supported in mixed-geometry batches (its coefficients and "
                                       "noise are per step, not per sample); use the Euler scheduler or __call__")
+        if isinstance(sch, FlowMatchMultistepScheduler):
+            raise NotImplementedError("call_mixed: the multistep sampler is not supported in mixed-geometry batches (its coefficients "
+                                      "are per step, not per sample, and its update is not fused into proj_out); use the Euler "
+                                      "scheduler or __call__")
         if not isinstance(sch, FlowMatchEulerDiscreteScheduler) or not self.fuse_euler_step:
             raise NotImplementedError("call_mixed needs FlowMatchEulerDiscreteScheduler with fuse_euler_step: only the Euler update "
                                       "fused into proj_out carries per-sample coefficients")
@@ -922,7 +927,7 @@ class FluxFillPipeline:
         mu = calculate_shift(image_seq_len, sc.base_image_seq_len, sc.max_image_seq_len, sc.base_shift, sc.max_shift)
         timesteps, num_inference_steps = retrieve_timesteps(self.scheduler, num_inference_steps, device, sigmas=sigmas, mu=mu)
         self._num_timesteps = len(timesteps)
-        engine = isinstance(self.scheduler, (FlowMatchEulerDiscreteScheduler, StochasticRFOvershotDiscreteScheduler))
+        engine = isinstance(self.scheduler, (FlowMatchEulerDiscreteScheduler, StochasticRFOvershotDiscreteScheduler, FlowMatchMultistepScheduler))
         with self.progress_bar(total=num_inference_steps) as bar:
             if engine:
                 latents = self._engine_loop(latents, masked_image_latents, prompt_embeds, pooled_prompt_embeds, text_ids,

@@ -9,6 +9,8 @@ Host side (this file): the sigma / timestep tables and the per-step scalar coeff
 precision and order as the reference.  Device side: the state update itself runs in libtextflux_hip.so
 (`tfx_euler_step` / `tfx_amo_step`); the AMO sampler's per-step `min(tensor, 1)` host syncs (reference :313, :342)
 disappear because the coefficient table is built once from the host copy of the sigmas.
+
+* FlowMatchMultistepScheduler             no reference counterpart: second-order multistep on the Euler class's grid (`tfx_multistep_step`)
 """
 from __future__ import annotations
 
@@ -255,3 +257,58 @@ class StochasticRFOvershotDiscreteScheduler(_FlowMatchBase):
         if not return_dict:
             return (prev, predicted_x1)
         return SimpleNamespace(prev_sample=prev, predicted_x1=predicted_x1)
+
+
+class FlowMatchMultistepScheduler(_FlowMatchBase):
+    """Second-order multistep (Adams-Bashforth) sampler on the flow-matching sigma grid: one model evaluation per step, like Euler,
+    plus the previous step's model output.  No reference counterpart and opt-in (DESIGN.md section 4 "Multistep sampler"): with
+    h_i = sigma_{i+1} - sigma_i,
+
+        x_1     = x_0 + h_0 v_0
+        x_{i+1} = x_i + h_i (1 + h_i / (2 h_{i-1})) v_i - h_i^2 / (2 h_{i-1}) v_{i-1}
+
+    -- no division by sigma, so the last step onto sigma = 0 is like any other.  Same config keys, `set_timesteps` (with the f32
+    cast before the shift) and `step` protocol as FlowMatchEulerDiscreteScheduler; `order` counts model evaluations per step.  The
+    scheduler owns the history: it is reset by `set_timesteps`, and a caller that replaces `sample` between steps leaves it as it is."""
+    _keys = FlowMatchEulerDiscreteScheduler._keys
+    order = 1
+
+    def __init__(self, *args, **kwargs):
+        euler = FlowMatchEulerDiscreteScheduler(*args, **kwargs)       # the same keys, defaults and refusals
+        self.config = _Config(**euler.config.to_dict())
+        self._init_tables()
+        self._v_prev: Optional[torch.Tensor] = None
+
+    def set_timesteps(self, num_inference_steps: int = None, device: Union[str, torch.device] = None,
+                      sigmas: Optional[List[float]] = None, mu: Optional[float] = None):
+        FlowMatchEulerDiscreteScheduler.set_timesteps(self, num_inference_steps, device, sigmas=sigmas, mu=mu)
+        self._v_prev = None
+
+    def coef_table(self, device, state_dtype=torch.bfloat16) -> torch.Tensor:
+        """fp32 [n, 2]: row 0 = (h_0, 0), row i = (h_i (1 + h_i / (2 h_{i-1})), -h_i^2 / (2 h_{i-1})), evaluated in float64 from the
+        host copy of the fp32 sigmas and rounded to fp32 once.  (state_dtype: the siblings' signature; the coefficients stay fp32.)"""
+        if self._coef is None or self._coef.device != torch.device(device):
+            h = np.diff(self._sigmas_host.numpy().astype(np.float64))
+            c = np.zeros((len(h), 2), dtype=np.float64)
+            c[0, 0] = h[0]
+            c[1:, 0] = h[1:] * (1.0 + h[1:] / (2.0 * h[:-1]))
+            c[1:, 1] = -h[1:] * h[1:] / (2.0 * h[:-1])
+            self._coef = torch.from_numpy(c.astype(np.float32)).to(device)
+        return self._coef
+
+    def step(self, model_output: torch.Tensor, timestep, sample: torch.Tensor, generator=None, return_dict: bool = True):
+        self._check_timestep(timestep)
+        if model_output.dtype != torch.bfloat16 or sample.dtype != torch.bfloat16:
+            raise TypeError("multistep_step_: the HIP scheduler kernels operate on bf16 latents / model outputs")
+        if self.step_index is None:
+            self._init_step_index(timestep)
+        v = model_output.contiguous()
+        hist = self._v_prev
+        if hist is None or hist.shape != v.shape or hist.dtype != v.dtype or hist.device != v.device:
+            hist = self._v_prev = torch.empty_like(v)
+        prev = sample.clone().contiguous()
+        ops.multistep_step_(v, prev, self.coef_table(sample.device), hist, step=self._step_index)
+        self._step_index += 1
+        if not return_dict:
+            return (prev,)
+        return SimpleNamespace(prev_sample=prev)
