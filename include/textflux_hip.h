@@ -256,6 +256,19 @@ int tfx_amo_step(const void* v, void* x, void* xin, int64_t ldxin, int32_t C, in
  *      then v_prev <- v.  C a positive multiple of 8, rows >= 0 (rows C == 0 launches nothing), ldxin % 8 == 0 and ldxin >= C. */
 int tfx_multistep_step(const void* v, void* x, void* xin, int64_t ldxin, int32_t C, int64_t rows, const float* coef,
                        const int32_t* step_ptr, int32_t step, void* v_prev, tfx_stream stream);
+/* ---- known-region blend (DESIGN.md section 4 "Known-region sampling"; the loop of FluxInpaintPipeline, D/pipelines/flux/
+ *      pipeline_flux_inpaint.py:974-984, with scale_noise of scheduling_flow_match_euler_discrete.py:174): behind a sampler update,
+ *      what lies outside the mask becomes the original's latents noised to the next sigma.  x bf16 [rows, C] with row pitch ldx
+ *      (elements); x0, noise, mask bf16 [rows, C] contiguous; keep_sigma fp32 [n_steps], entry i = sigma_{i+1} ALREADY ROUNDED TO
+ *      BF16, a NEGATIVE entry = "no noise" (the reference's last step); s = keep_sigma[*step_ptr or step].  Every op in fp32 on bf16
+ *      operands, rounded to bf16 on its own:
+ *        a = bf16(s noise)  u = bf16(1 - s)  b = bf16(u x0)  p = bf16(a + b)   (s < 0: p = x0)
+ *        w = bf16(1 - mask) c = bf16(w p)    d = bf16(mask x)                  x <- bf16(c + d)
+ *      written to x and, when xin != NULL, into columns [0, C) of xin (row pitch ldxin).  No shortcut for binary masks.  Refused: C
+ *      not a positive multiple of 8; ldx (ldxin) not a multiple of 8 or < C; a null or not 16-byte aligned pointer; x0 / noise / mask
+ *      overlapping x.  rows == 0 launches nothing.  No new TFX_ABI_VERSION: new entry points only. */
+int tfx_known_region_blend(void* x, int64_t ldx, const void* x0, const void* noise, const void* mask, int32_t C, int64_t rows,
+                           const float* keep_sigma, const int32_t* step_ptr, int32_t step, void* xin, int64_t ldxin, tfx_stream stream);
 
 /* ---- small ops of the conditioning path (CombinedTimestepGuidanceTextProjEmbeddings, D/models/embeddings.py:1327-1339) */
 int tfx_timestep_embedding(const float* t, void* out /* [n,256] = cos|sin */, int32_t n, tfx_stream stream);
@@ -456,6 +469,22 @@ int tfx_graph_destroy(tfx_graph graph);
  * index).  The history travels beside the descriptor, so tfx_step_desc and TFX_ABI_VERSION stay as they are. */
 int tfx_dit_step_run_multistep(const tfx_step_desc* step, void* v_prev, tfx_stream stream);
 int tfx_dit_step_capture_multistep(const tfx_step_desc* step, void* v_prev, tfx_stream stream, tfx_graph* out);
+/* The step with what travels beside the descriptor (tfx_step_desc and TFX_ABI_VERSION stay as they are).  v_prev != NULL: the
+ * multistep update, exactly tfx_dit_step_run_multistep (sampler 0 descriptor).  keep_x0 / keep_noise / keep_mask (bf16 [B*S,
+ * out_channels]) and keep_sigma (fp32 [n_steps]), all set or all NULL: tfx_known_region_blend behind the sampler update and in front
+ * of the step cache's store pass and the cursor advance -- on dit.xin with pitch in_channels for sampler 2 (the fused Euler keeps
+ * the latents there), else on latents, mirrored into dit.xin.  Every sampler, phases 0 / 2 / 3, one graph for every step.  Refused:
+ * a NULL extra, a partial keep set, keep_* with dit.seq_len, keep_* overlapping latents, dit.out, dit.xin or v_prev.  All fields
+ * NULL is the plain step. */
+typedef struct tfx_step_extra {
+  void* v_prev;
+  const void* keep_x0;
+  const void* keep_noise;
+  const void* keep_mask;
+  const float* keep_sigma;
+} tfx_step_extra;
+int tfx_dit_step_run_ex(const tfx_step_desc* step, const tfx_step_extra* extra, tfx_stream stream);
+int tfx_dit_step_capture_ex(const tfx_step_desc* step, const tfx_step_extra* extra, tfx_stream stream, tfx_graph* out);
 
 /* ---- VAE ends (AutoencoderKL, D/models/autoencoders/autoencoder_kl.py:263-332) on NHWC bf16 activations -------------
  * 3x3 convolution as an implicit GEMM on the MFMA kernel (ResnetBlock2D convs D/models/resnet.py:327-366, Upsample2D
@@ -705,6 +734,15 @@ int tfx_warp_grid_u8(const void* in, void* out, void* coverage, int32_t B, int32
  * then _pack_latents), t = ty * (W/16) + tx, row stride ld. */
 int tfx_pack_mask(const void* mask, int32_t mask_dtype, void* out, int32_t B, int32_t H, int32_t W, int32_t mask_batch,
                   int32_t binarize, int64_t ld, int32_t col0, tfx_stream stream);
+/* The packed latent mask of known-region sampling (DESIGN.md section 4 "Known-region sampling"): mask_u8 [B, H, W] uint8 (8-byte
+ * aligned, H and W multiples of 16) -> out bf16 [B, (H/16)(W/16), C] of 1.0 / 0.0, out[b, t, c*4 + py*2+px] = m(2ty+py, 2tx+px) for
+ * every c: _pack_latents of the latent-resolution mask repeated over the latent channels (FluxInpaintPipeline.prepare_mask_latents).
+ *   mode 0 (nearest, the reference's F.interpolate): m(ly, lx) = mask[8 ly, 8 lx] >= 128; grow must be 0
+ *   mode 1 (cover): m = 1 if any pixel of the 8x8 blocks of latent pixels [ly-grow, ly+grow] x [lx-grow, lx+grow] (clipped to the
+ *           image) is >= 128, 0 <= grow <= 8: a latent pixel counts as known only when nothing masked touches it or its neighbours
+ * C a positive multiple of 8 (64 for the Fill model). */
+int tfx_keep_mask_pack(const void* mask_u8, void* out, int32_t B, int32_t H, int32_t W, int32_t C, int32_t mode, int32_t grow,
+                       tfx_stream stream);
 /* moments [B, h, w, 2L] NHWC bf16 (mean | logvar: the encoder's conv_out), eps [B, L, h, w] f32 / bf16 or NULL (mode) ->
  * out[b, t, col0 + c*4 + py*2+px] = ((mean + exp(0.5 clamp(logvar, -30, 20)) * eps) - shift) * scale, every intermediate
  * rounded to bf16 as the reference's tensor ops do (D/models/autoencoders/vae.py:781-802, P:1528-1530, 1743-1748). */

@@ -59,8 +59,9 @@ def apply_scheduler_name(pipe):
         use_multistep_sampler(pipe)
 
 
-def run_inference(image_input, mask_input, words_input, num_steps=50, guidance_scale=30, seed=42, pipe=None, paste_back=None):
-    """paste_back (not in the reference): None, or dict(dilate, feather) -- the result is then blended back into the input image under
+def run_inference(image_input, mask_input, words_input, num_steps=50, guidance_scale=30, seed=42, pipe=None, paste_back=None, known=None):
+    """known (not in the reference): None, or dict(keep_known=..., strength=...) handed to the pipeline call (known-region sampling).
+    paste_back (not in the reference): None, or dict(dilate, feather) -- the result is then blended back into the input image under
     the dilated and feathered mask and returned at the INPUT's size (FluxFillPipeline.paste_back) instead of at the pipeline's size.
     seamless (True or dict(smooth, max_shift)) and grain (True or dict(ring, max_sigma, strength, min_pixels, seed)) in it are handed to
     that paste.
@@ -69,7 +70,7 @@ def run_inference(image_input, mask_input, words_input, num_steps=50, guidance_s
     image = (Image.open(image_input) if isinstance(image_input, str) else image_input).convert("RGB")
     mask = (Image.open(mask_input) if isinstance(mask_input, str) else mask_input).convert("RGB")
     if paste_back is not None and paste_back.get("per_line"):
-        return run_inference_per_line(image, mask, words_input, num_steps, guidance_scale, seed, pipe, paste_back)[0]
+        return run_inference_per_line(image, mask, words_input, num_steps, guidance_scale, seed, pipe, paste_back, known)[0]
     image_in, mask_in = image, mask
     new_w, new_h = glyph.pipe_size(image)
     image, mask = image.resize((new_w, new_h)), mask.resize((new_w, new_h))
@@ -81,21 +82,22 @@ def run_inference(image_input, mask_input, words_input, num_steps=50, guidance_s
     apply_scheduler_name(pipe)
     out = pipe(height=new_h, width=new_w, image=image, mask_image=mask, num_inference_steps=num_steps,
                generator=generator, max_sequence_length=512, guidance_scale=guidance_scale,
-               prompt=glyph.PROMPT_TEMPLATE2, prompt_2=prompt).images[0]
+               prompt=glyph.PROMPT_TEMPLATE2, prompt_2=prompt, **(known or {})).images[0]
     if paste_back is None:
         return out
     pasted = pipe.paste_back(image_in, out, mask_in, **{k: v for k, v in paste_back.items() if k in ("dilate", "feather", "seamless", "grain") and v is not None})
     return Image.fromarray(pasted[0].cpu().numpy())
 
 
-def run_inference_per_line(image, mask, words_input, num_steps, guidance_scale, seed, pipe, paste_back):
+def run_inference_per_line(image, mask, words_input, num_steps, guidance_scale, seed, pipe, paste_back, known=None):
     """-> (the scene with every line pasted in, [each line's raw canvas]): run_inference's per_line path."""
     from textflux_amd import batch_driver, per_line
     cfg = batch_driver._paste_back_cfg(paste_back)
     words = glyph.read_words_from_text(words_input) if isinstance(words_input, str) else list(words_input)
     pipe = pipe or load_flux_pipeline()
     apply_scheduler_name(pipe)
-    return per_line.edit_scene(pipe, image, mask, words, cfg, num_inference_steps=num_steps, guidance_scale=guidance_scale, seed=seed)
+    return per_line.edit_scene(pipe, image, mask, words, cfg, num_inference_steps=num_steps, guidance_scale=guidance_scale, seed=seed,
+                               **(dict(call_kw=known) if known else {}))
 
 
 def add_paste_back_args(ap):
@@ -259,6 +261,31 @@ def paste_back_from_args(a):
     return pb
 
 
+def add_known_region_args(ap):
+    """Not in the reference's Fill callers: known-region sampling (FluxFillPipeline.__call__: strength, keep_known)."""
+    ap.add_argument("--strength", type=float, default=1.0, metavar="F", help="start the loop from the noised input and run int(steps * F) steps (1.0: from pure noise, all steps)")
+    ap.add_argument("--keep_known", action="store_true", help="after every step, replace the latents outside the mask by the input's, noised to the next sigma")
+    ap.add_argument("--keep_known_mode", choices=("nearest", "cover"), default="nearest", help="how the pixel mask becomes the latent mask: "
+                    "its value at every 8th pixel, or 'cover': masked wherever anything masked touches the latent pixel")
+    ap.add_argument("--keep_known_grow", type=int, default=0, metavar="N", help="with cover: also mask the N neighbouring latent pixels (0..8)")
+
+
+def known_region_from_args(a):
+    """-> None (the defaults: today's call), or the keyword arguments of the pipeline call"""
+    if not a.keep_known and (a.keep_known_mode != "nearest" or a.keep_known_grow != 0):
+        raise SystemExit("--keep_known_mode / --keep_known_grow need --keep_known")
+    if not 0.0 <= a.strength <= 1.0:
+        raise SystemExit(f"--strength must lie in [0, 1], got {a.strength}")
+    if a.keep_known and (a.keep_known_grow < 0 or a.keep_known_grow > 8 or (a.keep_known_mode == "nearest" and a.keep_known_grow)):
+        raise SystemExit("--keep_known_grow is 0 with --keep_known_mode nearest and 0..8 with cover")
+    known = {}
+    if a.keep_known:
+        known["keep_known"] = dict(mode=a.keep_known_mode, grow=a.keep_known_grow)
+    if a.strength != 1.0:
+        known["strength"] = a.strength
+    return known or None
+
+
 def add_step_cache_args(ap):
     """Not in the reference: the first-block step cache (FluxFillPipeline.enable_step_cache)."""
     ap.add_argument("--step_cache", type=float, default=None, metavar="THR", help="skip the block stack on steps whose first-block residual "
@@ -280,8 +307,9 @@ def report_step_cache(pipe):
         print(f"Step cache: {sum(1 for r in rep if r['skipped'])} of {len(rep)} steps skipped")
 
 
-def process_normal_mode(image_path, mask_path, words_path, steps, guidance_scale, seed, pipe=None, out_dir="outputs_my", paste_back=None):
-    """paste_back: None, or dict(dilate, feather, region) as in batch_driver.run_items -- the saved crop is then the original scene at
+def process_normal_mode(image_path, mask_path, words_path, steps, guidance_scale, seed, pipe=None, out_dir="outputs_my", paste_back=None,
+                        known=None):
+    """known: None, or dict(keep_known, strength) for every pipeline call (known_region_from_args).  paste_back: None, or dict(dilate, feather, region) as in batch_driver.run_items -- the saved crop is then the original scene at
     its original size with the edit pasted in; with a region only that part of the scene goes through the pipeline."""
     scene, mask = Image.open(image_path).convert("RGB"), Image.open(mask_path).convert("RGB")
     words = glyph.read_words_from_text(words_path)
@@ -289,7 +317,7 @@ def process_normal_mode(image_path, mask_path, words_path, steps, guidance_scale
     if paste_back is not None and paste_back.get("per_line"):
         print(f"Using per-line region editing ({len(words)} text lines)")
         pipe = pipe or load_flux_pipeline()
-        cropped, fulls = run_inference_per_line(scene, mask, words, steps, guidance_scale, seed, pipe, paste_back)
+        cropped, fulls = run_inference_per_line(scene, mask, words, steps, guidance_scale, seed, pipe, paste_back, known)
         os.makedirs(os.path.join(out_dir, "crop"), exist_ok=True)
         n = 1
         while os.path.exists(os.path.join(out_dir, f"result_{n:04d}.png")):
@@ -307,7 +335,8 @@ def process_normal_mode(image_path, mask_path, words_path, steps, guidance_scale
     print("Using multi-line text rendering mode" if len(words) > 1 else "Using single-line text rendering mode")
     combined, cmask, meta = glyph.compose(scene, mask, words)
     print("Starting inference...")
-    full = run_inference(combined, cmask, words_path, num_steps=steps, guidance_scale=guidance_scale, seed=seed, pipe=pipe)
+    full = run_inference(combined, cmask, words_path, num_steps=steps, guidance_scale=guidance_scale, seed=seed, pipe=pipe,
+                         **(dict(known=known) if known else {}))
     cropped = full.crop(glyph.crop_box(full.size, meta))
     if work is not None:
         cropped = batch_driver._paste_into_original(pipe or load_flux_pipeline(), work, cropped, cfg)
@@ -331,6 +360,7 @@ def build_parser():
     ap.add_argument("--seed", type=int, default=42, help="Random seed")
     ap.add_argument("--multistep", action="store_true", help="sample with the second-order multistep sampler instead of Euler (not in "
                     "the reference; one model evaluation per step, meant for fewer --steps)")
+    add_known_region_args(ap)
     add_step_cache_args(ap)
     add_paste_back_args(ap)
     return ap
@@ -340,10 +370,12 @@ def main(argv=None):
     global scheduler_name
     a = build_parser().parse_args(argv)
     paste_back = paste_back_from_args(a)
+    known = known_region_from_args(a)
     if a.multistep:
         scheduler_name = "multistep"
     pipe = apply_step_cache_args(a, load_flux_pipeline()) if a.step_cache is not None or a.step_cache_max_consecutive is not None else None
-    process_normal_mode(a.image, a.mask, a.words, a.steps, a.guidance_scale, a.seed, pipe=pipe, paste_back=paste_back)
+    process_normal_mode(a.image, a.mask, a.words, a.steps, a.guidance_scale, a.seed, pipe=pipe, paste_back=paste_back,
+                        **(dict(known=known) if known else {}))
     report_step_cache(pipe)
     print("\nProcessing completed successfully!")
 

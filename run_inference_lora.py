@@ -48,6 +48,7 @@ def build_parser():
     ap.add_argument("--lora_runtime", action="store_true", help="keep the LoRA as an unmerged runtime adapter instead of merging it at load")
     ap.add_argument("--lora_scale", type=float, default=1.0, help="strength of the LoRA (1.0 = as trained)")
     ap.add_argument("--multistep", action="store_true", help="sample with the second-order multistep sampler (not in the reference)")
+    base.add_known_region_args(ap)
     base.add_step_cache_args(ap)
     base.add_paste_back_args(ap)
     return ap
@@ -56,9 +57,11 @@ def build_parser():
 def main(argv=None):
     a = build_parser().parse_args(argv)
     paste_back = base.paste_back_from_args(a)
+    known = base.known_region_from_args(a)
     base.scheduler_name = "multistep" if a.multistep else scheduler_name
     pipe = base.apply_step_cache_args(a, load_flux_pipeline(a.lora_runtime, a.lora_scale))
-    base.process_normal_mode(a.image, a.mask, a.words, a.steps, a.guidance_scale, a.seed, pipe=pipe, paste_back=paste_back)
+    base.process_normal_mode(a.image, a.mask, a.words, a.steps, a.guidance_scale, a.seed, pipe=pipe, paste_back=paste_back,
+                             **(dict(known=known) if known else {}))
     base.report_step_cache(pipe)
     print("\nProcessing completed successfully!")
 

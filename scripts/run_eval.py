@@ -4,7 +4,8 @@
 
     python scripts/run_eval.py --json_path annos.json --original_images_dir imgs/ --weights_path models/textflux/transformer \
         [--output_dir visualization_results --font_path resource/font/Arial-Unicode-Regular.ttf --text_height_ratio 0.1667
-         --steps 30 --guidance_scale 30 --seed 42 --num_gpus 4 --scheduler "" | overshoot | multistep]
+         --steps 30 --guidance_scale 30 --seed 42 --num_gpus 4 --scheduler "" | overshoot | multistep
+         --strength 1.0 --keep_known --keep_known_mode nearest | cover --keep_known_grow 0]
 
 `annos.json` = {"data_list": [{"img_name": ..., "annotations": [{"text": ..., "polygon": [[x, y], ...]}, ...]}, ...]}; per item
 the first annotation is used: polygon -> white-on-black mask, glyph strip of height int(width * text_height_ratio) stacked on
@@ -69,6 +70,12 @@ def build_parser(lora: bool = False):
     ap.add_argument("--batch_size", type=int, default=8, help="same-geometry images per pipeline call")
     ap.add_argument("--mixed_pad", type=float, default=0.0, help="let images of different sizes share a batch while at most this share of "
                     "its transformer rows is padding (Euler sampler only; 0 = same-geometry batches only)")
+    ap.add_argument("--strength", type=float, default=1.0, metavar="F", help="known-region sampling: start from the noised canvas and run int(steps * F) steps")
+    ap.add_argument("--keep_known", action="store_true", help="known-region sampling: after every step, replace the latents outside the mask "
+                    "by the canvas's, noised to the next sigma")
+    ap.add_argument("--keep_known_mode", choices=("nearest", "cover"), default="nearest", help="latent mask from the pixel mask: its value at "
+                    "every 8th pixel, or masked wherever anything masked touches the latent pixel (with --keep_known)")
+    ap.add_argument("--keep_known_grow", type=int, default=0, metavar="N", help="with cover: also mask the N neighbouring latent pixels, 0..8")
     ap.add_argument("--step_cache", type=float, default=None, metavar="THR", help="first-block step cache: skip the block stack on steps whose "
                     "first-block residual moved by less than THR relative to the last computed step (no default: the value is a property "
                     "of the checkpoint; 0 never skips)")
@@ -171,6 +178,19 @@ def main(argv=None, lora: bool = False, script: str = __file__):
     a = build_parser(lora).parse_args(argv)
     if a.mixed_pad > 0 and a.scheduler in ("overshoot", "multistep"):
         raise SystemExit("--mixed_pad needs the Euler sampler: mixed-geometry batches carry per-sample coefficients only in the fused Euler step")
+    if not a.keep_known and (a.keep_known_mode != "nearest" or a.keep_known_grow != 0):
+        raise SystemExit("--keep_known_mode / --keep_known_grow need --keep_known")
+    if not 0.0 <= a.strength <= 1.0:
+        raise SystemExit(f"--strength must lie in [0, 1], got {a.strength}")
+    if a.keep_known and (a.keep_known_grow < 0 or a.keep_known_grow > 8 or (a.keep_known_mode == "nearest" and a.keep_known_grow)):
+        raise SystemExit("--keep_known_grow is 0 with --keep_known_mode nearest and 0..8 with cover")
+    if (a.keep_known or a.strength != 1.0) and a.mixed_pad > 0:
+        raise SystemExit("--keep_known / --strength do not serve mixed-geometry batches (--mixed_pad)")
+    known = {}
+    if a.keep_known:
+        known["keep_known"] = dict(mode=a.keep_known_mode, grow=a.keep_known_grow)
+    if a.strength != 1.0:
+        known["strength"] = a.strength
     if a.step_cache is None and a.step_cache_max_consecutive is not None:
         raise SystemExit("--step_cache_max_consecutive needs --step_cache THR")
     if a.step_cache is not None and a.mixed_pad > 0:
@@ -284,7 +304,7 @@ def main(argv=None, lora: bool = False, script: str = __file__):
     pipe.enable_hip_graph(True)
     res = batch_driver.run_items(items, pipe, out_dir, batch_size=a.batch_size, num_inference_steps=steps,
                                  guidance_scale=a.guidance_scale, seed=a.seed, device=f"cuda:{local}", eval_cfg=eval_cfg,
-                                 mixed_pad=a.mixed_pad, paste_back=paste_back,
+                                 mixed_pad=a.mixed_pad, paste_back=paste_back, **known,
                                  step_cache=None if a.step_cache is None else dict(threshold=a.step_cache, max_consecutive=a.step_cache_max_consecutive))
     if "steps_total" in res:
         print(f"[rank {rank}] step cache: {res['steps_skipped']} of {res['steps_total']} steps skipped")

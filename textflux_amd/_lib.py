@@ -112,6 +112,11 @@ class StepDesc(C.Structure):
                 ("cache", C.POINTER(StepCache)), ("phase", c_int32)]
 
 
+class StepExtra(C.Structure):
+    """tfx_step_extra: what travels beside tfx_step_desc through the *_ex step entry points (not stamped: no struct of the ABI stamp grows)"""
+    _fields_ = [("v_prev", c_void_p), ("keep_x0", c_void_p), ("keep_noise", c_void_p), ("keep_mask", c_void_p), ("keep_sigma", c_void_p)]
+
+
 # name -> (restype, argtypes); every symbol include/textflux_hip.h declares must appear here (tests check it)
 SIGNATURES = {
     "tfx_version": (c_char_p, []),
@@ -149,6 +154,8 @@ SIGNATURES = {
                              c_void_p, c_void_p]),
     "tfx_multistep_step": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_int64, c_void_p, c_void_p, c_int32,
                                    c_void_p, c_void_p]),
+    "tfx_known_region_blend": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int32, c_int64, c_void_p, c_void_p, c_int32,
+                                       c_void_p, c_int64, c_void_p]),
     "tfx_timestep_embedding": (c_int, [c_void_p, c_void_p, c_int32, c_void_p]),
     "tfx_silu": (c_int, [c_void_p, c_void_p, c_int64, c_void_p]),
     "tfx_add": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
@@ -166,6 +173,8 @@ SIGNATURES = {
     "tfx_graph_destroy": (c_int, [c_void_p]),
     "tfx_dit_step_run_multistep": (c_int, [C.POINTER(StepDesc), c_void_p, c_void_p]),
     "tfx_dit_step_capture_multistep": (c_int, [C.POINTER(StepDesc), c_void_p, c_void_p, C.POINTER(c_void_p)]),
+    "tfx_dit_step_run_ex": (c_int, [C.POINTER(StepDesc), C.POINTER(StepExtra), c_void_p]),
+    "tfx_dit_step_capture_ex": (c_int, [C.POINTER(StepDesc), C.POINTER(StepExtra), c_void_p, C.POINTER(c_void_p)]),
     "tfx_step_cache_metric": (c_int, [c_void_p, c_int64, c_int64, C.POINTER(StepCache), c_int32, c_int32, c_int32, c_void_p]),
     "tfx_step_cache_store": (c_int, [c_void_p, c_int64, c_int64, C.POINTER(StepCache), c_int32, c_int32, c_int32, c_void_p]),
     "tfx_step_cache_apply": (c_int, [c_void_p, c_int64, c_int64, C.POINTER(StepCache), c_int32, c_int32, c_int32, c_void_p]),
@@ -198,6 +207,7 @@ SIGNATURES = {
     "tfx_warp_perspective_u8": (c_int, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p]),
     "tfx_warp_grid_u8": (c_int, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p, c_int32, c_void_p,
                                  c_void_p]),
+    "tfx_keep_mask_pack": (c_int, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p]),
     "tfx_pack_mask": (c_int, [c_void_p, c_int32, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_int64, c_int32,
                               c_void_p]),
     "tfx_vae_sample_pack": (c_int, [c_void_p, c_void_p, c_int32, c_void_p, c_int32, c_int32, c_int32, c_int32, c_float,

@@ -477,7 +477,8 @@ def run_items(items: Sequence[Dict[str, Any]], pipe, out_dir: Optional[str], bat
               guidance_scale: float = 30.0, seed: int = 42, device="cuda", loader: Optional[Callable] = None,
               save: Optional[Callable] = None, max_sequence_length: int = 512, eval_cfg: Optional[Dict[str, Any]] = None,
               encode: str = "auto", save_full: Optional[Callable] = None, mixed_pad: float = 0.0,
-              step_cache: Optional[Dict[str, Any]] = None, paste_back: Optional[Dict[str, Any]] = None) -> Dict[str, Any]:
+              step_cache: Optional[Dict[str, Any]] = None, paste_back: Optional[Dict[str, Any]] = None, keep_known=None,
+              strength: float = 1.0) -> Dict[str, Any]:
     """Runs the whole list; returns {"done": [indices this rank wrote], "failed": [...], "all_done": [...] on rank 0,
     "encode": "local" | "rank0"}.  `pipe` needs `encode_prompt(prompt, prompt_2, ...)` and the FluxFillPipeline `__call__`.
     encode: "local" = every rank encodes the T5 prompts of its own batches (needs a T5 on every rank), "rank0" = rank 0
@@ -523,7 +524,19 @@ def run_items(items: Sequence[Dict[str, Any]], pipe, out_dir: Optional[str], bat
     as hashed white grain under the same alpha, anchored at scene positions.  The bytes outside the grown mask stay the original's.
     With grain=dict(spectrum=True | dict(max_blur, luma), ...) (DESIGN.md section 4 "Grain spectrum") the grain is blurred over
     neighbouring pixels (a 3-tap kernel whose side tap is at most max_blur / 256, default 64) and, with luma (default True), shared
-    between the channels, as far as the scene's own noise on the ring is."""
+    between the channels, as far as the scene's own noise on the ring is.
+    keep_known=True | dict(mode, grow) and strength (DESIGN.md section 4 "Known-region sampling"): handed to every pipeline call as
+    they are -- the canvas outside the mask is then kept in the latents at every step, and the loop runs int(steps * strength) steps
+    from the noised canvas.  Paste-back runs after decode, unchanged.  Not with mixed_pad > 0."""
+    known = {}
+    if keep_known:
+        known["keep_known"] = keep_known
+    if strength != 1.0:
+        if strength < 0 or strength > 1:
+            raise ValueError(f"The value of strength should in [0.0, 1.0] but is {strength}")
+        known["strength"] = strength
+    if known and mixed_pad > 0:
+        raise NotImplementedError("keep_known / strength (known-region sampling) do not serve mixed-geometry batches (mixed_pad > 0)")
     if paste_back is not None:       # refused before anything is prepared or encoded
         if mixed_pad > 0:
             raise NotImplementedError("paste_back does not serve mixed-geometry batches (mixed_pad > 0)")
@@ -544,15 +557,16 @@ def run_items(items: Sequence[Dict[str, Any]], pipe, out_dir: Optional[str], bat
         pipe.enable_step_cache(**step_cache)
         try:
             return _run_items(items, pipe, out_dir, batch_size, num_inference_steps, guidance_scale, seed, device, loader, save,
-                              max_sequence_length, eval_cfg, encode, save_full, mixed_pad, count_steps=True, paste_back=paste_back)
+                              max_sequence_length, eval_cfg, encode, save_full, mixed_pad, count_steps=True, paste_back=paste_back, known=known)
         finally:
             pipe.disable_step_cache()
     return _run_items(items, pipe, out_dir, batch_size, num_inference_steps, guidance_scale, seed, device, loader, save,
-                      max_sequence_length, eval_cfg, encode, save_full, mixed_pad, paste_back=paste_back)
+                      max_sequence_length, eval_cfg, encode, save_full, mixed_pad, paste_back=paste_back, known=known)
 
 
 def _run_items(items, pipe, out_dir, batch_size, num_inference_steps, guidance_scale, seed, device, loader, save, max_sequence_length,
-               eval_cfg, encode, save_full, mixed_pad, count_steps: bool = False, paste_back: Optional[Dict[str, Any]] = None) -> Dict[str, Any]:
+               eval_cfg, encode, save_full, mixed_pad, count_steps: bool = False, paste_back: Optional[Dict[str, Any]] = None,
+               known: Optional[Dict[str, Any]] = None) -> Dict[str, Any]:
     steps_skipped = steps_total = 0
     if mixed_pad > 0:            # refused before anything is prepared or encoded, not batch by batch inside the loop
         if not hasattr(pipe, "call_mixed"):
@@ -666,6 +680,7 @@ def _run_items(items, pipe, out_dir, batch_size, num_inference_steps, guidance_s
             same_box = all(bx == boxes[0] for bx in boxes)      # one crop window for the whole batch: applied on the device
             kw = (dict(output_crop=boxes[0]) if same_box and not keep_full and not mine.mixed and getattr(pipe, "supports_output_crop", False)
                   else {})
+            call_kw = dict(kw, **(known or {}))     # keep_known / strength: only when given, so that other pipelines' calls stay as they were
             img_in, mask_in = _batch_inputs(mine.items, device)
             if mine.mixed:          # items of different sizes: one padded forward per step, every item at its own size
                 images = pipe.call_mixed(image=img_in, mask_image=mask_in, sizes=[w.size for w in mine.items],
@@ -676,7 +691,7 @@ def _run_items(items, pipe, out_dir, batch_size, num_inference_steps, guidance_s
                 images = pipe(height=mine.size[1], width=mine.size[0], image=img_in,
                               mask_image=mask_in, num_inference_steps=num_inference_steps, generator=gens,
                               max_sequence_length=max_sequence_length, guidance_scale=guidance_scale,
-                              prompt_embeds=pe_mine[:n], pooled_prompt_embeds=pooled1.expand(n, -1).contiguous(), **kw).images
+                              prompt_embeds=pe_mine[:n], pooled_prompt_embeds=pooled1.expand(n, -1).contiguous(), **call_kw).images
             if count_steps:
                 rep = getattr(pipe, "step_cache_report", None) or []
                 steps_total += len(rep)

@@ -279,6 +279,11 @@ int tfx_multistep_step(const void* v, void* x, void* xin, int64_t ldxin, int32_t
   return multistep_step(v, x, xin, ldxin, C, rows, coef, step_ptr, step, v_prev, S(stream));
 }
 
+int tfx_known_region_blend(void* x, int64_t ldx, const void* x0, const void* noise, const void* mask, int32_t C, int64_t rows,
+                           const float* keep_sigma, const int32_t* step_ptr, int32_t step, void* xin, int64_t ldxin, tfx_stream stream) {
+  return known_region_blend(x, ldx, x0, noise, mask, C, rows, keep_sigma, step_ptr, step, xin, ldxin, S(stream));
+}
+
 int tfx_timestep_embedding(const float* t, void* out, int32_t n, tfx_stream stream) {
   if (!t || !out) return fail("tfx_timestep_embedding: null pointer");
   return timestep_embedding(t, out, n, S(stream));
@@ -482,6 +487,11 @@ int tfx_warp_grid_u8(const void* in, void* out, void* coverage, int32_t B, int32
   if (!in || !out || !grid || !taps) return fail("tfx_warp_grid_u8: null pointer");
   return warp_grid_u8(in, out, coverage, B, H, W, C, out_h, out_w, grid, shift, taps, S(stream));
 }
+int tfx_keep_mask_pack(const void* mask_u8, void* out, int32_t B, int32_t H, int32_t W, int32_t C, int32_t mode, int32_t grow,
+                       tfx_stream stream) {
+  return keep_mask_pack(mask_u8, out, B, H, W, C, mode, grow, S(stream));
+}
+
 int tfx_pack_mask(const void* mask, int32_t mask_dtype, void* out, int32_t B, int32_t H, int32_t W, int32_t mask_batch,
                   int32_t binarize, int64_t ld, int32_t col0, tfx_stream stream) {
   if (!mask || !out) return fail("tfx_pack_mask: null pointer");
@@ -666,15 +676,25 @@ int step_check(const tfx_step_desc* s) {
 }
 
 // the scheduler update behind the final projection and the cursor advance: the end of a whole step and of both tails.
-// v_prev: the multistep entry points' history buffer -- the second-order update then stands where sampler 0 launches Euler's
-int step_finish(const tfx_step_desc& s, hipStream_t st, const StepCacheArgs* store, void* v_prev) {
+// ex.v_prev: the multistep history buffer -- the second-order update then stands where sampler 0 launches Euler's.  ex.keep_*: the
+// known-region blend, behind the update and in front of the step cache's store pass and the cursor advance (it reads the cursor)
+int step_finish(const tfx_step_desc& s, hipStream_t st, const StepCacheArgs* store, const tfx_step_extra& ex) {
   const int64_t rows = (int64_t)s.dit.B * s.dit.S;
+  void* v_prev = ex.v_prev;
   if (v_prev) {
     TRY(multistep_step(s.dit.out, s.latents, const_cast<void*>(s.dit.xin), s.dit.in_channels, s.dit.out_channels, rows, s.coef,
                        s.step_ptr, 0, v_prev, st));
   } else if (s.sampler != 2) {                                  // sampler 2: the update happened in proj_out's epilogue
     TRY(sched_step(s.sampler == 1, s.dit.out, s.latents, const_cast<void*>(s.dit.xin), s.dit.in_channels, s.dit.out_channels, rows,
                    s.coef, s.step_ptr, 0, s.noise, st));
+  }
+  if (ex.keep_mask) {
+    if (s.sampler == 2)                                          // the fused Euler form keeps the latents in xin[:, :out_channels]
+      TRY(known_region_blend(const_cast<void*>(s.dit.xin), s.dit.in_channels, ex.keep_x0, ex.keep_noise, ex.keep_mask, s.dit.out_channels,
+                             rows, ex.keep_sigma, s.step_ptr, 0, nullptr, 0, st));
+    else
+      TRY(known_region_blend(s.latents, s.dit.out_channels, ex.keep_x0, ex.keep_noise, ex.keep_mask, s.dit.out_channels, rows,
+                             ex.keep_sigma, s.step_ptr, 0, const_cast<void*>(s.dit.xin), s.dit.in_channels, st));
   }
   if (store) TRY(step_cache_store(*store, st));
   return advance_step(s.step_ptr, st);
@@ -687,11 +707,11 @@ int step_forward(const tfx_step_desc& s, int first, int last, int flags, hipStre
   return tfx_dit_forward(&d, (tfx_stream)st);
 }
 
-int step_enqueue(const tfx_step_desc& s, hipStream_t st, void* v_prev) {
+int step_enqueue(const tfx_step_desc& s, hipStream_t st, const tfx_step_extra& ex) {
   if (s.phase == 0) {
     TRY(select_step(s.mod_table, s.mod_cur, s.mod_step_elems, s.step_ptr, st));
     TRY(tfx_dit_forward(&s.dit, (tfx_stream)st));
-    return step_finish(s, st, nullptr, v_prev);
+    return step_finish(s, st, nullptr, ex);
   }
   StepCacheArgs a;
   TRY(step_cache_view(s, a));
@@ -705,11 +725,11 @@ int step_enqueue(const tfx_step_desc& s, hipStream_t st, void* v_prev) {
       return step_cache_metric(a, st);
     case 2:   // computed tail: the rest of the whole step, then r and f_prev
       TRY(step_forward(s, 1, -1, 1, st));
-      return step_finish(s, st, &a, v_prev);
+      return step_finish(s, st, &a, ex);
     default:  // 3, cached tail: the last computed step's residual stands in for blocks [1, n)
       TRY(step_cache_apply(a, st));
       TRY(step_forward(s, nblk, nblk, 1, st));
-      return step_finish(s, st, nullptr, v_prev);
+      return step_finish(s, st, nullptr, ex);
   }
 }
 
@@ -722,14 +742,39 @@ int step_check_multistep(const tfx_step_desc* s, const void* v_prev) {
   return 0;
 }
 
-int step_capture(const tfx_step_desc* s, void* v_prev, tfx_stream stream, tfx_graph* out) {
+// the _ex entry points: v_prev as above; keep_* all set or all NULL, not with dit.seq_len, aliasing no buffer the step writes
+int step_check_ex(const tfx_step_desc* s, const tfx_step_extra* ex) {
+  if (!ex) return fail("tfx_dit_step (ex): null tfx_step_extra (tfx_dit_step_run / tfx_dit_step_capture take none)");
+  if (ex->v_prev) TRY(step_check_multistep(s, ex->v_prev)); else TRY(step_check(s));
+  const void* keep[4] = {ex->keep_x0, ex->keep_noise, ex->keep_mask, ex->keep_sigma};
+  const int set = (keep[0] != nullptr) + (keep[1] != nullptr) + (keep[2] != nullptr) + (keep[3] != nullptr);
+  if (set == 0) return 0;
+  if (set != 4) return fail("tfx_dit_step (ex): keep_x0, keep_noise, keep_mask and keep_sigma must be all set or all NULL");
+  const tfx_dit_desc& d = s->dit;
+  if (d.seq_len) return fail("tfx_dit_step (ex): the known-region blend cannot serve a mixed-geometry batch (dit.seq_len): its buffers are [B * S, C] without padding rows");
+  if (!d.xin) return fail("tfx_dit_step (ex): dit.xin is null");
+  const int64_t rows = (int64_t)d.B * d.S, kb = rows * d.out_channels * 2;
+  const struct { const void* p; int64_t bytes; } written[4] = {{s->latents, kb}, {d.out, kb}, {d.xin, rows * d.in_channels * 2}, {ex->v_prev, kb}};
+  for (const void* k : keep) {
+    const char* p = (const char*)k;
+    const int64_t pb = k == ex->keep_sigma ? 4 : kb;
+    for (const auto& w : written) {
+      const char* q = (const char*)w.p;
+      if (q && (p == q || (p < q + w.bytes && q < p + pb)))
+        return fail("tfx_dit_step (ex): keep_x0, keep_noise, keep_mask and keep_sigma must not alias latents, dit.out, dit.xin or v_prev");
+    }
+  }
+  return 0;
+}
+
+int step_capture(const tfx_step_desc* s, const tfx_step_extra& ex, tfx_stream stream, tfx_graph* out) {
   if (!out) return fail("tfx_dit_step_capture: null output handle");
   if (!stream) return fail("tfx_dit_step_capture: the NULL stream cannot be captured; pass a created stream");
   hipStream_t st = S(stream);
   (void)attention_w4_prepare(st);   // the attention kernel's scratch (of this stream) cannot be allocated inside a capture
   hipError_t e = hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal);
   if (e != hipSuccess) return fail("tfx_dit_step_capture: hipStreamBeginCapture: %s", hipGetErrorString(e));
-  const int rc = step_enqueue(*s, st, v_prev);
+  const int rc = step_enqueue(*s, st, ex);
   hipGraph_t g = nullptr;
   e = hipStreamEndCapture(st, &g);
   if (rc) { if (g) (void)hipGraphDestroy(g); return rc; }    // last error already set by the failing launcher
@@ -744,22 +789,36 @@ int step_capture(const tfx_step_desc* s, void* v_prev, tfx_stream stream, tfx_gr
 
 int tfx_dit_step_run(const tfx_step_desc* s, tfx_stream stream) {
   TRY(step_check(s));
-  return step_enqueue(*s, S(stream), nullptr);
+  return step_enqueue(*s, S(stream), tfx_step_extra{});
 }
 
 int tfx_dit_step_capture(const tfx_step_desc* s, tfx_stream stream, tfx_graph* out) {
   TRY(step_check(s));
-  return step_capture(s, nullptr, stream, out);
+  return step_capture(s, tfx_step_extra{}, stream, out);
 }
 
 int tfx_dit_step_run_multistep(const tfx_step_desc* s, void* v_prev, tfx_stream stream) {
   TRY(step_check_multistep(s, v_prev));
-  return step_enqueue(*s, S(stream), v_prev);
+  tfx_step_extra ex{};
+  ex.v_prev = v_prev;
+  return step_enqueue(*s, S(stream), ex);
 }
 
 int tfx_dit_step_capture_multistep(const tfx_step_desc* s, void* v_prev, tfx_stream stream, tfx_graph* out) {
   TRY(step_check_multistep(s, v_prev));
-  return step_capture(s, v_prev, stream, out);
+  tfx_step_extra ex{};
+  ex.v_prev = v_prev;
+  return step_capture(s, ex, stream, out);
+}
+
+int tfx_dit_step_run_ex(const tfx_step_desc* s, const tfx_step_extra* ex, tfx_stream stream) {
+  TRY(step_check_ex(s, ex));
+  return step_enqueue(*s, S(stream), *ex);
+}
+
+int tfx_dit_step_capture_ex(const tfx_step_desc* s, const tfx_step_extra* ex, tfx_stream stream, tfx_graph* out) {
+  TRY(step_check_ex(s, ex));
+  return step_capture(s, *ex, stream, out);
 }
 
 int tfx_dit_step_replay(tfx_graph graph, tfx_stream stream) {

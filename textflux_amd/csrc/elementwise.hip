@@ -299,6 +299,49 @@ __global__ __launch_bounds__(256) void multistep_step_kernel(const bf16_t* __res
   }
 }
 
+// Known-region blend behind a sampler update (FluxInpaintPipeline's loop, D/pipelines/flux/pipeline_flux_inpaint.py:974-984, with
+// FlowMatchEulerDiscreteScheduler.scale_noise, scheduling_flow_match_euler_discrete.py:174; DESIGN.md section 4 "Known-region
+// sampling").  x [rows, C] with row pitch ldx (the fused Euler form keeps the latents in xin[:, :C]); x0, noise, mask contiguous.
+// s = keep_sigma[step], sigma_{i+1} already rounded to bf16; every torch op of the reference rounds to bf16 on its own:
+//   a = bf16(s n)   u = bf16(1 - s)   b = bf16(u x0)   p = bf16(a + b)      (s < 0, the last step: p = x0, no arithmetic)
+//   w = bf16(1 - m) c = bf16(w p)     d = bf16(m x)    x' = bf16(c + d)
+// The literal formula also for binary masks: 0 * x keeps x's sign in a -0, and the tests pin it.
+__global__ __launch_bounds__(256) void known_region_blend_kernel(bf16_t* __restrict__ x, int64_t ldx, const bf16_t* __restrict__ x0,
+                                                                 const bf16_t* __restrict__ noise, const bf16_t* __restrict__ mask,
+                                                                 int C, int64_t nchunks, const float* __restrict__ keep_sigma,
+                                                                 const int* __restrict__ step_ptr, int step,
+                                                                 bf16_t* __restrict__ xin, int64_t ldxin) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= nchunks) return;
+  const float s = keep_sigma[step_ptr ? *step_ptr : step];
+  const int64_t e0 = i * 8;
+  const int64_t row = e0 / C;
+  const int col = (int)(e0 - row * C);
+  bf16_t* xp = x + row * ldx + col;
+  float xx[8], zz[8], mm[8], p[8], o[8];
+  unpack8(*reinterpret_cast<const u32x4*>(xp), xx);
+  unpack8(*reinterpret_cast<const u32x4*>(x0 + e0), zz);
+  unpack8(*reinterpret_cast<const u32x4*>(mask + e0), mm);
+  if (s < 0.f) {
+#pragma unroll
+    for (int j = 0; j < 8; ++j) p[j] = zz[j];
+  } else {
+    float nn[8];
+    unpack8(*reinterpret_cast<const u32x4*>(noise + e0), nn);
+    const float u = round_bf(__fsub_rn(1.0f, s));
+#pragma unroll
+    for (int j = 0; j < 8; ++j) p[j] = round_bf(__fadd_rn(round_bf(__fmul_rn(s, nn[j])), round_bf(__fmul_rn(u, zz[j]))));
+  }
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    const float w = round_bf(__fsub_rn(1.0f, mm[j]));
+    o[j] = __fadd_rn(round_bf(__fmul_rn(w, p[j])), round_bf(__fmul_rn(mm[j], xx[j])));
+  }
+  const u32x4 packed = pack8(o);
+  *reinterpret_cast<u32x4*>(xp) = packed;
+  if (xin) *reinterpret_cast<u32x4*>(xin + row * ldxin + col) = packed;
+}
+
 // Sinusoidal timestep embedding, flip_sin_to_cos=True, downscale_freq_shift=0, dim 256, fp32 -> bf16
 // (get_timestep_embedding, D/models/embeddings.py:27-78 as configured at :1322).  out[n, 256] = cos | sin.
 __global__ void timestep_embedding_kernel(const float* __restrict__ t, bf16_t* __restrict__ out, int n) {
@@ -648,6 +691,29 @@ int multistep_step(const void* v, void* x, void* xin, int64_t ldxin, int C, int6
   multistep_step_kernel<<<dim3((unsigned)((nch + 255) / 256)), 256, 0, st>>>((const bf16_t*)v, (bf16_t*)x, (bf16_t*)xin, ldxin, C, nch,
                                                                              coef, step_ptr, step, (bf16_t*)v_prev);
   return check_launch("multistep_step");
+}
+
+int known_region_blend(void* x, int64_t ldx, const void* x0, const void* noise, const void* mask, int C, int64_t rows,
+                       const float* keep_sigma, const int* step_ptr, int step, void* xin, int64_t ldxin, hipStream_t st) {
+  if (C <= 0 || C % 8) return fail("known_region_blend: C must be a positive multiple of 8");
+  if (rows < 0) return fail("known_region_blend: negative row count");
+  if (ldx % 8 || ldx < C) return fail("known_region_blend: ldx must be a multiple of 8 and >= C");             // 16-byte accesses to x rows
+  if (xin && (ldxin % 8 || ldxin < C)) return fail("known_region_blend: ldxin must be a multiple of 8 and >= C");
+  const int64_t nch = rows * C / 8;
+  if (nch == 0) return 0;                               // nothing to blend: the pointers of empty tensors mean nothing
+  if (!x || !x0 || !noise || !mask || !keep_sigma) return fail("known_region_blend: null pointer");
+  if (((uintptr_t)x | (uintptr_t)x0 | (uintptr_t)noise | (uintptr_t)mask | (uintptr_t)xin) & 15)
+    return fail("known_region_blend: x, x0, noise, mask and xin must be 16-byte aligned");
+  const char* px = (const char*)x;
+  const int64_t xbytes = ((rows - 1) * ldx + C) * 2, bytes = nch * 16;
+  for (const void* q : {x0, noise, mask}) {
+    const char* p = (const char*)q;
+    if (p < px + xbytes && px < p + bytes) return fail("known_region_blend: x0, noise and mask must not alias x");
+  }
+  known_region_blend_kernel<<<dim3((unsigned)((nch + 255) / 256)), 256, 0, st>>>((bf16_t*)x, ldx, (const bf16_t*)x0, (const bf16_t*)noise,
+                                                                                 (const bf16_t*)mask, C, nch, keep_sigma, step_ptr, step,
+                                                                                 (bf16_t*)xin, ldxin);
+  return check_launch("known_region_blend");
 }
 
 int timestep_embedding(const float* t, void* out, int n, hipStream_t st) {

@@ -98,6 +98,46 @@ __global__ __launch_bounds__(256) void pack_mask_kernel(const TM* __restrict__ m
   *reinterpret_cast<u32x4*>(out + bt * ld + col0 + c8 * 8) = pack8(v);
 }
 
+// The packed latent mask of known-region sampling: mask [B, H, W] uint8 -> out [B, S, C] bf16 1.0 / 0.0 with
+// out[b, t, c*4 + py*2+px] = m(2ty+py, 2tx+px) for every c -- _pack_latents of the latent-resolution mask repeated over the latent
+// channels (FluxInpaintPipeline.prepare_mask_latents, D/pipelines/flux/pipeline_flux_inpaint.py:615, :656-662).
+//   mode 0  nearest, the reference's F.interpolate: m(ly, lx) = mask[8 ly, 8 lx] >= 128
+//   mode 1  cover: m = 1 if any pixel of the 8x8 blocks of latent pixels [ly-grow, ly+grow] x [lx-grow, lx+grow] (clipped) is >= 128
+// One thread = one token: four latent pixels, each block row one 8-byte load (>= 128 is the top bit of a byte), C/8 equal stores.
+__global__ __launch_bounds__(256) void keep_mask_pack_kernel(const uint8_t* __restrict__ mask, bf16_t* __restrict__ out, int B, int H,
+                                                             int W, int C, int mode, int grow) {
+  const int h = H / 8, w = W / 8, h2 = H / 16, w2 = W / 16;
+  const int64_t S = (int64_t)h2 * w2;
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= B * S) return;
+  const int b = (int)(i / S);
+  const int t = (int)(i - b * S);
+  const int ty = t / w2, tx = t - ty * w2;
+  const uint8_t* mb = mask + (int64_t)b * H * W;
+  float v[8];
+#pragma unroll
+  for (int pp = 0; pp < 4; ++pp) {
+    const int ly = 2 * ty + (pp >> 1), lx = 2 * tx + (pp & 1);
+    bool on;
+    if (mode == 0) {
+      on = mb[(int64_t)ly * 8 * W + lx * 8] >= 128;
+    } else {
+      const int r0 = max(ly - grow, 0) * 8, r1 = (min(ly + grow, h - 1) + 1) * 8;
+      const int c0 = max(lx - grow, 0), c1 = min(lx + grow, w - 1);
+      uint64_t any = 0;
+      for (int r = r0; r < r1; ++r) {
+        const uint64_t* rowp = reinterpret_cast<const uint64_t*>(mb + (int64_t)r * W);
+        for (int c = c0; c <= c1; ++c) any |= rowp[c];
+      }
+      on = (any & 0x8080808080808080ull) != 0;
+    }
+    v[pp] = v[pp + 4] = on ? 1.0f : 0.0f;
+  }
+  const u32x4 packed = pack8(v);
+  bf16_t* o = out + i * C;
+  for (int c8 = 0; c8 < C / 8; ++c8) *reinterpret_cast<u32x4*>(o + c8 * 8) = packed;
+}
+
 // moments NHWC [B, h, w, 2L] (mean | logvar) bf16, eps [B, L, h, w] bf16 or fp32 (null: the mode) ->
 // out[b, t, col0 + c*4 + py*2+px] = bf16chain( (mean + exp(0.5 * clamp(logvar)) * eps - shift) * scale ) at pixel
 // (2ty+py, 2tx+px); every intermediate rounded to bf16 as the reference's bf16 tensor ops round them
@@ -1354,6 +1394,20 @@ int pack_mask(const void* mask, int mask_dtype, void* out, int B, int H, int W, 
   else if (mask_dtype == 2) pack_mask_kernel<uint8_t><<<blocks_for(n), 256, 0, st>>>((const uint8_t*)mask, (bf16_t*)out, B, H, W, mask_b, binarize, ld, col0);
   else return fail("pack_mask: mask dtype must be 0 (f32) or 2 (u8)");
   return check_launch("pack_mask");
+}
+
+int keep_mask_pack(const void* mask_u8, void* out, int B, int H, int W, int C, int mode, int grow, hipStream_t st) {
+  if (B < 0 || H < 0 || W < 0 || H % 16 || W % 16) return fail("keep_mask_pack: B >= 0; H and W non-negative multiples of 16");
+  if (C <= 0 || C % 8) return fail("keep_mask_pack: C must be a positive multiple of 8");
+  if (mode != 0 && mode != 1) return fail("keep_mask_pack: mode must be 0 (nearest) or 1 (cover)");
+  if (mode == 0 && grow != 0) return fail("keep_mask_pack: grow must be 0 in mode 0 (nearest)");
+  if (grow < 0 || grow > 8) return fail("keep_mask_pack: grow %d outside 0..8", grow);
+  const int64_t n = (int64_t)B * (H / 16) * (W / 16);
+  if (n == 0) return 0;
+  if (!mask_u8 || !out) return fail("keep_mask_pack: null pointer");
+  if (((uintptr_t)mask_u8 & 7) || ((uintptr_t)out & 15)) return fail("keep_mask_pack: mask must be 8-byte and out 16-byte aligned");
+  keep_mask_pack_kernel<<<blocks_for(n), 256, 0, st>>>((const uint8_t*)mask_u8, (bf16_t*)out, B, H, W, C, mode, grow);
+  return check_launch("keep_mask_pack");
 }
 
 int sample_pack(const void* moments, const void* eps, int eps_dtype, void* out, int B, int h, int w, int L, float shift,

@@ -194,6 +194,10 @@ int sched_step(bool amo, const void* v, void* x, void* xin, int64_t ldxin, int C
 // second-order multistep update (coef fp32 [n_steps][2]); v_prev bf16 [rows, C] is read from step 1 on and then holds v
 int multistep_step(const void* v, void* x, void* xin, int64_t ldxin, int C, int64_t rows, const float* coef,
                    const int* step_ptr, int step, void* v_prev, hipStream_t st);
+// known-region blend behind a sampler update: x <- (1 - mask) scale_noise(x0, keep_sigma[step], noise) + mask x, bf16 per op;
+// x [rows, C] with pitch ldx, mirrored into xin[:, :C] when given; a negative keep_sigma entry stands for "x0 itself"
+int known_region_blend(void* x, int64_t ldx, const void* x0, const void* noise, const void* mask, int C, int64_t rows,
+                       const float* keep_sigma, const int* step_ptr, int step, void* xin, int64_t ldxin, hipStream_t st);
 int timestep_embedding(const float* t, void* out, int n, hipStream_t st);
 int silu_bf16(const void* a, void* out, int64_t n, hipStream_t st);
 int add_bf16(const void* a, const void* b, void* out, int64_t n, hipStream_t st);
@@ -251,6 +255,8 @@ int warp_grid_u8(const void* in, void* out, void* coverage, int B, int H, int W,
                  int shift, const int16_t* taps, hipStream_t st);
 int pack_mask(const void* mask, int mask_dtype, void* out, int B, int H, int W, int mask_b, int binarize, int64_t ld, int col0,
               hipStream_t st);
+// uint8 pixel mask [B, H, W] -> packed latent mask bf16 [B, (H/16)(W/16), C] of 1.0 / 0.0; mode 0 nearest (grow 0), 1 cover (grow 0..8)
+int keep_mask_pack(const void* mask_u8, void* out, int B, int H, int W, int C, int mode, int grow, hipStream_t st);
 int sample_pack(const void* moments, const void* eps, int eps_dtype, void* out, int B, int h, int w, int L, float shift,
                 float scale, int64_t ld, int col0, hipStream_t st);
 int unpack_latents(const void* lat, int64_t ld, void* out, int B, int h, int w, int L, float shift, float scale, hipStream_t st);

@@ -410,6 +410,45 @@ def multistep_step_(v: torch.Tensor, x: torch.Tensor, coef: torch.Tensor, v_prev
     return x
 
 
+def _flat_rows(t: torch.Tensor, name: str):
+    """(rows, pitch) of a [.., rows, C] tensor whose rows lie one pitch apart throughout (a contiguous tensor, or a column view of one)"""
+    if t.dim() < 2 or t.stride(-1) != 1:
+        raise ValueError(f"{name}: needs [.., rows, C] with unit inner stride")
+    ld = t.stride(-2)
+    rows = 1
+    for d in range(t.dim() - 2, -1, -1):
+        if t.shape[d] != 1 and t.stride(d) != rows * ld:
+            raise ValueError(f"{name}: the rows are not one pitch ({ld}) apart in dimension {d}")
+        rows *= t.shape[d]
+    return rows, ld
+
+
+def known_region_blend(x: torch.Tensor, x0: torch.Tensor, noise: torch.Tensor, mask: torch.Tensor, keep_sigma: torch.Tensor,
+                       step: int = 0, step_ptr: Optional[torch.Tensor] = None, xin: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """x <- (1 - mask) * scale_noise(x0, keep_sigma[step], noise) + mask * x in place, one bf16 rounding per op as the reference's
+    tensor ops (tfx_known_region_blend).  x [.., rows, C] may be a column view (row pitch = stride(-2)); x0 / noise / mask contiguous
+    of x's shape; keep_sigma fp32 [n], bf16-exact values, a negative entry = x0 itself; xin: the x_embedder input to mirror into."""
+    _chk_dev(x, x0, noise, mask, keep_sigma, step_ptr, xin)
+    if any(t.dtype != BF16 for t in (x, x0, noise, mask)) or (xin is not None and xin.dtype != BF16):
+        raise TypeError("known_region_blend: bf16 latents, noise and mask")
+    if keep_sigma.dtype != torch.float32 or not keep_sigma.is_contiguous() or keep_sigma.dim() != 1:
+        raise TypeError("known_region_blend: keep_sigma is a contiguous fp32 vector")
+    if not (x0.shape == noise.shape == mask.shape == x.shape) or not (x0.is_contiguous() and noise.is_contiguous() and mask.is_contiguous()):
+        raise ValueError("known_region_blend: x0, noise and mask must be contiguous and of x's shape")
+    Cc = x.shape[-1]
+    rows, ldx = _flat_rows(x, "known_region_blend: x")
+    ldxin = 0
+    if xin is not None:
+        rin, ldxin = _flat_rows(xin, "known_region_blend: xin")
+        if rin != rows:
+            raise ValueError(f"known_region_blend: xin has {rin} rows, x {rows}")
+    if step_ptr is None and not 0 <= step < keep_sigma.numel():
+        raise ValueError(f"known_region_blend: step {step} outside the sigma table of {keep_sigma.numel()} steps")
+    L.check(L.lib().tfx_known_region_blend(x.data_ptr(), ldx, x0.data_ptr(), noise.data_ptr(), mask.data_ptr(), Cc, rows,
+                                           keep_sigma.data_ptr(), _p(step_ptr), step, _p(xin), ldxin, _stream()), "known_region_blend")
+    return x
+
+
 def timestep_embedding(t: torch.Tensor) -> torch.Tensor:
     _chk_dev(t)
     t = t.contiguous().float()
@@ -1078,6 +1117,26 @@ def pack_mask(mask: torch.Tensor, out: torch.Tensor, col0: int, B: int, H: int, 
     assert mask.numel() == mb * H * W and out.dtype == BF16 and out.is_contiguous()
     L.check(L.lib().tfx_pack_mask(mask.data_ptr(), _dt(mask), out.data_ptr(), B, H, W, mb, 1 if binarize else 0,
                                   out.shape[-1], col0, _stream()), "pack_mask")
+    return out
+
+
+KEEP_MODES = {"nearest": 0, "cover": 1}
+
+
+def keep_mask_pack(mask_u8: torch.Tensor, C: int = 64, mode="nearest", grow: int = 0) -> torch.Tensor:
+    """uint8 pixel mask [B, H, W] -> the packed latent mask of known-region sampling, bf16 [B, (H/16)(W/16), C] of 1.0 / 0.0
+    (tfx_keep_mask_pack).  mode "nearest" (0): the reference's F.interpolate, grow must be 0; "cover" (1): a latent pixel is masked
+    when anything >= 128 lies in its 8x8 block or in those of its `grow` neighbours (0..8)."""
+    _chk_dev(mask_u8)
+    if mask_u8.dtype != torch.uint8 or mask_u8.dim() != 3:
+        raise TypeError("keep_mask_pack: the mask is uint8 [B, H, W]")
+    mode = KEEP_MODES.get(mode, mode)
+    mask_u8 = mask_u8.contiguous()
+    B, H, W = mask_u8.shape
+    if H % 16 or W % 16:
+        raise ValueError(f"keep_mask_pack: H and W must be multiples of 16, got {H} x {W}")
+    out = torch.empty(B, (H // 16) * (W // 16), C, dtype=BF16, device=mask_u8.device)
+    L.check(L.lib().tfx_keep_mask_pack(mask_u8.data_ptr(), out.data_ptr(), B, H, W, C, int(mode), int(grow), _stream()), "keep_mask_pack")
     return out
 
 

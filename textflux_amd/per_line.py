@@ -153,9 +153,10 @@ def write_item(lines: Sequence[Any], fulls: Sequence[Any], pasted, out_dir: Opti
 
 
 def edit_scene(pipe, scene, mask, texts: Sequence[str], cfg: Dict[str, Any], num_inference_steps: int = 30, guidance_scale: float = 30.0,
-               seed: int = 42, device=None, max_sequence_length: int = 512):
+               seed: int = 42, device=None, max_sequence_length: int = 512, call_kw: Optional[Dict[str, Any]] = None):
     """One scene outside the batch driver (run_inference.py): -> (the scene with all lines pasted in, [every line's raw canvas]).
-    Lines of equal editing size go through one pipeline call each; every line has the generator of a single-image call."""
+    Lines of equal editing size go through one pipeline call each; every line has the generator of a single-image call.  call_kw:
+    further keyword arguments of every pipeline call (keep_known, strength)."""
     import torch
     from . import batch_driver as bd
     device = device if device is not None else getattr(pipe, "_execution_device", "cuda")
@@ -176,7 +177,7 @@ def edit_scene(pipe, scene, mask, texts: Sequence[str], cfg: Dict[str, Any], num
         images = pipe(height=batch.size[1], width=batch.size[0], image=[w.image for w in batch.items],
                       mask_image=[w.mask for w in batch.items], num_inference_steps=num_inference_steps, generator=gens,
                       max_sequence_length=max_sequence_length, guidance_scale=guidance_scale, prompt=[glyph.PROMPT_TEMPLATE2] * n,
-                      prompt_2=[w.prompt for w in batch.items]).images
+                      prompt_2=[w.prompt for w in batch.items], **(call_kw or {})).images
         for w, img in zip(batch.items, images):
             fulls[w.line] = img
     crops = [fulls[w.line].crop(glyph.crop_box(w.size, w.meta)) for w in lines]

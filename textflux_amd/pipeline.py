@@ -112,6 +112,21 @@ class _NullBar:
         pass
 
 
+def _keep_known_cfg(keep_known):
+    """keep_known = None / False | True | dict(mode="nearest" | "cover", grow=int) -> None | (mode, grow)"""
+    if keep_known is None or keep_known is False:
+        return None
+    cfg = {} if keep_known is True else dict(keep_known)
+    mode, grow = cfg.pop("mode", "nearest"), int(cfg.pop("grow", 0))
+    if cfg:
+        raise ValueError(f"keep_known: unknown keys {sorted(cfg)}")
+    if mode not in ("nearest", "cover"):
+        raise ValueError(f"keep_known: mode must be 'nearest' or 'cover', got {mode!r}")
+    if grow < 0 or grow > 8 or (mode == "nearest" and grow != 0):
+        raise ValueError("keep_known: grow is 0 for mode 'nearest' and 0..8 for mode 'cover'")
+    return mode, grow
+
+
 class FluxFillPipeline:
     _callback_tensor_inputs = ["latents", "prompt_embeds"]
     supports_output_crop = True
@@ -522,9 +537,11 @@ class FluxFillPipeline:
         return modx
 
     def _engine_loop(self, latents, masked_image_latents, prompt_embeds, pooled, text_ids, latent_image_ids, timesteps,
-                     guidance_scale, callback_on_step_end, callback_tensor_inputs, amo_noise, progress_bar):
+                     guidance_scale, callback_on_step_end, callback_tensor_inputs, amo_noise, progress_bar, keep=None):
         """Session, conditioning, modulation table, x_embedder input, then the step loop (step_loop.denoise).  The loop starts at
-        step 0: _call_body sets the timesteps directly in front of it, which clears the scheduler's begin_index."""
+        step 0 of `timesteps`: _call_body sets the timesteps directly in front of it, which clears the scheduler's begin_index --
+        unless the call gave `strength` / `keep_known`: then get_timesteps set it, `timesteps` and the scheduler's tables start at that
+        step, and `keep` (dict x0 / noise / mask, or x0 / noise alone for a strength-only call) goes to the loop's blend."""
         tr, sch = self.transformer, self.scheduler
         dev = tr.device
         B, S, C = latents.shape
@@ -556,8 +573,77 @@ class FluxFillPipeline:
                 if new_pe is not prompt_embeds:
                     prompt_embeds = new_pe
                     ses.set_conditioning(prompt_embeds.to(dev, BF16), text_ids, latent_image_ids)
-        sch._step_index = 0
-        return step_loop.denoise(self, ses, mod, latents, coef, n, progress_bar, is_amo, fuse, amo_noise, on_step, multistep)
+        sch._step_index = sch.begin_index or 0
+        if keep is not None and "mask" in keep:
+            keep = dict(keep, sigma=sch.keep_sigma_table(dev, BF16))
+        else:
+            keep = None
+        return step_loop.denoise(self, ses, mod, latents, coef, n, progress_bar, is_amo, fuse, amo_noise, on_step, multistep, keep)
+
+    # ------------------------------------------------------------------ known-region sampling
+    def get_timesteps(self, num_inference_steps, strength, device):
+        """FluxInpaintPipeline.get_timesteps (D/pipelines/flux/pipeline_flux_inpaint.py:420-429), set_begin_index included."""
+        init_timestep = min(num_inference_steps * strength, num_inference_steps)
+        t_start = int(max(num_inference_steps - init_timestep, 0))
+        timesteps = self.scheduler.timesteps[t_start * self.scheduler.order:]
+        if hasattr(self.scheduler, "set_begin_index"):
+            self.scheduler.set_begin_index(t_start * self.scheduler.order)
+        return timesteps, num_inference_steps - t_start
+
+    def _prepare_known_region(self, noise, given_latents, image_latents, image, mask_image, keep_cfg, strength, height, width, dtype,
+                              device, generator):
+        """The original's latents x0, the start of a strength < 1 call and the loop's keep buffers.  x0: `image_latents`, or the VAE
+        latents of the UNMASKED preprocessed image (posterior sample, shift / scale, pack) -- drawn here, after every draw the plain
+        call makes.  noise: the initial noise (caller-given latents are both noise and start: the reference's quirk, :586-588).
+        Returns (start latents, dict(x0, noise[, mask]))."""
+        dev = self._execution_device
+        total = noise.shape[0]
+        if image_latents is not None:
+            x0 = image_latents.to(dev, BF16)
+        else:
+            if image is None:
+                raise ValueError("strength / keep_known need `image` (or `image_latents`): the known region is the original's latents")
+            raw = self.image_processor.to_raw(image, height=height, width=width)
+            if raw.dtype != torch.uint8 and raw.shape[1] == self.vae.config.latent_channels:
+                raise ValueError("strength / keep_known with `image` given as VAE latents: pass them packed as `image_latents`")
+            raw = raw.to(dev)
+            if raw.dtype == torch.uint8:
+                x8 = ops.prep_image(raw, None, norm_mode=1)
+            else:
+                flag = ops.any_negative(raw) if self.image_processor.do_normalize else None
+                x8 = ops.prep_image(raw, None, norm_mode=2 if flag is not None else 0, neg_flag=flag)
+            x0 = self._sample_and_pack(self.vae.encode_moments_nhwc(x8), generator, dtype, dev)
+        if x0.shape[0] < total:
+            if total % x0.shape[0]:
+                raise ValueError(f"Cannot duplicate `image` of batch size {x0.shape[0]} to {total} text prompts.")
+            x0 = x0.repeat(total // x0.shape[0], 1, 1)
+        noise = noise.to(dev, BF16).contiguous()
+        x0 = x0.contiguous()
+        if x0.shape != noise.shape:
+            raise ValueError(f"image latents {tuple(x0.shape)} do not match the latents {tuple(noise.shape)}")
+        keep = dict(x0=x0, noise=noise)
+        start = noise
+        if strength < 1.0 and not given_latents:
+            # scale_noise(x0, sigma[t_start], noise) as the blend with an all-zero mask: 0 * (-0) = -0 leaves every value, -0 included
+            start = torch.full_like(noise, -0.0)
+            sigma = self.scheduler._run_sigmas()[:1].to(BF16).float().to(dev)
+            ops.known_region_blend(start, x0, noise, torch.zeros_like(noise), sigma)
+        if keep_cfg is not None:
+            if mask_image is None:
+                raise ValueError("keep_known needs `mask_image`: the known region is what lies outside it")
+            rawm = self.mask_processor.to_raw(mask_image, height=height, width=width).to(dev)
+            if rawm.dtype != torch.uint8:
+                rawm = (rawm.reshape(rawm.shape[0], rawm.shape[-2], rawm.shape[-1]) >= 0.5).to(torch.uint8) * 255
+            mk = ops.keep_mask_pack(rawm, x0.shape[-1], keep_cfg[0], keep_cfg[1])
+            if mk.shape[0] < total:
+                if total % mk.shape[0]:
+                    raise ValueError("The passed mask and the required batch size don't match. Masks are supposed to be duplicated to"
+                                     f" a total batch size of {total}, but {mk.shape[0]} masks were passed.")
+                mk = mk.repeat(total // mk.shape[0], 1, 1)
+            if mk.shape != x0.shape:
+                raise ValueError(f"mask_image packs to {tuple(mk.shape)}, the latents are {tuple(x0.shape)}")
+            keep["mask"] = mk
+        return start, keep
 
     def enable_hip_graph(self, on: bool = True):
         """Replay ONE captured hipGraph per denoising step (device-side step cursor: modulation rows and scheduler
@@ -736,11 +822,19 @@ class FluxFillPipeline:
                  joint_attention_kwargs: Optional[Dict[str, Any]] = None,
                  callback_on_step_end: Optional[Callable] = None,
                  callback_on_step_end_tensor_inputs: List[str] = ["latents"], max_sequence_length: int = 512,
-                 amo_noise: Optional[List[torch.Tensor]] = None, output_crop=None):
-        """Same arguments / defaults / return as the reference `__call__` (P:1850-1873, 2122-2137).  Two additions:
+                 amo_noise: Optional[List[torch.Tensor]] = None, output_crop=None, strength: float = 1.0, keep_known=None,
+                 image_latents: Optional[torch.Tensor] = None):
+        """Same arguments / defaults / return as the reference `__call__` (P:1850-1873, 2122-2137).  Additions:
         `amo_noise`, a list of pre-drawn eps tensors for the AMO sampler (replay across devices), and
         `output_crop` = (left, top, right, bottom), the callers' result crop (run_inference.py:460-465) applied on the
-        device so that only the kept pixels are converted and copied to the host."""
+        device so that only the kept pixels are converted and copied to the host.
+        Known-region sampling (FluxInpaintPipeline's loop on the Fill model, opt-in, no quality claim):
+        `strength` in [0, 1] starts the loop part-way down the sigma grid from the noised original and runs int(n * strength)
+        steps; `keep_known` = True or dict(mode="nearest" | "cover", grow=int) replaces, after every step, the latents outside
+        `mask_image` by the original's latents noised to the next sigma (the original itself on the last step); `image_latents`,
+        packed [B, S, 64], stands in for the VAE latents of `image` (needed when `image` is not given)."""
+        if strength < 0 or strength > 1:
+            raise ValueError(f"The value of strength should in [0.0, 1.0] but is {strength}")
         height = height or self.default_sample_size * self.vae_scale_factor
         width = width or self.default_sample_size * self.vae_scale_factor
         self.check_inputs(prompt, prompt_2, height, width, prompt_embeds=prompt_embeds,
@@ -762,7 +856,8 @@ class FluxFillPipeline:
             return self._call_body(prompt, prompt_2, image, mask_image, masked_image_latents, height, width, num_inference_steps,
                                    sigmas, guidance_scale, num_images_per_prompt, generator, latents, prompt_embeds,
                                    pooled_prompt_embeds, output_type, return_dict, callback_on_step_end,
-                                   callback_on_step_end_tensor_inputs, max_sequence_length, amo_noise, output_crop)
+                                   callback_on_step_end_tensor_inputs, max_sequence_length, amo_noise, output_crop, strength,
+                                   keep_known, image_latents)
         finally:
             if lora_scale is not None:
                 self.transformer._write_scales(prev_lora_scale)
@@ -774,7 +869,7 @@ class FluxFillPipeline:
                    prompt_embeds: Optional[torch.Tensor] = None, pooled_prompt_embeds: Optional[torch.Tensor] = None,
                    output_type: Optional[str] = "pil", return_dict: bool = True, callback_on_step_end: Optional[Callable] = None,
                    max_sequence_length: int = 512, latents: Optional[List[torch.Tensor]] = None,
-                   masked_image_latents: Optional[List[torch.Tensor]] = None):
+                   masked_image_latents: Optional[List[torch.Tensor]] = None, strength: float = 1.0, keep_known=None):
         """One denoising run over samples of DIFFERENT sizes (no reference counterpart: the reference, like `__call__`, runs one
         geometry per call).  image / mask_image: one entry per sample, sizes[b] = (width, height) of sample b (multiples of 16).
         Every sample computes what its own single-image `__call__` computes -- its own latent noise and VAE posterior sample from
@@ -787,6 +882,9 @@ class FluxFillPipeline:
         Needs the flow-matching Euler scheduler with fuse_euler_step (only the fused Euler step carries per-sample coefficients) and
         no step callback."""
         sch, tr = self.scheduler, self.transformer
+        if strength != 1.0 or keep_known:
+            raise NotImplementedError("call_mixed: strength / keep_known (known-region sampling) are not supported in mixed-geometry "
+                                      "batches (the blend's buffers carry no padding rows); use __call__")
         if self._step_cache is not None:
             raise NotImplementedError("call_mixed: the step cache does not serve mixed-geometry batches (padded rows would enter the "
                                       "metric's sums); disable_step_cache() or use __call__")
@@ -894,7 +992,8 @@ class FluxFillPipeline:
 
     def _call_body(self, prompt, prompt_2, image, mask_image, masked_image_latents, height, width, num_inference_steps, sigmas,
                    guidance_scale, num_images_per_prompt, generator, latents, prompt_embeds, pooled_prompt_embeds, output_type,
-                   return_dict, callback_on_step_end, callback_on_step_end_tensor_inputs, max_sequence_length, amo_noise, output_crop):
+                   return_dict, callback_on_step_end, callback_on_step_end_tensor_inputs, max_sequence_length, amo_noise, output_crop,
+                   strength=1.0, keep_known=None, image_latents=None):
         if prompt is not None and isinstance(prompt, str):
             batch_size = 1
         elif prompt is not None and isinstance(prompt, list):
@@ -906,6 +1005,10 @@ class FluxFillPipeline:
             prompt=prompt, prompt_2=prompt_2, prompt_embeds=prompt_embeds, pooled_prompt_embeds=pooled_prompt_embeds,
             device=device, num_images_per_prompt=num_images_per_prompt, max_sequence_length=max_sequence_length)
         num_channels_latents = self.vae.config.latent_channels
+        keep_cfg = _keep_known_cfg(keep_known)
+        known = keep_cfg is not None or strength < 1.0
+        given_latents = latents is not None
+        src_image = image
         latents, latent_image_ids = self.prepare_latents(batch_size * num_images_per_prompt, num_channels_latents, height,
                                                          width, prompt_embeds.dtype, device, generator, latents)
         if masked_image_latents is not None:
@@ -926,13 +1029,23 @@ class FluxFillPipeline:
         sc = self.scheduler.config
         mu = calculate_shift(image_seq_len, sc.base_image_seq_len, sc.max_image_seq_len, sc.base_shift, sc.max_shift)
         timesteps, num_inference_steps = retrieve_timesteps(self.scheduler, num_inference_steps, device, sigmas=sigmas, mu=mu)
-        self._num_timesteps = len(timesteps)
         engine = isinstance(self.scheduler, (FlowMatchEulerDiscreteScheduler, StochasticRFOvershotDiscreteScheduler, FlowMatchMultistepScheduler))
+        keep = None
+        if known:
+            if not engine:
+                raise NotImplementedError("strength / keep_known need one of the engine's schedulers (their step loop holds the blend)")
+            timesteps, num_inference_steps = self.get_timesteps(num_inference_steps, strength, device)
+            if num_inference_steps < 1:
+                raise ValueError(f"After adjusting the num_inference_steps by strength parameter: {strength}, the number of pipeline"
+                                 f"steps is {num_inference_steps} which is < 1 and not appropriate for this pipeline.")
+            latents, keep = self._prepare_known_region(latents, given_latents, image_latents, src_image, mask_image, keep_cfg, strength,
+                                                       height, width, prompt_embeds.dtype, device, generator)
+        self._num_timesteps = len(timesteps)
         with self.progress_bar(total=num_inference_steps) as bar:
             if engine:
                 latents = self._engine_loop(latents, masked_image_latents, prompt_embeds, pooled_prompt_embeds, text_ids,
                                             latent_image_ids, timesteps, guidance_scale, callback_on_step_end,
-                                            callback_on_step_end_tensor_inputs, amo_noise, bar)
+                                            callback_on_step_end_tensor_inputs, amo_noise, bar, keep)
             else:
                 guidance = None
                 if self.transformer.config.guidance_embeds:

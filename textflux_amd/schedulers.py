@@ -11,6 +11,9 @@ precision and order as the reference.  Device side: the state update itself runs
 disappear because the coefficient table is built once from the host copy of the sigmas.
 
 * FlowMatchMultistepScheduler             no reference counterpart: second-order multistep on the Euler class's grid (`tfx_multistep_step`)
+
+Known-region sampling: all three carry `scale_noise` (the Euler class's, scheduling_flow_match_euler_discrete.py:
+130-176) and `keep_sigma_table` for `tfx_known_region_blend`, and their tables start at `begin_index` (`set_begin_index`).
 """
 from __future__ import annotations
 
@@ -76,6 +79,43 @@ class _FlowMatchBase:
 
     def set_begin_index(self, begin_index: int = 0):
         self._begin_index = begin_index
+        self._coef = None              # the coefficient tables start at the first executed step
+
+    def _run_sigmas(self) -> torch.Tensor:
+        """host fp32 sigmas of the steps that run, from begin_index on, and the closing 0"""
+        return self._sigmas_host[self._begin_index or 0:]
+
+    def _table_row(self) -> int:
+        """row of coef_table / keep_sigma_table of the current step: the tables start at begin_index, step_index counts the whole grid"""
+        return self._step_index - (self._begin_index or 0)
+
+    def scale_noise(self, sample: torch.Tensor, timestep, noise: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """Forward process sigma * noise + (1 - sigma) * sample with the reference's index rule and op order
+        (scheduling_flow_match_euler_discrete.py:130-176): begin_index None -> the timestep's own index; step_index set -> that
+        (inpainting, after a step); else begin_index (img2img, before the first step).  Protocol method on the caller's tensors; the
+        engine's loop runs the same arithmetic in tfx_known_region_blend."""
+        sigmas = self.sigmas.to(device=sample.device, dtype=sample.dtype)
+        schedule_timesteps = self.timesteps.to(sample.device)
+        timestep = torch.as_tensor(timestep).reshape(-1).to(sample.device)
+        if self.begin_index is None:
+            step_indices = [self.index_for_timestep(t, schedule_timesteps) for t in timestep]
+        elif self.step_index is not None:
+            step_indices = [self.step_index] * timestep.shape[0]
+        else:
+            step_indices = [self.begin_index] * timestep.shape[0]
+        sigma = sigmas[step_indices].flatten()
+        while len(sigma.shape) < len(sample.shape):
+            sigma = sigma.unsqueeze(-1)
+        return sigma * noise + (1.0 - sigma) * sample
+
+    def keep_sigma_table(self, device, state_dtype=torch.bfloat16) -> torch.Tensor:
+        """fp32 [n_run] for tfx_known_region_blend: entry i = sigma_{i+1} of the steps from begin_index on, rounded to the state dtype
+        as the reference's scale_noise rounds it (`sigmas.to(dtype=sample.dtype)`); the last entry is -1, "the original itself" (the
+        reference's `i == len(timesteps) - 1`, which is not the same as sigma = 0 for signed zeros)."""
+        s = self._run_sigmas()
+        tab = s[1:].to(state_dtype).float()
+        tab[-1] = -1.0
+        return tab.to(device)
 
     def _sigma_to_t(self, sigma):
         return sigma * self.config.num_train_timesteps
@@ -151,10 +191,10 @@ class FlowMatchEulerDiscreteScheduler(_FlowMatchBase):
         self._finish_set_timesteps(sigmas, device)
 
     def coef_table(self, device, state_dtype=torch.bfloat16) -> torch.Tensor:
-        """dsigma_i = sigma_{i+1} - sigma_i (f32), rounded to the model-output dtype exactly where the reference's
+        """dsigma_i = sigma_{i+1} - sigma_i (f32) of the steps from begin_index on, rounded to the model-output dtype exactly where the reference's
         `(sigma_next - sigma) * model_output` rounds it (0-dim f32 tensor cast to the common dtype, :327)."""
         if self._coef is None or self._coef.device != torch.device(device):
-            s = self._sigmas_host
+            s = self._run_sigmas()
             self._coef = (s[1:] - s[:-1]).to(state_dtype).float().to(device)
         return self._coef
 
@@ -165,7 +205,7 @@ class FlowMatchEulerDiscreteScheduler(_FlowMatchBase):
             self._init_step_index(timestep)
         prev = sample.to(model_output.dtype).clone().contiguous()
         ops.euler_step_(model_output.contiguous(), prev, self.coef_table(sample.device, model_output.dtype),
-                        step=self._step_index)
+                        step=self._table_row())
         self._step_index += 1
         if not return_dict:
             return (prev,)
@@ -223,7 +263,7 @@ class StochasticRFOvershotDiscreteScheduler(_FlowMatchBase):
         if self.c is None or self.overshot_func is None:
             raise RuntimeError("call set_c(...) and set_overshot_func(...) before stepping the AMO sampler")
         if self._coef is None or self._coef.device != torch.device(device):
-            s = self._sigmas_host
+            s = self._run_sigmas()
             rows = []
             for i in range(len(s) - 1):
                 sigma, sigma_next = s[i], s[i + 1]
@@ -250,7 +290,7 @@ class StochasticRFOvershotDiscreteScheduler(_FlowMatchBase):
             noise = torch.randn(sample.shape, generator=generator, device=sample.device, dtype=torch.float32)
         prev = sample.to(model_output.dtype).clone().contiguous()
         ops.amo_step_(model_output.contiguous(), prev, self.coef_table(sample.device, model_output.dtype),
-                      noise.to(sample.device, torch.float32).contiguous(), step=self._step_index)
+                      noise.to(sample.device, torch.float32).contiguous(), step=self._table_row())
         sigma = self._sigmas_host[self._step_index].to(sample.device)
         predicted_x1 = sample.to(torch.float32) - sigma * model_output
         self._step_index += 1
@@ -285,10 +325,10 @@ class FlowMatchMultistepScheduler(_FlowMatchBase):
         self._v_prev = None
 
     def coef_table(self, device, state_dtype=torch.bfloat16) -> torch.Tensor:
-        """fp32 [n, 2]: row 0 = (h_0, 0), row i = (h_i (1 + h_i / (2 h_{i-1})), -h_i^2 / (2 h_{i-1})), evaluated in float64 from the
+        """fp32 [n, 2] of the steps from begin_index on (the first executed step is the history-free one): row 0 = (h_0, 0), row i = (h_i (1 + h_i / (2 h_{i-1})), -h_i^2 / (2 h_{i-1})), evaluated in float64 from the
         host copy of the fp32 sigmas and rounded to fp32 once.  (state_dtype: the siblings' signature; the coefficients stay fp32.)"""
         if self._coef is None or self._coef.device != torch.device(device):
-            h = np.diff(self._sigmas_host.numpy().astype(np.float64))
+            h = np.diff(self._run_sigmas().numpy().astype(np.float64))
             c = np.zeros((len(h), 2), dtype=np.float64)
             c[0, 0] = h[0]
             c[1:, 0] = h[1:] * (1.0 + h[1:] / (2.0 * h[:-1]))
@@ -307,7 +347,7 @@ class FlowMatchMultistepScheduler(_FlowMatchBase):
         if hist is None or hist.shape != v.shape or hist.dtype != v.dtype or hist.device != v.device:
             hist = self._v_prev = torch.empty_like(v)
         prev = sample.clone().contiguous()
-        ops.multistep_step_(v, prev, self.coef_table(sample.device), hist, step=self._step_index)
+        ops.multistep_step_(v, prev, self.coef_table(sample.device), hist, step=self._table_row())
         self._step_index += 1
         if not return_dict:
             return (prev,)

@@ -1,6 +1,7 @@
 """The engine's denoising loop, once: n steps of tfx_dit_step_run -- or of the replay of the graph captured
 from it -- for the plain loop (phase 0) and the step cache (phases 1, 2 / 3), the Euler, AMO, fused-Euler and multistep samplers (the
-last through tfx_dit_step_run_multistep), with or without a step callback, on uniform and mixed-geometry sessions.
+last through tfx_dit_step_run_multistep), with or without a step callback, on uniform and mixed-geometry sessions; with the
+known-region blend behind every sampler update (tfx_dit_step_run_ex) when the call keeps the known region.
 
 `run_steps` is the control flow and touches no device: it drives a `steps` object with
     feed_noise(i)   run(phase)   replay(handle)   capture(phase) -> handle (raises CaptureRefused)   destroy(handle)
@@ -82,12 +83,17 @@ def run_steps(steps, n, pipe, progress_bar, graphs, key, decider=None, use_graph
 class SessionSteps:
     """run_steps' device operations on a DitSession: its persistent step buffers `gb`, one tfx_step_desc per phase, stream `side`."""
 
-    def __init__(self, ses, gb, side, phases, is_amo, fuse, amo_noise, multistep=False):
+    def __init__(self, ses, gb, side, phases, is_amo, fuse, amo_noise, multistep=False, keep=False):
         self.ses, self.gb, self.side, self.st, self.lib = ses, gb, side, side.cuda_stream, L.lib()
         self.sd = {ph: ses.step_desc(gb, is_amo, fuse, phase=ph) for ph in phases}
         self.is_amo, self.amo_noise = is_amo, amo_noise
         # the multistep sampler: sampler 0's descriptor through the *_multistep entry points, with the session's history buffer
         self.v_prev = gb["v_prev"].data_ptr() if multistep else None
+        # known-region sampling: the same descriptors through the *_ex entry points, the blend's buffers beside them
+        self.extra = None
+        if keep:
+            self.extra = L.StepExtra(v_prev=self.v_prev, keep_x0=gb["keep_x0"].data_ptr(), keep_noise=gb["keep_noise"].data_ptr(),
+                                     keep_mask=gb["keep_mask"].data_ptr(), keep_sigma=gb["keep_sigma"].data_ptr())
 
     def feed_noise(self, i):
         if not self.is_amo:
@@ -98,7 +104,9 @@ class SessionSteps:
             self.gb["noise"].copy_(self.amo_noise[i].to(self.gb["noise"].device, torch.float32))
 
     def run(self, ph):
-        if self.v_prev is not None:
+        if self.extra is not None:
+            L.check(self.lib.tfx_dit_step_run_ex(C.byref(self.sd[ph]), C.byref(self.extra), self.st), "dit_step_run_ex")
+        elif self.v_prev is not None:
             L.check(self.lib.tfx_dit_step_run_multistep(C.byref(self.sd[ph]), self.v_prev, self.st), "dit_step_run_multistep")
         else:
             L.check(self.lib.tfx_dit_step_run(C.byref(self.sd[ph]), self.st), "dit_step_run")
@@ -108,7 +116,9 @@ class SessionSteps:
 
     def capture(self, ph):
         h = C.c_void_p()
-        if self.v_prev is not None:
+        if self.extra is not None:
+            rc = self.lib.tfx_dit_step_capture_ex(C.byref(self.sd[ph]), C.byref(self.extra), self.st, C.byref(h))
+        elif self.v_prev is not None:
             rc = self.lib.tfx_dit_step_capture_multistep(C.byref(self.sd[ph]), self.v_prev, self.st, C.byref(h))
         else:
             rc = self.lib.tfx_dit_step_capture(C.byref(self.sd[ph]), self.st, C.byref(h))
@@ -138,13 +148,17 @@ class SessionSteps:
         return state + (self.gb["v_prev"],) if self.v_prev is not None else state
 
 
-def denoise(pipe, ses, mod, latents, coef, n, progress_bar, is_amo=False, fuse=False, amo_noise=None, on_step=None, multistep=False):
+def denoise(pipe, ses, mod, latents, coef, n, progress_bar, is_amo=False, fuse=False, amo_noise=None, on_step=None, multistep=False,
+            keep=None):
     """The n steps of one engine call on session `ses`, whose xin holds [latents | masked_image_latents] and whose conditioning is
     set.  mod [n, B, mod_len (+ EULER_PAD when fuse)]: the modulation table.  latents [B, S, C] and coef, the sampler's coefficient
     table, may be None when fuse: the fused step reads the latents from xin and its coefficients from `mod`.  on_step(i, lat): the
     step callback, handed the live latent buffer after step i (it may write to it and to ses.xin).  multistep: the second-order
     multistep sampler -- unfused, coef its [n, 2] table, the history buffer gb["v_prev"] owned by the session; a callback that
-    replaces the latents leaves the history (the previous model output) as it is.  Runs on the session's side
+    replaces the latents leaves the history (the previous model output) as it is.  keep: known-region sampling --
+    dict(x0, noise, mask: bf16 [B, S, C]; sigma: fp32 [n], the scheduler's keep_sigma_table): after every sampler update the latents
+    become (1 - mask) scale_noise(x0, sigma_{i+1}, noise) + mask latents (tfx_known_region_blend inside the step); the buffers live in
+    the session next to v_prev, because captured graphs bake their addresses.  Runs on the session's side
     stream (capture needs a non-NULL stream), fenced against the caller's current stream on both sides.  The step cache is on when
     pipe.enable_step_cache() is in force; graphs when pipe.enable_hip_graph(True), no callback and n > 1.  Returns the final
     latents and leaves pipe.step_cache_report set."""
@@ -161,6 +175,16 @@ def denoise(pipe, ses, mod, latents, coef, n, progress_bar, is_amo=False, fuse=F
         assert not is_amo and not fuse and latents is not None
         if "v_prev" not in gb:           # lives and dies with gb: captured graphs bake its address; step 0 never reads it
             gb["v_prev"] = torch.empty_like(gb["lat"])
+    if keep is not None:
+        if ses.mixed:
+            raise NotImplementedError("known-region sampling does not serve mixed-geometry sessions")
+        assert keep["sigma"].numel() == n and keep["sigma"].dtype == torch.float32
+        if "keep_x0" not in gb:          # live and die with gb, like v_prev
+            gb.update({"keep_" + k: torch.empty_like(gb["lat"]) for k in ("x0", "noise", "mask")})
+            gb["keep_sigma"] = torch.zeros(gb["mod_table"].shape[0], dtype=torch.float32, device=dev)
+        for k in ("x0", "noise", "mask"):
+            gb["keep_" + k].copy_(keep[k])
+        gb["keep_sigma"][:n].copy_(keep["sigma"])
     decider = None
     if pipe._step_cache is not None:
         ses.step_cache_reset()
@@ -169,9 +193,11 @@ def denoise(pipe, ses, mod, latents, coef, n, progress_bar, is_amo=False, fuse=F
     side = ses.graph_stream()
     side.wait_stream(cur)
     with torch.cuda.stream(side):
-        steps = SessionSteps(ses, gb, side, (0,) if decider is None else (1, 2, 3), is_amo, fuse, amo_noise, multistep)
+        steps = SessionSteps(ses, gb, side, (0,) if decider is None else (1, 2, 3), is_amo, fuse, amo_noise, multistep, keep is not None)
         ses._mod_keepalive = gb["mod_cur"]
         key = ("multistep", False) if multistep else (is_amo, fuse)
+        if keep is not None:
+            key += ("keep",)
         run_steps(steps, n, pipe, progress_bar, ses.graphs, key, decider, use_graph=pipe._use_hip_graph,
                   callback=None if on_step is None else lambda i: on_step(i, gb["lat"]))
         out = ops.copy_rows_(ses.xin[:, :, :shape[2]], torch.empty(shape, dtype=BF16, device=dev)) if fuse else gb["lat"].clone()
