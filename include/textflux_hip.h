@@ -269,6 +269,19 @@ int tfx_multistep_step(const void* v, void* x, void* xin, int64_t ldxin, int32_t
  *      overlapping x.  rows == 0 launches nothing.  No new TFX_ABI_VERSION: new entry points only. */
 int tfx_known_region_blend(void* x, int64_t ldx, const void* x0, const void* noise, const void* mask, int32_t C, int64_t rows,
                            const float* keep_sigma, const int32_t* step_ptr, int32_t step, void* xin, int64_t ldxin, tfx_stream stream);
+/* ---- change-map blend (DESIGN.md section 4 "Change-map sampling"; the loop of FluxDifferentialImg2ImgPipeline, D/examples/community/
+ *      pipeline_flux_differential_img2img.py:974-986): tfx_known_region_blend with the mask decided on the device from the step cursor.
+ *      hold u8 [rows, 4] (4-byte aligned; tfx_change_map_pack: 255 - map per latent pixel of the token's 2x2 patch), cut int32 [n_steps]
+ *      (schedulers.change_cut_table).  With i = *step_ptr or step, s = keep_sigma[i], k = (hold[r, c & 3] > cut[i]) ? 1 : 0 for column c
+ *      and p as above (s < 0: p = x0):
+ *        e = bf16(p k)  w = bf16(1 - k)  d = bf16(x w)  x <- bf16(e + d)
+ *      the reference's line 985 op by op, no select, so signed zeros come out as the reference's.  cut[i] >= 255: nothing is held and x
+ *      is NOT written (the reference's last step leaves the latents alone; e + d would turn -0 into +0); xin != NULL is still mirrored.
+ *      Refused: as tfx_known_region_blend, plus a null or misaligned hold / cut, and hold overlapping x or xin.  rows == 0 launches
+ *      nothing.  No new TFX_ABI_VERSION: new entry points only. */
+int tfx_change_map_blend(void* x, int64_t ldx, const void* x0, const void* noise, const void* hold, const int32_t* cut, int32_t C,
+                         int64_t rows, const float* keep_sigma, const int32_t* step_ptr, int32_t step, void* xin, int64_t ldxin,
+                         tfx_stream stream);
 
 /* ---- small ops of the conditioning path (CombinedTimestepGuidanceTextProjEmbeddings, D/models/embeddings.py:1327-1339) */
 int tfx_timestep_embedding(const float* t, void* out /* [n,256] = cos|sin */, int32_t n, tfx_stream stream);
@@ -485,6 +498,19 @@ typedef struct tfx_step_extra {
 } tfx_step_extra;
 int tfx_dit_step_run_ex(const tfx_step_desc* step, const tfx_step_extra* extra, tfx_stream stream);
 int tfx_dit_step_capture_ex(const tfx_step_desc* step, const tfx_step_extra* extra, tfx_stream stream, tfx_graph* out);
+/* The step with the change-map blend (DESIGN.md section 4 "Change-map sampling"): a second struct beside the descriptor, so that
+ * tfx_step_extra keeps its layout.  change == NULL is tfx_dit_step_run_ex.  With change set, extra->keep_x0 / keep_noise / keep_sigma
+ * must be set and keep_mask NULL; tfx_change_map_blend runs where tfx_known_region_blend runs (behind the sampler update, in front of
+ * the step cache's store pass and the cursor advance; on dit.xin with pitch in_channels for sampler 2, else on latents mirrored into
+ * dit.xin).  Every sampler, phases 0 / 2 / 3, one graph for every step.  Refused: dit.seq_len, and hold / cut / keep_* overlapping
+ * latents, dit.out, dit.xin or v_prev. */
+typedef struct tfx_step_change {
+  const void* hold;     /* u8 [B*S, 4] */
+  const int32_t* cut;   /* int32 [n_steps] */
+} tfx_step_change;
+int tfx_dit_step_run_ex2(const tfx_step_desc* step, const tfx_step_extra* extra, const tfx_step_change* change, tfx_stream stream);
+int tfx_dit_step_capture_ex2(const tfx_step_desc* step, const tfx_step_extra* extra, const tfx_step_change* change, tfx_stream stream,
+                             tfx_graph* out);
 
 /* ---- VAE ends (AutoencoderKL, D/models/autoencoders/autoencoder_kl.py:263-332) on NHWC bf16 activations -------------
  * 3x3 convolution as an implicit GEMM on the MFMA kernel (ResnetBlock2D convs D/models/resnet.py:327-366, Upsample2D
@@ -743,6 +769,13 @@ int tfx_pack_mask(const void* mask, int32_t mask_dtype, void* out, int32_t B, in
  * C a positive multiple of 8 (64 for the Fill model). */
 int tfx_keep_mask_pack(const void* mask_u8, void* out, int32_t B, int32_t H, int32_t W, int32_t C, int32_t mode, int32_t grow,
                        tfx_stream stream);
+/* The hold bytes of change-map sampling (DESIGN.md section 4 "Change-map sampling"): map_u8 [B, H, W] uint8 (8-byte aligned, H and W
+ * multiples of 16; 255 = free to change from the first step, 0 = never changes) -> hold u8 [B, (H/16)(W/16), 4] (4-byte aligned),
+ * hold[b, t, py*2+px] = 255 - g(2ty+py, 2tx+px), t = ty * (W/16) + tx.
+ *   mode 0 (nearest, the reference's F.interpolate): g(ly, lx) = map[8 ly, 8 lx]; grow must be 0
+ *   mode 1 (cover): g = the maximum of map over the 8x8 blocks of latent pixels [ly-grow, ly+grow] x [lx-grow, lx+grow] (clipped to the
+ *           image), 0 <= grow <= 8: tfx_keep_mask_pack's cover on grey values -- a token is held no longer than the freest pixel near it */
+int tfx_change_map_pack(const void* map_u8, void* hold, int32_t B, int32_t H, int32_t W, int32_t mode, int32_t grow, tfx_stream stream);
 /* moments [B, h, w, 2L] NHWC bf16 (mean | logvar: the encoder's conv_out), eps [B, L, h, w] f32 / bf16 or NULL (mode) ->
  * out[b, t, col0 + c*4 + py*2+px] = ((mean + exp(0.5 clamp(logvar, -30, 20)) * eps) - shift) * scale, every intermediate
  * rounded to bf16 as the reference's tensor ops do (D/models/autoencoders/vae.py:781-802, P:1528-1530, 1743-1748). */

@@ -60,7 +60,7 @@ def apply_scheduler_name(pipe):
 
 
 def run_inference(image_input, mask_input, words_input, num_steps=50, guidance_scale=30, seed=42, pipe=None, paste_back=None, known=None):
-    """known (not in the reference): None, or dict(keep_known=..., strength=...) handed to the pipeline call (known-region sampling).
+    """known (not in the reference): None, or dict(keep_known=..., strength=..., change_map=...) handed to the pipeline call (known-region sampling).
     paste_back (not in the reference): None, or dict(dilate, feather) -- the result is then blended back into the input image under
     the dilated and feathered mask and returned at the INPUT's size (FluxFillPipeline.paste_back) instead of at the pipeline's size.
     seamless (True or dict(smooth, max_shift)) and grain (True or dict(ring, max_sigma, strength, min_pixels, seed)) in it are handed to
@@ -268,6 +268,40 @@ def add_known_region_args(ap):
     ap.add_argument("--keep_known_mode", choices=("nearest", "cover"), default="nearest", help="how the pixel mask becomes the latent mask: "
                     "its value at every 8th pixel, or 'cover': masked wherever anything masked touches the latent pixel")
     ap.add_argument("--keep_known_grow", type=int, default=0, metavar="N", help="with cover: also mask the N neighbouring latent pixels (0..8)")
+    add_change_map_args(ap)
+
+
+def add_change_map_args(ap):
+    """Not in the reference's Fill callers: change-map sampling (FluxFillPipeline.__call__: change_map), the map derived from each call's mask."""
+    ap.add_argument("--change_map", action="store_true", help="give every latent pixel its own release step: the strokes change fully, a halo "
+                    "around them a little, the far field never (the map is the dilated and feathered mask; not with --keep_known)")
+    ap.add_argument("--change_dilate", type=int, default=None, metavar="N", help="with --change_map: grow the mask by N pixels (default: the paste-back's)")
+    ap.add_argument("--change_feather", type=int, default=None, metavar="N", help="with --change_map: soften the grown mask's edge over N pixels (default: the paste-back's)")
+    ap.add_argument("--change_mode", choices=("nearest", "cover"), default="nearest", help="with --change_map: the map's value at every 8th pixel, "
+                    "or 'cover': a latent pixel is as free as the freest pixel that touches it")
+    ap.add_argument("--change_grow", type=int, default=0, metavar="N", help="with --change_mode cover: also look at the N neighbouring latent pixels (0..8)")
+    ap.add_argument("--change_last", choices=("keep", "free"), default="keep", help="with --change_map: held pixels end as the input's latents "
+                    "(keep), or the last step belongs to the model (free)")
+
+
+def change_map_from_args(a):
+    """-> None (the defaults: today's call), or the change_map dict of the pipeline call"""
+    if not a.change_map:
+        if a.change_dilate is not None or a.change_feather is not None or a.change_mode != "nearest" or a.change_grow != 0 or a.change_last != "keep":
+            raise SystemExit("--change_dilate / --change_feather / --change_mode / --change_grow / --change_last need --change_map")
+        return None
+    if a.keep_known:
+        raise SystemExit("--change_map and --keep_known exclude each other")
+    if a.change_grow < 0 or a.change_grow > 8 or (a.change_mode == "nearest" and a.change_grow):
+        raise SystemExit("--change_grow is 0 with --change_mode nearest and 0..8 with cover")
+    if (a.change_dilate is not None and a.change_dilate < 0) or (a.change_feather is not None and a.change_feather < 0):
+        raise SystemExit("--change_dilate / --change_feather must be >= 0")
+    cm = dict(mode=a.change_mode, grow=a.change_grow, last=a.change_last)
+    if a.change_dilate is not None:
+        cm["dilate"] = a.change_dilate
+    if a.change_feather is not None:
+        cm["feather"] = a.change_feather
+    return cm
 
 
 def known_region_from_args(a):
@@ -283,6 +317,9 @@ def known_region_from_args(a):
         known["keep_known"] = dict(mode=a.keep_known_mode, grow=a.keep_known_grow)
     if a.strength != 1.0:
         known["strength"] = a.strength
+    cm = change_map_from_args(a)
+    if cm is not None:
+        known["change_map"] = cm
     return known or None
 
 

@@ -5,7 +5,8 @@
     python scripts/run_eval.py --json_path annos.json --original_images_dir imgs/ --weights_path models/textflux/transformer \
         [--output_dir visualization_results --font_path resource/font/Arial-Unicode-Regular.ttf --text_height_ratio 0.1667
          --steps 30 --guidance_scale 30 --seed 42 --num_gpus 4 --scheduler "" | overshoot | multistep
-         --strength 1.0 --keep_known --keep_known_mode nearest | cover --keep_known_grow 0]
+         --strength 1.0 --keep_known --keep_known_mode nearest | cover --keep_known_grow 0
+         --change_map --change_dilate N --change_feather N --change_mode nearest | cover --change_grow 0 --change_last keep | free]
 
 `annos.json` = {"data_list": [{"img_name": ..., "annotations": [{"text": ..., "polygon": [[x, y], ...]}, ...]}, ...]}; per item
 the first annotation is used: polygon -> white-on-black mask, glyph strip of height int(width * text_height_ratio) stacked on
@@ -76,6 +77,15 @@ def build_parser(lora: bool = False):
     ap.add_argument("--keep_known_mode", choices=("nearest", "cover"), default="nearest", help="latent mask from the pixel mask: its value at "
                     "every 8th pixel, or masked wherever anything masked touches the latent pixel (with --keep_known)")
     ap.add_argument("--keep_known_grow", type=int, default=0, metavar="N", help="with cover: also mask the N neighbouring latent pixels, 0..8")
+    ap.add_argument("--change_map", action="store_true", help="change-map sampling: every latent pixel gets its own release step from the "
+                    "dilated and feathered mask of its call (not with --keep_known)")
+    ap.add_argument("--change_dilate", type=int, default=None, metavar="N", help="with --change_map: grow the mask by N pixels (default: the paste-back's)")
+    ap.add_argument("--change_feather", type=int, default=None, metavar="N", help="with --change_map: soften the grown mask's edge over N pixels (default: the paste-back's)")
+    ap.add_argument("--change_mode", choices=("nearest", "cover"), default="nearest", help="with --change_map: the map at every 8th pixel, or "
+                    "'cover': a latent pixel is as free as the freest pixel that touches it")
+    ap.add_argument("--change_grow", type=int, default=0, metavar="N", help="with --change_mode cover: also look at the N neighbouring latent pixels, 0..8")
+    ap.add_argument("--change_last", choices=("keep", "free"), default="keep", help="with --change_map: held pixels end as the canvas's latents "
+                    "(keep), or the last step belongs to the model (free)")
     ap.add_argument("--step_cache", type=float, default=None, metavar="THR", help="first-block step cache: skip the block stack on steps whose "
                     "first-block residual moved by less than THR relative to the last computed step (no default: the value is a property "
                     "of the checkpoint; 0 never skips)")
@@ -191,6 +201,20 @@ def main(argv=None, lora: bool = False, script: str = __file__):
         known["keep_known"] = dict(mode=a.keep_known_mode, grow=a.keep_known_grow)
     if a.strength != 1.0:
         known["strength"] = a.strength
+    if not a.change_map and (a.change_dilate is not None or a.change_feather is not None or a.change_mode != "nearest" or a.change_grow != 0
+                             or a.change_last != "keep"):
+        raise SystemExit("--change_dilate / --change_feather / --change_mode / --change_grow / --change_last need --change_map")
+    if a.change_map:
+        if a.keep_known:
+            raise SystemExit("--change_map and --keep_known exclude each other")
+        if a.mixed_pad > 0:
+            raise SystemExit("--change_map does not serve mixed-geometry batches (--mixed_pad)")
+        if a.change_grow < 0 or a.change_grow > 8 or (a.change_mode == "nearest" and a.change_grow):
+            raise SystemExit("--change_grow is 0 with --change_mode nearest and 0..8 with cover")
+        if (a.change_dilate is not None and a.change_dilate < 0) or (a.change_feather is not None and a.change_feather < 0):
+            raise SystemExit("--change_dilate / --change_feather must be >= 0")
+        known["change_map"] = dict(mode=a.change_mode, grow=a.change_grow, last=a.change_last,
+                                   **{k: v for k, v in (("dilate", a.change_dilate), ("feather", a.change_feather)) if v is not None})
     if a.step_cache is None and a.step_cache_max_consecutive is not None:
         raise SystemExit("--step_cache_max_consecutive needs --step_cache THR")
     if a.step_cache is not None and a.mixed_pad > 0:

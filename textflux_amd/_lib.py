@@ -117,6 +117,11 @@ class StepExtra(C.Structure):
     _fields_ = [("v_prev", c_void_p), ("keep_x0", c_void_p), ("keep_noise", c_void_p), ("keep_mask", c_void_p), ("keep_sigma", c_void_p)]
 
 
+class StepChange(C.Structure):
+    """tfx_step_change: the change-map blend's hold bytes and cut table, beside tfx_step_extra through the *_ex2 step entry points"""
+    _fields_ = [("hold", c_void_p), ("cut", c_void_p)]
+
+
 # name -> (restype, argtypes); every symbol include/textflux_hip.h declares must appear here (tests check it)
 SIGNATURES = {
     "tfx_version": (c_char_p, []),
@@ -156,6 +161,8 @@ SIGNATURES = {
                                    c_void_p, c_void_p]),
     "tfx_known_region_blend": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int32, c_int64, c_void_p, c_void_p, c_int32,
                                        c_void_p, c_int64, c_void_p]),
+    "tfx_change_map_blend": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int64, c_void_p, c_void_p, c_int32,
+                                     c_void_p, c_int64, c_void_p]),
     "tfx_timestep_embedding": (c_int, [c_void_p, c_void_p, c_int32, c_void_p]),
     "tfx_silu": (c_int, [c_void_p, c_void_p, c_int64, c_void_p]),
     "tfx_add": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
@@ -175,6 +182,8 @@ SIGNATURES = {
     "tfx_dit_step_capture_multistep": (c_int, [C.POINTER(StepDesc), c_void_p, c_void_p, C.POINTER(c_void_p)]),
     "tfx_dit_step_run_ex": (c_int, [C.POINTER(StepDesc), C.POINTER(StepExtra), c_void_p]),
     "tfx_dit_step_capture_ex": (c_int, [C.POINTER(StepDesc), C.POINTER(StepExtra), c_void_p, C.POINTER(c_void_p)]),
+    "tfx_dit_step_run_ex2": (c_int, [C.POINTER(StepDesc), C.POINTER(StepExtra), C.POINTER(StepChange), c_void_p]),
+    "tfx_dit_step_capture_ex2": (c_int, [C.POINTER(StepDesc), C.POINTER(StepExtra), C.POINTER(StepChange), c_void_p, C.POINTER(c_void_p)]),
     "tfx_step_cache_metric": (c_int, [c_void_p, c_int64, c_int64, C.POINTER(StepCache), c_int32, c_int32, c_int32, c_void_p]),
     "tfx_step_cache_store": (c_int, [c_void_p, c_int64, c_int64, C.POINTER(StepCache), c_int32, c_int32, c_int32, c_void_p]),
     "tfx_step_cache_apply": (c_int, [c_void_p, c_int64, c_int64, C.POINTER(StepCache), c_int32, c_int32, c_int32, c_void_p]),
@@ -208,6 +217,7 @@ SIGNATURES = {
     "tfx_warp_grid_u8": (c_int, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p, c_int32, c_void_p,
                                  c_void_p]),
     "tfx_keep_mask_pack": (c_int, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p]),
+    "tfx_change_map_pack": (c_int, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p]),
     "tfx_pack_mask": (c_int, [c_void_p, c_int32, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_int64, c_int32,
                               c_void_p]),
     "tfx_vae_sample_pack": (c_int, [c_void_p, c_void_p, c_int32, c_void_p, c_int32, c_int32, c_int32, c_int32, c_float,

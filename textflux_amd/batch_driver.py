@@ -478,7 +478,7 @@ def run_items(items: Sequence[Dict[str, Any]], pipe, out_dir: Optional[str], bat
               save: Optional[Callable] = None, max_sequence_length: int = 512, eval_cfg: Optional[Dict[str, Any]] = None,
               encode: str = "auto", save_full: Optional[Callable] = None, mixed_pad: float = 0.0,
               step_cache: Optional[Dict[str, Any]] = None, paste_back: Optional[Dict[str, Any]] = None, keep_known=None,
-              strength: float = 1.0) -> Dict[str, Any]:
+              strength: float = 1.0, change_map=None) -> Dict[str, Any]:
     """Runs the whole list; returns {"done": [indices this rank wrote], "failed": [...], "all_done": [...] on rank 0,
     "encode": "local" | "rank0"}.  `pipe` needs `encode_prompt(prompt, prompt_2, ...)` and the FluxFillPipeline `__call__`.
     encode: "local" = every rank encodes the T5 prompts of its own batches (needs a T5 on every rank), "rank0" = rank 0
@@ -527,8 +527,18 @@ def run_items(items: Sequence[Dict[str, Any]], pipe, out_dir: Optional[str], bat
     between the channels, as far as the scene's own noise on the ring is.
     keep_known=True | dict(mode, grow) and strength (DESIGN.md section 4 "Known-region sampling"): handed to every pipeline call as
     they are -- the canvas outside the mask is then kept in the latents at every step, and the loop runs int(steps * strength) steps
-    from the noised canvas.  Paste-back runs after decode, unchanged.  Not with mixed_pad > 0."""
+    from the noised canvas.  Paste-back runs after decode, unchanged.  Not with mixed_pad > 0.
+    change_map (DESIGN.md section 4 "Change-map sampling"): handed to every pipeline call as it is -- True or dict(dilate, feather, mode,
+    grow, last) derives the map inside each call from that call's own mask, so it composes with paste_back, region, per_line and the
+    warps with no further work (every line's call sees its own line's mask); an explicit map (an image, or dict(map=...)) must have the
+    calls' size.  Not with keep_known, not with mixed_pad > 0."""
     known = {}
+    if change_map is not None and change_map is not False:
+        if keep_known:
+            raise ValueError("change_map and keep_known exclude each other")
+        if mixed_pad > 0:
+            raise NotImplementedError("change_map (change-map sampling) does not serve mixed-geometry batches (mixed_pad > 0)")
+        known["change_map"] = change_map
     if keep_known:
         known["keep_known"] = keep_known
     if strength != 1.0:
@@ -680,7 +690,7 @@ def _run_items(items, pipe, out_dir, batch_size, num_inference_steps, guidance_s
             same_box = all(bx == boxes[0] for bx in boxes)      # one crop window for the whole batch: applied on the device
             kw = (dict(output_crop=boxes[0]) if same_box and not keep_full and not mine.mixed and getattr(pipe, "supports_output_crop", False)
                   else {})
-            call_kw = dict(kw, **(known or {}))     # keep_known / strength: only when given, so that other pipelines' calls stay as they were
+            call_kw = dict(kw, **(known or {}))     # keep_known / strength / change_map: only when given, so that other pipelines' calls stay as they were
             img_in, mask_in = _batch_inputs(mine.items, device)
             if mine.mixed:          # items of different sizes: one padded forward per step, every item at its own size
                 images = pipe.call_mixed(image=img_in, mask_image=mask_in, sizes=[w.size for w in mine.items],

@@ -284,6 +284,12 @@ int tfx_known_region_blend(void* x, int64_t ldx, const void* x0, const void* noi
   return known_region_blend(x, ldx, x0, noise, mask, C, rows, keep_sigma, step_ptr, step, xin, ldxin, S(stream));
 }
 
+int tfx_change_map_blend(void* x, int64_t ldx, const void* x0, const void* noise, const void* hold, const int32_t* cut, int32_t C,
+                         int64_t rows, const float* keep_sigma, const int32_t* step_ptr, int32_t step, void* xin, int64_t ldxin,
+                         tfx_stream stream) {
+  return change_map_blend(x, ldx, x0, noise, hold, cut, C, rows, keep_sigma, step_ptr, step, xin, ldxin, S(stream));
+}
+
 int tfx_timestep_embedding(const float* t, void* out, int32_t n, tfx_stream stream) {
   if (!t || !out) return fail("tfx_timestep_embedding: null pointer");
   return timestep_embedding(t, out, n, S(stream));
@@ -487,6 +493,9 @@ int tfx_warp_grid_u8(const void* in, void* out, void* coverage, int32_t B, int32
   if (!in || !out || !grid || !taps) return fail("tfx_warp_grid_u8: null pointer");
   return warp_grid_u8(in, out, coverage, B, H, W, C, out_h, out_w, grid, shift, taps, S(stream));
 }
+int tfx_change_map_pack(const void* map_u8, void* hold, int32_t B, int32_t H, int32_t W, int32_t mode, int32_t grow, tfx_stream stream) {
+  return change_map_pack(map_u8, hold, B, H, W, mode, grow, S(stream));
+}
 int tfx_keep_mask_pack(const void* mask_u8, void* out, int32_t B, int32_t H, int32_t W, int32_t C, int32_t mode, int32_t grow,
                        tfx_stream stream) {
   return keep_mask_pack(mask_u8, out, B, H, W, C, mode, grow, S(stream));
@@ -677,8 +686,10 @@ int step_check(const tfx_step_desc* s) {
 
 // the scheduler update behind the final projection and the cursor advance: the end of a whole step and of both tails.
 // ex.v_prev: the multistep history buffer -- the second-order update then stands where sampler 0 launches Euler's.  ex.keep_*: the
-// known-region blend, behind the update and in front of the step cache's store pass and the cursor advance (it reads the cursor)
-int step_finish(const tfx_step_desc& s, hipStream_t st, const StepCacheArgs* store, const tfx_step_extra& ex) {
+// known-region blend, behind the update and in front of the step cache's store pass and the cursor advance (it reads the cursor).
+// ch: the change-map blend in the same place, its mask decided on the device from hold and cut (keep_mask is then NULL)
+int step_finish(const tfx_step_desc& s, hipStream_t st, const StepCacheArgs* store, const tfx_step_extra& ex,
+                const tfx_step_change* ch = nullptr) {
   const int64_t rows = (int64_t)s.dit.B * s.dit.S;
   void* v_prev = ex.v_prev;
   if (v_prev) {
@@ -688,7 +699,14 @@ int step_finish(const tfx_step_desc& s, hipStream_t st, const StepCacheArgs* sto
     TRY(sched_step(s.sampler == 1, s.dit.out, s.latents, const_cast<void*>(s.dit.xin), s.dit.in_channels, s.dit.out_channels, rows,
                    s.coef, s.step_ptr, 0, s.noise, st));
   }
-  if (ex.keep_mask) {
+  if (ch) {
+    if (s.sampler == 2)
+      TRY(change_map_blend(const_cast<void*>(s.dit.xin), s.dit.in_channels, ex.keep_x0, ex.keep_noise, ch->hold, ch->cut, s.dit.out_channels,
+                           rows, ex.keep_sigma, s.step_ptr, 0, nullptr, 0, st));
+    else
+      TRY(change_map_blend(s.latents, s.dit.out_channels, ex.keep_x0, ex.keep_noise, ch->hold, ch->cut, s.dit.out_channels, rows,
+                           ex.keep_sigma, s.step_ptr, 0, const_cast<void*>(s.dit.xin), s.dit.in_channels, st));
+  } else if (ex.keep_mask) {
     if (s.sampler == 2)                                          // the fused Euler form keeps the latents in xin[:, :out_channels]
       TRY(known_region_blend(const_cast<void*>(s.dit.xin), s.dit.in_channels, ex.keep_x0, ex.keep_noise, ex.keep_mask, s.dit.out_channels,
                              rows, ex.keep_sigma, s.step_ptr, 0, nullptr, 0, st));
@@ -707,11 +725,11 @@ int step_forward(const tfx_step_desc& s, int first, int last, int flags, hipStre
   return tfx_dit_forward(&d, (tfx_stream)st);
 }
 
-int step_enqueue(const tfx_step_desc& s, hipStream_t st, const tfx_step_extra& ex) {
+int step_enqueue(const tfx_step_desc& s, hipStream_t st, const tfx_step_extra& ex, const tfx_step_change* ch = nullptr) {
   if (s.phase == 0) {
     TRY(select_step(s.mod_table, s.mod_cur, s.mod_step_elems, s.step_ptr, st));
     TRY(tfx_dit_forward(&s.dit, (tfx_stream)st));
-    return step_finish(s, st, nullptr, ex);
+    return step_finish(s, st, nullptr, ex, ch);
   }
   StepCacheArgs a;
   TRY(step_cache_view(s, a));
@@ -725,11 +743,11 @@ int step_enqueue(const tfx_step_desc& s, hipStream_t st, const tfx_step_extra& e
       return step_cache_metric(a, st);
     case 2:   // computed tail: the rest of the whole step, then r and f_prev
       TRY(step_forward(s, 1, -1, 1, st));
-      return step_finish(s, st, &a, ex);
+      return step_finish(s, st, &a, ex, ch);
     default:  // 3, cached tail: the last computed step's residual stands in for blocks [1, n)
       TRY(step_cache_apply(a, st));
       TRY(step_forward(s, nblk, nblk, 1, st));
-      return step_finish(s, st, nullptr, ex);
+      return step_finish(s, st, nullptr, ex, ch);
   }
 }
 
@@ -767,14 +785,40 @@ int step_check_ex(const tfx_step_desc* s, const tfx_step_extra* ex) {
   return 0;
 }
 
-int step_capture(const tfx_step_desc* s, const tfx_step_extra& ex, tfx_stream stream, tfx_graph* out) {
+// the _ex2 entry points: change NULL is _ex; else keep_x0 / keep_noise / keep_sigma set, keep_mask NULL, hold and cut set, not with
+// dit.seq_len, and none of them aliasing a buffer the step writes
+int step_check_ex2(const tfx_step_desc* s, const tfx_step_extra* ex, const tfx_step_change* ch) {
+  if (!ch) return step_check_ex(s, ex);
+  if (!ex) return fail("tfx_dit_step (ex2): null tfx_step_extra: the change-map blend reads keep_x0, keep_noise and keep_sigma from it");
+  if (ex->v_prev) TRY(step_check_multistep(s, ex->v_prev)); else TRY(step_check(s));
+  if (!ch->hold || !ch->cut) return fail("tfx_dit_step (ex2): change->hold and change->cut must both be set");
+  if (!ex->keep_x0 || !ex->keep_noise || !ex->keep_sigma) return fail("tfx_dit_step (ex2): with change, keep_x0, keep_noise and keep_sigma must be set");
+  if (ex->keep_mask) return fail("tfx_dit_step (ex2): with change, keep_mask must be NULL: the mask is decided on the device from hold and cut");
+  const tfx_dit_desc& d = s->dit;
+  if (d.seq_len) return fail("tfx_dit_step (ex2): the change-map blend cannot serve a mixed-geometry batch (dit.seq_len): its buffers are [B * S, C] without padding rows");
+  if (!d.xin) return fail("tfx_dit_step (ex2): dit.xin is null");
+  const int64_t rows = (int64_t)d.B * d.S, kb = rows * d.out_channels * 2;
+  const struct { const void* p; int64_t bytes; } written[4] = {{s->latents, kb}, {d.out, kb}, {d.xin, rows * d.in_channels * 2}, {ex->v_prev, kb}};
+  const struct { const void* p; int64_t bytes; } read[5] = {{ex->keep_x0, kb}, {ex->keep_noise, kb}, {ex->keep_sigma, 4}, {ch->hold, rows * 4}, {ch->cut, 4}};
+  for (const auto& r : read) {
+    const char* p = (const char*)r.p;
+    for (const auto& w : written) {
+      const char* q = (const char*)w.p;
+      if (q && (p == q || (p < q + w.bytes && q < p + r.bytes)))
+        return fail("tfx_dit_step (ex2): keep_x0, keep_noise, keep_sigma, hold and cut must not alias latents, dit.out, dit.xin or v_prev");
+    }
+  }
+  return 0;
+}
+
+int step_capture(const tfx_step_desc* s, const tfx_step_extra& ex, tfx_stream stream, tfx_graph* out, const tfx_step_change* ch = nullptr) {
   if (!out) return fail("tfx_dit_step_capture: null output handle");
   if (!stream) return fail("tfx_dit_step_capture: the NULL stream cannot be captured; pass a created stream");
   hipStream_t st = S(stream);
   (void)attention_w4_prepare(st);   // the attention kernel's scratch (of this stream) cannot be allocated inside a capture
   hipError_t e = hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal);
   if (e != hipSuccess) return fail("tfx_dit_step_capture: hipStreamBeginCapture: %s", hipGetErrorString(e));
-  const int rc = step_enqueue(*s, st, ex);
+  const int rc = step_enqueue(*s, st, ex, ch);
   hipGraph_t g = nullptr;
   e = hipStreamEndCapture(st, &g);
   if (rc) { if (g) (void)hipGraphDestroy(g); return rc; }    // last error already set by the failing launcher
@@ -819,6 +863,16 @@ int tfx_dit_step_run_ex(const tfx_step_desc* s, const tfx_step_extra* ex, tfx_st
 int tfx_dit_step_capture_ex(const tfx_step_desc* s, const tfx_step_extra* ex, tfx_stream stream, tfx_graph* out) {
   TRY(step_check_ex(s, ex));
   return step_capture(s, *ex, stream, out);
+}
+
+int tfx_dit_step_run_ex2(const tfx_step_desc* s, const tfx_step_extra* ex, const tfx_step_change* ch, tfx_stream stream) {
+  TRY(step_check_ex2(s, ex, ch));
+  return step_enqueue(*s, S(stream), *ex, ch);
+}
+
+int tfx_dit_step_capture_ex2(const tfx_step_desc* s, const tfx_step_extra* ex, const tfx_step_change* ch, tfx_stream stream, tfx_graph* out) {
+  TRY(step_check_ex2(s, ex, ch));
+  return step_capture(s, *ex, stream, out, ch);
 }
 
 int tfx_dit_step_replay(tfx_graph graph, tfx_stream stream) {

@@ -342,6 +342,58 @@ __global__ __launch_bounds__(256) void known_region_blend_kernel(bf16_t* __restr
   if (xin) *reinterpret_cast<u32x4*>(xin + row * ldxin + col) = packed;
 }
 
+// Change-map blend behind a sampler update (FluxDifferentialImg2ImgPipeline's loop, D/examples/community/
+// pipeline_flux_differential_img2img.py:974-986; DESIGN.md section 4 "Change-map sampling"): known_region_blend_kernel with the mask
+// decided here from the step cursor.  hold [rows] is one 32-bit word per token, byte py*2+px = 255 - map of that latent pixel; a
+// thread's 8 columns are two channels x the four patch positions, so column j reads byte j & 3.  k = hold > cut[step] ? 1 : 0,
+//   p as above;  e = bf16(p k)   w = bf16(1 - k)   d = bf16(x w)   x' = bf16(e + d)
+// the reference's `image_latent * mask + latents * (1 - mask)` op by op, no select: p * 0 keeps p's sign in a -0.  cut[step] >= 255:
+// nothing is held and x is not written (the reference's last step leaves the latents alone; e + d would turn a -0 into +0); the
+// mirror into xin is still made.
+__global__ __launch_bounds__(256) void change_map_blend_kernel(bf16_t* __restrict__ x, int64_t ldx, const bf16_t* __restrict__ x0,
+                                                               const bf16_t* __restrict__ noise, const uint32_t* __restrict__ hold,
+                                                               const int* __restrict__ cut, int C, int64_t nchunks,
+                                                               const float* __restrict__ keep_sigma, const int* __restrict__ step_ptr,
+                                                               int step, bf16_t* __restrict__ xin, int64_t ldxin) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= nchunks) return;
+  const int cur = step_ptr ? *step_ptr : step;
+  const float s = keep_sigma[cur];
+  const int ct = cut[cur];
+  const int64_t e0 = i * 8;
+  const int64_t row = e0 / C;
+  const int col = (int)(e0 - row * C);
+  bf16_t* xp = x + row * ldx + col;
+  const u32x4 xraw = *reinterpret_cast<const u32x4*>(xp);
+  if (ct >= 255) {
+    if (xin) *reinterpret_cast<u32x4*>(xin + row * ldxin + col) = xraw;
+    return;
+  }
+  const uint32_t hw = hold[row];
+  float xx[8], zz[8], p[8], o[8];
+  unpack8(xraw, xx);
+  unpack8(*reinterpret_cast<const u32x4*>(x0 + e0), zz);
+  if (s < 0.f) {
+#pragma unroll
+    for (int j = 0; j < 8; ++j) p[j] = zz[j];
+  } else {
+    float nn[8];
+    unpack8(*reinterpret_cast<const u32x4*>(noise + e0), nn);
+    const float u = round_bf(__fsub_rn(1.0f, s));
+#pragma unroll
+    for (int j = 0; j < 8; ++j) p[j] = round_bf(__fadd_rn(round_bf(__fmul_rn(s, nn[j])), round_bf(__fmul_rn(u, zz[j]))));
+  }
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    const float k = (int)((hw >> (8 * (j & 3))) & 0xffu) > ct ? 1.0f : 0.0f;
+    const float w = __fsub_rn(1.0f, k);                 // 1 or 0: exact in bf16
+    o[j] = __fadd_rn(round_bf(__fmul_rn(p[j], k)), round_bf(__fmul_rn(xx[j], w)));
+  }
+  const u32x4 packed = pack8(o);
+  *reinterpret_cast<u32x4*>(xp) = packed;
+  if (xin) *reinterpret_cast<u32x4*>(xin + row * ldxin + col) = packed;
+}
+
 // Sinusoidal timestep embedding, flip_sin_to_cos=True, downscale_freq_shift=0, dim 256, fp32 -> bf16
 // (get_timestep_embedding, D/models/embeddings.py:27-78 as configured at :1322).  out[n, 256] = cos | sin.
 __global__ void timestep_embedding_kernel(const float* __restrict__ t, bf16_t* __restrict__ out, int n) {
@@ -714,6 +766,34 @@ int known_region_blend(void* x, int64_t ldx, const void* x0, const void* noise, 
                                                                                  (const bf16_t*)mask, C, nch, keep_sigma, step_ptr, step,
                                                                                  (bf16_t*)xin, ldxin);
   return check_launch("known_region_blend");
+}
+
+int change_map_blend(void* x, int64_t ldx, const void* x0, const void* noise, const void* hold, const int* cut, int C, int64_t rows,
+                     const float* keep_sigma, const int* step_ptr, int step, void* xin, int64_t ldxin, hipStream_t st) {
+  if (C <= 0 || C % 8) return fail("change_map_blend: C must be a positive multiple of 8");
+  if (rows < 0) return fail("change_map_blend: negative row count");
+  if (ldx % 8 || ldx < C) return fail("change_map_blend: ldx must be a multiple of 8 and >= C");               // 16-byte accesses to x rows
+  if (xin && (ldxin % 8 || ldxin < C)) return fail("change_map_blend: ldxin must be a multiple of 8 and >= C");
+  const int64_t nch = rows * C / 8;
+  if (nch == 0) return 0;                               // nothing to blend: the pointers of empty tensors mean nothing
+  if (!x || !x0 || !noise || !hold || !cut || !keep_sigma) return fail("change_map_blend: null pointer");
+  if (((uintptr_t)x | (uintptr_t)x0 | (uintptr_t)noise | (uintptr_t)xin) & 15)
+    return fail("change_map_blend: x, x0, noise and xin must be 16-byte aligned");
+  if (((uintptr_t)hold | (uintptr_t)cut | (uintptr_t)keep_sigma) & 3) return fail("change_map_blend: hold, cut and keep_sigma must be 4-byte aligned");
+  const char* px = (const char*)x;
+  const int64_t xbytes = ((rows - 1) * ldx + C) * 2, bytes = nch * 16;
+  for (const void* q : {x0, noise}) {
+    const char* p = (const char*)q;
+    if (p < px + xbytes && px < p + bytes) return fail("change_map_blend: x0 and noise must not alias x");
+  }
+  const char* ph = (const char*)hold;
+  const char* pi = (const char*)xin;
+  if ((ph < px + xbytes && px < ph + rows * 4) || (pi && ph < pi + ((rows - 1) * ldxin + C) * 2 && pi < ph + rows * 4))
+    return fail("change_map_blend: hold must not alias x or xin");
+  change_map_blend_kernel<<<dim3((unsigned)((nch + 255) / 256)), 256, 0, st>>>((bf16_t*)x, ldx, (const bf16_t*)x0, (const bf16_t*)noise,
+                                                                               (const uint32_t*)hold, cut, C, nch, keep_sigma, step_ptr, step,
+                                                                               (bf16_t*)xin, ldxin);
+  return check_launch("change_map_blend");
 }
 
 int timestep_embedding(const float* t, void* out, int n, hipStream_t st) {

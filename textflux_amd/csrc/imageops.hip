@@ -138,6 +138,46 @@ __global__ __launch_bounds__(256) void keep_mask_pack_kernel(const uint8_t* __re
   for (int c8 = 0; c8 < C / 8; ++c8) *reinterpret_cast<u32x4*>(o + c8 * 8) = packed;
 }
 
+// The hold bytes of change-map sampling: map [B, H, W] uint8 (255 = free from the first step, 0 = never changes)
+// -> hold [B, S, 4] uint8, hold[b, t, py*2+px] = 255 - g(2ty+py, 2tx+px); keep_mask_pack_kernel carried over to grey values.
+//   mode 0  nearest, the reference's F.interpolate: g(ly, lx) = map[8 ly, 8 lx]
+//   mode 1  cover: g = the maximum of map over the 8x8 blocks of latent pixels [ly-grow, ly+grow] x [lx-grow, lx+grow] (clipped)
+// One thread = one token, one 32-bit store; each block row one 8-byte load, the byte maximum taken on the two 4-byte halves.
+__global__ __launch_bounds__(256) void change_map_pack_kernel(const uint8_t* __restrict__ map, uint32_t* __restrict__ hold, int B, int H,
+                                                              int W, int mode, int grow) {
+  const int h = H / 8, w = W / 8, h2 = H / 16, w2 = W / 16;
+  const int64_t S = (int64_t)h2 * w2;
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= B * S) return;
+  const int b = (int)(i / S);
+  const int t = (int)(i - b * S);
+  const int ty = t / w2, tx = t - ty * w2;
+  const uint8_t* mb = map + (int64_t)b * H * W;
+  uint32_t word = 0;
+#pragma unroll
+  for (int pp = 0; pp < 4; ++pp) {
+    const int ly = 2 * ty + (pp >> 1), lx = 2 * tx + (pp & 1);
+    uint32_t g;
+    if (mode == 0) {
+      g = mb[(int64_t)ly * 8 * W + lx * 8];
+    } else {
+      const int r0 = max(ly - grow, 0) * 8, r1 = (min(ly + grow, h - 1) + 1) * 8;
+      const int c0 = max(lx - grow, 0), c1 = min(lx + grow, w - 1);
+      g = 0;
+      for (int r = r0; r < r1; ++r) {
+        const uint64_t* rowp = reinterpret_cast<const uint64_t*>(mb + (int64_t)r * W);
+        for (int c = c0; c <= c1; ++c) {
+          const uint64_t v = rowp[c];
+#pragma unroll
+          for (int k = 0; k < 8; ++k) g = max(g, (uint32_t)(v >> (8 * k)) & 0xffu);
+        }
+      }
+    }
+    word |= (255u - g) << (8 * pp);
+  }
+  hold[i] = word;
+}
+
 // moments NHWC [B, h, w, 2L] (mean | logvar) bf16, eps [B, L, h, w] bf16 or fp32 (null: the mode) ->
 // out[b, t, col0 + c*4 + py*2+px] = bf16chain( (mean + exp(0.5 * clamp(logvar)) * eps - shift) * scale ) at pixel
 // (2ty+py, 2tx+px); every intermediate rounded to bf16 as the reference's bf16 tensor ops round them
@@ -1408,6 +1448,19 @@ int keep_mask_pack(const void* mask_u8, void* out, int B, int H, int W, int C, i
   if (((uintptr_t)mask_u8 & 7) || ((uintptr_t)out & 15)) return fail("keep_mask_pack: mask must be 8-byte and out 16-byte aligned");
   keep_mask_pack_kernel<<<blocks_for(n), 256, 0, st>>>((const uint8_t*)mask_u8, (bf16_t*)out, B, H, W, C, mode, grow);
   return check_launch("keep_mask_pack");
+}
+
+int change_map_pack(const void* map_u8, void* hold, int B, int H, int W, int mode, int grow, hipStream_t st) {
+  if (B < 0 || H < 0 || W < 0 || H % 16 || W % 16) return fail("change_map_pack: B >= 0; H and W non-negative multiples of 16");
+  if (mode != 0 && mode != 1) return fail("change_map_pack: mode must be 0 (nearest) or 1 (cover)");
+  if (mode == 0 && grow != 0) return fail("change_map_pack: grow must be 0 in mode 0 (nearest)");
+  if (grow < 0 || grow > 8) return fail("change_map_pack: grow %d outside 0..8", grow);
+  const int64_t n = (int64_t)B * (H / 16) * (W / 16);
+  if (n == 0) return 0;
+  if (!map_u8 || !hold) return fail("change_map_pack: null pointer");
+  if (((uintptr_t)map_u8 & 7) || ((uintptr_t)hold & 3)) return fail("change_map_pack: map must be 8-byte and hold 4-byte aligned");
+  change_map_pack_kernel<<<blocks_for(n), 256, 0, st>>>((const uint8_t*)map_u8, (uint32_t*)hold, B, H, W, mode, grow);
+  return check_launch("change_map_pack");
 }
 
 int sample_pack(const void* moments, const void* eps, int eps_dtype, void* out, int B, int h, int w, int L, float shift,

@@ -198,6 +198,10 @@ int multistep_step(const void* v, void* x, void* xin, int64_t ldxin, int C, int6
 // x [rows, C] with pitch ldx, mirrored into xin[:, :C] when given; a negative keep_sigma entry stands for "x0 itself"
 int known_region_blend(void* x, int64_t ldx, const void* x0, const void* noise, const void* mask, int C, int64_t rows,
                        const float* keep_sigma, const int* step_ptr, int step, void* xin, int64_t ldxin, hipStream_t st);
+// change-map blend behind a sampler update: known_region_blend with the mask decided on the device, k = hold[row, col & 3] > cut[step]
+// (hold u8 [rows, 4], cut int32 [n_steps]); x <- p k + x (1 - k), bf16 per op; cut[step] >= 255 leaves x unwritten (xin still mirrored)
+int change_map_blend(void* x, int64_t ldx, const void* x0, const void* noise, const void* hold, const int* cut, int C, int64_t rows,
+                     const float* keep_sigma, const int* step_ptr, int step, void* xin, int64_t ldxin, hipStream_t st);
 int timestep_embedding(const float* t, void* out, int n, hipStream_t st);
 int silu_bf16(const void* a, void* out, int64_t n, hipStream_t st);
 int add_bf16(const void* a, const void* b, void* out, int64_t n, hipStream_t st);
@@ -257,6 +261,8 @@ int pack_mask(const void* mask, int mask_dtype, void* out, int B, int H, int W, 
               hipStream_t st);
 // uint8 pixel mask [B, H, W] -> packed latent mask bf16 [B, (H/16)(W/16), C] of 1.0 / 0.0; mode 0 nearest (grow 0), 1 cover (grow 0..8)
 int keep_mask_pack(const void* mask_u8, void* out, int B, int H, int W, int C, int mode, int grow, hipStream_t st);
+// uint8 change map [B, H, W] -> hold u8 [B, (H/16)(W/16), 4] = 255 - map per latent pixel; mode 0 nearest (grow 0), 1 cover = maximum (grow 0..8)
+int change_map_pack(const void* map_u8, void* hold, int B, int H, int W, int mode, int grow, hipStream_t st);
 int sample_pack(const void* moments, const void* eps, int eps_dtype, void* out, int B, int h, int w, int L, float shift,
                 float scale, int64_t ld, int col0, hipStream_t st);
 int unpack_latents(const void* lat, int64_t ld, void* out, int B, int h, int w, int L, float shift, float scale, hipStream_t st);

@@ -449,6 +449,38 @@ def known_region_blend(x: torch.Tensor, x0: torch.Tensor, noise: torch.Tensor, m
     return x
 
 
+def change_map_blend(x: torch.Tensor, x0: torch.Tensor, noise: torch.Tensor, hold: torch.Tensor, cut: torch.Tensor,
+                     keep_sigma: torch.Tensor, step: int = 0, step_ptr: Optional[torch.Tensor] = None,
+                     xin: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """x <- p k + x (1 - k) in place with p = scale_noise(x0, keep_sigma[step], noise) and k = hold[row, col & 3] > cut[step], one bf16
+    rounding per op as the reference's tensor ops (tfx_change_map_blend).  x [.., rows, C] may be a column view; x0 / noise contiguous
+    of x's shape; hold uint8 [.., rows, 4] contiguous (change_map_pack); cut int32 [n] (schedulers.change_cut_table) and keep_sigma
+    fp32 [n] of one length.  cut[step] >= 255 leaves x unwritten; xin, the x_embedder input, is mirrored into either way."""
+    _chk_dev(x, x0, noise, hold, cut, keep_sigma, step_ptr, xin)
+    if any(t.dtype != BF16 for t in (x, x0, noise)) or (xin is not None and xin.dtype != BF16):
+        raise TypeError("change_map_blend: bf16 latents and noise")
+    if keep_sigma.dtype != torch.float32 or not keep_sigma.is_contiguous() or keep_sigma.dim() != 1:
+        raise TypeError("change_map_blend: keep_sigma is a contiguous fp32 vector")
+    if cut.dtype != torch.int32 or not cut.is_contiguous() or cut.shape != keep_sigma.shape:
+        raise TypeError("change_map_blend: cut is a contiguous int32 vector of keep_sigma's length")
+    if not (x0.shape == noise.shape == x.shape) or not (x0.is_contiguous() and noise.is_contiguous()):
+        raise ValueError("change_map_blend: x0 and noise must be contiguous and of x's shape")
+    Cc = x.shape[-1]
+    rows, ldx = _flat_rows(x, "change_map_blend: x")
+    if hold.dtype != torch.uint8 or not hold.is_contiguous() or hold.numel() != rows * 4 or hold.shape[-1] != 4:
+        raise ValueError(f"change_map_blend: hold must be contiguous uint8 [.., {rows}, 4]")
+    ldxin = 0
+    if xin is not None:
+        rin, ldxin = _flat_rows(xin, "change_map_blend: xin")
+        if rin != rows:
+            raise ValueError(f"change_map_blend: xin has {rin} rows, x {rows}")
+    if step_ptr is None and not 0 <= step < keep_sigma.numel():
+        raise ValueError(f"change_map_blend: step {step} outside the tables of {keep_sigma.numel()} steps")
+    L.check(L.lib().tfx_change_map_blend(x.data_ptr(), ldx, x0.data_ptr(), noise.data_ptr(), hold.data_ptr(), cut.data_ptr(), Cc, rows,
+                                         keep_sigma.data_ptr(), _p(step_ptr), step, _p(xin), ldxin, _stream()), "change_map_blend")
+    return x
+
+
 def timestep_embedding(t: torch.Tensor) -> torch.Tensor:
     _chk_dev(t)
     t = t.contiguous().float()
@@ -1137,6 +1169,24 @@ def keep_mask_pack(mask_u8: torch.Tensor, C: int = 64, mode="nearest", grow: int
         raise ValueError(f"keep_mask_pack: H and W must be multiples of 16, got {H} x {W}")
     out = torch.empty(B, (H // 16) * (W // 16), C, dtype=BF16, device=mask_u8.device)
     L.check(L.lib().tfx_keep_mask_pack(mask_u8.data_ptr(), out.data_ptr(), B, H, W, C, int(mode), int(grow), _stream()), "keep_mask_pack")
+    return out
+
+
+def change_map_pack(map_u8: torch.Tensor, mode="nearest", grow: int = 0) -> torch.Tensor:
+    """uint8 change map [B, H, W] (255 = free from the first step, 0 = never changes) -> the hold bytes of change-map sampling, uint8
+    [B, (H/16)(W/16), 4] = 255 - map per latent pixel of each token's 2x2 patch (tfx_change_map_pack).  mode "nearest" (0): the map at
+    every 8th pixel, the reference's F.interpolate, grow must be 0; "cover" (1): the maximum of the map over the latent pixel's 8x8
+    block and those of its `grow` neighbours (0..8)."""
+    _chk_dev(map_u8)
+    if map_u8.dtype != torch.uint8 or map_u8.dim() != 3:
+        raise TypeError("change_map_pack: the map is uint8 [B, H, W]")
+    mode = KEEP_MODES.get(mode, mode)
+    map_u8 = map_u8.contiguous()
+    B, H, W = map_u8.shape
+    if H % 16 or W % 16:
+        raise ValueError(f"change_map_pack: H and W must be multiples of 16, got {H} x {W}")
+    out = torch.empty(B, (H // 16) * (W // 16), 4, dtype=torch.uint8, device=map_u8.device)
+    L.check(L.lib().tfx_change_map_pack(map_u8.data_ptr(), out.data_ptr(), B, H, W, int(mode), int(grow), _stream()), "change_map_pack")
     return out
 
 

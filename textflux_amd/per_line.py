@@ -156,7 +156,7 @@ def edit_scene(pipe, scene, mask, texts: Sequence[str], cfg: Dict[str, Any], num
                seed: int = 42, device=None, max_sequence_length: int = 512, call_kw: Optional[Dict[str, Any]] = None):
     """One scene outside the batch driver (run_inference.py): -> (the scene with all lines pasted in, [every line's raw canvas]).
     Lines of equal editing size go through one pipeline call each; every line has the generator of a single-image call.  call_kw:
-    further keyword arguments of every pipeline call (keep_known, strength)."""
+    further keyword arguments of every pipeline call (keep_known, strength, change_map)."""
     import torch
     from . import batch_driver as bd
     device = device if device is not None else getattr(pipe, "_execution_device", "cuda")

@@ -24,7 +24,7 @@ import torch
 
 from . import ops, step_loop
 from .image_processor import VaeImageProcessor
-from .schedulers import FlowMatchEulerDiscreteScheduler, FlowMatchMultistepScheduler, StochasticRFOvershotDiscreteScheduler
+from .schedulers import FlowMatchEulerDiscreteScheduler, FlowMatchMultistepScheduler, StochasticRFOvershotDiscreteScheduler, change_cut_table
 from .transformer import EULER_PAD, FluxTransformer2DModel
 
 BF16 = torch.bfloat16
@@ -125,6 +125,37 @@ def _keep_known_cfg(keep_known):
     if grow < 0 or grow > 8 or (mode == "nearest" and grow != 0):
         raise ValueError("keep_known: grow is 0 for mode 'nearest' and 0..8 for mode 'cover'")
     return mode, grow
+
+
+CHANGE_MAP_KEYS = ("map", "dilate", "feather", "mode", "grow", "last")
+
+
+def _change_map_cfg(change_map):
+    """change_map = None / False | True | a grey image / uint8 array / uint8 tensor | dict(map=..., dilate=D, feather=F,
+    mode="nearest" | "cover", grow=N, last="keep" | "free") -> None | dict(map, dilate, feather, mode, grow, last).  map None: the map
+    is derived from the call's mask_image as feather(dilate(mask >= 128)), the paste-back's alpha (dilate / feather default to the
+    paste-back's: starting points, not tuned values)."""
+    if change_map is None or change_map is False:
+        return None
+    from .paste_back import DILATE, FEATHER
+    cfg = {} if change_map is True else dict(change_map) if isinstance(change_map, dict) else dict(map=change_map)
+    unknown = sorted(k for k in cfg if k not in CHANGE_MAP_KEYS)
+    if unknown:
+        raise ValueError(f"change_map: unknown keys {unknown}")
+    given = cfg.get("map")
+    if given is not None and ("dilate" in cfg or "feather" in cfg):
+        raise ValueError("change_map: dilate / feather derive the map from mask_image and do not go with an explicit map")
+    out = dict(map=given, dilate=int(cfg.get("dilate", DILATE)), feather=int(cfg.get("feather", FEATHER)), mode=cfg.get("mode", "nearest"),
+               grow=int(cfg.get("grow", 0)), last=cfg.get("last", "keep"))
+    if out["mode"] not in ("nearest", "cover"):
+        raise ValueError(f"change_map: mode must be 'nearest' or 'cover', got {out['mode']!r}")
+    if out["grow"] < 0 or out["grow"] > 8 or (out["mode"] == "nearest" and out["grow"] != 0):
+        raise ValueError("change_map: grow is 0 for mode 'nearest' and 0..8 for mode 'cover'")
+    if out["last"] not in ("keep", "free"):
+        raise ValueError(f"change_map: last must be 'keep' or 'free', got {out['last']!r}")
+    if out["dilate"] < 0 or out["feather"] < 0:
+        raise ValueError("change_map: dilate and feather must be >= 0")
+    return out
 
 
 class FluxFillPipeline:
@@ -541,7 +572,8 @@ class FluxFillPipeline:
         """Session, conditioning, modulation table, x_embedder input, then the step loop (step_loop.denoise).  The loop starts at
         step 0 of `timesteps`: _call_body sets the timesteps directly in front of it, which clears the scheduler's begin_index --
         unless the call gave `strength` / `keep_known`: then get_timesteps set it, `timesteps` and the scheduler's tables start at that
-        step, and `keep` (dict x0 / noise / mask, or x0 / noise alone for a strength-only call) goes to the loop's blend."""
+        step, and `keep` (dict x0 / noise / mask, or x0 / noise alone for a strength-only call) goes to the loop's blend; with hold
+        and last in place of mask (`change_map`) it becomes the loop's `change`, with the cut table of the steps that run."""
         tr, sch = self.transformer, self.scheduler
         dev = tr.device
         B, S, C = latents.shape
@@ -574,10 +606,18 @@ class FluxFillPipeline:
                     prompt_embeds = new_pe
                     ses.set_conditioning(prompt_embeds.to(dev, BF16), text_ids, latent_image_ids)
         sch._step_index = sch.begin_index or 0
-        if keep is not None and "mask" in keep:
+        change = None
+        if keep is not None and "hold" in keep:
+            change = dict(x0=keep["x0"], noise=keep["noise"], hold=keep["hold"], sigma=sch.keep_sigma_table(dev, BF16),
+                          cut=change_cut_table(n, keep["last"]).to(dev))
+            keep = None
+        elif keep is not None and "mask" in keep:
             keep = dict(keep, sigma=sch.keep_sigma_table(dev, BF16))
         else:
             keep = None
+        if change is not None:
+            return step_loop.denoise(self, ses, mod, latents, coef, n, progress_bar, is_amo, fuse, amo_noise, on_step, multistep, keep,
+                                     change)
         return step_loop.denoise(self, ses, mod, latents, coef, n, progress_bar, is_amo, fuse, amo_noise, on_step, multistep, keep)
 
     # ------------------------------------------------------------------ known-region sampling
@@ -591,11 +631,11 @@ class FluxFillPipeline:
         return timesteps, num_inference_steps - t_start
 
     def _prepare_known_region(self, noise, given_latents, image_latents, image, mask_image, keep_cfg, strength, height, width, dtype,
-                              device, generator):
+                              device, generator, change_cfg=None):
         """The original's latents x0, the start of a strength < 1 call and the loop's keep buffers.  x0: `image_latents`, or the VAE
         latents of the UNMASKED preprocessed image (posterior sample, shift / scale, pack) -- drawn here, after every draw the plain
         call makes.  noise: the initial noise (caller-given latents are both noise and start: the reference's quirk, :586-588).
-        Returns (start latents, dict(x0, noise[, mask]))."""
+        Returns (start latents, dict(x0, noise[, mask])); with change_cfg (`change_map`) the dict carries hold and last instead of mask."""
         dev = self._execution_device
         total = noise.shape[0]
         if image_latents is not None:
@@ -643,7 +683,49 @@ class FluxFillPipeline:
             if mk.shape != x0.shape:
                 raise ValueError(f"mask_image packs to {tuple(mk.shape)}, the latents are {tuple(x0.shape)}")
             keep["mask"] = mk
+        if change_cfg is not None:
+            keep["hold"] = self._change_hold(change_cfg, mask_image, height, width, total, x0.shape[1], dev)
+            keep["last"] = change_cfg["last"]
         return start, keep
+
+    # ------------------------------------------------------------------ change-map sampling
+    def change_map_u8(self, change_cfg, mask_image, height, width, device):
+        """The call's change map, uint8 [B, height, width] on the device (255 = free from the first step, 0 = never changes): the
+        explicit map of the configuration, or feather(dilate(mask_image >= 128)) -- the paste-back's alpha of the same mask."""
+        given = change_cfg["map"]
+        if given is None:
+            if mask_image is None:
+                raise ValueError("change_map needs `mask_image` (the map is derived from it) or an explicit map")
+            rawm = self.mask_processor.to_raw(mask_image, height=height, width=width).to(device)
+            if rawm.dtype != torch.uint8:
+                rawm = (rawm.reshape(rawm.shape[0], rawm.shape[-2], rawm.shape[-1]) >= 0.5).to(torch.uint8) * 255
+            from .paste_back import alpha_mask
+            return alpha_mask(rawm.contiguous(), change_cfg["dilate"], change_cfg["feather"])
+        if isinstance(given, np.ndarray):
+            given = torch.from_numpy(np.ascontiguousarray(given))
+        if isinstance(given, torch.Tensor):
+            if given.dtype != torch.uint8 or given.dim() not in (2, 3):
+                raise ValueError(f"change_map: an array / tensor map must be uint8 [H, W] or [B, H, W], got {given.dtype} {tuple(given.shape)}")
+            m = given if given.dim() == 3 else given[None]
+        else:
+            m = self.mask_processor.to_raw(given, height=height, width=width)
+            if m.dtype != torch.uint8 or m.dim() != 3:
+                raise ValueError("change_map: the map must be an 8-bit grey image, a uint8 array or a uint8 tensor")
+        if tuple(m.shape[1:]) != (height, width):
+            raise ValueError(f"change_map: the map is {tuple(m.shape[1:])}, the call asks for {(height, width)}")
+        return m.to(device).contiguous()
+
+    def _change_hold(self, change_cfg, mask_image, height, width, total, S, device):
+        """-> the hold bytes uint8 [total, S, 4] of the call (ops.change_map_pack of its change map), duplicated like a mask"""
+        hold = ops.change_map_pack(self.change_map_u8(change_cfg, mask_image, height, width, device), change_cfg["mode"], change_cfg["grow"])
+        if hold.shape[0] < total:
+            if total % hold.shape[0]:
+                raise ValueError("The passed change_map and the required batch size don't match. Maps are supposed to be duplicated to"
+                                 f" a total batch size of {total}, but {hold.shape[0]} maps were passed.")
+            hold = hold.repeat(total // hold.shape[0], 1, 1)
+        if tuple(hold.shape) != (total, S, 4):
+            raise ValueError(f"change_map packs to {tuple(hold.shape)}, the latents have {(total, S)} tokens")
+        return hold.contiguous()
 
     def enable_hip_graph(self, on: bool = True):
         """Replay ONE captured hipGraph per denoising step (device-side step cursor: modulation rows and scheduler
@@ -823,7 +905,7 @@ class FluxFillPipeline:
                  callback_on_step_end: Optional[Callable] = None,
                  callback_on_step_end_tensor_inputs: List[str] = ["latents"], max_sequence_length: int = 512,
                  amo_noise: Optional[List[torch.Tensor]] = None, output_crop=None, strength: float = 1.0, keep_known=None,
-                 image_latents: Optional[torch.Tensor] = None):
+                 image_latents: Optional[torch.Tensor] = None, change_map=None):
         """Same arguments / defaults / return as the reference `__call__` (P:1850-1873, 2122-2137).  Additions:
         `amo_noise`, a list of pre-drawn eps tensors for the AMO sampler (replay across devices), and
         `output_crop` = (left, top, right, bottom), the callers' result crop (run_inference.py:460-465) applied on the
@@ -832,9 +914,18 @@ class FluxFillPipeline:
         `strength` in [0, 1] starts the loop part-way down the sigma grid from the noised original and runs int(n * strength)
         steps; `keep_known` = True or dict(mode="nearest" | "cover", grow=int) replaces, after every step, the latents outside
         `mask_image` by the original's latents noised to the next sigma (the original itself on the last step); `image_latents`,
-        packed [B, S, 64], stands in for the VAE latents of `image` (needed when `image` is not given)."""
+        packed [B, S, 64], stands in for the VAE latents of `image` (needed when `image` is not given).
+        Change-map sampling (FluxDifferentialImg2ImgPipeline's loop on the Fill model, opt-in, no quality
+        claim): `change_map` gives every latent pixel its own release step -- a grey image / uint8 array / uint8 tensor at call size
+        (255 = the model's from the first step, 0 = never changes), or dict(map=..., dilate, feather, mode, grow, last); without
+        `map` it is feather(dilate(mask_image >= 128)), the paste-back's alpha.  A pixel is held to the noised original while its
+        map value lies below the loop's progress; last="keep" (default) ends held pixels as the original's latents, "free" is the
+        reference, whose last step belongs to the model.  Not with `keep_known`; with `strength` / `image_latents` as `keep_known`.
+        The Fill model's own conditioning still comes from the binary `mask_image`."""
         if strength < 0 or strength > 1:
             raise ValueError(f"The value of strength should in [0.0, 1.0] but is {strength}")
+        if _change_map_cfg(change_map) is not None and _keep_known_cfg(keep_known) is not None:
+            raise ValueError("change_map and keep_known exclude each other: one blend stands behind the sampler update")
         height = height or self.default_sample_size * self.vae_scale_factor
         width = width or self.default_sample_size * self.vae_scale_factor
         self.check_inputs(prompt, prompt_2, height, width, prompt_embeds=prompt_embeds,
@@ -857,7 +948,7 @@ class FluxFillPipeline:
                                    sigmas, guidance_scale, num_images_per_prompt, generator, latents, prompt_embeds,
                                    pooled_prompt_embeds, output_type, return_dict, callback_on_step_end,
                                    callback_on_step_end_tensor_inputs, max_sequence_length, amo_noise, output_crop, strength,
-                                   keep_known, image_latents)
+                                   keep_known, image_latents, change_map)
         finally:
             if lora_scale is not None:
                 self.transformer._write_scales(prev_lora_scale)
@@ -869,7 +960,8 @@ class FluxFillPipeline:
                    prompt_embeds: Optional[torch.Tensor] = None, pooled_prompt_embeds: Optional[torch.Tensor] = None,
                    output_type: Optional[str] = "pil", return_dict: bool = True, callback_on_step_end: Optional[Callable] = None,
                    max_sequence_length: int = 512, latents: Optional[List[torch.Tensor]] = None,
-                   masked_image_latents: Optional[List[torch.Tensor]] = None, strength: float = 1.0, keep_known=None):
+                   masked_image_latents: Optional[List[torch.Tensor]] = None, strength: float = 1.0, keep_known=None,
+                   change_map=None):
         """One denoising run over samples of DIFFERENT sizes (no reference counterpart: the reference, like `__call__`, runs one
         geometry per call).  image / mask_image: one entry per sample, sizes[b] = (width, height) of sample b (multiples of 16).
         Every sample computes what its own single-image `__call__` computes -- its own latent noise and VAE posterior sample from
@@ -882,6 +974,9 @@ class FluxFillPipeline:
         Needs the flow-matching Euler scheduler with fuse_euler_step (only the fused Euler step carries per-sample coefficients) and
         no step callback."""
         sch, tr = self.scheduler, self.transformer
+        if change_map is not None and change_map is not False:
+            raise NotImplementedError("call_mixed: change_map (change-map sampling) is not supported in mixed-geometry batches (the "
+                                      "blend's buffers carry no padding rows); use __call__")
         if strength != 1.0 or keep_known:
             raise NotImplementedError("call_mixed: strength / keep_known (known-region sampling) are not supported in mixed-geometry "
                                       "batches (the blend's buffers carry no padding rows); use __call__")
@@ -993,7 +1088,7 @@ class FluxFillPipeline:
     def _call_body(self, prompt, prompt_2, image, mask_image, masked_image_latents, height, width, num_inference_steps, sigmas,
                    guidance_scale, num_images_per_prompt, generator, latents, prompt_embeds, pooled_prompt_embeds, output_type,
                    return_dict, callback_on_step_end, callback_on_step_end_tensor_inputs, max_sequence_length, amo_noise, output_crop,
-                   strength=1.0, keep_known=None, image_latents=None):
+                   strength=1.0, keep_known=None, image_latents=None, change_map=None):
         if prompt is not None and isinstance(prompt, str):
             batch_size = 1
         elif prompt is not None and isinstance(prompt, list):
@@ -1006,7 +1101,8 @@ class FluxFillPipeline:
             device=device, num_images_per_prompt=num_images_per_prompt, max_sequence_length=max_sequence_length)
         num_channels_latents = self.vae.config.latent_channels
         keep_cfg = _keep_known_cfg(keep_known)
-        known = keep_cfg is not None or strength < 1.0
+        change_cfg = _change_map_cfg(change_map)
+        known = keep_cfg is not None or change_cfg is not None or strength < 1.0
         given_latents = latents is not None
         src_image = image
         latents, latent_image_ids = self.prepare_latents(batch_size * num_images_per_prompt, num_channels_latents, height,
@@ -1033,13 +1129,14 @@ class FluxFillPipeline:
         keep = None
         if known:
             if not engine:
-                raise NotImplementedError("strength / keep_known need one of the engine's schedulers (their step loop holds the blend)")
+                raise NotImplementedError("strength / keep_known / change_map need one of the engine's schedulers (their step loop holds the blend)")
             timesteps, num_inference_steps = self.get_timesteps(num_inference_steps, strength, device)
             if num_inference_steps < 1:
                 raise ValueError(f"After adjusting the num_inference_steps by strength parameter: {strength}, the number of pipeline"
                                  f"steps is {num_inference_steps} which is < 1 and not appropriate for this pipeline.")
             latents, keep = self._prepare_known_region(latents, given_latents, image_latents, src_image, mask_image, keep_cfg, strength,
-                                                       height, width, prompt_embeds.dtype, device, generator)
+                                                       height, width, prompt_embeds.dtype, device, generator,
+                                                       **(dict(change_cfg=change_cfg) if change_cfg is not None else {}))
         self._num_timesteps = len(timesteps)
         with self.progress_bar(total=num_inference_steps) as bar:
             if engine:

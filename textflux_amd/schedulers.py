@@ -43,6 +43,31 @@ def _cfg_dict(config) -> dict:
     return dict(vars(config))
 
 
+def change_cut_table(n: int, last: str = "keep") -> torch.Tensor:
+    """int32 [n] for tfx_change_map_blend (DESIGN.md section 4 "Change-map sampling"): at step i a latent pixel with hold byte q is
+    held to the noised original exactly when q > cut[i].  The reference (FluxDifferentialImg2ImgPipeline, pipeline_flux_differential_
+    img2img.py:936-938) compares bf16(q / 255) with `torch.arange(n, dtype=bf16) / n`; both sides are evaluated here with the same
+    torch expressions on the host, and cut[i] is read off the 256 comparisons -- no integer formula: bf16 ties (n = 3: byte 85 is not
+    held at step 1) and the bf16 arange itself (n > 256) decide entries.  n: the number of steps that run, after `strength` (:892).
+    last="free": the reference, whose last step leaves the latents to the model (:977): cut[n - 1] = 255.  last="keep": the schedule
+    goes on to the last step, where keep_sigma's negative entry makes the held pixels the original's latents themselves."""
+    if last not in ("keep", "free"):
+        raise ValueError(f"change_map: last must be 'keep' or 'free', got {last!r}")
+    n = int(n)
+    if n < 1:
+        raise ValueError(f"change_cut_table: n must be >= 1, got {n}")
+    thresholds = torch.arange(n, dtype=torch.bfloat16) / n
+    levels = (torch.arange(256, dtype=torch.float32) / 255).to(torch.bfloat16)
+    held = levels[None, :] > thresholds[:, None]                     # [n, 256]
+    count = held.sum(dim=1)
+    if not bool((held == (torch.arange(256)[None, :] >= (256 - count)[:, None])).all()):
+        raise AssertionError("change_cut_table: the held bytes are not an upper set")      # both sides are monotone: cannot happen
+    cut = (255 - count).to(torch.int32)
+    if last == "free":
+        cut[-1] = 255
+    return cut
+
+
 class _FlowMatchBase:
     order = 1
     _keys: Sequence[str] = ()

@@ -1,7 +1,8 @@
 """The engine's denoising loop, once: n steps of tfx_dit_step_run -- or of the replay of the graph captured
 from it -- for the plain loop (phase 0) and the step cache (phases 1, 2 / 3), the Euler, AMO, fused-Euler and multistep samplers (the
 last through tfx_dit_step_run_multistep), with or without a step callback, on uniform and mixed-geometry sessions; with the
-known-region blend behind every sampler update (tfx_dit_step_run_ex) when the call keeps the known region.
+known-region blend behind every sampler update (tfx_dit_step_run_ex) when the call keeps the known region, or the change-map blend
+(tfx_dit_step_run_ex2) when the call gives every latent pixel its own release step.
 
 `run_steps` is the control flow and touches no device: it drives a `steps` object with
     feed_noise(i)   run(phase)   replay(handle)   capture(phase) -> handle (raises CaptureRefused)   destroy(handle)
@@ -83,7 +84,7 @@ def run_steps(steps, n, pipe, progress_bar, graphs, key, decider=None, use_graph
 class SessionSteps:
     """run_steps' device operations on a DitSession: its persistent step buffers `gb`, one tfx_step_desc per phase, stream `side`."""
 
-    def __init__(self, ses, gb, side, phases, is_amo, fuse, amo_noise, multistep=False, keep=False):
+    def __init__(self, ses, gb, side, phases, is_amo, fuse, amo_noise, multistep=False, keep=False, change=False):
         self.ses, self.gb, self.side, self.st, self.lib = ses, gb, side, side.cuda_stream, L.lib()
         self.sd = {ph: ses.step_desc(gb, is_amo, fuse, phase=ph) for ph in phases}
         self.is_amo, self.amo_noise = is_amo, amo_noise
@@ -94,6 +95,12 @@ class SessionSteps:
         if keep:
             self.extra = L.StepExtra(v_prev=self.v_prev, keep_x0=gb["keep_x0"].data_ptr(), keep_noise=gb["keep_noise"].data_ptr(),
                                      keep_mask=gb["keep_mask"].data_ptr(), keep_sigma=gb["keep_sigma"].data_ptr())
+        # change-map sampling: the *_ex2 entry points, keep_mask NULL and the hold bytes / cut table in a tfx_step_change beside
+        self.change = None
+        if change:
+            self.extra = L.StepExtra(v_prev=self.v_prev, keep_x0=gb["change_x0"].data_ptr(), keep_noise=gb["change_noise"].data_ptr(),
+                                     keep_mask=None, keep_sigma=gb["change_sigma"].data_ptr())
+            self.change = L.StepChange(hold=gb["change_hold"].data_ptr(), cut=gb["change_cut"].data_ptr())
 
     def feed_noise(self, i):
         if not self.is_amo:
@@ -104,7 +111,9 @@ class SessionSteps:
             self.gb["noise"].copy_(self.amo_noise[i].to(self.gb["noise"].device, torch.float32))
 
     def run(self, ph):
-        if self.extra is not None:
+        if self.change is not None:
+            L.check(self.lib.tfx_dit_step_run_ex2(C.byref(self.sd[ph]), C.byref(self.extra), C.byref(self.change), self.st), "dit_step_run_ex2")
+        elif self.extra is not None:
             L.check(self.lib.tfx_dit_step_run_ex(C.byref(self.sd[ph]), C.byref(self.extra), self.st), "dit_step_run_ex")
         elif self.v_prev is not None:
             L.check(self.lib.tfx_dit_step_run_multistep(C.byref(self.sd[ph]), self.v_prev, self.st), "dit_step_run_multistep")
@@ -116,7 +125,9 @@ class SessionSteps:
 
     def capture(self, ph):
         h = C.c_void_p()
-        if self.extra is not None:
+        if self.change is not None:
+            rc = self.lib.tfx_dit_step_capture_ex2(C.byref(self.sd[ph]), C.byref(self.extra), C.byref(self.change), self.st, C.byref(h))
+        elif self.extra is not None:
             rc = self.lib.tfx_dit_step_capture_ex(C.byref(self.sd[ph]), C.byref(self.extra), self.st, C.byref(h))
         elif self.v_prev is not None:
             rc = self.lib.tfx_dit_step_capture_multistep(C.byref(self.sd[ph]), self.v_prev, self.st, C.byref(h))
@@ -149,7 +160,7 @@ class SessionSteps:
 
 
 def denoise(pipe, ses, mod, latents, coef, n, progress_bar, is_amo=False, fuse=False, amo_noise=None, on_step=None, multistep=False,
-            keep=None):
+            keep=None, change=None):
     """The n steps of one engine call on session `ses`, whose xin holds [latents | masked_image_latents] and whose conditioning is
     set.  mod [n, B, mod_len (+ EULER_PAD when fuse)]: the modulation table.  latents [B, S, C] and coef, the sampler's coefficient
     table, may be None when fuse: the fused step reads the latents from xin and its coefficients from `mod`.  on_step(i, lat): the
@@ -158,7 +169,10 @@ def denoise(pipe, ses, mod, latents, coef, n, progress_bar, is_amo=False, fuse=F
     replaces the latents leaves the history (the previous model output) as it is.  keep: known-region sampling --
     dict(x0, noise, mask: bf16 [B, S, C]; sigma: fp32 [n], the scheduler's keep_sigma_table): after every sampler update the latents
     become (1 - mask) scale_noise(x0, sigma_{i+1}, noise) + mask latents (tfx_known_region_blend inside the step); the buffers live in
-    the session next to v_prev, because captured graphs bake their addresses.  Runs on the session's side
+    the session next to v_prev, because captured graphs bake their addresses.  change: change-map sampling --
+    dict(x0, noise: bf16 [B, S, C]; hold: uint8 [B, S, 4]; sigma: fp32 [n]; cut: int32 [n], schedulers.change_cut_table): the same blend
+    with the mask decided inside the step, held where hold > cut[step] (tfx_change_map_blend); not together with keep; its buffers
+    live in the session too.  Runs on the session's side
     stream (capture needs a non-NULL stream), fenced against the caller's current stream on both sides.  The step cache is on when
     pipe.enable_step_cache() is in force; graphs when pipe.enable_hip_graph(True), no callback and n > 1.  Returns the final
     latents and leaves pipe.step_cache_report set."""
@@ -185,6 +199,22 @@ def denoise(pipe, ses, mod, latents, coef, n, progress_bar, is_amo=False, fuse=F
         for k in ("x0", "noise", "mask"):
             gb["keep_" + k].copy_(keep[k])
         gb["keep_sigma"][:n].copy_(keep["sigma"])
+    if change is not None:
+        if keep is not None:
+            raise ValueError("change_map and keep_known exclude each other")
+        if ses.mixed:
+            raise NotImplementedError("change_map (change-map sampling) does not serve mixed-geometry sessions")
+        assert change["sigma"].numel() == n and change["sigma"].dtype == torch.float32
+        assert change["cut"].numel() == n and change["cut"].dtype == torch.int32
+        if "change_x0" not in gb:        # live and die with gb, like v_prev
+            gb.update({"change_" + k: torch.empty_like(gb["lat"]) for k in ("x0", "noise")})
+            gb["change_hold"] = torch.empty(shape[0], shape[1], 4, dtype=torch.uint8, device=dev)
+            gb["change_sigma"] = torch.zeros(gb["mod_table"].shape[0], dtype=torch.float32, device=dev)
+            gb["change_cut"] = torch.zeros(gb["mod_table"].shape[0], dtype=torch.int32, device=dev)
+        for k in ("x0", "noise", "hold"):
+            gb["change_" + k].copy_(change[k])
+        gb["change_sigma"][:n].copy_(change["sigma"])
+        gb["change_cut"][:n].copy_(change["cut"])
     decider = None
     if pipe._step_cache is not None:
         ses.step_cache_reset()
@@ -193,11 +223,14 @@ def denoise(pipe, ses, mod, latents, coef, n, progress_bar, is_amo=False, fuse=F
     side = ses.graph_stream()
     side.wait_stream(cur)
     with torch.cuda.stream(side):
-        steps = SessionSteps(ses, gb, side, (0,) if decider is None else (1, 2, 3), is_amo, fuse, amo_noise, multistep, keep is not None)
+        steps = SessionSteps(ses, gb, side, (0,) if decider is None else (1, 2, 3), is_amo, fuse, amo_noise, multistep, keep is not None,
+                             change is not None)
         ses._mod_keepalive = gb["mod_cur"]
         key = ("multistep", False) if multistep else (is_amo, fuse)
         if keep is not None:
             key += ("keep",)
+        if change is not None:
+            key += ("change",)
         run_steps(steps, n, pipe, progress_bar, ses.graphs, key, decider, use_graph=pipe._use_hip_graph,
                   callback=None if on_step is None else lambda i: on_step(i, gb["lat"]))
         out = ops.copy_rows_(ses.xin[:, :, :shape[2]], torch.empty(shape, dtype=BF16, device=dev)) if fuse else gb["lat"].clone()
