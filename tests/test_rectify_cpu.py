@@ -132,6 +132,24 @@ def test_restatement_identity_and_quarter_turn():
     assert (rref.warp_affine(flat, np.array([51234, -40000, -3 * Q + 77, 40000, 51234, 12345], np.int64), (20, 20)) == 201).all()
 
 
+@pytest.mark.parametrize("c", [1, 3, 4])
+@pytest.mark.parametrize("case", ["border", "thin"])
+def test_the_three_restatements_agree_on_an_affine_map(case, c):
+    """tests/test_rectify_gpu.py's identity of the three entry points, over the three numpy restatements: it keeps them honest."""
+    from tests.helpers import curve_ref as cref
+    from tests.helpers import perspective_ref as pref
+    from tests.test_rectify_gpu import CASES, affine_three_ways
+    (H, W), (h, w), ms = CASES[case]
+    x = np.random.default_rng(H * W + c).integers(0, 256, (2, H, W, c), dtype=np.uint8)
+    want, want_cov = rref.warp_affine(x, np.stack(ms), (h, w), coverage=True)
+    if case == "border":
+        assert (want_cov == 0).mean() > 0.3 and (want_cov == 255).any()
+    restated = {"warp_affine": rref.warp_affine, "warp_perspective": pref.warp_perspective, "warp_grid": cref.warp_grid}
+    for way, args in affine_three_ways(ms, (h, w)).items():
+        got, cov = restated[way.split(",")[0]](x, *args, (h, w), coverage=True)
+        assert np.array_equal(got, want) and np.array_equal(cov, want_cov), way
+
+
 # ---------------------------------------------------------------------------------------------- the batch driver around a stub
 T, J, P = 6, 8, 4
 SCENE_WH, FLAT_BOX, SLANT = (512, 384), (60, 40, 220, 70), (180, 28, 25, (330, 250))       # the slanted line: length, thickness, degrees, centre

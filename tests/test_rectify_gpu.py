@@ -67,6 +67,35 @@ def test_warp_is_the_restatement_exactly(ops, case, c):
     assert torch.equal(xd.cpu(), torch.from_numpy(x))
 
 
+def affine_three_ways(ms, out_size):
+    """{entry point: its arguments between the image and out_size} for one batch of Q16 affine matrices said three ways: as they are, as
+    homographies (m6 = m7 = 0, m8 = 2^16) and as control grids whose node (r, q) is the affine image of (q << shift, r << shift), at
+    shift 0 and 3.  All of them name the same position for every destination pixel, exactly: the blend of an affine map's nodes is the map."""
+    from tests.helpers import curve_ref as cref
+    from tests.helpers import perspective_ref as pref
+    m = np.stack(ms)
+    ways = {"warp_affine": (m,), "warp_perspective": (pref.embed(m),)}
+    for shift in (0, 3):
+        ways[f"warp_grid, shift {shift}"] = (np.stack([cref.embed(a, shift, out_size) for a in ms]), shift)
+    return ways
+
+
+@pytest.mark.parametrize("c", [1, 3, 4])
+@pytest.mark.parametrize("case", ["border", "thin"])
+def test_one_affine_map_through_all_three_entry_points(ops, case, c):
+    """The three maps share one kernel body: a map wired to the wrong entry point, or a lost zero / uncovered tail, shows here."""
+    (H, W), (h, w), ms = CASES[case]
+    x = np.random.default_rng(H * W + c).integers(0, 256, (2, H, W, c), dtype=np.uint8)
+    want, want_cov = rref.warp_affine(x, np.stack(ms), (h, w), coverage=True)
+    if case == "border":
+        assert (want_cov == 0).mean() > 0.3 and (want_cov == 255).any()          # coverage is exercised
+    xd = torch.from_numpy(x).cuda()
+    for way, args in affine_three_ways(ms, (h, w)).items():
+        got, cov = getattr(ops, way.split(",")[0] + "_u8")(xd, *args, (h, w), coverage=True)
+        assert np.array_equal(got.cpu().numpy(), want), way
+        assert np.array_equal(cov.cpu().numpy(), want_cov), way
+
+
 @pytest.mark.parametrize("c", [3, 1])
 def test_a_constant_survives_forward_and_back(ops, c):
     """Every tap row sums to one, so a constant source comes back as that constant on every covered pixel -- and, by edge replication,

@@ -29,7 +29,7 @@ from __future__ import annotations
 
 import os
 from dataclasses import dataclass, field
-from typing import Any, Callable, Dict, List, Optional, Sequence, Tuple
+from typing import Any, Callable, Dict, List, NamedTuple, Optional, Sequence, Tuple
 
 import torch
 import torch.distributed as dist
@@ -71,6 +71,53 @@ def eval_item_complete(item: Dict[str, Any]) -> bool:
     return bool(ann) and bool(ann[0].get("text")) and bool(ann[0].get("polygon"))
 
 
+class LinePath(NamedTuple):
+    key: str                         # the paste_back cfg key
+    module: str                      # the geometry module: plan(mask_grey, cfg) -> its shape or None, cfg(option)
+    attr: str                        # the pipeline's warp
+    keyword: str                     # the preparers' keyword that carries that warp
+    verb: str                        # "only single-line edits are <verb>"
+
+
+# The per-line paths that edit a line upright, in the order they are tried
+LINE_PATHS = (LinePath("curve", "curve", "warp_grid", "warp_grid", "cut as ribbons"),
+              LinePath("perspective", "perspective", "warp_perspective", "warp_quad", "cut as quads"),
+              LinePath("rectify", "rectify", "warp_affine", "warp", "rectified"))
+
+
+def _module(path: LinePath):
+    import importlib
+    return importlib.import_module("." + path.module, __package__)
+
+
+def pipeline_warps(pipe, cfg: Dict[str, Any]) -> Dict[str, Optional[Callable]]:
+    """{preparer keyword: the pipeline's warp for every line path the paste_back cfg asks for, None for the others}.  ValueError
+    when the pipeline lacks one that is asked for."""
+    warps = {}
+    for path in reversed(LINE_PATHS):
+        asked = bool(cfg.get(path.key))
+        if asked and not hasattr(pipe, path.attr):
+            raise ValueError(f"paste_back: {path.key} needs a pipeline with {path.attr} (FluxFillPipeline)")
+        warps[path.keyword] = getattr(pipe, path.attr) if asked else None
+    return warps
+
+
+def _paste_back_option(paste_back: Dict[str, Any], key: str, make_cfg: Callable, needs_per_line: Optional[str] = None):
+    """One option key of paste_back: None (absent) for None / False, make_cfg's dict for True or a dict, ValueError otherwise.
+    needs_per_line: the reason the key is refused with, given when it needs per_line and per_line is off."""
+    value = paste_back.get(key)
+    if value is None or value is False:
+        return None
+    if value is not True and not isinstance(value, dict):
+        raise ValueError(f"paste_back: {key} must be None, True or a dict")
+    if needs_per_line:
+        raise ValueError(f"paste_back: {key} needs per_line=True ({needs_per_line})")
+    try:
+        return make_cfg(value)
+    except ValueError as e:
+        raise ValueError(f"paste_back: {e}") from None
+
+
 def _paste_back_cfg(paste_back: Dict[str, Any]) -> Dict[str, Any]:
     """run_items' paste_back argument with its defaults filled in: dict(dilate, feather, region: None | dict(pad, min_side, max_side)),
     and, only when the caller gave them, per_line: True (which implies a region: {} when absent) and color_match: paste_back.
@@ -93,69 +140,20 @@ def _paste_back_cfg(paste_back: Dict[str, Any]) -> Dict[str, Any]:
         raise ValueError("paste_back: dilate and feather must be in [0, 255]")
     if region is not None:
         cfg["region"] = {k: v for k, v in region.items() if v is not None}
-    per_line, color_match = paste_back.get("per_line"), paste_back.get("color_match")
+    per_line = paste_back.get("per_line")
     if per_line not in (None, False, True):
         raise ValueError("paste_back: per_line must be True or False")
     if per_line:
         cfg["per_line"] = True
         if cfg["region"] is None:
             cfg["region"] = {}
-    if color_match is not None and color_match is not False:
-        if color_match is not True and not isinstance(color_match, dict):
-            raise ValueError("paste_back: color_match must be None, True or a dict")
-        try:
-            cfg["color_match"] = pb.color_match_cfg(color_match)
-        except ValueError as e:
-            raise ValueError(f"paste_back: {e}") from None
-    seamless = paste_back.get("seamless")
-    if seamless is not None and seamless is not False:
-        if seamless is not True and not isinstance(seamless, dict):
-            raise ValueError("paste_back: seamless must be None, True or a dict")
-        try:
-            cfg["seamless"] = pb.seamless_cfg(seamless)
-        except ValueError as e:
-            raise ValueError(f"paste_back: {e}") from None
-    grain = paste_back.get("grain")
-    if grain is not None and grain is not False:
-        if grain is not True and not isinstance(grain, dict):
-            raise ValueError("paste_back: grain must be None, True or a dict")
-        try:
-            cfg["grain"] = pb.grain_cfg(grain)
-        except ValueError as e:
-            raise ValueError(f"paste_back: {e}") from None
-    rectify = paste_back.get("rectify")
-    if rectify is not None and rectify is not False:
-        if rectify is not True and not isinstance(rectify, dict):
-            raise ValueError("paste_back: rectify must be None, True or a dict")
-        if not per_line:
-            raise ValueError("paste_back: rectify needs per_line=True (only single-line edits are rectified)")
-        from . import rectify as rc
-        try:
-            cfg["rectify"] = rc.rectify_cfg(rectify)
-        except ValueError as e:
-            raise ValueError(f"paste_back: {e}") from None
-    perspective = paste_back.get("perspective")
-    if perspective is not None and perspective is not False:
-        if perspective is not True and not isinstance(perspective, dict):
-            raise ValueError("paste_back: perspective must be None, True or a dict")
-        if not per_line:
-            raise ValueError("paste_back: perspective needs per_line=True (only single-line edits are cut as quads)")
-        from . import perspective as ps
-        try:
-            cfg["perspective"] = ps.perspective_cfg(perspective)
-        except ValueError as e:
-            raise ValueError(f"paste_back: {e}") from None
-    curve = paste_back.get("curve")
-    if curve is not None and curve is not False:
-        if curve is not True and not isinstance(curve, dict):
-            raise ValueError("paste_back: curve must be None, True or a dict")
-        if not per_line:
-            raise ValueError("paste_back: curve needs per_line=True (only single-line edits are cut as ribbons)")
-        from . import curve as cv
-        try:
-            cfg["curve"] = cv.curve_cfg(curve)
-        except ValueError as e:
-            raise ValueError(f"paste_back: {e}") from None
+    options = [("color_match", pb.color_match_cfg, None), ("seamless", pb.seamless_cfg, None), ("grain", pb.grain_cfg, None)]
+    options += [(path.key, lambda v, path=path: _module(path).cfg(v), None if per_line else f"only single-line edits are {path.verb}")
+                for path in reversed(LINE_PATHS)]
+    for key, make_cfg, needs_per_line in options:
+        got = _paste_back_option(paste_back, key, make_cfg, needs_per_line)
+        if got is not None:
+            cfg[key] = got
     return cfg
 
 
@@ -185,85 +183,48 @@ def _host_u8(x):
 
 
 def _warped_inputs(so, mo, warp: Callable, fwd, size, edit_size):
-    """The scene and the RGB mask warped into an upright frame `size` = (w, h) under `fwd` by `warp` (the device kernel), the mask
-    binarised at >= 128, both resized to edit_size with PIL's bicubic when that differs -> (scene, mask) as PIL images."""
+    """The scene and the RGB mask warped into an upright frame `size` = (w, h) by `warp` (the device kernel) under its arguments `fwd`,
+    the mask binarised at >= 128, both resized to edit_size with PIL's bicubic when that differs -> (scene, mask) as PIL images."""
     import numpy as np
     from PIL import Image
     w, h = size
-    s = _host_u8(warp(so, fwd, (h, w)))
-    m = np.where(_host_u8(warp(mo if mo.ndim == 3 else mo[:, :, None], fwd, (h, w))) >= 128, 255, 0).astype(np.uint8)
+    s = _host_u8(warp(so, *fwd, (h, w)))
+    m = np.where(_host_u8(warp(mo if mo.ndim == 3 else mo[:, :, None], *fwd, (h, w))) >= 128, 255, 0).astype(np.uint8)
     s, m = Image.fromarray(s), Image.fromarray(m if mo.ndim == 3 else m[:, :, 0])
     if s.size != tuple(edit_size):
         s, m = s.resize(tuple(edit_size), Image.BICUBIC), m.resize(tuple(edit_size), Image.BICUBIC)
     return s, m
 
 
-def _rectified_inputs(scene, mask, cfg: Dict[str, Any], warp: Callable):
-    """_paste_back_inputs for a line that is edited upright (DESIGN.md section 4 "Rectified lines"), or None when the line stays on
-    the unrectified path (rectify.plan).  -> (scene, mask, originals, Region, Rect): the scene and the RGB mask warped into the oriented
-    rectangle's upright frame (rw, rh) by `warp` (the pipeline's warp_affine: the device kernel; nothing is resampled in a rotated frame
-    on the host), the mask binarised at >= 128, both resized to the editing size (tw, th) with PIL's bicubic when that differs.  The
-    Region is the scene window the result is pasted into: the rectangle's bounding box cut at the image."""
+def _upright_inputs(scene, mask, cfg: Dict[str, Any], path: LinePath, warp: Callable):
+    """_paste_back_inputs for a line that is edited upright through `path` (DESIGN.md section 4 "Rectified lines", "Perspective
+    lines", "Curved lines"), or None when the line stays on the other paths (the path's module's plan).  -> (scene, mask, originals,
+    Region, shape): the scene and the RGB mask warped into the upright crop (rw, rh) of the shape -- a Rect, a Quad or a Ribbon -- by
+    `warp` (the pipeline's warp of that path: the device kernel; nothing is resampled in a rotated frame on the host) under the shape's
+    forward map, the mask binarised at >= 128, both resized to the editing size (tw, th) with PIL's bicubic when that differs.  The
+    Region is the scene window the result is pasted into: the bounding box of the shape's footprint cut at the image."""
     import numpy as np
     from . import paste_back as pb
-    from . import rectify as rc
     so, mo = np.array(scene), np.array(mask)
-    rect = rc.plan(pb.grey_of(mo), cfg)
-    if rect is None:
+    shape = _module(path).plan(pb.grey_of(mo), cfg)
+    if shape is None:
         return None
-    x0, y0, x1, y1 = rc.rect_window(rect, scene.size)
-    s, m = _warped_inputs(so, mo, warp, rc.matrices(rect)[0], (rect.rw, rect.rh), (rect.tw, rect.th))
-    return s, m, so, mo, pb.Region(x0, y0, x1, y1, rect.tw, rect.th), rect
-
-
-def _perspective_inputs(scene, mask, cfg: Dict[str, Any], warp_quad: Callable):
-    """_rectified_inputs for a line seen in perspective (DESIGN.md section 4 "Perspective lines"), or None when the line stays on the
-    other paths (perspective.plan).  -> (scene, mask, originals, Region, Quad): the scene and the RGB mask warped into the quad's upright
-    crop (rw, rh) by `warp_quad` (the pipeline's warp_perspective), prepared as _rectified_inputs does.  The Region is the scene window the
-    result is pasted into: the crop's footprint's bounding box cut at the image."""
-    import numpy as np
-    from . import paste_back as pb
-    from . import perspective as ps
-    so, mo = np.array(scene), np.array(mask)
-    quad = ps.plan(pb.grey_of(mo), cfg)
-    if quad is None:
-        return None
-    x0, y0, x1, y1 = ps.quad_window(quad, scene.size)
-    s, m = _warped_inputs(so, mo, warp_quad, ps.matrices(quad)[0], (quad.rw, quad.rh), (quad.tw, quad.th))
-    return s, m, so, mo, pb.Region(x0, y0, x1, y1, quad.tw, quad.th), quad
-
-
-def _curved_inputs(scene, mask, cfg: Dict[str, Any], warp_grid: Callable):
-    """_rectified_inputs for a line along a bend (DESIGN.md section 4 "Curved lines"), or None when the line stays on the other paths
-    (curve.plan).  -> (scene, mask, originals, Region, Ribbon): the scene and the RGB mask warped into the ribbon's upright crop (rw, rh)
-    by `warp_grid` (the pipeline's warp_grid) under the forward control grid, prepared as _rectified_inputs does.  The Region is the scene
-    window the result is pasted into: the crop's footprint's bounding box cut at the image."""
-    import numpy as np
-    from . import curve as cv
-    from . import paste_back as pb
-    so, mo = np.array(scene), np.array(mask)
-    ribbon = cv.plan(pb.grey_of(mo), cfg)
-    if ribbon is None:
-        return None
-    x0, y0, x1, y1 = cv.ribbon_window(ribbon, scene.size)
-    s, m = _warped_inputs(so, mo, lambda x, g, size: warp_grid(x, g, ribbon.shift, size), cv.forward_grid(ribbon), (ribbon.rw, ribbon.rh),
-                          (ribbon.tw, ribbon.th))
-    return s, m, so, mo, pb.Region(x0, y0, x1, y1, ribbon.tw, ribbon.th), ribbon
+    x0, y0, x1, y1 = shape.window(scene.size)
+    s, m = _warped_inputs(so, mo, warp, shape.forward(), (shape.rw, shape.rh), (shape.tw, shape.th))
+    return s, m, so, mo, pb.Region(x0, y0, x1, y1, shape.tw, shape.th), shape
 
 
 def _edit_inputs(scene, mask, cfg: Dict[str, Any], warp: Optional[Callable], warp_quad: Optional[Callable] = None,
                  warp_grid: Optional[Callable] = None):
-    """(scene, mask, the Work's paste-back fields): _curved_inputs where the cfg asks for it, a grid warp is at hand and the line
-    qualifies; otherwise _perspective_inputs, then _rectified_inputs, each under the same three conditions; _paste_back_inputs
-    otherwise."""
-    got = _curved_inputs(scene, mask, cfg, warp_grid) if (warp_grid is not None and cfg.get("curve")) else None
-    if got is None:
-        got = _perspective_inputs(scene, mask, cfg, warp_quad) if (warp_quad is not None and cfg.get("perspective")) else None
-    if got is None:
-        got = _rectified_inputs(scene, mask, cfg, warp) if (warp is not None and cfg.get("rectify")) else None
-    if got is not None:
-        scene, mask, so, mo, reg, rect = got
-        return scene, mask, dict(orig_scene=so, orig_mask=mo, region=reg, rect=rect)
+    """(scene, mask, the Work's paste-back fields): _upright_inputs through the first of LINE_PATHS that the cfg asks for, whose warp
+    is at hand and for which the line qualifies; _paste_back_inputs otherwise."""
+    warps = dict(warp=warp, warp_quad=warp_quad, warp_grid=warp_grid)
+    for path in LINE_PATHS:
+        if warps[path.keyword] is not None and cfg.get(path.key):
+            got = _upright_inputs(scene, mask, cfg, path, warps[path.keyword])
+            if got is not None:
+                scene, mask, so, mo, reg, rect = got
+                return scene, mask, dict(orig_scene=so, orig_mask=mo, region=reg, rect=rect)
     scene, mask, so, mo, reg = _paste_back_inputs(scene, mask, cfg)
     return scene, mask, dict(orig_scene=so, orig_mask=mo, region=reg)
 
@@ -277,10 +238,9 @@ def prepare_eval_item(index: int, item: Dict[str, Any], original_images_dir: str
     WIDTH -- with the annotation's text, stacked on top with a black mask; pipeline size ((w // 32) * 32,
     ((h + strip) // 32) * 32); T5 prompt generate_prompt([text]).  annotation: which entry of `annotations` (the reference, and
     every caller but per-line editing, reads the first).  warp: the pipeline's warp_affine, given by per-line editing when
-    paste_back["rectify"] is set: a slanted line is then edited upright (_rectified_inputs).  warp_quad: the pipeline's
-    warp_perspective, given when paste_back["perspective"] is set: a line seen in perspective is then cut as a quad (_perspective_inputs).
-    warp_grid: the pipeline's warp_grid, given when paste_back["curve"] is set: a line along a bend is then cut as a ribbon
-    (_curved_inputs)."""
+    paste_back["rectify"] is set: a slanted line is then edited upright (_upright_inputs).  warp_quad: the pipeline's
+    warp_perspective, given when paste_back["perspective"] is set: a line seen in perspective is then cut as a quad.
+    warp_grid: the pipeline's warp_grid, given when paste_back["curve"] is set: a line along a bend is then cut as a ribbon."""
     import numpy as np
     from PIL import Image
     load = loader or (lambda p: Image.open(p))
@@ -553,12 +513,7 @@ def run_items(items: Sequence[Dict[str, Any]], pipe, out_dir: Optional[str], bat
         if not hasattr(pipe, "paste_back"):
             raise ValueError("paste_back needs a pipeline with paste_back (FluxFillPipeline)")
         paste_back = _paste_back_cfg(paste_back)
-        if paste_back.get("rectify") and not hasattr(pipe, "warp_affine"):
-            raise ValueError("paste_back: rectify needs a pipeline with warp_affine (FluxFillPipeline)")
-        if paste_back.get("perspective") and not hasattr(pipe, "warp_perspective"):
-            raise ValueError("paste_back: perspective needs a pipeline with warp_perspective (FluxFillPipeline)")
-        if paste_back.get("curve") and not hasattr(pipe, "warp_grid"):
-            raise ValueError("paste_back: curve needs a pipeline with warp_grid (FluxFillPipeline)")
+        pipeline_warps(pipe, paste_back)
     if step_cache is not None:
         if mixed_pad > 0:
             raise NotImplementedError("step_cache does not serve mixed-geometry batches (mixed_pad > 0)")
@@ -599,10 +554,7 @@ def _run_items(items, pipe, out_dir, batch_size, num_inference_steps, guidance_s
             device_compose = bool(getattr(pipe, "supports_device_compose", False))
             if per_line:
                 from . import per_line as pl
-                lines[i] = pl.prepare_lines(i, it, loader, device_compose, eval_cfg, paste_back,
-                                            warp=pipe.warp_affine if paste_back.get("rectify") else None,
-                                            warp_quad=pipe.warp_perspective if paste_back.get("perspective") else None,
-                                            warp_grid=pipe.warp_grid if paste_back.get("curve") else None)
+                lines[i] = pl.prepare_lines(i, it, loader, device_compose, eval_cfg, paste_back, **pipeline_warps(pipe, paste_back))
                 works.extend(lines[i])
             else:
                 works.append(prepare_item(i, it, loader, device_compose=device_compose,

@@ -16,6 +16,8 @@
 #include "common.h"
 #include "launch.h"
 
+#include <type_traits>
+
 namespace tfx {
 
 // flag |= 1 if any element is negative (VaeImageProcessor.preprocess skips the 2x-1 normalisation for tensors that are
@@ -788,14 +790,18 @@ __global__ __launch_bounds__(256) void seam_apply_kernel(const uint8_t* orig, co
   }
 }
 
-// ---- rectified per-line edits (DESIGN.md section 4 "Rectified lines"): out[b, j, i, :] = in[b] sampled at the affine image of the
-// destination pixel (i, j), 4 x 4 Catmull-Rom taps, edge replicated.  Integer arithmetic only (include/textflux_hip.h spells it out),
-// so the result is exact.  One 256-thread workgroup per 32 x 8 destination tile: its rotated source footprint is a compact patch
-// of about 40 x 25 pixels that stays in cache.  The sample's matrix sits at an address that is uniform over the workgroup, so it is
-// read once per workgroup, not once per thread.  Every index is clamped into the image in 64 bits before it is narrowed: whatever the
-// matrix holds, no load leaves `in`.
-// warp_sample_u8: the part both warps share.  One destination pixel (its C bytes at `dst`, its coverage byte at `cov` unless NULL) from
-// the sample `src` [H, W, C] at the integer position (xi, yi) with the fractions fx, fy in 0..255.
+// ---- line warps (DESIGN.md section 4 "Rectified lines", "Perspective lines", "Curved lines"): out[b, j, i, :] = in[b] sampled at the
+// image of the destination pixel (i, j) under a map, 4 x 4 Catmull-Rom taps, edge replicated.  Integer arithmetic only
+// (include/textflux_hip.h spells it out), so the result is exact.  One kernel, warp_u8_kernel<C, Map>, does everything but the map: one
+// 256-thread workgroup per 32 x 8 destination tile (its rotated source footprint is a compact patch of about 40 x 25 pixels that stays
+// in cache), the bounds check, the output offset, warp_sample_u8, and the tail of a pixel without a source (0, coverage 0, `in` is not
+// read).  A Map is a small functor passed by value -- it lives in the kernel arguments, hence in SGPRs -- whose one member takes
+// (b, i, j, out_h, out_w) and either yields the integer position (xi, yi) with the fractions fx, fy in 0..255 to `sample`, or says
+// `none()`: no source.  The two are continuations, not a returned flag: each map then compiles to the control flow it had as a kernel
+// of its own (a flag costs the perspective map two VGPRs).  Three maps: WarpAffine, WarpPerspective, WarpGrid.  Every index is clamped
+// into the image in 64 bits before it is narrowed: whatever a map holds, no load leaves `in`.
+// warp_sample_u8: one destination pixel (its C bytes at `dst`, its coverage byte at `cov` unless NULL) from the sample `src` [H, W, C]
+// at the integer position (xi, yi) with the fractions fx, fy in 0..255.
 template <int C>
 __device__ __forceinline__ void warp_sample_u8(const uint8_t* __restrict__ src, int H, int W, int64_t xi, int64_t yi, int fx, int fy,
                                                const int16_t* __restrict__ taps, uint8_t* __restrict__ dst, uint8_t* __restrict__ cov) {
@@ -836,89 +842,87 @@ __device__ __forceinline__ void warp_sample_u8(const uint8_t* __restrict__ src, 
   if (cov) *cov = (xi >= 0 && xi < W && yi >= 0 && yi < H) ? 255 : 0;
 }
 
-template <int C>
-__global__ __launch_bounds__(256) void warp_affine_u8_kernel(const uint8_t* __restrict__ in, uint8_t* __restrict__ out,
-                                                             uint8_t* __restrict__ coverage, int H, int W, int out_h, int out_w,
-                                                             const int64_t* __restrict__ m, const int16_t* __restrict__ taps) {
-  const int b = blockIdx.z;
-  const int64_t* mb = m + (int64_t)b * 6;
-  const int64_t m0 = mb[0], m1 = mb[1], m2 = mb[2], m3 = mb[3], m4 = mb[4], m5 = mb[5];
-  const int i = blockIdx.x * 32 + (threadIdx.x & 31), j = blockIdx.y * 8 + (threadIdx.x >> 5);
-  if (i >= out_w || j >= out_h) return;
-  const int64_t X = m0 * i + m1 * j + m2, Y = m3 * i + m4 * j + m5;        // Q16
-  const int64_t o = ((int64_t)b * out_h + j) * out_w + i;
-  warp_sample_u8<C>(in + (int64_t)b * H * W * C, H, W, X >> 16, Y >> 16, (int)((X >> 8) & 255), (int)((Y >> 8) & 255), taps, out + o * C,
-                    coverage ? coverage + o : nullptr);
-}
+// Rectified lines: the Q16 affine image under p i64 [B][6].  The sample's matrix sits at an address that is uniform over the workgroup,
+// so it is read once per workgroup, not once per thread.
+struct WarpAffine {
+  const int64_t* __restrict__ p;
+  template <typename Sample, typename None>
+  __device__ __forceinline__ void operator()(int b, int i, int j, int, int, const Sample& sample, const None&) const {
+    const int64_t* mb = p + (int64_t)b * 6;
+    const int64_t m0 = mb[0], m1 = mb[1], m2 = mb[2], m3 = mb[3], m4 = mb[4], m5 = mb[5];
+    const int64_t X = m0 * i + m1 * j + m2, Y = m3 * i + m4 * j + m5;        // Q16
+    sample(X >> 16, Y >> 16, (int)((X >> 8) & 255), (int)((Y >> 8) & 255));
+  }
+};
 
-// ---- perspective per-line edits (DESIGN.md section 4 "Perspective lines"): the same resampler under a homography.  Per destination
-// pixel two rational positions Nx / D, Ny / D, brought to 8 fractional bits by a FLOOR division in 64-bit integers (the header spells
-// it out), then warp_sample_u8.  At or behind the horizon (D <= 0) the pixel is 0 with coverage 0 and `in` is not read.  The launch
-// shape is the affine kernel's.  Memory-safe whatever m holds: the linear forms and the * 256 wrap in unsigned arithmetic (no undefined
-// signed overflow), D > 0 rules out the two faulting divisions (by 0, INT64_MIN / -1), and warp_sample_u8 clamps in 64 bits.
-// Two plain 64-bit divisions per pixel: measured beside the affine warp by tools/perspective_cost.py.
+// Perspective lines: the homography p i64 [B][9].  Per destination pixel two rational positions Nx / D, Ny / D, brought to 8 fractional
+// bits by a FLOOR division in 64-bit integers (the header spells it out).  At or behind the horizon (D <= 0) there is no source.
+// Memory-safe whatever p holds: the linear forms and the * 256 wrap in unsigned arithmetic (no undefined signed overflow), D > 0 rules
+// out the two faulting divisions (by 0, INT64_MIN / -1), and warp_sample_u8 clamps in 64 bits.  Two plain 64-bit divisions per pixel:
+// measured beside the affine map by tools/perspective_cost.py.
 __device__ __forceinline__ int64_t floor_div_pos(int64_t n, int64_t d) {     // floor(n / d) for d > 0; C++ truncates towards zero
   const int64_t q = n / d;
   return (n % d < 0) ? q - 1 : q;
 }
 
-template <int C>
-__global__ __launch_bounds__(256) void warp_perspective_u8_kernel(const uint8_t* __restrict__ in, uint8_t* __restrict__ out,
-                                                                  uint8_t* __restrict__ coverage, int H, int W, int out_h, int out_w,
-                                                                  const int64_t* __restrict__ m, const int16_t* __restrict__ taps) {
-  const int b = blockIdx.z;
-  const uint64_t* mb = (const uint64_t*)m + (int64_t)b * 9;
-  const uint64_t i = blockIdx.x * 32 + (threadIdx.x & 31), j = blockIdx.y * 8 + (threadIdx.x >> 5);
-  if (i >= (uint64_t)out_w || j >= (uint64_t)out_h) return;
-  const uint64_t Nx = mb[0] * i + mb[1] * j + mb[2], Ny = mb[3] * i + mb[4] * j + mb[5];
-  const int64_t D = (int64_t)(mb[6] * i + mb[7] * j + mb[8]);
-  const int64_t o = ((int64_t)b * out_h + (int64_t)j) * out_w + (int64_t)i;
-  if (D <= 0) {
-#pragma unroll
-    for (int c = 0; c < C; ++c) out[o * C + c] = 0;
-    if (coverage) coverage[o] = 0;
-    return;
+struct WarpPerspective {
+  const int64_t* __restrict__ p;
+  template <typename Sample, typename None>
+  __device__ __forceinline__ void operator()(int b, int i_, int j_, int, int, const Sample& sample, const None& none) const {
+    const uint64_t* mb = (const uint64_t*)p + (int64_t)b * 9;
+    const uint64_t i = (unsigned)i_, j = (unsigned)j_;           // zero-extended: the tile index is unsigned
+    const uint64_t Nx = mb[0] * i + mb[1] * j + mb[2], Ny = mb[3] * i + mb[4] * j + mb[5];
+    const int64_t D = (int64_t)(mb[6] * i + mb[7] * j + mb[8]);
+    if (D <= 0) return none();
+    const int64_t PX = floor_div_pos((int64_t)(Nx << 8), D), PY = floor_div_pos((int64_t)(Ny << 8), D);
+    sample(PX >> 8, PY >> 8, (int)(PX & 255), (int)(PY & 255));
   }
-  const int64_t PX = floor_div_pos((int64_t)(Nx << 8), D), PY = floor_div_pos((int64_t)(Ny << 8), D);
-  warp_sample_u8<C>(in + (int64_t)b * H * W * C, H, W, PX >> 8, PY >> 8, (int)(PX & 255), (int)(PY & 255), taps, out + o * C,
-                    coverage ? coverage + o : nullptr);
-}
+};
 
-// ---- curved per-line edits (DESIGN.md section 4 "Curved lines"): the same resampler under a coarse control grid, which is also the
-// set's general remap (shift = 0: one node per pixel).  grid i64 [B][gh][gw][2] holds the Q16 source position (x, y) of every
-// destination pixel (q << shift, r << shift); a pixel's position is the bilinear blend of the four nodes around it, with integer
-// weights that sum to 4^shift, floored by an arithmetic shift (the header spells it out), then warp_sample_u8.  A pixel one of whose
-// four nodes carries INT64_MIN in x has no source: 0, coverage 0, `in` is not read.  The launch shape is the affine kernel's; the four
-// nodes of a 32 x 8 tile's pixels are a few cache lines that the tile's lanes share.  Memory-safe whatever the grid holds: gh and gw
-// are sized so that node (gy + 1, gx + 1) exists for every destination pixel, products and sums wrap in unsigned arithmetic, and
-// warp_sample_u8 clamps in 64 bits.
-template <int C>
-__global__ __launch_bounds__(256) void warp_grid_u8_kernel(const uint8_t* __restrict__ in, uint8_t* __restrict__ out,
-                                                           uint8_t* __restrict__ coverage, int H, int W, int out_h, int out_w,
-                                                           const int64_t* __restrict__ grid, int shift, const int16_t* __restrict__ taps) {
+// Curved lines: a coarse control grid, which is also the set's general remap (shift = 0: one node per pixel).  p i64 [B][gh][gw][2]
+// holds the Q16 source position (x, y) of every destination pixel (q << shift, r << shift); a pixel's position is the bilinear blend of
+// the four nodes around it, with integer weights that sum to 4^shift, floored by an arithmetic shift (the header spells it out).  A
+// pixel one of whose four nodes carries INT64_MIN in x has no source.  The four nodes of a 32 x 8 tile's pixels are a few cache lines
+// that the tile's lanes share.  Memory-safe whatever the grid holds: gh and gw are sized so that node (gy + 1, gx + 1) exists for every
+// destination pixel, products and sums wrap in unsigned arithmetic, and warp_sample_u8 clamps in 64 bits.
+struct WarpGrid {
+  const int64_t* __restrict__ p;
+  int shift;
+  template <typename Sample, typename None>
+  __device__ __forceinline__ void operator()(int b, int i, int j, int out_h, int out_w, const Sample& sample, const None& none) const {
+    const int64_t gh = ((out_h - 1) >> shift) + 2, gw = ((out_w - 1) >> shift) + 2;
+    const int cell = 1 << shift;
+    const int gx = i >> shift, gy = j >> shift;
+    const uint64_t ax = i & (cell - 1), ay = j & (cell - 1), bx = cell - ax, by = cell - ay;
+    const uint64_t* g0 = (const uint64_t*)p + (((int64_t)b * gh + gy) * gw + gx) * 2;           // g00, g01 = g0 + 2
+    const uint64_t* g1 = g0 + gw * 2;                                                            // g10, g11 = g1 + 2
+    const uint64_t x00 = g0[0], y00 = g0[1], x01 = g0[2], y01 = g0[3], x10 = g1[0], y10 = g1[1], x11 = g1[2], y11 = g1[3];
+    const uint64_t marker = (uint64_t)1 << 63;                                                    // INT64_MIN
+    if (x00 == marker || x01 == marker || x10 == marker || x11 == marker) return none();
+    const uint64_t w00 = bx * by, w01 = ax * by, w10 = bx * ay, w11 = ax * ay;
+    const int64_t X = (int64_t)(w00 * x00 + w01 * x01 + w10 * x10 + w11 * x11) >> (2 * shift);   // Q16, floored
+    const int64_t Y = (int64_t)(w00 * y00 + w01 * y01 + w10 * y10 + w11 * y11) >> (2 * shift);
+    sample(X >> 16, Y >> 16, (int)((X >> 8) & 255), (int)((Y >> 8) & 255));
+  }
+};
+
+template <int C, typename Map>
+__global__ __launch_bounds__(256) void warp_u8_kernel(const uint8_t* __restrict__ in, uint8_t* __restrict__ out,
+                                                      uint8_t* __restrict__ coverage, int H, int W, int out_h, int out_w, const Map map,
+                                                      const int16_t* __restrict__ taps) {
   const int b = blockIdx.z;
-  const int i = blockIdx.x * 32 + (threadIdx.x & 31), j = blockIdx.y * 8 + (threadIdx.x >> 5);
-  if (i >= out_w || j >= out_h) return;
-  const int64_t gh = ((out_h - 1) >> shift) + 2, gw = ((out_w - 1) >> shift) + 2;
-  const int cell = 1 << shift;
-  const int gx = i >> shift, gy = j >> shift;
-  const uint64_t ax = i & (cell - 1), ay = j & (cell - 1), bx = cell - ax, by = cell - ay;
-  const uint64_t* g0 = (const uint64_t*)grid + (((int64_t)b * gh + gy) * gw + gx) * 2;        // g00, g01 = g0 + 2
-  const uint64_t* g1 = g0 + gw * 2;                                                            // g10, g11 = g1 + 2
-  const uint64_t x00 = g0[0], y00 = g0[1], x01 = g0[2], y01 = g0[3], x10 = g1[0], y10 = g1[1], x11 = g1[2], y11 = g1[3];
+  const unsigned i = blockIdx.x * 32 + (threadIdx.x & 31), j = blockIdx.y * 8 + (threadIdx.x >> 5);
+  if (i >= (unsigned)out_w || j >= (unsigned)out_h) return;
   const int64_t o = ((int64_t)b * out_h + j) * out_w + i;
-  const uint64_t none = (uint64_t)1 << 63;                                                     // INT64_MIN
-  if (x00 == none || x01 == none || x10 == none || x11 == none) {
+  const auto sample = [&](int64_t xi, int64_t yi, int fx, int fy) {
+    warp_sample_u8<C>(in + (int64_t)b * H * W * C, H, W, xi, yi, fx, fy, taps, out + o * C, coverage ? coverage + o : nullptr);
+  };
+  const auto none = [&] {
 #pragma unroll
     for (int c = 0; c < C; ++c) out[o * C + c] = 0;
     if (coverage) coverage[o] = 0;
-    return;
-  }
-  const uint64_t w00 = bx * by, w01 = ax * by, w10 = bx * ay, w11 = ax * ay;
-  const int64_t X = (int64_t)(w00 * x00 + w01 * x01 + w10 * x10 + w11 * x11) >> (2 * shift);   // Q16, floored
-  const int64_t Y = (int64_t)(w00 * y00 + w01 * y01 + w10 * y10 + w11 * y11) >> (2 * shift);
-  warp_sample_u8<C>(in + (int64_t)b * H * W * C, H, W, X >> 16, Y >> 16, (int)((X >> 8) & 255), (int)((Y >> 8) & 255), taps, out + o * C,
-                    coverage ? coverage + o : nullptr);
+  };
+  map(b, (int)i, (int)j, out_h, out_w, sample, none);
 }
 
 int compose_canvas(const void* glyph, const void* scene, const void* smask, void* canvas, void* cmask, int B, int gh, int gw, int sh,
@@ -1359,68 +1363,44 @@ int grain_shaped_u8(const void* img, const void* alpha, const int* gain, const i
   return check_launch("grain_shaped_u8");
 }
 
-int warp_affine_u8(const void* in, void* out, void* coverage, int B, int H, int W, int C, int out_h, int out_w, const int64_t* m,
-                   const int16_t* taps, hipStream_t st) {
-  if (B < 1 || H < 1 || W < 1 || out_h < 1 || out_w < 1) return fail("warp_affine_u8: B, H, W, out_h, out_w must be at least 1");
-  if (C < 1 || C > 4) return fail("warp_affine_u8: 1..4 channels");
-  if (B > 65535) return fail("warp_affine_u8: batch %d exceeds 65535", B);
-  if ((out_h + 7) / 8 > 65535) return fail("warp_affine_u8: out_h %d exceeds 524280", out_h);
-  if ((int64_t)H * W * C > kMaxBytes || (int64_t)out_h * out_w * C > kMaxBytes) return fail("warp_affine_u8: more than 2^38 bytes per sample");
-  if (in == out || in == coverage || out == coverage) return fail("warp_affine_u8: in, out and coverage must be different buffers");
-  if (((uintptr_t)m | (uintptr_t)taps) & 7) return fail("warp_affine_u8: m and taps must be 8-byte aligned");
+// The one launcher of the line warps: `name` is the declared function's, `arg` what its messages call the map's pointer.
+template <typename Map>
+static int warp_u8(const char* name, const char* arg, const void* in, void* out, void* coverage, int B, int H, int W, int C, int out_h,
+                   int out_w, const Map map, const int16_t* taps, hipStream_t st) {
+  if (B < 1 || H < 1 || W < 1 || out_h < 1 || out_w < 1) return fail("%s: B, H, W, out_h, out_w must be at least 1", name);
+  if (C < 1 || C > 4) return fail("%s: 1..4 channels", name);
+  if constexpr (std::is_same_v<Map, WarpGrid>)
+    if (map.shift < 0 || map.shift > 5) return fail("%s: shift %d outside 0..5", name, map.shift);
+  if (B > 65535) return fail("%s: batch %d exceeds 65535", name, B);
+  if ((out_h + 7) / 8 > 65535) return fail("%s: out_h %d exceeds 524280", name, out_h);
+  if ((int64_t)H * W * C > kMaxBytes || (int64_t)out_h * out_w * C > kMaxBytes) return fail("%s: more than 2^38 bytes per sample", name);
+  if (in == out || in == coverage || out == coverage) return fail("%s: in, out and coverage must be different buffers", name);
+  if (((uintptr_t)map.p | (uintptr_t)taps) & 7) return fail("%s: %s and taps must be 8-byte aligned", name, arg);
   const dim3 grid((out_w + 31) / 32, (out_h + 7) / 8, B);
   const uint8_t* pi = (const uint8_t*)in;
   uint8_t *po = (uint8_t*)out, *pc = (uint8_t*)coverage;
   switch (C) {
-    case 1: warp_affine_u8_kernel<1><<<grid, 256, 0, st>>>(pi, po, pc, H, W, out_h, out_w, m, taps); break;
-    case 2: warp_affine_u8_kernel<2><<<grid, 256, 0, st>>>(pi, po, pc, H, W, out_h, out_w, m, taps); break;
-    case 3: warp_affine_u8_kernel<3><<<grid, 256, 0, st>>>(pi, po, pc, H, W, out_h, out_w, m, taps); break;
-    default: warp_affine_u8_kernel<4><<<grid, 256, 0, st>>>(pi, po, pc, H, W, out_h, out_w, m, taps); break;
+    case 1: warp_u8_kernel<1><<<grid, 256, 0, st>>>(pi, po, pc, H, W, out_h, out_w, map, taps); break;
+    case 2: warp_u8_kernel<2><<<grid, 256, 0, st>>>(pi, po, pc, H, W, out_h, out_w, map, taps); break;
+    case 3: warp_u8_kernel<3><<<grid, 256, 0, st>>>(pi, po, pc, H, W, out_h, out_w, map, taps); break;
+    default: warp_u8_kernel<4><<<grid, 256, 0, st>>>(pi, po, pc, H, W, out_h, out_w, map, taps); break;
   }
-  return check_launch("warp_affine_u8");
+  return check_launch(name);
+}
+
+int warp_affine_u8(const void* in, void* out, void* coverage, int B, int H, int W, int C, int out_h, int out_w, const int64_t* m,
+                   const int16_t* taps, hipStream_t st) {
+  return warp_u8("warp_affine_u8", "m", in, out, coverage, B, H, W, C, out_h, out_w, WarpAffine{m}, taps, st);
 }
 
 int warp_perspective_u8(const void* in, void* out, void* coverage, int B, int H, int W, int C, int out_h, int out_w, const int64_t* m,
                         const int16_t* taps, hipStream_t st) {
-  if (B < 1 || H < 1 || W < 1 || out_h < 1 || out_w < 1) return fail("warp_perspective_u8: B, H, W, out_h, out_w must be at least 1");
-  if (C < 1 || C > 4) return fail("warp_perspective_u8: 1..4 channels");
-  if (B > 65535) return fail("warp_perspective_u8: batch %d exceeds 65535", B);
-  if ((out_h + 7) / 8 > 65535) return fail("warp_perspective_u8: out_h %d exceeds 524280", out_h);
-  if ((int64_t)H * W * C > kMaxBytes || (int64_t)out_h * out_w * C > kMaxBytes) return fail("warp_perspective_u8: more than 2^38 bytes per sample");
-  if (in == out || in == coverage || out == coverage) return fail("warp_perspective_u8: in, out and coverage must be different buffers");
-  if (((uintptr_t)m | (uintptr_t)taps) & 7) return fail("warp_perspective_u8: m and taps must be 8-byte aligned");
-  const dim3 grid((out_w + 31) / 32, (out_h + 7) / 8, B);
-  const uint8_t* pi = (const uint8_t*)in;
-  uint8_t *po = (uint8_t*)out, *pc = (uint8_t*)coverage;
-  switch (C) {
-    case 1: warp_perspective_u8_kernel<1><<<grid, 256, 0, st>>>(pi, po, pc, H, W, out_h, out_w, m, taps); break;
-    case 2: warp_perspective_u8_kernel<2><<<grid, 256, 0, st>>>(pi, po, pc, H, W, out_h, out_w, m, taps); break;
-    case 3: warp_perspective_u8_kernel<3><<<grid, 256, 0, st>>>(pi, po, pc, H, W, out_h, out_w, m, taps); break;
-    default: warp_perspective_u8_kernel<4><<<grid, 256, 0, st>>>(pi, po, pc, H, W, out_h, out_w, m, taps); break;
-  }
-  return check_launch("warp_perspective_u8");
+  return warp_u8("warp_perspective_u8", "m", in, out, coverage, B, H, W, C, out_h, out_w, WarpPerspective{m}, taps, st);
 }
 
 int warp_grid_u8(const void* in, void* out, void* coverage, int B, int H, int W, int C, int out_h, int out_w, const int64_t* grid,
                  int shift, const int16_t* taps, hipStream_t st) {
-  if (B < 1 || H < 1 || W < 1 || out_h < 1 || out_w < 1) return fail("warp_grid_u8: B, H, W, out_h, out_w must be at least 1");
-  if (C < 1 || C > 4) return fail("warp_grid_u8: 1..4 channels");
-  if (shift < 0 || shift > 5) return fail("warp_grid_u8: shift %d outside 0..5", shift);
-  if (B > 65535) return fail("warp_grid_u8: batch %d exceeds 65535", B);
-  if ((out_h + 7) / 8 > 65535) return fail("warp_grid_u8: out_h %d exceeds 524280", out_h);
-  if ((int64_t)H * W * C > kMaxBytes || (int64_t)out_h * out_w * C > kMaxBytes) return fail("warp_grid_u8: more than 2^38 bytes per sample");
-  if (in == out || in == coverage || out == coverage) return fail("warp_grid_u8: in, out and coverage must be different buffers");
-  if (((uintptr_t)grid | (uintptr_t)taps) & 7) return fail("warp_grid_u8: grid and taps must be 8-byte aligned");
-  const dim3 blocks((out_w + 31) / 32, (out_h + 7) / 8, B);
-  const uint8_t* pi = (const uint8_t*)in;
-  uint8_t *po = (uint8_t*)out, *pc = (uint8_t*)coverage;
-  switch (C) {
-    case 1: warp_grid_u8_kernel<1><<<blocks, 256, 0, st>>>(pi, po, pc, H, W, out_h, out_w, grid, shift, taps); break;
-    case 2: warp_grid_u8_kernel<2><<<blocks, 256, 0, st>>>(pi, po, pc, H, W, out_h, out_w, grid, shift, taps); break;
-    case 3: warp_grid_u8_kernel<3><<<blocks, 256, 0, st>>>(pi, po, pc, H, W, out_h, out_w, grid, shift, taps); break;
-    default: warp_grid_u8_kernel<4><<<blocks, 256, 0, st>>>(pi, po, pc, H, W, out_h, out_w, grid, shift, taps); break;
-  }
-  return check_launch("warp_grid_u8");
+  return warp_u8("warp_grid_u8", "grid", in, out, coverage, B, H, W, C, out_h, out_w, WarpGrid{grid, shift}, taps, st);
 }
 
 int pack_mask(const void* mask, int mask_dtype, void* out, int B, int H, int W, int mask_b, int binarize, int64_t ld, int col0,

@@ -20,7 +20,7 @@ from typing import NamedTuple, Optional, Tuple
 import numpy as np
 
 from .perspective import _grow
-from .rectify import line_frame, mask_points
+from .rectify import bounding_window, edit_size, line_frame, mask_points
 
 # Which lines take the curved path (is_curved), and how hard the crop may squeeze the inner edge (select_ribbon).  Starting points, not
 # tuned values and no quality claim.
@@ -64,6 +64,17 @@ class Ribbon(NamedTuple):
     tw: int                          # the size the upright crop is edited at (its own size unless it exceeds max_side)
     th: int
     shift: int                       # the control grids' cell size is 1 << shift destination pixels (grids)
+
+    WARP = "warp_grid"               # rectify.Rect's interface
+
+    def forward(self):
+        return forward_grid(self), self.shift
+
+    def backward(self, origin, size):
+        return backward_grid(self, origin, size), self.shift
+
+    def window(self, size):
+        return ribbon_window(self, size)
 
 
 # ---------------------------------------------------------------------------------------------- the centre line of a region
@@ -292,6 +303,9 @@ def curve_cfg(curve) -> dict:
     return cfg
 
 
+cfg = curve_cfg                      # the name all three line paths share
+
+
 def is_curved(line: Optional[Line], cfg: Optional[dict] = None) -> bool:
     """Whether a line with this centre line (fit_line, or None) is edited through a ribbon.  With thickness = 2 half: sagitta / thickness
     >= min_bend (a rectangle's or a trapezoid's centre line is straight: sagitta 0, rectify's and perspective's ground), arc length /
@@ -387,8 +401,7 @@ def select_ribbon(points, dilate: int = 16, feather: int = 4, pad: float = 0.5, 
         shift = _shift_for(line, reach)
         if shift is None or reach + (1 << shift) * math.sqrt(2.0) > max_squeeze * line.r_min:
             continue
-        longer = max(rw, rh)
-        tw, th = (max(32, rw * max_side // longer), max(32, rh * max_side // longer)) if longer > max_side else (rw, rh)
+        tw, th = edit_size(rw, rh, max_side)
         rb = Ribbon(line, rw, rh, l, t, L, T, tw, th, shift)
         xy = np.stack([mu - line.u0 + rb.ox, mv + _v0(rb)], axis=1)
         if (xy >= 0).all() and (xy[:, 0] <= rw - 1).all() and (xy[:, 1] <= rh - 1).all():
@@ -408,12 +421,7 @@ def footprint(rb: Ribbon) -> np.ndarray:
 def ribbon_window(rb: Ribbon, size: Tuple[int, int]) -> Tuple[int, int, int, int]:
     """(x0, y0, x1, y1), half-open: the footprint's bounding box cut at the image (size = (W, H)) -- the scene window a curved line is
     pasted into (rectify.rect_window's rule).  ValueError when the footprint misses the image."""
-    pts = footprint(rb)
-    x0, y0 = max(int(math.floor(pts[:, 0].min())), 0), max(int(math.floor(pts[:, 1].min())), 0)
-    x1, y1 = min(int(math.ceil(pts[:, 0].max())) + 1, int(size[0])), min(int(math.ceil(pts[:, 1].max())) + 1, int(size[1]))
-    if x1 <= x0 or y1 <= y0:
-        raise ValueError("ribbon_window: the ribbon's footprint lies outside the image")
-    return x0, y0, x1, y1
+    return bounding_window(footprint(rb), size, "ribbon_window: the ribbon's footprint lies outside the image")
 
 
 # ---------------------------------------------------------------------------------------------- the control grids

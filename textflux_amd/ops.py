@@ -1030,9 +1030,10 @@ def _grain_args(name, img, alpha, gain, max_gain, origin, out):
 _WARP_TAPS = {}
 
 
-def _warp_u8(name: str, n: int, x: torch.Tensor, m, out_size, coverage: bool, host_check=None):
-    """warp_affine_u8 / warp_perspective_u8: the checks, the tap table and the call of tfx_<name> with n matrix entries per sample.
-    host_check(matrices [k, n] as a host array, out_h, out_w): applied when m arrives as a host array."""
+def _warp_u8(name: str, x: torch.Tensor, out_size, coverage: bool, shape_map):
+    """The line warps' common part: the checks of x and out_size, the tap table and the call of tfx_<name>.  shape_map(B, out_h, out_w)
+    -> (the map as an int64 tensor whose leading axis is B, expanded where one map serves the batch; the arguments between the map
+    and the tap table): the caller's own checks, the host-side magnitude check among them."""
     _chk_dev(x)
     if x.dtype != torch.uint8 or x.dim() != 4 or not x.is_contiguous() or x.numel() == 0 or not 1 <= x.shape[3] <= 4:
         raise ValueError(f"{name}: x must be a contiguous, non-empty uint8 [B, H, W, C <= 4] tensor, got {x.dtype} {tuple(x.shape)}")
@@ -1040,16 +1041,8 @@ def _warp_u8(name: str, n: int, x: torch.Tensor, m, out_size, coverage: bool, ho
     Ho, Wo = (int(v) for v in out_size)
     if Ho < 1 or Wo < 1:
         raise ValueError(f"{name}: out_size must be (out_h, out_w) with both at least 1, got {tuple(out_size)}")
-    host = None
-    if not isinstance(m, torch.Tensor):
-        import numpy as np
-        host = np.ascontiguousarray(m)
-        m = torch.from_numpy(host)
-    if m.dtype != torch.int64 or m.numel() not in (n, n * B) or m.shape[-1] != n:
-        raise ValueError(f"{name}: m must be int64 [{B}, {n}] or [{n}], got {m.dtype} {tuple(m.shape)}")
-    if host is not None and host_check is not None:
-        host_check(host.reshape(-1, n), Ho, Wo)
-    m = m.reshape(-1, n).expand(B, n).to(x.device).contiguous()
+    m, extra = shape_map(B, Ho, Wo)
+    m = m.to(x.device).contiguous()
     key = str(x.device)
     if key not in _WARP_TAPS:
         from .rectify import catmull_rom_taps
@@ -1057,9 +1050,26 @@ def _warp_u8(name: str, n: int, x: torch.Tensor, m, out_size, coverage: bool, ho
     taps = _WARP_TAPS[key]
     out = torch.empty(B, Ho, Wo, Cc, dtype=torch.uint8, device=x.device)
     cov = torch.empty(B, Ho, Wo, dtype=torch.uint8, device=x.device) if coverage else None
-    L.check(getattr(L.lib(), "tfx_" + name)(x.data_ptr(), out.data_ptr(), _p(cov), B, H, W, Cc, Ho, Wo, m.data_ptr(), taps.data_ptr(),
-                                            _stream()), name)
+    L.check(getattr(L.lib(), "tfx_" + name)(x.data_ptr(), out.data_ptr(), _p(cov), B, H, W, Cc, Ho, Wo, m.data_ptr(), *extra,
+                                            taps.data_ptr(), _stream()), name)
     return (out, cov) if coverage else out
+
+
+def _warp_matrix_u8(name: str, n: int, x: torch.Tensor, m, out_size, coverage: bool, host_check=None):
+    """warp_affine_u8 / warp_perspective_u8: _warp_u8 with n matrix entries per sample.  host_check(matrices [k, n] as a host array,
+    out_h, out_w): applied when m arrives as a host array."""
+    def shape_map(B, Ho, Wo):
+        host, t = None, m
+        if not isinstance(m, torch.Tensor):
+            import numpy as np
+            host = np.ascontiguousarray(m)
+            t = torch.from_numpy(host)
+        if t.dtype != torch.int64 or t.numel() not in (n, n * B) or t.shape[-1] != n:
+            raise ValueError(f"{name}: m must be int64 [{B}, {n}] or [{n}], got {t.dtype} {tuple(t.shape)}")
+        if host is not None and host_check is not None:
+            host_check(host.reshape(-1, n), Ho, Wo)
+        return t.reshape(-1, n).expand(B, n), ()
+    return _warp_u8(name, x, out_size, coverage, shape_map)
 
 
 def warp_affine_u8(x: torch.Tensor, m, out_size, coverage: bool = False):
@@ -1067,7 +1077,7 @@ def warp_affine_u8(x: torch.Tensor, m, out_size, coverage: bool = False):
     under m (int64 [B, 6] or [6], tensor or array: one matrix per sample, or one for all), 4 x 4 Catmull-Rom taps, edge replicated, in
     integer arithmetic (tfx_warp_affine_u8; include/textflux_hip.h has the arithmetic, rectify.matrices builds m).  out_size =
     (out_h, out_w).  coverage: also return uint8 [B, out_h, out_w], 255 where the sample position lies inside the image."""
-    return _warp_u8("warp_affine_u8", 6, x, m, out_size, coverage)
+    return _warp_matrix_u8("warp_affine_u8", 6, x, m, out_size, coverage)
 
 
 def _perspective_magnitudes(m, out_h: int, out_w: int) -> None:
@@ -1088,10 +1098,17 @@ def warp_perspective_u8(x: torch.Tensor, m, out_size, coverage: bool = False):
     a pixel with D <= 0 is 0 and uncovered (tfx_warp_perspective_u8; include/textflux_hip.h has the arithmetic, perspective.matrices
     builds m).  A host array is checked against the magnitude contract (|Nx|, |Ny|, D < 2^54 at the destination's corners: ValueError);
     a device tensor is taken as it is, which is memory-safe but leaves such pixels undefined."""
-    return _warp_u8("warp_perspective_u8", 9, x, m, out_size, coverage, _perspective_magnitudes)
+    return _warp_matrix_u8("warp_perspective_u8", 9, x, m, out_size, coverage, _perspective_magnitudes)
 
 
 GRID_NONE = -(1 << 63)               # warp_grid_u8: a node whose x is this marks "no source" (INT64_MIN)
+
+
+def _grid_magnitudes(grid) -> None:
+    """tfx_warp_grid_u8's magnitude contract on a host grid: every value is the marker or below 2^50 in magnitude."""
+    bad = (grid != GRID_NONE) & ((grid >= 1 << 50) | (grid <= -(1 << 50)))
+    if bad.any():
+        raise ValueError(f"warp_grid_u8: every grid value must be the marker or below 2^50 in magnitude; {int(bad.sum())} are not")
 
 
 def warp_grid_u8(x: torch.Tensor, grid, shift: int, out_size, coverage: bool = False):
@@ -1102,43 +1119,25 @@ def warp_grid_u8(x: torch.Tensor, grid, shift: int, out_size, coverage: bool = F
     (tfx_warp_grid_u8; include/textflux_hip.h has the arithmetic, curve.grids builds the grids).  A host grid is checked against the
     magnitude contract (every value the marker or below 2^50 in magnitude: ValueError); a device tensor is taken as it is, which is
     memory-safe but leaves such pixels undefined."""
-    _chk_dev(x)
-    if x.dtype != torch.uint8 or x.dim() != 4 or not x.is_contiguous() or x.numel() == 0 or not 1 <= x.shape[3] <= 4:
-        raise ValueError(f"warp_grid_u8: x must be a contiguous, non-empty uint8 [B, H, W, C <= 4] tensor, got {x.dtype} {tuple(x.shape)}")
-    B, H, W, Cc = x.shape
-    Ho, Wo = (int(v) for v in out_size)
-    if Ho < 1 or Wo < 1:
-        raise ValueError(f"warp_grid_u8: out_size must be (out_h, out_w) with both at least 1, got {tuple(out_size)}")
-    if isinstance(shift, bool) or int(shift) != shift or not 0 <= int(shift) <= 5:
-        raise ValueError(f"warp_grid_u8: shift must be an integer in 0..5, got {shift!r}")
-    shift = int(shift)
-    gh, gw = ((Ho - 1) >> shift) + 2, ((Wo - 1) >> shift) + 2
-    host = None
-    if not isinstance(grid, torch.Tensor):
-        import numpy as np
-        host = np.ascontiguousarray(grid)
-        if host.dtype != np.int64:
-            raise ValueError(f"warp_grid_u8: grid must be int64, got {host.dtype}")
-        grid = torch.from_numpy(host)
-    if grid.dtype != torch.int64 or tuple(grid.shape) not in ((gh, gw, 2), (B, gh, gw, 2)):
-        raise ValueError(f"warp_grid_u8: grid must be int64 [{gh}, {gw}, 2] or [{B}, {gh}, {gw}, 2] for out_size {(Ho, Wo)} at shift {shift}, "
-                         f"got {grid.dtype} {tuple(grid.shape)}")
-    if host is not None:
-        import numpy as np
-        bad = (host != GRID_NONE) & ((host >= 1 << 50) | (host <= -(1 << 50)))
-        if bad.any():
-            raise ValueError(f"warp_grid_u8: every grid value must be the marker or below 2^50 in magnitude; {int(bad.sum())} are not")
-    grid = grid.reshape(-1, gh, gw, 2).expand(B, gh, gw, 2).to(x.device).contiguous()
-    key = str(x.device)
-    if key not in _WARP_TAPS:
-        from .rectify import catmull_rom_taps
-        _WARP_TAPS[key] = torch.from_numpy(catmull_rom_taps()).to(x.device)
-    taps = _WARP_TAPS[key]
-    out = torch.empty(B, Ho, Wo, Cc, dtype=torch.uint8, device=x.device)
-    cov = torch.empty(B, Ho, Wo, dtype=torch.uint8, device=x.device) if coverage else None
-    L.check(L.lib().tfx_warp_grid_u8(x.data_ptr(), out.data_ptr(), _p(cov), B, H, W, Cc, Ho, Wo, grid.data_ptr(), shift, taps.data_ptr(),
-                                     _stream()), "warp_grid_u8")
-    return (out, cov) if coverage else out
+    def shape_map(B, Ho, Wo):
+        if isinstance(shift, bool) or int(shift) != shift or not 0 <= int(shift) <= 5:
+            raise ValueError(f"warp_grid_u8: shift must be an integer in 0..5, got {shift!r}")
+        sh = int(shift)
+        gh, gw = ((Ho - 1) >> sh) + 2, ((Wo - 1) >> sh) + 2
+        host, g = None, grid
+        if not isinstance(grid, torch.Tensor):
+            import numpy as np
+            host = np.ascontiguousarray(grid)
+            if host.dtype != np.int64:
+                raise ValueError(f"warp_grid_u8: grid must be int64, got {host.dtype}")
+            g = torch.from_numpy(host)
+        if g.dtype != torch.int64 or tuple(g.shape) not in ((gh, gw, 2), (B, gh, gw, 2)):
+            raise ValueError(f"warp_grid_u8: grid must be int64 [{gh}, {gw}, 2] or [{B}, {gh}, {gw}, 2] for out_size {(Ho, Wo)} at shift {sh}, "
+                             f"got {g.dtype} {tuple(g.shape)}")
+        if host is not None:
+            _grid_magnitudes(host)
+        return g.reshape(-1, gh, gw, 2).expand(B, gh, gw, 2), (sh,)
+    return _warp_u8("warp_grid_u8", x, out_size, coverage, shape_map)
 
 
 def pack_mask(mask: torch.Tensor, out: torch.Tensor, col0: int, B: int, H: int, W: int, binarize: bool = True) -> torch.Tensor:

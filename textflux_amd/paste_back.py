@@ -420,16 +420,10 @@ def paste(original: torch.Tensor, edited: torch.Tensor, mask_grey: torch.Tensor,
     original, edited = original.contiguous(), edited.contiguous()
     covered = None
     if rect is not None:
-        from . import curve, perspective, rectify
         if tuple(edited.shape[1:3]) != (rect.rh, rect.rw):
             edited = ops.resample_u8(edited, (rect.rh, rect.rw))
         size = (original.shape[1], original.shape[2])
-        if isinstance(rect, curve.Ribbon):
-            edited, covered = ops.warp_grid_u8(edited, curve.backward_grid(rect, origin, size), rect.shift, size, coverage=True)
-        elif isinstance(rect, perspective.Quad):
-            edited, covered = ops.warp_perspective_u8(edited, perspective.matrices(rect, origin)[1], size, coverage=True)
-        else:
-            edited, covered = ops.warp_affine_u8(edited, rectify.matrices(rect, origin)[1], size, coverage=True)
+        edited, covered = getattr(ops, rect.WARP + "_u8")(edited, *rect.backward(origin, size), size, coverage=True)
     elif edited.shape[1:3] != original.shape[1:3]:
         edited = ops.resample_u8(edited, (original.shape[1], original.shape[2]))
     alpha = alpha_mask(mask_grey.contiguous(), dilate, feather)

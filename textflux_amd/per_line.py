@@ -46,9 +46,9 @@ def prepare_scene_lines(index: int, scene, mask, texts: Sequence[str], cfg: Dict
     _paste_back_inputs does, a glyph strip at the region's width (glyph.render_single_line), prompt generate_prompt([text]), meta of
     mode singleline.  Work.parent = index, Work.line = the position in the list.  No line at all: ValueError.
     warp (the pipeline's warp_affine; with cfg["rectify"]): a slanted line is cut as an oriented rectangle and prepared upright
-    (batch_driver._rectified_inputs); its Work then carries `rect`.  warp_quad (the pipeline's warp_perspective; with
-    cfg["perspective"]): a line seen in perspective is cut as a quad instead (batch_driver._perspective_inputs); `rect` is then its Quad.
-    warp_grid (the pipeline's warp_grid; with cfg["curve"]): a line along a bend is cut as a ribbon (batch_driver._curved_inputs), which
+    (batch_driver._upright_inputs); its Work then carries `rect`.  warp_quad (the pipeline's warp_perspective; with
+    cfg["perspective"]): a line seen in perspective is cut as a quad instead; `rect` is then its Quad.
+    warp_grid (the pipeline's warp_grid; with cfg["curve"]): a line along a bend is cut as a ribbon, which
     is tried first; `rect` is then its Ribbon."""
     from PIL import Image
     from . import batch_driver as bd
@@ -160,16 +160,7 @@ def edit_scene(pipe, scene, mask, texts: Sequence[str], cfg: Dict[str, Any], num
     import torch
     from . import batch_driver as bd
     device = device if device is not None else getattr(pipe, "_execution_device", "cuda")
-    if cfg.get("rectify") and not hasattr(pipe, "warp_affine"):
-        raise ValueError("paste_back: rectify needs a pipeline with warp_affine (FluxFillPipeline)")
-    if cfg.get("perspective") and not hasattr(pipe, "warp_perspective"):
-        raise ValueError("paste_back: perspective needs a pipeline with warp_perspective (FluxFillPipeline)")
-    if cfg.get("curve") and not hasattr(pipe, "warp_grid"):
-        raise ValueError("paste_back: curve needs a pipeline with warp_grid (FluxFillPipeline)")
-    lines = prepare_scene_lines(0, scene.convert("RGB"), mask.convert("RGB"), texts, cfg,
-                                warp=pipe.warp_affine if cfg.get("rectify") else None,
-                                warp_quad=pipe.warp_perspective if cfg.get("perspective") else None,
-                                warp_grid=pipe.warp_grid if cfg.get("curve") else None)
+    lines = prepare_scene_lines(0, scene.convert("RGB"), mask.convert("RGB"), texts, cfg, **bd.pipeline_warps(pipe, cfg))
     fulls: Dict[int, Any] = {}
     for batch in bd.plan_batches(lines, len(lines)):
         n = len(batch.items)

@@ -19,7 +19,7 @@ from typing import NamedTuple, Optional, Tuple
 import numpy as np
 
 from . import glyph
-from .rectify import mask_points
+from .rectify import bounding_window, edit_size, mask_points
 
 # Which lines take the perspective path (is_perspective).  fit = area(quad) / area(its minimum-area rectangle): 1 for a rectangle at any
 # angle (that is rectify's ground), about 0.75 for a 2:1 taper.  A starting point, not a tuned value and no quality claim.
@@ -38,6 +38,17 @@ class Quad(NamedTuple):
     ih: int
     tw: int                          # the size the upright crop is edited at (its own size unless it exceeds max_side)
     th: int
+
+    WARP = "warp_perspective"        # rectify.Rect's interface
+
+    def forward(self):
+        return (matrices(self)[0],)
+
+    def backward(self, origin, size):
+        return (matrices(self, origin)[1],)
+
+    def window(self, size):
+        return quad_window(self, size)
 
 
 # ---------------------------------------------------------------------------------------------- the quad of a region
@@ -147,6 +158,9 @@ def perspective_cfg(perspective) -> dict:
     return cfg
 
 
+cfg = perspective_cfg                # the name all three line paths share
+
+
 def is_perspective(quad, cfg: Optional[dict] = None) -> bool:
     """Whether a line whose quad is `quad` (order_quad's TL, TR, BR, BL, or None) is edited through a homography: the quad exists and is
     convex, every side is at least 8 px, fit = area(quad) / area(its minimum-area rectangle) <= max_fit (a rectangle at any angle has
@@ -246,8 +260,7 @@ def _select(q: np.ndarray, dilate: int = 16, feather: int = 4, pad: float = 0.5,
         tried.add(p)
         (l, r), (t, b) = _grow(max(need[0], p), max(need[1], p), L, min_side), _grow(max(need[2], p), max(need[3], p), T, min_side)
         rw, rh = L + l + r, T + t + b
-        longer = max(rw, rh)
-        tw, th = (max(32, rw * max_side // longer), max(32, rh * max_side // longer)) if longer > max_side else (rw, rh)
+        tw, th = edit_size(rw, rh, max_side)
         quad = Quad(corners, rw, rh, l, t, L, T, tw, th)
         d = np.c_[_outer(rw, rh), np.ones(4)] @ upright_to_scene(quad)[2]
         if (d >= 1.0 / max_taper).all() and _inside(footprint(quad), moved):
@@ -281,12 +294,7 @@ def select_quad(points, dilate: int = 16, feather: int = 4, pad: float = 0.5, mi
 def quad_window(quad: Quad, size: Tuple[int, int]) -> Tuple[int, int, int, int]:
     """(x0, y0, x1, y1), half-open: the footprint's bounding box cut at the image (size = (W, H)) -- the scene window a perspective line
     is pasted into (rectify.rect_window's rule).  ValueError when the footprint misses the image."""
-    pts = footprint(quad)
-    x0, y0 = max(int(math.floor(pts[:, 0].min())), 0), max(int(math.floor(pts[:, 1].min())), 0)
-    x1, y1 = min(int(math.ceil(pts[:, 0].max())) + 1, int(size[0])), min(int(math.ceil(pts[:, 1].max())) + 1, int(size[1]))
-    if x1 <= x0 or y1 <= y0:
-        raise ValueError("quad_window: the quad's footprint lies outside the image")
-    return x0, y0, x1, y1
+    return bounding_window(footprint(quad), size, "quad_window: the quad's footprint lies outside the image")
 
 
 def _fixed(h: np.ndarray, at) -> np.ndarray:

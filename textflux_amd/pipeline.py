@@ -817,38 +817,33 @@ class FluxFillPipeline:
         return pb.paste(original, rgb(edited), grey(mask, tuple(original.shape[1:3])), dilate, feather, color_match=color_match,
                         color_ref=None if color_ref is None else rgb(color_ref), **kw)
 
-    # ------------------------------------------------------------------ rectified lines (DESIGN.md section 4 "Rectified lines")
+    # ------------------------------------------------------------------ line warps (DESIGN.md section 4 "Rectified lines" and after)
+    def _warp_image(self, name: str, image) -> torch.Tensor:
+        """A uint8 image (array or tensor, [H, W, C] or [B, H, W, C]) as a contiguous uint8 [B, H, W, C] tensor on the device; others
+        are refused under the caller's `name`."""
+        t = image if isinstance(image, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(image))
+        t = t[None] if t.dim() == 3 else t
+        if t.dtype != torch.uint8 or t.dim() != 4:
+            raise ValueError(f"{name}: the image must be uint8 [H, W, C] or [B, H, W, C], got {t.dtype} {tuple(t.shape)}")
+        return t.to(self._execution_device).contiguous()
+
     def warp_affine(self, image, m, out_size, coverage: bool = False):
         """A uint8 image (array or tensor, [H, W, C] or [B, H, W, C], C in 1..4) sampled under the Q16 affine matrix m (int64 [6] or
         [B, 6]; rectify.matrices) into out_size = (out_h, out_w) on the device (ops.warp_affine_u8): the resampler of the rectified
         per-line path.  Returns uint8 [B, out_h, out_w, C] on the device, with coverage=True also the coverage [B, out_h, out_w]."""
-        t = image if isinstance(image, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(image))
-        t = t[None] if t.dim() == 3 else t
-        if t.dtype != torch.uint8 or t.dim() != 4:
-            raise ValueError(f"warp_affine: the image must be uint8 [H, W, C] or [B, H, W, C], got {t.dtype} {tuple(t.shape)}")
-        return ops.warp_affine_u8(t.to(self._execution_device).contiguous(), m, out_size, coverage=coverage)
+        return ops.warp_affine_u8(self._warp_image("warp_affine", image), m, out_size, coverage=coverage)
 
-    # ------------------------------------------------------------------ perspective lines (DESIGN.md section 4 "Perspective lines")
     def warp_perspective(self, image, m, out_size, coverage: bool = False):
         """warp_affine under a homography: m is int64 [9] or [B, 9] (perspective.matrices; ops.warp_perspective_u8), the resampler of
         the perspective per-line path.  Returns uint8 [B, out_h, out_w, C] on the device, with coverage=True also the coverage
         [B, out_h, out_w]."""
-        t = image if isinstance(image, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(image))
-        t = t[None] if t.dim() == 3 else t
-        if t.dtype != torch.uint8 or t.dim() != 4:
-            raise ValueError(f"warp_perspective: the image must be uint8 [H, W, C] or [B, H, W, C], got {t.dtype} {tuple(t.shape)}")
-        return ops.warp_perspective_u8(t.to(self._execution_device).contiguous(), m, out_size, coverage=coverage)
+        return ops.warp_perspective_u8(self._warp_image("warp_perspective", image), m, out_size, coverage=coverage)
 
-    # ------------------------------------------------------------------ curved lines (DESIGN.md section 4 "Curved lines")
     def warp_grid(self, image, grid, shift, out_size, coverage: bool = False):
         """warp_affine under a control grid: grid is int64 [gh, gw, 2] or [B, gh, gw, 2] of Q16 source positions, one node per
         (1 << shift) destination pixels (curve.grids; ops.warp_grid_u8), the resampler of the curved per-line path and, at shift = 0, a
         per-pixel remap.  Returns uint8 [B, out_h, out_w, C] on the device, with coverage=True also the coverage [B, out_h, out_w]."""
-        t = image if isinstance(image, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(image))
-        t = t[None] if t.dim() == 3 else t
-        if t.dtype != torch.uint8 or t.dim() != 4:
-            raise ValueError(f"warp_grid: the image must be uint8 [H, W, C] or [B, H, W, C], got {t.dtype} {tuple(t.shape)}")
-        return ops.warp_grid_u8(t.to(self._execution_device).contiguous(), grid, shift, out_size, coverage=coverage)
+        return ops.warp_grid_u8(self._warp_image("warp_grid", image), grid, shift, out_size, coverage=coverage)
 
     def _generic_loop(self, latents, masked_image_latents, prompt_embeds, pooled, text_ids, latent_image_ids, timesteps,
                       guidance, callback_on_step_end, callback_tensor_inputs, progress_bar):

@@ -36,6 +36,20 @@ class Rect(NamedTuple):
     tw: int                          # the size the upright crop is edited at (its own size unless it exceeds max_side)
     th: int
 
+    # What batch_driver and paste_back ask of a line's shape (perspective.Quad and curve.Ribbon answer the same four)
+    WARP = "warp_affine"             # the pipeline's warp; ops' is WARP + "_u8"
+
+    def forward(self):
+        """The warp's arguments after the image, scene -> upright crop."""
+        return (matrices(self)[0],)
+
+    def backward(self, origin, size):
+        """The same, upright crop -> the scene window [size = (h, w)] whose top-left pixel is scene pixel `origin`."""
+        return (matrices(self, origin)[1],)
+
+    def window(self, size):
+        return rect_window(self, size)
+
 
 def catmull_rom_taps() -> np.ndarray:
     """int16 [256][4]: row f = the Catmull-Rom (a = -0.5) weights of the taps at distances 1 + t, t, 1 - t, 2 - t for t = f / 256, with
@@ -88,6 +102,9 @@ def rectify_cfg(rectify) -> dict:
     return dict(min_angle=lo, max_angle=hi, min_aspect=aspect)
 
 
+cfg = rectify_cfg                    # the name all three line paths share (perspective.cfg, curve.cfg)
+
+
 def is_rectified(frame, min_angle: float = MIN_ANGLE, max_angle: float = MAX_ANGLE, min_aspect: float = MIN_ASPECT) -> bool:
     """Whether a line of this line_frame is edited upright: min_angle <= |theta| <= max_angle and length / thickness >= min_aspect."""
     _, _, length, thickness, theta = frame
@@ -104,6 +121,13 @@ def _centre_offsets(rect: Rect) -> Tuple[int, int, float, float]:
     (0 for an odd side, half a pixel for an even one)."""
     ic, jc = rect.rw // 2, rect.rh // 2
     return ic, jc, ic + 0.5 - rect.rw / 2.0, jc + 0.5 - rect.rh / 2.0
+
+
+def edit_size(rw: int, rh: int, max_side: int) -> Tuple[int, int]:
+    """(tw, th): the size an upright crop [rh, rw] is edited at: its own, unless its longer side m exceeds max_side; then
+    (max(32, rw max_side // m), max(32, rh max_side // m))."""
+    longer = max(rw, rh)
+    return (max(32, rw * max_side // longer), max(32, rh * max_side // longer)) if longer > max_side else (rw, rh)
 
 
 def select_rect(points, dilate: int = 16, feather: int = 4, pad: float = 0.5, min_side: int = 256, max_side: int = 1024) -> Rect:
@@ -123,8 +147,7 @@ def select_rect(points, dilate: int = 16, feather: int = 4, pad: float = 0.5, mi
     c, s = _axes(theta)
     p = max(int(math.ceil(halo(dilate, feather) * (abs(c) + abs(s)) - 1e-9)), int(math.ceil(pad * L)))
     rw, rh = max(L + 2 * p, int(min_side)), max(T + 2 * p, int(min_side))
-    longer = max(rw, rh)
-    tw, th = (max(32, rw * max_side // longer), max(32, rh * max_side // longer)) if longer > max_side else (rw, rh)
+    tw, th = edit_size(rw, rh, max_side)
     _, _, da, db = _centre_offsets(Rect(cx, cy, rw, rh, theta, tw, th))
     px, py = round(cx + da * c - db * s), round(cy + da * s + db * c)
     return Rect(px - da * c + db * s, py - da * s - db * c, rw, rh, theta, tw, th)
@@ -139,15 +162,20 @@ def rect_corners(rect: Rect) -> np.ndarray:
     return np.array(out, np.float64)
 
 
-def rect_window(rect: Rect, size: Tuple[int, int]) -> Tuple[int, int, int, int]:
-    """(x0, y0, x1, y1), half-open: the rectangle's bounding box cut at the image (size = (W, H)) -- the scene window a rectified line
-    is pasted into.  ValueError when the rectangle misses the image."""
-    pts = rect_corners(rect)
+def bounding_window(pts: np.ndarray, size: Tuple[int, int], missed: str) -> Tuple[int, int, int, int]:
+    """(x0, y0, x1, y1), half-open: the bounding box of the scene positions pts [n, 2] cut at the image (size = (W, H)) -- the window
+    rule of all three line paths.  ValueError(missed) when the box misses the image."""
     x0, y0 = max(int(math.floor(pts[:, 0].min())), 0), max(int(math.floor(pts[:, 1].min())), 0)
     x1, y1 = min(int(math.ceil(pts[:, 0].max())) + 1, int(size[0])), min(int(math.ceil(pts[:, 1].max())) + 1, int(size[1]))
     if x1 <= x0 or y1 <= y0:
-        raise ValueError("rect_window: the rectangle lies outside the image")
+        raise ValueError(missed)
     return x0, y0, x1, y1
+
+
+def rect_window(rect: Rect, size: Tuple[int, int]) -> Tuple[int, int, int, int]:
+    """(x0, y0, x1, y1), half-open: the rectangle's bounding box cut at the image (size = (W, H)) -- the scene window a rectified line
+    is pasted into.  ValueError when the rectangle misses the image."""
+    return bounding_window(rect_corners(rect), size, "rect_window: the rectangle lies outside the image")
 
 
 def matrices(rect: Rect, origin: Tuple[int, int] = (0, 0)) -> Tuple[np.ndarray, np.ndarray]:
