@@ -1,8 +1,9 @@
 // Driver of change-map sampling's CPU launch-trace test (tests/test_change_map_cpu.py): the step descriptors of
 // step_cache_trace_driver.cpp (2 double + 2 single blocks, batch 2, bf16, joint attention) over fake device addresses, run three ways
 // per sampler and phase -- tfx_dit_step_run_ex without a blend, with the known-region blend, and tfx_dit_step_run_ex2 with the
-// change-map blend -- against launch_recorder.cpp + step_cache_recorder.cpp + change_map_recorder.cpp.  Per scenario: a header line,
-// the recorded launches, the return code and the error text.
+// change-map blend -- against launch_recorder.cpp + step_cache_recorder.cpp + change_map_recorder.cpp; then the same step through
+// every entry point that must issue it (the `entry_*` scenarios).  Per scenario: a header line, the recorded launches, the return code
+// and the error text.
 #include <cstdio>
 #include <cstring>
 #include <functional>
@@ -107,6 +108,26 @@ void scenario(const std::string& name, int sampler, int phase, int mode, const T
   std::fflush(stdout);
 }
 
+// One blend-free step through entry point `how`: "run" tfx_dit_step_run, "ex" tfx_dit_step_run_ex with an all-NULL tfx_step_extra,
+// "ex2" tfx_dit_step_run_ex2 with that and no change; for sampler 3 "multistep" tfx_dit_step_run_multistep and "ex" the history
+// in a tfx_step_extra
+void entry(const std::string& how, int sampler, int phase) {
+  static Model m;
+  build(m, sampler);
+  m.s.phase = phase;
+  if (phase == 0) m.s.cache = nullptr;
+  tfx_step_extra ex{};
+  ex.v_prev = m.ex.v_prev;
+  tfx::g_probe_mask = 7;
+  std::printf("== entry_%s_sampler%d_phase%d\n", how.c_str(), sampler, phase);
+  const int rc = how == "run"         ? tfx_dit_step_run(&m.s, nullptr)
+                 : how == "multistep" ? tfx_dit_step_run_multistep(&m.s, ex.v_prev, nullptr)
+                 : how == "ex"        ? tfx_dit_step_run_ex(&m.s, &ex, nullptr)
+                                      : tfx_dit_step_run_ex2(&m.s, &ex, nullptr, nullptr);
+  std::printf("rc %d\nerror %s\n", rc, rc ? tfx_last_error() : "");
+  std::fflush(stdout);
+}
+
 }  // namespace
 
 int main() {
@@ -115,6 +136,9 @@ int main() {
     for (int phase : {0, 1, 2, 3})
       for (int mode = 0; mode < 3; ++mode)
         scenario(std::string(modes[mode]) + "_sampler" + std::to_string(sampler) + "_phase" + std::to_string(phase), sampler, phase, mode);
+  for (int sampler = 0; sampler < 4; ++sampler)
+    for (int phase : {0, 1, 2, 3})
+      for (const char* how : {sampler == 3 ? "multistep" : "run", "ex", "ex2"}) entry(how, sampler, phase);
   // change == NULL through _ex2 is _ex
   {
     static Model m;

@@ -325,6 +325,21 @@ def test_ex2_refusals_and_the_null_change(scenarios):
     assert len([k for k in scenarios if k.startswith("fail_")]) == len(want)
 
 
+@pytest.mark.skipif(not CXX, reason="no C++ compiler")
+@pytest.mark.skipif(not HAVE_HIP_HEADERS, reason="no ROCm headers")
+@pytest.mark.parametrize("sampler", [0, 1, 2, 3], ids=["euler", "amo", "fused", "multistep"])
+def test_every_entry_point_issues_the_same_step(scenarios, sampler):
+    """tfx_dit_step_run(s), tfx_dit_step_run_ex(s, {}) and tfx_dit_step_run_ex2(s, {}, NULL) are one step, and so are
+    tfx_dit_step_run_multistep(s, v) and the two with v_prev = v: the step loop drives every sampler through _ex2 alone"""
+    first = "multistep" if sampler == 3 else "run"
+    for phase in (0, 1, 2, 3):
+        one, ex, ex2 = (launches(scenarios[f"entry_{e}_sampler{sampler}_phase{phase}"]) for e in (first, "ex", "ex2"))
+        assert one == ex == ex2 and len(one) >= 3 and not any("blend" in l for l in one)
+        assert one == launches(scenarios[f"plain_sampler{sampler}_phase{phase}"])
+        update = [l.split()[0] for l in one if l.split()[0] in ("sched_step", "multistep_step")]
+        assert update == ([] if phase == 1 or sampler == 2 else ["multistep_step" if sampler == 3 else "sched_step"])
+
+
 def test_ex2_entry_points_refuse_without_a_device(lib):
     from tests.test_keep_known_cpu import step_desc
     from textflux_amd import _lib as L

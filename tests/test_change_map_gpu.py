@@ -90,6 +90,42 @@ def test_blend_keeps_a_negative_zero_only_where_it_does_not_write():
     assert bits(x)[0, 3] == -32768 and bits(free)[0, 3] == 0 and bits(R.blend(x, x0, noise, hold, 255, 0.90625))[0, 3] == -32768
 
 
+@pytest.mark.parametrize("ldx", ["C", 384])
+@pytest.mark.parametrize("C", [8, 64])
+@pytest.mark.parametrize("rows", [1, 33, 257])
+def test_a_binary_hold_is_the_known_region_blend_on_the_device(rows, C, ldx):
+    """The two blends are one kernel frame with two mask sources: hold bytes of {0, 255} under any cut of 0..254 hold exactly the
+    255s, and tfx_change_map_blend then equals tfx_known_region_blend with mask = 1 - k in every bit of x and of the mirror, for a
+    positive sigma and a negative one (p = x0).  cut >= 255 is no part of this: there the change-map blend does not write."""
+    from textflux_amd import ops
+    ldx = C if ldx == "C" else ldx
+    x, x0, noise = (X.arbitrary_bf16((rows, C), 29 * rows + C + k) for k in range(3))
+    # the first chunk (all there is at rows 1, C 8) holds both zeros and both signs in every operand, under either decision
+    for t, pattern in ((x, (0.0, -0.0, 1.5, -2.25, -0.0, 0.0, -3.0, 0.75)), (x0, (0.0, -0.0, -0.0, 0.0, 2.5, -1.25, 0.5, -4.0)),
+                       (noise, (-0.0, 0.0, 1.0, -1.0, 0.0, -0.0, -0.5, 2.0))):
+        t.view(-1)[:8] = torch.tensor(pattern, dtype=BF)
+        assert (bits(t)[0, :8] == 0).any() and (bits(t)[0, :8] == -32768).any() and (t[0, :8] > 0).any() and (t[0, :8] < 0).any()
+    hold = (torch.randint(0, 2, (rows, 4), generator=X.gen(rows + C)) * 255).to(torch.uint8)
+    hold[0] = torch.tensor([0, 255, 255, 0], dtype=torch.uint8)
+    k = (hold == 255).repeat(1, C // 4)                                     # column j reads byte j & 3
+    mask = (1 - k.float()).to(BF).cuda()
+    x0d, nd, hd = x0.cuda(), noise.cuda(), hold.cuda()
+    pad_src, xin_src = X.arbitrary_bf16((rows, ldx), 79).cuda(), X.arbitrary_bf16((rows, C + 16), 80).cuda()
+    for cut in (0, 127, 254):
+        for sigma in SIGMAS:
+            sig, ct = torch.tensor([sigma], dtype=torch.float32, device="cuda"), torch.tensor([cut], dtype=torch.int32, device="cuda")
+            got = []
+            for blend in (lambda xd, xin: ops.change_map_blend(xd, x0d, nd, hd, ct, sig, xin=xin),
+                          lambda xd, xin: ops.known_region_blend(xd, x0d, nd, mask, sig, xin=xin)):
+                pad, xin = pad_src.clone(), xin_src.clone()
+                pad[:, :C] = x.cuda()
+                blend(pad[:, :C], xin)
+                got.append((pad, xin))
+            (pc, ic), (pk, ik) = got
+            assert same(pc, pk) and same(ic, ik), (cut, sigma)
+            assert same(ic[:, :C], pc[:, :C]) and not same(pc[:, :C], x), (cut, sigma)
+
+
 def test_blend_refusals():
     from textflux_amd import ops
     x, x0, noise, hold = (t.cuda() for t in blend_inputs(16, 64, 5))
@@ -150,6 +186,23 @@ def test_pack_equals_the_restatement(Hm, Wm, Bm, mode, grow):
         assert Hm // 8 <= 8 and Wm // 8 <= 8 and (want == 255 - m.amax(dim=(1, 2))[:, None, None]).all()
     if mode == 1:
         assert (want <= R.pack(m, 0, 0)).all()                               # cover never holds longer than nearest
+
+
+@pytest.mark.parametrize("mode,grow", [(0, 0), (1, 0), (1, 1), (1, 8)], ids=["nearest", "cover0", "cover1", "cover8"])
+@pytest.mark.parametrize("Hm,Wm", [(16, 16), (32, 48)], ids=["one_token", "32x48"])
+def test_a_binary_map_packs_to_the_keep_mask_on_the_device(Hm, Wm, mode, grow):
+    """The two packers are one kernel frame with two reducers: on a map of {0, 255} the hold byte is 0 exactly where
+    tfx_keep_mask_pack writes 1.0 (any byte >= 128 is the maximum being 255), and 255 elsewhere"""
+    from textflux_amd import ops
+    m = torch.zeros(2, Hm, Wm, dtype=torch.uint8)
+    m[0, 8, 8] = m[1, Hm - 3, Wm - 5] = m[1, 5, 3] = 255                    # on the sampling lattice, and off it in two blocks
+    hold = ops.change_map_pack(m.cuda(), mode, grow).cpu()
+    mk = ops.keep_mask_pack(m.cuda(), 16, mode, grow).cpu()
+    assert ((hold == 0) | (hold == 255)).all() and (hold[0] == 0).any()
+    if (Hm, grow) == (32, 0) or (Hm, grow) == (32, 1):
+        assert (hold[0] == 255).any()                                       # both values, where the window is smaller than the image
+    want = (hold == 0).to(BF)[:, :, None, :].expand(2, hold.shape[1], 4, 4).reshape(2, hold.shape[1], 16)
+    assert same(mk, want)
 
 
 def test_pack_refusals():

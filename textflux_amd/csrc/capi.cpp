@@ -688,31 +688,27 @@ int step_check(const tfx_step_desc* s) {
 // ex.v_prev: the multistep history buffer -- the second-order update then stands where sampler 0 launches Euler's.  ex.keep_*: the
 // known-region blend, behind the update and in front of the step cache's store pass and the cursor advance (it reads the cursor).
 // ch: the change-map blend in the same place, its mask decided on the device from hold and cut (keep_mask is then NULL)
-int step_finish(const tfx_step_desc& s, hipStream_t st, const StepCacheArgs* store, const tfx_step_extra& ex,
-                const tfx_step_change* ch = nullptr) {
-  const int64_t rows = (int64_t)s.dit.B * s.dit.S;
-  void* v_prev = ex.v_prev;
-  if (v_prev) {
-    TRY(multistep_step(s.dit.out, s.latents, const_cast<void*>(s.dit.xin), s.dit.in_channels, s.dit.out_channels, rows, s.coef,
-                       s.step_ptr, 0, v_prev, st));
+int step_finish(const tfx_step_desc& s, hipStream_t st, const StepCacheArgs* store, const tfx_step_extra& ex, const tfx_step_change* ch) {
+  const tfx_dit_desc& d = s.dit;
+  const int64_t rows = (int64_t)d.B * d.S;
+  void* xin = const_cast<void*>(d.xin);
+  if (ex.v_prev) {
+    TRY(multistep_step(d.out, s.latents, xin, d.in_channels, d.out_channels, rows, s.coef, s.step_ptr, 0, ex.v_prev, st));
   } else if (s.sampler != 2) {                                  // sampler 2: the update happened in proj_out's epilogue
-    TRY(sched_step(s.sampler == 1, s.dit.out, s.latents, const_cast<void*>(s.dit.xin), s.dit.in_channels, s.dit.out_channels, rows,
-                   s.coef, s.step_ptr, 0, s.noise, st));
+    TRY(sched_step(s.sampler == 1, d.out, s.latents, xin, d.in_channels, d.out_channels, rows, s.coef, s.step_ptr, 0, s.noise, st));
   }
-  if (ch) {
-    if (s.sampler == 2)
-      TRY(change_map_blend(const_cast<void*>(s.dit.xin), s.dit.in_channels, ex.keep_x0, ex.keep_noise, ch->hold, ch->cut, s.dit.out_channels,
-                           rows, ex.keep_sigma, s.step_ptr, 0, nullptr, 0, st));
+  if (ch || ex.keep_mask) {
+    const bool fused = s.sampler == 2;                          // the fused Euler form keeps the latents in xin[:, :out_channels]
+    void* x = fused ? xin : s.latents;
+    const int64_t ldx = fused ? d.in_channels : d.out_channels;
+    void* mirror = fused ? nullptr : xin;
+    const int64_t ldmirror = fused ? 0 : d.in_channels;
+    if (ch)
+      TRY(change_map_blend(x, ldx, ex.keep_x0, ex.keep_noise, ch->hold, ch->cut, d.out_channels, rows, ex.keep_sigma, s.step_ptr, 0, mirror,
+                           ldmirror, st));
     else
-      TRY(change_map_blend(s.latents, s.dit.out_channels, ex.keep_x0, ex.keep_noise, ch->hold, ch->cut, s.dit.out_channels, rows,
-                           ex.keep_sigma, s.step_ptr, 0, const_cast<void*>(s.dit.xin), s.dit.in_channels, st));
-  } else if (ex.keep_mask) {
-    if (s.sampler == 2)                                          // the fused Euler form keeps the latents in xin[:, :out_channels]
-      TRY(known_region_blend(const_cast<void*>(s.dit.xin), s.dit.in_channels, ex.keep_x0, ex.keep_noise, ex.keep_mask, s.dit.out_channels,
-                             rows, ex.keep_sigma, s.step_ptr, 0, nullptr, 0, st));
-    else
-      TRY(known_region_blend(s.latents, s.dit.out_channels, ex.keep_x0, ex.keep_noise, ex.keep_mask, s.dit.out_channels, rows,
-                             ex.keep_sigma, s.step_ptr, 0, const_cast<void*>(s.dit.xin), s.dit.in_channels, st));
+      TRY(known_region_blend(x, ldx, ex.keep_x0, ex.keep_noise, ex.keep_mask, d.out_channels, rows, ex.keep_sigma, s.step_ptr, 0, mirror,
+                             ldmirror, st));
   }
   if (store) TRY(step_cache_store(*store, st));
   return advance_step(s.step_ptr, st);
@@ -725,7 +721,7 @@ int step_forward(const tfx_step_desc& s, int first, int last, int flags, hipStre
   return tfx_dit_forward(&d, (tfx_stream)st);
 }
 
-int step_enqueue(const tfx_step_desc& s, hipStream_t st, const tfx_step_extra& ex, const tfx_step_change* ch = nullptr) {
+int step_enqueue(const tfx_step_desc& s, hipStream_t st, const tfx_step_extra& ex, const tfx_step_change* ch) {
   if (s.phase == 0) {
     TRY(select_step(s.mod_table, s.mod_cur, s.mod_step_elems, s.step_ptr, st));
     TRY(tfx_dit_forward(&s.dit, (tfx_stream)st));
@@ -760,58 +756,47 @@ int step_check_multistep(const tfx_step_desc* s, const void* v_prev) {
   return 0;
 }
 
-// the _ex entry points: v_prev as above; keep_* all set or all NULL, not with dit.seq_len, aliasing no buffer the step writes
-int step_check_ex(const tfx_step_desc* s, const tfx_step_extra* ex) {
-  if (!ex) return fail("tfx_dit_step (ex): null tfx_step_extra (tfx_dit_step_run / tfx_dit_step_capture take none)");
-  if (ex->v_prev) TRY(step_check_multistep(s, ex->v_prev)); else TRY(step_check(s));
-  const void* keep[4] = {ex->keep_x0, ex->keep_noise, ex->keep_mask, ex->keep_sigma};
-  const int set = (keep[0] != nullptr) + (keep[1] != nullptr) + (keep[2] != nullptr) + (keep[3] != nullptr);
-  if (set == 0) return 0;
-  if (set != 4) return fail("tfx_dit_step (ex): keep_x0, keep_noise, keep_mask and keep_sigma must be all set or all NULL");
-  const tfx_dit_desc& d = s->dit;
-  if (d.seq_len) return fail("tfx_dit_step (ex): the known-region blend cannot serve a mixed-geometry batch (dit.seq_len): its buffers are [B * S, C] without padding rows");
-  if (!d.xin) return fail("tfx_dit_step (ex): dit.xin is null");
-  const int64_t rows = (int64_t)d.B * d.S, kb = rows * d.out_channels * 2;
-  const struct { const void* p; int64_t bytes; } written[4] = {{s->latents, kb}, {d.out, kb}, {d.xin, rows * d.in_channels * 2}, {ex->v_prev, kb}};
-  for (const void* k : keep) {
-    const char* p = (const char*)k;
-    const int64_t pb = k == ex->keep_sigma ? 4 : kb;
-    for (const auto& w : written) {
-      const char* q = (const char*)w.p;
-      if (q && (p == q || (p < q + w.bytes && q < p + pb)))
-        return fail("tfx_dit_step (ex): keep_x0, keep_noise, keep_mask and keep_sigma must not alias latents, dit.out, dit.xin or v_prev");
-    }
+// What every step entry point checks.  ex: the history and the blend's buffers, all NULL for the plain step; need_history: the
+// *_multistep entry points, which refuse a NULL v_prev.  ch NULL (`who` "ex"): keep_* all set, the known-region blend, or all NULL.
+// ch set (`who` "ex2"), the change-map blend: keep_x0 / keep_noise / keep_sigma, hold and cut set, keep_mask NULL.  Neither blend
+// with dit.seq_len, and nothing a blend reads may alias a buffer the step writes.
+int step_check_extra(const tfx_step_desc* s, const tfx_step_extra* ex, const tfx_step_change* ch, const char* who, bool need_history) {
+  if (!ex)
+    return ch ? fail("tfx_dit_step (ex2): null tfx_step_extra: the change-map blend reads keep_x0, keep_noise and keep_sigma from it")
+              : fail("tfx_dit_step (ex): null tfx_step_extra (tfx_dit_step_run / tfx_dit_step_capture take none)");
+  if (ex->v_prev || need_history) TRY(step_check_multistep(s, ex->v_prev)); else TRY(step_check(s));
+  if (ch) {
+    if (!ch->hold || !ch->cut) return fail("tfx_dit_step (ex2): change->hold and change->cut must both be set");
+    if (!ex->keep_x0 || !ex->keep_noise || !ex->keep_sigma) return fail("tfx_dit_step (ex2): with change, keep_x0, keep_noise and keep_sigma must be set");
+    if (ex->keep_mask) return fail("tfx_dit_step (ex2): with change, keep_mask must be NULL: the mask is decided on the device from hold and cut");
+  } else {
+    const int set = (ex->keep_x0 != nullptr) + (ex->keep_noise != nullptr) + (ex->keep_mask != nullptr) + (ex->keep_sigma != nullptr);
+    if (set == 0) return 0;
+    if (set != 4) return fail("tfx_dit_step (ex): keep_x0, keep_noise, keep_mask and keep_sigma must be all set or all NULL");
   }
-  return 0;
-}
-
-// the _ex2 entry points: change NULL is _ex; else keep_x0 / keep_noise / keep_sigma set, keep_mask NULL, hold and cut set, not with
-// dit.seq_len, and none of them aliasing a buffer the step writes
-int step_check_ex2(const tfx_step_desc* s, const tfx_step_extra* ex, const tfx_step_change* ch) {
-  if (!ch) return step_check_ex(s, ex);
-  if (!ex) return fail("tfx_dit_step (ex2): null tfx_step_extra: the change-map blend reads keep_x0, keep_noise and keep_sigma from it");
-  if (ex->v_prev) TRY(step_check_multistep(s, ex->v_prev)); else TRY(step_check(s));
-  if (!ch->hold || !ch->cut) return fail("tfx_dit_step (ex2): change->hold and change->cut must both be set");
-  if (!ex->keep_x0 || !ex->keep_noise || !ex->keep_sigma) return fail("tfx_dit_step (ex2): with change, keep_x0, keep_noise and keep_sigma must be set");
-  if (ex->keep_mask) return fail("tfx_dit_step (ex2): with change, keep_mask must be NULL: the mask is decided on the device from hold and cut");
   const tfx_dit_desc& d = s->dit;
-  if (d.seq_len) return fail("tfx_dit_step (ex2): the change-map blend cannot serve a mixed-geometry batch (dit.seq_len): its buffers are [B * S, C] without padding rows");
-  if (!d.xin) return fail("tfx_dit_step (ex2): dit.xin is null");
+  if (d.seq_len)
+    return fail("tfx_dit_step (%s): the %s blend cannot serve a mixed-geometry batch (dit.seq_len): its buffers are [B * S, C] without padding rows",
+                who, ch ? "change-map" : "known-region");
+  if (!d.xin) return fail("tfx_dit_step (%s): dit.xin is null", who);
   const int64_t rows = (int64_t)d.B * d.S, kb = rows * d.out_channels * 2;
-  const struct { const void* p; int64_t bytes; } written[4] = {{s->latents, kb}, {d.out, kb}, {d.xin, rows * d.in_channels * 2}, {ex->v_prev, kb}};
-  const struct { const void* p; int64_t bytes; } read[5] = {{ex->keep_x0, kb}, {ex->keep_noise, kb}, {ex->keep_sigma, 4}, {ch->hold, rows * 4}, {ch->cut, 4}};
-  for (const auto& r : read) {
+  struct Span { const void* p; int64_t bytes; };
+  const Span written[4] = {{s->latents, kb}, {d.out, kb}, {d.xin, rows * d.in_channels * 2}, {ex->v_prev, kb}};
+  const Span read[6] = {{ex->keep_x0, kb}, {ex->keep_noise, kb}, {ex->keep_mask, kb}, {ex->keep_sigma, 4},
+                        {ch ? ch->hold : nullptr, rows * 4}, {ch ? ch->cut : nullptr, 4}};
+  for (const Span& r : read) {
     const char* p = (const char*)r.p;
-    for (const auto& w : written) {
+    for (const Span& w : written) {
       const char* q = (const char*)w.p;
-      if (q && (p == q || (p < q + w.bytes && q < p + r.bytes)))
-        return fail("tfx_dit_step (ex2): keep_x0, keep_noise, keep_sigma, hold and cut must not alias latents, dit.out, dit.xin or v_prev");
+      if (p && q && (p == q || (p < q + w.bytes && q < p + r.bytes)))
+        return fail("tfx_dit_step (%s): %s must not alias latents, dit.out, dit.xin or v_prev", who,
+                    ch ? "keep_x0, keep_noise, keep_sigma, hold and cut" : "keep_x0, keep_noise, keep_mask and keep_sigma");
     }
   }
   return 0;
 }
 
-int step_capture(const tfx_step_desc* s, const tfx_step_extra& ex, tfx_stream stream, tfx_graph* out, const tfx_step_change* ch = nullptr) {
+int step_capture(const tfx_step_desc* s, const tfx_step_extra& ex, const tfx_step_change* ch, tfx_stream stream, tfx_graph* out) {
   if (!out) return fail("tfx_dit_step_capture: null output handle");
   if (!stream) return fail("tfx_dit_step_capture: the NULL stream cannot be captured; pass a created stream");
   hipStream_t st = S(stream);
@@ -829,50 +814,50 @@ int step_capture(const tfx_step_desc* s, const tfx_step_extra& ex, tfx_stream st
   *out = new StepGraph{g, x};
   return 0;
 }
-}  // namespace
 
-int tfx_dit_step_run(const tfx_step_desc* s, tfx_stream stream) {
-  TRY(step_check(s));
-  return step_enqueue(*s, S(stream), tfx_step_extra{});
+// Every step entry point: the checks, then the step on the stream, or (CAPTURE) captured from it into *graph_out
+enum { RUN = 0, CAPTURE = 1, NEED_HISTORY = 2 };
+int step_entry(const tfx_step_desc* s, const tfx_step_extra* ex, const tfx_step_change* ch, tfx_stream stream, tfx_graph* graph_out, int how) {
+  TRY(step_check_extra(s, ex, ch, ch ? "ex2" : "ex", (how & NEED_HISTORY) != 0));
+  return how & CAPTURE ? step_capture(s, *ex, ch, stream, graph_out) : step_enqueue(*s, S(stream), *ex, ch);
 }
 
-int tfx_dit_step_capture(const tfx_step_desc* s, tfx_stream stream, tfx_graph* out) {
-  TRY(step_check(s));
-  return step_capture(s, tfx_step_extra{}, stream, out);
-}
+const tfx_step_extra kPlain{};   // the plain step's tfx_step_extra: no history, no blend
 
-int tfx_dit_step_run_multistep(const tfx_step_desc* s, void* v_prev, tfx_stream stream) {
-  TRY(step_check_multistep(s, v_prev));
+// the *_multistep entry points' tfx_step_extra: the history alone
+tfx_step_extra history(void* v_prev) {
   tfx_step_extra ex{};
   ex.v_prev = v_prev;
-  return step_enqueue(*s, S(stream), ex);
+  return ex;
+}
+}  // namespace
+
+int tfx_dit_step_run(const tfx_step_desc* s, tfx_stream stream) { return step_entry(s, &kPlain, nullptr, stream, nullptr, RUN); }
+
+int tfx_dit_step_capture(const tfx_step_desc* s, tfx_stream stream, tfx_graph* out) { return step_entry(s, &kPlain, nullptr, stream, out, CAPTURE); }
+
+int tfx_dit_step_run_multistep(const tfx_step_desc* s, void* v_prev, tfx_stream stream) {
+  const tfx_step_extra ex = history(v_prev);
+  return step_entry(s, &ex, nullptr, stream, nullptr, RUN | NEED_HISTORY);
 }
 
 int tfx_dit_step_capture_multistep(const tfx_step_desc* s, void* v_prev, tfx_stream stream, tfx_graph* out) {
-  TRY(step_check_multistep(s, v_prev));
-  tfx_step_extra ex{};
-  ex.v_prev = v_prev;
-  return step_capture(s, ex, stream, out);
+  const tfx_step_extra ex = history(v_prev);
+  return step_entry(s, &ex, nullptr, stream, out, CAPTURE | NEED_HISTORY);
 }
 
-int tfx_dit_step_run_ex(const tfx_step_desc* s, const tfx_step_extra* ex, tfx_stream stream) {
-  TRY(step_check_ex(s, ex));
-  return step_enqueue(*s, S(stream), *ex);
-}
+int tfx_dit_step_run_ex(const tfx_step_desc* s, const tfx_step_extra* ex, tfx_stream stream) { return step_entry(s, ex, nullptr, stream, nullptr, RUN); }
 
 int tfx_dit_step_capture_ex(const tfx_step_desc* s, const tfx_step_extra* ex, tfx_stream stream, tfx_graph* out) {
-  TRY(step_check_ex(s, ex));
-  return step_capture(s, *ex, stream, out);
+  return step_entry(s, ex, nullptr, stream, out, CAPTURE);
 }
 
 int tfx_dit_step_run_ex2(const tfx_step_desc* s, const tfx_step_extra* ex, const tfx_step_change* ch, tfx_stream stream) {
-  TRY(step_check_ex2(s, ex, ch));
-  return step_enqueue(*s, S(stream), *ex, ch);
+  return step_entry(s, ex, ch, stream, nullptr, RUN);
 }
 
 int tfx_dit_step_capture_ex2(const tfx_step_desc* s, const tfx_step_extra* ex, const tfx_step_change* ch, tfx_stream stream, tfx_graph* out) {
-  TRY(step_check_ex2(s, ex, ch));
-  return step_capture(s, *ex, stream, out, ch);
+  return step_entry(s, ex, ch, stream, out, CAPTURE);
 }
 
 int tfx_dit_step_replay(tfx_graph graph, tfx_stream stream) {

@@ -3,6 +3,7 @@
 // All loads/stores are 16 B per lane (bf16x8); math is fp32; every bf16 rounding point of the
 // reference's unfused op chain is reproduced so results track the bf16 reference.
 #include <algorithm>
+#include <type_traits>
 
 #include "common.h"
 #include "launch.h"
@@ -217,6 +218,19 @@ __global__ __launch_bounds__(256) void rmsnorm_rope_kernel(bf16_t* __restrict__ 
 }
 
 // ---------------------------------------------------------------------------------------------
+// The mirror: the 8 values of chunk e0 of [rows, C] into xin's row pitch.  Every step-tail kernel ends in it.
+__device__ __forceinline__ void mirror_chunk(const u32x4& packed, bf16_t* __restrict__ xin, int64_t ldxin, int C, int64_t e0) {
+  if (!xin) return;
+  const int64_t row = e0 / C;
+  const int col = (int)(e0 - row * C);
+  *reinterpret_cast<u32x4*>(xin + row * ldxin + col) = packed;
+}
+__device__ __forceinline__ void store_and_mirror(bf16_t* xp, const u32x4& packed, bf16_t* __restrict__ xin, int64_t ldxin, int C,
+                                                 int64_t e0) {
+  *reinterpret_cast<u32x4*>(xp) = packed;
+  mirror_chunk(packed, xin, ldxin, C, e0);
+}
+
 // Scheduler steps on packed latents [rows, C] (C = 64): results are written both to the bf16 latent
 // state and, when xin != nullptr, into columns [0, C) of the next step's x_embedder input [rows, ldxin]
 // (this replaces the per-step torch.cat of pipeline_flux_fill.py:2085).
@@ -225,6 +239,7 @@ __global__ __launch_bounds__(256) void rmsnorm_rope_kernel(bf16_t* __restrict__ 
 //            x' = bf16( (f32(x) + bf16(dt * (-v))) * a + eps * b )
 // coef points at {dsigma} (Euler) or {dt_over, a, b} (AMO) per step; step index read from *step_ptr when
 // given (device-side, so that one captured graph serves every step), else `step`.
+
 template <bool AMO>
 __global__ __launch_bounds__(256) void sched_step_kernel(const bf16_t* __restrict__ v, bf16_t* __restrict__ x,
                                                          bf16_t* __restrict__ xin, int64_t ldxin, int C,
@@ -250,14 +265,7 @@ __global__ __launch_bounds__(256) void sched_step_kernel(const bf16_t* __restric
 #pragma unroll
     for (int j = 0; j < 8; ++j) o[j] = __fadd_rn(xx[j], round_bf(__fmul_rn(ds, vv[j])));
   }
-  const u32x4 packed = pack8(o);
-  *reinterpret_cast<u32x4*>(x + i * 8) = packed;
-  if (xin) {
-    const int64_t e0 = i * 8;
-    const int64_t row = e0 / C;
-    const int col = (int)(e0 - row * C);
-    *reinterpret_cast<u32x4*>(xin + row * ldxin + col) = packed;
-  }
+  store_and_mirror(x + i * 8, pack8(o), xin, ldxin, C, i * 8);
 }
 
 // Second-order multistep (Adams-Bashforth) update, same layout and xin mirror as sched_step_kernel; no reference counterpart
@@ -290,108 +298,89 @@ __global__ __launch_bounds__(256) void multistep_step_kernel(const bf16_t* __res
   }
   const u32x4 packed = pack8(o);
   *reinterpret_cast<u32x4*>(v_prev + i * 8) = vraw;
-  *reinterpret_cast<u32x4*>(x + i * 8) = packed;
-  if (xin) {
-    const int64_t e0 = i * 8;
-    const int64_t row = e0 / C;
-    const int col = (int)(e0 - row * C);
-    *reinterpret_cast<u32x4*>(xin + row * ldxin + col) = packed;
-  }
+  store_and_mirror(x + i * 8, packed, xin, ldxin, C, i * 8);
 }
 
-// Known-region blend behind a sampler update (FluxInpaintPipeline's loop, D/pipelines/flux/pipeline_flux_inpaint.py:974-984, with
-// FlowMatchEulerDiscreteScheduler.scale_noise, scheduling_flow_match_euler_discrete.py:174; DESIGN.md section 4 "Known-region
-// sampling").  x [rows, C] with row pitch ldx (the fused Euler form keeps the latents in xin[:, :C]); x0, noise, mask contiguous.
-// s = keep_sigma[step], sigma_{i+1} already rounded to bf16; every torch op of the reference rounds to bf16 on its own:
+// The blend behind a sampler update, known-region and change-map sampling alike: FluxInpaintPipeline's loop
+// (D/pipelines/flux/pipeline_flux_inpaint.py:974-984) and FluxDifferentialImg2ImgPipeline's (D/examples/community/
+// pipeline_flux_differential_img2img.py:974-986), with FlowMatchEulerDiscreteScheduler.scale_noise
+// (scheduling_flow_match_euler_discrete.py:174).  x [rows, C] with row pitch ldx (the fused Euler form keeps the latents in
+// xin[:, :C]); x0 and noise contiguous.  s = keep_sigma[step], sigma_{i+1} already rounded to bf16; every torch op of the references
+// rounds to bf16 on its own:
 //   a = bf16(s n)   u = bf16(1 - s)   b = bf16(u x0)   p = bf16(a + b)      (s < 0, the last step: p = x0, no arithmetic)
 //   w = bf16(1 - m) c = bf16(w p)     d = bf16(m x)    x' = bf16(c + d)
-// The literal formula also for binary masks: 0 * x keeps x's sign in a -0, and the tests pin it.
-__global__ __launch_bounds__(256) void known_region_blend_kernel(bf16_t* __restrict__ x, int64_t ldx, const bf16_t* __restrict__ x0,
-                                                                 const bf16_t* __restrict__ noise, const bf16_t* __restrict__ mask,
-                                                                 int C, int64_t nchunks, const float* __restrict__ keep_sigma,
-                                                                 const int* __restrict__ step_ptr, int step,
-                                                                 bf16_t* __restrict__ xin, int64_t ldxin) {
-  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (i >= nchunks) return;
-  const float s = keep_sigma[step_ptr ? *step_ptr : step];
-  const int64_t e0 = i * 8;
-  const int64_t row = e0 / C;
-  const int col = (int)(e0 - row * C);
-  bf16_t* xp = x + row * ldx + col;
-  float xx[8], zz[8], mm[8], p[8], o[8];
-  unpack8(*reinterpret_cast<const u32x4*>(xp), xx);
-  unpack8(*reinterpret_cast<const u32x4*>(x0 + e0), zz);
-  unpack8(*reinterpret_cast<const u32x4*>(mask + e0), mm);
-  if (s < 0.f) {
-#pragma unroll
-    for (int j = 0; j < 8; ++j) p[j] = zz[j];
-  } else {
-    float nn[8];
-    unpack8(*reinterpret_cast<const u32x4*>(noise + e0), nn);
-    const float u = round_bf(__fsub_rn(1.0f, s));
-#pragma unroll
-    for (int j = 0; j < 8; ++j) p[j] = round_bf(__fadd_rn(round_bf(__fmul_rn(s, nn[j])), round_bf(__fmul_rn(u, zz[j]))));
-  }
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    const float w = round_bf(__fsub_rn(1.0f, mm[j]));
-    o[j] = __fadd_rn(round_bf(__fmul_rn(w, p[j])), round_bf(__fmul_rn(mm[j], xx[j])));
-  }
-  const u32x4 packed = pack8(o);
-  *reinterpret_cast<u32x4*>(xp) = packed;
-  if (xin) *reinterpret_cast<u32x4*>(xin + row * ldxin + col) = packed;
-}
+// The literal formula, no select, also for binary masks: 0 * x keeps x's sign in a -0, and the tests pin it.  `mask` hands the chunk's
+// eight m to the `blend` continuation, or does not call it: then x is not written and the mirror into xin is still made.
 
-// Change-map blend behind a sampler update (FluxDifferentialImg2ImgPipeline's loop, D/examples/community/
-// pipeline_flux_differential_img2img.py:974-986; DESIGN.md section 4 "Change-map sampling"): known_region_blend_kernel with the mask
-// decided here from the step cursor.  hold [rows] is one 32-bit word per token, byte py*2+px = 255 - map of that latent pixel; a
-// thread's 8 columns are two channels x the four patch positions, so column j reads byte j & 3.  k = hold > cut[step] ? 1 : 0,
-//   p as above;  e = bf16(p k)   w = bf16(1 - k)   d = bf16(x w)   x' = bf16(e + d)
-// the reference's `image_latent * mask + latents * (1 - mask)` op by op, no select: p * 0 keeps p's sign in a -0.  cut[step] >= 255:
-// nothing is held and x is not written (the reference's last step leaves the latents alone; e + d would turn a -0 into +0); the
-// mirror into xin is still made.
-__global__ __launch_bounds__(256) void change_map_blend_kernel(bf16_t* __restrict__ x, int64_t ldx, const bf16_t* __restrict__ x0,
-                                                               const bf16_t* __restrict__ noise, const uint32_t* __restrict__ hold,
-                                                               const int* __restrict__ cut, int C, int64_t nchunks,
-                                                               const float* __restrict__ keep_sigma, const int* __restrict__ step_ptr,
-                                                               int step, bf16_t* __restrict__ xin, int64_t ldxin) {
+// Known-region sampling: m from a bf16 tensor of x0's shape (1 = free, 0 = known)
+struct TensorMask {
+  const bf16_t* mask;
+  template <class Blend>
+  __device__ __forceinline__ void operator()(int, int64_t, int64_t e0, Blend blend) const {
+    float mm[8];
+    unpack8(*reinterpret_cast<const u32x4*>(mask + e0), mm);
+    blend(mm);
+  }
+};
+
+// Change-map sampling: m decided here from the step cursor.  hold [rows] is one 32-bit word per token, byte py*2+px = 255 - map of that
+// latent pixel; a thread's 8 columns are two channels x the four patch positions, so column j reads byte j & 3.  A pixel is held
+// (m = 0, the reference's mask k = 1 - m = 1) where hold > cut[step]: with w = k this is the reference's `image_latent * mask +
+// latents * (1 - mask)` operand for operand.  cut[step] >= 255: nothing is held and the reference's last step leaves the latents
+// alone, where the arithmetic with m = 1 would turn a -0 into +0 -- no blend.
+struct HoldMask {
+  const uint32_t* hold;
+  const int* cut;
+  template <class Blend>
+  __device__ __forceinline__ void operator()(int cur, int64_t row, int64_t, Blend blend) const {
+    const int ct = cut[cur];
+    if (ct >= 255) return;
+    const uint32_t hw = hold[row];
+    float mm[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) mm[j] = (int)((hw >> (8 * (j & 3))) & 0xffu) > ct ? 0.0f : 1.0f;
+    blend(mm);
+  }
+};
+
+template <class Mask>
+__global__ __launch_bounds__(256) void post_update_blend_kernel(bf16_t* __restrict__ x, int64_t ldx, const bf16_t* __restrict__ x0,
+                                                                const bf16_t* __restrict__ noise, const Mask mask, int C,
+                                                                int64_t nchunks, const float* __restrict__ keep_sigma,
+                                                                const int* __restrict__ step_ptr, int step,
+                                                                bf16_t* __restrict__ xin, int64_t ldxin) {
   const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (i >= nchunks) return;
   const int cur = step_ptr ? *step_ptr : step;
-  const float s = keep_sigma[cur];
-  const int ct = cut[cur];
   const int64_t e0 = i * 8;
   const int64_t row = e0 / C;
   const int col = (int)(e0 - row * C);
   bf16_t* xp = x + row * ldx + col;
-  const u32x4 xraw = *reinterpret_cast<const u32x4*>(xp);
-  if (ct >= 255) {
-    if (xin) *reinterpret_cast<u32x4*>(xin + row * ldxin + col) = xraw;
-    return;
-  }
-  const uint32_t hw = hold[row];
-  float xx[8], zz[8], p[8], o[8];
-  unpack8(xraw, xx);
-  unpack8(*reinterpret_cast<const u32x4*>(x0 + e0), zz);
-  if (s < 0.f) {
+  u32x4 packed = *reinterpret_cast<const u32x4*>(xp);
+  mask(cur, row, e0, [&](const float (&mm)[8]) {
+    const float s = keep_sigma[cur];
+    float xx[8], zz[8], p[8], o[8];
+    unpack8(packed, xx);
+    unpack8(*reinterpret_cast<const u32x4*>(x0 + e0), zz);
+    if (s < 0.f) {
 #pragma unroll
-    for (int j = 0; j < 8; ++j) p[j] = zz[j];
-  } else {
-    float nn[8];
-    unpack8(*reinterpret_cast<const u32x4*>(noise + e0), nn);
-    const float u = round_bf(__fsub_rn(1.0f, s));
+      for (int j = 0; j < 8; ++j) p[j] = zz[j];
+    } else {
+      float nn[8];
+      unpack8(*reinterpret_cast<const u32x4*>(noise + e0), nn);
+      const float u = round_bf(__fsub_rn(1.0f, s));
 #pragma unroll
-    for (int j = 0; j < 8; ++j) p[j] = round_bf(__fadd_rn(round_bf(__fmul_rn(s, nn[j])), round_bf(__fmul_rn(u, zz[j]))));
-  }
+      for (int j = 0; j < 8; ++j) p[j] = round_bf(__fadd_rn(round_bf(__fmul_rn(s, nn[j])), round_bf(__fmul_rn(u, zz[j]))));
+    }
 #pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    const float k = (int)((hw >> (8 * (j & 3))) & 0xffu) > ct ? 1.0f : 0.0f;
-    const float w = __fsub_rn(1.0f, k);                 // 1 or 0: exact in bf16
-    o[j] = __fadd_rn(round_bf(__fmul_rn(p[j], k)), round_bf(__fmul_rn(xx[j], w)));
-  }
-  const u32x4 packed = pack8(o);
-  *reinterpret_cast<u32x4*>(xp) = packed;
-  if (xin) *reinterpret_cast<u32x4*>(xin + row * ldxin + col) = packed;
+    for (int j = 0; j < 8; ++j) {
+      const float w = round_bf(__fsub_rn(1.0f, mm[j]));
+      o[j] = __fadd_rn(round_bf(__fmul_rn(w, p[j])), round_bf(__fmul_rn(mm[j], xx[j])));
+    }
+    packed = pack8(o);
+    *reinterpret_cast<u32x4*>(xp) = packed;
+  });
+  mirror_chunk(packed, xin, ldxin, C, e0);
 }
 
 // Sinusoidal timestep embedding, flip_sin_to_cos=True, downscale_freq_shift=0, dim 256, fp32 -> bf16
@@ -709,11 +698,19 @@ int rmsnorm_rope(void* buf, int64_t ld, int64_t bstride, int q_off, int k_off, i
   return rmsnorm_rope_tab(buf, ld, bstride, q_off, k_off, H, Ntok, T, B, wq_img, wk_img, wq_txt, wk_txt, cosT, sinT, 0, eps, st);
 }
 
+// The shape checks of the step tail's launchers.  ldx: the row pitch of x, C where x is contiguous (16-byte accesses to x rows); xin
+// rows are stored 16 bytes at a time too.
+static int step_tail_check(const char* who, int C, int64_t rows, int64_t ldx, const void* xin, int64_t ldxin) {
+  if (C <= 0 || C % 8) return fail("%s: C must be a positive multiple of 8", who);
+  if (rows < 0) return fail("%s: negative row count", who);
+  if (ldx % 8 || ldx < C) return fail("%s: ldx must be a multiple of 8 and >= C", who);
+  if (xin && (ldxin % 8 || ldxin < C)) return fail("%s: ldxin must be a multiple of 8 and >= C", who);
+  return 0;
+}
+
 int sched_step(bool amo, const void* v, void* x, void* xin, int64_t ldxin, int C, int64_t rows, const float* coef,
                const int* step_ptr, int step, const float* noise, hipStream_t st) {
-  if (C <= 0 || C % 8) return fail("sched_step: C must be a positive multiple of 8");
-  if (rows < 0) return fail("sched_step: negative row count");
-  if (xin && (ldxin % 8 || ldxin < C)) return fail("sched_step: ldxin must be a multiple of 8 and >= C");   // 16-byte stores into xin rows
+  if (int e = step_tail_check("sched_step", C, rows, C, xin, ldxin)) return e;
   const int64_t nch = rows * C / 8;
   if (nch == 0) return 0;
   dim3 grid((unsigned)((nch + 255) / 256));
@@ -730,9 +727,7 @@ int sched_step(bool amo, const void* v, void* x, void* xin, int64_t ldxin, int C
 
 int multistep_step(const void* v, void* x, void* xin, int64_t ldxin, int C, int64_t rows, const float* coef,
                    const int* step_ptr, int step, void* v_prev, hipStream_t st) {
-  if (C <= 0 || C % 8) return fail("multistep_step: C must be a positive multiple of 8");
-  if (rows < 0) return fail("multistep_step: negative row count");
-  if (xin && (ldxin % 8 || ldxin < C)) return fail("multistep_step: ldxin must be a multiple of 8 and >= C");   // 16-byte stores into xin rows
+  if (int e = step_tail_check("multistep_step", C, rows, C, xin, ldxin)) return e;
   const int64_t nch = rows * C / 8;
   if (nch == 0) return 0;                               // nothing to update: the pointers of empty tensors mean nothing
   if (!v || !x || !coef) return fail("multistep_step: null pointer");
@@ -745,55 +740,51 @@ int multistep_step(const void* v, void* x, void* xin, int64_t ldxin, int C, int6
   return check_launch("multistep_step");
 }
 
-int known_region_blend(void* x, int64_t ldx, const void* x0, const void* noise, const void* mask, int C, int64_t rows,
-                       const float* keep_sigma, const int* step_ptr, int step, void* xin, int64_t ldxin, hipStream_t st) {
-  if (C <= 0 || C % 8) return fail("known_region_blend: C must be a positive multiple of 8");
-  if (rows < 0) return fail("known_region_blend: negative row count");
-  if (ldx % 8 || ldx < C) return fail("known_region_blend: ldx must be a multiple of 8 and >= C");             // 16-byte accesses to x rows
-  if (xin && (ldxin % 8 || ldxin < C)) return fail("known_region_blend: ldxin must be a multiple of 8 and >= C");
+// The one launcher of the two blends: `who` is the declared function's name.  A TensorMask's mask is a third [rows, C] bf16 operand
+// beside x0 and noise; a HoldMask's hold words and cut table are 4-byte data, and hold must not lie in what the kernel writes.
+template <class Mask>
+static int post_update_blend(const char* who, const Mask mask, void* x, int64_t ldx, const void* x0, const void* noise, int C, int64_t rows,
+                             const float* keep_sigma, const int* step_ptr, int step, void* xin, int64_t ldxin, hipStream_t st) {
+  constexpr bool held = std::is_same_v<Mask, HoldMask>;
+  if (int e = step_tail_check(who, C, rows, ldx, xin, ldxin)) return e;
   const int64_t nch = rows * C / 8;
   if (nch == 0) return 0;                               // nothing to blend: the pointers of empty tensors mean nothing
-  if (!x || !x0 || !noise || !mask || !keep_sigma) return fail("known_region_blend: null pointer");
-  if (((uintptr_t)x | (uintptr_t)x0 | (uintptr_t)noise | (uintptr_t)mask | (uintptr_t)xin) & 15)
-    return fail("known_region_blend: x, x0, noise, mask and xin must be 16-byte aligned");
+  const void* mt = nullptr;
+  bool mask_null;
+  if constexpr (held) mask_null = !mask.hold || !mask.cut;
+  else mask_null = !(mt = mask.mask);
+  if (!x || !x0 || !noise || mask_null || !keep_sigma) return fail("%s: null pointer", who);
+  if (((uintptr_t)x | (uintptr_t)x0 | (uintptr_t)noise | (uintptr_t)mt | (uintptr_t)xin) & 15)
+    return fail("%s: x, x0, noise%s and xin must be 16-byte aligned", who, held ? "" : ", mask");
+  if constexpr (held)
+    if (((uintptr_t)mask.hold | (uintptr_t)mask.cut | (uintptr_t)keep_sigma) & 3) return fail("%s: hold, cut and keep_sigma must be 4-byte aligned", who);
   const char* px = (const char*)x;
   const int64_t xbytes = ((rows - 1) * ldx + C) * 2, bytes = nch * 16;
-  for (const void* q : {x0, noise, mask}) {
+  for (const void* q : {x0, noise, mt}) {
     const char* p = (const char*)q;
-    if (p < px + xbytes && px < p + bytes) return fail("known_region_blend: x0, noise and mask must not alias x");
+    if (p && p < px + xbytes && px < p + bytes) return fail("%s: %s must not alias x", who, held ? "x0 and noise" : "x0, noise and mask");
   }
-  known_region_blend_kernel<<<dim3((unsigned)((nch + 255) / 256)), 256, 0, st>>>((bf16_t*)x, ldx, (const bf16_t*)x0, (const bf16_t*)noise,
-                                                                                 (const bf16_t*)mask, C, nch, keep_sigma, step_ptr, step,
-                                                                                 (bf16_t*)xin, ldxin);
-  return check_launch("known_region_blend");
+  if constexpr (held) {
+    const char* ph = (const char*)mask.hold;
+    const char* pi = (const char*)xin;
+    if ((ph < px + xbytes && px < ph + rows * 4) || (pi && ph < pi + ((rows - 1) * ldxin + C) * 2 && pi < ph + rows * 4))
+      return fail("%s: hold must not alias x or xin", who);
+  }
+  post_update_blend_kernel<<<dim3((unsigned)((nch + 255) / 256)), 256, 0, st>>>((bf16_t*)x, ldx, (const bf16_t*)x0, (const bf16_t*)noise, mask, C,
+                                                                                nch, keep_sigma, step_ptr, step, (bf16_t*)xin, ldxin);
+  return check_launch(who);
+}
+
+int known_region_blend(void* x, int64_t ldx, const void* x0, const void* noise, const void* mask, int C, int64_t rows,
+                       const float* keep_sigma, const int* step_ptr, int step, void* xin, int64_t ldxin, hipStream_t st) {
+  return post_update_blend("known_region_blend", TensorMask{(const bf16_t*)mask}, x, ldx, x0, noise, C, rows, keep_sigma, step_ptr, step,
+                           xin, ldxin, st);
 }
 
 int change_map_blend(void* x, int64_t ldx, const void* x0, const void* noise, const void* hold, const int* cut, int C, int64_t rows,
                      const float* keep_sigma, const int* step_ptr, int step, void* xin, int64_t ldxin, hipStream_t st) {
-  if (C <= 0 || C % 8) return fail("change_map_blend: C must be a positive multiple of 8");
-  if (rows < 0) return fail("change_map_blend: negative row count");
-  if (ldx % 8 || ldx < C) return fail("change_map_blend: ldx must be a multiple of 8 and >= C");               // 16-byte accesses to x rows
-  if (xin && (ldxin % 8 || ldxin < C)) return fail("change_map_blend: ldxin must be a multiple of 8 and >= C");
-  const int64_t nch = rows * C / 8;
-  if (nch == 0) return 0;                               // nothing to blend: the pointers of empty tensors mean nothing
-  if (!x || !x0 || !noise || !hold || !cut || !keep_sigma) return fail("change_map_blend: null pointer");
-  if (((uintptr_t)x | (uintptr_t)x0 | (uintptr_t)noise | (uintptr_t)xin) & 15)
-    return fail("change_map_blend: x, x0, noise and xin must be 16-byte aligned");
-  if (((uintptr_t)hold | (uintptr_t)cut | (uintptr_t)keep_sigma) & 3) return fail("change_map_blend: hold, cut and keep_sigma must be 4-byte aligned");
-  const char* px = (const char*)x;
-  const int64_t xbytes = ((rows - 1) * ldx + C) * 2, bytes = nch * 16;
-  for (const void* q : {x0, noise}) {
-    const char* p = (const char*)q;
-    if (p < px + xbytes && px < p + bytes) return fail("change_map_blend: x0 and noise must not alias x");
-  }
-  const char* ph = (const char*)hold;
-  const char* pi = (const char*)xin;
-  if ((ph < px + xbytes && px < ph + rows * 4) || (pi && ph < pi + ((rows - 1) * ldxin + C) * 2 && pi < ph + rows * 4))
-    return fail("change_map_blend: hold must not alias x or xin");
-  change_map_blend_kernel<<<dim3((unsigned)((nch + 255) / 256)), 256, 0, st>>>((bf16_t*)x, ldx, (const bf16_t*)x0, (const bf16_t*)noise,
-                                                                               (const uint32_t*)hold, cut, C, nch, keep_sigma, step_ptr, step,
-                                                                               (bf16_t*)xin, ldxin);
-  return check_launch("change_map_blend");
+  return post_update_blend("change_map_blend", HoldMask{(const uint32_t*)hold, cut}, x, ldx, x0, noise, C, rows, keep_sigma, step_ptr, step,
+                           xin, ldxin, st);
 }
 
 int timestep_embedding(const float* t, void* out, int n, hipStream_t st) {

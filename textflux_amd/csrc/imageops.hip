@@ -100,53 +100,55 @@ __global__ __launch_bounds__(256) void pack_mask_kernel(const TM* __restrict__ m
   *reinterpret_cast<u32x4*>(out + bt * ld + col0 + c8 * 8) = pack8(v);
 }
 
-// The packed latent mask of known-region sampling: mask [B, H, W] uint8 -> out [B, S, C] bf16 1.0 / 0.0 with
-// out[b, t, c*4 + py*2+px] = m(2ty+py, 2tx+px) for every c -- _pack_latents of the latent-resolution mask repeated over the latent
-// channels (FluxInpaintPipeline.prepare_mask_latents, D/pipelines/flux/pipeline_flux_inpaint.py:615, :656-662).
-//   mode 0  nearest, the reference's F.interpolate: m(ly, lx) = mask[8 ly, 8 lx] >= 128
-//   mode 1  cover: m = 1 if any pixel of the 8x8 blocks of latent pixels [ly-grow, ly+grow] x [lx-grow, lx+grow] (clipped) is >= 128
-// One thread = one token: four latent pixels, each block row one 8-byte load (>= 128 is the top bit of a byte), C/8 equal stores.
-__global__ __launch_bounds__(256) void keep_mask_pack_kernel(const uint8_t* __restrict__ mask, bf16_t* __restrict__ out, int B, int H,
-                                                             int W, int C, int mode, int grow) {
-  const int h = H / 8, w = W / 8, h2 = H / 16, w2 = W / 16;
-  const int64_t S = (int64_t)h2 * w2;
-  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (i >= B * S) return;
-  const int b = (int)(i / S);
-  const int t = (int)(i - b * S);
-  const int ty = t / w2, tx = t - ty * w2;
-  const uint8_t* mb = mask + (int64_t)b * H * W;
-  float v[8];
-#pragma unroll
-  for (int pp = 0; pp < 4; ++pp) {
-    const int ly = 2 * ty + (pp >> 1), lx = 2 * tx + (pp & 1);
-    bool on;
-    if (mode == 0) {
-      on = mb[(int64_t)ly * 8 * W + lx * 8] >= 128;
-    } else {
-      const int r0 = max(ly - grow, 0) * 8, r1 = (min(ly + grow, h - 1) + 1) * 8;
-      const int c0 = max(lx - grow, 0), c1 = min(lx + grow, w - 1);
-      uint64_t any = 0;
-      for (int r = r0; r < r1; ++r) {
-        const uint64_t* rowp = reinterpret_cast<const uint64_t*>(mb + (int64_t)r * W);
-        for (int c = c0; c <= c1; ++c) any |= rowp[c];
-      }
-      on = (any & 0x8080808080808080ull) != 0;
-    }
-    v[pp] = v[pp + 4] = on ? 1.0f : 0.0f;
-  }
-  const u32x4 packed = pack8(v);
-  bf16_t* o = out + i * C;
-  for (int c8 = 0; c8 < C / 8; ++c8) *reinterpret_cast<u32x4*>(o + c8 * 8) = packed;
-}
+// The per-token packers of known-region and change-map sampling: in [B, H, W] uint8, one thread = one token =
+// four latent pixels (ly, lx) = (2ty+py, 2tx+px), each reduced over the bytes of a window of the image:
+//   mode 0  nearest, the references' F.interpolate: the one byte in[8 ly, 8 lx]
+//   mode 1  cover: the 8x8 blocks of latent pixels [ly-grow, ly+grow] x [lx-grow, lx+grow] (clipped), each block row one 8-byte load
+// `Reduce` folds the 8-byte words into its Acc (a single byte stands as the word that holds it alone), turns a pixel's Acc into the
+// pixel's value and stores the token's four.
 
-// The hold bytes of change-map sampling: map [B, H, W] uint8 (255 = free from the first step, 0 = never changes)
-// -> hold [B, S, 4] uint8, hold[b, t, py*2+px] = 255 - g(2ty+py, 2tx+px); keep_mask_pack_kernel carried over to grey values.
-//   mode 0  nearest, the reference's F.interpolate: g(ly, lx) = map[8 ly, 8 lx]
-//   mode 1  cover: g = the maximum of map over the 8x8 blocks of latent pixels [ly-grow, ly+grow] x [lx-grow, lx+grow] (clipped)
-// One thread = one token, one 32-bit store; each block row one 8-byte load, the byte maximum taken on the two 4-byte halves.
-__global__ __launch_bounds__(256) void change_map_pack_kernel(const uint8_t* __restrict__ map, uint32_t* __restrict__ hold, int B, int H,
-                                                              int W, int mode, int grow) {
+// The packed latent mask of known-region sampling: out [B, S, C] bf16 1.0 / 0.0 with out[b, t, c*4 + py*2+px] = m(ly, lx) for every c
+// -- _pack_latents of the latent-resolution mask repeated over the latent channels (FluxInpaintPipeline.prepare_mask_latents,
+// D/pipelines/flux/pipeline_flux_inpaint.py:615, :656-662).  m = 1 if any byte of the window is >= 128 (the top bit of a byte);
+// C/8 equal 16-byte stores.
+struct AnyTopBit {
+  using Acc = uint64_t;
+  bf16_t* out;
+  int C;
+  static __device__ __forceinline__ Acc merge(Acc any, uint64_t v) { return any | v; }
+  static __device__ __forceinline__ uint32_t value(Acc any) { return (any & 0x8080808080808080ull) != 0; }
+  __device__ __forceinline__ void store(int64_t i, const uint32_t (&on)[4]) const {
+    float v[8];
+#pragma unroll
+    for (int pp = 0; pp < 4; ++pp) v[pp] = v[pp + 4] = on[pp] ? 1.0f : 0.0f;
+    const u32x4 packed = pack8(v);
+    bf16_t* o = out + i * C;
+    for (int c8 = 0; c8 < C / 8; ++c8) *reinterpret_cast<u32x4*>(o + c8 * 8) = packed;
+  }
+};
+
+// The hold bytes of change-map sampling: map (255 = free from the first step, 0 = never changes) -> hold [B, S, 4] uint8,
+// hold[b, t, py*2+px] = 255 - g(ly, lx), g the maximum byte of the window, taken on the two 4-byte halves of a word; one 32-bit store.
+struct ByteMax {
+  using Acc = uint32_t;
+  uint32_t* hold;
+  static __device__ __forceinline__ Acc merge(Acc g, uint64_t v) {
+#pragma unroll
+    for (int k = 0; k < 8; ++k) g = max(g, (uint32_t)(v >> (8 * k)) & 0xffu);
+    return g;
+  }
+  static __device__ __forceinline__ uint32_t value(Acc g) { return 255u - g; }
+  __device__ __forceinline__ void store(int64_t i, const uint32_t (&byte)[4]) const {
+    uint32_t word = 0;
+#pragma unroll
+    for (int pp = 0; pp < 4; ++pp) word |= byte[pp] << (8 * pp);
+    hold[i] = word;
+  }
+};
+
+template <class Reduce>
+__global__ __launch_bounds__(256) void latent_pack_kernel(const uint8_t* __restrict__ in, const Reduce red, int B, int H, int W, int mode,
+                                                          int grow) {
   const int h = H / 8, w = W / 8, h2 = H / 16, w2 = W / 16;
   const int64_t S = (int64_t)h2 * w2;
   const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
@@ -154,30 +156,25 @@ __global__ __launch_bounds__(256) void change_map_pack_kernel(const uint8_t* __r
   const int b = (int)(i / S);
   const int t = (int)(i - b * S);
   const int ty = t / w2, tx = t - ty * w2;
-  const uint8_t* mb = map + (int64_t)b * H * W;
-  uint32_t word = 0;
+  const uint8_t* mb = in + (int64_t)b * H * W;
+  uint32_t px[4];
 #pragma unroll
   for (int pp = 0; pp < 4; ++pp) {
     const int ly = 2 * ty + (pp >> 1), lx = 2 * tx + (pp & 1);
-    uint32_t g;
     if (mode == 0) {
-      g = mb[(int64_t)ly * 8 * W + lx * 8];
+      px[pp] = Reduce::value(mb[(int64_t)ly * 8 * W + lx * 8]);
     } else {
       const int r0 = max(ly - grow, 0) * 8, r1 = (min(ly + grow, h - 1) + 1) * 8;
       const int c0 = max(lx - grow, 0), c1 = min(lx + grow, w - 1);
-      g = 0;
+      typename Reduce::Acc acc = 0;
       for (int r = r0; r < r1; ++r) {
         const uint64_t* rowp = reinterpret_cast<const uint64_t*>(mb + (int64_t)r * W);
-        for (int c = c0; c <= c1; ++c) {
-          const uint64_t v = rowp[c];
-#pragma unroll
-          for (int k = 0; k < 8; ++k) g = max(g, (uint32_t)(v >> (8 * k)) & 0xffu);
-        }
+        for (int c = c0; c <= c1; ++c) acc = Reduce::merge(acc, rowp[c]);
       }
+      px[pp] = Reduce::value(acc);      // per branch: a pixel leaves either one as one register, not as a 64-bit Acc
     }
-    word |= (255u - g) << (8 * pp);
   }
-  hold[i] = word;
+  red.store(i, px);
 }
 
 // moments NHWC [B, h, w, 2L] (mean | logvar) bf16, eps [B, L, h, w] bf16 or fp32 (null: the mode) ->
@@ -1416,30 +1413,33 @@ int pack_mask(const void* mask, int mask_dtype, void* out, int B, int H, int W, 
   return check_launch("pack_mask");
 }
 
+// The argument checks the two latent packers share; C: the packed mask's channel count, nullptr where the output has none
+static int latent_pack_check(const char* who, int B, int H, int W, const int* C, int mode, int grow) {
+  if (B < 0 || H < 0 || W < 0 || H % 16 || W % 16) return fail("%s: B >= 0; H and W non-negative multiples of 16", who);
+  if (C && (*C <= 0 || *C % 8)) return fail("%s: C must be a positive multiple of 8", who);
+  if (mode != 0 && mode != 1) return fail("%s: mode must be 0 (nearest) or 1 (cover)", who);
+  if (mode == 0 && grow != 0) return fail("%s: grow must be 0 in mode 0 (nearest)", who);
+  if (grow < 0 || grow > 8) return fail("%s: grow %d outside 0..8", who, grow);
+  return 0;
+}
+
 int keep_mask_pack(const void* mask_u8, void* out, int B, int H, int W, int C, int mode, int grow, hipStream_t st) {
-  if (B < 0 || H < 0 || W < 0 || H % 16 || W % 16) return fail("keep_mask_pack: B >= 0; H and W non-negative multiples of 16");
-  if (C <= 0 || C % 8) return fail("keep_mask_pack: C must be a positive multiple of 8");
-  if (mode != 0 && mode != 1) return fail("keep_mask_pack: mode must be 0 (nearest) or 1 (cover)");
-  if (mode == 0 && grow != 0) return fail("keep_mask_pack: grow must be 0 in mode 0 (nearest)");
-  if (grow < 0 || grow > 8) return fail("keep_mask_pack: grow %d outside 0..8", grow);
+  if (int e = latent_pack_check("keep_mask_pack", B, H, W, &C, mode, grow)) return e;
   const int64_t n = (int64_t)B * (H / 16) * (W / 16);
   if (n == 0) return 0;
   if (!mask_u8 || !out) return fail("keep_mask_pack: null pointer");
   if (((uintptr_t)mask_u8 & 7) || ((uintptr_t)out & 15)) return fail("keep_mask_pack: mask must be 8-byte and out 16-byte aligned");
-  keep_mask_pack_kernel<<<blocks_for(n), 256, 0, st>>>((const uint8_t*)mask_u8, (bf16_t*)out, B, H, W, C, mode, grow);
+  latent_pack_kernel<<<blocks_for(n), 256, 0, st>>>((const uint8_t*)mask_u8, AnyTopBit{(bf16_t*)out, C}, B, H, W, mode, grow);
   return check_launch("keep_mask_pack");
 }
 
 int change_map_pack(const void* map_u8, void* hold, int B, int H, int W, int mode, int grow, hipStream_t st) {
-  if (B < 0 || H < 0 || W < 0 || H % 16 || W % 16) return fail("change_map_pack: B >= 0; H and W non-negative multiples of 16");
-  if (mode != 0 && mode != 1) return fail("change_map_pack: mode must be 0 (nearest) or 1 (cover)");
-  if (mode == 0 && grow != 0) return fail("change_map_pack: grow must be 0 in mode 0 (nearest)");
-  if (grow < 0 || grow > 8) return fail("change_map_pack: grow %d outside 0..8", grow);
+  if (int e = latent_pack_check("change_map_pack", B, H, W, nullptr, mode, grow)) return e;
   const int64_t n = (int64_t)B * (H / 16) * (W / 16);
   if (n == 0) return 0;
   if (!map_u8 || !hold) return fail("change_map_pack: null pointer");
   if (((uintptr_t)map_u8 & 7) || ((uintptr_t)hold & 3)) return fail("change_map_pack: map must be 8-byte and hold 4-byte aligned");
-  change_map_pack_kernel<<<blocks_for(n), 256, 0, st>>>((const uint8_t*)map_u8, (uint32_t*)hold, B, H, W, mode, grow);
+  latent_pack_kernel<<<blocks_for(n), 256, 0, st>>>((const uint8_t*)map_u8, ByteMax{(uint32_t*)hold}, B, H, W, mode, grow);
   return check_launch("change_map_pack");
 }
 

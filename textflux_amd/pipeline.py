@@ -3,7 +3,7 @@ reference class (diffusers/src/diffusers/pipelines/flux/pipeline_flux_fill.py:13
 `run_inference.py`-style callers can switch by changing one import.
 
 What is different underneath:
-* the denoising loop (step_loop.py) never re-enters Python-level model code: per step it is ONE `tfx_dit_step_run`, or the
+* the denoising loop (step_loop.py) never re-enters Python-level model code: per step it is ONE `tfx_dit_step_run_ex2`, or the
   replay of the graph captured from it -- the forward and a scheduler update that also writes the new latents into the next
   x_embedder input (no torch.cat per step, P:2085);
 * context projection, RoPE tables and the time/guidance/pooled embedding -> AdaLN modulation of ALL steps are computed
@@ -112,6 +112,24 @@ class _NullBar:
         pass
 
 
+def _check_mode_grow(who, mode, grow):
+    """the latent packers' mode / grow, as `keep_known` and `change_map` both take them"""
+    if mode not in ("nearest", "cover"):
+        raise ValueError(f"{who}: mode must be 'nearest' or 'cover', got {mode!r}")
+    if grow < 0 or grow > 8 or (mode == "nearest" and grow != 0):
+        raise ValueError(f"{who}: grow is 0 for mode 'nearest' and 0..8 for mode 'cover'")
+
+
+def _repeat_to_batch(t, total, message):
+    """t [b, ...] -> [total, ...] by whole repeats; ValueError(message, with {have} and {total} filled in) where b does not divide total"""
+    have = t.shape[0]
+    if have < total:
+        if total % have:
+            raise ValueError(message.format(have=have, total=total))
+        t = t.repeat(total // have, *([1] * (t.dim() - 1)))
+    return t
+
+
 def _keep_known_cfg(keep_known):
     """keep_known = None / False | True | dict(mode="nearest" | "cover", grow=int) -> None | (mode, grow)"""
     if keep_known is None or keep_known is False:
@@ -120,10 +138,7 @@ def _keep_known_cfg(keep_known):
     mode, grow = cfg.pop("mode", "nearest"), int(cfg.pop("grow", 0))
     if cfg:
         raise ValueError(f"keep_known: unknown keys {sorted(cfg)}")
-    if mode not in ("nearest", "cover"):
-        raise ValueError(f"keep_known: mode must be 'nearest' or 'cover', got {mode!r}")
-    if grow < 0 or grow > 8 or (mode == "nearest" and grow != 0):
-        raise ValueError("keep_known: grow is 0 for mode 'nearest' and 0..8 for mode 'cover'")
+    _check_mode_grow("keep_known", mode, grow)
     return mode, grow
 
 
@@ -147,10 +162,7 @@ def _change_map_cfg(change_map):
         raise ValueError("change_map: dilate / feather derive the map from mask_image and do not go with an explicit map")
     out = dict(map=given, dilate=int(cfg.get("dilate", DILATE)), feather=int(cfg.get("feather", FEATHER)), mode=cfg.get("mode", "nearest"),
                grow=int(cfg.get("grow", 0)), last=cfg.get("last", "keep"))
-    if out["mode"] not in ("nearest", "cover"):
-        raise ValueError(f"change_map: mode must be 'nearest' or 'cover', got {out['mode']!r}")
-    if out["grow"] < 0 or out["grow"] > 8 or (out["mode"] == "nearest" and out["grow"] != 0):
-        raise ValueError("change_map: grow is 0 for mode 'nearest' and 0..8 for mode 'cover'")
+    _check_mode_grow("change_map", out["mode"], out["grow"])
     if out["last"] not in ("keep", "free"):
         raise ValueError(f"change_map: last must be 'keep' or 'free', got {out['last']!r}")
     if out["dilate"] < 0 or out["feather"] < 0:
@@ -615,10 +627,7 @@ class FluxFillPipeline:
             keep = dict(keep, sigma=sch.keep_sigma_table(dev, BF16))
         else:
             keep = None
-        if change is not None:
-            return step_loop.denoise(self, ses, mod, latents, coef, n, progress_bar, is_amo, fuse, amo_noise, on_step, multistep, keep,
-                                     change)
-        return step_loop.denoise(self, ses, mod, latents, coef, n, progress_bar, is_amo, fuse, amo_noise, on_step, multistep, keep)
+        return step_loop.denoise(self, ses, mod, latents, coef, n, progress_bar, is_amo, fuse, amo_noise, on_step, multistep, keep, change)
 
     # ------------------------------------------------------------------ known-region sampling
     def get_timesteps(self, num_inference_steps, strength, device):
@@ -653,10 +662,7 @@ class FluxFillPipeline:
                 flag = ops.any_negative(raw) if self.image_processor.do_normalize else None
                 x8 = ops.prep_image(raw, None, norm_mode=2 if flag is not None else 0, neg_flag=flag)
             x0 = self._sample_and_pack(self.vae.encode_moments_nhwc(x8), generator, dtype, dev)
-        if x0.shape[0] < total:
-            if total % x0.shape[0]:
-                raise ValueError(f"Cannot duplicate `image` of batch size {x0.shape[0]} to {total} text prompts.")
-            x0 = x0.repeat(total // x0.shape[0], 1, 1)
+        x0 = _repeat_to_batch(x0, total, "Cannot duplicate `image` of batch size {have} to {total} text prompts.")
         noise = noise.to(dev, BF16).contiguous()
         x0 = x0.contiguous()
         if x0.shape != noise.shape:
@@ -671,15 +677,9 @@ class FluxFillPipeline:
         if keep_cfg is not None:
             if mask_image is None:
                 raise ValueError("keep_known needs `mask_image`: the known region is what lies outside it")
-            rawm = self.mask_processor.to_raw(mask_image, height=height, width=width).to(dev)
-            if rawm.dtype != torch.uint8:
-                rawm = (rawm.reshape(rawm.shape[0], rawm.shape[-2], rawm.shape[-1]) >= 0.5).to(torch.uint8) * 255
-            mk = ops.keep_mask_pack(rawm, x0.shape[-1], keep_cfg[0], keep_cfg[1])
-            if mk.shape[0] < total:
-                if total % mk.shape[0]:
-                    raise ValueError("The passed mask and the required batch size don't match. Masks are supposed to be duplicated to"
-                                     f" a total batch size of {total}, but {mk.shape[0]} masks were passed.")
-                mk = mk.repeat(total // mk.shape[0], 1, 1)
+            mk = ops.keep_mask_pack(self._mask_image_u8(mask_image, height, width, dev), x0.shape[-1], keep_cfg[0], keep_cfg[1])
+            mk = _repeat_to_batch(mk, total, "The passed mask and the required batch size don't match. Masks are supposed to be duplicated to"
+                                             " a total batch size of {total}, but {have} masks were passed.")
             if mk.shape != x0.shape:
                 raise ValueError(f"mask_image packs to {tuple(mk.shape)}, the latents are {tuple(x0.shape)}")
             keep["mask"] = mk
@@ -687,6 +687,13 @@ class FluxFillPipeline:
             keep["hold"] = self._change_hold(change_cfg, mask_image, height, width, total, x0.shape[1], dev)
             keep["last"] = change_cfg["last"]
         return start, keep
+
+    def _mask_image_u8(self, mask_image, height, width, device):
+        """-> the call's mask as uint8 [B, height, width] on the device, a float mask cut at 0.5 (>= 128 is inside the mask)"""
+        rawm = self.mask_processor.to_raw(mask_image, height=height, width=width).to(device)
+        if rawm.dtype != torch.uint8:
+            rawm = (rawm.reshape(rawm.shape[0], rawm.shape[-2], rawm.shape[-1]) >= 0.5).to(torch.uint8) * 255
+        return rawm
 
     # ------------------------------------------------------------------ change-map sampling (DESIGN.md section 4)
     def change_map_u8(self, change_cfg, mask_image, height, width, device):
@@ -696,11 +703,8 @@ class FluxFillPipeline:
         if given is None:
             if mask_image is None:
                 raise ValueError("change_map needs `mask_image` (the map is derived from it) or an explicit map")
-            rawm = self.mask_processor.to_raw(mask_image, height=height, width=width).to(device)
-            if rawm.dtype != torch.uint8:
-                rawm = (rawm.reshape(rawm.shape[0], rawm.shape[-2], rawm.shape[-1]) >= 0.5).to(torch.uint8) * 255
             from .paste_back import alpha_mask
-            return alpha_mask(rawm.contiguous(), change_cfg["dilate"], change_cfg["feather"])
+            return alpha_mask(self._mask_image_u8(mask_image, height, width, device).contiguous(), change_cfg["dilate"], change_cfg["feather"])
         if isinstance(given, np.ndarray):
             given = torch.from_numpy(np.ascontiguousarray(given))
         if isinstance(given, torch.Tensor):
@@ -718,11 +722,8 @@ class FluxFillPipeline:
     def _change_hold(self, change_cfg, mask_image, height, width, total, S, device):
         """-> the hold bytes uint8 [total, S, 4] of the call (ops.change_map_pack of its change map), duplicated like a mask"""
         hold = ops.change_map_pack(self.change_map_u8(change_cfg, mask_image, height, width, device), change_cfg["mode"], change_cfg["grow"])
-        if hold.shape[0] < total:
-            if total % hold.shape[0]:
-                raise ValueError("The passed change_map and the required batch size don't match. Maps are supposed to be duplicated to"
-                                 f" a total batch size of {total}, but {hold.shape[0]} maps were passed.")
-            hold = hold.repeat(total // hold.shape[0], 1, 1)
+        hold = _repeat_to_batch(hold, total, "The passed change_map and the required batch size don't match. Maps are supposed to be duplicated"
+                                             " to a total batch size of {total}, but {have} maps were passed.")
         if tuple(hold.shape) != (total, S, 4):
             raise ValueError(f"change_map packs to {tuple(hold.shape)}, the latents have {(total, S)} tokens")
         return hold.contiguous()
@@ -1130,8 +1131,7 @@ class FluxFillPipeline:
                 raise ValueError(f"After adjusting the num_inference_steps by strength parameter: {strength}, the number of pipeline"
                                  f"steps is {num_inference_steps} which is < 1 and not appropriate for this pipeline.")
             latents, keep = self._prepare_known_region(latents, given_latents, image_latents, src_image, mask_image, keep_cfg, strength,
-                                                       height, width, prompt_embeds.dtype, device, generator,
-                                                       **(dict(change_cfg=change_cfg) if change_cfg is not None else {}))
+                                                       height, width, prompt_embeds.dtype, device, generator, change_cfg=change_cfg)
         self._num_timesteps = len(timesteps)
         with self.progress_bar(total=num_inference_steps) as bar:
             if engine:

@@ -1,8 +1,8 @@
-"""The engine's denoising loop, once: n steps of tfx_dit_step_run -- or of the replay of the graph captured
+"""The engine's denoising loop, once: n steps of tfx_dit_step_run_ex2 -- or of the replay of the graph captured
 from it -- for the plain loop (phase 0) and the step cache (phases 1, 2 / 3), the Euler, AMO, fused-Euler and multistep samplers (the
-last through tfx_dit_step_run_multistep), with or without a step callback, on uniform and mixed-geometry sessions; with the
-known-region blend behind every sampler update (tfx_dit_step_run_ex) when the call keeps the known region, or the change-map blend
-(tfx_dit_step_run_ex2) when the call gives every latent pixel its own release step.
+last by the history buffer in the step's tfx_step_extra), with or without a step callback, on uniform and mixed-geometry sessions; with
+the known-region blend behind every sampler update (the tfx_step_extra's keep_* buffers) when the call keeps the known region, or the
+change-map blend (a tfx_step_change beside it) when the call gives every latent pixel its own release step.
 
 `run_steps` is the control flow and touches no device: it drives a `steps` object with
     feed_noise(i)   run(phase)   replay(handle)   capture(phase) -> handle (raises CaptureRefused)   destroy(handle)
@@ -88,19 +88,22 @@ class SessionSteps:
         self.ses, self.gb, self.side, self.st, self.lib = ses, gb, side, side.cuda_stream, L.lib()
         self.sd = {ph: ses.step_desc(gb, is_amo, fuse, phase=ph) for ph in phases}
         self.is_amo, self.amo_noise = is_amo, amo_noise
-        # the multistep sampler: sampler 0's descriptor through the *_multistep entry points, with the session's history buffer
-        self.v_prev = gb["v_prev"].data_ptr() if multistep else None
-        # known-region sampling: the same descriptors through the *_ex entry points, the blend's buffers beside them
-        self.extra = None
-        if keep:
-            self.extra = L.StepExtra(v_prev=self.v_prev, keep_x0=gb["keep_x0"].data_ptr(), keep_noise=gb["keep_noise"].data_ptr(),
-                                     keep_mask=gb["keep_mask"].data_ptr(), keep_sigma=gb["keep_sigma"].data_ptr())
-        # change-map sampling: the *_ex2 entry points, keep_mask NULL and the hold bytes / cut table in a tfx_step_change beside
+        # One entry point serves every loop: an all-NULL tfx_step_extra is the plain step, v_prev alone the multistep sampler
+        # (sampler 0's descriptor, the session's history buffer), keep_* all set the known-region blend; with a tfx_step_change
+        # (hold bytes, cut table) keep_mask stays NULL and the blend is the change-map's.
+        ptr = lambda name: gb[name].data_ptr()
+        self.v_prev = ptr("v_prev") if multistep else None
+        self.extra = L.StepExtra(v_prev=self.v_prev)
         self.change = None
+        if keep or change:
+            self.extra.keep_x0, self.extra.keep_noise, self.extra.keep_sigma = ptr("known_x0"), ptr("known_noise"), ptr("known_sigma")
+        if keep:
+            self.extra.keep_mask = ptr("known_mask")
         if change:
-            self.extra = L.StepExtra(v_prev=self.v_prev, keep_x0=gb["change_x0"].data_ptr(), keep_noise=gb["change_noise"].data_ptr(),
-                                     keep_mask=None, keep_sigma=gb["change_sigma"].data_ptr())
-            self.change = L.StepChange(hold=gb["change_hold"].data_ptr(), cut=gb["change_cut"].data_ptr())
+            self.change = L.StepChange(hold=ptr("known_hold"), cut=ptr("known_cut"))
+        self.args = {ph: (C.byref(sd), C.byref(self.extra), C.byref(self.change) if change else None) for ph, sd in self.sd.items()}
+        # what a failing step is reported as: the entry point of the C ABI that stands for this loop
+        self.what = "dit_step_run" + ("_ex2" if change else "_ex" if keep else "_multistep" if multistep else "")
 
     def feed_noise(self, i):
         if not self.is_amo:
@@ -111,29 +114,14 @@ class SessionSteps:
             self.gb["noise"].copy_(self.amo_noise[i].to(self.gb["noise"].device, torch.float32))
 
     def run(self, ph):
-        if self.change is not None:
-            L.check(self.lib.tfx_dit_step_run_ex2(C.byref(self.sd[ph]), C.byref(self.extra), C.byref(self.change), self.st), "dit_step_run_ex2")
-        elif self.extra is not None:
-            L.check(self.lib.tfx_dit_step_run_ex(C.byref(self.sd[ph]), C.byref(self.extra), self.st), "dit_step_run_ex")
-        elif self.v_prev is not None:
-            L.check(self.lib.tfx_dit_step_run_multistep(C.byref(self.sd[ph]), self.v_prev, self.st), "dit_step_run_multistep")
-        else:
-            L.check(self.lib.tfx_dit_step_run(C.byref(self.sd[ph]), self.st), "dit_step_run")
+        L.check(self.lib.tfx_dit_step_run_ex2(*self.args[ph], self.st), self.what)
 
     def replay(self, handle):
         L.check(self.lib.tfx_dit_step_replay(handle, self.st), "dit_step_replay")
 
     def capture(self, ph):
         h = C.c_void_p()
-        if self.change is not None:
-            rc = self.lib.tfx_dit_step_capture_ex2(C.byref(self.sd[ph]), C.byref(self.extra), C.byref(self.change), self.st, C.byref(h))
-        elif self.extra is not None:
-            rc = self.lib.tfx_dit_step_capture_ex(C.byref(self.sd[ph]), C.byref(self.extra), self.st, C.byref(h))
-        elif self.v_prev is not None:
-            rc = self.lib.tfx_dit_step_capture_multistep(C.byref(self.sd[ph]), self.v_prev, self.st, C.byref(h))
-        else:
-            rc = self.lib.tfx_dit_step_capture(C.byref(self.sd[ph]), self.st, C.byref(h))
-        if rc != 0:
+        if self.lib.tfx_dit_step_capture_ex2(*self.args[ph], self.st, C.byref(h)) != 0:
             raise CaptureRefused(self.lib.tfx_last_error().decode())
         return h.value
 
@@ -168,11 +156,11 @@ def denoise(pipe, ses, mod, latents, coef, n, progress_bar, is_amo=False, fuse=F
     multistep sampler -- unfused, coef its [n, 2] table, the history buffer gb["v_prev"] owned by the session; a callback that
     replaces the latents leaves the history (the previous model output) as it is.  keep: known-region sampling --
     dict(x0, noise, mask: bf16 [B, S, C]; sigma: fp32 [n], the scheduler's keep_sigma_table): after every sampler update the latents
-    become (1 - mask) scale_noise(x0, sigma_{i+1}, noise) + mask latents (tfx_known_region_blend inside the step); the buffers live in
-    the session next to v_prev, because captured graphs bake their addresses.  change: change-map sampling --
-    dict(x0, noise: bf16 [B, S, C]; hold: uint8 [B, S, 4]; sigma: fp32 [n]; cut: int32 [n], schedulers.change_cut_table): the same blend
-    with the mask decided inside the step, held where hold > cut[step] (tfx_change_map_blend); not together with keep; its buffers
-    live in the session too.  Runs on the session's side
+    become (1 - mask) scale_noise(x0, sigma_{i+1}, noise) + mask latents (tfx_known_region_blend inside the step).  change:
+    change-map sampling -- dict(x0, noise: bf16 [B, S, C]; hold: uint8 [B, S, 4]; sigma: fp32 [n]; cut: int32 [n],
+    schedulers.change_cut_table): the same blend with the mask decided inside the step, held where hold > cut[step]
+    (tfx_change_map_blend); not together with keep.  Either one's buffers live in the session next to v_prev, because captured graphs
+    bake their addresses.  Runs on the session's side
     stream (capture needs a non-NULL stream), fenced against the caller's current stream on both sides.  The step cache is on when
     pipe.enable_step_cache() is in force; graphs when pipe.enable_hip_graph(True), no callback and n > 1.  Returns the final
     latents and leaves pipe.step_cache_report set."""
@@ -189,32 +177,25 @@ def denoise(pipe, ses, mod, latents, coef, n, progress_bar, is_amo=False, fuse=F
         assert not is_amo and not fuse and latents is not None
         if "v_prev" not in gb:           # lives and dies with gb: captured graphs bake its address; step 0 never reads it
             gb["v_prev"] = torch.empty_like(gb["lat"])
-    if keep is not None:
+    known = keep if keep is not None else change
+    if known is not None:
         if ses.mixed:
-            raise NotImplementedError("known-region sampling does not serve mixed-geometry sessions")
-        assert keep["sigma"].numel() == n and keep["sigma"].dtype == torch.float32
-        if "keep_x0" not in gb:          # live and die with gb, like v_prev
-            gb.update({"keep_" + k: torch.empty_like(gb["lat"]) for k in ("x0", "noise", "mask")})
-            gb["keep_sigma"] = torch.zeros(gb["mod_table"].shape[0], dtype=torch.float32, device=dev)
-        for k in ("x0", "noise", "mask"):
-            gb["keep_" + k].copy_(keep[k])
-        gb["keep_sigma"][:n].copy_(keep["sigma"])
-    if change is not None:
-        if keep is not None:
+            raise NotImplementedError(("known-region sampling" if keep is not None else "change_map (change-map sampling)")
+                                      + " does not serve mixed-geometry sessions")
+        if keep is not None and change is not None:
             raise ValueError("change_map and keep_known exclude each other")
-        if ses.mixed:
-            raise NotImplementedError("change_map (change-map sampling) does not serve mixed-geometry sessions")
-        assert change["sigma"].numel() == n and change["sigma"].dtype == torch.float32
-        assert change["cut"].numel() == n and change["cut"].dtype == torch.int32
-        if "change_x0" not in gb:        # live and die with gb, like v_prev
-            gb.update({"change_" + k: torch.empty_like(gb["lat"]) for k in ("x0", "noise")})
-            gb["change_hold"] = torch.empty(shape[0], shape[1], 4, dtype=torch.uint8, device=dev)
-            gb["change_sigma"] = torch.zeros(gb["mod_table"].shape[0], dtype=torch.float32, device=dev)
-            gb["change_cut"] = torch.zeros(gb["mod_table"].shape[0], dtype=torch.int32, device=dev)
-        for k in ("x0", "noise", "hold"):
-            gb["change_" + k].copy_(change[k])
-        gb["change_sigma"][:n].copy_(change["sigma"])
-        gb["change_cut"][:n].copy_(change["cut"])
+        # one buffer family for both blends, living and dying with gb like v_prev: x0, noise and sigma, and the mask or the hold
+        # bytes and the cut table
+        for k in ("x0", "noise", "mask" if keep is not None else "hold"):             # per token
+            if "known_" + k not in gb:
+                gb["known_" + k] = torch.empty(*shape[:2], 4, dtype=torch.uint8, device=dev) if k == "hold" else torch.empty_like(gb["lat"])
+            gb["known_" + k].copy_(known[k])
+        per_step = {"sigma": torch.float32} if keep is not None else {"sigma": torch.float32, "cut": torch.int32}
+        for k, dtype in per_step.items():                                             # as long as the session's longest schedule
+            assert known[k].numel() == n and known[k].dtype == dtype
+            if "known_" + k not in gb:
+                gb["known_" + k] = torch.zeros(gb["mod_table"].shape[0], dtype=dtype, device=dev)
+            gb["known_" + k][:n].copy_(known[k])
     decider = None
     if pipe._step_cache is not None:
         ses.step_cache_reset()
