@@ -185,17 +185,85 @@ def fp8_bytes(t: torch.Tensor) -> torch.Tensor:
     return q.view(torch.uint8)
 
 
-def quantizable_rows(shape, seed: int):
+def quantizable_rows(shape, seed: int, edge_peaks: bool = False):
     """bf16 rows whose quantisation is known exactly: row r = 2^e_r * integers in [-8, 8] with one entry +-448, so the scale is 2^e_r
-    and the codes are the integers.  Returns (x bf16, codes uint8, scale fp32)."""
+    and the codes are the integers.  edge_peaks: the first row of every sample has its +-448 in the last column and the second row in
+    the first, so a row maximum that misses the last (partly filled) round of a workgroup's lanes gives another scale.
+    Returns (x bf16, codes uint8, scale fp32)."""
     ints = integers(shape, -8, 8, seed)
     pos = torch.randint(0, shape[-1], shape[:-1], generator=gen(seed + 1))
+    if edge_peaks:
+        pos[..., 0] = shape[-1] - 1
+        pos[..., 1:2] = 0
     sign = torch.where(torch.rand(shape[:-1], generator=gen(seed + 2)) < 0.5, -448.0, 448.0)
     ints.scatter_(-1, pos[..., None], sign[..., None])
     scale = pow2(shape[:-1], -3, 3, seed + 3)
     x = ints * scale[..., None]
     assert bool((x.to(BF).float() == x).all())
     return x.to(BF), fp8_bytes(ints), scale
+
+
+# --------------------------------------------------------------------------------------------------------- K-sliced launches
+def plan_slices(T: int, per_batch: int, batch: int, nt: int, ws_bytes: int, grid: int):
+    """gemm.hip::plan_slices restated: (slices, whole-tile units, sliced tiles per sample) of a persistent-kernel GEMM with T tiles of
+    nt K-tiles (128 bytes of a row: 64 bf16 or 128 e4m3 values), a workspace and gemm_splitk = 2 (the default).  A slice keeps an even
+    number >= 8 of K-tiles, a (tile, slice) unit takes 256 KiB of the workspace."""
+    def ok(units, c):
+        return units * c <= grid and nt % (2 * c) == 0 and nt // c >= 8 and units * c * 262144 <= ws_bytes
+    if T < grid:
+        for c in (8, 6, 4, 3, 2):
+            if ok(T, c):
+                return c, 0, per_batch
+        return 1, 0, 0
+    R = T % grid
+    if R == 0 or T // grid >= 8 or R % batch:
+        return 1, 0, 0
+    for c in (4, 3, 2):
+        if ok(R, c):
+            return c, T - R, R // batch
+    return 1, 0, 0
+
+
+def gemm_tiles(B: int, M: int, N: int):
+    """(T, tiles per sample) of 256 x 256 output tiles."""
+    per_batch = ((M + 255) // 256) * ((N + 255) // 256)
+    return B * per_batch, per_batch
+
+
+def plan_slices_bf16(B: int, M: int, N: int, K: int, ws_bytes: int, grid: int):
+    T, per_batch = gemm_tiles(B, M, N)
+    return plan_slices(T, per_batch, B, K // 64, ws_bytes, grid)
+
+
+def plan_slices_fp8(B: int, M: int, N: int, K: int, ws_bytes: int, grid: int):
+    """gemm.hip::launch_fp8: K-tiles of 128 e4m3 bytes, and only a whole GEMM with fewer tiles than workgroups is sliced."""
+    T, per_batch = gemm_tiles(B, M, N)
+    return plan_slices(T, per_batch, B, K // 128, ws_bytes, grid) if T < grid else (1, 0, 0)
+
+
+@functools.lru_cache(maxsize=None)
+def fp8_sliced_case(B: int, M: int, N: int, K: int) -> dict:
+    """One K-sliced fp8 case, shared by the GPU test and the CPU fault injection: gemm_operands' ternary values (as e4m3 bytes: aq, wq),
+    power-of-two row scales sa [B, M] and channel scales sw [N], gate and res, and lin = bf16(acc * sa * sw + bias).  The accumulator
+    bound max|acc + bias| <= 256 holds at the default density of a quarter for every K of GEMM_FP8_KSLICE (K = 15360: 4.5 standard
+    deviations of sqrt(K / 16) = 31 are 140), so no case lowers it.  Callers must not modify what they get."""
+    seed = shape_seed(B, M, N, K, 8)
+    cs = gemm_operands(B, M, N, K, seed)
+    cs.update(sa=pow2((B, M), -3, 3, seed + 5), sw=pow2((N,), -3, 3, seed + 6), gate=gates(B, N, seed + 11), res=arbitrary_bf16((B, M, N), seed + 12),
+              aq=fp8_bytes(cs["a"]), wq=fp8_bytes(cs["w"]))
+    cs["lin"] = linear_bf16(cs["acc"], cs["bias"].float(), row_scale=cs["sa"], col_scale=cs["sw"])
+    return cs
+
+
+def k_slice_products(cs: dict, slices: int) -> torch.Tensor:
+    """fp64 [slices, B, M, N]: the contribution of each of `slices` equal K ranges to acc (their sum is acc, asserted)."""
+    a, w = cs["a"].double(), cs["w"].double()
+    K = a.shape[-1]
+    assert K % slices == 0
+    ks = K // slices
+    parts = torch.stack([a[..., s * ks:(s + 1) * ks] @ w[:, s * ks:(s + 1) * ks].T for s in range(slices)])
+    assert torch.equal(parts.sum(0), cs["acc"])
+    return parts
 
 
 # --------------------------------------------------------------------------------------------------------- q / k norm + RoPE
@@ -995,7 +1063,17 @@ def t5_case(rows: int, D: int, f32: bool) -> dict:
 # --------------------------------------------------------------------------------------------------------- the shapes of tests/test_exact_gpu.py
 # (tests/test_exact_inputs_cpu.py runs every generator at every one of them: a condition that fails must fail without a GPU)
 GEMM_EPI_SHAPES = [(2, 300, 264, 128), (3, 37, 72, 192), (1, 8, 64, 128), (2, 513, 520, 384)]          # (B, M, N, K)
-GEMM_KSLICE_KS = (1024, 1536, 2048, 3072)                                                              # (1, 300, 520, K)
+GEMM_WS_BYTES = 64 << 20                                # the workspace of every K-slicing test: the engine's scratch, 256 units of 256 KiB
+GEMM_KSLICE_BMN = (1, 300, 520)                         # 6 tiles, ragged both ways (row tiles of 256 and 44 rows, column tiles of 256, 256 and 8)
+GEMM_KSLICE = {1024: 2, 1536: 3, 2048: 4, 3072: 6, 4096: 8}                                            # bf16 K: slices at grids 256 and 304
+GEMM_KSLICE_KS = tuple(GEMM_KSLICE)                                                                    # (1, 300, 520, K)
+# fp8 K: slices.  Every slice count tail_reduce_kernel has a case for, and the production depths 3072, 12288, 15360 (16 .. 120 K-tiles)
+GEMM_FP8_KSLICE = {2048: 2, 3072: 3, 4096: 4, 6144: 6, 8192: 8, 12288: 8, 15360: 6}
+GEMM_FP8_BATCH2, GEMM_FP8_BATCH2_SLICES = (2, 300, 520, 3072), 3                                       # 12 tiles
+# quantize_rows_fp8 (B, rows, K): 256 lanes take 8 values each per round -- quant_rows_fp8_kernel<2> up to K = 4096, <6> up to 12288, <8> up
+# to 16384.  4104: the first K of <6>, one lane in its third round | 12288: <6> full | 12296: the first K of <8> | 16384: the limit
+QUANT_SHAPES = [(2, 37, 256), (1, 300, 512), (2, 5, 4104), (1, 3, 12288), (1, 3, 12296), (1, 2, 16384)]
+QUANT_K_LIMIT = 16384
 GEMM_TAIL_SHAPE = (1, 4096, 9216, 1024)
 # |lin| <= 71 at K <= 3072, and gate * lin is then a bf16 number for every gate of GATES: epilogue 2's intermediate rounding cannot be
 # seen.  At K = 12288 (std 28) a couple of dozen elements of this launch have a |lin| whose product with +-0.75 / +-1.5 needs a ninth bit.

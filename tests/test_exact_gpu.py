@@ -8,6 +8,7 @@ import pytest
 import torch
 
 from tests.helpers import exact_inputs as X
+from tests.helpers import framing
 
 pytestmark = pytest.mark.gpu
 
@@ -26,34 +27,17 @@ def grid_of_device():
     return torch.cuda.get_device_properties(0).multi_processor_count & ~7
 
 
-def plan_slices(T, per_batch, batch, nt, ws_bytes, grid):
-    """gemm.hip::plan_slices restated: (slices, whole-tile units, sliced tiles per sample) of a persistent-kernel GEMM with T tiles of
-    nt 64-wide K-tiles, a workspace and gemm_splitk = 2 (the default)."""
-    def ok(units, c):
-        return units * c <= grid and nt % (2 * c) == 0 and nt // c >= 8 and units * c * 262144 <= ws_bytes
-    if T < grid:
-        for c in (8, 6, 4, 3, 2):
-            if ok(T, c):
-                return c, 0, per_batch
-        return 1, 0, 0
-    R = T % grid
-    if R == 0 or T // grid >= 8 or R % batch:
-        return 1, 0, 0
-    for c in (4, 3, 2):
-        if ok(R, c):
-            return c, T - R, R // batch
-    return 1, 0, 0
-
-
 def epilogue_operands(B, M, N, seed):
     return X.gates(B, N, seed + 11), X.arbitrary_bf16((B, M, N), seed + 12)
 
 
 def check_epilogue(got, epi, lin, res, gate, gelu_from, what):
     """got against the chain of `epi` on the exact Linear output lin.  GELU columns: one bf16 step against the fp64 tanh-GELU of the exact
-    pre-activation -- common.h::gelu_tanh evaluates x * rcp(1 + exp2(x * fma(x * x, c1, c0))): no cancelling subtraction, and v_exp_f32 /
-    v_rcp_f32 are accurate to ~1e-6 relative, far inside half a bf16 step (2e-3), so the device value can only land on the other side of a
-    rounding boundary the fp64 value sits next to -- and bit-equal where that value is 0 or x itself."""
+    pre-activation -- common.h::gelu_tanh evaluates x * (rcp(exp2(z - 32) + 2^-32) * 2^-32), z = x * fma(x * x, c1, c0): no cancelling
+    subtraction, and v_exp_f32 / v_rcp_f32 are accurate to ~1e-6 relative, far inside half a bf16 step (2e-3), so the device value can only
+    land on the other side of a rounding boundary the fp64 value sits next to -- and bit-equal where that value is 0 or x itself.  The
+    scale of 2^-32 keeps both transcendental results normal (they flush subnormals) down to values that round to zero: the fp8 cases' scaled
+    pre-activations reach x in [-10.4, -10.0], where GELU is 1e-37 .. 1e-40 and the unscaled form returned -0, four and more bf16 steps away."""
     want = X.chain(epi, lin, res=res, gate=gate, gelu_from_col=gelu_from)
     got = got.cpu()
     if epi != 1:
@@ -98,13 +82,13 @@ def test_gemm_epilogue_chains_per_element(ops, B, M, N, K, variant):
 
 @pytest.mark.parametrize("K", X.GEMM_KSLICE_KS)
 def test_gemm_whole_k_slicing_is_exact(ops, K):
-    """(1, 300, 520, K): 6 tiles, fewer than CUs, so with a workspace the auto path cuts every tile into 2 / 3 / 4 / 6 K slices (fp32
+    """(1, 300, 520, K): 6 tiles, fewer than CUs, so with a workspace the auto path cuts every tile into 2 / 3 / 4 / 6 / 8 K slices (fp32
     partials, summed by tail_reduce_kernel, then the epilogue).  Every epilogue must give the chain's bits, which are also the unsliced
     persistent kernel's -- where Gaussian inputs allow 2 % of one-step flips."""
-    B, M, N = 1, 300, 520
-    want_slices = {1024: 2, 1536: 3, 2048: 4, 3072: 6}[K]
-    ws = torch.empty(64 << 20, dtype=torch.uint8, device="cuda")
-    plan = plan_slices(6, 6, 1, K // 64, ws.numel(), grid_of_device())
+    B, M, N = X.GEMM_KSLICE_BMN
+    want_slices = X.GEMM_KSLICE[K]
+    ws = torch.empty(X.GEMM_WS_BYTES, dtype=torch.uint8, device="cuda")
+    plan = X.plan_slices_bf16(B, M, N, K, ws.numel(), grid_of_device())
     if plan[0] != want_slices:
         pytest.skip(f"this device plans {plan[0]} slices at K = {K}, not {want_slices}")
     seed = X.shape_seed(B, M, N, K)
@@ -121,8 +105,8 @@ def test_gemm_whole_k_slicing_is_exact(ops, K):
 
 def test_gemm_k_slicing_keeps_identical_samples_identical(ops):
     B, M, N, K = 2, 300, 520, 1024
-    ws = torch.empty(64 << 20, dtype=torch.uint8, device="cuda")
-    if plan_slices(12, 6, 2, K // 64, ws.numel(), grid_of_device())[0] != 2:
+    ws = torch.empty(X.GEMM_WS_BYTES, dtype=torch.uint8, device="cuda")
+    if X.plan_slices_bf16(B, M, N, K, ws.numel(), grid_of_device())[0] != 2:
         pytest.skip("this device does not slice 12 tiles in two")
     seed = X.shape_seed(1, M, N, K)
     cs = X.gemm_operands(1, M, N, K, seed)
@@ -143,9 +127,9 @@ def test_gemm_sliced_last_round_is_exact(ops):
     magnitude <= 1024 < 2^24 -- whose rows 61 + 256 i, 125 + 256 i, 189 + 256 i, 253 + 256 i of every row tile (64 rows: each of the 576
     tiles, the sliced ones included) are recomputed in fp64 on the CPU."""
     B, M, N, K = X.GEMM_TAIL_SHAPE
-    ws = torch.empty(64 << 20, dtype=torch.uint8, device="cuda")
+    ws = torch.empty(X.GEMM_WS_BYTES, dtype=torch.uint8, device="cuda")
     grid = grid_of_device()
-    plan = plan_slices(576, 576, 1, K // 64, ws.numel(), grid)
+    plan = X.plan_slices_bf16(B, M, N, K, ws.numel(), grid)
     if plan != (2, 512, 64):
         pytest.skip(f"this device ({grid} persistent workgroups) plans {plan}, not 2 slices of the last 64 tiles")
     seed = X.shape_seed(B, M, N, K)
@@ -272,26 +256,175 @@ def test_gemm_lora_row_split_takes_the_second_weight_set(ops, R, fused_norm):
 @pytest.mark.parametrize("B,M,N,K", X.GEMM_FP8_SHAPES)
 def test_gemm_fp8_is_exact_on_ternary_codes(ops, B, M, N, K):
     """The same ternary values as e4m3 bytes, power-of-two row and channel scales: acc * s_a * s_w + bias is an fp32 number (asserted),
-    rounded once; epilogues 0, 2, 3, with and without a workspace (few-tile shapes then run K-sliced)."""
+    rounded once; epilogues 0, 1, 2, 3, with and without a workspace.  These shapes have two and four 128-byte K-tiles and a slice keeps
+    eight, so they are NEVER K-sliced (asserted from the restated plan): both arms run gemm8pp_kernel<EPI, 2, true>, the workspace arm
+    only shows that an unused workspace changes nothing.  The sliced fp8 kernels are test_gemm_fp8_whole_k_slicing_is_exact's."""
     seed = X.shape_seed(B, M, N, K)
     cs = X.gemm_operands(B, M, N, K, seed)
     gate, res = epilogue_operands(B, M, N, seed)
     sa, sw = X.pow2((B, M), -3, 3, seed + 5), X.pow2((N,), -3, 3, seed + 6)
     lin = X.linear_bf16(cs["acc"], cs["bias"].float(), row_scale=sa, col_scale=sw)
     aq, wq = X.fp8_bytes(cs["a"]).cuda(), X.fp8_bytes(cs["w"]).cuda()
-    ws = torch.empty(64 << 20, dtype=torch.uint8, device="cuda")
-    for epi in (0, 2, 3):
+    ws = torch.empty(X.GEMM_WS_BYTES, dtype=torch.uint8, device="cuda")
+    assert X.plan_slices_fp8(B, M, N, K, ws.numel(), grid_of_device()) == (1, 0, 0)
+    gf = 256 if N > 256 else 0
+    for epi in (0, 1, 2, 3):
         kw = dict(res=res.cuda(), gate=gate.cuda()) if epi == 2 else dict(res=res.cuda()) if epi == 3 else {}
         for wsp in (None, ws):
-            got = ops.gemm_fp8(aq, sa.cuda(), wq, sw.cuda(), cs["bias"].cuda(), epilogue=epi, workspace=wsp, **kw)
-            check_epilogue(got, epi, lin, res, gate, 0, f"gemm_fp8 epilogue {epi} workspace {wsp is not None}")
+            got = ops.gemm_fp8(aq, sa.cuda(), wq, sw.cuda(), cs["bias"].cuda(), epilogue=epi, gelu_from_col=gf, workspace=wsp, **kw)
+            check_epilogue(got, epi, lin, res, gate, gf, f"gemm_fp8 epilogue {epi} workspace {wsp is not None}")
 
 
-@pytest.mark.parametrize("shape", [(2, 37, 256), (1, 300, 512)])
+WS_NAN = 0x7FC0BEEF           # the workspace's fill: a quiet NaN with a payload no arithmetic produces
+
+
+class Fp8Framed:
+    """An X.fp8_sliced_case on the device in the arrangement of test_gemm_epilogue_chains_per_element: A a column slice of a wider uint8
+    buffer (row pitch K + 64 bytes, the other bytes hold e4m3 1.0 and must stay), C a column slice inside a sentinel frame, res aliasing C."""
+
+    def __init__(self, ops, cs):
+        self.ops, self.cs = ops, cs
+        self.B, self.M, self.K = cs["aq"].shape
+        self.N = cs["wq"].shape[0]
+        self.abuf = torch.full((self.B, self.M, self.K + 64), 0x38, dtype=torch.uint8, device="cuda")
+        self.abuf[:, :, 64:] = cs["aq"].cuda()
+        self.dev = {k: cs[k].cuda() for k in ("sa", "wq", "sw", "bias", "gate", "res")}
+
+    def run(self, epi, workspace, gelu_from=256):
+        d, N = self.dev, self.N
+        cbuf = torch.full((self.B, self.M, N + 136), SENTINEL, dtype=BF, device="cuda")
+        out = cbuf[:, :, 128:128 + N]
+        kw = {}
+        if epi in (2, 3):
+            out.copy_(d["res"])
+            kw = dict(res=out, gate=d["gate"]) if epi == 2 else dict(res=out)
+        self.ops.gemm_fp8(self.abuf[:, :, 64:], d["sa"], d["wq"], d["sw"], d["bias"], out=out, epilogue=epi, gelu_from_col=gelu_from,
+                          workspace=workspace, **kw)
+        assert (cbuf[:, :, :128] == SENTINEL).all() and (cbuf[:, :, 128 + N:] == SENTINEL).all(), "bytes outside the C slice were written"
+        return out
+
+    def check_operand_untouched(self):
+        assert (self.abuf[:, :, :64] == 0x38).all() and torch.equal(self.abuf[:, :, 64:].cpu(), self.cs["aq"])
+
+
+def check_sliced_workspace(ws32, B, M, N, slices, acc, what):
+    """The device-side proof that `slices` K slices ran: of a workspace filled with WS_NAN, the first T * slices units of 256 KiB -- [slice]
+    [tile][256][256] fp32, tiles in the kernels' order, which with at most 12 column tiles is sample, row tile, column tile
+    (gemm.hip::make_params: gm = 1) -- have every in-range element overwritten, nothing beyond them has changed, and the slices'
+    partials sum to the integer product (they are the raw accumulators: fp8 scales and the bias come after the reduction)."""
+    T, _ = X.gemm_tiles(B, M, N)
+    tm, tn = (M + 255) // 256, (N + 255) // 256
+    assert tn <= 12
+    units = T * slices
+    changed = (ws32 != WS_NAN).view(-1, 65536)
+    touched = changed.any(1).nonzero()
+    extent = (int(touched.max()) + 1 if touched.numel() else 0) * 262144
+    print(f"{what}: workspace written up to {extent} bytes; T * sk * 256 KiB = {T} * {slices} * 262144 = {units * 262144}")
+    assert not bool(changed[units:].any()), f"{what}: the workspace changed beyond {units} units of 256 KiB"
+
+    def in_range(t):
+        return t.view(slices, B, tm, tn, 256, 256).permute(0, 1, 2, 4, 3, 5).reshape(slices, B, tm * 256, tn * 256)[:, :, :M, :N]
+    assert bool(in_range(changed[:units]).all()), f"{what}: a (slice, tile) unit was not written, or not all of its rows and columns"
+    assert extent == units * 262144
+    parts = in_range(ws32[:units * 65536].view(torch.float32))
+    assert torch.equal(parts.double().sum(0).cpu(), acc), f"{what}: the slices' partials do not sum to the integer product"
+
+
+def fp8_sliced_checks(ops, B, M, N, K, slices, epilogues):
+    """Sliced (workspace) and unsliced (no workspace) launches of one X.fp8_sliced_case under `epilogues`: each against the chain, the two
+    against each other bit for bit, the slicing proven from the workspace."""
+    cs = X.fp8_sliced_case(B, M, N, K)
+    f = Fp8Framed(ops, cs)
+    ws32 = torch.empty(X.GEMM_WS_BYTES // 4, dtype=torch.int32, device="cuda")
+    for epi in epilogues:
+        what = f"gemm_fp8 ({B}, {M}, {N}, {K}) epilogue {epi}"
+        ws32.fill_(WS_NAN)
+        sliced = f.run(epi, ws32)
+        check_sliced_workspace(ws32, B, M, N, slices, cs["acc"], what)
+        unsliced = f.run(epi, None)
+        check_epilogue(sliced, epi, cs["lin"], cs["res"], cs["gate"], 256, f"{what}, {slices} K slices")
+        check_epilogue(unsliced, epi, cs["lin"], cs["res"], cs["gate"], 256, f"{what}, unsliced at {K // 128} K-tiles")
+        X.assert_elementwise(sliced, unsliced, f"{what}, sliced vs unsliced")
+    f.check_operand_untouched()
+    return f
+
+
+@pytest.mark.parametrize("K", list(X.GEMM_FP8_KSLICE))
+def test_gemm_fp8_whole_k_slicing_is_exact(ops, K):
+    """The fp8 twin of test_gemm_whole_k_slicing_is_exact.  (1, 300, 520, K): 6 tiles, so with a workspace launch_fp8 cuts every tile into
+    2 / 3 / 4 / 6 / 8 K slices -- gemm8pp_kernel<EPI_BIAS, 2, true, true> writes fp32 partials, tail_reduce_kernel<EPI, true> sums them,
+    applies the row scale, the channel scale, the bias and the epilogue -- at every slice count the reduction has a case for and at the
+    production depths K = 3072, 12288, 15360.  Ternary e4m3 operands, power-of-two scales: ONE bf16 value per element, so every epilogue of
+    the sliced launch must give the chain's bits (GELU columns as check_epilogue treats them) and the bits of the launch without a
+    workspace, which is itself compared with the chain: the exact test of the unsliced fp8 kernel at 16 .. 120 K-tiles.  A and C are
+    column slices of wider buffers, res aliases C.  That slicing happened is read from the workspace (check_sliced_workspace), not inferred
+    from the restated plan; the plan only decides the skip on a device whose workgroup count gives another slice count.
+    The accumulator bound of X.gemm_operands holds at every K at the default density of a quarter, K = 15360 included."""
+    B, M, N = X.GEMM_KSLICE_BMN
+    slices = X.GEMM_FP8_KSLICE[K]
+    plan = X.plan_slices_fp8(B, M, N, K, X.GEMM_WS_BYTES, grid_of_device())
+    if plan[0] != slices:
+        pytest.skip(f"this device plans {plan[0]} slices at K = {K}, not {slices}")
+    fp8_sliced_checks(ops, B, M, N, K, slices, (0, 1, 2, 3))
+
+
+def test_gemm_fp8_k_slicing_takes_each_samples_own_row_scales(ops):
+    """(2, 300, 520, 3072): 12 tiles in 3 slices.  Two different samples with different row scales, epilogues 0 and 2 -- tail_reduce_kernel
+    reads a_scale[b * M + m], the gate and the residual per sample -- and then the first sample twice: identical samples, identical bits."""
+    B, M, N, K = X.GEMM_FP8_BATCH2
+    slices = X.GEMM_FP8_BATCH2_SLICES
+    plan = X.plan_slices_fp8(B, M, N, K, X.GEMM_WS_BYTES, grid_of_device())
+    if plan[0] != slices:
+        pytest.skip(f"this device plans {plan[0]} slices for 12 tiles at K = {K}, not {slices}")
+    cs = X.fp8_sliced_case(B, M, N, K)
+    assert not torch.equal(cs["aq"][0], cs["aq"][1]) and int((cs["sa"][0] != cs["sa"][1]).sum()) > M // 2
+    f = fp8_sliced_checks(ops, B, M, N, K, slices, (0, 2))
+    d = f.dev
+    aq = f.abuf[:1, :, 64:].expand(B, M, K).contiguous()
+    twice = {k: d[k][:1].expand(B, *d[k].shape[1:]).contiguous() for k in ("sa", "gate", "res")}
+    lin, res, gate = (cs[k][:1].expand(B, *cs[k].shape[1:]) for k in ("lin", "res", "gate"))
+    ws = torch.empty(X.GEMM_WS_BYTES, dtype=torch.uint8, device="cuda")
+    for epi in (0, 2):
+        kw = dict(res=twice["res"], gate=twice["gate"]) if epi == 2 else {}
+        got = ops.gemm_fp8(aq, twice["sa"], d["wq"], d["sw"], d["bias"], epilogue=epi, workspace=ws, **kw)
+        check_epilogue(got, epi, lin, res, gate, 0, f"gemm_fp8 K-sliced, the same sample twice, epilogue {epi}")
+        assert torch.equal(got[0], got[1])
+
+
+def quantize_framed(ops, x):
+    """quantize_rows_fp8 of x (CPU) through row- and batch-strided views inside canary frames: x in a bf16 frame of -2^127 (a value read from
+    it would become the row maximum), the codes in a uint8 frame, the scales in a flat one.  Returns (codes, scales) on the CPU."""
+    B, R, K = x.shape
+    xbuf, xv = framing.framed(B, R, K)
+    xv.copy_(x)
+    qbuf, qv = framing.framed(B, R, K, dtype=torch.uint8)
+    sbuf, sv = framing.flat_framed((B, R), dtype=torch.float32)
+    assert not xv.is_contiguous() and not qv.is_contiguous() and xv.stride(0) != R * xv.stride(1)
+    ops.quantize_rows_fp8(xv, out=qv, scale=sv)
+    framing.check_frame(qbuf, qv, "quantize_rows_fp8 codes")
+    framing.check_frame(sbuf, sv, "quantize_rows_fp8 scales")
+    assert torch.equal(xv.cpu(), x), "quantize_rows_fp8 wrote its input"
+    framing.check_frame(xbuf, xv, "quantize_rows_fp8 input")
+    return qv.cpu(), sv.cpu()
+
+
+@pytest.mark.parametrize("shape", X.QUANT_SHAPES)
 def test_quantize_rows_fp8_reproduces_known_codes_and_scales(ops, shape):
-    x, codes, scale = X.quantizable_rows(shape, X.shape_seed(*shape))
+    """Rows whose scale (a power of two) and codes (integers) are known, at the K edges of all three instantiations: <2> (256, 512), <6>
+    (4104: its first K, one lane in the third round; 12288: full), <8> (12296: its first K; 16384: the limit).  The first row's +-448 sits in
+    the last column, the second row's in the first.  Contiguous tensors, and row- and batch-strided views of x and of the codes in canary
+    frames; K = 16392 is refused."""
+    x, codes, scale = X.quantizable_rows(shape, X.shape_seed(*shape), edge_peaks=True)
     q, s = ops.quantize_rows_fp8(x.cuda())
     assert torch.equal(s.cpu(), scale) and torch.equal(q.cpu(), codes)
+    q, s = quantize_framed(ops, x)
+    assert torch.equal(s, scale) and torch.equal(q, codes)
+
+
+def test_quantize_rows_fp8_refuses_k_beyond_its_limit(ops):
+    K = X.QUANT_K_LIMIT + 8
+    with pytest.raises(RuntimeError, match=f"quantize_rows_fp8: K = {K} exceeds {X.QUANT_K_LIMIT}"):
+        ops.quantize_rows_fp8(torch.zeros(1, 2, K, dtype=BF, device="cuda"))
 
 
 # ----------------------------------------------------------------------------------------------------------------- fused q / k norm + RoPE

@@ -3,7 +3,9 @@
 Three things, for every shape tests/test_exact_gpu.py uses: each generator meets the exactness condition it asserts; each CPU
 restatement in fp64 rounds to the bits the construction claims (uniform attention -> c, selector -> v[pi], the integer GEMM and
 convolution chains); and assert_elementwise rejects every emulated kernel fault -- a dropped product, a dropped K-tile, a shifted
-bias chunk, another sample's gate, a missing rounding, a dropped / padded / swapped key, swapped heads, a shifted rotary pair.
+bias chunk, another sample's gate, a missing rounding, a left-out K slice, another sample's row scales, a bias added before the fp8
+scales, a dropped / padded / swapped key, swapped heads, a shifted rotary pair.  It also holds the one restatement of the K-slice plan
+(X.plan_slices) to the slice counts the GPU tests' case tables claim.
 The faults are injected into the CPU computation; no kernel code is restated here, with one exception: the dyadic attention form
 (power-of-two softmax weights) is there to see the guarded kernel's reference moves and the merges of key ranges, so its faults -- a lost
 or misplaced rescale, unshifted scores, a merge weight, an admitted masked key, doubled weights -- are injected into X.guarded_walk, the
@@ -174,10 +176,14 @@ def test_fault_intermediate_rounding_of_epilogue_2_omitted(g):
 
 
 def test_fp8_operands_and_quantisable_rows():
-    for shape in ((2, 37, 256), (1, 300, 512)):
-        x, codes, scale = X.quantizable_rows(shape, X.shape_seed(*shape))
+    for shape in X.QUANT_SHAPES:
+        x, codes, scale = X.quantizable_rows(shape, X.shape_seed(*shape), edge_peaks=True)
         assert torch.equal(x.float().abs().amax(-1) / 448.0, scale)                      # the header's scale, exactly a power of two
         assert torch.equal((x.float() / scale[..., None]).to(X.F8).view(torch.uint8), codes)
+        assert bool((x[:, 0, -1].float().abs() == 448 * scale[:, 0]).all()) and bool((x[:, 1, 0].float().abs() == 448 * scale[:, 1]).all())
+        last = x.clone()                                                                 # a row maximum that misses the last 8 columns
+        last[..., -8:] = 0
+        assert not torch.equal(last.float().abs().amax(-1) / 448.0, scale)
     B, M, N, K = X.GEMM_FP8_SHAPES[0]
     cs = X.gemm_operands(B, M, N, K, X.shape_seed(B, M, N, K))
     sa, sw = X.pow2((B, M), -3, 3, 1), X.pow2((N,), -3, 3, 2)
@@ -186,6 +192,68 @@ def test_fp8_operands_and_quantisable_rows():
     sw2 = sw.clone()
     sw2[8:16] = sw[0:8] * 2
     rejects(X.linear_bf16(cs["acc"], cs["bias"].float(), row_scale=sa, col_scale=sw2), lin, "shifted channel scale")
+
+
+# ------------------------------------------------------------------------------------------------ K-sliced launches: plans, faults
+@pytest.mark.parametrize("grid", [256, 304])
+def test_restated_slice_plan_gives_the_tabled_slice_counts(grid):
+    """X.plan_slices with the 64 MiB workspace of the GPU tests, at the workgroup counts of a 256-CU and a 304-CU device: every table
+    entry gets its slice count, and the two GEMM_FP8_SHAPES are never sliced (two and four 128-byte K-tiles, a slice keeps eight)."""
+    B, M, N = X.GEMM_KSLICE_BMN
+    ws = X.GEMM_WS_BYTES
+    for K, want in X.GEMM_KSLICE.items():
+        plan = X.plan_slices_bf16(B, M, N, K, ws, grid)
+        print(f"grid {grid} bf16 ({B}, {M}, {N}, {K}): {plan}")
+        assert plan == (want, 0, 6)
+    assert X.plan_slices_bf16(2, M, N, 1024, ws, grid) == (2, 0, 6)
+    for K, want in X.GEMM_FP8_KSLICE.items():
+        plan = X.plan_slices_fp8(B, M, N, K, ws, grid)
+        print(f"grid {grid} fp8  ({B}, {M}, {N}, {K}): {plan}")
+        assert plan == (want, 0, 6)
+    plan = X.plan_slices_fp8(*X.GEMM_FP8_BATCH2, ws, grid)
+    print(f"grid {grid} fp8  {X.GEMM_FP8_BATCH2}: {plan}")
+    assert plan == (X.GEMM_FP8_BATCH2_SLICES, 0, 6)
+    assert sorted(set(X.GEMM_FP8_KSLICE.values())) == [2, 3, 4, 6, 8] and sorted(set(X.GEMM_KSLICE.values())) == [2, 3, 4, 6, 8]
+    for shape in X.GEMM_FP8_SHAPES:
+        for bytes_ in (ws, 1 << 40):
+            assert X.plan_slices_fp8(*shape, bytes_, grid) == (1, 0, 0), shape
+    assert X.plan_slices_fp8(1, 300, 264, 12288, ws, grid) == (8, 0, 4)                   # tests/test_kernels_gpu.py's sliced shape ...
+    assert X.plan_slices_fp8(1, 300, 264, 12288, 16 * 300 * 264, grid) == (1, 0, 0)      # ... which a workspace of 16 B M N bytes leaves whole
+    assert X.plan_slices_fp8(2, 4736, 3072, 3072, ws, grid) == (1, 0, 0)                 # 456 tiles: fp8 slices whole GEMMs only
+
+
+def fp8_sliced_cases():
+    return [(*X.GEMM_KSLICE_BMN, K, sk) for K, sk in X.GEMM_FP8_KSLICE.items()] + [(*X.GEMM_FP8_BATCH2, X.GEMM_FP8_BATCH2_SLICES)]
+
+
+@pytest.mark.parametrize("B,M,N,K,slices", fp8_sliced_cases())
+def test_fp8_sliced_cases_meet_their_conditions_and_reject_the_slicing_faults(B, M, N, K, slices):
+    """The cases of test_gemm_fp8_whole_k_slicing_is_exact and its batch-2 twin: the construction's conditions (asserted by the
+    generator), and the comparison of the GPU test -- `ulps=0`, GELU columns one step -- refuses the chain with any one K slice left out,
+    with the other sample's row scales, and with the bias added before the scales, under every epilogue."""
+    cs = X.fp8_sliced_case(B, M, N, K)
+    acc, bias, sa, sw, res, gate = cs["acc"], cs["bias"].float(), cs["sa"], cs["sw"], cs["res"], cs["gate"]
+    assert set(cs["aq"].unique().tolist()) <= {0x00, 0x38, 0xB8} and 0.2 < (cs["aq"] != 0).float().mean().item() < 0.3    # 0, 1, -1 as e4m3
+    assert torch.equal(cs["lin"], (acc * sa.double()[..., None] * sw.double() + bias.double()).float().to(BF))
+    want = {epi: X.chain(epi, cs["lin"], res=res, gate=gate, gelu_from_col=256) for epi in (0, 1, 2, 3)}
+
+    def refused(lin_bad, what):
+        moved = []
+        for epi in (0, 1, 2, 3):
+            got = X.chain(epi, lin_bad, res=res, gate=gate, gelu_from_col=256)
+            rejects(got, want[epi], what, ulps=int(epi == 1))
+            moved.append(int(X.mismatches(got, want[epi], int(epi == 1)).sum()))
+        print(f"({B}, {M}, {N}, {K}) {what}: moves {moved} of {acc.numel()} elements (epilogues 0, 1, 2, 3)")
+        assert min(moved) > 0
+
+    parts = X.k_slice_products(cs, slices)
+    for s in range(slices):
+        refused(X.linear_bf16(acc - parts[s], bias, row_scale=sa, col_scale=sw), f"K slice {s} of {slices} left out")
+    scaled_bias = ((acc + bias.double()) * sa.double()[..., None] * sw.double()).float().to(BF)
+    refused(scaled_bias, "bias added before the scales")
+    if B == 2:
+        assert not torch.equal(cs["a"][0], cs["a"][1]) and int((sa[0] != sa[1]).sum()) > M // 2
+        refused(X.linear_bf16(acc, bias, row_scale=sa.flip(0), col_scale=sw), "row scales of the other sample")
 
 
 @pytest.mark.parametrize("M", X.LORA_MS)

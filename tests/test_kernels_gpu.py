@@ -13,6 +13,8 @@ pytestmark = pytest.mark.gpu
 from oracle import flux_oracle as fo
 from oracle import pipeline_oracle as po
 from oracle import sched_oracle as so
+from tests.helpers import exact_inputs as X
+from tests.helpers import framing
 
 BF = torch.bfloat16
 
@@ -247,29 +249,42 @@ def test_gemm_persistent_rejects_odd_k_tiles(ops):
 F8 = torch.float8_e4m3fn
 
 
-@pytest.mark.parametrize("shape", [(1, 37, 256), (2, 300, 3072), (3, 64, 15360)])
+@pytest.mark.parametrize("shape", [(1, 37, 256), (2, 300, 3072), (3, 64, 15360), (2, 5, 4104), (1, 3, 12288), (1, 3, 12296), (1, 2, 16384)])
 def test_quantize_rows_fp8_matches_torch(ops, shape):
     """scale = max|row| / 448 and bytes = torch's round-to-nearest-even e4m3 cast of the exactly rounded quotient x / scale,
     bit for bit (bf16 data with a scale of few mantissa bits sits on e4m3 rounding ties all the time, so the kernel divides
-    rather than multiplying by a reciprocal)."""
+    rather than multiplying by a reciprocal).  The shapes reach all three instantiations -- quant_rows_fp8_kernel<2> (K <= 4096), <6>
+    (4104, its first K with one lane in the third round; 3072 * 4 = 12288, full) and <8> (12296, its first K; 15360; 16384, the limit) --
+    with contiguous tensors and with row- and batch-strided views of x and of the codes inside canary frames."""
     B, R, K = shape
     x = (rnd(shape, 31) * (rnd((B, R, 1), 32).abs() * 3 + 0.01)).to(BF)
     x[0, 0] = 0                                            # all-zero row -> scale 1, zeros
-    q, sc = ops.quantize_rows_fp8(x.cuda())
     s_ref = x.float().abs().amax(-1) / 448.0
     s_ref = torch.where(s_ref > 0, s_ref, torch.ones_like(s_ref))
-    assert torch.equal(sc.cpu(), s_ref)
     ref = (x.float() / s_ref[..., None]).clamp(-448, 448).to(F8).float()
-    got = q.cpu().view(F8).float()
-    assert torch.isfinite(got).all()
-    assert torch.equal(got, ref)
-    assert got[0, 0].abs().max().item() == 0 and sc[0, 0].item() == 1.0
+    xbuf, xv = framing.framed(B, R, K)
+    xv.copy_(x)
+    qbuf, qv = framing.framed(B, R, K, dtype=torch.uint8)
+    sbuf, sv = framing.flat_framed((B, R), dtype=torch.float32)
+    for q, sc in (ops.quantize_rows_fp8(x.cuda()), ops.quantize_rows_fp8(xv, out=qv, scale=sv)):
+        assert torch.equal(sc.cpu(), s_ref)
+        got = q.cpu().view(F8).float()
+        assert torch.isfinite(got).all()
+        assert torch.equal(got, ref)
+        assert got[0, 0].abs().max().item() == 0 and sc[0, 0].item() == 1.0
+    framing.check_frame(qbuf, qv, "quantize_rows_fp8 codes")
+    framing.check_frame(sbuf, sv, "quantize_rows_fp8 scales")
+    framing.check_frame(xbuf, xv, "quantize_rows_fp8 input")
+    assert torch.equal(xv.cpu(), x)
 
 
 @pytest.mark.parametrize("B,M,N,K", [(1, 512, 512, 256), (2, 1000, 3136, 512), (1, 300, 264, 12288), (2, 4736, 3072, 3072)])
 def test_gemm_fp8_matches_dequantised_matmul(ops, B, M, N, K):
     """tfx_gemm_fp8 against (q_a . q_w^T) * s_a * s_w + bias evaluated in fp32 on the SAME e4m3 operands, all epilogues;
-    tolerance = the bf16 output rounding (max-norm 1e-2, MAE 2e-3 relative, as for the bf16 GEMM)."""
+    tolerance = the bf16 output rounding (max-norm 1e-2, MAE 2e-3 relative, as for the bf16 GEMM).  Every case runs without and with
+    the engine's 64 MiB workspace; with it (1, 300, 264, 12288) -- 4 tiles of 96 K-tiles -- runs as 8 K slices, the other three shapes
+    are never sliced (too few K-tiles, or at least as many tiles as workgroups).  Asserted from the restated plan; the workspace-level
+    proof is tests/test_exact_gpu.py::test_gemm_fp8_whole_k_slicing_is_exact's."""
     a = (rnd((B, M, K), 41) * (rnd((B, M, 1), 42).abs() + 0.1)).to(BF).cuda()
     w = rnd((N, K), 43, 0.05).to(BF).cuda()
     bias, gate, res = rnd((N,), 44).to(BF).cuda(), rnd((B, N), 45).to(BF).cuda(), rnd((B, M, N), 46).to(BF).cuda()
@@ -281,7 +296,10 @@ def test_gemm_fp8_matches_dequantised_matmul(ops, B, M, N, K):
     cases = [(ops.EPI_BIAS, {}, lin), (ops.EPI_BIAS_GELU, dict(gelu_from_col=gf), gelu_ref),
              (ops.EPI_BIAS_GATE_RES, dict(gate=gate, res=res), res.float() + (gate.float()[:, None] * lin.to(BF).float()).to(BF).float()),
              (ops.EPI_BIAS_RES, dict(res=res), res.float() + lin.to(BF).float())]
-    ws = torch.empty(4 * B * M * N, dtype=torch.float32, device="cuda")   # few-tile shapes then also run split-K
+    ws = torch.empty(X.GEMM_WS_BYTES, dtype=torch.uint8, device="cuda")
+    grid = torch.cuda.get_device_properties(0).multi_processor_count & ~7
+    plan = X.plan_slices_fp8(B, M, N, K, ws.numel(), grid)
+    assert plan == ((8, 0, 4) if (B, M, N, K) == (1, 300, 264, 12288) else (1, 0, 0)), plan
     for epi, kw, ref in cases:
         close(ops.gemm_fp8(aq, sa, wq, sw, bias, epilogue=epi, **kw), ref.to(BF))
         close(ops.gemm_fp8(aq, sa, wq, sw, bias, epilogue=epi, workspace=ws, **kw), ref.to(BF))

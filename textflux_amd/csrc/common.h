@@ -55,12 +55,17 @@ __device__ __forceinline__ u32x4 pack8(const float* f) {
 // nn.GELU(approximate="tanh")):  0.5 x (1 + tanh(u)),  u = sqrt(2/pi) (x + 0.044715 x^3).
 // Evaluated as x * sigmoid(2u) = x / (1 + 2^(-2u log2 e)) with the hardware v_exp_f32 / v_rcp_f32 (1 ulp each, far
 // below the bf16 output rounding); ocml tanhf costs ~4x more VALU in the GEMM epilogue.
+// Both transcendental ops flush subnormal results and exp2 overflows at 2^128, so the plain form returned -0 for every x below about
+// -10.0 (z >= 126), where the true value is still a bf16 number (x = -10.25: -3.7e-40; x = -10.06: -2.8e-38, a normal one).  The
+// quotient is therefore taken at a scale of 2^32: e' = 2^(z - 32), r = 1 / (e' + 2^-32) = 2^32 / (1 + e) <= 2^32, result x * (r * 2^-32).
+// e' and r stay normal up to z = 158, beyond which the result is below half the smallest fp32 subnormal for every |x| < 2^8; the last two
+// products are ordinary multiplies, which keep subnormals.  One VALU op more than the plain form (the -32 rides on a multiply-add).
 __device__ __forceinline__ float gelu_tanh(float x) {
   // -2 u log2(e) = x * (c0 + c1 x^2): 3 multiply-adds in front of the two transcendental ops (each costs two VALU slots, tools/ubench/valu_rate)
   const float c0 = -2.3022081981443252f, c1 = -0.10294323958002349f;
-  const float z = x * __builtin_fmaf(x * x, c1, c0);
-  const float e = __builtin_amdgcn_exp2f(z);  // exp(-2u)
-  return x * __builtin_amdgcn_rcpf(1.0f + e);
+  const float z = __builtin_fmaf(x, __builtin_fmaf(x * x, c1, c0), -32.0f);
+  const float e = __builtin_amdgcn_exp2f(z);  // exp(-2u) * 2^-32
+  return x * (__builtin_amdgcn_rcpf(e + 0x1p-32f) * 0x1p-32f);
 }
 __device__ __forceinline__ float silu(float x) { return x / (1.0f + __expf(-x)); }
 
