@@ -202,6 +202,11 @@ class AutoencoderKL:
             self._scores = (torch.empty(B, rows, Np, dtype=torch.float32, device=q.device),
                             torch.zeros(B, rows, Np, dtype=torch.bfloat16, device=q.device))
         s, pw = self._scores
+        # tfx_row_softmax writes the N key columns only: after an image with more keys at the same Np (tiles of a tiled run, a smaller
+        # image after a larger one) the padded columns would still hold that image's weights, and only the zeros of v^T kept them out
+        if Np != N and getattr(self, "_scores_keys", N) != N:
+            pw[:, :, N:].zero_()
+        self._scores_keys = N
         # the P v product of one chunk has B x rows / 256 x C / 256 tiles for 256 CUs and K = Np: where that is fewer than the CUs it runs
         # K-sliced through the GEMM's split-K scratch (fp32 partials, fixed order: deterministic for a given image and batch size)
         if getattr(self, "_pv_ws", None) is None or self._pv_ws.device != q.device:
