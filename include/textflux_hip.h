@@ -689,6 +689,43 @@ int tfx_highpass_hist_step_u8(const void* img, const void* sel, int32_t lo, int3
  *      the window that contains it, the window's border included.  out may be img (no other aliasing). */
 int tfx_grain_shaped_u8(const void* img, const void* alpha, const int32_t* gain, const int32_t* shape, const int32_t* origin, uint32_t seed,
                         void* out, int32_t B, int32_t H, int32_t W, int32_t C, tfx_stream stream);
+/* ---- keyed paste (DESIGN.md section 4 "Keyed paste"): inside the blend a pixel keeps the scene's byte unless the edit really differs
+ *      there.  The difference of the blended result to the scene is measured, thresholded with hysteresis, grown and feathered into a key,
+ *      and the result goes over the scene once more under that key.  Added without a new TFX_ABI_VERSION: three new entry points (one of
+ *      them host arithmetic), no stamped struct and no existing entry point changes.  Tensors contiguous, batch-major, u8; B, H, W >= 1,
+ *      B <= 65535, C in 1..4; integer arithmetic throughout, so the results are exact.  Every offset that can pass 2^31 is formed in 64
+ *      bits.
+ * tfx_change_metric_u8: a, b [B, H, W, C] -> out [B, H, W].  Per pixel and channel s_c = sum w[dy] w[dx] (a - b) over the 3 x 3
+ *      neighbourhood, w = [1 2 1], the neighbour indices clamped to the image (edge replicated: tfx_highpass_hist_u8's stencil), and
+ *      out = max over c of (|s_c| + 8) >> 4.  Hence, exactly: a == b on a pixel's neighbourhood gives 0, a - b == k there gives |k|, and
+ *      out lies in 0..255 (|s_c| <= 16 * 255).  out may alias neither a nor b.
+ * tfx_hysteresis_workspace_bytes: the bytes of `workspace` the call below needs (host arithmetic, no device is touched); -1 with
+ *      tfx_last_error for a geometry outside the contract.
+ * tfx_hysteresis_u8: m [B, H, W] -> out [B, H, W] in {0, 255}; 0 <= lo <= hi <= 256.  out = 255 exactly on the pixels with m >= lo that an
+ *      8-connected path of pixels with m >= lo, inside the same sample, joins to a pixel with m >= hi (a pixel with m >= hi is such a pixel
+ *      itself); every other pixel is 0.  That set is unique: the result depends on no tiling, launch order or number of rounds.  hi == 256
+ *      gives all zeros, hi == 0 all 255, lo == hi the plain threshold m >= hi.  A neighbour outside the image does not exist, so no read
+ *      leaves the buffers and the call is memory-safe whatever m holds.
+ *      One round is one launch: every workgroup spreads the marks inside its tile (and from its one-pixel halo) until nothing changes,
+ *      stores 255 on the pixels it newly reached and, if there were any, the round's number into a word of the workspace, with ordinary
+ *      stores: all writers of an address store the same value, a pixel only ever goes from 0 to 255, and no workgroup waits for another
+ *      (no atomics, no grid-wide barrier).  The entry point repeats the launch until a round leaves the word as it was, so every round but
+ *      the last has marked at least one new pixel and the call ends after at most B H W + 1 rounds; *rounds (may be NULL) receives their
+ *      number, at least 1.  THE CALL SYNCHRONISES `stream` ONCE PER ROUND, to read the word back (an image of a single tile, 64 x 16,
+ *      takes one round and is not synchronised), AND IS REFUSED, with tfx_last_error, ON A CAPTURING STREAM.  m, out and workspace are
+ *      three different buffers; workspace: 4-byte aligned, workspace_bytes at least tfx_hysteresis_workspace_bytes(B, H, W), else the call
+ *      is refused; nothing in it survives the call.
+ *      The keyed paste (textflux_amd/paste_back.py) is, with orig the scene, result today's blend of the edit and alpha its weight:
+ *          m     = tfx_change_metric_u8(result, orig)
+ *          key   = tfx_mask_feather_u8(tfx_mask_dilate_u8(tfx_hysteresis_u8(m, lo_eff, hi_eff), dilate), feather),   dilate >= 3 feather
+ *          final = tfx_overlay_u8(orig, result, key)
+ *      Hence, exactly: final == orig wherever key == 0, and everywhere outside the grown mask, where result == orig whatever the key
+ *      holds; hi_eff == 0 (lo == hi == 0 on a scene whose noise estimate is 0, or with noise == 0) gives result's bytes; every pixel with
+ *      m >= hi_eff has key == 255 and carries result's byte; and min(orig, result) <= final <= max(orig, result). */
+int tfx_change_metric_u8(const void* a, const void* b, void* out, int32_t B, int32_t H, int32_t W, int32_t C, tfx_stream stream);
+int64_t tfx_hysteresis_workspace_bytes(int32_t B, int32_t H, int32_t W);
+int tfx_hysteresis_u8(const void* m, void* out, int32_t lo, int32_t hi, void* workspace, int64_t workspace_bytes, int32_t* rounds, int32_t B,
+                      int32_t H, int32_t W, tfx_stream stream);
 /* ---- rectified per-line edits (DESIGN.md section 4 "Rectified lines"): a slanted text line is cut as an oriented rectangle, edited
  *      upright and warped back.  Added without a new TFX_ABI_VERSION: one new entry point, no stamped struct and no existing entry point
  *      changes.  Tensors contiguous, batch-major; B, H, W, out_h, out_w >= 1, B <= 65535, C in 1..4; in, out and coverage are three

@@ -63,9 +63,9 @@ def run_inference(image_input, mask_input, words_input, num_steps=50, guidance_s
     """known (not in the reference): None, or dict(keep_known=..., strength=..., change_map=...) handed to the pipeline call (known-region sampling).
     paste_back (not in the reference): None, or dict(dilate, feather) -- the result is then blended back into the input image under
     the dilated and feathered mask and returned at the INPUT's size (FluxFillPipeline.paste_back) instead of at the pipeline's size.
-    seamless (True or dict(smooth, max_shift)) and grain (True or dict(ring, max_sigma, strength, min_pixels, seed)) in it are handed to
-    that paste.
-    With per_line=True in it (batch_driver.run_items' keys: region, color_match, rectify, perspective, curve, seamless, grain) the input is the plain scene and its mask: every text
+    seamless (True or dict(smooth, max_shift)), grain (True or dict(ring, max_sigma, strength, min_pixels, seed)) and keyed (True or
+    dict(lo, hi, dilate, feather, noise, ring, min_pixels)) in it are handed to that paste.
+    With per_line=True in it (batch_driver.run_items' keys: region, color_match, rectify, perspective, curve, seamless, grain, keyed) the input is the plain scene and its mask: every text
     line is edited through its own region with a single-line glyph strip and pasted into the scene (textflux_amd/per_line.py)."""
     image = (Image.open(image_input) if isinstance(image_input, str) else image_input).convert("RGB")
     mask = (Image.open(mask_input) if isinstance(mask_input, str) else mask_input).convert("RGB")
@@ -85,7 +85,7 @@ def run_inference(image_input, mask_input, words_input, num_steps=50, guidance_s
                prompt=glyph.PROMPT_TEMPLATE2, prompt_2=prompt, **(known or {})).images[0]
     if paste_back is None:
         return out
-    pasted = pipe.paste_back(image_in, out, mask_in, **{k: v for k, v in paste_back.items() if k in ("dilate", "feather", "seamless", "grain") and v is not None})
+    pasted = pipe.paste_back(image_in, out, mask_in, **{k: v for k, v in paste_back.items() if k in ("dilate", "feather", "seamless", "grain", "keyed") and v is not None})
     return Image.fromarray(pasted[0].cpu().numpy())
 
 
@@ -149,6 +149,18 @@ def add_paste_back_args(ap):
                     "neighbouring pixels and shared between the channels as far as the scene's is (implies --paste_grain)")
     ap.add_argument("--paste_grain_max_blur", type=int, default=None, metavar="N", help="largest side tap of the grain's 3-tap blur in 1/256, "
                     "0..64, default 64 (implies --paste_grain_spectrum)")
+    ap.add_argument("--paste_keyed", action="store_true", help="keep the scene's bytes inside each pasted edit wherever the edit did not "
+                    "really change them: the blend goes over the scene once more under a key grown from the changed pixels (with --paste_back)")
+    ap.add_argument("--paste_keyed_lo", type=int, default=None, metavar="N", help="lower threshold of the change in grey levels, 0..256, "
+                    "default 10 (implies --paste_keyed)")
+    ap.add_argument("--paste_keyed_hi", type=int, default=None, metavar="N", help="upper threshold: a change is kept where it reaches this, and "
+                    "as far around as it stays above the lower one, 0..256, default 28 (implies --paste_keyed)")
+    ap.add_argument("--paste_keyed_dilate", type=int, default=None, metavar="N", help="grow the changed pixels by N, at least 3 times the "
+                    "feather, default 6 (implies --paste_keyed)")
+    ap.add_argument("--paste_keyed_feather", type=int, default=None, metavar="N", help="soften the key's edge over N pixels, default 2 "
+                    "(implies --paste_keyed)")
+    ap.add_argument("--paste_keyed_noise", type=float, default=None, metavar="F", help="keep the lower threshold F standard deviations of "
+                    "the scene's noise above zero, 0..64, default 3 (implies --paste_keyed)")
 
 
 RECTIFY_FLAGS = ("paste_rectify", "paste_rectify_min_angle", "paste_rectify_max_angle")
@@ -231,11 +243,26 @@ def grain_from_args(a):
     return values or True
 
 
+KEYED_FLAGS = ("paste_keyed", "paste_keyed_lo", "paste_keyed_hi", "paste_keyed_dilate", "paste_keyed_feather", "paste_keyed_noise")
+
+
+def keyed_from_args(a):
+    """None, or the `keyed` value of the paste_back dict (True, or a dict of the values that were given).  The flags are refused without
+    --paste_back."""
+    given = [f for f in KEYED_FLAGS if getattr(a, f, None) is not None and getattr(a, f) is not False]       # a threshold or a noise of 0 is given
+    if not given:
+        return None
+    if not a.paste_back:
+        raise SystemExit(f"--{given[0]} needs --paste_back")
+    values = {k: getattr(a, "paste_keyed_" + k) for k in ("lo", "hi", "dilate", "feather", "noise") if getattr(a, "paste_keyed_" + k, None) is not None}
+    return values or True
+
+
 def paste_back_from_args(a):
-    """None, or the paste_back dict of batch_driver.run_items / process_normal_mode.  The per-line, colour, seamless and grain keys appear
-    only when their flags were given."""
+    """None, or the paste_back dict of batch_driver.run_items / process_normal_mode.  The per-line, colour, seamless, grain and keyed keys
+    appear only when their flags were given."""
     rectify, perspective, curve, seamless = rectify_from_args(a), perspective_from_args(a), curve_from_args(a), seamless_from_args(a)
-    grain = grain_from_args(a)
+    grain, keyed = grain_from_args(a), keyed_from_args(a)
     if not a.paste_back:
         for flag in ("paste_region", "paste_per_line", "paste_color_match", "paste_color_ring"):
             if getattr(a, flag, None) not in (None, False):
@@ -258,6 +285,8 @@ def paste_back_from_args(a):
         pb["seamless"] = seamless
     if grain is not None:
         pb["grain"] = grain
+    if keyed is not None:
+        pb["keyed"] = keyed
     return pb
 
 

@@ -137,6 +137,18 @@ def build_parser(lora: bool = False):
                     "neighbouring pixels and shared between the channels as far as the scene's is (implies --paste_grain)")
     ap.add_argument("--paste_grain_max_blur", type=int, default=None, metavar="N", help="largest side tap of the grain's 3-tap blur in 1/256, "
                     "0..64, default 64 (implies --paste_grain_spectrum)")
+    ap.add_argument("--paste_keyed", action="store_true", help="keep the scene's bytes inside each pasted edit wherever the edit did not "
+                    "really change them: the blend goes over the scene once more under a key grown from the changed pixels (with --paste_back)")
+    ap.add_argument("--paste_keyed_lo", type=int, default=None, metavar="N", help="lower threshold of the change in grey levels, 0..256, "
+                    "default 10 (implies --paste_keyed)")
+    ap.add_argument("--paste_keyed_hi", type=int, default=None, metavar="N", help="upper threshold: a change is kept where it reaches this, and "
+                    "as far around as it stays above the lower one, 0..256, default 28 (implies --paste_keyed)")
+    ap.add_argument("--paste_keyed_dilate", type=int, default=None, metavar="N", help="grow the changed pixels by N, at least 3 times the "
+                    "feather, default 6 (implies --paste_keyed)")
+    ap.add_argument("--paste_keyed_feather", type=int, default=None, metavar="N", help="soften the key's edge over N pixels, default 2 "
+                    "(implies --paste_keyed)")
+    ap.add_argument("--paste_keyed_noise", type=float, default=None, metavar="F", help="keep the lower threshold F standard deviations of "
+                    "the scene's noise above zero, 0..64, default 3 (implies --paste_keyed)")
     ap.add_argument("--items", type=str, default=None, help="JSON list of {image, mask, text} instead of --json_path")
     ap.add_argument("--out", type=str, default=None, help="output folder of --items mode")
     ap.add_argument("--num_inference_steps", type=int, default=None, help=argparse.SUPPRESS)
@@ -267,6 +279,13 @@ def main(argv=None, lora: bool = False, script: str = __file__):
         elif a.paste_grain_spectrum:
             values["spectrum"] = True
         paste_back["grain"] = values or True
+    keyed_given = [f for f in ("paste_keyed", "paste_keyed_lo", "paste_keyed_hi", "paste_keyed_dilate", "paste_keyed_feather", "paste_keyed_noise")
+                   if getattr(a, f) is not None and getattr(a, f) is not False]             # a threshold or a noise of 0 is given
+    if keyed_given:
+        if not a.paste_back:
+            raise SystemExit(f"--{keyed_given[0]} needs --paste_back")
+        values = {k: getattr(a, "paste_keyed_" + k) for k in ("lo", "hi", "dilate", "feather", "noise") if getattr(a, "paste_keyed_" + k) is not None}
+        paste_back["keyed"] = values or True
     legacy = a.items is not None
     weights = a.lora_weights_path if lora else a.weights_path
     if not legacy and not (a.json_path and a.original_images_dir and weights):

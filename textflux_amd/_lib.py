@@ -212,6 +212,9 @@ SIGNATURES = {
     "tfx_highpass_hist_step_u8": (c_int, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p]),
     "tfx_grain_shaped_u8": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, C.c_uint32, c_void_p, c_int32, c_int32, c_int32, c_int32,
                                     c_void_p]),
+    "tfx_change_metric_u8": (c_int, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p]),
+    "tfx_hysteresis_workspace_bytes": (c_int64, [c_int32, c_int32, c_int32]),
+    "tfx_hysteresis_u8": (c_int, [c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_int64, c_void_p, c_int32, c_int32, c_int32, c_void_p]),
     "tfx_warp_affine_u8": (c_int, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p]),
     "tfx_warp_perspective_u8": (c_int, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p]),
     "tfx_warp_grid_u8": (c_int, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p, c_int32, c_void_p,

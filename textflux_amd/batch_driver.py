@@ -125,10 +125,11 @@ def _paste_back_cfg(paste_back: Dict[str, Any]) -> Dict[str, Any]:
     perspective: perspective.perspective_cfg's dict(max_fit, max_taper, min_aspect, max_angle) and curve: curve.curve_cfg's
     dict(min_bend, max_squeeze, max_turn, min_aspect, min_fill, max_angle) (all three need per_line), seamless: paste_back.
     seamless_cfg's dict(smooth, max_shift) and grain: paste_back.grain_cfg's dict(ring, max_sigma, strength, min_pixels, seed) with, only
-    when the caller gave it, spectrum: dict(max_blur, luma)."""
+    when the caller gave it, spectrum: dict(max_blur, luma), and keyed: paste_back.keyed_cfg's dict(lo, hi, dilate, feather, noise, ring,
+    min_pixels)."""
     from . import paste_back as pb
     unknown = set(paste_back) - {"dilate", "feather", "region", "per_line", "color_match", "rectify", "perspective", "curve", "seamless",
-                                  "grain"}
+                                  "grain", "keyed"}
     region = paste_back.get("region")
     if region is not None:
         unknown |= {f"region.{k}" for k in set(region) - {"pad", "min_side", "max_side"}}
@@ -147,7 +148,8 @@ def _paste_back_cfg(paste_back: Dict[str, Any]) -> Dict[str, Any]:
         cfg["per_line"] = True
         if cfg["region"] is None:
             cfg["region"] = {}
-    options = [("color_match", pb.color_match_cfg, None), ("seamless", pb.seamless_cfg, None), ("grain", pb.grain_cfg, None)]
+    options = [("color_match", pb.color_match_cfg, None), ("seamless", pb.seamless_cfg, None), ("grain", pb.grain_cfg, None),
+               ("keyed", pb.keyed_cfg, None)]
     options += [(path.key, lambda v, path=path: _module(path).cfg(v), None if per_line else f"only single-line edits are {path.verb}")
                 for path in reversed(LINE_PATHS)]
     for key, make_cfg, needs_per_line in options:
@@ -346,6 +348,8 @@ def _paste_into_original(pipe, w: Work, cropped, cfg: Dict[str, Any]):
         kw["seamless"] = cfg["seamless"]
     if cfg.get("grain"):                             # the grain is anchored at scene positions: the region's own place in the scene
         kw.update(grain=cfg["grain"], origin=(reg.x0, reg.y0))
+    if cfg.get("keyed"):
+        kw["keyed"] = cfg["keyed"]
     pasted = pipe.paste_back(oc, cropped, om, dilate=cfg["dilate"], feather=cfg["feather"], **kw)
     pasted = pasted.cpu().numpy() if isinstance(pasted, torch.Tensor) else np.asarray(pasted)
     out = w.orig_scene.copy()
@@ -485,6 +489,12 @@ def run_items(items: Sequence[Dict[str, Any]], pipe, out_dir: Optional[str], bat
     With grain=dict(spectrum=True | dict(max_blur, luma), ...) (DESIGN.md section 4 "Grain spectrum") the grain is blurred over
     neighbouring pixels (a 3-tap kernel whose side tap is at most max_blur / 256, default 64) and, with luma (default True), shared
     between the channels, as far as the scene's own noise on the ring is.
+    keyed=True | dict(lo, hi, dilate, feather, noise, ring, min_pixels) (DESIGN.md section 4 "Keyed paste"; with or without the keys
+    above): behind the blend of every paste and in front of its grain, the blend's difference to the scene is measured (a 3 x 3 weighted
+    sum per channel), thresholded with hysteresis at lo / hi grey levels (defaults 10 and 28; the lower one stays `noise`, default 3,
+    standard deviations of the scene's noise on the ring above zero), grown by `dilate` and feathered by `feather` (6 and 2) into a key,
+    and the blend goes over the scene once more under that key: a pixel inside the mask that the edit did not change keeps the scene's
+    byte.  The bytes outside the grown mask stay the original's.
     keep_known=True | dict(mode, grow) and strength (DESIGN.md section 4 "Known-region sampling"): handed to every pipeline call as
     they are -- the canvas outside the mask is then kept in the latents at every step, and the loop runs int(steps * strength) steps
     from the noised canvas.  Paste-back runs after decode, unchanged.  Not with mixed_pad > 0.

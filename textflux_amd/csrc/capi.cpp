@@ -478,6 +478,16 @@ int tfx_grain_shaped_u8(const void* img, const void* alpha, const int32_t* gain,
   if (!img || !alpha || !gain || !shape || !out) return fail("tfx_grain_shaped_u8: null pointer");
   return grain_shaped_u8(img, alpha, gain, shape, origin, seed, out, B, H, W, C, S(stream));
 }
+int tfx_change_metric_u8(const void* a, const void* b, void* out, int32_t B, int32_t H, int32_t W, int32_t C, tfx_stream stream) {
+  if (!a || !b || !out) return fail("tfx_change_metric_u8: null pointer");
+  return change_metric_u8(a, b, out, B, H, W, C, S(stream));
+}
+int64_t tfx_hysteresis_workspace_bytes(int32_t B, int32_t H, int32_t W) { return hysteresis_workspace_bytes(B, H, W); }
+int tfx_hysteresis_u8(const void* m, void* out, int32_t lo, int32_t hi, void* workspace, int64_t workspace_bytes, int32_t* rounds, int32_t B,
+                      int32_t H, int32_t W, tfx_stream stream) {
+  if (!m || !out || !workspace) return fail("tfx_hysteresis_u8: null pointer");
+  return hysteresis_u8(m, out, lo, hi, workspace, workspace_bytes, rounds, B, H, W, S(stream));
+}
 int tfx_warp_affine_u8(const void* in, void* out, void* coverage, int32_t B, int32_t H, int32_t W, int32_t C, int32_t out_h, int32_t out_w,
                        const int64_t* m, const int16_t* taps, tfx_stream stream) {
   if (!in || !out || !m || !taps) return fail("tfx_warp_affine_u8: null pointer");

@@ -1360,6 +1360,159 @@ int grain_shaped_u8(const void* img, const void* alpha, const int* gain, const i
   return check_launch("grain_shaped_u8");
 }
 
+// ---- keyed paste (DESIGN.md section 4 "Keyed paste"): how much two images differ around a pixel, and the hysteresis threshold of that
+// metric.  Integer arithmetic only, so both are exact whatever the partition.
+
+// out[p] = max over the channels of (|s_c| + 8) >> 4, s_c = sum w (a - b) with w = [1 2 1] x [1 2 1] over the 3 x 3 neighbourhood, its
+// indices clamped to the image: highpass_hist_kernel's stencil at step 1, on the difference.  |s_c| <= 16 * 255, so out <= 255.  One
+// thread per pixel and step of the grid.
+template <int C>
+__global__ __launch_bounds__(256) void change_metric_kernel(const uint8_t* __restrict__ a, const uint8_t* __restrict__ b,
+                                                            uint8_t* __restrict__ out, int H, int W) {
+  const int s = blockIdx.y;
+  const int64_t hw = (int64_t)H * W;
+  a += (int64_t)s * hw * C; b += (int64_t)s * hw * C; out += (int64_t)s * hw;
+  for (int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x; p < hw; p += (int64_t)gridDim.x * 256) {
+    const int y = (int)(p / W), x = (int)(p - (int64_t)y * W);
+    const int64_t r0 = (int64_t)(y > 0 ? y - 1 : 0) * W, r1 = (int64_t)y * W, r2 = (int64_t)(y < H - 1 ? y + 1 : H - 1) * W;
+    const int x0 = x > 0 ? x - 1 : 0, x2 = x < W - 1 ? x + 1 : W - 1;
+    int best = 0;
+#pragma unroll
+    for (int c = 0; c < C; ++c) {
+      auto at = [&](int64_t row, int col) { const int64_t i = (row + col) * C + c; return (int)a[i] - (int)b[i]; };
+      int v = at(r0, x0) + 2 * at(r0, x) + at(r0, x2) + 2 * at(r1, x0) + 4 * at(r1, x) + 2 * at(r1, x2) + at(r2, x0) + 2 * at(r2, x) + at(r2, x2);
+      v = v < 0 ? -v : v;
+      best = v > best ? v : best;
+    }
+    out[p] = (uint8_t)((best + 8) >> 4);
+  }
+}
+
+int change_metric_u8(const void* a, const void* b, void* out, int B, int H, int W, int C, hipStream_t st) {
+  if (grain_geometry("change_metric_u8", B, H, W, C)) return 1;
+  if (out == a || out == b) return fail("change_metric_u8: out may alias neither a nor b");
+  const int64_t want = ((int64_t)H * W + 255) / 256;
+  const dim3 grid((unsigned)(want > 4096 ? 4096 : want), B);            // grid-stride beyond, as grain_u8
+  const uint8_t *pa = (const uint8_t*)a, *pb = (const uint8_t*)b;
+  switch (C) {
+    case 1: change_metric_kernel<1><<<grid, 256, 0, st>>>(pa, pb, (uint8_t*)out, H, W); break;
+    case 2: change_metric_kernel<2><<<grid, 256, 0, st>>>(pa, pb, (uint8_t*)out, H, W); break;
+    case 3: change_metric_kernel<3><<<grid, 256, 0, st>>>(pa, pb, (uint8_t*)out, H, W); break;
+    default: change_metric_kernel<4><<<grid, 256, 0, st>>>(pa, pb, (uint8_t*)out, H, W); break;
+  }
+  return check_launch("change_metric_u8");
+}
+
+// Hysteresis: a tile of 64 x 16 pixels per workgroup of 256 threads, every thread a run of four pixels of one row, so that a row of the
+// tile is one 64-byte read.  The tile and its one-pixel halo take 18 rows of 68 bytes of LDS, 1224 bytes: the LDS never bounds the
+// occupancy, and a byte per pixel lets neighbouring threads update their pixels without touching each other's.
+constexpr int kHystTW = 64, kHystTH = 16, kHystPitch = 68;
+enum : uint8_t { kHystOff = 0, kHystWeak = 1, kHystOn = 2 };          // below lo or outside the image; >= lo and not reached; reached
+
+// One round.  kFirst: the state comes from m alone (on: m >= hi, weak: m >= lo) and every pixel of the tile is written, 255 or 0.  Later
+// rounds: on where out == 255, weak where m >= lo; a halo pixel is on or off, since nothing spreads THROUGH another tile's pixel here;
+// only the newly reached pixels are written.  Inside the tile the on state spreads over the eight neighbours until a sweep changes
+// nothing.  Every store into out and into *changed writes a value that every other writer of that address writes in this launch (255;
+// `round`), and a pixel only ever goes from 0 to 255, so a halo read that races with its owner's store sees either a state that was or
+// one that will be true: the fixed point, where a round marks nothing, is the one set whatever the order.  A neighbour outside the image
+// does not exist: no read leaves the buffers, whatever m holds.
+template <bool kFirst>
+__global__ __launch_bounds__(256) void hysteresis_kernel(const uint8_t* __restrict__ m, uint8_t* out, int lo, int hi, uint32_t* changed,
+                                                         uint32_t round, int H, int W, int tiles_x) {
+  __shared__ uint8_t st[(kHystTH + 2) * kHystPitch];
+  const int64_t base = (int64_t)blockIdx.y * H * W;
+  const int ty0 = (int)(blockIdx.x / (unsigned)tiles_x) * kHystTH, tx0 = (int)(blockIdx.x % (unsigned)tiles_x) * kHystTW;
+  for (int k = threadIdx.x; k < (kHystTH + 2) * (kHystTW + 2); k += 256) {
+    const int r = k / (kHystTW + 2), c = k - r * (kHystTW + 2);
+    const int gy = ty0 - 1 + r, gx = tx0 - 1 + c;
+    uint8_t v = kHystOff;
+    if (gy >= 0 && gy < H && gx >= 0 && gx < W) {
+      const int64_t i = base + (int64_t)gy * W + gx;
+      const bool inner = r >= 1 && r <= kHystTH && c >= 1 && c <= kHystTW;
+      const int mv = m[i];
+      if (kFirst) v = mv >= hi ? kHystOn : (inner && mv >= lo) ? kHystWeak : kHystOff;
+      else v = out[i] == 255 ? kHystOn : (inner && mv >= lo) ? kHystWeak : kHystOff;
+    }
+    st[r * kHystPitch + c] = v;
+  }
+  __syncthreads();
+  const int row = threadIdx.x / (kHystTW / 4), col = (threadIdx.x % (kHystTW / 4)) * 4;      // the thread's four pixels: (row, col .. col + 3)
+  uint8_t* mine = &st[(row + 1) * kHystPitch + col + 1];
+  uint8_t before[4];
+#pragma unroll
+  for (int k = 0; k < 4; ++k) before[k] = mine[k];
+  auto reached = [&](const uint8_t* p) {
+    return p[-kHystPitch - 1] == kHystOn || p[-kHystPitch] == kHystOn || p[-kHystPitch + 1] == kHystOn || p[-1] == kHystOn || p[1] == kHystOn ||
+           p[kHystPitch - 1] == kHystOn || p[kHystPitch] == kHystOn || p[kHystPitch + 1] == kHystOn;
+  };
+  for (;;) {                                         // ends: a sweep that changes something turns a weak pixel on, of which there are 1024
+    int moved = 0;
+#pragma unroll
+    for (int k = 0; k < 4; ++k)                      // left to right, then right to left: a run is crossed in one sweep either way
+      if (mine[k] == kHystWeak && reached(mine + k)) { mine[k] = kHystOn; moved = 1; }
+#pragma unroll
+    for (int k = 3; k >= 0; --k)
+      if (mine[k] == kHystWeak && reached(mine + k)) { mine[k] = kHystOn; moved = 1; }
+    if (!__syncthreads_or(moved)) break;             // the last sweep changed nothing, so every thread read the final state
+  }
+  const int gy = ty0 + row;
+  bool marked = false;
+  if (gy < H) {
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const int gx = tx0 + col + k;
+      if (gx >= W) break;
+      const bool on = mine[k] == kHystOn;
+      if (kFirst) out[base + (int64_t)gy * W + gx] = on ? 255 : 0;
+      else if (on && before[k] != kHystOn) out[base + (int64_t)gy * W + gx] = 255;
+      marked |= on && (kFirst || before[k] != kHystOn);
+    }
+  }
+  if (marked) *changed = round;                      // an ordinary store: every writer of this launch stores the same value
+}
+
+int64_t hysteresis_workspace_bytes(int B, int H, int W) {
+  if (B < 1 || H < 1 || W < 1 || B > 65535) { fail("hysteresis_workspace_bytes: B in 1..65535, H and W at least 1"); return -1; }
+  const int64_t tiles = (int64_t)((W + kHystTW - 1) / kHystTW) * ((H + kHystTH - 1) / kHystTH);
+  if (tiles > 0x7fffffffll) { fail("hysteresis_workspace_bytes: more than 2^31 - 1 tiles per sample"); return -1; }
+  return 64;                                         // the word that a round raises
+}
+
+int hysteresis_u8(const void* m, void* out, int lo, int hi, void* workspace, int64_t workspace_bytes, int* rounds, int B, int H, int W,
+                  hipStream_t st) {
+  const int64_t need = hysteresis_workspace_bytes(B, H, W);
+  if (need < 0) return 1;
+  if (lo < 0 || lo > hi || hi > 256) return fail("hysteresis_u8: 0 <= lo <= hi <= 256 required, got %d, %d", lo, hi);
+  if (workspace_bytes < need) return fail("hysteresis_u8: workspace of %lld bytes, %lld needed", (long long)workspace_bytes, (long long)need);
+  if ((uintptr_t)workspace & 3) return fail("hysteresis_u8: workspace must be 4-byte aligned");
+  if (out == m || workspace == m || workspace == out) return fail("hysteresis_u8: m, out and workspace must be different buffers");
+  hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+  if (hipStreamIsCapturing(st, &cs) != hipSuccess) { (void)hipGetLastError(); cs = hipStreamCaptureStatusNone; }
+  if (cs != hipStreamCaptureStatusNone)
+    return fail("hysteresis_u8: the stream is capturing; the call reads a word back after every round and cannot be captured");
+  const int tiles_x = (W + kHystTW - 1) / kHystTW;
+  const dim3 grid((unsigned)((int64_t)tiles_x * ((H + kHystTH - 1) / kHystTH)), B);      // hysteresis_workspace_bytes bounded it
+  const uint8_t* pm = (const uint8_t*)m;
+  uint32_t* word = (uint32_t*)workspace;
+  if (hipMemsetAsync(word, 0, 4, st) != hipSuccess) return fail("hysteresis_u8: clearing the workspace failed");
+  hysteresis_kernel<true><<<grid, 256, 0, st>>>(pm, (uint8_t*)out, lo, hi, word, 1u, H, W, tiles_x);
+  if (check_launch("hysteresis_u8")) return 1;
+  int done = 1;
+  if (grid.x > 1) {                                  // one tile per sample has no neighbour to hear from: its first round is its last
+    for (;;) {
+      uint32_t raised = 0;
+      if (hipMemcpyAsync(&raised, word, 4, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
+        return fail("hysteresis_u8: reading the round's word back failed");
+      if (raised != (uint32_t)done) break;           // round `done` marked nothing
+      ++done;
+      hysteresis_kernel<false><<<grid, 256, 0, st>>>(pm, (uint8_t*)out, lo, hi, word, (uint32_t)done, H, W, tiles_x);
+      if (check_launch("hysteresis_u8")) return 1;
+    }
+  }
+  if (rounds) *rounds = done;
+  return 0;
+}
+
 // The one launcher of the line warps: `name` is the declared function's, `arg` what its messages call the map's pointer.
 template <typename Map>
 static int warp_u8(const char* name, const char* arg, const void* in, void* out, void* coverage, int B, int H, int W, int C, int out_h,

@@ -244,6 +244,13 @@ int grain_u8(const void* img, const void* alpha, const int* gain, const int* ori
 int highpass_hist_step_u8(const void* img, const void* sel, int lo, int hi, int step, void* out, int B, int H, int W, int C, hipStream_t st);
 int grain_shaped_u8(const void* img, const void* alpha, const int* gain, const int* shape, const int* origin, uint32_t seed, void* out, int B,
                     int H, int W, int C, hipStream_t st);
+// keyed paste: out u8 [B, H, W] = max over the channels of (|[1 2 1] x [1 2 1] (a - b)| + 8) >> 4, and its hysteresis threshold: 255 where
+// m >= lo and an 8-connected path of such pixels leads to one with m >= hi, else 0; the launch is repeated until a round marks nothing
+// (one stream synchronisation per round; refused on a capturing stream); workspace: hysteresis_workspace_bytes (-1 on bad geometry)
+int change_metric_u8(const void* a, const void* b, void* out, int B, int H, int W, int C, hipStream_t st);
+int64_t hysteresis_workspace_bytes(int B, int H, int W);
+int hysteresis_u8(const void* m, void* out, int lo, int hi, void* workspace, int64_t workspace_bytes, int* rounds, int B, int H, int W,
+                  hipStream_t st);
 // rectified per-line edits: out [B, out_h, out_w, C] u8 = in [B, H, W, C] sampled at the Q16 affine image (m i64 [B][6], device) of every
 // destination pixel, 4 x 4 taps from the i16 [256][4] table (device), edge replicated; coverage [B, out_h, out_w] u8 or NULL
 int warp_affine_u8(const void* in, void* out, void* coverage, int B, int H, int W, int C, int out_h, int out_w, const int64_t* m,

@@ -1027,6 +1027,47 @@ def _grain_args(name, img, alpha, gain, max_gain, origin, out):
     return np.ascontiguousarray(g.astype(np.int32)), o, out
 
 
+def change_metric(a: torch.Tensor, b: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """uint8 [B, H, W]: how much two uint8 images [B, H, W, C] (C in 1..4) differ around a pixel (tfx_change_metric_u8): the largest, over
+    the channels, of (|s_c| + 8) >> 4 with s_c the [1 2 1] x [1 2 1] sum of a - b over the edge-replicated 3 x 3 neighbourhood.  0 where
+    the images agree on the neighbourhood, |k| where they differ by the constant k.  Exact: integer arithmetic.  out: None (a new tensor)
+    or a uint8 [B, H, W] tensor that is neither a nor b."""
+    _chk_dev(a, b, out)
+    for t in (a, b):
+        if t.dtype != torch.uint8 or not t.is_contiguous():
+            raise ValueError("change_metric: a and b must be contiguous uint8 tensors")
+    if a.dim() != 4 or a.numel() == 0 or not 1 <= a.shape[3] <= 4 or b.shape != a.shape:
+        raise ValueError(f"change_metric: a and b [B, H, W, C <= 4] must agree, got {tuple(a.shape)}, {tuple(b.shape)}")
+    B, H, W, Cc = a.shape
+    if out is None:
+        out = torch.empty(B, H, W, dtype=torch.uint8, device=a.device)
+    elif tuple(out.shape) != (B, H, W) or out.dtype != torch.uint8 or not out.is_contiguous():
+        raise ValueError(f"change_metric: out must be a contiguous uint8 [{B}, {H}, {W}] tensor")
+    L.check(L.lib().tfx_change_metric_u8(a.data_ptr(), b.data_ptr(), out.data_ptr(), B, H, W, Cc, _stream()), "change_metric")
+    return out
+
+
+def hysteresis(m: torch.Tensor, lo: int, hi: int, rounds: bool = False):
+    """uint8 [B, H, W] in {0, 255} (tfx_hysteresis_u8): 255 exactly on the pixels of a uint8 field m [B, H, W] with m >= lo that an
+    8-connected path of such pixels, inside the same sample, joins to a pixel with m >= hi; 0 <= lo <= hi <= 256 (hi = 256: all 0,
+    hi = 0: all 255).  The launch is repeated until a round marks nothing: the call synchronises the current stream once per round and is
+    refused while that stream is capturing.  rounds=True: (the result, the number of rounds, at least 1)."""
+    _chk_dev(m)
+    if m.dtype != torch.uint8 or m.dim() != 3 or not m.is_contiguous() or m.numel() == 0:
+        raise ValueError(f"hysteresis: m must be a contiguous, non-empty uint8 [B, H, W] tensor, got {m.dtype} {tuple(m.shape)}")
+    if int(lo) != lo or int(hi) != hi or not 0 <= int(lo) <= int(hi) <= 256:
+        raise ValueError(f"hysteresis: lo and hi must be integers with 0 <= lo <= hi <= 256, got {lo}, {hi}")
+    B, H, W = m.shape
+    need = L.lib().tfx_hysteresis_workspace_bytes(B, H, W)
+    L.check(1 if need < 0 else 0, "hysteresis")
+    out = torch.empty_like(m)
+    ws = torch.empty((need + 7) // 8, dtype=torch.int64, device=m.device)
+    n = C.c_int32(0)
+    L.check(L.lib().tfx_hysteresis_u8(m.data_ptr(), out.data_ptr(), int(lo), int(hi), ws.data_ptr(), ws.numel() * 8, C.byref(n), B, H, W,
+                                      _stream()), "hysteresis")
+    return (out, int(n.value)) if rounds else out
+
+
 _WARP_TAPS = {}
 
 

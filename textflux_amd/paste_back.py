@@ -38,6 +38,13 @@ Grain spectrum (opt-in, grain=dict(spectrum=...); DESIGN.md section 4 "Grain spe
     lam    = the share of one field common to the channels, from the channel sum's median      host: grain_shape
     gain   = sigma_add / w(s, lam), its true deviation held below max_sigma                    host: grain_shaped_gains
     out    = clamp(result + blurred, channel-mixed grain gain alpha)                           ops.grain_shaped
+
+Keyed paste (opt-in, paste(keyed=...); DESIGN.md section 4 "Keyed paste"): behind the blend and in front of the grain, a pixel inside the
+blend keeps the scene's byte unless the blend really differs there:
+
+    m     = max over the channels of (|[1 2 1] x [1 2 1] (result - orig)| + 8) >> 4            ops.change_metric
+    key   = feather(dilate(hysteresis(m, lo_eff, hi_eff), dilate), feather)                    ops.hysteresis, ops.mask_dilate / mask_feather
+    final = (orig (255 - key) + result key + 127) // 255                                       ops.overlay
 """
 from __future__ import annotations
 
@@ -215,6 +222,76 @@ def grain_cfg(grain) -> dict:
     return dict(ring=ring, max_sigma=max_sigma, strength=strength, min_pixels=min_pixels, seed=seed)
 
 
+# Keyed paste (DESIGN.md section 4 "Keyed paste"): the two thresholds of the change metric in grey levels, how far the key is grown and
+# feathered, and how many standard deviations of the scene's noise the lower threshold is kept above.  The ring and the fewest pixels a
+# noise estimate is trusted with are colour matching's.  A starting point, not a tuned value and no quality claim.
+KEYED_LO, KEYED_HI, KEYED_DILATE, KEYED_FEATHER, KEYED_NOISE = 10, 28, 6, 2, 3.0
+
+
+def keyed_cfg(keyed) -> dict:
+    """paste's keyed argument (True or a dict of lo, hi, dilate, feather, noise, ring, min_pixels) with its defaults filled in and
+    checked: 0 <= lo <= hi <= 256, dilate >= 3 feather (every pixel the hysteresis marks then has key = 255), 0 <= noise <= 64."""
+    if keyed is not True and not isinstance(keyed, dict):
+        raise ValueError("keyed: must be True or a dict")
+    kd = {} if keyed is True else dict(keyed)
+    unknown = set(kd) - {"lo", "hi", "dilate", "feather", "noise", "ring", "min_pixels"}
+    if unknown:
+        raise ValueError(f"keyed: unknown keys {sorted(unknown)}")
+    for k in ("lo", "hi", "dilate", "feather", "ring", "min_pixels"):
+        if kd.get(k) is not None and (isinstance(kd[k], bool) or not isinstance(kd[k], (int, np.integer))):
+            raise ValueError(f"keyed: {k} must be an integer")
+    lo = KEYED_LO if kd.get("lo") is None else int(kd["lo"])
+    hi = KEYED_HI if kd.get("hi") is None else int(kd["hi"])
+    dilate = KEYED_DILATE if kd.get("dilate") is None else int(kd["dilate"])
+    feather = KEYED_FEATHER if kd.get("feather") is None else int(kd["feather"])
+    noise = KEYED_NOISE if kd.get("noise") is None else float(kd["noise"])
+    ring = RING if kd.get("ring") is None else int(kd["ring"])
+    min_pixels = MIN_PIXELS if kd.get("min_pixels") is None else int(kd["min_pixels"])
+    if not 0 <= lo <= hi <= 256:
+        raise ValueError("keyed: lo and hi must satisfy 0 <= lo <= hi <= 256")
+    if not (0 <= feather and 3 * feather <= dilate <= 255):
+        raise ValueError("keyed: dilate and feather must satisfy 0 <= 3 feather <= dilate <= 255")
+    if not 0.0 <= noise <= 64.0:                     # also refuses NaN
+        raise ValueError("keyed: noise must be in [0, 64]")
+    if not 1 <= ring <= 255 or min_pixels < 1:
+        raise ValueError("keyed: ring must be in [1, 255] and min_pixels at least 1")
+    return dict(lo=lo, hi=hi, dilate=dilate, feather=feather, noise=noise, ring=ring, min_pixels=min_pixels)
+
+
+def keyed_sigma(hist, cfg=True) -> np.ndarray:
+    """hist int [B, C, 1024] (ops.highpass_hist of the scene on the ring) -> float64 [B]: the largest per-channel noise_sigma of every
+    sample under keyed_cfg(cfg); 0 where the histogram counts fewer than min_pixels pixels."""
+    cfg = keyed_cfg(cfg)
+    h = _hist(hist)
+    return np.where(h.sum(axis=2).min(axis=1) >= cfg["min_pixels"], noise_sigma(h).max(axis=1), 0.0)
+
+
+def keyed_levels(cfg=True, sigma: float = 0.0) -> Tuple[int, int]:
+    """(lo_eff, hi_eff), the hysteresis thresholds of one sample whose scene has the noise level sigma, under keyed_cfg(cfg):
+    lo_eff = max(lo, ceil(noise sigma)) and hi_eff = hi + (lo_eff - lo), both at most 256.  The difference between a clean edit and a
+    noisy scene has the scene's noise level; that noise is not keyed as change."""
+    cfg = keyed_cfg(cfg)
+    lo_eff = min(max(cfg["lo"], int(math.ceil(cfg["noise"] * float(sigma)))), 256)
+    return lo_eff, min(cfg["hi"] + (lo_eff - cfg["lo"]), 256)
+
+
+def change_key(original: torch.Tensor, result: torch.Tensor, cfg=True, sigma=None) -> torch.Tensor:
+    """uint8 [B, H, W], the key of the keyed paste: ops.change_metric(result, original), thresholded by ops.hysteresis at
+    keyed_levels(cfg, sigma[b]) per sample, grown by cfg's dilate (ops.mask_dilate) and feathered by its feather (ops.mask_feather).
+    original, result: uint8 [B, H, W, C] on the device; sigma: None (0), a number or one per sample.  Every pixel whose metric reaches
+    hi_eff has key = 255; a pixel farther than dilate + 3 feather (per axis) from every marked pixel has key = 0."""
+    cfg = keyed_cfg(cfg)
+    B = original.shape[0]
+    sg = np.broadcast_to(np.zeros(1) if sigma is None else np.asarray(sigma, np.float64), (B,))
+    levels = [keyed_levels(cfg, s) for s in sg]
+    m = ops.change_metric(result, original)
+    if len(set(levels)) == 1:
+        marked = ops.hysteresis(m, *levels[0])
+    else:                                            # the thresholds are the call's, not the sample's: one call per sample
+        marked = torch.cat([ops.hysteresis(m[b:b + 1], *levels[b]) for b in range(B)])
+    return ops.mask_feather(ops.mask_dilate(marked, cfg["dilate"]), cfg["feather"])
+
+
 def _hist(hist) -> np.ndarray:
     h = hist.cpu().numpy() if isinstance(hist, torch.Tensor) else np.asarray(hist)
     if h.ndim != 3 or h.shape[2] != ops.HIGHPASS_BINS:
@@ -378,7 +455,7 @@ def fit_luts(moments, gain: Tuple[float, float] = GAIN, max_shift: int = MAX_SHI
 
 def paste(original: torch.Tensor, edited: torch.Tensor, mask_grey: torch.Tensor, dilate: int = DILATE, feather: int = FEATHER,
           color_match=None, color_ref: Optional[torch.Tensor] = None, rect=None, origin: Tuple[int, int] = (0, 0), seamless=None,
-          grain=None) -> torch.Tensor:
+          grain=None, keyed=None) -> torch.Tensor:
     """original uint8 [B, H, W, 3], edited uint8 [B, h, w, 3], mask_grey uint8 [B, H, W], all on the device -> [B, H, W, 3]: the edit,
     resampled to (H, W) when its size differs (ops.resample_u8: Pillow's bicubic), blended over the original under alpha_mask computed at
     the ORIGINAL resolution.  Outside the mask dilated by dilate + 3 feather the result is the original byte for byte; with
@@ -408,15 +485,26 @@ def paste(original: torch.Tensor, edited: torch.Tensor, mask_grey: torch.Tensor,
     grain=dict(spectrum=True | dict(max_blur, luma), ...) (DESIGN.md section 4 "Grain spectrum"): the three histograms become
     ops.highpass_hist_step (the ring at steps 1 and 2, the result at step 1), grain_shape estimates the scene noise's blur and the share
     its channels have in common, and ops.grain_shaped adds grain of that shape at grain_shaped_gains' level.  Without the sub-key the
-    grain's calls are those above, unchanged; with max_blur=0, luma=False the bytes are."""
+    grain's calls are those above, unchanged; with max_blur=0, luma=False the bytes are.
+    keyed: None, or True / dict(lo, hi, dilate, feather, noise, ring, min_pixels) (DESIGN.md section 4 "Keyed paste"): behind the blend
+    above (plain, colour-matched and / or seamless) and in front of the grain, a pixel keeps `original`'s byte unless the blend really
+    differs there: key = change_key(original, result, keyed, sigma) and the result goes over `original` once more under it
+    (ops.overlay).  sigma, per sample, is the largest per-channel noise level of color_ref (None: `original`) on the ring just outside
+    the blend, cut to what the warp covered (ops.highpass_hist, keyed_sigma): the lower threshold stays `noise` standard deviations above
+    it (keyed_levels); noise = 0 takes no estimate.  The grain then runs on the keyed result under min(alpha, key) where it took alpha.
+    Exactly: the result is `original` wherever the key is 0 and, as before, everywhere outside the grown mask; it carries the blend's
+    byte wherever the metric reaches hi_eff; it lies between `original` and the blend; and hi_eff = 0 (lo = hi = 0 on a ring without
+    noise, or with noise = 0) gives the bytes of the call without the key.  color_ref may then be given without color_match.  Without
+    the key the calls are those above, unchanged."""
     if original.dtype != torch.uint8 or original.dim() != 4 or edited.dtype != torch.uint8 or edited.dim() != 4:
         raise ValueError("paste: original and edited must be uint8 [B, H, W, C]")
     if edited.shape[0] != original.shape[0] or edited.shape[3] != original.shape[3] or mask_grey.shape != original.shape[:3]:
         raise ValueError(f"paste: original {tuple(original.shape)}, edited {tuple(edited.shape)} and mask {tuple(mask_grey.shape)} do not agree")
-    if color_match is None and seamless is None and grain is None and color_ref is not None:
+    if color_match is None and seamless is None and grain is None and keyed is None and color_ref is not None:
         raise ValueError("paste: color_ref needs color_match")
     sm = None if seamless is None else seamless_cfg(seamless)
     gr = None if grain is None else grain_cfg(grain)
+    kd = None if keyed is None else keyed_cfg(keyed)
     original, edited = original.contiguous(), edited.contiguous()
     covered = None
     if rect is not None:
@@ -427,7 +515,7 @@ def paste(original: torch.Tensor, edited: torch.Tensor, mask_grey: torch.Tensor,
     elif edited.shape[1:3] != original.shape[1:3]:
         edited = ops.resample_u8(edited, (original.shape[1], original.shape[2]))
     alpha = alpha_mask(mask_grey.contiguous(), dilate, feather)
-    if color_match is None and sm is None and gr is None:
+    if color_match is None and sm is None and gr is None and kd is None:
         return ops.overlay(original, edited, alpha)
     cm = None if color_match is None else color_match_cfg(color_match)
     ref = original if color_ref is None else color_ref.contiguous()
@@ -451,20 +539,26 @@ def paste(original: torch.Tensor, edited: torch.Tensor, mask_grey: torch.Tensor,
             result = ops.seamless_overlay(original, ref, edited, alpha, covered=covered, lut=luts, smooth=sm["smooth"], max_shift=sm["max_shift"])
         else:
             result = ops.overlay_lut(original, edited, alpha, luts)
+    under = alpha                                    # the weight the grain is added under
+    if kd is not None:
+        sigma = keyed_sigma(ops.highpass_hist(ref, ring_of(kd["ring"]), 255, 255), kd) if kd["noise"] > 0 else None
+        key = change_key(original, result, kd, sigma)
+        result = ops.overlay(original, result, key)
+        under = torch.minimum(alpha, key)
     if gr is None:
         return result
     if "spectrum" in gr:
         ring = ring_of(gr["ring"])
         h1, h2 = ops.highpass_hist_step(ref, ring, 255, 255, 1), ops.highpass_hist_step(ref, ring, 255, 255, 2)
         shape = grain_shape(h1, h2, gr)
-        gains = grain_shaped_gains(h1, ops.highpass_hist_step(result, alpha, 255, 255, 1), shape, gr)
+        gains = grain_shaped_gains(h1, ops.highpass_hist_step(result, under, 255, 255, 1), shape, gr)
         if not gains.any():
             return result
-        return ops.grain_shaped(result, alpha, gains, shape, origin, gr["seed"], out=result)
-    gains = grain_gains(ops.highpass_hist(ref, ring_of(gr["ring"]), 255, 255), ops.highpass_hist(result, alpha, 255, 255), gr)
+        return ops.grain_shaped(result, under, gains, shape, origin, gr["seed"], out=result)
+    gains = grain_gains(ops.highpass_hist(ref, ring_of(gr["ring"]), 255, 255), ops.highpass_hist(result, under, 255, 255), gr)
     if not gains.any():
         return result                                # nothing to add: the scene is no noisier than the edit, or too few pixels to tell
-    return ops.grain(result, alpha, gains, origin, gr["seed"], out=result)
+    return ops.grain(result, under, gains, origin, gr["seed"], out=result)
 
 
 def grey_of(mask) -> np.ndarray:

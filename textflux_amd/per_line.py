@@ -98,7 +98,9 @@ def compose_lines(pipe, lines: Sequence[Any], crops: Sequence[Any], cfg: Dict[st
     seamless and, for the same reason, the same color_ref (the membrane's difference is taken against the original region); passed
     only then.  With cfg["grain"] the call gets grain, origin = the region's top-left scene pixel (the grain is anchored at scene
     positions) and the same color_ref (the scene's noise level is measured on the original region, not on grain an earlier line's paste
-    added); passed only then.
+    added); passed only then.  With cfg["keyed"] the call gets keyed and the same color_ref (the noise level that the key's thresholds
+    stay above is the original region's); passed only then.  The key itself compares the blend with the CURRENT pixels, so what an
+    earlier line pasted is kept like any other scene content.
     A rectified, perspective or curved line (Work.rect: a Rect, a Quad or a Ribbon) is pasted into its window `region`, the bounding box
     of the oriented rectangle or of the upright crop's footprint cut at the image: the call
     also gets rect and origin = the window's top-left scene pixel, and the pipeline warps the upright result into the window before
@@ -118,6 +120,8 @@ def compose_lines(pipe, lines: Sequence[Any], crops: Sequence[Any], cfg: Dict[st
             kw.update(seamless=cfg["seamless"], color_ref=np.ascontiguousarray(w.orig_scene[reg.y0:reg.y1, reg.x0:reg.x1]))
         if cfg.get("grain"):
             kw.update(grain=cfg["grain"], origin=(reg.x0, reg.y0), color_ref=np.ascontiguousarray(w.orig_scene[reg.y0:reg.y1, reg.x0:reg.x1]))
+        if cfg.get("keyed"):
+            kw.update(keyed=cfg["keyed"], color_ref=np.ascontiguousarray(w.orig_scene[reg.y0:reg.y1, reg.x0:reg.x1]))
         if w.rect is not None:
             kw.update(rect=w.rect, origin=(reg.x0, reg.y0))
         pasted = pipe.paste_back(cur, cropped, om, dilate=cfg["dilate"], feather=cfg["feather"], **kw)

@@ -759,7 +759,7 @@ class FluxFillPipeline:
 
     # ------------------------------------------------------------------ paste-back (DESIGN.md section 4 "Paste-back")
     def paste_back(self, original, edited, mask, dilate: int = 16, feather: int = 4, color_match=None, color_ref=None, rect=None,
-                   origin=(0, 0), seamless=None, grain=None) -> torch.Tensor:
+                   origin=(0, 0), seamless=None, grain=None, keyed=None) -> torch.Tensor:
         """The edited image blended into the ORIGINAL one, at the original's size, under the dilated and feathered mask
         (textflux_amd/paste_back.py::paste): pixels outside the mask grown by dilate + 3 feather keep their bytes.  Opt-in, no reference
         counterpart.  original / edited: a PIL image, a uint8 array or tensor [H, W, 3] / [B, H, W, 3], or a list of PIL images (edited
@@ -773,7 +773,9 @@ class FluxFillPipeline:
         without color_match.  grain: None, or True / dict(ring, max_sigma, strength, min_pixels, seed): after the blend the pasted pixels
         get the noise level of color_ref (None: `original`) just outside the blend, as hashed white grain anchored at the scene position
         `origin` + the pixel's place in `original` (paste_back.paste; DESIGN.md section 4 "Grain match"); color_ref may then be given
-        without color_match.  Returns uint8 [B, H, W, 3] on the device."""
+        without color_match.  keyed: None, or True / dict(lo, hi, dilate, feather, noise, ring, min_pixels): behind the blend and in
+        front of the grain, a pixel keeps `original`'s byte unless the blend really differs there (paste_back.paste; DESIGN.md section 4
+        "Keyed paste"); color_ref may then be given without color_match.  Returns uint8 [B, H, W, 3] on the device."""
         from . import paste_back as pb
         dev = self._execution_device
 
@@ -813,6 +815,8 @@ class FluxFillPipeline:
             kw["seamless"] = seamless
         if grain is not None:
             kw.update(grain=grain, origin=origin)
+        if keyed is not None:
+            kw["keyed"] = keyed
         if color_match is None and color_ref is None:
             return pb.paste(original, rgb(edited), grey(mask, tuple(original.shape[1:3])), dilate, feather, **kw)
         return pb.paste(original, rgb(edited), grey(mask, tuple(original.shape[1:3])), dilate, feather, color_match=color_match,
