@@ -282,6 +282,14 @@ int tfx_known_region_blend(void* x, int64_t ldx, const void* x0, const void* noi
 int tfx_change_map_blend(void* x, int64_t ldx, const void* x0, const void* noise, const void* hold, const int32_t* cut, int32_t C,
                          int64_t rows, const float* keep_sigma, const int32_t* step_ptr, int32_t step, void* xin, int64_t ldxin,
                          tfx_stream stream);
+/* ---- true CFG combine (DESIGN.md section 4 "True CFG"; D/examples/community/pipeline_flux_with_cfg.py:808, noise_pred = neg +
+ *      true_cfg * (pos - neg) on bf16 tensors): v_neg, v_pos, out bf16 [rows, C] contiguous, g = *scale a DEVICE fp32 read when the kernel
+ *      runs.  Every torch op rounds on its own and the Python float takes part as fp32:
+ *        d = bf16(f32(pos) - f32(neg))   m = bf16(g f32(d))   out = bf16(f32(neg) + f32(m))
+ *      out may be v_neg itself (in place).  Refused: C not a positive multiple of 8; a null or not 16-byte aligned tensor pointer, a null or
+ *      not 4-byte aligned scale; out overlapping v_pos; out partly overlapping v_neg; scale inside out.  rows == 0 launches nothing.  No new
+ *      TFX_ABI_VERSION: new entry points only. */
+int tfx_cfg_combine(const void* v_neg, const void* v_pos, void* out, int32_t C, int64_t rows, const float* scale, tfx_stream stream);
 
 /* ---- small ops of the conditioning path (CombinedTimestepGuidanceTextProjEmbeddings, D/models/embeddings.py:1327-1339) */
 int tfx_timestep_embedding(const float* t, void* out /* [n,256] = cos|sin */, int32_t n, tfx_stream stream);
@@ -511,6 +519,22 @@ typedef struct tfx_step_change {
 int tfx_dit_step_run_ex2(const tfx_step_desc* step, const tfx_step_extra* extra, const tfx_step_change* change, tfx_stream stream);
 int tfx_dit_step_capture_ex2(const tfx_step_desc* step, const tfx_step_extra* extra, const tfx_step_change* change, tfx_stream stream,
                              tfx_graph* out);
+/* The step with true CFG (DESIGN.md section 4 "True CFG"; the loop of FluxCFGPipeline, D/examples/community/pipeline_flux_with_cfg.py:
+ * 778-812): a third struct beside the descriptor, so that every other struct keeps its layout.  cfg == NULL is tfx_dit_step_run_ex2.
+ * With cfg set, step->dit describes a batch of 2B: samples [0, B) carry the negative conditioning and [B, 2B) the positive (the order of
+ * the reference's torch.cat); latents, noise, extra->v_prev, the keep_* buffers and hold have B * S rows.  A step is: the modulation rows,
+ * tfx_dit_forward on 2B, tfx_cfg_combine over the two halves of dit.out into the first, the sampler update on B * S rows (sampler 0,
+ * sampler 1 or the multistep update), the known-region or change-map blend when given, tfx_copy_rows of columns [0, out_channels) of
+ * dit.xin's first half into its second (sample B + b mirrors sample b), the cursor advance.  scale: DEVICE fp32, read when the step runs
+ * -- one captured graph serves every step and every scale.  Refused: sampler 2 (the fused Euler epilogue updates each half on its own),
+ * dit.seq_len, a phase other than 0, an odd dit.B, a NULL or misaligned scale, scale inside a buffer the step writes. */
+typedef struct tfx_step_cfg {
+  const float* scale;
+} tfx_step_cfg;
+int tfx_dit_step_run_ex3(const tfx_step_desc* step, const tfx_step_extra* extra, const tfx_step_change* change, const tfx_step_cfg* cfg,
+                         tfx_stream stream);
+int tfx_dit_step_capture_ex3(const tfx_step_desc* step, const tfx_step_extra* extra, const tfx_step_change* change, const tfx_step_cfg* cfg,
+                             tfx_stream stream, tfx_graph* out);
 
 /* ---- VAE ends (AutoencoderKL, D/models/autoencoders/autoencoder_kl.py:263-332) on NHWC bf16 activations -------------
  * 3x3 convolution as an implicit GEMM on the MFMA kernel (ResnetBlock2D convs D/models/resnet.py:327-366, Upsample2D

@@ -298,6 +298,25 @@ def add_known_region_args(ap):
                     "its value at every 8th pixel, or 'cover': masked wherever anything masked touches the latent pixel")
     ap.add_argument("--keep_known_grow", type=int, default=0, metavar="N", help="with cover: also mask the N neighbouring latent pixels (0..8)")
     add_change_map_args(ap)
+    add_true_cfg_args(ap)
+
+
+def add_true_cfg_args(ap):
+    """Not in the reference's Fill callers: true CFG (FluxFillPipeline.__call__: true_cfg, negative_prompt)."""
+    ap.add_argument("--true_cfg", type=float, default=1.0, metavar="F", help="classifier-free guidance against --negative_prompt: every step runs "
+                    "the model on [negative; positive] and steps along neg + F * (pos - neg); > 1 switches it on, at about twice the step cost")
+    ap.add_argument("--negative_prompt", type=str, default=None, metavar="STR", help="with --true_cfg > 1: the negative prompt (both text encoders)")
+
+
+def true_cfg_from_args(a):
+    """-> {} (the defaults: today's call), or dict(true_cfg, negative_prompt) for the pipeline call"""
+    if a.negative_prompt is None and a.true_cfg == 1.0:
+        return {}
+    if a.negative_prompt is None:
+        raise SystemExit("--true_cfg needs --negative_prompt")
+    if not a.true_cfg > 1.0:
+        raise SystemExit(f"--negative_prompt needs --true_cfg > 1, got {a.true_cfg}")
+    return dict(true_cfg=a.true_cfg, negative_prompt=a.negative_prompt)
 
 
 def add_change_map_args(ap):
@@ -349,6 +368,7 @@ def known_region_from_args(a):
     cm = change_map_from_args(a)
     if cm is not None:
         known["change_map"] = cm
+    known.update(true_cfg_from_args(a))
     return known or None
 
 

@@ -6,7 +6,8 @@
         [--output_dir visualization_results --font_path resource/font/Arial-Unicode-Regular.ttf --text_height_ratio 0.1667
          --steps 30 --guidance_scale 30 --seed 42 --num_gpus 4 --scheduler "" | overshoot | multistep
          --strength 1.0 --keep_known --keep_known_mode nearest | cover --keep_known_grow 0
-         --change_map --change_dilate N --change_feather N --change_mode nearest | cover --change_grow 0 --change_last keep | free]
+         --change_map --change_dilate N --change_feather N --change_mode nearest | cover --change_grow 0 --change_last keep | free
+         --true_cfg F --negative_prompt STR]
 
 `annos.json` = {"data_list": [{"img_name": ..., "annotations": [{"text": ..., "polygon": [[x, y], ...]}, ...]}, ...]}; per item
 the first annotation is used: polygon -> white-on-black mask, glyph strip of height int(width * text_height_ratio) stacked on
@@ -77,6 +78,9 @@ def build_parser(lora: bool = False):
     ap.add_argument("--keep_known_mode", choices=("nearest", "cover"), default="nearest", help="latent mask from the pixel mask: its value at "
                     "every 8th pixel, or masked wherever anything masked touches the latent pixel (with --keep_known)")
     ap.add_argument("--keep_known_grow", type=int, default=0, metavar="N", help="with cover: also mask the N neighbouring latent pixels, 0..8")
+    ap.add_argument("--true_cfg", type=float, default=1.0, metavar="F", help="true CFG against --negative_prompt: every step runs the model on "
+                    "[negative; positive] and steps along neg + F * (pos - neg); > 1 switches it on (not with --mixed_pad, not with --step_cache)")
+    ap.add_argument("--negative_prompt", type=str, default=None, metavar="STR", help="with --true_cfg > 1: one negative prompt for all items")
     ap.add_argument("--change_map", action="store_true", help="change-map sampling: every latent pixel gets its own release step from the "
                     "dilated and feathered mask of its call (not with --keep_known)")
     ap.add_argument("--change_dilate", type=int, default=None, metavar="N", help="with --change_map: grow the mask by N pixels (default: the paste-back's)")
@@ -227,6 +231,16 @@ def main(argv=None, lora: bool = False, script: str = __file__):
             raise SystemExit("--change_dilate / --change_feather must be >= 0")
         known["change_map"] = dict(mode=a.change_mode, grow=a.change_grow, last=a.change_last,
                                    **{k: v for k, v in (("dilate", a.change_dilate), ("feather", a.change_feather)) if v is not None})
+    if a.negative_prompt is not None or a.true_cfg != 1.0:
+        if a.negative_prompt is None:
+            raise SystemExit("--true_cfg needs --negative_prompt")
+        if not a.true_cfg > 1.0:
+            raise SystemExit(f"--negative_prompt needs --true_cfg > 1, got {a.true_cfg}")
+        if a.mixed_pad > 0:
+            raise SystemExit("--true_cfg does not serve mixed-geometry batches (--mixed_pad)")
+        if a.step_cache is not None:
+            raise SystemExit("--true_cfg does not run with --step_cache")
+        known["true_cfg"], known["negative_prompt"] = a.true_cfg, a.negative_prompt
     if a.step_cache is None and a.step_cache_max_consecutive is not None:
         raise SystemExit("--step_cache_max_consecutive needs --step_cache THR")
     if a.step_cache is not None and a.mixed_pad > 0:

@@ -5,7 +5,8 @@
         [--output_dir ... --font_path ... --text_height_ratio 0.1667 --steps 30 --guidance_scale 30 --seed 42 --num_gpus 4
          --scheduler overshoot (the default here, as in the reference) | "" | multistep
          --strength 1.0 --keep_known --keep_known_mode nearest | cover --keep_known_grow 0 (known-region sampling, as in run_eval.py)
-         --change_map --change_dilate N --change_feather N --change_mode ... --change_grow N --change_last ... (change-map sampling, as in run_eval.py)]
+         --change_map --change_dilate N --change_feather N --change_mode ... --change_grow N --change_last ... (change-map sampling, as in run_eval.py)
+         --true_cfg F --negative_prompt STR (true CFG, as in run_eval.py)]
 
 Every rank loads the base FLUX.1-Fill-dev transformer ($TEXTFLUX_BASE/transformer), reads the LoRA with
 FluxFillPipeline.lora_state_dict(return_alphas=True), applies the reference's format check ("Invalid LoRA checkpoint.") and

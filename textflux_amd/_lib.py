@@ -122,6 +122,11 @@ class StepChange(C.Structure):
     _fields_ = [("hold", c_void_p), ("cut", c_void_p)]
 
 
+class StepCfg(C.Structure):
+    """tfx_step_cfg: true CFG's device scale, beside tfx_step_extra and tfx_step_change through the *_ex3 step entry points"""
+    _fields_ = [("scale", c_void_p)]
+
+
 # name -> (restype, argtypes); every symbol include/textflux_hip.h declares must appear here (tests check it)
 SIGNATURES = {
     "tfx_version": (c_char_p, []),
@@ -163,6 +168,7 @@ SIGNATURES = {
                                        c_void_p, c_int64, c_void_p]),
     "tfx_change_map_blend": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int64, c_void_p, c_void_p, c_int32,
                                      c_void_p, c_int64, c_void_p]),
+    "tfx_cfg_combine": (c_int, [c_void_p, c_void_p, c_void_p, c_int32, c_int64, c_void_p, c_void_p]),
     "tfx_timestep_embedding": (c_int, [c_void_p, c_void_p, c_int32, c_void_p]),
     "tfx_silu": (c_int, [c_void_p, c_void_p, c_int64, c_void_p]),
     "tfx_add": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
@@ -184,6 +190,9 @@ SIGNATURES = {
     "tfx_dit_step_capture_ex": (c_int, [C.POINTER(StepDesc), C.POINTER(StepExtra), c_void_p, C.POINTER(c_void_p)]),
     "tfx_dit_step_run_ex2": (c_int, [C.POINTER(StepDesc), C.POINTER(StepExtra), C.POINTER(StepChange), c_void_p]),
     "tfx_dit_step_capture_ex2": (c_int, [C.POINTER(StepDesc), C.POINTER(StepExtra), C.POINTER(StepChange), c_void_p, C.POINTER(c_void_p)]),
+    "tfx_dit_step_run_ex3": (c_int, [C.POINTER(StepDesc), C.POINTER(StepExtra), C.POINTER(StepChange), C.POINTER(StepCfg), c_void_p]),
+    "tfx_dit_step_capture_ex3": (c_int, [C.POINTER(StepDesc), C.POINTER(StepExtra), C.POINTER(StepChange), C.POINTER(StepCfg), c_void_p,
+                                         C.POINTER(c_void_p)]),
     "tfx_step_cache_metric": (c_int, [c_void_p, c_int64, c_int64, C.POINTER(StepCache), c_int32, c_int32, c_int32, c_void_p]),
     "tfx_step_cache_store": (c_int, [c_void_p, c_int64, c_int64, C.POINTER(StepCache), c_int32, c_int32, c_int32, c_void_p]),
     "tfx_step_cache_apply": (c_int, [c_void_p, c_int64, c_int64, C.POINTER(StepCache), c_int32, c_int32, c_int32, c_void_p]),

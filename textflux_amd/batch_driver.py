@@ -442,7 +442,7 @@ def run_items(items: Sequence[Dict[str, Any]], pipe, out_dir: Optional[str], bat
               save: Optional[Callable] = None, max_sequence_length: int = 512, eval_cfg: Optional[Dict[str, Any]] = None,
               encode: str = "auto", save_full: Optional[Callable] = None, mixed_pad: float = 0.0,
               step_cache: Optional[Dict[str, Any]] = None, paste_back: Optional[Dict[str, Any]] = None, keep_known=None,
-              strength: float = 1.0, change_map=None) -> Dict[str, Any]:
+              strength: float = 1.0, change_map=None, true_cfg: float = 1.0, negative_prompt: Optional[str] = None) -> Dict[str, Any]:
     """Runs the whole list; returns {"done": [indices this rank wrote], "failed": [...], "all_done": [...] on rank 0,
     "encode": "local" | "rank0"}.  `pipe` needs `encode_prompt(prompt, prompt_2, ...)` and the FluxFillPipeline `__call__`.
     encode: "local" = every rank encodes the T5 prompts of its own batches (needs a T5 on every rank), "rank0" = rank 0
@@ -501,8 +501,19 @@ def run_items(items: Sequence[Dict[str, Any]], pipe, out_dir: Optional[str], bat
     change_map (DESIGN.md section 4 "Change-map sampling"): handed to every pipeline call as it is -- True or dict(dilate, feather, mode,
     grow, last) derives the map inside each call from that call's own mask, so it composes with paste_back, region, per_line and the
     warps with no further work (every line's call sees its own line's mask); an explicit map (an image, or dict(map=...)) must have the
-    calls' size.  Not with keep_known, not with mixed_pad > 0."""
+    calls' size.  Not with keep_known, not with mixed_pad > 0.
+    true_cfg, negative_prompt (DESIGN.md section 4 "True CFG"): one negative prompt string for all items and the guidance scale against
+    it, handed to every pipeline call as they are (the calls behind paste_back, region and per_line included) when true_cfg > 1 and a
+    negative prompt is given; every step then runs on twice the batch.  Not with mixed_pad > 0, not with step_cache."""
     known = {}
+    if negative_prompt is not None and not isinstance(negative_prompt, str):
+        raise ValueError("negative_prompt is one string for all items")
+    if negative_prompt is not None and true_cfg > 1:
+        if mixed_pad > 0:
+            raise NotImplementedError("true_cfg / negative_prompt (true CFG) do not serve mixed-geometry batches (mixed_pad > 0)")
+        if step_cache is not None:
+            raise NotImplementedError("true_cfg / negative_prompt (true CFG) do not run with step_cache")
+        known["true_cfg"], known["negative_prompt"] = float(true_cfg), negative_prompt
     if change_map is not None and change_map is not False:
         if keep_known:
             raise ValueError("change_map and keep_known exclude each other")

@@ -284,6 +284,10 @@ int tfx_known_region_blend(void* x, int64_t ldx, const void* x0, const void* noi
   return known_region_blend(x, ldx, x0, noise, mask, C, rows, keep_sigma, step_ptr, step, xin, ldxin, S(stream));
 }
 
+int tfx_cfg_combine(const void* v_neg, const void* v_pos, void* out, int32_t C, int64_t rows, const float* scale, tfx_stream stream) {
+  return cfg_combine(v_neg, v_pos, out, C, rows, scale, S(stream));
+}
+
 int tfx_change_map_blend(void* x, int64_t ldx, const void* x0, const void* noise, const void* hold, const int32_t* cut, int32_t C,
                          int64_t rows, const float* keep_sigma, const int32_t* step_ptr, int32_t step, void* xin, int64_t ldxin,
                          tfx_stream stream) {
@@ -697,11 +701,16 @@ int step_check(const tfx_step_desc* s) {
 // the scheduler update behind the final projection and the cursor advance: the end of a whole step and of both tails.
 // ex.v_prev: the multistep history buffer -- the second-order update then stands where sampler 0 launches Euler's.  ex.keep_*: the
 // known-region blend, behind the update and in front of the step cache's store pass and the cursor advance (it reads the cursor).
-// ch: the change-map blend in the same place, its mask decided on the device from hold and cut (keep_mask is then NULL)
-int step_finish(const tfx_step_desc& s, hipStream_t st, const StepCacheArgs* store, const tfx_step_extra& ex, const tfx_step_change* ch) {
+// ch: the change-map blend in the same place, its mask decided on the device from hold and cut (keep_mask is then NULL).
+// cfg: true CFG -- the batch is [negative; positive], the two halves of dit.out are combined into the first in front of the update,
+// the update and the blend run on the first half's rows, and the new latents are copied into the second half of xin behind them
+int step_finish(const tfx_step_desc& s, hipStream_t st, const StepCacheArgs* store, const tfx_step_extra& ex, const tfx_step_change* ch,
+                const tfx_step_cfg* cfg) {
   const tfx_dit_desc& d = s.dit;
-  const int64_t rows = (int64_t)d.B * d.S;
+  const int Bx = cfg ? d.B / 2 : d.B;                           // samples of the loop state
+  const int64_t rows = (int64_t)Bx * d.S;
   void* xin = const_cast<void*>(d.xin);
+  if (cfg) TRY(cfg_combine(d.out, (const uint16_t*)d.out + rows * d.out_channels, d.out, d.out_channels, rows, cfg->scale, st));
   if (ex.v_prev) {
     TRY(multistep_step(d.out, s.latents, xin, d.in_channels, d.out_channels, rows, s.coef, s.step_ptr, 0, ex.v_prev, st));
   } else if (s.sampler != 2) {                                  // sampler 2: the update happened in proj_out's epilogue
@@ -720,6 +729,9 @@ int step_finish(const tfx_step_desc& s, hipStream_t st, const StepCacheArgs* sto
       TRY(known_region_blend(x, ldx, ex.keep_x0, ex.keep_noise, ex.keep_mask, d.out_channels, rows, ex.keep_sigma, s.step_ptr, 0, mirror,
                              ldmirror, st));
   }
+  if (cfg)                                                      // sample B + b of the x_embedder input mirrors sample b
+    TRY(copy_rows(xin, d.in_channels, (int64_t)d.S * d.in_channels, (uint16_t*)xin + rows * d.in_channels, d.in_channels,
+                  (int64_t)d.S * d.in_channels, d.S, d.out_channels, Bx, st));
   if (store) TRY(step_cache_store(*store, st));
   return advance_step(s.step_ptr, st);
 }
@@ -731,11 +743,11 @@ int step_forward(const tfx_step_desc& s, int first, int last, int flags, hipStre
   return tfx_dit_forward(&d, (tfx_stream)st);
 }
 
-int step_enqueue(const tfx_step_desc& s, hipStream_t st, const tfx_step_extra& ex, const tfx_step_change* ch) {
+int step_enqueue(const tfx_step_desc& s, hipStream_t st, const tfx_step_extra& ex, const tfx_step_change* ch, const tfx_step_cfg* cfg) {
   if (s.phase == 0) {
     TRY(select_step(s.mod_table, s.mod_cur, s.mod_step_elems, s.step_ptr, st));
     TRY(tfx_dit_forward(&s.dit, (tfx_stream)st));
-    return step_finish(s, st, nullptr, ex, ch);
+    return step_finish(s, st, nullptr, ex, ch, cfg);
   }
   StepCacheArgs a;
   TRY(step_cache_view(s, a));
@@ -749,11 +761,11 @@ int step_enqueue(const tfx_step_desc& s, hipStream_t st, const tfx_step_extra& e
       return step_cache_metric(a, st);
     case 2:   // computed tail: the rest of the whole step, then r and f_prev
       TRY(step_forward(s, 1, -1, 1, st));
-      return step_finish(s, st, &a, ex, ch);
+      return step_finish(s, st, &a, ex, ch, nullptr);
     default:  // 3, cached tail: the last computed step's residual stands in for blocks [1, n)
       TRY(step_cache_apply(a, st));
       TRY(step_forward(s, nblk, nblk, 1, st));
-      return step_finish(s, st, nullptr, ex, ch);
+      return step_finish(s, st, nullptr, ex, ch, nullptr);
   }
 }
 
@@ -770,11 +782,37 @@ int step_check_multistep(const tfx_step_desc* s, const void* v_prev) {
 // *_multistep entry points, which refuse a NULL v_prev.  ch NULL (`who` "ex"): keep_* all set, the known-region blend, or all NULL.
 // ch set (`who` "ex2"), the change-map blend: keep_x0 / keep_noise / keep_sigma, hold and cut set, keep_mask NULL.  Neither blend
 // with dit.seq_len, and nothing a blend reads may alias a buffer the step writes.
-int step_check_extra(const tfx_step_desc* s, const tfx_step_extra* ex, const tfx_step_change* ch, const char* who, bool need_history) {
+// cfg set (`who` "ex3"), true CFG: sampler 0 or 1, phase 0, an even dit.B, no dit.seq_len, and a scale outside what the step writes;
+// latents, v_prev and the blends' buffers then have dit.B / 2 samples.
+int step_check_cfg(const tfx_step_desc* s, const tfx_step_extra* ex, const tfx_step_cfg* cfg) {
+  const tfx_dit_desc& d = s->dit;
+  if (!cfg->scale) return fail("tfx_dit_step (ex3): cfg->scale is null");
+  if ((uintptr_t)cfg->scale & 3) return fail("tfx_dit_step (ex3): cfg->scale must be 4-byte aligned");
+  if (s->sampler == 2)
+    return fail("tfx_dit_step (ex3): true CFG cannot run with sampler 2: the fused Euler epilogue updates each half of the batch on its own");
+  if (d.seq_len) return fail("tfx_dit_step (ex3): true CFG cannot serve a mixed-geometry batch (dit.seq_len)");
+  if (s->phase != 0) return fail("tfx_dit_step (ex3): true CFG runs whole steps only (phase 0), not the step cache's phase %d", s->phase);
+  if (d.B < 2 || d.B % 2) return fail("tfx_dit_step (ex3): true CFG needs an even dit.B (the batch is [negative; positive]), got %d", d.B);
+  if (!d.xin) return fail("tfx_dit_step (ex3): dit.xin is null");
+  const int64_t N = (int64_t)d.S + d.T, half = (int64_t)(d.B / 2) * d.S * d.out_channels * 2, tok = (int64_t)d.B * N * d.D * 2;
+  struct Span { const void* p; int64_t bytes; };
+  const Span written[9] = {{s->latents, half}, {d.out, 2 * half}, {d.xin, (int64_t)d.B * d.S * d.in_channels * 2}, {ex->v_prev, half},
+                           {s->mod_cur, s->mod_step_elems * 2}, {s->step_ptr, 4}, {d.hid, tok}, {d.xn, tok}, {d.y, 7 * tok}};
+  const char* p = (const char*)cfg->scale;
+  for (const Span& w : written) {
+    const char* q = (const char*)w.p;
+    if (q && p < q + w.bytes && q < p + 4) return fail("tfx_dit_step (ex3): cfg->scale must not lie in a buffer the step writes");
+  }
+  return 0;
+}
+
+int step_check_extra(const tfx_step_desc* s, const tfx_step_extra* ex, const tfx_step_change* ch, const tfx_step_cfg* cfg, const char* who,
+                     bool need_history) {
   if (!ex)
     return ch ? fail("tfx_dit_step (ex2): null tfx_step_extra: the change-map blend reads keep_x0, keep_noise and keep_sigma from it")
               : fail("tfx_dit_step (ex): null tfx_step_extra (tfx_dit_step_run / tfx_dit_step_capture take none)");
   if (ex->v_prev || need_history) TRY(step_check_multistep(s, ex->v_prev)); else TRY(step_check(s));
+  if (cfg) TRY(step_check_cfg(s, ex, cfg));
   if (ch) {
     if (!ch->hold || !ch->cut) return fail("tfx_dit_step (ex2): change->hold and change->cut must both be set");
     if (!ex->keep_x0 || !ex->keep_noise || !ex->keep_sigma) return fail("tfx_dit_step (ex2): with change, keep_x0, keep_noise and keep_sigma must be set");
@@ -789,9 +827,9 @@ int step_check_extra(const tfx_step_desc* s, const tfx_step_extra* ex, const tfx
     return fail("tfx_dit_step (%s): the %s blend cannot serve a mixed-geometry batch (dit.seq_len): its buffers are [B * S, C] without padding rows",
                 who, ch ? "change-map" : "known-region");
   if (!d.xin) return fail("tfx_dit_step (%s): dit.xin is null", who);
-  const int64_t rows = (int64_t)d.B * d.S, kb = rows * d.out_channels * 2;
+  const int64_t all = (int64_t)d.B * d.S, rows = cfg ? all / 2 : all, kb = rows * d.out_channels * 2;   // true CFG: the loop state is half the batch
   struct Span { const void* p; int64_t bytes; };
-  const Span written[4] = {{s->latents, kb}, {d.out, kb}, {d.xin, rows * d.in_channels * 2}, {ex->v_prev, kb}};
+  const Span written[4] = {{s->latents, kb}, {d.out, all * d.out_channels * 2}, {d.xin, all * d.in_channels * 2}, {ex->v_prev, kb}};
   const Span read[6] = {{ex->keep_x0, kb}, {ex->keep_noise, kb}, {ex->keep_mask, kb}, {ex->keep_sigma, 4},
                         {ch ? ch->hold : nullptr, rows * 4}, {ch ? ch->cut : nullptr, 4}};
   for (const Span& r : read) {
@@ -806,14 +844,15 @@ int step_check_extra(const tfx_step_desc* s, const tfx_step_extra* ex, const tfx
   return 0;
 }
 
-int step_capture(const tfx_step_desc* s, const tfx_step_extra& ex, const tfx_step_change* ch, tfx_stream stream, tfx_graph* out) {
+int step_capture(const tfx_step_desc* s, const tfx_step_extra& ex, const tfx_step_change* ch, const tfx_step_cfg* cfg, tfx_stream stream,
+                 tfx_graph* out) {
   if (!out) return fail("tfx_dit_step_capture: null output handle");
   if (!stream) return fail("tfx_dit_step_capture: the NULL stream cannot be captured; pass a created stream");
   hipStream_t st = S(stream);
   (void)attention_w4_prepare(st);   // the attention kernel's scratch (of this stream) cannot be allocated inside a capture
   hipError_t e = hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal);
   if (e != hipSuccess) return fail("tfx_dit_step_capture: hipStreamBeginCapture: %s", hipGetErrorString(e));
-  const int rc = step_enqueue(*s, st, ex, ch);
+  const int rc = step_enqueue(*s, st, ex, ch, cfg);
   hipGraph_t g = nullptr;
   e = hipStreamEndCapture(st, &g);
   if (rc) { if (g) (void)hipGraphDestroy(g); return rc; }    // last error already set by the failing launcher
@@ -827,9 +866,10 @@ int step_capture(const tfx_step_desc* s, const tfx_step_extra& ex, const tfx_ste
 
 // Every step entry point: the checks, then the step on the stream, or (CAPTURE) captured from it into *graph_out
 enum { RUN = 0, CAPTURE = 1, NEED_HISTORY = 2 };
-int step_entry(const tfx_step_desc* s, const tfx_step_extra* ex, const tfx_step_change* ch, tfx_stream stream, tfx_graph* graph_out, int how) {
-  TRY(step_check_extra(s, ex, ch, ch ? "ex2" : "ex", (how & NEED_HISTORY) != 0));
-  return how & CAPTURE ? step_capture(s, *ex, ch, stream, graph_out) : step_enqueue(*s, S(stream), *ex, ch);
+int step_entry(const tfx_step_desc* s, const tfx_step_extra* ex, const tfx_step_change* ch, const tfx_step_cfg* cfg, tfx_stream stream,
+               tfx_graph* graph_out, int how) {
+  TRY(step_check_extra(s, ex, ch, cfg, cfg ? "ex3" : ch ? "ex2" : "ex", (how & NEED_HISTORY) != 0));
+  return how & CAPTURE ? step_capture(s, *ex, ch, cfg, stream, graph_out) : step_enqueue(*s, S(stream), *ex, ch, cfg);
 }
 
 const tfx_step_extra kPlain{};   // the plain step's tfx_step_extra: no history, no blend
@@ -842,32 +882,41 @@ tfx_step_extra history(void* v_prev) {
 }
 }  // namespace
 
-int tfx_dit_step_run(const tfx_step_desc* s, tfx_stream stream) { return step_entry(s, &kPlain, nullptr, stream, nullptr, RUN); }
+int tfx_dit_step_run(const tfx_step_desc* s, tfx_stream stream) { return step_entry(s, &kPlain, nullptr, nullptr, stream, nullptr, RUN); }
 
-int tfx_dit_step_capture(const tfx_step_desc* s, tfx_stream stream, tfx_graph* out) { return step_entry(s, &kPlain, nullptr, stream, out, CAPTURE); }
+int tfx_dit_step_capture(const tfx_step_desc* s, tfx_stream stream, tfx_graph* out) { return step_entry(s, &kPlain, nullptr, nullptr, stream, out, CAPTURE); }
 
 int tfx_dit_step_run_multistep(const tfx_step_desc* s, void* v_prev, tfx_stream stream) {
   const tfx_step_extra ex = history(v_prev);
-  return step_entry(s, &ex, nullptr, stream, nullptr, RUN | NEED_HISTORY);
+  return step_entry(s, &ex, nullptr, nullptr, stream, nullptr, RUN | NEED_HISTORY);
 }
 
 int tfx_dit_step_capture_multistep(const tfx_step_desc* s, void* v_prev, tfx_stream stream, tfx_graph* out) {
   const tfx_step_extra ex = history(v_prev);
-  return step_entry(s, &ex, nullptr, stream, out, CAPTURE | NEED_HISTORY);
+  return step_entry(s, &ex, nullptr, nullptr, stream, out, CAPTURE | NEED_HISTORY);
 }
 
-int tfx_dit_step_run_ex(const tfx_step_desc* s, const tfx_step_extra* ex, tfx_stream stream) { return step_entry(s, ex, nullptr, stream, nullptr, RUN); }
+int tfx_dit_step_run_ex(const tfx_step_desc* s, const tfx_step_extra* ex, tfx_stream stream) { return step_entry(s, ex, nullptr, nullptr, stream, nullptr, RUN); }
 
 int tfx_dit_step_capture_ex(const tfx_step_desc* s, const tfx_step_extra* ex, tfx_stream stream, tfx_graph* out) {
-  return step_entry(s, ex, nullptr, stream, out, CAPTURE);
+  return step_entry(s, ex, nullptr, nullptr, stream, out, CAPTURE);
 }
 
 int tfx_dit_step_run_ex2(const tfx_step_desc* s, const tfx_step_extra* ex, const tfx_step_change* ch, tfx_stream stream) {
-  return step_entry(s, ex, ch, stream, nullptr, RUN);
+  return step_entry(s, ex, ch, nullptr, stream, nullptr, RUN);
 }
 
 int tfx_dit_step_capture_ex2(const tfx_step_desc* s, const tfx_step_extra* ex, const tfx_step_change* ch, tfx_stream stream, tfx_graph* out) {
-  return step_entry(s, ex, ch, stream, out, CAPTURE);
+  return step_entry(s, ex, ch, nullptr, stream, out, CAPTURE);
+}
+
+int tfx_dit_step_run_ex3(const tfx_step_desc* s, const tfx_step_extra* ex, const tfx_step_change* ch, const tfx_step_cfg* cfg, tfx_stream stream) {
+  return step_entry(s, ex, ch, cfg, stream, nullptr, RUN);
+}
+
+int tfx_dit_step_capture_ex3(const tfx_step_desc* s, const tfx_step_extra* ex, const tfx_step_change* ch, const tfx_step_cfg* cfg,
+                             tfx_stream stream, tfx_graph* out) {
+  return step_entry(s, ex, ch, cfg, stream, out, CAPTURE);
 }
 
 int tfx_dit_step_replay(tfx_graph graph, tfx_stream stream) {

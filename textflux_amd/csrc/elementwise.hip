@@ -301,6 +301,26 @@ __global__ __launch_bounds__(256) void multistep_step_kernel(const bf16_t* __res
   store_and_mirror(x + i * 8, packed, xin, ldxin, C, i * 8);
 }
 
+// True CFG (DESIGN.md section 4 "True CFG"; D/examples/community/pipeline_flux_with_cfg.py:808): the model outputs of the negative and
+// the positive half of a doubled batch become one, in front of the sampler update.  v_neg, v_pos, out [nchunks * 8] contiguous; the
+// scale g is a device fp32 read when the kernel runs (a captured step graph serves every true_cfg).  The reference's three torch ops
+// on bf16 tensors with a Python float, each rounded on its own:
+//   d = bf16(f32(pos) - f32(neg))   m = bf16(g * f32(d))   out = bf16(f32(neg) + f32(m))
+// explicit _rn ops, no FMA contraction.  out may be v_neg itself: a thread reads chunk i of v_neg and then writes chunk i of out, and
+// no other thread touches that chunk (hence no __restrict__ on the two).
+__global__ __launch_bounds__(256) void cfg_combine_kernel(const bf16_t* v_neg, const bf16_t* __restrict__ v_pos, bf16_t* out,
+                                                          int64_t nchunks, const float* __restrict__ scale) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= nchunks) return;
+  const float g = *scale;
+  float nn[8], pp[8], o[8];
+  unpack8(*reinterpret_cast<const u32x4*>(v_neg + i * 8), nn);
+  unpack8(*reinterpret_cast<const u32x4*>(v_pos + i * 8), pp);
+#pragma unroll
+  for (int j = 0; j < 8; ++j) o[j] = __fadd_rn(nn[j], round_bf(__fmul_rn(g, round_bf(__fsub_rn(pp[j], nn[j])))));
+  *reinterpret_cast<u32x4*>(out + i * 8) = pack8(o);
+}
+
 // The blend behind a sampler update, known-region and change-map sampling alike: FluxInpaintPipeline's loop
 // (D/pipelines/flux/pipeline_flux_inpaint.py:974-984) and FluxDifferentialImg2ImgPipeline's (D/examples/community/
 // pipeline_flux_differential_img2img.py:974-986), with FlowMatchEulerDiscreteScheduler.scale_noise
@@ -738,6 +758,22 @@ int multistep_step(const void* v, void* x, void* xin, int64_t ldxin, int C, int6
   multistep_step_kernel<<<dim3((unsigned)((nch + 255) / 256)), 256, 0, st>>>((const bf16_t*)v, (bf16_t*)x, (bf16_t*)xin, ldxin, C, nch,
                                                                              coef, step_ptr, step, (bf16_t*)v_prev);
   return check_launch("multistep_step");
+}
+
+int cfg_combine(const void* v_neg, const void* v_pos, void* out, int C, int64_t rows, const float* scale, hipStream_t st) {
+  if (int e = step_tail_check("cfg_combine", C, rows, C, nullptr, 0)) return e;
+  const int64_t nch = rows * C / 8;
+  if (nch == 0) return 0;                               // nothing to combine: the pointers of empty tensors mean nothing
+  if (!v_neg || !v_pos || !out || !scale) return fail("cfg_combine: null pointer");
+  if (((uintptr_t)v_neg | (uintptr_t)v_pos | (uintptr_t)out) & 15) return fail("cfg_combine: v_neg, v_pos and out must be 16-byte aligned");
+  if ((uintptr_t)scale & 3) return fail("cfg_combine: scale must be 4-byte aligned");
+  const char *pn = (const char*)v_neg, *pp = (const char*)v_pos, *po = (const char*)out, *ps = (const char*)scale;
+  const int64_t bytes = nch * 16;
+  if (po < pp + bytes && pp < po + bytes) return fail("cfg_combine: out must not overlap v_pos");
+  if (po != pn && po < pn + bytes && pn < po + bytes) return fail("cfg_combine: out must be v_neg itself or not overlap it");
+  if (ps < po + bytes && po < ps + 4) return fail("cfg_combine: scale must not lie in out");
+  cfg_combine_kernel<<<dim3((unsigned)((nch + 255) / 256)), 256, 0, st>>>((const bf16_t*)v_neg, (const bf16_t*)v_pos, (bf16_t*)out, nch, scale);
+  return check_launch("cfg_combine");
 }
 
 // The one launcher of the two blends: `who` is the declared function's name.  A TensorMask's mask is a third [rows, C] bf16 operand

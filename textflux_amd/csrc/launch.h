@@ -202,6 +202,9 @@ int known_region_blend(void* x, int64_t ldx, const void* x0, const void* noise, 
 // (hold u8 [rows, 4], cut int32 [n_steps]); x <- p k + x (1 - k), bf16 per op; cut[step] >= 255 leaves x unwritten (xin still mirrored)
 int change_map_blend(void* x, int64_t ldx, const void* x0, const void* noise, const void* hold, const int* cut, int C, int64_t rows,
                      const float* keep_sigma, const int* step_ptr, int step, void* xin, int64_t ldxin, hipStream_t st);
+// true CFG in front of a sampler update: out <- neg + g (pos - neg), bf16 per op, g = *scale read on the device; v_neg, v_pos, out
+// bf16 [rows, C] contiguous, out may be v_neg itself
+int cfg_combine(const void* v_neg, const void* v_pos, void* out, int C, int64_t rows, const float* scale, hipStream_t st);
 int timestep_embedding(const float* t, void* out, int n, hipStream_t st);
 int silu_bf16(const void* a, void* out, int64_t n, hipStream_t st);
 int add_bf16(const void* a, const void* b, void* out, int64_t n, hipStream_t st);

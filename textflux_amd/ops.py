@@ -481,6 +481,28 @@ def change_map_blend(x: torch.Tensor, x0: torch.Tensor, noise: torch.Tensor, hol
     return x
 
 
+def cfg_combine(v_neg: torch.Tensor, v_pos: torch.Tensor, scale: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """out <- v_neg + scale * (v_pos - v_neg), one bf16 rounding per op as the reference's tensor ops with a Python float
+    (tfx_cfg_combine; true CFG, pipeline_flux_with_cfg.py:808).  v_neg / v_pos bf16 [.., rows, C], contiguous and of one shape; scale:
+    a DEVICE fp32 tensor of one element, read when the kernel runs; out: None (a new tensor), v_neg itself (in place) or a contiguous
+    tensor of the same shape that overlaps neither input."""
+    _chk_dev(v_neg, v_pos, scale, out)
+    if out is None:
+        out = torch.empty_like(v_neg)
+    if any(t.dtype != BF16 for t in (v_neg, v_pos, out)):
+        raise TypeError("cfg_combine: bf16 model outputs")
+    if scale.dtype != torch.float32 or scale.numel() != 1:
+        raise TypeError("cfg_combine: scale is a device fp32 tensor of one element")
+    if v_neg.dim() < 1 or not (v_neg.shape == v_pos.shape == out.shape):
+        raise ValueError("cfg_combine: v_neg, v_pos and out must be of one shape")
+    if not (v_neg.is_contiguous() and v_pos.is_contiguous() and out.is_contiguous()):
+        raise ValueError("cfg_combine: v_neg, v_pos and out must be contiguous")
+    Cc = v_neg.shape[-1]
+    rows = v_neg.numel() // Cc if Cc else 0
+    L.check(L.lib().tfx_cfg_combine(v_neg.data_ptr(), v_pos.data_ptr(), out.data_ptr(), Cc, rows, scale.data_ptr(), _stream()), "cfg_combine")
+    return out
+
+
 def timestep_embedding(t: torch.Tensor) -> torch.Tensor:
     _chk_dev(t)
     t = t.contiguous().float()

@@ -3,7 +3,7 @@ reference class (diffusers/src/diffusers/pipelines/flux/pipeline_flux_fill.py:13
 `run_inference.py`-style callers can switch by changing one import.
 
 What is different underneath:
-* the denoising loop (step_loop.py) never re-enters Python-level model code: per step it is ONE `tfx_dit_step_run_ex2`, or the
+* the denoising loop (step_loop.py) never re-enters Python-level model code: per step it is ONE `tfx_dit_step_run_ex3`, or the
   replay of the graph captured from it -- the forward and a scheduler update that also writes the new latents into the next
   x_embedder input (no torch.cat per step, P:2085);
 * context projection, RoPE tables and the time/guidance/pooled embedding -> AdaLN modulation of ALL steps are computed
@@ -168,6 +168,12 @@ def _change_map_cfg(change_map):
     if out["dilate"] < 0 or out["feather"] < 0:
         raise ValueError("change_map: dilate and feather must be >= 0")
     return out
+
+
+def _true_cfg_on(true_cfg, negative_prompt, negative_prompt_embeds) -> bool:
+    """True CFG runs when true_cfg > 1 and a negative prompt OR negative embeds are given.  The reference looks at the string alone
+    (pipeline_flux_with_cfg.py:714), so negative embeds without a string silently switch it off there; here both count."""
+    return true_cfg > 1 and (negative_prompt is not None or negative_prompt_embeds is not None)
 
 
 class FluxFillPipeline:
@@ -525,8 +531,10 @@ class FluxFillPipeline:
 
     def check_inputs(self, prompt, prompt_2, height, width, prompt_embeds=None, pooled_prompt_embeds=None,
                      callback_on_step_end_tensor_inputs=None, max_sequence_length=None, image=None, mask_image=None,
-                     masked_image_latents=None):
-        """P:1665-1724 (same conditions, same exception type)."""
+                     masked_image_latents=None, negative_prompt=None, negative_prompt_2=None, negative_prompt_embeds=None,
+                     negative_pooled_prompt_embeds=None):
+        """P:1665-1724 (same conditions, same exception type); the negative_* conditions are FluxCFGPipeline.check_inputs'
+        (D/examples/community/pipeline_flux_with_cfg.py:435-460)."""
         if callback_on_step_end_tensor_inputs is not None and not all(
                 k in self._callback_tensor_inputs for k in callback_on_step_end_tensor_inputs):
             raise ValueError(f"`callback_on_step_end_tensor_inputs` has to be in {self._callback_tensor_inputs}, but found "
@@ -541,8 +549,23 @@ class FluxFillPipeline:
             raise ValueError(f"`prompt` has to be of type `str` or `list` but is {type(prompt)}")
         elif prompt_2 is not None and (not isinstance(prompt_2, str) and not isinstance(prompt_2, list)):
             raise ValueError(f"`prompt_2` has to be of type `str` or `list` but is {type(prompt_2)}")
+        if negative_prompt is not None and negative_prompt_embeds is not None:
+            raise ValueError(f"Cannot forward both `negative_prompt`: {negative_prompt} and `negative_prompt_embeds`:"
+                             f" {negative_prompt_embeds}. Please make sure to only forward one of the two.")
+        elif negative_prompt_2 is not None and negative_prompt_embeds is not None:
+            raise ValueError(f"Cannot forward both `negative_prompt_2`: {negative_prompt_2} and `negative_prompt_embeds`:"
+                             f" {negative_prompt_embeds}. Please make sure to only forward one of the two.")
+        if prompt_embeds is not None and negative_prompt_embeds is not None:
+            if prompt_embeds.shape != negative_prompt_embeds.shape:
+                raise ValueError("`prompt_embeds` and `negative_prompt_embeds` must have the same shape when passed directly, but"
+                                 f" got: `prompt_embeds` {prompt_embeds.shape} != `negative_prompt_embeds`"
+                                 f" {negative_prompt_embeds.shape}.")
         if prompt_embeds is not None and pooled_prompt_embeds is None:
             raise ValueError("If `prompt_embeds` are provided, `pooled_prompt_embeds` also have to be passed.")
+        if negative_prompt_embeds is not None and negative_pooled_prompt_embeds is None:
+            raise ValueError("If `negative_prompt_embeds` are provided, `negative_pooled_prompt_embeds` also have to be passed. Make sure to "
+                             "generate `negative_pooled_prompt_embeds` from the same text encoder that was used to generate "
+                             "`negative_prompt_embeds`.")
         if max_sequence_length is not None and max_sequence_length > 512:
             raise ValueError(f"`max_sequence_length` cannot be greater than 512 but is {max_sequence_length}")
         if image is not None and masked_image_latents is not None:
@@ -580,29 +603,41 @@ class FluxFillPipeline:
         return modx
 
     def _engine_loop(self, latents, masked_image_latents, prompt_embeds, pooled, text_ids, latent_image_ids, timesteps,
-                     guidance_scale, callback_on_step_end, callback_tensor_inputs, amo_noise, progress_bar, keep=None):
+                     guidance_scale, callback_on_step_end, callback_tensor_inputs, amo_noise, progress_bar, keep=None, cfg=None):
         """Session, conditioning, modulation table, x_embedder input, then the step loop (step_loop.denoise).  The loop starts at
         step 0 of `timesteps`: _call_body sets the timesteps directly in front of it, which clears the scheduler's begin_index --
         unless the call gave `strength` / `keep_known`: then get_timesteps set it, `timesteps` and the scheduler's tables start at that
         step, and `keep` (dict x0 / noise / mask, or x0 / noise alone for a strength-only call) goes to the loop's blend; with hold
-        and last in place of mask (`change_map`) it becomes the loop's `change`, with the cut table of the steps that run."""
+        and last in place of mask (`change_map`) it becomes the loop's `change`, with the cut table of the steps that run.
+        cfg: true CFG -- dict(scale, prompt_embeds, pooled), the negative conditioning of the B samples: the
+        session then has 2B samples, its conditioning and the pooled rows of the modulation table are [negative; positive] (the
+        reference's torch.cat, pipeline_flux_with_cfg.py:739-740), both halves of its xin hold the same [latents |
+        masked_image_latents] rows, and Euler runs unfused; the loop state (latents, keep, amo_noise) keeps B samples."""
         tr, sch = self.transformer, self.scheduler
         dev = tr.device
         B, S, C = latents.shape
         n = len(timesteps)
-        ses = tr.session(B, S, prompt_embeds.shape[1])
-        ses.set_conditioning(prompt_embeds.to(dev, BF16), text_ids, latent_image_ids)
+        both = lambda neg, pos: pos if cfg is None else torch.cat((neg.to(pos.device, pos.dtype), pos), dim=0)
+        cond = lambda pe: both(cfg["prompt_embeds"], pe) if cfg is not None else pe
+        Bs = B if cfg is None else 2 * B
+        ses = tr.session(Bs, S, prompt_embeds.shape[1])
+        ses.set_conditioning(cond(prompt_embeds).to(dev, BF16), text_ids, latent_image_ids)
+        halves = (ses.xin,) if cfg is None else (ses.xin[:B], ses.xin[B:])      # sample B + b mirrors sample b
         is_amo = isinstance(sch, StochasticRFOvershotDiscreteScheduler)
         multistep = isinstance(sch, FlowMatchMultistepScheduler)    # unfused: its [n, 2] table, the history in the session
         coef = sch.coef_table(dev, BF16)
         # Euler update in proj_out's epilogue (north_star: "flow-matching Euler step fused into the residual add"); the latents then
         # live in xin[:, :, :C].  Not with a step callback (it wants the latents as a tensor every step) and not for AMO.
-        fuse = self.fuse_euler_step and not is_amo and not multistep and callback_on_step_end is None and C == EULER_PAD and tr.out_channels == C
-        mod = self._modulation_table(timesteps, B, pooled, guidance_scale, coef[:n] if fuse else None)
+        fuse = (self.fuse_euler_step and not is_amo and not multistep and callback_on_step_end is None and C == EULER_PAD
+                and tr.out_channels == C and cfg is None)        # the fused epilogue would update each half of a CFG batch on its own
+        mod = self._modulation_table(timesteps, Bs, pooled if cfg is None else both(cfg["pooled"], pooled), guidance_scale,
+                                     coef[:n] if fuse else None)
         # x_embedder input [latents | masked_image_latents]; the step keeps columns 0..C-1 up to date
         latents = latents.to(dev, BF16).contiguous()
-        ops.scatter_cols_(latents, ses.xin, 0)
-        ops.scatter_cols_(masked_image_latents.to(dev, BF16).contiguous(), ses.xin, C)
+        mil = masked_image_latents.to(dev, BF16).contiguous()
+        for xin in halves:
+            ops.scatter_cols_(latents, xin, 0)
+            ops.scatter_cols_(mil, xin, C)
         on_step = None
         if callback_on_step_end is not None:
             def on_step(i, lat):     # lat: the live latents; what the callback returns goes back into the loop's state
@@ -612,11 +647,12 @@ class FluxFillPipeline:
                 new_lat = out.pop("latents", lat)
                 if new_lat is not lat:
                     lat.copy_(new_lat.to(dev, BF16))
-                    ops.scatter_cols_(lat, ses.xin, 0)
+                    for xin in halves:
+                        ops.scatter_cols_(lat, xin, 0)
                 new_pe = out.pop("prompt_embeds", prompt_embeds)
                 if new_pe is not prompt_embeds:
                     prompt_embeds = new_pe
-                    ses.set_conditioning(prompt_embeds.to(dev, BF16), text_ids, latent_image_ids)
+                    ses.set_conditioning(cond(prompt_embeds).to(dev, BF16), text_ids, latent_image_ids)
         sch._step_index = sch.begin_index or 0
         change = None
         if keep is not None and "hold" in keep:
@@ -627,7 +663,8 @@ class FluxFillPipeline:
             keep = dict(keep, sigma=sch.keep_sigma_table(dev, BF16))
         else:
             keep = None
-        return step_loop.denoise(self, ses, mod, latents, coef, n, progress_bar, is_amo, fuse, amo_noise, on_step, multistep, keep, change)
+        return step_loop.denoise(self, ses, mod, latents, coef, n, progress_bar, is_amo, fuse, amo_noise, on_step, multistep,
+                                 cfg=None if cfg is None else cfg["scale"], keep=keep, change=change)
 
     # ------------------------------------------------------------------ known-region sampling
     def get_timesteps(self, num_inference_steps, strength, device):
@@ -905,7 +942,10 @@ class FluxFillPipeline:
                  callback_on_step_end: Optional[Callable] = None,
                  callback_on_step_end_tensor_inputs: List[str] = ["latents"], max_sequence_length: int = 512,
                  amo_noise: Optional[List[torch.Tensor]] = None, output_crop=None, strength: float = 1.0, keep_known=None,
-                 image_latents: Optional[torch.Tensor] = None, change_map=None):
+                 image_latents: Optional[torch.Tensor] = None, change_map=None,
+                 negative_prompt: Optional[Union[str, List[str]]] = None, negative_prompt_2: Optional[Union[str, List[str]]] = None,
+                 negative_prompt_embeds: Optional[torch.Tensor] = None, negative_pooled_prompt_embeds: Optional[torch.Tensor] = None,
+                 true_cfg: float = 1.0):
         """Same arguments / defaults / return as the reference `__call__` (P:1850-1873, 2122-2137).  Additions:
         `amo_noise`, a list of pre-drawn eps tensors for the AMO sampler (replay across devices), and
         `output_crop` = (left, top, right, bottom), the callers' result crop (run_inference.py:460-465) applied on the
@@ -921,7 +961,16 @@ class FluxFillPipeline:
         `map` it is feather(dilate(mask_image >= 128)), the paste-back's alpha.  A pixel is held to the noised original while its
         map value lies below the loop's progress; last="keep" (default) ends held pixels as the original's latents, "free" is the
         reference, whose last step belongs to the model.  Not with `keep_known`; with `strength` / `image_latents` as `keep_known`.
-        The Fill model's own conditioning still comes from the binary `mask_image`."""
+        The Fill model's own conditioning still comes from the binary `mask_image`.
+        True CFG (FluxCFGPipeline's loop, D/examples/community/pipeline_flux_with_cfg.py:714-812, on the Fill
+        model, opt-in, no quality claim): `negative_prompt` / `negative_prompt_2` or `negative_prompt_embeds` +
+        `negative_pooled_prompt_embeds`, with the reference's checks, and `true_cfg`.  It is on when true_cfg > 1 and a negative
+        prompt OR negative embeds are given -- the reference looks at the string alone, so embeds without a string silently switch
+        it off there; here both count.  One negative string serves every sample of the batch.  Every step is then one forward over
+        [negative; positive] and noise_pred = neg + true_cfg * (pos - neg) in front of the sampler update, at about twice the cost
+        of a plain step.  Works with fp8 linears, runtime LoRA, `strength`, `keep_known`, `change_map`, all three engine
+        schedulers, eager and graphs; refused (NotImplementedError) with the step cache and with a foreign scheduler object.  Off,
+        the call is today's call."""
         if strength < 0 or strength > 1:
             raise ValueError(f"The value of strength should in [0.0, 1.0] but is {strength}")
         if _change_map_cfg(change_map) is not None and _keep_known_cfg(keep_known) is not None:
@@ -932,7 +981,16 @@ class FluxFillPipeline:
                           pooled_prompt_embeds=pooled_prompt_embeds,
                           callback_on_step_end_tensor_inputs=callback_on_step_end_tensor_inputs,
                           max_sequence_length=max_sequence_length, image=image, mask_image=mask_image,
-                          masked_image_latents=masked_image_latents)
+                          masked_image_latents=masked_image_latents, negative_prompt=negative_prompt,
+                          negative_prompt_2=negative_prompt_2, negative_prompt_embeds=negative_prompt_embeds,
+                          negative_pooled_prompt_embeds=negative_pooled_prompt_embeds)
+        negative = None
+        if _true_cfg_on(true_cfg, negative_prompt, negative_prompt_embeds):
+            if self._step_cache is not None:
+                raise NotImplementedError("true CFG does not run with the step cache (its metric would mix the two conditionings); "
+                                          "call disable_step_cache() or leave negative_prompt / true_cfg out")
+            negative = dict(scale=float(true_cfg), prompt=negative_prompt, prompt_2=negative_prompt_2, prompt_embeds=negative_prompt_embeds,
+                            pooled_prompt_embeds=negative_pooled_prompt_embeds)
         self._guidance_scale, self._joint_attention_kwargs, self._interrupt = guidance_scale, joint_attention_kwargs, False
         runtime_lora = bool(getattr(self.transformer, "_adapters", None))
         if joint_attention_kwargs is not None and joint_attention_kwargs.get("scale", 1.0) != 1.0 and not runtime_lora:
@@ -948,7 +1006,7 @@ class FluxFillPipeline:
                                    sigmas, guidance_scale, num_images_per_prompt, generator, latents, prompt_embeds,
                                    pooled_prompt_embeds, output_type, return_dict, callback_on_step_end,
                                    callback_on_step_end_tensor_inputs, max_sequence_length, amo_noise, output_crop, strength,
-                                   keep_known, image_latents, change_map)
+                                   keep_known, image_latents, change_map, negative)
         finally:
             if lora_scale is not None:
                 self.transformer._write_scales(prev_lora_scale)
@@ -1088,7 +1146,7 @@ class FluxFillPipeline:
     def _call_body(self, prompt, prompt_2, image, mask_image, masked_image_latents, height, width, num_inference_steps, sigmas,
                    guidance_scale, num_images_per_prompt, generator, latents, prompt_embeds, pooled_prompt_embeds, output_type,
                    return_dict, callback_on_step_end, callback_on_step_end_tensor_inputs, max_sequence_length, amo_noise, output_crop,
-                   strength=1.0, keep_known=None, image_latents=None, change_map=None):
+                   strength=1.0, keep_known=None, image_latents=None, change_map=None, negative=None):
         if prompt is not None and isinstance(prompt, str):
             batch_size = 1
         elif prompt is not None and isinstance(prompt, list):
@@ -1099,6 +1157,23 @@ class FluxFillPipeline:
         prompt_embeds, pooled_prompt_embeds, text_ids = self.encode_prompt(
             prompt=prompt, prompt_2=prompt_2, prompt_embeds=prompt_embeds, pooled_prompt_embeds=pooled_prompt_embeds,
             device=device, num_images_per_prompt=num_images_per_prompt, max_sequence_length=max_sequence_length)
+        cfg = None
+        if negative is not None:      # the negatives go through the same encode_prompt (the prompt cache serves them)
+            total = batch_size * num_images_per_prompt
+            neg = negative["prompt"]
+            if isinstance(neg, list) and len(neg) not in (1, batch_size):
+                raise ValueError(f"Negative prompt batch size ({len(neg)}) does not match prompt batch size ({batch_size})")
+            neg_pe, neg_pooled, _ = self.encode_prompt(
+                prompt=neg, prompt_2=negative["prompt_2"], prompt_embeds=negative["prompt_embeds"],
+                pooled_prompt_embeds=negative["pooled_prompt_embeds"], device=device, num_images_per_prompt=num_images_per_prompt,
+                max_sequence_length=max_sequence_length)
+            if neg_pe.shape[0] != total:        # one negative prompt for the whole batch
+                neg_pe = _repeat_to_batch(neg_pe, total, "negative prompt embeds")
+                neg_pooled = _repeat_to_batch(neg_pooled, total, "negative pooled prompt embeds")
+            if neg_pe.shape != prompt_embeds.shape or neg_pooled.shape != pooled_prompt_embeds.shape:
+                raise ValueError(f"true CFG: the negative embeddings {tuple(neg_pe.shape)} / {tuple(neg_pooled.shape)} must have the shapes of "
+                                 f"the positive ones {tuple(prompt_embeds.shape)} / {tuple(pooled_prompt_embeds.shape)}")
+            cfg = dict(scale=negative["scale"], prompt_embeds=neg_pe, pooled=neg_pooled)
         num_channels_latents = self.vae.config.latent_channels
         keep_cfg = _keep_known_cfg(keep_known)
         change_cfg = _change_map_cfg(change_map)
@@ -1127,6 +1202,8 @@ class FluxFillPipeline:
         timesteps, num_inference_steps = retrieve_timesteps(self.scheduler, num_inference_steps, device, sigmas=sigmas, mu=mu)
         engine = isinstance(self.scheduler, (FlowMatchEulerDiscreteScheduler, StochasticRFOvershotDiscreteScheduler, FlowMatchMultistepScheduler))
         keep = None
+        if cfg is not None and not engine:
+            raise NotImplementedError("true CFG needs one of the engine's schedulers (their step loop holds the combine)")
         if known:
             if not engine:
                 raise NotImplementedError("strength / keep_known / change_map need one of the engine's schedulers (their step loop holds the blend)")
@@ -1139,9 +1216,15 @@ class FluxFillPipeline:
         self._num_timesteps = len(timesteps)
         with self.progress_bar(total=num_inference_steps) as bar:
             if engine:
-                latents = self._engine_loop(latents, masked_image_latents, prompt_embeds, pooled_prompt_embeds, text_ids,
-                                            latent_image_ids, timesteps, guidance_scale, callback_on_step_end,
-                                            callback_on_step_end_tensor_inputs, amo_noise, bar, keep)
+                try:
+                    latents = self._engine_loop(latents, masked_image_latents, prompt_embeds, pooled_prompt_embeds, text_ids,
+                                                latent_image_ids, timesteps, guidance_scale, callback_on_step_end,
+                                                callback_on_step_end_tensor_inputs, amo_noise, bar, keep, cfg)
+                except RuntimeError as e:
+                    if cfg is None or isinstance(e, NotImplementedError):
+                        raise
+                    raise RuntimeError(f"{e}\n(true CFG runs every step on a session of {2 * latents.shape[0]} samples, [negative; positive]: "
+                                       f"where that is larger than the engine takes, halve the batch)") from e
             else:
                 guidance = None
                 if self.transformer.config.guidance_embeds:

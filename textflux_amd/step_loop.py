@@ -1,8 +1,10 @@
-"""The engine's denoising loop, once: n steps of tfx_dit_step_run_ex2 -- or of the replay of the graph captured
+"""The engine's denoising loop, once: n steps of tfx_dit_step_run_ex3 -- or of the replay of the graph captured
 from it -- for the plain loop (phase 0) and the step cache (phases 1, 2 / 3), the Euler, AMO, fused-Euler and multistep samplers (the
 last by the history buffer in the step's tfx_step_extra), with or without a step callback, on uniform and mixed-geometry sessions; with
 the known-region blend behind every sampler update (the tfx_step_extra's keep_* buffers) when the call keeps the known region, or the
-change-map blend (a tfx_step_change beside it) when the call gives every latent pixel its own release step.
+change-map blend (a tfx_step_change beside it) when the call gives every latent pixel its own release step; with true CFG (a
+tfx_step_cfg beside those) when the call carries a negative prompt: the session is then twice the loop state's batch.  Without a
+tfx_step_cfg the _ex3 pair is exactly tfx_dit_step_run_ex2 / tfx_dit_step_capture_ex2.
 
 `run_steps` is the control flow and touches no device: it drives a `steps` object with
     feed_noise(i)   run(phase)   replay(handle)   capture(phase) -> handle (raises CaptureRefused)   destroy(handle)
@@ -84,7 +86,7 @@ def run_steps(steps, n, pipe, progress_bar, graphs, key, decider=None, use_graph
 class SessionSteps:
     """run_steps' device operations on a DitSession: its persistent step buffers `gb`, one tfx_step_desc per phase, stream `side`."""
 
-    def __init__(self, ses, gb, side, phases, is_amo, fuse, amo_noise, multistep=False, keep=False, change=False):
+    def __init__(self, ses, gb, side, phases, is_amo, fuse, amo_noise, multistep=False, keep=False, change=False, cfg=False):
         self.ses, self.gb, self.side, self.st, self.lib = ses, gb, side, side.cuda_stream, L.lib()
         self.sd = {ph: ses.step_desc(gb, is_amo, fuse, phase=ph) for ph in phases}
         self.is_amo, self.amo_noise = is_amo, amo_noise
@@ -101,27 +103,31 @@ class SessionSteps:
             self.extra.keep_mask = ptr("known_mask")
         if change:
             self.change = L.StepChange(hold=ptr("known_hold"), cut=ptr("known_cut"))
-        self.args = {ph: (C.byref(sd), C.byref(self.extra), C.byref(self.change) if change else None) for ph, sd in self.sd.items()}
+        # true CFG: the scale's address (the value is rewritten every call); the per-sample buffers are then the first half of gb's
+        self.cfg = L.StepCfg(scale=ptr("cfg_scale")) if cfg else None
+        self.noise = gb["noise"][:ses.B // 2] if cfg else gb["noise"]
+        self.args = {ph: (C.byref(sd), C.byref(self.extra), C.byref(self.change) if change else None, C.byref(self.cfg) if cfg else None)
+                     for ph, sd in self.sd.items()}
         # what a failing step is reported as: the entry point of the C ABI that stands for this loop
-        self.what = "dit_step_run" + ("_ex2" if change else "_ex" if keep else "_multistep" if multistep else "")
+        self.what = "dit_step_run" + ("_ex3" if cfg else "_ex2" if change else "_ex" if keep else "_multistep" if multistep else "")
 
     def feed_noise(self, i):
         if not self.is_amo:
             return
         if self.amo_noise is None:
-            self.gb["noise"].normal_()      # global device RNG, as the reference's randn_tensor(generator=None); never captured
+            self.noise.normal_()            # global device RNG, as the reference's randn_tensor(generator=None); never captured
         else:
-            self.gb["noise"].copy_(self.amo_noise[i].to(self.gb["noise"].device, torch.float32))
+            self.noise.copy_(self.amo_noise[i].to(self.noise.device, torch.float32))
 
     def run(self, ph):
-        L.check(self.lib.tfx_dit_step_run_ex2(*self.args[ph], self.st), self.what)
+        L.check(self.lib.tfx_dit_step_run_ex3(*self.args[ph], self.st), self.what)
 
     def replay(self, handle):
         L.check(self.lib.tfx_dit_step_replay(handle, self.st), "dit_step_replay")
 
     def capture(self, ph):
         h = C.c_void_p()
-        if self.lib.tfx_dit_step_capture_ex2(*self.args[ph], self.st, C.byref(h)) != 0:
+        if self.lib.tfx_dit_step_capture_ex3(*self.args[ph], self.st, C.byref(h)) != 0:
             raise CaptureRefused(self.lib.tfx_last_error().decode())
         return h.value
 
@@ -148,7 +154,7 @@ class SessionSteps:
 
 
 def denoise(pipe, ses, mod, latents, coef, n, progress_bar, is_amo=False, fuse=False, amo_noise=None, on_step=None, multistep=False,
-            keep=None, change=None):
+            cfg=None, keep=None, change=None):
     """The n steps of one engine call on session `ses`, whose xin holds [latents | masked_image_latents] and whose conditioning is
     set.  mod [n, B, mod_len (+ EULER_PAD when fuse)]: the modulation table.  latents [B, S, C] and coef, the sampler's coefficient
     table, may be None when fuse: the fused step reads the latents from xin and its coefficients from `mod`.  on_step(i, lat): the
@@ -160,18 +166,31 @@ def denoise(pipe, ses, mod, latents, coef, n, progress_bar, is_amo=False, fuse=F
     change-map sampling -- dict(x0, noise: bf16 [B, S, C]; hold: uint8 [B, S, 4]; sigma: fp32 [n]; cut: int32 [n],
     schedulers.change_cut_table): the same blend with the mask decided inside the step, held where hold > cut[step]
     (tfx_change_map_blend); not together with keep.  Either one's buffers live in the session next to v_prev, because captured graphs
-    bake their addresses.  Runs on the session's side
+    bake their addresses.  cfg: true CFG -- the scale g of noise_pred = neg + g (pos - neg); `ses` is then a session
+    of 2B samples whose conditioning and modulation rows are [negative; positive] and whose xin holds the same rows in both halves, while
+    latents, amo_noise, keep and change have B samples (they live in the first half of the session's buffers: the addresses are the
+    same ones, whatever the call).  The scale lives in the session too and is rewritten every call: a captured graph serves every g.
+    Unfused samplers only, not with the step cache, not on mixed sessions.  Runs on the session's side
     stream (capture needs a non-NULL stream), fenced against the caller's current stream on both sides.  The step cache is on when
     pipe.enable_step_cache() is in force; graphs when pipe.enable_hip_graph(True), no callback and n > 1.  Returns the final
     latents and leaves pipe.step_cache_report set."""
     dev = ses.xin.device
     shape = (ses.B, ses.S, ses.model.out_channels)
     gb = ses.graph_buffers(n, 0 if coef is None else coef.numel(), shape)
+    state = lambda t: t                     # the loop state's samples of a per-sample session buffer
+    if cfg is not None:
+        if fuse or ses.mixed or ses.B % 2:
+            raise ValueError("true CFG needs an unfused sampler and a uniform session of 2B samples")
+        if pipe._step_cache is not None:
+            raise NotImplementedError("true CFG does not run with the step cache: the cache's metric would mix the two conditionings")
+        state = lambda t: t[:ses.B // 2]
+        if "cfg_scale" not in gb:           # lives and dies with gb: captured graphs bake its address
+            gb["cfg_scale"] = torch.ones(1, dtype=torch.float32, device=dev)
     gb["mod_table"][:n, :, :mod.shape[2]].copy_(mod)
     if coef is not None:
         gb["coef"][:coef.numel()].copy_(coef.reshape(-1))
     if latents is not None:
-        gb["lat"].copy_(latents)
+        state(gb["lat"]).copy_(latents)
     gb["step"].zero_()
     if multistep:
         assert not is_amo and not fuse and latents is not None
@@ -189,7 +208,7 @@ def denoise(pipe, ses, mod, latents, coef, n, progress_bar, is_amo=False, fuse=F
         for k in ("x0", "noise", "mask" if keep is not None else "hold"):             # per token
             if "known_" + k not in gb:
                 gb["known_" + k] = torch.empty(*shape[:2], 4, dtype=torch.uint8, device=dev) if k == "hold" else torch.empty_like(gb["lat"])
-            gb["known_" + k].copy_(known[k])
+            state(gb["known_" + k]).copy_(known[k])
         per_step = {"sigma": torch.float32} if keep is not None else {"sigma": torch.float32, "cut": torch.int32}
         for k, dtype in per_step.items():                                             # as long as the session's longest schedule
             assert known[k].numel() == n and known[k].dtype == dtype
@@ -204,17 +223,21 @@ def denoise(pipe, ses, mod, latents, coef, n, progress_bar, is_amo=False, fuse=F
     side = ses.graph_stream()
     side.wait_stream(cur)
     with torch.cuda.stream(side):
+        if cfg is not None:
+            gb["cfg_scale"].fill_(float(cfg))
         steps = SessionSteps(ses, gb, side, (0,) if decider is None else (1, 2, 3), is_amo, fuse, amo_noise, multistep, keep is not None,
-                             change is not None)
+                             change is not None, cfg is not None)
         ses._mod_keepalive = gb["mod_cur"]
         key = ("multistep", False) if multistep else (is_amo, fuse)
         if keep is not None:
             key += ("keep",)
         if change is not None:
             key += ("change",)
+        if cfg is not None:
+            key += ("cfg",)
         run_steps(steps, n, pipe, progress_bar, ses.graphs, key, decider, use_graph=pipe._use_hip_graph,
-                  callback=None if on_step is None else lambda i: on_step(i, gb["lat"]))
-        out = ops.copy_rows_(ses.xin[:, :, :shape[2]], torch.empty(shape, dtype=BF16, device=dev)) if fuse else gb["lat"].clone()
+                  callback=None if on_step is None else lambda i: on_step(i, state(gb["lat"])))
+        out = ops.copy_rows_(ses.xin[:, :, :shape[2]], torch.empty(shape, dtype=BF16, device=dev)) if fuse else state(gb["lat"]).clone()
     out.record_stream(cur)
     cur.wait_stream(side)
     pipe.step_cache_report = decider.report if decider is not None else None

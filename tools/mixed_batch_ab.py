@@ -103,13 +103,13 @@ def main():
 
     transformer.DitSession.__init__ = init1
     lib = L.lib()
-    cap0 = lib.tfx_dit_step_capture_ex2
+    cap0 = lib.tfx_dit_step_capture_ex3
 
-    class _Lib:       # the pipeline's graph loop calls lib.tfx_dit_step_capture_ex2: count it on the way through
+    class _Lib:       # the pipeline's graph loop calls lib.tfx_dit_step_capture_ex3: count it on the way through
         def __getattr__(self, name):
             return getattr(lib, name)
 
-        def tfx_dit_step_capture_ex2(self, *args):
+        def tfx_dit_step_capture_ex3(self, *args):
             counts["captures"] += 1
             return cap0(*args)
 
