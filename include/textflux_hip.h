@@ -888,6 +888,58 @@ int tfx_add_into_f32(float* x, const void* y, int64_t n, int32_t mode, tfx_strea
 int tfx_mul_act(const void* a, int64_t lda, const void* b, int64_t ldb, void* out, int64_t ldo, int64_t rows, int32_t cols,
                 int32_t mode, tfx_stream stream);
 
+/* ---- read-back: the text recogniser that scores what an edit wrote (eval/recognizer.py + eval/ocr_recog of the reference: a
+ *      MobileNetV1Enhance backbone, a two-block SVTR neck, a CTC head) and the CTC decode / loss behind it (ocr.hip; DESIGN.md §4
+ *      "Read-back").  Activations are fp32 NHWC with the channels contiguous; weights are fp32 with BatchNorm folded in by the caller.
+ *      No floating-point atomics: two runs give the same bits.  act: 0 none, 1 relu, 2 hard-swish (x * relu6(x + 3)) / 6, 3 hard-sigmoid
+ *      relu6(x + 3) / 6 (both with an IEEE division), 4 swish x * (1 / (1 + exp(-x))). ---- */
+/* TextRecognizer.resize_norm_img for n line crops in ONE launch: crop i is u8 [h, w, 3] at src + table[i][0], table = device int32
+ * [n][4] = {byte offset, h, w, turn}; src_bytes is the size of the packed buffer (an entry that leaves it, or has h or w < 1, writes
+ * zeros and reads nothing).  turn != 0 reads the crop through the reference's quarter turn (transpose(1, 2).flip(dims=[1]): turned
+ * pixel (r, c) = source pixel (c, w - 1 - r)).  out fp32 [n, img_h, img_w, 3]: bilinear with align_corners = True to
+ * (img_h, resized_w), resized_w = min(img_w, ceil(img_h * w / h)) of the turned size in fp64, then (v / 255 - 0.5) / 0.5; the
+ * columns >= resized_w are 0.0. */
+int tfx_ocr_resize_norm(const void* src, int64_t src_bytes, const int32_t* table, float* out, int32_t n, int32_t img_h, int32_t img_w,
+                        tfx_stream stream);
+/* Dense convolution as an implicit GEMM on v_mfma_f32_16x16x4_f32 (exact f32 products and sums): x [B, H, W, Cin] with pixel pitch
+ * ldx floats, w [Cout][ksize][ksize][Cin], bias [Cout] or NULL, ksize 1 or 3, padding ksize / 2, strides >= 1; pixel p of the
+ * [B, Ho, Wo] output grid writes out[p * ldo + co_off + n] = act(sum + bias[n]) for n < Cout, so a result can land in a column range of
+ * a wider buffer.  A linear [M, K] -> [M, N] is B = M, H = W = 1, ksize = 1.  The sum over k = (ky, kx, ci) is taken in 16-wide chunks:
+ * chunk c goes to partial sum c % 4, inside a chunk the products are added in the order k = j, 4 + j, 8 + j, 12 + j for j = 0 .. 3 (one
+ * fmaf each), and the four partial sums are added in rising order; taps outside the image add 0. */
+int tfx_ocr_conv_f32(const float* x, const float* w, const float* bias, float* out, int32_t B, int32_t H, int32_t W, int32_t Cin, int32_t Cout,
+                     int32_t ksize, int32_t stride_h, int32_t stride_w, int32_t act, int64_t ldx, int64_t ldo, int32_t co_off, tfx_stream stream);
+/* Depthwise convolution: x [B, H, W, C] contiguous, w [ksize][ksize][C], bias [C] or NULL, ksize 3 or 5, padding ksize / 2, strides 1
+ * or 2 each, act 0 or 2; C % 4 == 0 and 16-byte aligned pointers.  One fmaf per tap in (ky, kx) order; taps outside the image are
+ * skipped (the padding may be wider than the image). */
+int tfx_ocr_conv_dw(const float* x, const float* w, const float* bias, float* out, int32_t B, int32_t H, int32_t W, int32_t C, int32_t ksize,
+                    int32_t stride_h, int32_t stride_w, int32_t act, tfx_stream stream);
+/* mode 0: out [B, C] = the sum over (h, w) in row-major order, then ONE division by H * W (nn.AdaptiveAvgPool2d(1));
+ * mode 1: out [B, H / 2, W / 2, C] with pixel pitch ldo = ((x00 + x01) + (x10 + x11)) * 0.25 (nn.AvgPool2d(2, 2)). */
+int tfx_ocr_pool(const float* x, float* out, int32_t B, int32_t H, int32_t W, int32_t C, int32_t mode, int64_t ldo, tfx_stream stream);
+/* out[b, p, c] = x[b, p, c] * s[b, c] for p < HW (the squeeze-excite product); C % 4 == 0, 16-byte aligned pointers; out may be x. */
+int tfx_ocr_scale_channels(const float* x, const float* s, float* out, int32_t B, int64_t HW, int32_t C, tfx_stream stream);
+/* nn.LayerNorm on fp32 rows [rows, D], D <= 512, with row pitches: mean = sum / D, var = sum (x - mean)^2 / D,
+ * y = (x - mean) * (1 / sqrt(var + eps)) * gamma + beta; the sums are wave reductions in a fixed order. */
+int tfx_ocr_layernorm(const float* x, int64_t ldx, float* out, int64_t ldo, const float* gamma, const float* beta, int64_t rows, int32_t D,
+                      float eps, tfx_stream stream);
+/* Softmax attention of the SVTR blocks: qkv fp32 [B, N, 3 * H * d] contiguous (column = which * H * d + head * d + e) -> out
+ * [B, N, H * d]; d <= 32, N <= 256.  q is multiplied by scale (rounded) BEFORE the product, as the reference does; scores are fmaf
+ * chains over e; the softmax is exp(s - max) / sum in fp32; the output sums p[j] v[j] over the first ceil(N / 2) keys and over the
+ * rest, each as an fmaf chain in rising j, and adds the two.  One workgroup per (b, head), scores in LDS. */
+int tfx_ocr_attention(const float* qkv, float* out, int32_t B, int32_t N, int32_t H, int32_t d, float scale, tfx_stream stream);
+/* Per row of C logits (rows with pitch ld): row_max = the maximum, row_arg = its FIRST index (numpy's argmax tie rule), row_lse =
+ * max + log(sum exp(x - max)).  Thread t of 256 takes the classes t, t + 256, ... in rising order; a fixed tree folds the 256 partial results. */
+int tfx_ctc_rows(const float* logits, int64_t ld, int64_t rows, int32_t C, float* row_max, int32_t* row_arg, float* row_lse, tfx_stream stream);
+/* Per sample of logits [n, T, C] (T <= 256), from tfx_ctc_rows' row_arg / row_lse [n, T]: the greedy decode of TextRecognizer.decode
+ * -- collapse repeats, then drop the blank 0 -- as ids / time_index int32 [n, T] (the first count[n] entries; the rest 0 / -1) and
+ * count [n]; and, when loss != NULL, loss[n] = -log p(target | logits) by the forward recursion in log space over the 2 L + 1 states
+ * (torch.nn.CTCLoss(reduction='none'), blank 0): targets = the concatenated int32 ids, offsets int32 [n + 1], L <= max_target <= 127.
+ * L = 0 is valid; a target that cannot be emitted in T steps gives +inf. */
+int tfx_ctc_score(const float* logits, const int32_t* row_arg, const float* row_lse, const int32_t* targets, const int32_t* offsets,
+                  int32_t max_target, int32_t n, int32_t T, int32_t C, int32_t* ids, int32_t* time_index, int32_t* count, float* loss,
+                  tfx_stream stream);
+
 /* ---- tuning knobs (no reference counterpart).  "attention_waves" selects the attention kernel: 30 (default) = one
  *      256-thread workgroup per CU -- one wave per SIMD, 64 query rows per wave, the tile loop pipelined per (32-key block,
  *      32-row q-block) unit (attention_w4.hip); it stores whole output rows in 16-byte pieces, so output views whose row or

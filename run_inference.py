@@ -372,6 +372,39 @@ def known_region_from_args(a):
     return known or None
 
 
+def add_ocr_args(ap):
+    """Not in the reference's Fill callers: read-back (textflux_amd/ocr.py) -- every edited line is cropped from the final image, read by the
+    recogniser of the reference's eval/ and scored against its text."""
+    ap.add_argument("--ocr_weights", type=str, default=None, metavar="P", help="read the result back: the recogniser's state dict (.pth or "
+                    ".safetensors, the reference's ppv3_rec.pth); every line's prediction, sentence accuracy, NED and CTC loss are reported")
+    ap.add_argument("--ocr_lang", choices=("ch", "en"), default="ch", help="with --ocr_weights: 'ch' = 6625 classes, 'en' = 97")
+    ap.add_argument("--ocr_dict", type=str, default=None, metavar="D", help="with --ocr_weights: the model's character list (ppocr_keys_v1.txt / en_dict.txt)")
+
+
+def ocr_from_args(a):
+    """-> None (the defaults: nothing is constructed or launched), or run_items' ocr dict"""
+    if a.ocr_weights is None:
+        if a.ocr_dict is not None or a.ocr_lang != "ch":
+            raise SystemExit("--ocr_lang / --ocr_dict need --ocr_weights")
+        return None
+    if a.ocr_dict is None:
+        raise SystemExit("--ocr_weights needs --ocr_dict (the character list the model was trained with)")
+    return dict(weights=a.ocr_weights, lang=a.ocr_lang, dict_path=a.ocr_dict)
+
+
+def report_read_back(ocr, final, mask, words):
+    """Reads every line of `final` (the saved crop) back and prints the records; mask = the scene's mask as loaded."""
+    from textflux_amd import ocr as rb
+    from textflux_amd import per_line
+    cfg = rb.ocr_cfg(ocr)
+    lines = [(text, lm) for _, text, lm in per_line.split_lines(mask.convert("L"), words)]
+    rep = rb.report(rb.read_lines(rb.make_reader(cfg), final, mask.size, lines))
+    for r in rep["lines"]:
+        print(f"read-back: wanted {r['text']!r}, read {r['pred']!r}, NED {r['ned']:.3f}, CTC loss {r['ctc_loss']:.3f}")
+    print(f"read-back: sentence accuracy {rep['sen_acc']:.3f}, NED {rep['ned']:.3f} over {rep['line_count']} lines")
+    return rep
+
+
 def add_step_cache_args(ap):
     """Not in the reference: the first-block step cache (FluxFillPipeline.enable_step_cache)."""
     ap.add_argument("--step_cache", type=float, default=None, metavar="THR", help="skip the block stack on steps whose first-block residual "
@@ -394,10 +427,11 @@ def report_step_cache(pipe):
 
 
 def process_normal_mode(image_path, mask_path, words_path, steps, guidance_scale, seed, pipe=None, out_dir="outputs_my", paste_back=None,
-                        known=None):
-    """known: None, or dict(keep_known, strength) for every pipeline call (known_region_from_args).  paste_back: None, or dict(dilate, feather, region) as in batch_driver.run_items -- the saved crop is then the original scene at
+                        known=None, ocr=None):
+    """ocr: None, or ocr_from_args' dict: the saved crop is read back line by line (report_read_back).  known: None, or dict(keep_known, strength) for every pipeline call (known_region_from_args).  paste_back: None, or dict(dilate, feather, region) as in batch_driver.run_items -- the saved crop is then the original scene at
     its original size with the edit pasted in; with a region only that part of the scene goes through the pipeline."""
     scene, mask = Image.open(image_path).convert("RGB"), Image.open(mask_path).convert("RGB")
+    mask_loaded = mask
     words = glyph.read_words_from_text(words_path)
     work = None
     if paste_back is not None and paste_back.get("per_line"):
@@ -412,6 +446,8 @@ def process_normal_mode(image_path, mask_path, words_path, steps, guidance_scale
             full.save(os.path.join(out_dir, f"result_{n:04d}.png" if k == 0 else f"result_{n:04d}_line{k}.png"))
         cropped.save(os.path.join(out_dir, "crop", f"crop_{n:04d}.png"))
         print(f"\nProcessing mode: per-line\nFull Result: {out_dir}/result_{n:04d}.png")
+        if ocr is not None:
+            report_read_back(ocr, cropped, mask_loaded, words)
         return cropped
     if paste_back is not None:
         from textflux_amd import batch_driver
@@ -433,6 +469,8 @@ def process_normal_mode(image_path, mask_path, words_path, steps, guidance_scale
     full.save(os.path.join(out_dir, f"result_{n:04d}.png"))
     cropped.save(os.path.join(out_dir, "crop", f"crop_{n:04d}.png"))
     print(f"\nProcessing mode: {meta['mode']}\nFull Result: {out_dir}/result_{n:04d}.png")
+    if ocr is not None:
+        report_read_back(ocr, cropped, mask_loaded, words)
     return cropped
 
 
@@ -449,6 +487,7 @@ def build_parser():
     add_known_region_args(ap)
     add_step_cache_args(ap)
     add_paste_back_args(ap)
+    add_ocr_args(ap)
     return ap
 
 
@@ -457,11 +496,12 @@ def main(argv=None):
     a = build_parser().parse_args(argv)
     paste_back = paste_back_from_args(a)
     known = known_region_from_args(a)
+    ocr = ocr_from_args(a)
     if a.multistep:
         scheduler_name = "multistep"
     pipe = apply_step_cache_args(a, load_flux_pipeline()) if a.step_cache is not None or a.step_cache_max_consecutive is not None else None
     process_normal_mode(a.image, a.mask, a.words, a.steps, a.guidance_scale, a.seed, pipe=pipe, paste_back=paste_back,
-                        **(dict(known=known) if known else {}))
+                        **(dict(known=known) if known else {}), **(dict(ocr=ocr) if ocr else {}))
     report_step_cache(pipe)
     print("\nProcessing completed successfully!")
 

@@ -51,6 +51,7 @@ def build_parser():
     base.add_known_region_args(ap)
     base.add_step_cache_args(ap)
     base.add_paste_back_args(ap)
+    base.add_ocr_args(ap)
     return ap
 
 
@@ -58,10 +59,11 @@ def main(argv=None):
     a = build_parser().parse_args(argv)
     paste_back = base.paste_back_from_args(a)
     known = base.known_region_from_args(a)
+    ocr = base.ocr_from_args(a)
     base.scheduler_name = "multistep" if a.multistep else scheduler_name
     pipe = base.apply_step_cache_args(a, load_flux_pipeline(a.lora_runtime, a.lora_scale))
     base.process_normal_mode(a.image, a.mask, a.words, a.steps, a.guidance_scale, a.seed, pipe=pipe, paste_back=paste_back,
-                             **(dict(known=known) if known else {}))
+                             **(dict(known=known) if known else {}), **(dict(ocr=ocr) if ocr else {}))
     base.report_step_cache(pipe)
     print("\nProcessing completed successfully!")
 

@@ -7,13 +7,15 @@
          --steps 30 --guidance_scale 30 --seed 42 --num_gpus 4 --scheduler "" | overshoot | multistep
          --strength 1.0 --keep_known --keep_known_mode nearest | cover --keep_known_grow 0
          --change_map --change_dilate N --change_feather N --change_mode nearest | cover --change_grow 0 --change_last keep | free
-         --true_cfg F --negative_prompt STR]
+         --true_cfg F --negative_prompt STR
+         --ocr_weights ppv3_rec.pth --ocr_lang ch | en --ocr_dict ppocr_keys_v1.txt]
 
 `annos.json` = {"data_list": [{"img_name": ..., "annotations": [{"text": ..., "polygon": [[x, y], ...]}, ...]}, ...]}; per item
 the first annotation is used: polygon -> white-on-black mask, glyph strip of height int(width * text_height_ratio) stacked on
 top, resize to multiples of 32, prompt = template / generate_prompt([text]); outputs <output_dir>/full_images/<name> and
 <output_dir>/cropped_images/<name> (crop top = int(res_h * strip / (orig_h + strip))).  Items with incomplete annotations
-are skipped, per-item failures do not stop the run.
+are skipped, per-item failures do not stop the run.  With --ocr_weights every annotation's line is cropped from the item's final image,
+read by the recogniser of the reference's eval/ and scored (textflux_amd/ocr.py); <output_dir>/ocr_report.json holds the records.
 
 Where the reference starts --num_gpus worker processes that each pull ONE item at a time from a queue, this script re-executes
 itself as --num_gpus ranks under torch.distributed.run (one process per GPU, RCCL) and hands the list to
@@ -90,6 +92,11 @@ def build_parser(lora: bool = False):
     ap.add_argument("--change_grow", type=int, default=0, metavar="N", help="with --change_mode cover: also look at the N neighbouring latent pixels, 0..8")
     ap.add_argument("--change_last", choices=("keep", "free"), default="keep", help="with --change_map: held pixels end as the canvas's latents "
                     "(keep), or the last step belongs to the model (free)")
+    ap.add_argument("--ocr_weights", type=str, default=None, metavar="P", help="read-back: score every edited line with the recogniser of the "
+                    "reference's eval/ (its state dict, .pth or .safetensors) and write ocr_report.json (ocr_report.rank<k>.json per rank "
+                    "with more than one) into the output folder")
+    ap.add_argument("--ocr_lang", choices=("ch", "en"), default="ch", help="with --ocr_weights: 'ch' = 6625 classes, 'en' = 97")
+    ap.add_argument("--ocr_dict", type=str, default=None, metavar="D", help="with --ocr_weights: the model's character list (ppocr_keys_v1.txt / en_dict.txt)")
     ap.add_argument("--step_cache", type=float, default=None, metavar="THR", help="first-block step cache: skip the block stack on steps whose "
                     "first-block residual moved by less than THR relative to the last computed step (no default: the value is a property "
                     "of the checkpoint; 0 never skips)")
@@ -200,6 +207,18 @@ def load_lora_transformer(lora_weights_path, base_transformer=None, lora_runtime
     return transformer
 
 
+def write_ocr_report(read, out_dir, rank: int = 0, world: int = 1) -> str:
+    """ocr_report.json (ocr_report.rank<k>.json with more than one rank, each over its own items): the per-line records in item
+    order, each with its item index, and the mean sentence accuracy, the mean NED and the line count, as the reference's
+    eval/eval_dgocr.py prints them.  Returns the summary line."""
+    from textflux_amd import ocr as rb
+    rep = rb.report([dict(r, item=i) for i in sorted(read) for r in read[i]])
+    path = os.path.join(out_dir, "ocr_report.json" if world == 1 else f"ocr_report.rank{rank}.json")
+    with open(path, "w") as f:
+        json.dump(rep, f, ensure_ascii=False, indent=1)
+    return f"sentence accuracy {rep['sen_acc']:.4f}, NED {rep['ned']:.4f} over {rep['line_count']} lines -> {path}"
+
+
 def main(argv=None, lora: bool = False, script: str = __file__):
     a = build_parser(lora).parse_args(argv)
     if a.mixed_pad > 0 and a.scheduler in ("overshoot", "multistep"):
@@ -241,6 +260,11 @@ def main(argv=None, lora: bool = False, script: str = __file__):
         if a.step_cache is not None:
             raise SystemExit("--true_cfg does not run with --step_cache")
         known["true_cfg"], known["negative_prompt"] = a.true_cfg, a.negative_prompt
+    if a.ocr_weights is None and (a.ocr_dict is not None or a.ocr_lang != "ch"):
+        raise SystemExit("--ocr_lang / --ocr_dict need --ocr_weights")
+    if a.ocr_weights is not None and a.ocr_dict is None:
+        raise SystemExit("--ocr_weights needs --ocr_dict (the character list the model was trained with)")
+    ocr = dict(weights=a.ocr_weights, lang=a.ocr_lang, dict_path=a.ocr_dict) if a.ocr_weights is not None else None
     if a.step_cache is None and a.step_cache_max_consecutive is not None:
         raise SystemExit("--step_cache_max_consecutive needs --step_cache THR")
     if a.step_cache is not None and a.mixed_pad > 0:
@@ -361,8 +385,10 @@ def main(argv=None, lora: bool = False, script: str = __file__):
     pipe.enable_hip_graph(True)
     res = batch_driver.run_items(items, pipe, out_dir, batch_size=a.batch_size, num_inference_steps=steps,
                                  guidance_scale=a.guidance_scale, seed=a.seed, device=f"cuda:{local}", eval_cfg=eval_cfg,
-                                 mixed_pad=a.mixed_pad, paste_back=paste_back, **known,
+                                 mixed_pad=a.mixed_pad, paste_back=paste_back, **known, **(dict(ocr=ocr) if ocr else {}),
                                  step_cache=None if a.step_cache is None else dict(threshold=a.step_cache, max_consecutive=a.step_cache_max_consecutive))
+    if ocr:
+        print(f"[rank {rank}] read-back: " + write_ocr_report(res["ocr"], out_dir, rank, world))
     if "steps_total" in res:
         print(f"[rank {rank}] step cache: {res['steps_skipped']} of {res['steps_total']} steps skipped")
     print(f"[rank {rank}] {len(res['done'])} images written" + (f"; {len(res['all_done'])}/{len(items)} in total, "

@@ -245,6 +245,18 @@ SIGNATURES = {
     "tfx_gather_rows": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_int64, c_void_p]),
     "tfx_add_into_f32": (c_int, [c_void_p, c_void_p, c_int64, c_int32, c_void_p]),
     "tfx_mul_act": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int32, c_int32, c_void_p]),
+    "tfx_ocr_resize_norm": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p]),
+    "tfx_ocr_conv_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32,
+                                 c_int32, c_int32, c_int64, c_int64, c_int32, c_void_p]),
+    "tfx_ocr_conv_dw": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32,
+                                c_int32, c_void_p]),
+    "tfx_ocr_pool": (c_int, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_int64, c_void_p]),
+    "tfx_ocr_scale_channels": (c_int, [c_void_p, c_void_p, c_void_p, c_int32, c_int64, c_int32, c_void_p]),
+    "tfx_ocr_layernorm": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int32, c_float, c_void_p]),
+    "tfx_ocr_attention": (c_int, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_float, c_void_p]),
+    "tfx_ctc_rows": (c_int, [c_void_p, c_int64, c_int64, c_int32, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "tfx_ctc_score": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p,
+                              c_void_p, c_void_p, c_void_p]),
     "tfx_set_option": (c_int, [c_char_p, c_int]),
     "tfx_release_scratch": (c_int, []),
     "tfx_prof_enable": (c_int, [c_int]),

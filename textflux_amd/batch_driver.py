@@ -442,7 +442,8 @@ def run_items(items: Sequence[Dict[str, Any]], pipe, out_dir: Optional[str], bat
               save: Optional[Callable] = None, max_sequence_length: int = 512, eval_cfg: Optional[Dict[str, Any]] = None,
               encode: str = "auto", save_full: Optional[Callable] = None, mixed_pad: float = 0.0,
               step_cache: Optional[Dict[str, Any]] = None, paste_back: Optional[Dict[str, Any]] = None, keep_known=None,
-              strength: float = 1.0, change_map=None, true_cfg: float = 1.0, negative_prompt: Optional[str] = None) -> Dict[str, Any]:
+              strength: float = 1.0, change_map=None, true_cfg: float = 1.0, negative_prompt: Optional[str] = None,
+              ocr: Optional[Dict[str, Any]] = None) -> Dict[str, Any]:
     """Runs the whole list; returns {"done": [indices this rank wrote], "failed": [...], "all_done": [...] on rank 0,
     "encode": "local" | "rank0"}.  `pipe` needs `encode_prompt(prompt, prompt_2, ...)` and the FluxFillPipeline `__call__`.
     encode: "local" = every rank encodes the T5 prompts of its own batches (needs a T5 on every rank), "rank0" = rank 0
@@ -504,7 +505,14 @@ def run_items(items: Sequence[Dict[str, Any]], pipe, out_dir: Optional[str], bat
     calls' size.  Not with keep_known, not with mixed_pad > 0.
     true_cfg, negative_prompt (DESIGN.md section 4 "True CFG"): one negative prompt string for all items and the guidance scale against
     it, handed to every pipeline call as they are (the calls behind paste_back, region and per_line included) when true_cfg > 1 and a
-    negative prompt is given; every step then runs on twice the batch.  Not with mixed_pad > 0, not with step_cache."""
+    negative prompt is given; every step then runs on twice the batch.  Not with mixed_pad > 0, not with step_cache.
+    ocr (DESIGN.md section 4 "Read-back"): None, or dict(weights, lang='ch' | 'en', dict_path, image_shape=(3, 48, 320), batch=6): after an
+    item's image is final -- the pasted scene with paste_back, else the pipeline-size result -- every line of it (ocr.item_lines) is
+    cropped from that image, read by the recogniser and scored against its text; the result then carries "ocr": {item index: [{text,
+    pred, seq_acc, ned, ctc_loss}]} for this rank's items.  Without the key nothing is constructed or launched."""
+    if ocr is not None:              # refused before anything is prepared or encoded
+        from . import ocr as rb
+        ocr = rb.ocr_cfg(ocr)
     known = {}
     if negative_prompt is not None and not isinstance(negative_prompt, str):
         raise ValueError("negative_prompt is one string for all items")
@@ -543,17 +551,27 @@ def run_items(items: Sequence[Dict[str, Any]], pipe, out_dir: Optional[str], bat
         pipe.enable_step_cache(**step_cache)
         try:
             return _run_items(items, pipe, out_dir, batch_size, num_inference_steps, guidance_scale, seed, device, loader, save,
-                              max_sequence_length, eval_cfg, encode, save_full, mixed_pad, count_steps=True, paste_back=paste_back, known=known)
+                              max_sequence_length, eval_cfg, encode, save_full, mixed_pad, count_steps=True, paste_back=paste_back, known=known,
+                              ocr=ocr)
         finally:
             pipe.disable_step_cache()
     return _run_items(items, pipe, out_dir, batch_size, num_inference_steps, guidance_scale, seed, device, loader, save,
-                      max_sequence_length, eval_cfg, encode, save_full, mixed_pad, paste_back=paste_back, known=known)
+                      max_sequence_length, eval_cfg, encode, save_full, mixed_pad, paste_back=paste_back, known=known, ocr=ocr)
 
 
 def _run_items(items, pipe, out_dir, batch_size, num_inference_steps, guidance_scale, seed, device, loader, save, max_sequence_length,
                eval_cfg, encode, save_full, mixed_pad, count_steps: bool = False, paste_back: Optional[Dict[str, Any]] = None,
-               known: Optional[Dict[str, Any]] = None) -> Dict[str, Any]:
+               known: Optional[Dict[str, Any]] = None, ocr: Optional[Dict[str, Any]] = None) -> Dict[str, Any]:
     steps_skipped = steps_total = 0
+    read: Dict[int, Any] = {}       # ocr: item index -> its lines' records
+    reader: List[Any] = []          # the recogniser, made when the first image is final
+
+    def read_back(index, final):
+        from . import ocr as rb
+        if not reader:
+            reader.append(rb.make_reader(ocr, device))
+        size, item_ln = rb.item_lines(items[index], loader, eval_cfg)
+        read[index] = rb.read_lines(reader[0], final, size, item_ln, device)
     if mixed_pad > 0:            # refused before anything is prepared or encoded, not batch by batch inside the loop
         if not hasattr(pipe, "call_mixed"):
             raise ValueError("mixed_pad > 0 needs a pipeline with call_mixed (FluxFillPipeline)")
@@ -690,6 +708,8 @@ def _run_items(items, pipe, out_dir, batch_size, num_inference_steps, guidance_s
                         from . import per_line as pl
                         ws = lines[w.index]
                         pasted = pl.compose_lines(pipe, ws, [got[x.line][1] for x in ws], paste_back)
+                        if ocr is not None:
+                            read_back(w.index, pasted)
                         pl.write_item(ws, [got[x.line][0] for x in ws], pasted, out_dir, save, save_full)
                         done.append(w.index)
                     except Exception as e:
@@ -700,6 +720,8 @@ def _run_items(items, pipe, out_dir, batch_size, num_inference_steps, guidance_s
                     continue
                 if paste_back is not None:
                     cropped = _paste_into_original(pipe, w, cropped, paste_back)
+                if ocr is not None:
+                    read_back(w.index, cropped)
                 if w.name is not None and (save_full is not None or (save is None and out_dir is not None)):
                     if save_full is not None:
                         save_full(w, img, cropped)
@@ -718,6 +740,8 @@ def _run_items(items, pipe, out_dir, batch_size, num_inference_steps, guidance_s
     res: Dict[str, Any] = {"done": done, "failed": failed, "batches": sum(len(p) for p in plans), "rounds": rounds, "encode": encode}
     if count_steps:
         res["steps_skipped"], res["steps_total"] = steps_skipped, steps_total
+    if ocr is not None:
+        res["ocr"] = read
     if grouped:
         cnt = torch.zeros(len(items) + 1, dtype=torch.int32, device=device)
         for i in done:

@@ -1421,3 +1421,170 @@ def quick_gelu(a: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Ten
     L.check(L.lib().tfx_mul_act(a.data_ptr(), a.stride(0), None, 0, out.data_ptr(), out.stride(0), a.shape[0], a.shape[1], 1,
                                 _stream()), "quick_gelu")
     return out
+
+
+# ---- read-back: the fp32 NHWC kernels of the text recogniser and the CTC decode / loss (ocr.hip) --------------------------------------
+OCR_ACTS = {None: 0, "none": 0, "relu": 1, "hard_swish": 2, "hard_sigmoid": 3, "swish": 4}
+F32 = torch.float32
+
+
+def _chk_f32(*ts):
+    _chk_dev(*ts)
+    for t in ts:
+        if t is not None and (t.dtype != F32 or not t.is_contiguous()):
+            raise RuntimeError("the read-back kernels take contiguous fp32 tensors")
+
+
+def ocr_resize_norm(packed: torch.Tensor, table: torch.Tensor, img_h: int, img_w: int) -> torch.Tensor:
+    """packed u8 line crops ([h, w, 3] each) + table int32 [n, 4] = (byte offset, h, w, turn) -> fp32 [n, img_h, img_w, 3]."""
+    _chk_dev(packed, table)
+    assert packed.dtype == torch.uint8 and packed.dim() == 1 and packed.is_contiguous()
+    assert table.dtype == torch.int32 and table.dim() == 2 and table.shape[1] == 4 and table.is_contiguous()
+    n = table.shape[0]
+    out = torch.empty(n, img_h, img_w, 3, dtype=F32, device=packed.device)
+    L.check(L.lib().tfx_ocr_resize_norm(packed.data_ptr(), packed.numel(), table.data_ptr(), out.data_ptr(), n, img_h, img_w, _stream()),
+            "ocr_resize_norm")
+    return out
+
+
+def _conv_out(size: int, k: int, s: int) -> int:
+    return (size + 2 * (k // 2) - k) // s + 1
+
+
+def ocr_conv_f32(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor], stride=(1, 1), act=None, cin: Optional[int] = None,
+                 out: Optional[torch.Tensor] = None, co_off: int = 0) -> torch.Tensor:
+    """x [B, H, W, >= cin] fp32 (the first cin channels are read), w [Cout, k, k, cin], k in (1, 3) -> act(conv + bias) written to
+    out[..., co_off : co_off + Cout] (a fresh [B, Ho, Wo, Cout] when out is None)."""
+    _chk_f32(x, w, bias, out)
+    assert x.dim() == 4 and w.dim() == 4 and w.shape[1] == w.shape[2]
+    B, H, W, ldx = x.shape
+    Cout, k, _, Cin = w.shape
+    assert (cin or ldx) == Cin and Cin <= ldx and (bias is None or bias.shape == (Cout,))
+    Ho, Wo = _conv_out(H, k, stride[0]), _conv_out(W, k, stride[1])
+    if out is None:
+        out = torch.empty(B, Ho, Wo, Cout, dtype=F32, device=x.device)
+    assert out.shape[:3] == (B, Ho, Wo) and out.shape[3] >= co_off + Cout
+    L.check(L.lib().tfx_ocr_conv_f32(x.data_ptr(), w.data_ptr(), _p(bias), out.data_ptr(), B, H, W, Cin, Cout, k, stride[0], stride[1],
+                                     OCR_ACTS[act], ldx, out.shape[3], co_off, _stream()), "ocr_conv_f32")
+    return out
+
+
+def ocr_linear(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor], act=None) -> torch.Tensor:
+    """x [M, K] fp32, w [N, K] -> act(x w^T + bias) [M, N]: the 1 x 1 case of ocr_conv_f32."""
+    assert x.dim() == 2 and w.dim() == 2
+    M, K = x.shape
+    return ocr_conv_f32(x.view(M, 1, 1, K), w.view(w.shape[0], 1, 1, K), bias, act=act).view(M, w.shape[0])
+
+
+def ocr_conv_dw(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor], stride=(1, 1), act=None) -> torch.Tensor:
+    """depthwise: x [B, H, W, C] fp32, w [k, k, C], k in (3, 5) -> act(conv + bias), act None or 'hard_swish'."""
+    _chk_f32(x, w, bias)
+    assert x.dim() == 4 and w.dim() == 3 and w.shape[0] == w.shape[1] and w.shape[2] == x.shape[3]
+    B, H, W, Cc = x.shape
+    k = w.shape[0]
+    out = torch.empty(B, _conv_out(H, k, stride[0]), _conv_out(W, k, stride[1]), Cc, dtype=F32, device=x.device)
+    L.check(L.lib().tfx_ocr_conv_dw(x.data_ptr(), w.data_ptr(), _p(bias), out.data_ptr(), B, H, W, Cc, k, stride[0], stride[1],
+                                    OCR_ACTS[act], _stream()), "ocr_conv_dw")
+    return out
+
+
+def ocr_pool_mean(x: torch.Tensor) -> torch.Tensor:
+    """x [B, H, W, C] fp32 -> the mean over (H, W), [B, C]."""
+    _chk_f32(x)
+    B, H, W, Cc = x.shape
+    out = torch.empty(B, Cc, dtype=F32, device=x.device)
+    L.check(L.lib().tfx_ocr_pool(x.data_ptr(), out.data_ptr(), B, H, W, Cc, 0, Cc, _stream()), "ocr_pool")
+    return out
+
+
+def ocr_pool_2x2(x: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """x [B, H, W, C] fp32 -> the 2 x 2 stride-2 average written to out[..., :C] (a fresh [B, H // 2, W // 2, C] when out is None)."""
+    _chk_f32(x, out)
+    B, H, W, Cc = x.shape
+    if out is None:
+        out = torch.empty(B, H // 2, W // 2, Cc, dtype=F32, device=x.device)
+    assert out.shape[:3] == (B, H // 2, W // 2) and out.shape[3] >= Cc
+    L.check(L.lib().tfx_ocr_pool(x.data_ptr(), out.data_ptr(), B, H, W, Cc, 1, out.shape[3], _stream()), "ocr_pool")
+    return out
+
+
+def ocr_scale_channels(x: torch.Tensor, s: torch.Tensor) -> torch.Tensor:
+    """x [B, H, W, C] * s [B, C] (fp32)."""
+    _chk_f32(x, s)
+    B, H, W, Cc = x.shape
+    assert s.shape == (B, Cc)
+    out = torch.empty_like(x)
+    L.check(L.lib().tfx_ocr_scale_channels(x.data_ptr(), s.data_ptr(), out.data_ptr(), B, H * W, Cc, _stream()), "ocr_scale_channels")
+    return out
+
+
+def ocr_layernorm(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, eps: float) -> torch.Tensor:
+    """nn.LayerNorm over the last dim of fp32 rows [rows, D]."""
+    _chk_f32(x, gamma, beta)
+    assert x.dim() == 2 and gamma.shape == beta.shape == (x.shape[1],)
+    out = torch.empty_like(x)
+    L.check(L.lib().tfx_ocr_layernorm(x.data_ptr(), x.shape[1], out.data_ptr(), x.shape[1], gamma.data_ptr(), beta.data_ptr(), x.shape[0],
+                                      x.shape[1], eps, _stream()), "ocr_layernorm")
+    return out
+
+
+def ocr_add_(x: torch.Tensor, y: torch.Tensor) -> torch.Tensor:
+    """x += y on fp32 tensors (the residual add of the neck's blocks): the fp32 mode of tfx_add_into_f32."""
+    _chk_f32(x, y)
+    return add_into_f32_(x, y)
+
+
+def ocr_attention(qkv: torch.Tensor, heads: int) -> torch.Tensor:
+    """qkv fp32 [B, N, 3 * heads * d] -> softmax((q d^-0.5) k^T) v as [B, N, heads * d]."""
+    _chk_f32(qkv)
+    B, N, three = qkv.shape
+    d = three // (3 * heads)
+    assert three == 3 * heads * d
+    out = torch.empty(B, N, heads * d, dtype=F32, device=qkv.device)
+    L.check(L.lib().tfx_ocr_attention(qkv.data_ptr(), out.data_ptr(), B, N, heads, d, float(d) ** -0.5, _stream()), "ocr_attention")
+    return out
+
+
+def ctc_rows(logits: torch.Tensor):
+    """logits fp32 [..., C] -> (max fp32, first argmax int32, log-sum-exp fp32), each of shape logits.shape[:-1]."""
+    _chk_f32(logits)
+    Cc = logits.shape[-1]
+    rows = logits.numel() // Cc
+    mx = torch.empty(logits.shape[:-1], dtype=F32, device=logits.device)
+    arg = torch.empty(logits.shape[:-1], dtype=torch.int32, device=logits.device)
+    lse = torch.empty_like(mx)
+    L.check(L.lib().tfx_ctc_rows(logits.data_ptr(), Cc, rows, Cc, mx.data_ptr(), arg.data_ptr(), lse.data_ptr(), _stream()), "ctc_rows")
+    return mx, arg, lse
+
+
+def ctc_score(logits: torch.Tensor, row_arg: torch.Tensor, row_lse: torch.Tensor, targets=None):
+    """logits fp32 [n, T, C] with ctc_rows' outputs -> (ids int32 [n, T], time_index int32 [n, T], count int32 [n], loss fp32 [n] or None);
+    targets: one list of class ids per sample (None: decode only)."""
+    _chk_f32(logits, row_lse)
+    n, T, Cc = logits.shape
+    assert row_arg.dtype == torch.int32 and row_arg.shape == (n, T) and row_arg.is_contiguous() and row_lse.shape == (n, T)
+    dev = logits.device
+    ids = torch.empty(n, T, dtype=torch.int32, device=dev)
+    tix = torch.empty(n, T, dtype=torch.int32, device=dev)
+    count = torch.empty(n, dtype=torch.int32, device=dev)
+    loss = tg = off = None
+    longest = 0
+    if targets is not None:
+        if len(targets) != n:
+            raise ValueError(f"ctc_score: {len(targets)} targets for {n} samples")
+        flat, offs = [], [0]
+        for t in targets:
+            t = [int(v) for v in t]
+            if any(v < 0 or v >= Cc for v in t):
+                raise ValueError(f"ctc_score: a target id lies outside [0, {Cc})")
+            flat += t
+            offs.append(len(flat))
+            longest = max(longest, len(t))
+        if longest > 127:
+            raise ValueError("ctc_score: targets of at most 127 symbols")
+        tg = torch.tensor(flat or [0], dtype=torch.int32, device=dev)
+        off = torch.tensor(offs, dtype=torch.int32, device=dev)
+        loss = torch.empty(n, dtype=F32, device=dev)
+    L.check(L.lib().tfx_ctc_score(logits.data_ptr(), row_arg.data_ptr(), row_lse.data_ptr(), _p(tg), _p(off), longest, n, T, Cc,
+                                  ids.data_ptr(), tix.data_ptr(), count.data_ptr(), _p(loss), _stream()), "ctc_score")
+    return ids, tix, count, loss
