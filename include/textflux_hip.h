@@ -290,6 +290,17 @@ int tfx_change_map_blend(void* x, int64_t ldx, const void* x0, const void* noise
  *      not 4-byte aligned scale; out overlapping v_pos; out partly overlapping v_neg; scale inside out.  rows == 0 launches nothing.  No new
  *      TFX_ABI_VERSION: new entry points only. */
 int tfx_cfg_combine(const void* v_neg, const void* v_pos, void* out, int32_t C, int64_t rows, const float* scale, tfx_stream stream);
+/* ---- clean-image estimate (DESIGN.md section 4 "Candidates"): what a flow-matching state would decode to if the model's output held
+ *      for the rest of the way, `latents - sigma * noise_pred` on bf16 tensors with a Python float.  x bf16 [rows, C] with row pitch ldx (so
+ *      that it also reads the latents kept in xin[:, :C]), v and out bf16 [rows, C] contiguous, sigma fp32 [n_steps + 1] on the DEVICE.
+ *      With i = *step_ptr when step_ptr is given, else step, and s = sigma[i]; every torch op rounds on its own and the Python float takes
+ *      part as fp32, no FMA contraction:
+ *        m = bf16(s f32(v))   out = bf16(f32(x) - f32(m))
+ *      A NaN stays a NaN (its payload is not pinned).  Refused: C not a positive multiple of 8; ldx not a multiple of 8 or below C; a
+ *      negative row count; a null or not 16-byte aligned x, v or out; a null or not 4-byte aligned sigma or step_ptr; out overlapping x
+ *      or v.  rows == 0 launches nothing.  No new TFX_ABI_VERSION: new entry points only. */
+int tfx_x0_predict(const void* x, int64_t ldx, const void* v, void* out, int32_t C, int64_t rows, const float* sigma, const int32_t* step_ptr,
+                   int32_t step, tfx_stream stream);
 
 /* ---- small ops of the conditioning path (CombinedTimestepGuidanceTextProjEmbeddings, D/models/embeddings.py:1327-1339) */
 int tfx_timestep_embedding(const float* t, void* out /* [n,256] = cos|sin */, int32_t n, tfx_stream stream);
@@ -817,6 +828,20 @@ int tfx_warp_perspective_u8(const void* in, void* out, void* coverage, int32_t B
  *      c^2 X with no remainder), so the result is tfx_warp_affine_u8's bit for bit at every shift. */
 int tfx_warp_grid_u8(const void* in, void* out, void* coverage, int32_t B, int32_t H, int32_t W, int32_t C, int32_t out_h, int32_t out_w,
                      const int64_t* grid, int32_t shift, const int16_t* taps, tfx_stream stream);
+/* ---- candidates (DESIGN.md section 4 "Candidates"): all line crops of a batch in one launch, packed for tfx_ocr_resize_norm.  Added
+ *      without a new TFX_ABI_VERSION: one new entry point, no stamped struct and no existing entry point changes.
+ * tfx_warp_affine_gather_u8: images u8 [B, H, W, C] (contiguous, B, H, W >= 1, C in 1..4), table i64 [n][10] on the DEVICE, 8-byte aligned,
+ *      one row per crop: (b, m0, m1, m2, m3, m4, m5, out_h, out_w, offset).  Crop k is images[b] under the Q16 matrix m0..m5 exactly as
+ *      tfx_warp_affine_u8 computes it (the same map, the same taps table, edge replicated), written as u8 [out_h, out_w, C] at BYTE
+ *      `offset` of the packed buffer out u8 [out_bytes].  Offsets are byte-granular: no alignment of a crop's start is assumed.  The
+ *      caller keeps the crops' byte ranges apart from each other.
+ *      A row that cannot be served writes NOTHING and adds 1 to *refused (DEVICE int32, 4-byte aligned, zeroed by the caller): b outside
+ *      [0, B), out_h or out_w outside 1..2^24, or [offset, offset + out_h out_w C) not inside [0, out_bytes).  Every other row is served.
+ *      blocks_per_crop in 1..65535: how many workgroups share one crop's 32 x 8 tiles; the result does not depend on it.
+ *      Refused on the host: a null pointer, n < 0 or n > 65535, C outside 1..4, out_bytes < 0, misaligned table, taps or refused, or
+ *      images, out, table and refused overlapping.  n == 0 launches nothing. */
+int tfx_warp_affine_gather_u8(const void* images, void* out, int64_t out_bytes, const int64_t* table, int32_t n, int32_t* refused, int32_t B,
+                              int32_t H, int32_t W, int32_t C, int32_t blocks_per_crop, const int16_t* taps, tfx_stream stream);
 /* out[b, t, col0 + (i*8+j)*4 + py*2+px] = mask[(2ty+py)*8 + i, (2tx+px)*8 + j]  (P:1563-1580: 8x8 pixel blocks -> channels,
  * then _pack_latents), t = ty * (W/16) + tx, row stride ld. */
 int tfx_pack_mask(const void* mask, int32_t mask_dtype, void* out, int32_t B, int32_t H, int32_t W, int32_t mask_batch,

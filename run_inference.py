@@ -392,6 +392,69 @@ def ocr_from_args(a):
     return dict(weights=a.ocr_weights, lang=a.ocr_lang, dict_path=a.ocr_dict)
 
 
+def add_candidates_args(ap):
+    """Not in the reference: candidates (textflux_amd/candidates.py) -- every edit is run with N seeds and the one that reads best is kept."""
+    ap.add_argument("--candidates", type=int, default=None, metavar="N", help="run every edit with the N seeds seed .. seed + N - 1 and keep the "
+                    "one the recogniser reads best (needs --ocr_weights; no default: no quality claim is made)")
+    ap.add_argument("--candidates_prune_at", type=int, default=None, metavar="P", help="with --candidates: rank the candidates on their "
+                    "clean-image estimates after P steps and finish only the best --candidates_keep of every edit (Euler sampler only)")
+    ap.add_argument("--candidates_keep", type=int, default=None, metavar="K", help="with --candidates_prune_at: how many candidates of an "
+                    "edit are finished (default 1)")
+
+
+def candidates_from_args(a):
+    """-> None (the defaults: the run without the key), or run_items' candidates dict"""
+    if a.candidates is None:
+        if a.candidates_prune_at is not None or a.candidates_keep is not None:
+            raise SystemExit("--candidates_prune_at / --candidates_keep need --candidates N")
+        return None
+    if a.candidates < 1:
+        raise SystemExit(f"--candidates must be at least 1, got {a.candidates}")
+    if a.ocr_weights is None:
+        raise SystemExit("--candidates needs --ocr_weights / --ocr_dict: the recogniser chooses among them")
+    if a.candidates_keep is not None and a.candidates_prune_at is None:
+        raise SystemExit("--candidates_keep needs --candidates_prune_at P")
+    prune = None
+    if a.candidates_prune_at is not None:
+        if getattr(a, "step_cache", None) is not None or getattr(a, "multistep", False) or getattr(a, "scheduler", None) in ("overshoot", "multistep"):
+            raise SystemExit("--candidates_prune_at needs the Euler sampler without --step_cache (step windows carry the latents alone)")
+        prune = dict(at=a.candidates_prune_at, keep=1 if a.candidates_keep is None else a.candidates_keep)
+    return dict(n=a.candidates, prune=prune)
+
+
+def report_candidates(chosen):
+    """prints run_items' "candidates" result: per item and line the seeds, the winner and every candidate's score"""
+    for item in sorted(chosen):
+        for e in chosen[item]:
+            print(f"candidates: item {item} line {e['line']}: seed {e['seeds'][e['chosen']]} of {e['seeds']} kept")
+            for s in e["scores"]:
+                print(f"candidates:   seed {s['seed']} ({s['stage']}): read {s['pred']!r}, NED {s['ned']:.3f}, CTC loss {s['ctc_loss']:.3f}")
+
+
+def process_candidates(image_path, mask_path, words_path, steps, guidance_scale, seed, pipe, candidates, ocr, out_dir="outputs_my",
+                       paste_back=None, known=None):
+    """process_normal_mode with candidates: the one item goes through batch_driver.run_items, which runs, reads and chooses; the winner's
+    crop (the pasted scene with paste_back) is saved under crop/ as usual."""
+    from textflux_amd import batch_driver
+    pipe = pipe or load_flux_pipeline()
+    saved = []
+    res = batch_driver.run_items([dict(image=image_path, mask=mask_path, text=words_path)], pipe, None, batch_size=max(8, candidates["n"]),
+                                 num_inference_steps=steps, guidance_scale=guidance_scale, seed=seed, save=lambda i, img: saved.append(img),
+                                 paste_back=paste_back, ocr=ocr, candidates=candidates, **(known or {}))
+    if not saved:
+        raise SystemExit(f"candidates: the item failed ({res['failed']})")
+    os.makedirs(os.path.join(out_dir, "crop"), exist_ok=True)
+    n = 1
+    while os.path.exists(os.path.join(out_dir, "crop", f"crop_{n:04d}.png")):
+        n += 1
+    saved[0].save(os.path.join(out_dir, "crop", f"crop_{n:04d}.png"))
+    report_candidates(res.get("candidates", {}))
+    for r in res["ocr"].get(0, []):
+        print(f"read-back: wanted {r['text']!r}, read {r['pred']!r}, NED {r['ned']:.3f}, CTC loss {r['ctc_loss']:.3f}")
+    print(f"\nProcessing mode: candidates\nCrop: {out_dir}/crop/crop_{n:04d}.png")
+    return saved[0]
+
+
 def report_read_back(ocr, final, mask, words):
     """Reads every line of `final` (the saved crop) back and prints the records; mask = the scene's mask as loaded."""
     from textflux_amd import ocr as rb
@@ -488,6 +551,7 @@ def build_parser():
     add_step_cache_args(ap)
     add_paste_back_args(ap)
     add_ocr_args(ap)
+    add_candidates_args(ap)
     return ap
 
 
@@ -497,9 +561,15 @@ def main(argv=None):
     paste_back = paste_back_from_args(a)
     known = known_region_from_args(a)
     ocr = ocr_from_args(a)
+    candidates = candidates_from_args(a)
     if a.multistep:
         scheduler_name = "multistep"
     pipe = apply_step_cache_args(a, load_flux_pipeline()) if a.step_cache is not None or a.step_cache_max_consecutive is not None else None
+    if candidates is not None:
+        process_candidates(a.image, a.mask, a.words, a.steps, a.guidance_scale, a.seed, pipe, candidates, ocr, paste_back=paste_back, known=known)
+        report_step_cache(pipe)
+        print("\nProcessing completed successfully!")
+        return
     process_normal_mode(a.image, a.mask, a.words, a.steps, a.guidance_scale, a.seed, pipe=pipe, paste_back=paste_back,
                         **(dict(known=known) if known else {}), **(dict(ocr=ocr) if ocr else {}))
     report_step_cache(pipe)

@@ -52,6 +52,7 @@ def build_parser():
     base.add_step_cache_args(ap)
     base.add_paste_back_args(ap)
     base.add_ocr_args(ap)
+    base.add_candidates_args(ap)
     return ap
 
 
@@ -61,7 +62,14 @@ def main(argv=None):
     known = base.known_region_from_args(a)
     ocr = base.ocr_from_args(a)
     base.scheduler_name = "multistep" if a.multistep else scheduler_name
+    candidates = base.candidates_from_args(a)
     pipe = base.apply_step_cache_args(a, load_flux_pipeline(a.lora_runtime, a.lora_scale))
+    if candidates is not None:
+        base.process_candidates(a.image, a.mask, a.words, a.steps, a.guidance_scale, a.seed, pipe, candidates, ocr, paste_back=paste_back,
+                                known=known)
+        base.report_step_cache(pipe)
+        print("\nProcessing completed successfully!")
+        return
     base.process_normal_mode(a.image, a.mask, a.words, a.steps, a.guidance_scale, a.seed, pipe=pipe, paste_back=paste_back,
                              **(dict(known=known) if known else {}), **(dict(ocr=ocr) if ocr else {}))
     base.report_step_cache(pipe)

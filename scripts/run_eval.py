@@ -97,6 +97,8 @@ def build_parser(lora: bool = False):
                     "with more than one) into the output folder")
     ap.add_argument("--ocr_lang", choices=("ch", "en"), default="ch", help="with --ocr_weights: 'ch' = 6625 classes, 'en' = 97")
     ap.add_argument("--ocr_dict", type=str, default=None, metavar="D", help="with --ocr_weights: the model's character list (ppocr_keys_v1.txt / en_dict.txt)")
+    import run_inference as ri
+    ri.add_candidates_args(ap)       # --candidates N --candidates_prune_at P --candidates_keep K: best of N seeds per edit, chosen by read-back
     ap.add_argument("--step_cache", type=float, default=None, metavar="THR", help="first-block step cache: skip the block stack on steps whose "
                     "first-block residual moved by less than THR relative to the last computed step (no default: the value is a property "
                     "of the checkpoint; 0 never skips)")
@@ -219,6 +221,17 @@ def write_ocr_report(read, out_dir, rank: int = 0, world: int = 1) -> str:
     return f"sentence accuracy {rep['sen_acc']:.4f}, NED {rep['ned']:.4f} over {rep['line_count']} lines -> {path}"
 
 
+def write_candidates_report(chosen, out_dir, rank: int = 0, world: int = 1) -> str:
+    """candidates_report.json next to ocr_report.json (candidates_report.rank<k>.json with more than one rank): run_items' "candidates"
+    result in item order -- per edited line the seeds, the winner's position and every candidate's score.  Returns the summary line."""
+    path = os.path.join(out_dir, "candidates_report.json" if world == 1 else f"candidates_report.rank{rank}.json")
+    works = [dict(e, item=i) for i in sorted(chosen) for e in chosen[i]]
+    with open(path, "w") as f:
+        json.dump(dict(works=works, work_count=len(works)), f, ensure_ascii=False, indent=1)
+    moved = sum(1 for e in works if e["chosen"] != 0)
+    return f"{len(works)} edits, {moved} kept another seed than the first -> {path}"
+
+
 def main(argv=None, lora: bool = False, script: str = __file__):
     a = build_parser(lora).parse_args(argv)
     if a.mixed_pad > 0 and a.scheduler in ("overshoot", "multistep"):
@@ -265,6 +278,13 @@ def main(argv=None, lora: bool = False, script: str = __file__):
     if a.ocr_weights is not None and a.ocr_dict is None:
         raise SystemExit("--ocr_weights needs --ocr_dict (the character list the model was trained with)")
     ocr = dict(weights=a.ocr_weights, lang=a.ocr_lang, dict_path=a.ocr_dict) if a.ocr_weights is not None else None
+    import run_inference as ri
+    candidates = ri.candidates_from_args(a)
+    if candidates is not None and a.mixed_pad > 0:
+        raise SystemExit("--candidates does not serve mixed-geometry batches (--mixed_pad)")
+    if candidates is not None and candidates["prune"] is not None and (known or candidates["n"] > a.batch_size):
+        raise SystemExit("--candidates_prune_at runs without --keep_known / --strength / --change_map / --true_cfg, and --candidates N must "
+                         "not exceed --batch_size")
     if a.step_cache is None and a.step_cache_max_consecutive is not None:
         raise SystemExit("--step_cache_max_consecutive needs --step_cache THR")
     if a.step_cache is not None and a.mixed_pad > 0:
@@ -386,9 +406,12 @@ def main(argv=None, lora: bool = False, script: str = __file__):
     res = batch_driver.run_items(items, pipe, out_dir, batch_size=a.batch_size, num_inference_steps=steps,
                                  guidance_scale=a.guidance_scale, seed=a.seed, device=f"cuda:{local}", eval_cfg=eval_cfg,
                                  mixed_pad=a.mixed_pad, paste_back=paste_back, **known, **(dict(ocr=ocr) if ocr else {}),
+                                 **(dict(candidates=candidates) if candidates else {}),
                                  step_cache=None if a.step_cache is None else dict(threshold=a.step_cache, max_consecutive=a.step_cache_max_consecutive))
     if ocr:
         print(f"[rank {rank}] read-back: " + write_ocr_report(res["ocr"], out_dir, rank, world))
+    if "candidates" in res:
+        print(f"[rank {rank}] candidates: " + write_candidates_report(res["candidates"], out_dir, rank, world))
     if "steps_total" in res:
         print(f"[rank {rank}] step cache: {res['steps_skipped']} of {res['steps_total']} steps skipped")
     print(f"[rank {rank}] {len(res['done'])} images written" + (f"; {len(res['all_done'])}/{len(items)} in total, "

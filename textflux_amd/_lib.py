@@ -169,6 +169,7 @@ SIGNATURES = {
     "tfx_change_map_blend": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int64, c_void_p, c_void_p, c_int32,
                                      c_void_p, c_int64, c_void_p]),
     "tfx_cfg_combine": (c_int, [c_void_p, c_void_p, c_void_p, c_int32, c_int64, c_void_p, c_void_p]),
+    "tfx_x0_predict": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_int32, c_int64, c_void_p, c_void_p, c_int32, c_void_p]),
     "tfx_timestep_embedding": (c_int, [c_void_p, c_void_p, c_int32, c_void_p]),
     "tfx_silu": (c_int, [c_void_p, c_void_p, c_int64, c_void_p]),
     "tfx_add": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
@@ -228,6 +229,8 @@ SIGNATURES = {
     "tfx_warp_perspective_u8": (c_int, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p]),
     "tfx_warp_grid_u8": (c_int, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p, c_int32, c_void_p,
                                  c_void_p]),
+    "tfx_warp_affine_gather_u8": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int32, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32,
+                                          c_void_p, c_void_p]),
     "tfx_keep_mask_pack": (c_int, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p]),
     "tfx_change_map_pack": (c_int, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p]),
     "tfx_pack_mask": (c_int, [c_void_p, c_int32, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_int64, c_int32,

@@ -56,6 +56,9 @@ class Work:
     rect: Any = None                 # rectified lines only (rectify.py): the oriented rectify.Rect that was edited upright; perspective lines
                                      # only (perspective.py): the perspective.Quad that was; curved lines only (curve.py): the curve.Ribbon.
                                      # `region` is then the scene window it is pasted into
+    texts: Any = None                # the text lines the work writes: one for a strip edit, the item's words on the multi-line canvas
+    seed: Optional[int] = None       # candidates only (candidates.py): the seed of this candidate's generator (None: the run's seed) ...
+    cand: Optional[int] = None       # ... and its position k among the candidates of its work
 
 
 @dataclass
@@ -262,10 +265,10 @@ def prepare_eval_item(index: int, item: Dict[str, Any], original_images_dir: str
     prompt = glyph.generate_prompt([text])
     name = os.path.basename(item["img_name"])
     if device_compose:
-        return Work(index, None, None, prompt, meta, size, parts=(g, np.array(scene), m, False), name=name, **extra)
+        return Work(index, None, None, prompt, meta, size, parts=(g, np.array(scene), m, False), name=name, texts=[text], **extra)
     combined = Image.fromarray(np.vstack((g, np.array(scene))))
     cmask = Image.fromarray(np.vstack((np.zeros_like(g), m)))
-    return Work(index, combined.resize(size), cmask.resize(size), prompt, meta, size, name=name, **extra)
+    return Work(index, combined.resize(size), cmask.resize(size), prompt, meta, size, name=name, texts=[text], **extra)
 
 
 def prepare_item(index: int, item: Dict[str, Any], loader: Optional[Callable] = None, device_compose: bool = False,
@@ -299,11 +302,11 @@ def prepare_plain(index: int, scene, mask, words: Sequence[str], device_compose:
     w, h = (W // 32) * 32, (H // 32) * 32
     prompt = glyph.generate_prompt(words)
     if device_compose:               # stacking, the resize to (w, h) and the grey mask happen on the device, per batch
-        return Work(index, None, None, prompt, meta, (w, h), parts=(g, s_, m, horizontal), **extra)
+        return Work(index, None, None, prompt, meta, (w, h), parts=(g, s_, m, horizontal), texts=list(words), **extra)
     import numpy as np
     stack = np.hstack if horizontal else np.vstack
     combined, cmask = Image.fromarray(stack((g, s_))), Image.fromarray(stack((np.zeros_like(g), m)))
-    return Work(index, combined.resize((w, h)), cmask.resize((w, h)), prompt, meta, (w, h), **extra)
+    return Work(index, combined.resize((w, h)), cmask.resize((w, h)), prompt, meta, (w, h), texts=list(words), **extra)
 
 
 def _batch_inputs(items: Sequence[Work], device):
@@ -373,15 +376,20 @@ def pad_fraction(sizes: Sequence[Tuple[int, int]], text_tokens: int = 512) -> fl
     return 1.0 - sum(lens) / (len(lens) * n)
 
 
-def plan_batches(works: Sequence[Work], batch_size: int, max_pad_fraction: float = 0.0, text_tokens: int = 512) -> List[Batch]:
+def plan_batches(works: Sequence[Work], batch_size: int, max_pad_fraction: float = 0.0, text_tokens: int = 512, group: int = 1) -> List[Batch]:
     """Same-geometry batches of up to batch_size items, deterministic (every rank computes the same plan): geometries in
     order of first appearance, items in list order.
+    group > 1 (candidates with prune; candidates.py): the works come in runs of `group` adjacent works of one geometry, the candidates
+    of one work, and no run straddles two batches -- a batch holds batch_size // group whole runs; group <= batch_size, not with
+    max_pad_fraction > 0.
     max_pad_fraction > 0: items of different sizes may share a batch (Batch.mixed; FluxFillPipeline.call_mixed pads their rows to
     the longest).  Greedy over the items sorted by image token count (stable: ties keep list order): the next item joins the open
     batch unless the batch is full or pad_fraction of the batch with it would exceed the cap, in which case the batch is closed.
     text_tokens: the T5 sequence length every item carries (max_sequence_length)."""
     if max_pad_fraction < 0 or max_pad_fraction >= 1:
         raise ValueError("max_pad_fraction must be in [0, 1)")
+    if group < 1 or group > batch_size or (group > 1 and max_pad_fraction > 0):
+        raise ValueError(f"group must be in 1..batch_size = {batch_size} and 1 with max_pad_fraction > 0, got {group}")
     if max_pad_fraction > 0:
         out: List[Batch] = []
         cur: List[Work] = []
@@ -398,23 +406,25 @@ def plan_batches(works: Sequence[Work], batch_size: int, max_pad_fraction: float
     for w in works:
         by_size.setdefault(w.size, []).append(w)
     out: List[Batch] = []
+    per_batch = batch_size // group * group
     for size, ws in by_size.items():
-        for i in range(0, len(ws), batch_size):
-            out.append(Batch(size, list(ws[i:i + batch_size])))
+        for i in range(0, len(ws), per_batch):
+            out.append(Batch(size, list(ws[i:i + per_batch])))
     return out
 
 
 def rank_plans(works: Sequence[Work], world: int, batch_size: int, max_pad_fraction: float = 0.0, text_tokens: int = 512,
-               per_line: bool = False) -> List[List[Batch]]:
+               per_line: bool = False, group: int = 1) -> List[List[Batch]]:
     """plans[k][r] = the batch rank k runs in round r; deterministic, so every rank computes all of them.  Batches are dealt
     round-robin: plans[k] = plan_batches(works)[k::world], i.e. plans[k][r] = plan[r world + k].  per_line: ITEMS are dealt round-robin
     instead (in order of first appearance of Work.index) and each rank plans the lines of its own items, so all lines of an item run on
-    the rank that pastes them together."""
+    the rank that pastes them together.  Candidates deal items whole in the same way (run_items passes per_line=True for them: all
+    candidates of a work meet on the rank that chooses among them); group: plan_batches' group."""
     if not per_line:
-        plan = plan_batches(works, batch_size, max_pad_fraction, text_tokens)
+        plan = plan_batches(works, batch_size, max_pad_fraction, text_tokens, group)
         return [plan[k::world] for k in range(world)]
     owner = {idx: n % world for n, idx in enumerate(dict.fromkeys(w.index for w in works))}
-    return [plan_batches([w for w in works if owner[w.index] == k], batch_size, max_pad_fraction, text_tokens) for k in range(world)]
+    return [plan_batches([w for w in works if owner[w.index] == k], batch_size, max_pad_fraction, text_tokens, group) for k in range(world)]
 
 
 def _scatter(rows: Optional[List[torch.Tensor]], shape, dtype, device) -> torch.Tensor:
@@ -443,7 +453,7 @@ def run_items(items: Sequence[Dict[str, Any]], pipe, out_dir: Optional[str], bat
               encode: str = "auto", save_full: Optional[Callable] = None, mixed_pad: float = 0.0,
               step_cache: Optional[Dict[str, Any]] = None, paste_back: Optional[Dict[str, Any]] = None, keep_known=None,
               strength: float = 1.0, change_map=None, true_cfg: float = 1.0, negative_prompt: Optional[str] = None,
-              ocr: Optional[Dict[str, Any]] = None) -> Dict[str, Any]:
+              ocr: Optional[Dict[str, Any]] = None, candidates=None) -> Dict[str, Any]:
     """Runs the whole list; returns {"done": [indices this rank wrote], "failed": [...], "all_done": [...] on rank 0,
     "encode": "local" | "rank0"}.  `pipe` needs `encode_prompt(prompt, prompt_2, ...)` and the FluxFillPipeline `__call__`.
     encode: "local" = every rank encodes the T5 prompts of its own batches (needs a T5 on every rank), "rank0" = rank 0
@@ -509,10 +519,37 @@ def run_items(items: Sequence[Dict[str, Any]], pipe, out_dir: Optional[str], bat
     ocr (DESIGN.md section 4 "Read-back"): None, or dict(weights, lang='ch' | 'en', dict_path, image_shape=(3, 48, 320), batch=6): after an
     item's image is final -- the pasted scene with paste_back, else the pipeline-size result -- every line of it (ocr.item_lines) is
     cropped from that image, read by the recogniser and scored against its text; the result then carries "ocr": {item index: [{text,
-    pred, seq_acc, ned, ctc_loss}]} for this rank's items.  Without the key nothing is constructed or launched."""
+    pred, seq_acc, ned, ctc_loss}]} for this rank's items.  Without the key nothing is constructed or launched.
+    candidates (DESIGN.md section 4 "Candidates"; needs ocr): None, a count N, or dict(n, prune=None | dict(at, keep=1), seeds=None).
+    Every work -- an item, or a line of an item with per_line -- is run as n candidates that differ in the seed (seed + k, or seeds[k]),
+    adjacent in the plan; items are dealt to the ranks whole.  Every candidate is read on its own pipeline-size result (a device uint8
+    tensor, TextRecognizer.read_device: one gather launch per batch) where the work's own pipeline mask says its lines are, and per work
+    the smallest (lines not read exactly, sum of ctc_loss, k) wins.  Only the winner is converted, pasted and saved, by the code that
+    serves a run without the key; the result carries "candidates": {item: [{line, seeds, chosen (the winner's position k), scores:
+    [{seed, line, text, pred, seq_acc, ned, ctc_loss, stage}]}]}.  prune=dict(at=p, keep=K): a batch runs steps 0..p-1
+    (step_window=(0, p)), the clean-image estimates (pipe.x0_preview) are decoded, read and ranked by the same rule (stage
+    "preview"), and the K best of every work are finished on the smaller batch (step_window=(p, n)) and read again (stage "final").
+    The n candidates of a work then share a batch (n <= batch_size), and what step_window refuses is refused here, up front.  None or
+    n == 1 issues exactly the calls of a run without the key.  Not with mixed_pad > 0.  No quality claim is made: no real checkpoint
+    or recogniser weights exist here, so there is no default n and no recommended prune step."""
     if ocr is not None:              # refused before anything is prepared or encoded
         from . import ocr as rb
         ocr = rb.ocr_cfg(ocr)
+    cand = None
+    if candidates is not None:       # refused before anything is prepared or encoded
+        from . import candidates as cd
+        cand = cd.candidates_cfg(candidates, seed, num_inference_steps, batch_size)
+    if cand is not None:
+        if ocr is None:
+            raise ValueError("candidates needs ocr=dict(...): the reader and its dictionary choose among them")
+        if mixed_pad > 0:
+            raise NotImplementedError("candidates do not serve mixed-geometry batches (mixed_pad > 0)")
+        if cand["prune"] is not None:
+            from . import step_loop
+            step_loop.refuse_step_window(getattr(pipe, "scheduler", None), strength, keep_known, change_map,
+                                         negative_prompt is not None and true_cfg > 1, step_cache is not None)
+            if not hasattr(pipe, "decode_latents"):
+                raise ValueError("candidates with prune need a pipeline with step_window and decode_latents (FluxFillPipeline)")
     known = {}
     if negative_prompt is not None and not isinstance(negative_prompt, str):
         raise ValueError("negative_prompt is one string for all items")
@@ -552,16 +589,17 @@ def run_items(items: Sequence[Dict[str, Any]], pipe, out_dir: Optional[str], bat
         try:
             return _run_items(items, pipe, out_dir, batch_size, num_inference_steps, guidance_scale, seed, device, loader, save,
                               max_sequence_length, eval_cfg, encode, save_full, mixed_pad, count_steps=True, paste_back=paste_back, known=known,
-                              ocr=ocr)
+                              ocr=ocr, cand=cand)
         finally:
             pipe.disable_step_cache()
     return _run_items(items, pipe, out_dir, batch_size, num_inference_steps, guidance_scale, seed, device, loader, save,
-                      max_sequence_length, eval_cfg, encode, save_full, mixed_pad, paste_back=paste_back, known=known, ocr=ocr)
+                      max_sequence_length, eval_cfg, encode, save_full, mixed_pad, paste_back=paste_back, known=known, ocr=ocr, cand=cand)
 
 
 def _run_items(items, pipe, out_dir, batch_size, num_inference_steps, guidance_scale, seed, device, loader, save, max_sequence_length,
                eval_cfg, encode, save_full, mixed_pad, count_steps: bool = False, paste_back: Optional[Dict[str, Any]] = None,
-               known: Optional[Dict[str, Any]] = None, ocr: Optional[Dict[str, Any]] = None) -> Dict[str, Any]:
+               known: Optional[Dict[str, Any]] = None, ocr: Optional[Dict[str, Any]] = None,
+               cand: Optional[Dict[str, Any]] = None) -> Dict[str, Any]:
     steps_skipped = steps_total = 0
     read: Dict[int, Any] = {}       # ocr: item index -> its lines' records
     reader: List[Any] = []          # the recogniser, made when the first image is final
@@ -602,7 +640,78 @@ def _run_items(items, pipe, out_dir, batch_size, num_inference_steps, guidance_s
             failed.append(i)
             if rank == 0:
                 print(f"item {i} failed in preparation: {e}")
-    plans = rank_plans(works, world, batch_size, mixed_pad, max_sequence_length, per_line)
+    if cand is None:
+        plans = rank_plans(works, world, batch_size, mixed_pad, max_sequence_length, per_line)
+    else:                        # every work becomes its n candidates, adjacent; items are dealt to the ranks whole, as per_line deals them
+        from . import candidates as cd
+        works = cd.expand(works, cand)
+        plans = rank_plans(works, world, batch_size, mixed_pad, max_sequence_length, True, cand["n"] if cand["prune"] else 1)
+    cand_pending: Dict[Any, Dict[int, Any]] = {}     # (item, line) -> {k: (line records, the pipeline-size result, device uint8)}
+    cand_scores: Dict[Any, List[Any]] = {}          # (item, line) -> every record of the work's candidates, preview and final
+    cand_report: Dict[int, List[Any]] = {}          # the result's "candidates"
+    cand_lines: Dict[Any, Any] = {}                 # (item, line) -> where the work's lines are on its canvas
+
+    def get_reader():
+        from . import ocr as rb
+        if not reader:
+            reader.append(rb.make_reader(ocr, device))
+        return reader[0]
+
+    def cand_masks(mask_in):
+        """the batch's pipeline masks as host grey arrays [H, W]"""
+        import numpy as np
+        if isinstance(mask_in, torch.Tensor):
+            m = mask_in.cpu().numpy()
+            return [m[j][..., 0] if m[j].ndim == 3 else m[j] for j in range(m.shape[0])]
+        return [np.array(m.convert("L")) for m in mask_in]
+
+    def cand_settle(batch_items, recs, images_u8):
+        """files a batch's final records and results; -> [(the winning Work, its result as a PIL image)] of the works that are complete"""
+        from PIL import Image
+        won = []
+        for w, r, u8 in zip(batch_items, recs, images_u8):
+            key = cd.group_key(w)
+            cand_pending.setdefault(key, {})[w.cand] = (w, r, u8)
+            cand_scores.setdefault(key, []).extend(r)
+        for key in dict.fromkeys(cd.group_key(w) for w in batch_items):
+            got = cand_pending[key]
+            want = cand["prune"]["keep"] if cand["prune"] else cand["n"]
+            if len(got) < want:
+                continue
+            ks = sorted(got)
+            k = ks[cd.choose([got[k][1] for k in ks])[0]]
+            cand_report.setdefault(key[0], []).append(dict(line=key[1], seeds=list(cand["seeds"]), chosen=k, scores=cand_scores.pop(key)))
+            won.append((got[k][0], Image.fromarray(got[k][2].cpu().numpy())))
+            del cand_pending[key]
+        return won
+
+    def cand_batch(mine, call, gens, pe, pooled):
+        """One batch of candidates -> cand_settle's winners.  call(**kw): the pipeline call of this batch with the arguments every call of
+        it shares.  Without prune: one call, every result read at pipeline size.  With prune: steps 0..p-1, the estimates read and
+        ranked, the survivors of every work finished on the smaller batch and read again."""
+        img_in, mask_in = _batch_inputs(mine.items, device)
+        masks = cand_masks(mask_in)
+        size = dict(height=mine.size[1], width=mine.size[0])
+        if cand["prune"] is None:
+            images = call(image=img_in, mask_image=mask_in, generator=gens, prompt_embeds=pe, pooled_prompt_embeds=pooled, output_type="u8",
+                          **size).images
+            return cand_settle(mine.items, cd.score_batch(get_reader(), images, mine.items, masks, "final", cand_lines), images)
+        p, keep = cand["prune"]["at"], cand["prune"]["keep"]
+        lat = call(image=img_in, mask_image=mask_in, generator=gens, prompt_embeds=pe, pooled_prompt_embeds=pooled, output_type="latent",
+                   step_window=(0, p), **size).images
+        cond = pipe.window_conditioning
+        previews = pipe.decode_latents(pipe.x0_preview, mine.size[1], mine.size[0], "u8")
+        recs = cd.score_batch(get_reader(), previews, mine.items, masks, "preview", cand_lines)
+        groups: Dict[Any, List[int]] = {}
+        for j, w in enumerate(mine.items):
+            groups.setdefault(cd.group_key(w), []).append(j)
+            cand_scores.setdefault(cd.group_key(w), []).extend(recs[j])
+        alive = sorted(js[o] for js in groups.values() for o in cd.choose([recs[j] for j in js], keep))    # batch order, so k order per work
+        idx = torch.tensor(alive, dtype=torch.long, device=lat.device)
+        images = call(masked_image_latents=cond[idx], latents=lat[idx], generator=[gens[j] for j in alive], prompt_embeds=pe[idx],
+                      pooled_prompt_embeds=pooled[idx], output_type="u8", step_window=(p, num_inference_steps), **size).images
+        items = [mine.items[j] for j in alive]
+        return cand_settle(items, cd.score_batch(get_reader(), images, items, [masks[j] for j in alive], "final", cand_lines), images)
     rounds = max(len(p) for p in plans)
     if encode == "auto":
         has_t5 = 1 if (getattr(pipe, "text_encoder_2", None) is not None or getattr(pipe, "encodes_locally", False)) else 0
@@ -675,20 +784,29 @@ def _run_items(items, pipe, out_dir, batch_size, num_inference_steps, guidance_s
                 pe_mine, _, _ = pipe.encode_prompt(prompt=[glyph.PROMPT_TEMPLATE2] * n, prompt_2=prompts, device=device,
                                                    max_sequence_length=max_sequence_length)
                 pe_mine = pe_mine.to(dtype)
-            gens = [torch.Generator(device=device).manual_seed(int(seed)) for _ in range(n)]   # run_inference.py:76, per image
+            # run_inference.py:76, per image; a candidate carries its own seed
+            gens = [torch.Generator(device=device).manual_seed(int(seed if w.seed is None else w.seed)) for w in mine.items]
             boxes = [glyph.crop_box(w.size, w.meta) for w in mine.items]
             keep_full = any(w.name is not None for w in mine.items)   # eval schema: the uncropped result is an output too
             same_box = all(bx == boxes[0] for bx in boxes)      # one crop window for the whole batch: applied on the device
             kw = (dict(output_crop=boxes[0]) if same_box and not keep_full and not mine.mixed and getattr(pipe, "supports_output_crop", False)
                   else {})
             call_kw = dict(kw, **(known or {}))     # keep_known / strength / change_map: only when given, so that other pipelines' calls stay as they were
-            img_in, mask_in = _batch_inputs(mine.items, device)
-            if mine.mixed:          # items of different sizes: one padded forward per step, every item at its own size
+            finished = None
+            if cand is not None:    # read at pipeline size, so no crop on the device; only the winners go on, through the code below
+                kw = {}
+                call = lambda **k: pipe(num_inference_steps=num_inference_steps, max_sequence_length=max_sequence_length,
+                                        guidance_scale=guidance_scale, **k, **(known or {}))
+                finished = [(w, img, glyph.crop_box(w.size, w.meta))
+                            for w, img in cand_batch(mine, call, gens, pe_mine[:n], pooled1.expand(n, -1).contiguous())]
+            elif mine.mixed:        # items of different sizes: one padded forward per step, every item at its own size
+                img_in, mask_in = _batch_inputs(mine.items, device)
                 images = pipe.call_mixed(image=img_in, mask_image=mask_in, sizes=[w.size for w in mine.items],
                                          num_inference_steps=num_inference_steps, generator=gens,
                                          max_sequence_length=max_sequence_length, guidance_scale=guidance_scale,
                                          prompt_embeds=pe_mine[:n], pooled_prompt_embeds=pooled1.expand(n, -1).contiguous()).images
             else:
+                img_in, mask_in = _batch_inputs(mine.items, device)
                 images = pipe(height=mine.size[1], width=mine.size[0], image=img_in,
                               mask_image=mask_in, num_inference_steps=num_inference_steps, generator=gens,
                               max_sequence_length=max_sequence_length, guidance_scale=guidance_scale,
@@ -697,7 +815,7 @@ def _run_items(items, pipe, out_dir, batch_size, num_inference_steps, guidance_s
                 rep = getattr(pipe, "step_cache_report", None) or []
                 steps_total += len(rep)
                 steps_skipped += sum(1 for r_ in rep if r_["skipped"])
-            for w, img, bx in zip(mine.items, images, boxes):
+            for w, img, bx in (zip(mine.items, images, boxes) if finished is None else finished):
                 cropped = img if kw else img.crop(bx)
                 if per_line:         # kept until the item's last line is in; then all of them are pasted into the one scene
                     got = results.setdefault(w.index, {})
@@ -742,6 +860,8 @@ def _run_items(items, pipe, out_dir, batch_size, num_inference_steps, guidance_s
         res["steps_skipped"], res["steps_total"] = steps_skipped, steps_total
     if ocr is not None:
         res["ocr"] = read
+    if cand is not None:
+        res["candidates"] = {i: sorted(v, key=lambda e: e["line"]) for i, v in cand_report.items()}
     if grouped:
         cnt = torch.zeros(len(items) + 1, dtype=torch.int32, device=device)
         for i in done:

@@ -287,6 +287,10 @@ int tfx_known_region_blend(void* x, int64_t ldx, const void* x0, const void* noi
 int tfx_cfg_combine(const void* v_neg, const void* v_pos, void* out, int32_t C, int64_t rows, const float* scale, tfx_stream stream) {
   return cfg_combine(v_neg, v_pos, out, C, rows, scale, S(stream));
 }
+int tfx_x0_predict(const void* x, int64_t ldx, const void* v, void* out, int32_t C, int64_t rows, const float* sigma, const int32_t* step_ptr,
+                   int32_t step, tfx_stream stream) {
+  return x0_predict(x, ldx, v, out, C, rows, sigma, step_ptr, step, S(stream));
+}
 
 int tfx_change_map_blend(void* x, int64_t ldx, const void* x0, const void* noise, const void* hold, const int32_t* cut, int32_t C,
                          int64_t rows, const float* keep_sigma, const int32_t* step_ptr, int32_t step, void* xin, int64_t ldxin,
@@ -506,6 +510,11 @@ int tfx_warp_grid_u8(const void* in, void* out, void* coverage, int32_t B, int32
                      const int64_t* grid, int32_t shift, const int16_t* taps, tfx_stream stream) {
   if (!in || !out || !grid || !taps) return fail("tfx_warp_grid_u8: null pointer");
   return warp_grid_u8(in, out, coverage, B, H, W, C, out_h, out_w, grid, shift, taps, S(stream));
+}
+int tfx_warp_affine_gather_u8(const void* images, void* out, int64_t out_bytes, const int64_t* table, int32_t n, int32_t* refused, int32_t B,
+                              int32_t H, int32_t W, int32_t C, int32_t blocks_per_crop, const int16_t* taps, tfx_stream stream) {
+  if (!images || !out || !table || !refused || !taps) return fail("tfx_warp_affine_gather_u8: null pointer");
+  return warp_affine_gather_u8(images, out, out_bytes, table, n, refused, B, H, W, C, blocks_per_crop, taps, S(stream));
 }
 int tfx_change_map_pack(const void* map_u8, void* hold, int32_t B, int32_t H, int32_t W, int32_t mode, int32_t grow, tfx_stream stream) {
   return change_map_pack(map_u8, hold, B, H, W, mode, grow, S(stream));

@@ -321,6 +321,28 @@ __global__ __launch_bounds__(256) void cfg_combine_kernel(const bf16_t* v_neg, c
   *reinterpret_cast<u32x4*>(out + i * 8) = pack8(o);
 }
 
+// Clean-image estimate (DESIGN.md section 4 "Candidates"): where a flow-matching state x at sigma s would end if the model's output v
+// held for the rest of the way, torch's `latents - sigma * noise_pred` on bf16 tensors with a Python float, each op rounded on its own:
+//   m = bf16(s * f32(v))   out = bf16(f32(x) - f32(m))
+// explicit _rn ops, no FMA contraction.  x [rows, C] with row pitch ldx (the fused Euler form keeps the latents in xin[:, :C]); v and
+// out contiguous.  s = sigma[step], the step from *step_ptr when given (one captured launch then serves every step).
+__global__ __launch_bounds__(256) void x0_predict_kernel(const bf16_t* __restrict__ x, int64_t ldx, const bf16_t* __restrict__ v,
+                                                         bf16_t* __restrict__ out, int C, int64_t nchunks, const float* __restrict__ sigma,
+                                                         const int* __restrict__ step_ptr, int step) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= nchunks) return;
+  const float s = sigma[step_ptr ? *step_ptr : step];
+  const int64_t e0 = i * 8;
+  const int64_t row = e0 / C;
+  const int col = (int)(e0 - row * C);
+  float xx[8], vv[8], o[8];
+  unpack8(*reinterpret_cast<const u32x4*>(x + row * ldx + col), xx);
+  unpack8(*reinterpret_cast<const u32x4*>(v + e0), vv);
+#pragma unroll
+  for (int j = 0; j < 8; ++j) o[j] = __fsub_rn(xx[j], round_bf(__fmul_rn(s, vv[j])));
+  *reinterpret_cast<u32x4*>(out + e0) = pack8(o);
+}
+
 // The blend behind a sampler update, known-region and change-map sampling alike: FluxInpaintPipeline's loop
 // (D/pipelines/flux/pipeline_flux_inpaint.py:974-984) and FluxDifferentialImg2ImgPipeline's (D/examples/community/
 // pipeline_flux_differential_img2img.py:974-986), with FlowMatchEulerDiscreteScheduler.scale_noise
@@ -774,6 +796,23 @@ int cfg_combine(const void* v_neg, const void* v_pos, void* out, int C, int64_t 
   if (ps < po + bytes && po < ps + 4) return fail("cfg_combine: scale must not lie in out");
   cfg_combine_kernel<<<dim3((unsigned)((nch + 255) / 256)), 256, 0, st>>>((const bf16_t*)v_neg, (const bf16_t*)v_pos, (bf16_t*)out, nch, scale);
   return check_launch("cfg_combine");
+}
+
+int x0_predict(const void* x, int64_t ldx, const void* v, void* out, int C, int64_t rows, const float* sigma, const int* step_ptr, int step,
+               hipStream_t st) {
+  if (int e = step_tail_check("x0_predict", C, rows, ldx, nullptr, 0)) return e;
+  const int64_t nch = rows * C / 8;
+  if (nch == 0) return 0;                               // nothing to estimate: the pointers of empty tensors mean nothing
+  if (!x || !v || !out || !sigma) return fail("x0_predict: null pointer");
+  if (((uintptr_t)x | (uintptr_t)v | (uintptr_t)out) & 15) return fail("x0_predict: x, v and out must be 16-byte aligned");
+  if (((uintptr_t)sigma | (uintptr_t)step_ptr) & 3) return fail("x0_predict: sigma and step_ptr must be 4-byte aligned");
+  if (!step_ptr && step < 0) return fail("x0_predict: negative step");
+  const char *px = (const char*)x, *pv = (const char*)v, *po = (const char*)out;
+  const int64_t xbytes = ((rows - 1) * ldx + C) * 2, bytes = nch * 16;
+  if ((po < px + xbytes && px < po + bytes) || (po < pv + bytes && pv < po + bytes)) return fail("x0_predict: out must not overlap x or v");
+  x0_predict_kernel<<<dim3((unsigned)((nch + 255) / 256)), 256, 0, st>>>((const bf16_t*)x, ldx, (const bf16_t*)v, (bf16_t*)out, C, nch, sigma,
+                                                                         step_ptr, step);
+  return check_launch("x0_predict");
 }
 
 // The one launcher of the two blends: `who` is the declared function's name.  A TensorMask's mask is a third [rows, C] bf16 operand

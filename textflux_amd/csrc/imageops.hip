@@ -922,6 +922,42 @@ __global__ __launch_bounds__(256) void warp_u8_kernel(const uint8_t* __restrict_
   map(b, (int)i, (int)j, out_h, out_w, sample, none);
 }
 
+// Candidates (DESIGN.md section 4 "Candidates"): every line crop of a batch in one launch.  table i64 [n][10] holds per crop (b, m0..m5,
+// out_h, out_w, byte offset); crop k = blockIdx.y is images[b] under the Q16 matrix m, written as [out_h, out_w, C] at its byte offset
+// in the packed buffer `out` -- the layout tfx_ocr_resize_norm reads.  The map is WarpAffine on the row's own six words and the taps are
+// warp_sample_u8's: a crop is tfx_warp_affine_u8's bit for bit.  The crops' sizes live on the device, so the grid cannot be sized by
+// them: gridDim.x workgroups walk a crop's 32 x 8 tiles in a stride, whatever their number.  The row's address is uniform over the
+// workgroup.  A row that cannot be served (b outside [0, B), a side outside 1..kGatherMaxSide, [offset, offset + h w C) outside
+// [0, out_bytes)) writes nothing and its first workgroup's first lane adds 1 to *refused (a vector atomic).  Stores are single bytes:
+// a crop may start at any byte.  The side bound keeps h w C below 2^50 and the pixel indices inside an int.
+static const int64_t kGatherMaxSide = (int64_t)1 << 24;
+
+template <int C>
+__global__ __launch_bounds__(256) void warp_gather_u8_kernel(const uint8_t* __restrict__ in, uint8_t* __restrict__ out, int64_t out_bytes,
+                                                             const int64_t* __restrict__ table, int* __restrict__ refused, int B, int H,
+                                                             int W, const int16_t* __restrict__ taps) {
+  const int64_t* row = table + (int64_t)blockIdx.y * 10;
+  const int64_t b = row[0], oh = row[7], ow = row[8], off = row[9];
+  const bool served = b >= 0 && b < B && oh >= 1 && oh <= kGatherMaxSide && ow >= 1 && ow <= kGatherMaxSide && off >= 0 &&
+                      off <= out_bytes && oh * ow * C <= out_bytes - off;
+  if (!served) {
+    if (blockIdx.x == 0 && threadIdx.x == 0) atomicAdd(refused, 1);
+    return;
+  }
+  const uint8_t* src = in + b * H * W * C;
+  uint8_t* dst = out + off;
+  const WarpAffine map{row + 1};
+  const int64_t tiles_x = (ow + 31) >> 5, tiles = tiles_x * ((oh + 7) >> 3);
+  for (int64_t t = blockIdx.x; t < tiles; t += gridDim.x) {
+    const int64_t ty = t / tiles_x;
+    const int i = (int)(t - ty * tiles_x) * 32 + (threadIdx.x & 31), j = (int)ty * 8 + (threadIdx.x >> 5);
+    if (i >= ow || j >= oh) continue;
+    uint8_t* px = dst + ((int64_t)j * ow + i) * C;
+    map(0, i, j, (int)oh, (int)ow,
+        [&](int64_t xi, int64_t yi, int fx, int fy) { warp_sample_u8<C>(src, H, W, xi, yi, fx, fy, taps, px, nullptr); }, [] {});
+  }
+}
+
 int compose_canvas(const void* glyph, const void* scene, const void* smask, void* canvas, void* cmask, int B, int gh, int gw, int sh,
                    int sw, int dir, int mask_rgb, hipStream_t st) {
   if (dir != 0 && dir != 1) return fail("compose_canvas: direction 0 (vertical) or 1 (horizontal)");
@@ -1551,6 +1587,38 @@ int warp_perspective_u8(const void* in, void* out, void* coverage, int B, int H,
 int warp_grid_u8(const void* in, void* out, void* coverage, int B, int H, int W, int C, int out_h, int out_w, const int64_t* grid,
                  int shift, const int16_t* taps, hipStream_t st) {
   return warp_u8("warp_grid_u8", "grid", in, out, coverage, B, H, W, C, out_h, out_w, WarpGrid{grid, shift}, taps, st);
+}
+
+// blocks_per_crop: how many workgroups share a crop's tiles (the kernel strides over them, so any value >= 1 gives the same bytes)
+int warp_affine_gather_u8(const void* images, void* out, int64_t out_bytes, const int64_t* table, int n, int* refused, int B, int H, int W,
+                          int C, int blocks_per_crop, const int16_t* taps, hipStream_t st) {
+  const char* who = "warp_affine_gather_u8";
+  if (n < 0) return fail("%s: negative crop count", who);
+  if (B < 1 || H < 1 || W < 1) return fail("%s: B, H, W must be at least 1", who);
+  if (C < 1 || C > 4) return fail("%s: 1..4 channels", who);
+  if (out_bytes < 0) return fail("%s: negative out_bytes", who);
+  if (n > 65535) return fail("%s: %d crops exceed 65535", who, n);
+  if (blocks_per_crop < 1 || blocks_per_crop > 65535) return fail("%s: blocks_per_crop outside 1..65535", who);
+  if ((int64_t)H * W * C > kMaxBytes) return fail("%s: more than 2^38 bytes per sample", who);
+  if (((uintptr_t)table | (uintptr_t)taps) & 7) return fail("%s: table and taps must be 8-byte aligned", who);
+  if ((uintptr_t)refused & 3) return fail("%s: refused must be 4-byte aligned", who);
+  const char *pi = (const char*)images, *po = (const char*)out, *pt = (const char*)table, *pr = (const char*)refused;
+  const int64_t in_bytes = (int64_t)B * H * W * C, table_bytes = (int64_t)n * 80;
+  const auto overlap = [](const char* a, int64_t na, const char* b, int64_t nb) { return a < b + nb && b < a + na; };
+  if (overlap(po, out_bytes, pi, in_bytes) || overlap(po, out_bytes, pt, table_bytes) || overlap(po, out_bytes, pr, 4) ||
+      overlap(pr, 4, pi, in_bytes) || overlap(pr, 4, pt, table_bytes))
+    return fail("%s: images, out, table and refused must not overlap", who);
+  if (n == 0) return 0;
+  const dim3 grid((unsigned)blocks_per_crop, (unsigned)n);
+  const uint8_t* src = (const uint8_t*)images;
+  uint8_t* dst = (uint8_t*)out;
+  switch (C) {
+    case 1: warp_gather_u8_kernel<1><<<grid, 256, 0, st>>>(src, dst, out_bytes, table, refused, B, H, W, taps); break;
+    case 2: warp_gather_u8_kernel<2><<<grid, 256, 0, st>>>(src, dst, out_bytes, table, refused, B, H, W, taps); break;
+    case 3: warp_gather_u8_kernel<3><<<grid, 256, 0, st>>>(src, dst, out_bytes, table, refused, B, H, W, taps); break;
+    default: warp_gather_u8_kernel<4><<<grid, 256, 0, st>>>(src, dst, out_bytes, table, refused, B, H, W, taps); break;
+  }
+  return check_launch(who);
 }
 
 int pack_mask(const void* mask, int mask_dtype, void* out, int B, int H, int W, int mask_b, int binarize, int64_t ld, int col0,

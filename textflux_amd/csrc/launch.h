@@ -205,6 +205,10 @@ int change_map_blend(void* x, int64_t ldx, const void* x0, const void* noise, co
 // true CFG in front of a sampler update: out <- neg + g (pos - neg), bf16 per op, g = *scale read on the device; v_neg, v_pos, out
 // bf16 [rows, C] contiguous, out may be v_neg itself
 int cfg_combine(const void* v_neg, const void* v_pos, void* out, int C, int64_t rows, const float* scale, hipStream_t st);
+// the clean-image estimate behind an Euler update: out <- x - sigma[step] v, bf16 per op; x bf16 [rows, C] with pitch ldx, v and out
+// contiguous; the step index from *step_ptr when given, else `step`
+int x0_predict(const void* x, int64_t ldx, const void* v, void* out, int C, int64_t rows, const float* sigma, const int* step_ptr, int step,
+               hipStream_t st);
 int timestep_embedding(const float* t, void* out, int n, hipStream_t st);
 int silu_bf16(const void* a, void* out, int64_t n, hipStream_t st);
 int add_bf16(const void* a, const void* b, void* out, int64_t n, hipStream_t st);
@@ -267,6 +271,11 @@ int warp_perspective_u8(const void* in, void* out, void* coverage, int B, int H,
 // and reads nothing
 int warp_grid_u8(const void* in, void* out, void* coverage, int B, int H, int W, int C, int out_h, int out_w, const int64_t* grid,
                  int shift, const int16_t* taps, hipStream_t st);
+// candidates: the crops of table i64 [n][10] = (b, m0..m5, out_h, out_w, byte offset) (device) from images [B, H, W, C] u8, each
+// warp_affine_u8's, packed as [out_h, out_w, C] at its byte offset in out; a row that cannot be served writes nothing and adds 1 to
+// *refused (device); blocks_per_crop workgroups stride over a crop's tiles
+int warp_affine_gather_u8(const void* images, void* out, int64_t out_bytes, const int64_t* table, int n, int* refused, int B, int H, int W,
+                          int C, int blocks_per_crop, const int16_t* taps, hipStream_t st);
 int pack_mask(const void* mask, int mask_dtype, void* out, int B, int H, int W, int mask_b, int binarize, int64_t ld, int col0,
               hipStream_t st);
 // uint8 pixel mask [B, H, W] -> packed latent mask bf16 [B, (H/16)(W/16), C] of 1.0 / 0.0; mode 0 nearest (grow 0), 1 cover (grow 0..8)

@@ -291,6 +291,48 @@ class TextRecognizer:
         return [dict(text=self.get_text(ids[i]), ids=[int(v) for v in ids[i]], ctc_loss=None if loss is None else loss[i])
                 for i in range(len(ids))]
 
+    def read_device(self, images_u8: torch.Tensor, lines: Sequence[Tuple[int, Any]],
+                    targets: Optional[Sequence[str]] = None) -> List[Dict[str, Any]]:
+        """read() on lines that are cut on the device (DESIGN.md section 4 "Candidates"): images_u8 is a device uint8 [B, H, W, 3]
+        tensor and `lines` a list of (b, polygon | mask), crop_line's shapes in image b's coordinates.  The minimum-area rectangles
+        are computed on the host as crop_line does; then one table upload and ONE ops.warp_affine_gather_u8 launch cut every crop
+        into one packed buffer, which ocr_resize_norm reads in batches of rec_batch_num in pred_imglist's aspect-ratio order.  No crop
+        visits the host.  The records are read()'s, bit for bit those of read([crop_line(images_u8[b], shape) ...], targets)."""
+        if not isinstance(images_u8, torch.Tensor) or images_u8.dtype != torch.uint8 or images_u8.dim() != 4 or images_u8.shape[3] != 3:
+            raise ValueError("read_device: images_u8 is a device uint8 [B, H, W, 3] tensor")
+        if targets is not None and len(targets) != len(lines):
+            raise ValueError(f"read_device: {len(targets)} targets for {len(lines)} lines")
+        if not lines:
+            raise ValueError("read_device: no lines")
+        o, dev = self.predictor.ops, self.predictor.device
+        _, imgH, imgW = self.rec_image_shape
+        imgW = int(imgH * (imgW / imgH))
+        rows, off = [], 0
+        for b, shape in lines:
+            if not 0 <= int(b) < images_u8.shape[0]:
+                raise ValueError(f"read_device: line of image {b}, the batch has {images_u8.shape[0]}")
+            m6, h, w = line_matrix(shape)
+            rows.append([int(b)] + [int(v) for v in m6] + [h, w, off])
+            off += h * w * 3
+        packed, refused = o.warp_affine_gather_u8(images_u8.contiguous(), np.array(rows, dtype=np.int64),
+                                                  out=torch.empty(off, dtype=torch.uint8, device=dev))
+        order = np.argsort(np.array([r[8] / float(r[7]) for r in rows]))
+        table = torch.tensor([(rows[i][9], rows[i][7], rows[i][8], 1 if rows[i][7] > rows[i][8] * 1.2 else 0) for i in order],
+                             dtype=torch.int32).to(dev)
+        ctc = [None] * len(rows)
+        for beg in range(0, len(rows), self.rec_batch_num):
+            idx = order[beg:beg + self.rec_batch_num]
+            preds = self.predictor(o.ocr_resize_norm(packed, table[beg:beg + len(idx)], imgH, imgW))
+            for r, i in enumerate(idx):
+                ctc[i] = preds["ctc"][r]
+        preds = torch.stack(ctc, dim=0)
+        ids, _, loss = self._score(preds, None if targets is None else [self.text_ids(t) for t in targets])
+        if int(refused.item()):
+            raise RuntimeError(f"read_device: the gather refused {int(refused.item())} of {len(rows)} crops")
+        loss = None if loss is None else (loss.cpu() / preds.shape[1]).tolist()
+        return [dict(text=self.get_text(ids[i]), ids=[int(v) for v in ids[i]], ctc_loss=None if loss is None else loss[i])
+                for i in range(len(ids))]
+
 
 # ---- line crops ------------------------------------------------------------------------------------------------------------------
 def line_corners(points: np.ndarray) -> np.ndarray:
@@ -309,6 +351,14 @@ def crop_line(image_u8: torch.Tensor, polygon_or_mask, ops=None) -> torch.Tensor
     ops.warp_affine_u8 (the reference's crop -- cv2 contours, a skimage similarity, grid_sample -- is not what is pinned)."""
     if ops is None:
         from . import ops
+    m6, h, w = line_matrix(polygon_or_mask)
+    if image_u8.dim() != 3 or image_u8.dtype != torch.uint8:
+        raise ValueError("crop_line: image_u8 is a uint8 [H, W, 3] tensor")
+    return ops.warp_affine_u8(image_u8.unsqueeze(0).contiguous(), m6, (h, w))[0]
+
+
+def line_matrix(polygon_or_mask) -> Tuple[np.ndarray, int, int]:
+    """(m int64 [6] Q16, h, w) of crop_line's warp: the minimum-area rectangle around the line, its own size, its upright frame."""
     a = np.asarray(polygon_or_mask)
     if a.ndim == 2 and a.shape[1] == 2 and a.shape[0] >= 3 and a.dtype != np.uint8:
         pts = a.astype(np.float64)
@@ -326,9 +376,7 @@ def crop_line(image_u8: torch.Tensor, polygon_or_mask, ops=None) -> torch.Tensor
     uy = (bl - tl) / max(np.linalg.norm(bl - tl), 1e-9) if np.linalg.norm(bl - tl) > 0 else np.array([0.0, 1.0])
     q = 1 << 16
     m6 = np.array([round(ux[0] * q), round(uy[0] * q), round(tl[0] * q), round(ux[1] * q), round(uy[1] * q), round(tl[1] * q)], dtype=np.int64)
-    if image_u8.dim() != 3 or image_u8.dtype != torch.uint8:
-        raise ValueError("crop_line: image_u8 is a uint8 [H, W, 3] tensor")
-    return ops.warp_affine_u8(image_u8.unsqueeze(0).contiguous(), m6, (h, w))[0]
+    return m6, h, w
 
 
 # ---- metrics (eval/eval_dgocr.py), host-side ---------------------------------------------------------------------------------------

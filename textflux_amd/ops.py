@@ -503,6 +503,37 @@ def cfg_combine(v_neg: torch.Tensor, v_pos: torch.Tensor, scale: torch.Tensor, o
     return out
 
 
+def x0_predict(x: torch.Tensor, v: torch.Tensor, sigma: torch.Tensor, step: int = 0, step_ptr: Optional[torch.Tensor] = None,
+               out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """out <- x - sigma[step] * v, one bf16 rounding per op as torch's `latents - sigma * noise_pred` on bf16 tensors with a Python
+    float (tfx_x0_predict; DESIGN.md section 4 "Candidates").  x bf16 [.., rows, C] with unit inner stride and one row pitch (a
+    contiguous tensor, or a column slice such as xin[:, :, :C] of one); v bf16, contiguous, of x's shape; sigma: a DEVICE fp32
+    vector; the step index is step_ptr's word (a device int32 tensor of one element) when given, else `step`."""
+    _chk_dev(x, v, sigma, step_ptr, out)
+    if out is None:
+        out = torch.empty(x.shape, dtype=BF16, device=x.device)
+    if any(t.dtype != BF16 for t in (x, v, out)):
+        raise TypeError("x0_predict: bf16 latents and model output")
+    if sigma.dtype != torch.float32 or sigma.dim() != 1 or not sigma.is_contiguous():
+        raise TypeError("x0_predict: sigma is a contiguous device fp32 vector")
+    if step_ptr is not None and (step_ptr.dtype != torch.int32 or step_ptr.numel() != 1):
+        raise TypeError("x0_predict: step_ptr is a device int32 tensor of one element")
+    if x.dim() < 2 or not (x.shape == v.shape == out.shape):
+        raise ValueError("x0_predict: x, v and out must be of one shape [.., rows, C]")
+    if not (v.is_contiguous() and out.is_contiguous()):
+        raise ValueError("x0_predict: v and out must be contiguous")
+    Cc = x.shape[-1]
+    rows = x.numel() // Cc if Cc else 0
+    ldx = x.stride(-2)
+    if x.stride(-1) != 1 or any(x.stride(d) != x.stride(d + 1) * x.shape[d + 1] for d in range(x.dim() - 2)):
+        raise ValueError("x0_predict: x must have unit inner stride and one row pitch over all its rows")
+    if step_ptr is None and not 0 <= int(step) < sigma.numel():
+        raise ValueError(f"x0_predict: step {step} outside the table of {sigma.numel()} sigmas")
+    L.check(L.lib().tfx_x0_predict(x.data_ptr(), ldx, v.data_ptr(), out.data_ptr(), Cc, rows, sigma.data_ptr(), _p(step_ptr), int(step),
+                                   _stream()), "x0_predict")
+    return out
+
+
 def timestep_embedding(t: torch.Tensor) -> torch.Tensor:
     _chk_dev(t)
     t = t.contiguous().float()
@@ -1141,6 +1172,59 @@ def warp_affine_u8(x: torch.Tensor, m, out_size, coverage: bool = False):
     integer arithmetic (tfx_warp_affine_u8; include/textflux_hip.h has the arithmetic, rectify.matrices builds m).  out_size =
     (out_h, out_w).  coverage: also return uint8 [B, out_h, out_w], 255 where the sample position lies inside the image."""
     return _warp_matrix_u8("warp_affine_u8", 6, x, m, out_size, coverage)
+
+
+GATHER_COLS = 10                    # warp_affine_gather_u8's table row: (b, m0..m5, out_h, out_w, byte offset)
+
+
+def warp_affine_gather_u8(images: torch.Tensor, table, out: Optional[torch.Tensor] = None, refused: Optional[torch.Tensor] = None,
+                          blocks_per_crop: int = 64):
+    """Every crop of `table` in one launch (tfx_warp_affine_gather_u8; DESIGN.md section 4 "Candidates") -> (out, refused).  images uint8
+    [B, H, W, C] (C in 1..4), contiguous.  table int64 [n, 10], a host array or a device tensor, one row per crop: (b, m0..m5 Q16, out_h,
+    out_w, byte offset); crop k is warp_affine_u8(images[b], m, (out_h, out_w)) bit for bit, written as [out_h, out_w, C] at its byte
+    offset of the packed uint8 vector `out` -- the layout ocr_resize_norm reads; offsets are byte-granular.  out: None = a new vector as
+    long as the host table's furthest crop end (a device table needs `out`).  refused: a device int32 tensor of one element the kernel adds
+    1 to for every row it cannot serve (b outside [0, B), a non-positive side, a byte range outside out) and then leaves unwritten; None =
+    a fresh zero.  blocks_per_crop: the workgroups that share a crop's tiles; the bytes do not depend on it."""
+    _chk_dev(images, out, refused)
+    if images.dtype != torch.uint8 or images.dim() != 4 or not images.is_contiguous() or images.numel() == 0 or not 1 <= images.shape[3] <= 4:
+        raise ValueError(f"warp_affine_gather_u8: images must be a contiguous, non-empty uint8 [B, H, W, C <= 4] tensor, got {images.dtype} "
+                         f"{tuple(images.shape)}")
+    B, H, W, Cc = images.shape
+    host = None
+    if not isinstance(table, torch.Tensor):
+        import numpy as np
+        host = np.ascontiguousarray(table)
+        table = torch.from_numpy(host)
+    if table.dtype != torch.int64 or table.dim() != 2 or table.shape[1] != GATHER_COLS:
+        raise ValueError(f"warp_affine_gather_u8: table must be int64 [n, {GATHER_COLS}], got {table.dtype} {tuple(table.shape)}")
+    n = table.shape[0]
+    if out is None:
+        if host is None:
+            raise ValueError("warp_affine_gather_u8: a device table needs `out`")
+        ends = [int(r[9]) + int(r[7]) * int(r[8]) * Cc for r in host.tolist() if r[7] > 0 and r[8] > 0 and r[9] >= 0]
+        out = torch.empty(max(ends, default=0), dtype=torch.uint8, device=images.device)
+    elif out.dtype != torch.uint8 or out.dim() != 1 or not out.is_contiguous():
+        raise ValueError("warp_affine_gather_u8: out must be a contiguous uint8 vector")
+    if refused is None:
+        refused = torch.zeros(1, dtype=torch.int32, device=images.device)
+    elif refused.dtype != torch.int32 or refused.numel() != 1:
+        raise ValueError("warp_affine_gather_u8: refused must be a device int32 tensor of one element")
+    if int(blocks_per_crop) != blocks_per_crop or not 1 <= int(blocks_per_crop) <= 65535:
+        raise ValueError(f"warp_affine_gather_u8: blocks_per_crop must be an integer in 1..65535, got {blocks_per_crop!r}")
+    table = table.to(images.device).contiguous()
+    _chk_dev(table)
+    key = str(images.device)
+    if key not in _WARP_TAPS:
+        from .rectify import catmull_rom_taps
+        _WARP_TAPS[key] = torch.from_numpy(catmull_rom_taps()).to(images.device)
+    if n and out.numel():
+        L.check(L.lib().tfx_warp_affine_gather_u8(images.data_ptr(), out.data_ptr(), out.numel(), table.data_ptr(), n, refused.data_ptr(), B,
+                                                  H, W, Cc, int(blocks_per_crop), _WARP_TAPS[key].data_ptr(), _stream()),
+                "warp_affine_gather_u8")
+    elif n:                              # an empty out has no address to hand over: every row is refused, as the kernel would
+        refused += n
+    return out, refused
 
 
 def _perspective_magnitudes(m, out_h: int, out_w: int) -> None:

@@ -203,6 +203,9 @@ class FluxFillPipeline:
         self.fuse_euler_step = True     # Euler update in proj_out's GEMM epilogue (tfx_dit_desc.euler_gate); False = separate scheduler kernel
         self._step_cache = None         # StepCacheConfig while enable_step_cache() is in force
         self.step_cache_report = None   # per step of the last call with the cache: {"metric": [B floats], "skipped": bool}
+        # what a call with step_window=(a, b), b < n, leaves (DESIGN.md section 4 "Candidates"): the packed bf16 [B, S, C] clean-image
+        # estimate at sigma_b, and the packed conditioning [B, S, 320] the continuing window takes as masked_image_latents
+        self.x0_preview = self.window_conditioning = None
 
     # ------------------------------------------------------------------ loading / placement
     @classmethod
@@ -603,7 +606,8 @@ class FluxFillPipeline:
         return modx
 
     def _engine_loop(self, latents, masked_image_latents, prompt_embeds, pooled, text_ids, latent_image_ids, timesteps,
-                     guidance_scale, callback_on_step_end, callback_tensor_inputs, amo_noise, progress_bar, keep=None, cfg=None):
+                     guidance_scale, callback_on_step_end, callback_tensor_inputs, amo_noise, progress_bar, keep=None, cfg=None,
+                     preview=None):
         """Session, conditioning, modulation table, x_embedder input, then the step loop (step_loop.denoise).  The loop starts at
         step 0 of `timesteps`: _call_body sets the timesteps directly in front of it, which clears the scheduler's begin_index --
         unless the call gave `strength` / `keep_known`: then get_timesteps set it, `timesteps` and the scheduler's tables start at that
@@ -612,7 +616,9 @@ class FluxFillPipeline:
         cfg: true CFG -- dict(scale, prompt_embeds, pooled), the negative conditioning of the B samples: the
         session then has 2B samples, its conditioning and the pooled rows of the modulation table are [negative; positive] (the
         reference's torch.cat, pipeline_flux_with_cfg.py:739-740), both halves of its xin hold the same [latents |
-        masked_image_latents] rows, and Euler runs unfused; the loop state (latents, keep, amo_noise) keeps B samples."""
+        masked_image_latents] rows, and Euler runs unfused; the loop state (latents, keep, amo_noise) keeps B samples.
+        preview: a step_window that ends early (DESIGN.md section 4 "Candidates") -- dict(sigma, step) for step_loop.denoise; Euler
+        then runs unfused too, so that the last step's model output exists in the session's `out`."""
         tr, sch = self.transformer, self.scheduler
         dev = tr.device
         B, S, C = latents.shape
@@ -629,7 +635,8 @@ class FluxFillPipeline:
         # Euler update in proj_out's epilogue (north_star: "flow-matching Euler step fused into the residual add"); the latents then
         # live in xin[:, :, :C].  Not with a step callback (it wants the latents as a tensor every step) and not for AMO.
         fuse = (self.fuse_euler_step and not is_amo and not multistep and callback_on_step_end is None and C == EULER_PAD
-                and tr.out_channels == C and cfg is None)        # the fused epilogue would update each half of a CFG batch on its own
+                and tr.out_channels == C and cfg is None         # the fused epilogue would update each half of a CFG batch on its own
+                and preview is None)                             # ... and leaves no model output behind for the estimate
         mod = self._modulation_table(timesteps, Bs, pooled if cfg is None else both(cfg["pooled"], pooled), guidance_scale,
                                      coef[:n] if fuse else None)
         # x_embedder input [latents | masked_image_latents]; the step keeps columns 0..C-1 up to date
@@ -664,7 +671,7 @@ class FluxFillPipeline:
         else:
             keep = None
         return step_loop.denoise(self, ses, mod, latents, coef, n, progress_bar, is_amo, fuse, amo_noise, on_step, multistep,
-                                 cfg=None if cfg is None else cfg["scale"], keep=keep, change=change)
+                                 cfg=None if cfg is None else cfg["scale"], keep=keep, change=change, preview=preview)
 
     # ------------------------------------------------------------------ known-region sampling
     def get_timesteps(self, num_inference_steps, strength, device):
@@ -912,7 +919,7 @@ class FluxFillPipeline:
     def _decode_to_output(self, latents, height, width, output_type, crop=None):
         """P:2126-2129 + VaeImageProcessor.postprocess: un-patchify, z / scale + shift, VAE decode, denormalise, and the
         output layout, all on NHWC device tensors; only the finished uint8 / float32 image crosses to the host."""
-        if output_type not in ("pt", "np", "pil"):
+        if output_type not in ("pt", "np", "pil", "u8"):
             raise ValueError(f"unknown output_type {output_type}")
         c = self.vae.config
         h = 2 * (int(height) // (self.vae_scale_factor * 2))
@@ -924,11 +931,19 @@ class FluxFillPipeline:
             return ops.postprocess(img, c.out_channels, "pt", denorm, crop)
         if output_type == "np":
             return ops.postprocess(img, c.out_channels, "np", denorm, crop).cpu().numpy()
+        if output_type == "u8":        # the "pil" output's bytes as a device uint8 [B, H, W, C] tensor: nothing crosses to the host
+            return ops.postprocess(img, c.out_channels, "u8", denorm, crop)
         import PIL.Image
         u8 = ops.postprocess(img, c.out_channels, "u8", denorm, crop).cpu().numpy()
         if u8.shape[-1] == 1:
             return [PIL.Image.fromarray(a.squeeze(), mode="L") for a in u8]
         return [PIL.Image.fromarray(a) for a in u8]
+
+    @torch.no_grad()
+    def decode_latents(self, latents, height, width, output_type: str = "u8", output_crop=None):
+        """Packed latents [B, S, C] (a call's output_type="latent" result, or `x0_preview`) -> what the call itself would have
+        returned for them under output_type / output_crop: the same decode, nothing else."""
+        return self._decode_to_output(latents, height, width, output_type, output_crop)
 
     @torch.no_grad()
     def __call__(self, prompt: Union[str, List[str]] = None, prompt_2: Optional[Union[str, List[str]]] = None,
@@ -945,8 +960,19 @@ class FluxFillPipeline:
                  image_latents: Optional[torch.Tensor] = None, change_map=None,
                  negative_prompt: Optional[Union[str, List[str]]] = None, negative_prompt_2: Optional[Union[str, List[str]]] = None,
                  negative_prompt_embeds: Optional[torch.Tensor] = None, negative_pooled_prompt_embeds: Optional[torch.Tensor] = None,
-                 true_cfg: float = 1.0):
+                 true_cfg: float = 1.0, step_window: Optional[Tuple[int, int]] = None):
         """Same arguments / defaults / return as the reference `__call__` (P:1850-1873, 2122-2137).  Additions:
+        `output_type="u8"`: the "pil" output's bytes as a device uint8 [B, H, W, 3] tensor (with `output_crop`: of that window), no
+        host copy.
+        `step_window` = (a, b), 0 <= a < b <= n (DESIGN.md section 4 "Candidates"; Euler sampler only): run steps a <= i < b of this
+        call's n-step schedule, with the tables of the full schedule sliced by absolute step index.  a > 0 needs `latents`, the
+        packed state after step a - 1, used as it is (no noise is drawn); a caller who wants the bits of the unwindowed call also
+        passes the first window's `pipe.window_conditioning` as `masked_image_latents`, because the conditioning's VAE sample is
+        drawn behind the noise from the same generator.  b < n needs output_type="latent", returns the latents at sigma_b, runs the
+        unfused Euler step (bit-equal to the fused one) and leaves `pipe.x0_preview`, the packed bf16 [B, S, C] estimate
+        x_b - sigma_b v_{b-1} (tfx_x0_predict), and `pipe.window_conditioning`.  NotImplementedError, before anything is launched,
+        with the AMO and multistep samplers, a foreign scheduler, `strength`, `keep_known`, `change_map`, true CFG, the step cache
+        and a step callback.  None (default) is the call without the key.
         `amo_noise`, a list of pre-drawn eps tensors for the AMO sampler (replay across devices), and
         `output_crop` = (left, top, right, bottom), the callers' result crop (run_inference.py:460-465) applied on the
         device so that only the kept pixels are converted and copied to the host.
@@ -975,6 +1001,17 @@ class FluxFillPipeline:
             raise ValueError(f"The value of strength should in [0.0, 1.0] but is {strength}")
         if _change_map_cfg(change_map) is not None and _keep_known_cfg(keep_known) is not None:
             raise ValueError("change_map and keep_known exclude each other: one blend stands behind the sampler update")
+        if step_window is not None:    # refused before anything is encoded or launched
+            n_steps = num_inference_steps if sigmas is None else len(sigmas)
+            a, b = step_window = step_loop.check_step_window(step_window, n_steps)
+            step_loop.refuse_step_window(self.scheduler, strength, keep_known, change_map,
+                                         _true_cfg_on(true_cfg, negative_prompt, negative_prompt_embeds), self._step_cache is not None,
+                                         callback_on_step_end is not None)
+            if a > 0 and latents is None:
+                raise ValueError(f"step_window=({a}, {b}) starts behind step 0 and needs `latents`, the packed state after step {a - 1}")
+            if b < n_steps and output_type != "latent":
+                raise ValueError(f"step_window=({a}, {b}) ends before step {n_steps} and needs output_type='latent' "
+                                 "(pipe.x0_preview holds the clean-image estimate)")
         height = height or self.default_sample_size * self.vae_scale_factor
         width = width or self.default_sample_size * self.vae_scale_factor
         self.check_inputs(prompt, prompt_2, height, width, prompt_embeds=prompt_embeds,
@@ -1006,7 +1043,7 @@ class FluxFillPipeline:
                                    sigmas, guidance_scale, num_images_per_prompt, generator, latents, prompt_embeds,
                                    pooled_prompt_embeds, output_type, return_dict, callback_on_step_end,
                                    callback_on_step_end_tensor_inputs, max_sequence_length, amo_noise, output_crop, strength,
-                                   keep_known, image_latents, change_map, negative)
+                                   keep_known, image_latents, change_map, negative, step_window)
         finally:
             if lora_scale is not None:
                 self.transformer._write_scales(prev_lora_scale)
@@ -1146,7 +1183,7 @@ class FluxFillPipeline:
     def _call_body(self, prompt, prompt_2, image, mask_image, masked_image_latents, height, width, num_inference_steps, sigmas,
                    guidance_scale, num_images_per_prompt, generator, latents, prompt_embeds, pooled_prompt_embeds, output_type,
                    return_dict, callback_on_step_end, callback_on_step_end_tensor_inputs, max_sequence_length, amo_noise, output_crop,
-                   strength=1.0, keep_known=None, image_latents=None, change_map=None, negative=None):
+                   strength=1.0, keep_known=None, image_latents=None, change_map=None, negative=None, step_window=None):
         if prompt is not None and isinstance(prompt, str):
             batch_size = 1
         elif prompt is not None and isinstance(prompt, list):
@@ -1213,13 +1250,22 @@ class FluxFillPipeline:
                                  f"steps is {num_inference_steps} which is < 1 and not appropriate for this pipeline.")
             latents, keep = self._prepare_known_region(latents, given_latents, image_latents, src_image, mask_image, keep_cfg, strength,
                                                        height, width, prompt_embeds.dtype, device, generator, change_cfg=change_cfg)
+        preview = None
+        if step_window is not None:    # the schedule's own tables from step a on (set_begin_index), its timesteps a..b-1
+            a, b = step_window
+            if b < num_inference_steps:
+                preview = dict(sigma=self.scheduler.sigmas.to(self.transformer.device, torch.float32).contiguous(), step=b)
+                self.x0_preview, self.window_conditioning = None, masked_image_latents
+            timesteps = timesteps[a:b]
+            self.scheduler.set_begin_index(a)
+            num_inference_steps = b - a
         self._num_timesteps = len(timesteps)
         with self.progress_bar(total=num_inference_steps) as bar:
             if engine:
                 try:
                     latents = self._engine_loop(latents, masked_image_latents, prompt_embeds, pooled_prompt_embeds, text_ids,
                                                 latent_image_ids, timesteps, guidance_scale, callback_on_step_end,
-                                                callback_on_step_end_tensor_inputs, amo_noise, bar, keep, cfg)
+                                                callback_on_step_end_tensor_inputs, amo_noise, bar, keep, cfg, preview)
                 except RuntimeError as e:
                     if cfg is None or isinstance(e, NotImplementedError):
                         raise

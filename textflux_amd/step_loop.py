@@ -30,6 +30,49 @@ class CaptureRefused(RuntimeError):
     """tfx_dit_step_capture returned an error (driver / runtime state); the message is the library's."""
 
 
+def check_step_window(window, n=None):
+    """(a, b) of a step_window as integers; ValueError unless 0 <= a < b (<= n when the schedule's length n is known)."""
+    try:
+        a, b = window
+        ok = int(a) == a and int(b) == b and 0 <= a < b and (n is None or b <= n)
+    except (TypeError, ValueError):
+        ok = False
+    if not ok:
+        raise ValueError(f"step_window must be (a, b) with 0 <= a < b <= {'n' if n is None else n}, got {window!r}")
+    return int(a), int(b)
+
+
+def refuse_step_window(scheduler, strength=1.0, keep_known=None, change_map=None, true_cfg=False, step_cache=False, callback=False,
+                       mixed=False):
+    """NotImplementedError with the reason when a call with step_window (DESIGN.md section 4 "Candidates") cannot be served: a window
+    carries the latents and nothing else from one call to the next, and every sampler state, blend buffer or decision beyond them would
+    have to travel with it.  Touches no device: the pipeline and the batch driver both ask in front of everything else."""
+    from .schedulers import FlowMatchEulerDiscreteScheduler, FlowMatchMultistepScheduler, StochasticRFOvershotDiscreteScheduler
+    why = None
+    if isinstance(scheduler, StochasticRFOvershotDiscreteScheduler):
+        why = "the AMO sampler (its noise draws belong to the whole schedule)"
+    elif isinstance(scheduler, FlowMatchMultistepScheduler):
+        why = "the multistep sampler (its history, the previous model output, would have to travel with the latents)"
+    elif not isinstance(scheduler, FlowMatchEulerDiscreteScheduler):
+        why = f"a scheduler other than FlowMatchEulerDiscreteScheduler ({type(scheduler).__name__})"
+    elif strength != 1.0:
+        why = "strength (the window already names the steps that run)"
+    elif keep_known:
+        why = "keep_known (the blend's noise and original latents would have to travel with the latents)"
+    elif change_map is not None and change_map is not False:
+        why = "change_map (the blend's noise, original latents and hold bytes would have to travel with the latents)"
+    elif true_cfg:
+        why = "true CFG (negative_prompt / true_cfg > 1)"
+    elif step_cache:
+        why = "the step cache (its cached residual and decisions belong to one uninterrupted loop)"
+    elif callback:
+        why = "a step callback"
+    elif mixed:
+        why = "mixed-geometry batches (call_mixed / mixed_pad > 0)"
+    if why is not None:
+        raise NotImplementedError(f"step_window does not run with {why}")
+
+
 def _graph_handles(steps, graphs, keys):
     """{phase: handle} for the phases of `keys`, captured now if the session holds none yet; False = eager (a refusal, now or cached).
     Capture does not execute, the state is kept explicit around it anyway."""
@@ -154,7 +197,7 @@ class SessionSteps:
 
 
 def denoise(pipe, ses, mod, latents, coef, n, progress_bar, is_amo=False, fuse=False, amo_noise=None, on_step=None, multistep=False,
-            cfg=None, keep=None, change=None):
+            preview=None, cfg=None, keep=None, change=None):
     """The n steps of one engine call on session `ses`, whose xin holds [latents | masked_image_latents] and whose conditioning is
     set.  mod [n, B, mod_len (+ EULER_PAD when fuse)]: the modulation table.  latents [B, S, C] and coef, the sampler's coefficient
     table, may be None when fuse: the fused step reads the latents from xin and its coefficients from `mod`.  on_step(i, lat): the
@@ -170,8 +213,10 @@ def denoise(pipe, ses, mod, latents, coef, n, progress_bar, is_amo=False, fuse=F
     of 2B samples whose conditioning and modulation rows are [negative; positive] and whose xin holds the same rows in both halves, while
     latents, amo_noise, keep and change have B samples (they live in the first half of the session's buffers: the addresses are the
     same ones, whatever the call).  The scale lives in the session too and is rewritten every call: a captured graph serves every g.
-    Unfused samplers only, not with the step cache, not on mixed sessions.  Runs on the session's side
-    stream (capture needs a non-NULL stream), fenced against the caller's current stream on both sides.  The step cache is on when
+    Unfused samplers only, not with the step cache, not on mixed sessions.  preview: dict(sigma: fp32 [..] on the device, step) of a
+    window that ends early (DESIGN.md section 4 "Candidates") -- behind the last step, pipe.x0_preview becomes tfx_x0_predict of the
+    final latents, that step's model output (ses.out: unfused samplers only) and sigma[step]; the launch is outside the step graph.
+    Runs on the session's side stream (capture needs a non-NULL stream), fenced against the caller's current stream on both sides.  The step cache is on when
     pipe.enable_step_cache() is in force; graphs when pipe.enable_hip_graph(True), no callback and n > 1.  Returns the final
     latents and leaves pipe.step_cache_report set."""
     dev = ses.xin.device
@@ -238,6 +283,11 @@ def denoise(pipe, ses, mod, latents, coef, n, progress_bar, is_amo=False, fuse=F
         run_steps(steps, n, pipe, progress_bar, ses.graphs, key, decider, use_graph=pipe._use_hip_graph,
                   callback=None if on_step is None else lambda i: on_step(i, state(gb["lat"])))
         out = ops.copy_rows_(ses.xin[:, :, :shape[2]], torch.empty(shape, dtype=BF16, device=dev)) if fuse else state(gb["lat"]).clone()
+        if preview is not None:
+            if fuse or cfg is not None or pipe._interrupt:
+                raise ValueError("the clean-image estimate needs the model output of the last step: an unfused, uninterrupted loop without true CFG")
+            pipe.x0_preview = ops.x0_predict(out, ses.out, preview["sigma"], step=int(preview["step"]))
+            pipe.x0_preview.record_stream(cur)
     out.record_stream(cur)
     cur.wait_stream(side)
     pipe.step_cache_report = decider.report if decider is not None else None
